@@ -1,9 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the rendering hot path on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, exactly K timed steps, the
+outputs of the last timed step if --dump-outputs is given, one JSON line (`value`, `ms_per_step`, ...).  Everything else
+the script measures or checks is behind --full: the `roofline` object (three more in-order steps with HIP events around
+every launch, plus the committed counter passes), the record's self-check (counters of the timed region against those
+steps, the last timed frame against the job rendered alone), both exchanges of the single-process multi-device form,
+the host-buffer figure of `--workload ref` and `cpu_baseline`.  A plain run still checks the device-counted samples of
+its timed region (free: the counters are read once, after the last step) and exits non-zero when they do not add up.
+
+--dump-outputs DIR writes the frame of the last timed step as a caller of pt_render_device receives it: DIR/linear.npy
+(rows, width, 3) and DIR/rgba8.npy (rows, width, 4), both float32 (the RGBA8 values exactly).  A frame above 64 MB in
+all is replaced by the same fixed, seeded sample of 2^20 pixels in both planes (DIR/pixel_index.npy: their row-major
+indices).  Scene, camera and seeds are fixed, so the same arguments give the same inputs in every run.
 
 Both launch forms work for every N (launch_mode() below): under torch.distributed.run it is one process per GPU
 (pathtrace_amd/dist.py: pack kernel, ONE dist.gather over RCCL, unpack kernel); started as a plain process with
@@ -69,6 +82,9 @@ F_SPHERE, F_TRIANGLE, F_SHADE = 23, 51, 200     # flops per primiti
 F_TRIANGLE_PLANE, F_TRIANGLE_PAIR = 31, 42
 PROFILE_DIR = os.path.join(ROOT, "profiles", "r05")
 REGEN_MIN_PATHS = 1 << 17     # pt_api.cpp kRegenMinPaths: batches above this over a scene in LDS take a regenerating form
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: at most this much in all ...
+DUMP_SAMPLE_PIXELS = 1 << 20  # ... else this many pixels of every plane, drawn with DUMP_SEED
+DUMP_SEED = 20250101
 
 
 def launch_mode(gpus, env, force_dist=False, force_multi=False):
@@ -174,6 +190,21 @@ def counter_problems(tag, timed, want_samples, steps, ref=None, ref_steps=0):
     return problems
 
 
+def dump_outputs(directory, lin, rgba):
+    """--dump-outputs: the two film planes of one frame -> DIR/linear.npy, DIR/rgba8.npy (float32), sampled above DUMP_MAX_BYTES."""
+    import numpy as np
+    lin = lin.cpu().numpy().astype(np.float32)
+    rgba = rgba.cpu().numpy().astype(np.float32)
+    arrays = {"linear": lin, "rgba8": rgba}
+    if lin.nbytes + rgba.nbytes > DUMP_MAX_BYTES:
+        n_pix = lin.shape[0] * lin.shape[1]
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pix, size=DUMP_SAMPLE_PIXELS, replace=False))
+        arrays = {"linear": lin.reshape(n_pix, -1)[idx], "rgba8": rgba.reshape(n_pix, -1)[idx], "pixel_index": idx.astype(np.float64)}
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def profile_summary(world, workload, accel, level0_form=0):
     """Counter-derived figures of the dominant kernel from the committed rocprofv3 passes of THIS command
     (profiles/r05/roofline_<workload>[_bvh | _queue].json, written by tools/profile_workload.sh on the GPU box).  PMC counters
@@ -233,7 +264,16 @@ def main(argv=None):
                          "device copies where the real object calls ncclGather (pt_debug_multi_create_shared); everything else -- host "
                          "threads, frames posted back to back, the packed resolve, the row permutation, this script's N > 1 branches -- "
                          "is the real path.  The line it prints is marked as a rehearsal and is not a measurement of N GPUs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/linear.npy and DIR/rgba8.npy (float32; a seeded sample "
+                         "of 2^20 pixels above 64 MB, with DIR/pixel_index.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline (extra in-order steps, committed "
+                         "counter passes), the record's self-check, both multi-device exchanges, host buffers (--workload ref), "
+                         "cpu_baseline")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     mode, world, rank, local_rank = launch_mode(args.gpus, os.environ, args.force_dist, args.force_multi)
 
@@ -378,19 +418,23 @@ def main(argv=None):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         counters = dict(acc)
-        # the frame the LAST timed step produced, kept for the bitwise check below (later steps reuse the buffers)
-        if dist_path:
+        # the frame the LAST timed step produced, kept for --dump-outputs and the bitwise check below (later steps reuse the buffers)
+        if not (args.full or args.dump_outputs):
+            last = None
+        elif dist_path:
             last = (fr.clone(), fr8.clone()) if rank == 0 else None
         else:
             last = (lin.clone(), rgba.clone())
         return dt, counters, last
 
     elapsed, timed, last_frame = timed_region(args.warmup)
-    # Single-process multi-device form: BOTH exchanges in the one run -- `value` with ONE ncclGather per frame (north_star's form),
-    # `config.exchange_copy` with one DMA copy per device in its place (pt_multi_set_exchange; no kernel takes part) -- so that the
-    # first run on a multi-GPU node settles the default by measurement.  Each with its own bitwise frame check.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_frame)
+    # Single-process multi-device form (--full): BOTH exchanges in the one run -- `value` with ONE ncclGather per frame (north_star's
+    # form), `config.exchange_copy` with one DMA copy per device in its place (pt_multi_set_exchange; no kernel takes part) -- so that
+    # the first run on a multi-GPU node settles the default by measurement.  Each with its own bitwise frame check.
     copy_run = None
-    if mode == "multi" and not args.shared_device and args.exchange == "rccl":
+    if args.full and mode == "multi" and not args.shared_device and args.exchange == "rccl":
         ctx.set_exchange("copy")
         c_elapsed, c_timed, c_last = timed_region(max(1, args.warmup))
         copy_run = {"elapsed": c_elapsed, "timed": c_timed, "last": c_last}
@@ -402,7 +446,7 @@ def main(argv=None):
     else:
         job_samples = float(timed["samples"])   # pt_multi_get_stats sums over the devices
 
-    post_pass = not args.in_order
+    post_pass = args.full and not args.in_order
     if post_pass:
         # launch times for the roofline: three more steps, in order, with HIP events around every launch, outside the timed region
         prm.profile = 1
@@ -418,7 +462,7 @@ def main(argv=None):
     multi_info = ctx.info() if mode == "multi" else None
 
     host_buffers = None
-    if args.workload == "ref" and rank == 0 and world == 1:
+    if args.full and args.workload == "ref" and rank == 0 and world == 1:
         # the same job through the one-shot entry with HOST buffers (scene upload, render, film over PCIe): what replaces
         # main.rs:43-66 as it stands
         pt.render_host(cam, objs, pt.default_params(spp=spp))                   # creates the cached context and its buffers
@@ -439,6 +483,8 @@ def main(argv=None):
     #     deterministic) -- and
     # (c) the LAST timed frame must equal, bit for bit, the job rendered once, alone and in order, on one GPU by a context of its
     #     own: in every mode and for every N.  Any difference -> the JSON line says so and the exit code is non-zero.
+    # A plain run (no --full) has no per-step figures and renders no reference frame: it checks the samples of (b) and that the
+    # vertices and shadow rays are a multiple of the step count, from the counters it read anyway.
     problems = []
 
     want = rows * WIDTH * spp * args.steps          # this process's share of the job (multi: all devices, summed by the library)
@@ -447,7 +493,7 @@ def main(argv=None):
     if copy_run:
         problems += counter_problems("timed region (exchange by copies)", copy_run["timed"], want, args.steps, per_step, prof_steps)
     frame_ok = None
-    if rank == 0:
+    if args.full and rank == 0:
         ref_ctx = pt.Context(dev_index)
         ref_ctx.upload(objs)
         ref_ctx.set_tuning(in_order=1)
@@ -474,7 +520,9 @@ def main(argv=None):
         if problems and rank != 0:
             print(f"[bench rank {rank}] " + "; ".join(problems), file=sys.stderr, flush=True)
 
-    if rank == 0:
+    accel_name = {0: "linear scan (reference)", 1: "BVH traversal (accel=1, same film as the linear scan)",
+                  2: "PT_ACCEL_AUTO (product default: BVH above ~512 sphere tests per scan, same film)"}[args.accel]
+    if args.full and rank == 0:
         # the dominant kernel = the level-0 launch of each batch (camera rays + every bounce until its waves hand
         # their sparse tails over); it processes p_vertices of the vertices and all of the camera samples.
         # Single-process multi-device runs: counters are sums over the devices, launch times the slowest device's
@@ -499,8 +547,6 @@ def main(argv=None):
         alg_bytes = (BYTES_PER_VERTEX * acc["p_vertices"] + BYTES_PER_SAMPLE * acc["samples"]) / n_stat
         avg_ms = acc["p_ms"] / max(p_launches, 1)
         prof = profile_summary(world if mode != "multi" else 0, args.workload, args.accel, args.level0_form)
-        accel_name = {0: "linear scan (reference)", 1: "BVH traversal (accel=1, same film as the linear scan)",
-                      2: "PT_ACCEL_AUTO (product default: BVH above ~512 sphere tests per scan, same film)"}[args.accel]
         diffuse = all(o.mat_tag in (0, 1) for o in objs)
         if args.accel == 1 or (args.accel == 2 and len(objs) > 512):
             kernel = "k_paths_bvh<MIS, OVF=false%s>" % (", DIFFUSE" if diffuse else "")
@@ -579,9 +625,11 @@ def main(argv=None):
             roof["bytes_model"] = "128 B per vertex whose path goes on (64 B state written, 64 B read by the next pass) + 12 B per sample"
             roof["kernel"] = roof["kernel"].replace("Bound by f32 VALU issue (no contraction on this path: the schema's mfma slot does not apply; "
                                                     "same 157.3 TFLOP/s f32 peak)", "Bound by HBM (the path queue's round trip per vertex)")
+    if rank == 0:
         if world == 1:
             tiles = "whole image" + (" (through the single-process multi-device path: ncclCommInitAll over 1 device, ONE ncclGather, row "
-                                     "permutation; frame checked bitwise against the plain render)" if mode == "multi" else "")
+                                     "permutation" + ("; frame checked bitwise against the plain render" if args.full else "") + ")"
+                                     if mode == "multi" else "")
         elif mode == "multi":
             tiles = (f"interleaved bands of {band_rows} rows over {world} devices driven by ONE process (pt_multi_*): ONE ncclGather "
                      f"(RCCL, the calls of the {world} devices inside one ncclGroup) of the packed f32 + RGBA8 tiles to device 0 per step, "
@@ -608,21 +656,23 @@ def main(argv=None):
                 "workload": f"{wl_desc}, {WIDTH}x{HEIGHT}, {spp} spp, MIS, min_depth 4 / max_depth 50",
                 "hit_scene": accel_name,
                 "samples_per_step": int(job_samples / args.steps),
-                "vertices_per_sample": round(acc["vertices"] / max(acc["samples"], 1), 3),
-                # the same figure from the device counters of the TIMED (overlapped) region, rank 0 / all devices of the process;
-                # `samples` there are counted on the device where a path's radiance is written (PtStats.samples)
+                # device counters of the TIMED (overlapped) region, rank 0 / all devices of the process; `samples` there are
+                # counted on the device where a path's radiance is written (PtStats.samples)
                 "timed_region_vertices_per_sample": round(timed["vertices"] / max(timed["samples"], 1), 3),
                 "timed_region_samples": int(timed["samples"]),
-                "timed_region_counters_equal_steps_x_per_step": not any(p.startswith("timed region") for p in problems),
-                "frame_equals_single_gpu": bool(frame_ok),
                 "launch": {"single": "one process, one GPU", "multi": "one process, all GPUs (pt_multi_*)",
                            "dist": "one process per GPU (torch.distributed)"}[mode] +
                           (f" -- REHEARSAL: {world} contexts on ONE device, copies in place of ncclGather; not a measurement of {world} GPUs"
                            if args.shared_device else ""),
                 "tiles": tiles,
             },
-            "roofline": roof,
         }
+        if args.full:
+            # the same figure from the in-order steps after the timed region (--in-order: the timed steps themselves)
+            out["config"]["vertices_per_sample"] = round(acc["vertices"] / max(acc["samples"], 1), 3)
+            out["config"]["timed_region_counters_equal_steps_x_per_step"] = not any(p.startswith("timed region") for p in problems)
+            out["config"]["frame_equals_single_gpu"] = bool(frame_ok)
+            out["roofline"] = roof
         if multi_info is not None:
             # proof that N ranks took part: the communicator's own count and the library version, plus what a frame costs the host
             out["config"]["rccl"] = {"ncclCommCount": int(multi_info.comm_count), "version": int(multi_info.rccl_version),
@@ -641,7 +691,7 @@ def main(argv=None):
             roof["frac_of_timed_step"] = round(step_flops / (elapsed / args.steps) / 1e12 / VALU_PEAK_TFLOPS, 4)
             roof["frac_of_timed_step_note"] = ("algorithmic flops of this process's launches of one timed step / the step's wall time (resolve, "
                                                "gather and everything else included) / peak: what the overlap buys, against `frac` of a launch on its own")
-        else:
+        elif args.full:
             roof["launch_times_from"] = "HIP events around every path-kernel launch of the timed steps (--in-order: launches strictly one after the other)"
         if host_buffers:
             out["host_buffers"] = host_buffers
@@ -653,7 +703,7 @@ def main(argv=None):
                         "ncclGather (no kernel takes part in the exchange); `value` above is the ncclGather form"}
         if problems:
             out["verification_failed"] = problems
-        if world == 1 and not args.no_cpu_baseline and not problems:
+        if args.full and world == 1 and not args.no_cpu_baseline and not problems:
             out["cpu_baseline"] = cpu_baseline(pt, objs, WIDTH, HEIGHT, SPP, wl_desc.split(":")[0] + " scene")
         print(json.dumps(out), flush=True)
     ctx.close()

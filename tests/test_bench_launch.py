@@ -62,3 +62,40 @@ def test_the_timed_regions_counters_are_checked_against_the_job(bench):
     assert any("vertices" in p for p in bench.counter_problems("t", dict(good, vertices=good["vertices"] + 1), 20 * 67_108_864, 20))
     wrong_job = bench.counter_problems("t", good, 19 * 67_108_864, 20, per3, 3)
     assert wrong_job and "renders of the job" in wrong_job[0]
+
+
+def test_dump_outputs_writes_float32_planes_and_samples_large_frames(bench, tmp_path, monkeypatch):
+    """--dump-outputs: both film planes as float32; above the size cap, the same seeded pixels of both planes and their indices."""
+    import numpy as np
+    import torch
+    lin = torch.rand((48, 40, 3), dtype=torch.float32, generator=torch.Generator().manual_seed(1))
+    rgba = torch.randint(0, 256, (48, 40, 4), dtype=torch.uint8, generator=torch.Generator().manual_seed(2))
+    bench.dump_outputs(str(tmp_path / "full"), lin, rgba)
+    got_lin, got_rgba = np.load(tmp_path / "full" / "linear.npy"), np.load(tmp_path / "full" / "rgba8.npy")
+    assert got_lin.dtype == np.float32 and got_rgba.dtype == np.float32
+    assert np.array_equal(got_lin, lin.numpy()) and np.array_equal(got_rgba, rgba.numpy().astype(np.float32))
+    assert not (tmp_path / "full" / "pixel_index.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1024)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 100)
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"sampled{k}"
+        bench.dump_outputs(str(out), lin, rgba)
+        runs.append({n: np.load(out / f"{n}.npy") for n in ("linear", "rgba8", "pixel_index")})
+    a, b = runs
+    assert all(np.array_equal(a[n], b[n]) for n in a)                    # the same sample in every run
+    idx = a["pixel_index"]
+    assert idx.dtype == np.float64 and idx.shape == (100,) and len(np.unique(idx)) == 100
+    i = idx.astype(np.int64)
+    assert np.array_equal(a["linear"], lin.numpy().reshape(-1, 3)[i]) and np.array_equal(a["rgba8"], rgba.numpy().reshape(-1, 4)[i].astype(np.float32))
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+
+
+def test_the_largest_workload_dumps_under_the_cap(bench):
+    """C5 (3840 x 2160) is above 64 MB as float32 planes: its sample, with the index, must fit."""
+    w, h = bench.WORKLOADS["c5"][2:4]
+    assert w * h * (3 + 4) * 4 > bench.DUMP_MAX_BYTES
+    assert bench.DUMP_SAMPLE_PIXELS * ((3 + 4) * 4 + 8) <= bench.DUMP_MAX_BYTES
+    for name, (_, _, w, h, _, _) in bench.WORKLOADS.items():
+        assert min(w * h, bench.DUMP_SAMPLE_PIXELS) * ((3 + 4) * 4 + 8) <= bench.DUMP_MAX_BYTES, name

@@ -216,7 +216,7 @@ def test_an_unaligned_rgba8_pointer_is_refused(pt, gpu_ctx):
 
 def _bench(*args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", *args],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", *args],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads(r.stdout.strip().splitlines()[-1])
@@ -228,7 +228,7 @@ def _bench(*args):
 def test_the_bench_record_verifies_itself(args):
     """bench.py keeps the device counters of its timed (overlapped) region and compares the last timed frame, bit for bit, with
     the job rendered alone and in order by a context of its own -- in every mode."""
-    d = _bench(*args)
+    d = _bench("--full", "--no-cpu-baseline", *args)
     c = d["config"]
     assert "verification_failed" not in d
     assert c["frame_equals_single_gpu"] is True and c["timed_region_counters_equal_steps_x_per_step"] is True
@@ -247,3 +247,20 @@ def test_the_bench_record_verifies_itself(args):
         assert abs(r["algorithmic_bytes_per_launch"] - (128.0 * (v - per_launch) + 12.0 * per_launch)) <= 1e-3 * r["algorithmic_bytes_per_launch"]
     else:
         assert r["bound"] == "valu" and r["unit"] == "TFLOP/s"
+
+
+def test_a_plain_bench_run_times_its_steps_and_dumps_the_last_frame(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes the last timed frame as float32 planes."""
+    d = _bench("--steps", "3", "--dump-outputs", str(tmp_path))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["dtype"] == "f32" and d["higher_is_better"] is True and "verification_failed" not in d
+    assert "roofline" not in d and "cpu_baseline" not in d and "frame_equals_single_gpu" not in d["config"]
+    c = d["config"]
+    assert c["timed_region_samples"] == 3 * c["samples_per_step"] == 3 * 1024 * 1024 * 64
+    assert abs(d["value"] - c["samples_per_step"] / (d["ms_per_step"] * 1e-3) / 1e6) <= 0.002 * d["value"]
+    lin, rgba = np.load(tmp_path / "linear.npy"), np.load(tmp_path / "rgba8.npy")
+    assert lin.shape == (1024, 1024, 3) and rgba.shape == (1024, 1024, 4)
+    assert lin.dtype == np.float32 and rgba.dtype == np.float32 and not (tmp_path / "pixel_index.npy").exists()
+    assert np.isfinite(lin).all() and lin.min() >= 0.0 and lin.mean() > 0.0
+    assert (rgba == np.round(rgba)).all() and rgba.min() >= 0 and rgba.max() <= 255 and (rgba[..., 3] == 255).all()

@@ -69,25 +69,58 @@ def test_constants_match_the_header():
     assert re.search(r"#define PT_ABI_VERSION (\d+)", HEADER).group(1) == re.search(r"PT_ABI_VERSION: u32 = (\d+);", RUST).group(1)
 
 
-def test_reference_patch_applies(tmp_path):
+def _patch_hunks(text):
+    """unified diff -> {file: [(old_start, old_lines, pre-image text), ...]}; asserts every hunk's line counts."""
+    out, cur, hunk = {}, None, None
+    lines = text.splitlines()
+    i = 0
+    while i < len(lines):
+        m = re.match(r"^\+\+\+ b/(\S+)", lines[i])
+        h = re.match(r"^@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", lines[i])
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif h:
+            old_n, new_n = int(h.group(2) or 1), int(h.group(4) or 1)
+            pre, n_old, n_new = [], 0, 0
+            i += 1
+            while i < len(lines) and (n_old < old_n or n_new < new_n):
+                tag, body = lines[i][:1], lines[i][1:]
+                assert tag in (" ", "-", "+"), lines[i]
+                if tag != "+":
+                    pre.append(body + "\n")
+                    n_old += 1
+                if tag != "-":
+                    n_new += 1
+                i += 1
+            assert (n_old, n_new) == (old_n, new_n), h.group(0)
+            cur.append((int(h.group(1)), old_n, "".join(pre)))
+            continue
+        i += 1
+    return out
+
+
+def test_reference_patch_applies():
     """rust/reference-shim/reference-gpu.patch (describe() on the traits, Camera::to_pod, gpu::render in main) must
-    apply to the reference's sources.  Only where the reference is present (this container; not the GPU box)."""
-    import shutil
-    import subprocess
-    import pytest
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "src")):
-        pytest.skip("reference sources not present")
-    patch = os.path.join(ROOT, "rust", "reference-shim", "reference-gpu.patch")
-    touched = sorted(set(re.findall(r"^\+\+\+ b/(\S+)", open(patch).read(), flags=re.M)))
+    apply to the reference's sources.  The reference is not part of this repository: tests/golden/reference_patch_targets.json
+    records, per file the patch touches, its line count and the sha256 of the lines each hunk replaces (tests/tools/
+    make_patch_targets.py), so every hunk must find exactly its pre-image at its own position -- no offset, no fuzz."""
+    import hashlib
+    import json
+    targets = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_patch_targets.json")))
+    patch = open(os.path.join(ROOT, "rust", "reference-shim", "reference-gpu.patch")).read()
+    hunks = _patch_hunks(patch)
+    touched = sorted(hunks)
     assert "src/main.rs" in touched and "src/objects/shape.rs" in touched and "src/objects/material.rs" in touched
+    assert touched == sorted(targets["files"])
     for f in touched:
-        os.makedirs(os.path.dirname(tmp_path / f), exist_ok=True)
-        shutil.copy(os.path.join(ref, f), tmp_path / f)
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+        want = targets["files"][f]
+        assert [(s, n) for s, n, _ in hunks[f]] == [(h["old_start"], h["old_lines"]) for h in want["hunks"]], f
+        end = 0
+        for (start, n, pre), h in zip(hunks[f], want["hunks"]):
+            assert start > end and start - 1 + n <= want["lines"], (f, start)       # in order, inside the file
+            assert hashlib.sha256(pre.encode()).hexdigest() == h["sha256"], (f, start)
+            end = start - 1 + n
     # every impl of the two traits in the reference gets a description (or the trait's default)
-    shape_impls = len(re.findall(r"^impl Shape for", open(os.path.join(ref, "src/objects/shape.rs")).read(), flags=re.M))
-    assert open(patch).read().count("fn describe(&self) -> (u32, [f64; 9])") == shape_impls + 1        # + the trait itself
+    assert patch.count("fn describe(&self) -> (u32, [f64; 9])") == targets["shape_impls"] + 1        # + the trait itself
     gpu_rs = open(os.path.join(ROOT, "rust", "reference-shim", "gpu.rs")).read()
     assert "unsafe" not in gpu_rs.replace("forbid(unsafe_code)", "").replace("`unsafe`", "")

@@ -3,4 +3,4 @@
 set -e
 N=${1:-2}
 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29531 \
-    bench.py --gpus $N --steps 3 --warmup 1 --backend gloo
+    bench.py --full --gpus $N --steps 3 --warmup 1 --backend gloo
