@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 4
+#define PT_ABI_VERSION 5
 
 typedef enum {
     PT_OK = 0,
@@ -388,6 +388,26 @@ int pt_debug_fail_after(PtContext* ctx, int64_t n);
 int pt_render_pixels(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params,
                      const uint32_t* xy, uint32_t n, float* out_linear_rgb, uint8_t* out_rgba8,
                      float* out_samples);
+
+/* Adaptive sampling: every pixel gets spp_min samples, then passes of spp_step more go to the pixels whose noise estimate has
+ * not converged, up to params->spp (= spp_max; the last pass is cut to it).  The rule (pathtrace_amd/csrc/pt_adaptive.h), per
+ * pixel over its samples' luminance L = 0.2126 r + 0.7152 g + 0.0722 b in f64, S1 = sum L, S2 = sum L^2, checked at
+ * n = spp_min, spp_min + spp_step, ...:
+ *   mean = S1 / n,  var = max(0, (S2 - S1 mean) / (n - 1)),  se = sqrt(var / n)
+ *   converged  <=>  se <= rel_tol * max(mean, abs_floor)   (never with rel_tol = 0 or a non-finite sum)
+ * Pixel (x, y) gets samples spp_offset .. spp_offset + n - 1 and its film is their mean through the same gamma / `as u8`
+ * steps as every render: bit-identical to pt_render_pixels / pt_render_host of that pixel with spp = n.  out_spp = n,
+ * out_rel_err = se / max(mean, abs_floor) at n (both optional, width * height entries).  Host buffers, blocking; the whole
+ * image (band_count = 1).  PT_ERR_INVALID_ARG: spp_min < 2, spp_step = 0, params->spp < spp_min, rel_tol negative or not
+ * finite, abs_floor <= 0.                                                                                               */
+typedef struct {
+    uint32_t spp_min;    /* samples every pixel gets first (>= 2)                                   */
+    uint32_t spp_step;   /* samples per later pass, for the pixels not yet converged (>= 1)          */
+    double rel_tol;      /* a pixel stops once se(L) <= rel_tol * max(mean(L), abs_floor)            */
+    double abs_floor;    /* keeps dark pixels from running to spp_max (> 0)                          */
+} PtAdaptive;
+int pt_render_adaptive(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, const PtAdaptive* ad,
+                       float* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, float* out_rel_err);
 
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on

@@ -83,6 +83,15 @@ class PtStats(C.Structure):
     ]
 
 
+class PtAdaptive(C.Structure):
+    _fields_ = [
+        ("spp_min", C.c_uint32),
+        ("spp_step", C.c_uint32),
+        ("rel_tol", C.c_double),
+        ("abs_floor", C.c_double),
+    ]
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -151,6 +160,8 @@ SYMBOLS = {
     "pt_debug_bvh_check": (C.c_int, [_P(PtObject), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "pt_render_pixels": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(C.c_uint32), C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "pt_render_adaptive": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtAdaptive), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

@@ -267,6 +267,19 @@ class _ContextFunctions:
                                      rgba.ctypes.data_as(C.c_void_p), smp.ctypes.data_as(C.c_void_p) if want_samples else None))
         return lin, rgba, smp
 
+    def render_adaptive(self, cam, params, spp_min, spp_step, rel_tol, abs_floor=1e-3):
+        """pt_render_adaptive: params.spp = spp_max.  -> (linear f32[H,W,3], rgba u8[H,W,4], spp u32[H,W], rel_err f32[H,W])"""
+        ad = _lib.PtAdaptive(spp_min, spp_step, rel_tol, abs_floor)
+        H, W = cam.height, cam.width
+        lin = np.empty((H, W, 3), dtype=np.float32)
+        rgba = np.empty((H, W, 4), dtype=np.uint8)
+        spp = np.empty((H, W), dtype=np.uint32)
+        err = np.empty((H, W), dtype=np.float32)
+        check(lib().pt_render_adaptive(self._h, C.byref(cam), C.byref(params), C.byref(ad), lin.ctypes.data_as(C.c_void_p),
+                                       rgba.ctypes.data_as(C.c_void_p), spp.ctypes.data_as(C.c_void_p),
+                                       err.ctypes.data_as(C.c_void_p)))
+        return lin, rgba, spp, err
+
     def ray_color(self, params, rays, xy):
         """pt_ray_color = RenderingStrategy::ray_color(world, ray, 0, rng(key xy, sample spp_offset), 1) -> f32[n,3]"""
         rays = _f64(rays, 6)

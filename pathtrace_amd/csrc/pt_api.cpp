@@ -22,6 +22,15 @@
 #include "pt_kernels.h"
 #include "pt_sched.h"
 
+#ifdef PT_SAN_NO_KERNELS
+// The host-only sanitizer build (tests/tools/run_sanitizers.sh) links no device code; its stub file covers the launchers
+// that existed before adaptive sampling, these two are stubbed here.  Nothing that build runs reaches them.
+namespace ptk {
+void launch_resolve_adaptive(const AdaptiveResolveArgs&, hipStream_t) { std::abort(); }
+void launch_adaptive_select(const uint2*, uint32_t, uint32_t, const uint32_t*, uint32_t*, uint2*, uint32_t*, hipStream_t) { std::abort(); }
+}  // namespace ptk
+#endif
+
 static thread_local std::string g_err;
 namespace {
 
@@ -199,6 +208,12 @@ struct PtContext {
     DevBuf<float4> inject[4];
     DevBuf<float> fn_in, fn_out;               // pt_debug_* function entries
     DevBuf<uint32_t> fn_words;
+    // pt_render_adaptive: image-indexed per-pixel state (ptk::AdaptiveFilm), the active lists of two consecutive passes,
+    // and [survivor count | per-workgroup counts of k_adaptive_select]
+    DevBuf<double> ad_sums;
+    DevBuf<uint32_t> ad_count, ad_conv, ad_words;
+    DevBuf<float> ad_err;
+    DevBuf<uint2> ad_list[2];
 };
 
 namespace {
@@ -215,6 +230,13 @@ struct ListRender {
     const uint2* d_pixels = nullptr;
     uint32_t n = 0;
     const float4* inject[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool regen = false;       // the list may take the regenerating level-0 kernel (pt_render_adaptive's passes)
+};
+// A pass of pt_render_adaptive: the film resolve is k_resolve_adaptive into the image-indexed state instead of k_resolve.
+struct AdaptivePass {
+    ptk::AdaptiveFilm f{};
+    bool load = false;        // the pixels already have samples (every pass after the first)
+    uint32_t n_total = 0;     // samples per pixel of the pass's pixels once it is done
 };
 
 // The lanes' streams are created with a priority other than the default: the runtime keeps a pool of hardware queues per
@@ -444,6 +466,8 @@ int pt_context_destroy(PtContext* c) {
     if (c->h_posted) (void)hipHostFree(c->h_posted);
     c->lsamp.release(); c->film.release(); c->host_lin.release(); c->host_rgba.release();
     c->pixel_list.release(); c->fn_in.release(); c->fn_out.release(); c->fn_words.release();
+    c->ad_sums.release(); c->ad_count.release(); c->ad_conv.release(); c->ad_words.release(); c->ad_err.release();
+    c->ad_list[0].release(); c->ad_list[1].release();
     for (auto& b : c->inject) b.release();
     if (c->h_dstats) (void)hipHostFree(c->h_dstats);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -673,7 +697,7 @@ void sched_recover(PtContext* c, hipStream_t st, const ptsched::State& planned) 
 // error here leaves the context as it was), PLAN (ptsched::plan on a copy of the scheduling state: pure), EXECUTE (the
 // plan's stream operations in order) and COMMIT of the copy.  A failure during EXECUTE: sched_recover.
 int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
-                float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr) {
+                float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr) {
     if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "render: null argument");
     if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
     const bool inject = list && list->inject[0];
@@ -720,8 +744,9 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
         return fail(PT_ERR_UNSUPPORTED, "tile %ux%llu: width and tile rows must be < 65536", cam->width, (unsigned long long)tile_rows);
     // scene / job that can take the regenerating level-0 kernel (decided below, once the batch size is known)
     // level0_form 3 / default for scenes with a minority of Mirror objects: the regenerating form with the Mirror vertices batched
-    const bool lds_job = !list && !prm->accel && c->view.n_objs <= ptk::kSmallObjs && c->view.blob_f4 != 0;
-    const bool split = lds_job && (c->tuning.level0_form == 3 || (c->tuning.level0_form == 0 && c->split_ok && kSplitByDefault));
+    // (a list takes the regenerating kernel only where its caller asks for it, and never the split form)
+    const bool lds_job = (!list || list->regen) && !prm->accel && c->view.n_objs <= ptk::kSmallObjs && c->view.blob_f4 != 0;
+    const bool split = lds_job && !list && (c->tuning.level0_form == 3 || (c->tuning.level0_form == 0 && c->split_ok && kSplitByDefault));
     // default (round 3): every scene in LDS takes a regenerating form -- compiled for its material set (diffuse only; no
     // Mirror; everything); with the Mirror vertices batched where they are the exception (split, above).  The queue form
     // is level0_form = 1 (all-Mirror Cornell scene: queue form 12.6 ms, regenerating 10.0, split 13.8; tools/r03/mirror_forms.py)
@@ -975,6 +1000,19 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
         }
         case kOpResolve: {
             const uint32_t s0 = o.batch * nb_max, nb = std::min(nb_max, spp - s0);
+            if (ad) {
+                ptk::AdaptiveResolveArgs r{};
+                r.f = ad->f;
+                r.lsamp = sample_buffer(c, o.set).p;
+                r.pixels = list ? list->d_pixels : nullptr;
+                r.width = cam->width; r.n = np; r.nb = nb; r.n_total = ad->n_total;
+                r.load = o.batch > 0 || ad->load;
+                r.finalize = o.batch + 1 == n_batches;
+                if (o.zero_words) { r.zero_words = c->ovf_count.p + kStatsWords + kCountStride * o.set; r.n_zero = o.zero_words; }
+                ptk::launch_resolve_adaptive(r, s);
+                HIP_TRY(hipGetLastError());
+                return PT_OK;
+            }
             ptk::ResolveArgs r{};
             r.lsamp = sample_buffer(c, o.set).p;
             r.film = c->film.p;
@@ -1478,6 +1516,71 @@ int pt_render_pixels(PtContext* c, const PtCamera* cam, const PtRenderParams* pr
             float* o = out_samples + ((size_t)i * prm->spp + sidx) * 3;
             o[0] = v.r; o[1] = v.g; o[2] = v.b;
         }
+    return PT_OK;
+}
+
+// Adaptive sampling: pass 0 gives every pixel spp_min samples (the full-frame kernels); then, while pixels are left whose
+// last check failed (pt_adaptive.h), k_adaptive_select compacts them into a list and the next pass gives them spp_step more
+// (the regenerating kernel's LIST instances where the scene takes that kernel).  Every pass is a render_impl whose resolve
+// is k_resolve_adaptive.  A pixel's samples are spp_offset .. spp_offset + n - 1 and its f64 sums are added in sample order,
+// so it is bit-identical to a uniform render of that pixel with spp = n.
+int pt_render_adaptive(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad, float* out_linear,
+                       uint8_t* out_rgba, uint32_t* out_spp, float* out_rel_err) {
+    if (!c || !cam || !prm || !ad || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: null argument");
+    if (ad->spp_min < 2) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: spp_min %u < 2 (the variance needs two samples)", ad->spp_min);
+    if (ad->spp_step == 0) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: spp_step must be > 0");
+    if (prm->spp < ad->spp_min) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: spp (= spp_max) %u < spp_min %u", prm->spp, ad->spp_min);
+    if (!(ad->rel_tol >= 0.0) || !std::isfinite(ad->rel_tol)) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: rel_tol must be finite and >= 0");
+    if (!(ad->abs_floor > 0.0)) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: abs_floor must be > 0");
+    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
+        return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: renders the whole image (band_count = 1)");
+    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
+    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    const uint64_t np64 = (uint64_t)cam->width * cam->height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_render_adaptive: %llu pixels", (unsigned long long)np64);
+    const uint32_t np = (uint32_t)np64, spp_max = prm->spp, W = cam->width;
+    HIP_TRY(hipSetDevice(c->device));
+    const hipStream_t st = c->stream;
+    int rc;
+    if ((rc = c->ad_sums.ensure(5 * (size_t)np)) || (rc = c->ad_count.ensure(np)) || (rc = c->ad_conv.ensure(np)) ||
+        (rc = c->ad_err.ensure(np)) || (rc = c->ad_list[0].ensure(np)) || (rc = c->ad_list[1].ensure(np)) ||
+        (rc = c->ad_words.ensure(1 + (np + ptk::kSelectTile - 1) / ptk::kSelectTile)) || (rc = c->host_lin.ensure(3 * (size_t)np)) ||
+        (rc = c->host_rgba.ensure(4 * (size_t)np)))
+        return rc;
+    AdaptivePass pass;
+    pass.f.sums = c->ad_sums.p; pass.f.count = c->ad_count.p; pass.f.rel_err = c->ad_err.p; pass.f.conv = c->ad_conv.p;
+    pass.f.out_linear = c->host_lin.p; pass.f.out_rgba = c->host_rgba.p;
+    pass.f.rel_tol = ad->rel_tol; pass.f.abs_floor = ad->abs_floor;
+    PtRenderParams p = *prm;
+    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
+    // pass 0: the whole image, full-frame kernels; list slot = image pixel
+    p.spp = ad->spp_min;
+    pass.load = false; pass.n_total = ad->spp_min;
+    if ((rc = render_impl(c, cam, &p, FilmState{}, nullptr, c->host_lin.p, c->host_rgba.p, nullptr, &pass))) return rc;
+    uint32_t done = ad->spp_min, n_cur = np, which = 0;
+    const uint2* cur = nullptr;                 // the last pass's list (null: every pixel, image order)
+    uint32_t* const d_n = c->ad_words.p;
+    while (done < spp_max) {
+        ptk::launch_adaptive_select(cur, n_cur, W, c->ad_conv.p, c->ad_words.p + 1, c->ad_list[which].p, d_n, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->h_ovf, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t n_next = c->h_ovf[0];
+        if (n_next == 0) break;
+        const uint32_t step = std::min(ad->spp_step, spp_max - done);
+        ListRender lr;
+        lr.d_pixels = c->ad_list[which].p; lr.n = n_next; lr.regen = true;
+        p.spp = step; p.spp_offset = prm->spp_offset + done;
+        pass.load = true; pass.n_total = done + step;
+        if ((rc = render_impl(c, cam, &p, FilmState{}, &lr, c->host_lin.p, c->host_rgba.p, nullptr, &pass))) return rc;
+        done += step;
+        cur = c->ad_list[which].p; n_cur = n_next; which ^= 1u;
+    }
+    if ((rc = pt_sync(c))) return rc;
+    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, 3 * (size_t)np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * (size_t)np, hipMemcpyDeviceToHost));
+    if (out_spp) HIP_TRY(hipMemcpy(out_spp, c->ad_count.p, (size_t)np * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_rel_err) HIP_TRY(hipMemcpy(out_rel_err, c->ad_err.p, (size_t)np * sizeof(float), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

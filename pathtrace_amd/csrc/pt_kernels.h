@@ -84,9 +84,9 @@ struct BounceArgs {
     // (src_mode = 1) takes its n_first paths from ovf_in instead of generating camera rays
     Queue ovf_in, ovf_out;
     uint32_t* ovf_out_count;
-    // non-null: level-0 launch in the regenerating form (k_paths_regen; scene in LDS, src_mode 0, no pixel list): the
-    // waves take the batch's 64-path chunks from this counter (zeroed before the launch) and export what is alive
-    // when it runs out
+    // non-null: level-0 launch in the regenerating form (k_paths_regen; scene in LDS, src_mode 0; a pixel list only for
+    // pt_render_adaptive's passes): the waves take the batch's 64-path chunks from this counter (zeroed before the launch)
+    // and export what is alive when it runs out
     uint32_t* chunk_counter;
     // non-null (with chunk_counter): the regenerating form that batches Mirror vertices (k_paths_regen_split); per wave of the
     // launch kXqF4PerWave float4 of exchange stacks + parking area
@@ -115,7 +115,8 @@ struct BounceArgs {
     const uint32_t* n_first_dev;
     // pixel-list renders (pt_render_pixels / pt_ray_color): film slot i = (tile_row << 16) | x of the path state,
     // RNG key and camera pixel = pixels[i] = (x, y) of the image.  film_w = row pitch of the film-slot arithmetic
-    // (camera width, or 65536 for a list).
+    // (camera width, or 65536 for a list).  A list with chunk_counter set (pt_render_adaptive's passes) takes the
+    // regenerating kernel's LIST instances (k_paths_regen<MIS, mats, true>).
     const uint2* pixels;
     uint32_t film_w;
     uint32_t film_w_magic;    // floor(2^32 / film_w), 0xFFFFFFFF for 1 (divmod_magic)
@@ -203,6 +204,36 @@ struct ResolveArgs {
     uint32_t n_zero;
 };
 void launch_resolve(const ResolveArgs& a, hipStream_t st);
+
+// Adaptive sampling (pt_render_adaptive, the rule in pt_adaptive.h).  Image-indexed state: f64 sums per pixel (R, G, B, S1 =
+// sum of luminance, S2 = sum of its square) in sample order, sample count, relative error, converged flag.
+struct AdaptiveFilm {
+    double* sums;             // 5 doubles per image pixel
+    uint32_t* count;          // samples per image pixel
+    float* rel_err;           // se / max(mean, abs_floor) at count
+    uint32_t* conv;           // 1: the last check passed
+    float* out_linear;        // image-indexed film (mean), 3 floats per pixel
+    uint8_t* out_rgba;        // 4 bytes per pixel
+    double rel_tol, abs_floor;
+};
+// One sample batch of a pass: list slot i (pixel pixels[i], or image pixel i when pixels is null) adds the nb samples
+// lsamp[s * n + i] to its sums; on the pass's last batch (finalize) the pixel's film, count (= n_total), rel_err and flag.
+struct AdaptiveResolveArgs {
+    AdaptiveFilm f;
+    const Rgb* lsamp;
+    const uint2* pixels;
+    uint32_t width, n, nb, n_total;
+    uint32_t load;            // start from the stored sums (else from zero: the pixel's first samples)
+    uint32_t finalize;
+    uint32_t* zero_words;     // as ResolveArgs
+    uint32_t n_zero;
+};
+void launch_resolve_adaptive(const AdaptiveResolveArgs& a, hipStream_t st);
+// The pixels of a list (null: every image pixel in order, n = width * height) whose last check failed, compacted into
+// out in the list's order.  block_counts: ceil(n / kSelectTile) words of scratch; *out_n = survivors.
+constexpr uint32_t kSelectTile = 1024;
+void launch_adaptive_select(const uint2* pixels, uint32_t n, uint32_t width, const uint32_t* conv, uint32_t* block_counts,
+                            uint2* out, uint32_t* out_n, hipStream_t st);
 
 // Multi-GPU film exchange (pt_multi.cpp): tile -> 16 B per pixel (linear RGB + RGBA8) before the gather, gathered
 // padded tiles -> frame in image order after it.

@@ -415,6 +415,25 @@ public:
         check(pt_render_progressive(ctx_, &camera_.pod(), &p, spp_step, tramp, &cx, lin.data(), rgba.data()));
         unpack(lin, rgba);
     }
+    // Adaptive form of render() (pt_render_adaptive): params().spp = spp_max; a pixel stops at the first check (spp_min,
+    // spp_min + spp_step, ...) where se(luminance) <= rel_tol * max(mean, abs_floor).  data / luminance_data as render();
+    // spp (optional) receives the samples of every pixel and rel_err (optional) its se / max(mean, abs_floor), y*W+x.
+    void render_adaptive(uint32_t spp_min, uint32_t spp_step, double rel_tol, double abs_floor = 1e-3, std::vector<uint32_t>* spp = nullptr,
+                         std::vector<float>* rel_err = nullptr, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3);
+        std::vector<uint8_t> rgba(n * 4);
+        if (spp) spp->assign(n, 0u);
+        if (rel_err) rel_err->assign(n, 0.0f);
+        PtAdaptive ad{spp_min, spp_step, rel_tol, abs_floor};
+        check(pt_render_adaptive(ctx_, &camera_.pod(), &p, &ad, lin.data(), rgba.data(), spp ? spp->data() : nullptr,
+                                 rel_err ? rel_err->data() : nullptr));
+        unpack(lin, rgba);
+    }
     PtStats stats() { PtStats s{}; if (ctx_) check(pt_get_stats(ctx_, &s)); return s; }
 
     // World::draw (world.rs:335-341): blit RGBA8 into a frame of 4*W*H bytes

@@ -3,7 +3,7 @@
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const PT_ABI_VERSION: u32 = 4;
+pub const PT_ABI_VERSION: u32 = 5;
 
 pub const PT_OK: c_int = 0;
 pub const PT_ERR_INVALID_ARG: c_int = 1;
@@ -74,6 +74,16 @@ pub struct PtTuning {
     pub level0_form: u32,
     pub regen_workgroups: u32,
     pub in_order: u32,
+}
+
+/// pt_render_adaptive: the stopping rule's parameters (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtAdaptive {
+    pub spp_min: u32,
+    pub spp_step: u32,
+    pub rel_tol: f64,
+    pub abs_floor: f64,
 }
 
 #[repr(C)]
@@ -221,6 +231,7 @@ extern "C" {
     pub fn pt_film_unpack(hip_stream: *mut c_void, d_gathered: *const c_void, width: u32, height: u32, band_rows: u32, n_ranks: u32, max_rows: u32, d_linear_rgb: *mut f32, d_rgba8: *mut u8) -> c_int;
     pub fn pt_debug_multi_emulate(ctx: *mut PtContext, n_virtual: u32, cam: *const PtCamera, params: *const PtRenderParams, out_linear_rgb: *mut f32, out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_pixels(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, xy: *const u32, n: u32, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_samples: *mut f32) -> c_int;
+    pub fn pt_render_adaptive(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, ad: *const PtAdaptive, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_spp: *mut u32, out_rel_err: *mut f32) -> c_int;
     pub fn pt_ray_color(ctx: *mut PtContext, params: *const PtRenderParams, rays: *const f64, xy: *const u32, n: u32, out_rgb: *mut f32) -> c_int;
     pub fn pt_debug_hit_scene(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_t: *mut f32) -> c_int;
     pub fn pt_debug_hit_records(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_rec: *mut f32) -> c_int;

@@ -1,0 +1,152 @@
+"""pt_render_adaptive (adaptive sampling): every pixel gets spp_min samples, then passes of spp_step more go to the pixels
+whose noise estimate (pathtrace_amd/csrc/pt_adaptive.h) has not converged, up to spp_max = params.spp.
+
+A pixel that got n samples must be BIT-IDENTICAL to the same pixel of a uniform render with spp = n: its samples are
+spp_offset .. spp_offset + n - 1 (Philox draws addressed by (x, y, sample, depth)) and its f64 sums are added in sample
+order.  These tests check that against pt_render_device / pt_render_pixels, on every kernel form an adaptive pass can
+take, and restate the stopping rule in numpy on the per-sample radiance pt_render_pixels reports."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+LUM = (0.2126, 0.7152, 0.0722)
+
+
+def _with(prm, **kw):
+    q = type(prm)()
+    for name, _ in prm._fields_:
+        setattr(q, name, getattr(prm, name))
+    for k, v in kw.items():
+        setattr(q, k, v)
+    return q
+
+
+def _uniform(ctx, cam, prm):
+    lin, rgba = ctx.render(cam, prm)
+    return lin.cpu().numpy(), rgba.cpu().numpy()
+
+
+def _pixel_parity(ctx, cam, prm, lin, rgba, spp, n_sample=512, seed=0):
+    """pt_render_pixels(group, spp = n) for a seeded sample of pixels, grouped by their adaptive spp: bit-identical."""
+    rng = np.random.default_rng(seed)
+    flat = rng.choice(cam.width * cam.height, size=min(n_sample, cam.width * cam.height), replace=False)
+    ys, xs = flat // cam.width, flat % cam.width
+    for n in np.unique(spp[ys, xs]):
+        sel = spp[ys, xs] == n
+        xy = np.stack([xs[sel], ys[sel]], axis=1)
+        plin, prgba, _ = ctx.render_pixels(cam, _with(prm, spp=int(n)), xy)
+        assert np.array_equal(plin, lin[ys[sel], xs[sel]]), f"spp {n}: linear film differs from pt_render_pixels"
+        assert np.array_equal(prgba, rgba[ys[sel], xs[sel]]), f"spp {n}: RGBA8 differs from pt_render_pixels"
+
+
+@pytest.mark.parametrize("scene,exact", [(2, 0), (2, 1), (1, 0), (1, 1)])
+def test_no_tolerance_is_the_uniform_render(pt, gpu_ctx, scene, exact):
+    """rel_tol = 0: every pixel runs to spp_max, and the film is the uniform one bit for bit.  spp_max = 45 is not
+    spp_min + k * spp_step (8, 24, 40): the last pass is cut to 5 samples."""
+    gpu_ctx.upload(pt.builtin_scene(scene))
+    cam = pt.camera_new(width=128, height=128)
+    prm = pt.default_params(spp=45, exact_math=exact, spp_offset=3)
+    lin, rgba, spp, err = gpu_ctx.render_adaptive(cam, prm, spp_min=8, spp_step=16, rel_tol=0.0)
+    assert (spp == 45).all()
+    ulin, urgba = _uniform(gpu_ctx, cam, prm)
+    assert np.array_equal(lin, ulin) and np.array_equal(rgba, urgba)
+    assert np.isfinite(err).all() and (err >= 0).all()
+
+
+def test_huge_tolerance_stops_everything_at_spp_min(pt, gpu_ctx):
+    gpu_ctx.upload(pt.builtin_scene(1))
+    cam = pt.camera_new(width=96, height=80)
+    prm = pt.default_params(spp=200)
+    lin, rgba, spp, _ = gpu_ctx.render_adaptive(cam, prm, spp_min=6, spp_step=10, rel_tol=1e30)
+    assert (spp == 6).all()
+    ulin, urgba = _uniform(gpu_ctx, cam, _with(prm, spp=6))
+    assert np.array_equal(lin, ulin) and np.array_equal(rgba, urgba)
+
+
+def _world_adaptive(pt, ctx, size=200, **kw):
+    ctx.upload(pt.builtin_scene(1))
+    cam = pt.camera_new(width=size, height=size)
+    prm = pt.default_params(spp=kw.pop("spp_max", 256), **kw)
+    return cam, prm, ctx.render_adaptive(cam, prm, spp_min=16, spp_step=16, rel_tol=0.05, abs_floor=1e-3)
+
+
+def test_each_pixel_equals_pt_render_pixels_at_its_spp(pt, gpu_ctx):
+    cam, prm, (lin, rgba, spp, err) = _world_adaptive(pt, gpu_ctx)
+    assert len(np.unique(spp)) >= 3, np.unique(spp)
+    assert spp.min() >= 16 and spp.max() <= 256
+    _pixel_parity(gpu_ctx, cam, prm, lin, rgba, spp)
+
+
+def test_the_rule_restated_in_numpy(pt, gpu_ctx):
+    """Replay S1 / S2 from the per-sample radiance at every check point in f64: the first check that passes is out_spp
+    and out_rel_err is se / max(mean, abs_floor) there."""
+    spp_min, step, spp_max, tol, floor = 16, 16, 200, 0.05, 1e-3
+    gpu_ctx.upload(pt.builtin_scene(1))
+    cam = pt.camera_new(width=200, height=200)
+    prm = pt.default_params(spp=spp_max)
+    _, _, spp, err = gpu_ctx.render_adaptive(cam, prm, spp_min=spp_min, spp_step=step, rel_tol=tol, abs_floor=floor)
+    rng = np.random.default_rng(1)
+    flat = rng.choice(cam.width * cam.height, size=64, replace=False)
+    xy = np.stack([flat % cam.width, flat // cam.width], axis=1)
+    _, _, smp = gpu_ctx.render_pixels(cam, prm, xy, want_samples=True)
+    checks = list(range(spp_min, spp_max, step)) + [spp_max]
+    tested = 0
+    for i, (x, y) in enumerate(xy):
+        s = smp[i].astype(np.float64)
+        L = LUM[0] * s[:, 0] + LUM[1] * s[:, 1] + LUM[2] * s[:, 2]
+        s1, s2 = np.cumsum(L), np.cumsum(L * L)
+        stop, rel, near = None, None, False
+        for n in checks:
+            mean = s1[n - 1] / n
+            var = max(0.0, (s2[n - 1] - s1[n - 1] * mean) / (n - 1))
+            se = np.sqrt(var / n)
+            scale = max(mean, floor)
+            thr = tol * scale
+            near = near or abs(se - thr) <= 1e-9 * thr
+            if se <= thr or n == spp_max:
+                stop, rel = n, se / scale
+                break
+        if near:
+            continue
+        tested += 1
+        assert spp[y, x] == stop, (x, y, spp[y, x], stop)
+        assert err[y, x] == pytest.approx(rel, rel=1e-6, abs=0)
+    assert tested >= 48
+
+
+@pytest.mark.parametrize("form", ["tiled", "bvh", "batches"])
+def test_other_kernel_forms(pt, gpu_ctx, form):
+    """A scene of more than 128 objects (tiled scan), the BVH, and a max_paths_in_flight that cuts every pass into
+    several sample batches: each pixel still equals pt_render_pixels at its spp."""
+    if form == "tiled":
+        gpu_ctx.upload(pt.builtin_scene(4, 200))
+        cam, prm = pt.camera_new(width=96, height=96), pt.default_params(spp=96, accel=0)
+    elif form == "bvh":
+        gpu_ctx.upload(pt.builtin_scene(1))
+        cam, prm = pt.camera_new(width=96, height=96), pt.default_params(spp=96, accel=1)
+    else:
+        gpu_ctx.upload(pt.builtin_scene(1))
+        cam, prm = pt.camera_new(width=64, height=64), pt.default_params(spp=96, max_paths_in_flight=64 * 64 * 3)
+    lin, rgba, spp, _ = gpu_ctx.render_adaptive(cam, prm, spp_min=8, spp_step=8, rel_tol=0.08)
+    assert len(np.unique(spp)) >= 2, np.unique(spp)
+    _pixel_parity(gpu_ctx, cam, prm, lin, rgba, spp, n_sample=256)
+
+
+def test_counts_determinism_and_arguments(pt, gpu_ctx):
+    cam, prm, (lin, rgba, spp, err) = _world_adaptive(pt, gpu_ctx, size=128)
+    st = gpu_ctx.stats()
+    assert st.samples == st.samples_expected == int(spp.sum(dtype=np.uint64))
+    lin2, rgba2, spp2, err2 = gpu_ctx.render_adaptive(cam, prm, spp_min=16, spp_step=16, rel_tol=0.05, abs_floor=1e-3)
+    assert np.array_equal(lin, lin2) and np.array_equal(rgba, rgba2) and np.array_equal(spp, spp2)
+    assert np.array_equal(err.view(np.uint32), err2.view(np.uint32))
+    bad = [dict(spp_min=1, spp_step=4, rel_tol=0.1), dict(spp_min=4, spp_step=0, rel_tol=0.1),
+           dict(spp_min=300, spp_step=4, rel_tol=0.1), dict(spp_min=4, spp_step=4, rel_tol=-0.1),
+           dict(spp_min=4, spp_step=4, rel_tol=float("nan")), dict(spp_min=4, spp_step=4, rel_tol=float("inf")),
+           dict(spp_min=4, spp_step=4, rel_tol=0.1, abs_floor=0.0), dict(spp_min=4, spp_step=4, rel_tol=0.1, abs_floor=-1.0)]
+    for kw in bad:
+        with pytest.raises(pt._lib.PtError) as e:
+            gpu_ctx.render_adaptive(cam, prm, **kw)
+        assert e.value.code == 1, kw
+    with pytest.raises(pt._lib.PtError) as e:
+        gpu_ctx.render_adaptive(cam, _with(prm, band_count=2), spp_min=4, spp_step=4, rel_tol=0.1)
+    assert e.value.code == 1
