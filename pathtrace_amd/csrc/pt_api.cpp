@@ -1119,9 +1119,6 @@ int pt_sync(PtContext* c) {
         c->stats.samples_expected = exp;
         bool ok = dev == exp;
         if (!ok && c->capture_gcd) ok = dev >= exp && (dev - exp) % c->capture_gcd == 0;
-#if defined(PT_COUNT_FINISHED) && !PT_COUNT_FINISHED
-        ok = true;                        // measurement build whose kernels do not count (A/B of the counting's cost only)
-#endif
         c->expected_samples = 0;
         if (c->h_dstats[7] != 0)     // a kernel found one of its own invariants violated: the film is not to be trusted
             rc = fail(PT_ERR_HIP, "internal: the exchange stacks of k_paths_regen_split overflowed (please report; PtTuning.level0_form = 1 avoids the kernel)");

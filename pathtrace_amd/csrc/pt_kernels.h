@@ -33,7 +33,7 @@ struct BvhView {
 };
 
 struct SceneView {
-    const float4* scan;      // scan records, run-packed: sphere = 1 float4 (c, r^2); triangle = 3 float4 (v0, n, N1, N2: pt_bvh.h triangle_scan_record)
+    const float4* scan;      // scan records, run-packed: sphere = 1 float4 (c, r^2); triangle = 3 float4 (n, N1.x) (v0, N1.y) (N1.z, N2): pt_bvh.h triangle_scan_record
     const float4* shape;     // 3 float4 per object (gather form), see pt_device.h
     const float4* mat;       // 2 float4 per object
     const Run* runs;

@@ -57,30 +57,6 @@ using namespace ptk;
 #define PT_TU_MAIN (PT_TU == 0 || PT_TU == 1)
 #define PT_TU_SPLIT (PT_TU == 0 || PT_TU == 2)
 #define PT_TU_BVH (PT_TU == 0 || PT_TU == 3)
-#ifndef PT_PAIR_PREFETCH
-#define PT_PAIR_PREFETCH 1      // 1: the next pair's normal one pair ahead (C1 launch 7.16 -> 7.07 ms); 2: its v0 too (2 spilled registers, 7.17) -- profiles/r05/ab_lds_latency.txt
-#endif
-#ifndef PT_PAIR_PREFETCH_GENERIC
-#define PT_PAIR_PREFETCH_GENERIC 0      // the same in the generic-material kernels (5 waves per SIMD: registers to spare)
-#endif
-#ifndef PT_SPHERE_REM2
-#define PT_SPHERE_REM2 1
-#endif
-#ifndef PT_RUN0_SGPR
-#define PT_RUN0_SGPR 0          // measured (round 5): C1 launch +1.7 %, C2 +0.3 % -- profiles/r05/ab_lds_latency.txt
-#endif
-#ifndef PT_PAIR_S_EARLY
-#define PT_PAIR_S_EARLY 0       // measured (round 5): C1 launch 7.09 -> 7.05 / 7.17 ms without / with the prefetch -- profiles/r05/ab_pair_s_early.txt
-#endif
-#ifndef PT_U_MED3
-#define PT_U_MED3 1             // measured (round 5): C1 launch 7.04-7.07 -> 7.00-7.04 ms (two scalar instructions less per pair test) -- profiles/r05/ab_u_med3.txt
-#endif
-#ifndef PT_PAIR_FLAT
-#define PT_PAIR_FLAT 0          // measured (round 5): C1 7.46 -> 7.92 ms per launch -- profiles/r05/ab_c1_replace_flat.txt
-#endif
-#ifndef PT_SPHERE_FLAT
-#define PT_SPHERE_FLAT 0        // measured (round 5): C2 5.54 -> 5.55 ms per launch, nothing -- profiles/r05/ab_noslp.txt
-#endif
 namespace PTK_IMPL {
 
 // ------------------------------------------------------------------ primitive tests
@@ -114,15 +90,12 @@ PT_DEV void sphere_test(float4 s, f3 o, f3 d, float t_min, float& closest, int& 
     closest = c;
     id = obj;
 }
-// RangeInclusive(0.0..=1.0).contains(u) (shape.rs:176): true for -0.0, false for NaN.  Evaluated (round 5, PT_U_MED3) as
-// "the median of (u, 0, 1) is u" -- one v_med3 + one compare instead of two compares and a scalar AND of their masks (the scalar ALU is
-// one per CU).  Equivalent for every input: a NaN is not equal to itself, and med3(-0, 0, 1) compares equal to -0 whichever zero it returns.
+// RangeInclusive(0.0..=1.0).contains(u) (shape.rs:176): true for -0.0, false for NaN.  Evaluated as "the median of (u, 0, 1) is u"
+// -- one v_med3 + one compare instead of two compares and a scalar AND of their masks (the scalar ALU is one per CU; round 5: C1 launch
+// 7.04-7.07 -> 7.00-7.04 ms).  Equivalent for every input: a NaN is not equal to itself, and med3(-0, 0, 1) compares equal to -0 whichever
+// zero it returns.
 PT_DEV bool in_unit_range(float u) {
-#if PT_U_MED3
     return __builtin_amdgcn_fmed3f(u, 0.0f, 1.0f) == u;
-#else
-    return u >= 0.0f && u <= 1.0f;
-#endif
 }
 // TriangleShape::hit (shape.rs:161-192).  The reference runs Moeller-Trumbore per ray (two cross products, three dot
 // products with the edges); the f32 specification evaluates the same u, v, t from per-triangle constants built once at
@@ -140,18 +113,12 @@ PT_DEV void triangle_test(float4 r0, float4 r1, float4 r2, f3 o, f3 d, float t_m
     if (__builtin_fabsf(det) < 1e-8f) return;
     const f3 s = o - mk(r1.x, r1.y, r1.z);
     const float t = pt_div(-dot(s, n), det);
-#ifdef PT_TRI_BRANCHLESS      // measurement variant: one reject at the end instead of three early-outs
-    const f3 p = madd(d, t, s);
-    const float u = dot(p, mk(r0.w, r1.w, r2.x)), v = dot(p, mk(r2.y, r2.z, r2.w));
-    if (t < t_min || t > closest || !(u >= 0.0f && u <= 1.0f) || v < 0.0f || u + v > 1.0f) return;
-#else
     if (t < t_min || t > closest) return;
     const f3 p = madd(d, t, s);                      // hit point relative to v0
     const float u = dot(p, mk(r0.w, r1.w, r2.x));
     if (!in_unit_range(u)) return;                 // RangeInclusive::contains: NaN rejected
     const float v = dot(p, mk(r2.y, r2.z, r2.w));
     if (v < 0.0f || u + v > 1.0f) return;
-#endif
     if (ANY) { id = 0; return; }
     if (ORDERED && t == closest && obj < id) return;
     closest = t;
@@ -167,33 +134,11 @@ template <bool ANY = false>
 PT_DEV void tripair_test(float4 r0, float4 r1, float4 r2, float4 r3, float4 r4, f3 o, f3 d, float t_min, float& closest, int& id, int obj) {
     const f3 n = mk(r0.x, r0.y, r0.z);
     const float det = dot(d, n);
-#if PT_PAIR_S_EARLY
-    // measurement variant: o - v0 before the determinant's test, so that v0 is requested together with the normal (one dependent LDS
-    // latency less per pair; three subtractions more for the waves whose rays are all parallel to the plane: none in practice)
-    f3 s = o - mk(r1.x, r1.y, r1.z);
-    asm volatile("" : "+v"(s.x), "+v"(s.y), "+v"(s.z));
-    if (__builtin_fabsf(det) < 1e-8f) return;
-#else
     if (__builtin_fabsf(det) < 1e-8f) return;
     const f3 s = o - mk(r1.x, r1.y, r1.z);
-#endif
     const float t = pt_div(-dot(s, n), det);
     if (t < t_min || t > closest) return;
     const f3 p = madd(d, t, s);
-#if PT_PAIR_FLAT
-    // measurement variant: both triangles' barycentric tests without branches (same predicates on the same values; a wave of
-    // incoherent rays nearly always has a lane inside each u range, so the branches skip little and cost scalar instructions)
-    {
-        const float u0 = dot(p, mk(r2.x, r2.y, r2.z)), v0 = dot(p, mk(r2.w, r3.x, r3.y));
-        const float u1 = dot(p, mk(r3.z, r3.w, r4.x)), v1 = dot(p, mk(r4.y, r4.z, r4.w));
-        const bool acc0 = (u0 >= 0.0f && u0 <= 1.0f) && !(v0 < 0.0f || u0 + v0 > 1.0f);
-        const bool acc1 = (u1 >= 0.0f && u1 <= 1.0f) && !(v1 < 0.0f || u1 + v1 > 1.0f);
-        if (ANY) { if (acc0 || acc1) id = 0; return; }
-        closest = (acc0 || acc1) ? t : closest;
-        id = acc1 ? obj + 1 : acc0 ? obj : id;
-        return;
-    }
-#endif
     const float u0 = dot(p, mk(r2.x, r2.y, r2.z));
     if (in_unit_range(u0)) {
         const float v0 = dot(p, mk(r2.w, r3.x, r3.y));
@@ -223,20 +168,6 @@ PT_DEV void sphere_pre(float4 s, f3 o, f3 d, float& half_b, float& disc) {
 }
 template <bool ANY>
 PT_DEV void sphere_post(float half_b, float disc, float t_min, float& closest, int& id, int obj) {
-#if PT_SPHERE_FLAT
-    // measurement variant: no branch on the discriminant (the root of a negative one is a NaN nobody reads)
-    {
-        const float sq = pt_sqrt(disc);
-        const float ra = -half_b - sq, rb = -half_b + sq;
-        const float cc = ra < t_min ? rb : ra;
-        const bool rej = disc < 0.0f || cc < t_min || closest < cc;
-        if (ANY) { id = rej ? id : 0; return; }
-        closest = rej ? closest : cc;
-        id = rej ? id : obj;
-        __builtin_amdgcn_sched_barrier(0);      // (one test after the other: interleaved, four of them need 30 registers more)
-        return;
-    }
-#endif
     if (disc < 0.0f) return;
     float sqrtd = pt_sqrt(disc);
     float root1 = -half_b - sqrtd;
@@ -258,7 +189,7 @@ PT_DEV float sphere_disc(float4 s, f3 o, f3 d) {
 // branch "did any lane hit any of the four?" instead of a divergent branch per sphere; the exact
 // sequential tests run only then.  max() drops NaNs unless all four are NaN, which is exactly the
 // NaN-ray case the reference lets through (Q10), so a NaN still reaches sphere_test.
-template <bool GROUPED, bool ANY = false, int PF = 0>      // PF: pair records requested ahead (PT_PAIR_PREFETCH; the split kernel only)
+template <bool GROUPED, bool ANY = false, bool PF = false>      // PF: the next pair's normal requested one pair ahead (the split kernel only)
 PT_DEV void scan_run(const float4* __restrict__ p, uint32_t tag, uint32_t n, int first_obj, f3 o, f3 d, float t_min,
                      float& closest, int& id) {
     if (tag == SHAPE_SPHERE) {
@@ -287,7 +218,6 @@ PT_DEV void scan_run(const float4* __restrict__ p, uint32_t tag, uint32_t n, int
             sphere_test<false, ANY>(s2, o, d, t_min, closest, id, first_obj + (int)i + 2);
             sphere_test<false, ANY>(s3, o, d, t_min, closest, id, first_obj + (int)i + 3);
         }
-#if PT_SPHERE_REM2
         // of the last (n mod 4) records two reads in flight at once instead of one read per test (round 5: C2's ten spheres are two
         // groups and two; launch 5.58 -> 5.52 ms, profiles/r05/ab_lds_latency.txt; three at once for n mod 4 = 3 spills four registers)
         if (!GROUPED && i + 2u <= n) {
@@ -298,7 +228,6 @@ PT_DEV void scan_run(const float4* __restrict__ p, uint32_t tag, uint32_t n, int
             sphere_post<ANY>(h1, d1, t_min, closest, id, first_obj + (int)i + 1);
             i += 2u;
         }
-#endif
         for (; i < n; ++i) sphere_test<false, ANY>(p[i], o, d, t_min, closest, id, first_obj + (int)i);
     } else if (tag == kRunTriangle) {
         for (uint32_t i = 0; i < n; ++i) {
@@ -306,14 +235,15 @@ PT_DEV void scan_run(const float4* __restrict__ p, uint32_t tag, uint32_t n, int
             triangle_test<false, ANY>(a0, a1, a2, o, d, t_min, closest, id, first_obj + (int)i);
         }
     } else {
-        if (PF > 0) {
+        if (PF) {
             // the next pair's plane normal is requested while this pair is tested (one of the three dependent LDS latencies of a pair
-            // test off the critical path, for three registers: kernels with registers to spare only -- k_paths_regen_split)
-            float4 a0n = p[0], a1n = p[1];
+            // test off the critical path, for three registers: kernels with registers to spare only -- k_paths_regen_split; round 5:
+            // C1 launch 7.16 -> 7.07 ms, profiles/r05/ab_lds_latency.txt)
+            float4 a0n = p[0];
             for (uint32_t i = 0; i < n; ++i) {
                 const float4 a0 = a0n;
-                float4 a1 = PF > 1 ? a1n : p[5 * i + 1];
-                if (i + 1u < n) { a0n = p[5 * i + 5]; if (PF > 1) a1n = p[5 * i + 6]; }
+                float4 a1 = p[5 * i + 1];
+                if (i + 1u < n) a0n = p[5 * i + 5];
                 float4 a2 = p[5 * i + 2], a3 = p[5 * i + 3], a4 = p[5 * i + 4];
                 tripair_test<ANY>(a0, a1, a2, a3, a4, o, d, t_min, closest, id, first_obj + 2 * (int)i);
             }
@@ -344,9 +274,6 @@ struct SceneRef {
     uint32_t n_runs, n_lights;
     BvhView bvh;
     uint32_t* stack;        // kModeBvh: LDS traversal stack, entry e of thread t at stack[e * kBlock + t]
-#if PT_RUN0_SGPR
-    Run run0;               // kModeLds: the first run record, read once per kernel into scalar registers (measured, round 5: C1 +1.7 %, C2 +0.3 %: rejected)
-#endif
 };
 template <int MODE>
 PT_DEV SceneRef stage_scene(const SceneView& sc, float4* lds) {
@@ -364,11 +291,6 @@ PT_DEV SceneRef stage_scene(const SceneView& sc, float4* lds) {
         r.mat = lds + sc.scan_f4 + 3u * sc.n_objs;
         r.runs = reinterpret_cast<const Run*>(lds + sc.scan_f4 + 5u * sc.n_objs);
         r.lights = reinterpret_cast<const uint32_t*>(lds + sc.scan_f4 + 5u * sc.n_objs + sc.n_runs);
-#if PT_RUN0_SGPR
-        r.run0 = r.runs[0];
-        r.run0.tag = __builtin_amdgcn_readfirstlane(r.run0.tag); r.run0.first_obj = __builtin_amdgcn_readfirstlane(r.run0.first_obj);
-        r.run0.count = __builtin_amdgcn_readfirstlane(r.run0.count); r.run0.off4 = __builtin_amdgcn_readfirstlane(r.run0.off4);
-#endif
     } else {
         r.scan = lds;
         r.shape = sc.shape; r.mat = sc.mat; r.runs = sc.runs; r.lights = sc.lights;
@@ -391,18 +313,13 @@ PT_DEV void scan_global(const SceneRef& sc, f3 o, f3 d, float t_min, float t_max
 // shrinking t_max.  kModeLds: the whole scan array already sits in LDS.  kModeTiled:
 // every run is streamed through one LDS tile; the loop is block-uniform (all
 // threads of the workgroup call this together, active or not).
-template <int MODE, bool ANY = false, int PF = 0>
+template <int MODE, bool ANY = false, bool PF = false>
 PT_DEV void scan_closest(const SceneRef& sc, f3 o, f3 d, float t_min, float t_max, int& id_out, float& t_out) {
     constexpr bool SMALL = MODE == kModeLds;
     float closest = t_max;
     int id = -1;
     for (uint32_t r = 0; r < sc.n_runs; ++r) {
-#if PT_RUN0_SGPR
-        Run run = sc.run0;
-        if (!SMALL || r != 0u) run = sc.runs[r];
-#else
         Run run = sc.runs[r];
-#endif
         // the run record is the same in every lane: keep it (and the loop counters and object indices derived
         // from it) in scalar registers
         run.tag = __builtin_amdgcn_readfirstlane(run.tag); run.first_obj = __builtin_amdgcn_readfirstlane(run.first_obj);
@@ -468,10 +385,6 @@ PT_DEV uint32_t image_row(const TileMap& t, uint32_t yl) {
 // ~30 000 atomics on ONE cache line per launch, serialised in L2 at the very end of the launch, where every microsecond is tail
 // (measured: the fifth word, the finished-sample count, alone cost 1.5 % of a C2 launch: profiles/r05/ab_count_finished.txt).
 // So the waves of a workgroup add up in LDS first and the LAST of them to end does the global atomics: a quarter of the traffic.
-#ifndef PT_WG_TOTALS
-#define PT_WG_TOTALS 1
-#endif
-
 struct WgTotals { uint32_t done, shadow, vertices, samples, dmax; };
 PT_DEV void wg_totals_init(WgTotals& t) {                 // by one thread, before the workgroup's first barrier
     t.done = 0u; t.shadow = 0u; t.vertices = 0u; t.samples = 0u; t.dmax = 0u;
@@ -480,7 +393,6 @@ PT_DEV void wg_totals_init(WgTotals& t) {                 // by one thread, befo
 template <bool MIS, bool PRIMARY = true>     // PRIMARY: a level-0 launch (its vertices also count as primary_vertices)
 PT_DEV void wave_totals(WgTotals& t, uint32_t waves_in_block, unsigned long long* stats, uint32_t shadow, uint32_t vertices,
                         uint32_t samples, uint32_t dmax) {
-#if PT_WG_TOTALS
     if (MIS && shadow != 0u) __hip_atomic_fetch_add(&t.shadow, shadow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (vertices != 0u) __hip_atomic_fetch_add(&t.vertices, vertices, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (samples != 0u) __hip_atomic_fetch_add(&t.samples, samples, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -491,7 +403,6 @@ PT_DEV void wave_totals(WgTotals& t, uint32_t waves_in_block, unsigned long long
     vertices = __hip_atomic_load(&t.vertices, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     samples = __hip_atomic_load(&t.samples, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     dmax = __hip_atomic_load(&t.dmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
     if (MIS && shadow != 0u) atomicAdd(&stats[0], (unsigned long long)shadow);
     if (vertices != 0u) atomicAdd(&stats[1], (unsigned long long)vertices);
     if (PRIMARY && vertices != 0u) atomicAdd(&stats[3], (unsigned long long)vertices);
@@ -873,9 +784,6 @@ k_paths(BounceArgs a) {
                 if (!first || active) unpack_carry(p, src.q[2][s1], src.q[3][s1]);
             }
         };
-#ifdef PT_EARLY_CARRY
-        load_carry();
-#endif
 
         wave_vertices += (uint32_t)__popcll(__ballot(active));
         // deepest vertex: in a level-0 launch every path of pass p is at depth p; only a continuation launch
@@ -890,7 +798,7 @@ k_paths(BounceArgs a) {
 
         // ---- scan #1: closest hit of the path ray (rendering.rs:41)
         int id; float t;
-        scan_closest<MODE, false, (MODE == kModeLds && !DIFFUSE) ? PT_PAIR_PREFETCH_GENERIC : 0>(sc, p.o, p.d, a.t_min, kInf, id, t);
+        scan_closest<MODE, false>(sc, p.o, p.d, a.t_min, kInf, id, t);
         Vertex v;
         vertex_begin<MIS, DIFFUSE>(sc, p, active, id, t, sample, kx, py, v);
 
@@ -904,17 +812,15 @@ k_paths(BounceArgs a) {
                 f3 sdir = v.need_shadow ? v.light_dir : parked_dir();
                 f3 sorg = v.need_shadow ? v.hit.point : parked_origin();
                 int sid; float st;
-                scan_closest<MODE, true, (MODE == kModeLds && !DIFFUSE) ? PT_PAIR_PREFETCH_GENERIC : 0>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);   // any-hit form
+                scan_closest<MODE, true>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);   // any-hit form
                 visible = v.need_shadow && sid < 0;
                 wave_shadow += (uint32_t)__popcll(__ballot(v.need_shadow));
             }
         }
         // ---- the carry part only now: none of it was needed -- or occupied a register -- during the two scans.
         // (The compiler barrier keeps the loads down here.)
-#ifndef PT_EARLY_CARRY
         asm volatile("" ::: "memory");
         load_carry();
-#endif
         const bool alive = vertex_end<MIS, DIFFUSE, SMALL>(sc, p, v, visible, sample, kx, py, a.min_depth, a.max_depth);
 
         // ---- retire, or compact in place into the wave's own segment
@@ -996,9 +902,6 @@ k_paths(BounceArgs a) {
 // over at the end): one scalar add per iteration on a number the loop computes anyway.  (Counting at the store itself was measured:
 // a per-lane count packed into the depth word cost 1.5 % on C2 -- profiles/r05/ab_count_finished.txt; a ballot per iteration
 // costs the split form two more spilled registers.)
-#ifndef PT_COUNT_FINISHED
-#define PT_COUNT_FINISHED 1      // 0: measurement variant without the count (pt_sync's check is compiled out with it: A/B of its cost only)
-#endif
 constexpr uint32_t kPool = 128;            // ring entries per wave (>= 2 chunks: refilled whenever fewer than 64 are left)
 // Workgroup size of k_paths_regen.  Its waves share nothing but the LDS copy of the scene, so a workgroup could be ONE wave --
 // a wave that ends would free a slot the next launch (pt_api.cpp, lanes) can take at once, where a four-wave workgroup needs
@@ -1008,21 +911,9 @@ constexpr uint32_t kPool = 128;            // ring entries per wave (>= 2 chunks
 #define PT_REGEN_BLOCK 256
 #endif
 constexpr uint32_t kRegenBlock = PT_REGEN_BLOCK;
-#ifndef PT_RING_LAZY
-#define PT_RING_LAZY 0
-#endif
 #ifndef PT_RESOLVE_UNROLL
 #define PT_RESOLVE_UNROLL 4     // k_resolve: samples whose loads are in flight together (32 VGPRs: what is free beside six 80-VGPR waves;
 #endif                          // 8 -> 56 VGPRs and C1 1.3 % slower; a raised wave priority: nothing.  profiles/r04/ab_resolve_variants.txt)
-#ifndef PT_DRAIN_MAIL
-#define PT_DRAIN_MAIL 0      // measured (round 4): N = 1 5.96 -> 6.17 ms (4 spilled dwords, the per-iteration checks), one rank's share at 8 ranks
-#endif                       // 0.955 -> 0.975 ms: pooling a workgroup's last paths in one wave buys nothing -- kept as a measurement variant
-#if PT_DRAIN_MAIL
-constexpr uint32_t kMailT = 16;            // a wave with at most this many live paths at the end of the batch donates them
-#endif
-#ifndef PT_DRAIN_PRIO
-#define PT_DRAIN_PRIO 0
-#endif
 // DIFFUSE = the material set the kernel is compiled for (kMatsDiffuse / kMatsNoMirror / kMatsAll); round 3 added the
 // middle one: a scene with OrenNayar but no Mirror surface (material.rs:166-296) takes this kernel too by default.
 // LIST (pt_render_adaptive's passes): the batch's paths come from a pixel list -- list slot pid % np, sample pid / np (the
@@ -1035,15 +926,6 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
     __shared__ uint32_t s_pool_s[kRegenBlock / 64][kPool];    // s_local << 16 (depth 0)
     __shared__ WgTotals s_totals;
     if (threadIdx.x == 0u) wg_totals_init(s_totals);
-#if PT_DRAIN_MAIL
-    // End of the batch: a wave left with a handful of paths hands them to a sibling wave of its workgroup and ends (see the
-    // main loop).  One region per donor wave, plane-major; cnt = entries published, head = entries taken (atomic), active =
-    // waves of the workgroup that have neither ended nor donated.
-    __shared__ float4 s_mail[kRegenBlock / 64][4][kMailT];
-    __shared__ uint32_t s_mail_cnt[kRegenBlock / 64], s_mail_head[kRegenBlock / 64], s_active;
-    if (threadIdx.x < kRegenBlock / 64) { s_mail_cnt[threadIdx.x] = 0u; s_mail_head[threadIdx.x] = 0u; }
-    if (threadIdx.x == 0u) s_active = kRegenBlock / 64;
-#endif
     // Spare workgroups (BounceArgs.posted): in a sequence of overlapping launches only the first core_blocks of a launch work -- two
     // launches then sit side by side and the third fills the slots the first frees while it runs dry -- but the LAST launches of
     // a sequence, and a launch on its own, would leave half of the device empty.  So every launch brings a full device's worth of
@@ -1074,9 +956,6 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
     uint32_t dmax = 0;                     // per lane: deepest vertex of the paths this lane finished
     PathState p = parked_state();
     bool alive = false;
-#if PT_DRAIN_MAIL
-    bool mail_spent = false;               // wave-uniform: this wave's mail region has been published once and withdrawn
-#endif
 #ifdef PT_DRAIN_TIMING      // measurement build: when does the batch run out under the waves, when does the last wave end
     const unsigned long long t_begin = wall_clock64();
     unsigned long long t_exhausted = 0ull;
@@ -1087,14 +966,7 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
         if (exhausted && t_exhausted == 0ull) t_exhausted = wall_clock64();
 #endif
         // ---- keep at least one chunk of camera rays in the ring
-#if PT_RING_LAZY
-        // ... or rather: only what the lanes without a path ask for now.  The ring then holds 0 .. 63 entries between
-        // refills instead of 64 .. 127, and what it holds when the batch runs out is work the wave has to do alone
-        const uint32_t ring_want = (uint32_t)__popcll(__ballot(!alive));
-        while (!exhausted && pool_cnt < ring_want) {
-#else
         while (!exhausted && pool_cnt < 64u) {
-#endif
             uint32_t chunk;
             if (st_next < a.regen_static) {            // dealt round-robin, like pass 0 of k_paths
                 chunk = st_next; st_next += nw;
@@ -1127,19 +999,6 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
             pool_cnt += valid;
         }
         __builtin_amdgcn_wave_barrier();
-#if PT_DRAIN_PRIO == 1
-        // end of the batch: the waves with the most work left go first (they end the launch)
-        if (exhausted) {
-            if (pool_cnt >= 32u) __builtin_amdgcn_s_setprio(3);
-            else if (pool_cnt != 0u) __builtin_amdgcn_s_setprio(2);
-            else __builtin_amdgcn_s_setprio(1);
-        }
-#elif PT_DRAIN_PRIO == 2
-        // a wave with fresh work goes before a wave that runs dry (of this launch or of the previous one, beside which this
-        // launch starts: pt_api.cpp, lanes): an issue slot spent on 64 live lanes does more than one spent on a few
-        if (exhausted && pool_cnt == 0u) __builtin_amdgcn_s_setprio(0);
-        else __builtin_amdgcn_s_setprio(2);
-#endif
         // ---- lanes without a path take the ring's next entries, in lane order
         {
             const unsigned long long need = __ballot(!alive);
@@ -1159,82 +1018,10 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
             const uint32_t n_need = (uint32_t)__popcll(need);
             const uint32_t n_take = n_need < pool_cnt ? n_need : pool_cnt;
             pool_head += n_take; pool_cnt -= n_take;
-            if (PT_COUNT_FINISHED) wave_taken += n_take;
+            wave_taken += n_take;
         }
         __builtin_amdgcn_wave_barrier();
-#if PT_DRAIN_MAIL
-        // ---- end of the batch, nothing left in the ring: the workgroup's waves pool their last paths.
-        // A wave with at most kMailT live paths publishes them in its region and ends; a sibling with free lanes takes them.
-        // No wave ever waits: a donor publishes BEFORE it leaves the count of active waves, and every wave looks at the mail
-        // once more AFTER it has left that count (and comes back if there is some) -- so whichever of two leaves first, the
-        // other one sees either the mail or that it is the last wave, which keeps (takes back) its paths.
-        const bool mail_phase = a.export_below <= 1u && exhausted && pool_cnt == 0u;
-        if (mail_phase) {
-            const unsigned long long freem = __ballot(!alive);
-            uint32_t n_free = (uint32_t)__popcll(freem);
-            const uint32_t my_rank = lane_rank(freem);
-            uint32_t taken = 0;
-            for (uint32_t r = 0; r < kRegenBlock / 64; ++r) {
-                if (r == wib || n_free == taken) continue;
-                const uint32_t cnt = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_mail_cnt[r], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-                const uint32_t head = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_mail_head[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-                if (cnt <= head) continue;
-                const uint32_t want = cnt - head < n_free - taken ? cnt - head : n_free - taken;
-                uint32_t old = 0;
-                if (lane == 0u) old = __hip_atomic_fetch_add(&s_mail_head[r], want, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-                old = __builtin_amdgcn_readfirstlane(old);
-                const uint32_t got = old < cnt ? (cnt - old < want ? cnt - old : want) : 0u;
-                if (!alive && my_rank >= taken && my_rank < taken + got) {
-                    const uint32_t e = old + (my_rank - taken);
-                    p = unpack_state(s_mail[r][0][e], s_mail[r][1][e], s_mail[r][2][e], s_mail[r][3][e]);
-                    alive = true;
-                }
-                taken += got;
-            }
-        }
-        uint32_t n_alive = (uint32_t)__popcll(__ballot(alive));
-        // (a wave that once had to take its mail back -- mail_spent -- traces its paths to their end)
-        if (mail_phase && n_alive <= kMailT && !(mail_spent && n_alive != 0u)) {
-            if (n_alive != 0u) {                         // publish, then leave
-                const unsigned long long am = __ballot(alive);
-                if (alive) {
-                    const uint32_t e = lane_rank(am);
-                    s_mail[wib][0][e] = make_float4(p.o.x, p.o.y, p.o.z, p.d.x);
-                    s_mail[wib][1][e] = make_float4(p.d.y, p.d.z, __uint_as_float((p.yl << 16) | p.px), __uint_as_float((p.s_local << 16) | p.depth));
-                    s_mail[wib][2][e] = make_float4(p.beta.x, p.beta.y, p.beta.z, p.pdf_prev);
-                    s_mail[wib][3][e] = make_float4(p.L.x, p.L.y, p.L.z, p.eta_in);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if (lane == 0u) __hip_atomic_store(&s_mail_cnt[wib], n_alive, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            uint32_t prev = 0;
-            if (lane == 0u) prev = __hip_atomic_fetch_sub(&s_active, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-            prev = __builtin_amdgcn_readfirstlane(prev);
-            // mail of the others that nobody has taken yet?  (also after a donation: it must not be the last look anybody takes)
-            bool pending = false;
-            for (uint32_t r = 0; r < kRegenBlock / 64; ++r)
-                if (r != wib) pending = pending || __hip_atomic_load(&s_mail_cnt[r], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >
-                                                       __hip_atomic_load(&s_mail_head[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            pending = __builtin_amdgcn_readfirstlane(pending ? 1u : 0u) != 0u;
-            if (n_alive != 0u && prev > 1u && !pending) { alive = false; break; }      // donated: a sibling is (still) there to take them
-            if (n_alive == 0u && !pending) break;                                        // nothing left anywhere this wave could see
-            // stay: the last wave keeps its paths (takes its own mail back), or there is mail to take in the next iteration
-            if (lane == 0u) __hip_atomic_fetch_add(&s_active, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (n_alive != 0u) {
-                // un-publish what nobody took (a sibling may have taken some in the meantime: those lanes' paths are gone)
-                uint32_t old = 0;
-                if (lane == 0u) old = __hip_atomic_fetch_add(&s_mail_head[wib], n_alive, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-                old = __builtin_amdgcn_readfirstlane(old);             // entries [0, old) were taken by siblings, [old, n_alive) come back
-                const unsigned long long am = __ballot(alive);
-                if (alive && lane_rank(am) < old) { alive = false; p.o = parked_origin(); p.d = parked_dir(); }
-                mail_spent = true;                       // the region is used up for good (cnt <= head from now on)
-            }
-            n_alive = (uint32_t)__popcll(__ballot(alive));
-            if (n_alive == 0u) continue;                 // only mail to fetch: next iteration
-        }
-#else
         const uint32_t n_alive = (uint32_t)__popcll(__ballot(alive));
-#endif
         // running dry (only once the batch is exhausted): hand the rest over
         if (n_alive < a.export_below) break;           // export_below >= 1: a wave without paths ends
 
@@ -1246,7 +1033,7 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
 
         // ---- scan #1: closest hit of the path ray (rendering.rs:41)
         int id; float t;
-        scan_closest<kModeLds, false, DIFFUSE == kMatsDiffuse ? 0 : PT_PAIR_PREFETCH_GENERIC>(sc, p.o, p.d, a.t_min, kInf, id, t);
+        scan_closest<kModeLds, false>(sc, p.o, p.d, a.t_min, kInf, id, t);
         Vertex v;
         vertex_begin<MIS, DIFFUSE>(sc, p, active, id, t, sample, kx, py, v);
 
@@ -1258,7 +1045,7 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
                 f3 sdir = v.need_shadow ? v.light_dir : parked_dir();
                 f3 sorg = v.need_shadow ? v.hit.point : parked_origin();
                 int sid; float st;
-                scan_closest<kModeLds, true, DIFFUSE == kMatsDiffuse ? 0 : PT_PAIR_PREFETCH_GENERIC>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);
+                scan_closest<kModeLds, true>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);
                 visible = v.need_shadow && sid < 0;
                 wave_shadow += (uint32_t)__popcll(sm);
             }
@@ -1285,7 +1072,7 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
                 dmax = done > dmax ? done : dmax;
             }
         }
-        wave_taken -= n_left;              // (mail pooling, a measurement variant, moves paths between waves: the launch's sum stays right)
+        wave_taken -= n_left;
     }
     const uint32_t wave_samples = wave_taken;
     for (int off = 32; off > 0; off >>= 1) { const uint32_t w2 = (uint32_t)__shfl_xor((int)dmax, off); dmax = w2 > dmax ? w2 : dmax; }
@@ -1322,7 +1109,7 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
 // Both stacks share one 128-entry region per wave in global memory (L2-resident: 10 KB per wave), special growing up, plain
 // growing down.  They cannot collide.  Let S, P be the entries of the two stacks.  At the top of an iteration S <= 63 (batches
 // run whenever >= 64 specials wait).  A plain iteration finds f <= 64 Mirror vertices; each of the first min(f, P) takes an
-// entry OFF the plain stack as it puts one ON the special stack (PT_SPLIT_REPLACE, round 5: S + P unchanged), the others push
+// entry OFF the plain stack as it puts one ON the special stack (round 5: S + P unchanged), the others push
 // with the plain stack empty, so afterwards S + P <= max(S + P before, 63 + 64).  A batch takes 64 entries off the special
 // stack and puts at most 64 back on either: S + P does not grow.  Hence S + P <= 127 < 128 always.  (Round 3-4 form, without
 // the replacement: lanes take plain entries before camera rays, so a push finds the plain stack empty.)  No atomics, no other
@@ -1333,21 +1120,7 @@ constexpr int kWaitVm0 = 0x0F70;                                 // s_waitcnt vm
 constexpr uint32_t kXq = 128;                                    // exchange entries per wave
 constexpr uint32_t kXqEntryF4 = 5;                               // stack entry: 4 float4 of path state (layout of Queue) + (bits(id), t, -, -)
 constexpr uint32_t kXqF4PerWave = kXq * kXqEntryF4;               // the stacks (round 3 also parked the wave's 64 plain paths here: LDS since round 4, ab_c1_park_in_lds.txt)
-#ifndef PT_SPLIT_REPLACE
-#define PT_SPLIT_REPLACE 1       // measured (round 5): 7.40 -> 7.30 ms per C1 launch -- profiles/r05/ab_c1_replace_flat.txt, ab_noslp.txt
-#endif
-#ifndef PT_SPLIT_BATCH_MATS
-#define PT_SPLIT_BATCH_MATS kMatsAll      // kMatsMirror: the batch's vertex code compiled for Mirror hits only (measurement)
-#endif
-#ifndef PT_SPLIT_STAY
-#define PT_SPLIT_STAY 0          // measured (round 5): 7.52 -> 7.62 ms per C1 launch at every threshold tried -- profiles/r05/ab_c1_stay_in_lane.txt
-#endif
-#ifndef PT_SPLIT_STAY_MIN
-#define PT_SPLIT_STAY_MIN 32
-#endif
-#if PT_SPLIT_STAY
-constexpr uint32_t kSplitStayMin = PT_SPLIT_STAY_MIN;             // a batch goes on while at least this many specials are in lanes + waiting
-#endif
+constexpr bool kSplitPairPrefetch = true;                          // scan_run's PF in this kernel (registers to spare)
 static_assert(kXqF4PerWave == kRegenSplitF4PerWave, "pt_kernels.h sizes the buffer");
 // One wave-uniform base pointer (two scalar registers); entry-major, so the planes of an entry are immediate offsets of
 // ONE address -- with plane-major arrays the compiler kept a scalar base per plane (24 SGPRs more than the kernel has).
@@ -1441,26 +1214,18 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
             pool_cnt += valid;
         }
         __builtin_amdgcn_wave_barrier();
-        // ---- lanes without a path: first the plain stack (paths that left a Mirror surface), then the ring
-        // (PT_SPLIT_REPLACE: the ring first -- what waits on the plain stack has its next vertex scanned already and takes the place
-        // of the lanes that find a Mirror vertex below; the lanes here take it only when the ring cannot serve them: the end of the batch)
+        // ---- lanes without a path: first the ring, then the plain stack (paths that left a Mirror surface).  What waits on the plain
+        // stack has its next vertex scanned already and takes the place of the lanes that find a Mirror vertex below; the lanes here
+        // take it only when the ring cannot serve them: the end of the batch
         {
             const unsigned long long need = __ballot(!alive);
             const uint32_t r = lane_rank(need);
             const uint32_t n_need = (uint32_t)__popcll(need);
-#if PT_SPLIT_REPLACE
             const uint32_t n_ring = n_need < pool_cnt ? n_need : pool_cnt;
             const uint32_t n_pq = n_need - n_ring < pq_cnt ? n_need - n_ring : pq_cnt;
             const bool from_pq = !alive && r >= n_ring && r - n_ring < n_pq;
             const bool from_ring = !alive && r < n_ring;
             const uint32_t e_pq = kXq - pq_cnt + (r - n_ring), e_ring = (pool_head + r) & (kPool - 1u);
-#else
-            const uint32_t n_pq = n_need < pq_cnt ? n_need : pq_cnt;
-            const uint32_t n_ring = n_need - n_pq < pool_cnt ? n_need - n_pq : pool_cnt;
-            const bool from_pq = !alive && r < n_pq;
-            const bool from_ring = !alive && r >= n_pq && r - n_pq < pool_cnt;
-            const uint32_t e_pq = kXq - pq_cnt + r, e_ring = (pool_head + r - n_pq) & (kPool - 1u);
-#endif
             if (from_pq) {
                 const float4* src = x.entry(e_pq);
                 p = unpack_state(src[0], src[1], src[2], src[3]);
@@ -1483,7 +1248,7 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
             }
             pq_cnt -= n_pq;
             pool_head += n_ring; pool_cnt -= n_ring;
-            if (PT_COUNT_FINISHED) wave_taken += n_ring;
+            wave_taken += n_ring;
         }
         __builtin_amdgcn_wave_barrier();
         const uint32_t n_alive = (uint32_t)__popcll(__ballot(alive));
@@ -1493,12 +1258,11 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
         if (n_alive != 0u) {
             // ---- plain iteration: scan #1 (rendering.rs:41)
             int id; float t;
-            scan_closest<kModeLds, false, PT_PAIR_PREFETCH>(sc, p.o, p.d, a.t_min, kInf, id, t);
+            scan_closest<kModeLds, false, kSplitPairPrefetch>(sc, p.o, p.d, a.t_min, kInf, id, t);
             // a Mirror vertex is not shaded here: the path waits on the special stack for a batch of its kind
             const bool special = alive && id >= 0 && is_mirror_obj(sc, id);
             const unsigned long long spm = __ballot(special);
             if (spm != 0ull) {
-#if PT_SPLIT_REPLACE
                 // Round 5: a lane that hands its path to the special stack takes, in the same breath, a path from the plain stack --
                 // one that left the glass in an earlier batch, whose next vertex that batch has scanned already: (id, t) travel with
                 // the entry.  The lane goes on with vertex_begin at once instead of idling through the rest of the iteration, and the
@@ -1521,7 +1285,7 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
                 if (special) {
                     float4* dst = x.entry(sq_cnt + rk);
                     store_entry(dst, p);
-                    *reinterpret_cast<float2*>(dst + 4) = make_float2(__int_as_float(id), t);
+                    *reinterpret_cast<float2*>(dst + 4) = make_float2(__int_as_float(id), t);     // (8 of the slot's 16 bytes: no padding words to keep in registers)
                     if (rep) {
                         p = q; id = qid; t = qt;
                     } else {
@@ -1532,17 +1296,6 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
                 }
                 sq_cnt += n_sp;
                 pq_cnt -= n_rep;
-#else
-                if (special) {
-                    float4* dst = x.entry(sq_cnt + lane_rank(spm));
-                    store_entry(dst, p);
-                    *reinterpret_cast<float2*>(dst + 4) = make_float2(__int_as_float(id), t);     // (8 of the slot's 16 bytes: no padding words to keep in registers)
-                    alive = false;
-                    p.o = parked_origin(); p.d = parked_dir();
-                    id = -1;
-                }
-                sq_cnt += (uint32_t)__popcll(spm);
-#endif
                 overflow = overflow || sq_cnt + pq_cnt > kXq;
             }
             const bool active = alive;
@@ -1558,7 +1311,7 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
                     f3 sdir = v.need_shadow ? v.light_dir : parked_dir();
                     f3 sorg = v.need_shadow ? v.hit.point : parked_origin();
                     int sid; float st;
-                    scan_closest<kModeLds, true, PT_PAIR_PREFETCH>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);
+                    scan_closest<kModeLds, true, kSplitPairPrefetch>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);
                     visible = v.need_shadow && sid < 0;
                     wave_shadow += (uint32_t)__popcll(sm);
                 }
@@ -1582,82 +1335,6 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
             park[2][lane] = make_float4(p.beta.x, p.beta.y, p.beta.z, p.pdf_prev);
             park[3][lane] = make_float4(p.L.x, p.L.y, p.L.z, p.eta_in);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");     // entries pushed above are read by other lanes below
-#if PT_SPLIT_STAY
-            // Round 5: a path whose NEXT vertex is Mirror again (it is inside the glass sphere: most of what a batch refracts)
-            // STAYS in its lane with the scan's (id, t) and is shaded by the next iteration of this loop, where the lanes the
-            // others freed take what still waits on the stack.  Round 4 pushed it (80 B written) and popped it again in a later
-            // batch (80 B read): a third of the form's stack traffic, and a dozen plain iterations of latency for the path.
-            PathState q = parked_state();
-            bool qa = false;                                           // this lane carries a special waiting for its vertex
-            int qid = -1; float qt = 0.0f;
-            uint32_t n_stay = 0;                                       // wave-uniform: lanes with qa
-            do {
-                {   // lanes without a special take the top entries of the special stack, in lane order
-                    const unsigned long long need = __ballot(!qa);
-                    const uint32_t r = lane_rank(need);
-                    const uint32_t n_need = (uint32_t)__popcll(need);
-                    const uint32_t n_pop = n_need < sq_cnt ? n_need : sq_cnt;
-                    if (!qa && r < n_pop) {
-                        const float4* src = x.entry(sq_cnt - 1u - r);
-                        q = unpack_state(src[0], src[1], src[2], src[3]);
-                        const float2 it = *reinterpret_cast<const float2*>(src + 4);
-                        qid = __float_as_int(it.x); qt = it.y;
-                        qa = true;
-                    }
-                    sq_cnt -= n_pop;
-                    n_stay += n_pop;
-                }
-                if (!qa) { q.o = parked_origin(); q.d = parked_dir(); qid = -1; }
-                const uint32_t kx = q.px, py = image_row(a.tile, q.yl);
-                const uint32_t sample = a.s_base + q.s_local;
-                wave_vertices += n_stay;
-                Vertex v;
-                vertex_begin<MIS, PT_SPLIT_BATCH_MATS>(sc, q, qa, qid, qt, sample, kx, py, v);
-                bool visible = false;
-                if (MIS) {
-                    const unsigned long long sm = __ballot(v.need_shadow);
-                    if (sm != 0ull) {
-                        f3 sdir = v.need_shadow ? v.light_dir : parked_dir();
-                        f3 sorg = v.need_shadow ? v.hit.point : parked_origin();
-                        int sid; float st;
-                        scan_closest<kModeLds, true, PT_PAIR_PREFETCH>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);
-                        visible = v.need_shadow && sid < 0;
-                        wave_shadow += (uint32_t)__popcll(sm);
-                    }
-                }
-                const bool qalive = vertex_end<MIS, PT_SPLIT_BATCH_MATS, true>(sc, q, v, visible, sample, kx, py, a.min_depth, a.max_depth);
-                if (qa && !qalive) {
-                    a.lsamp[q.s_local * a.np + q.yl * W + q.px] = Rgb{q.L.x, q.L.y, q.L.z};
-                    dmax = q.depth > dmax ? q.depth : dmax;
-                }
-                // the survivors' next vertex: Mirror again or not?
-                const f3 so = qalive ? q.o : parked_origin(), sd = qalive ? q.d : parked_dir();
-                asm volatile("" ::: "memory");
-                int id2; float t2;
-                scan_closest<kModeLds, false, PT_PAIR_PREFETCH>(sc, so, sd, a.t_min, kInf, id2, t2);
-                const bool spec2 = qalive && id2 >= 0 && is_mirror_obj(sc, id2);
-                const bool plain2 = qalive && !spec2;
-                const unsigned long long m_p = __ballot(plain2);
-                const uint32_t n_p = (uint32_t)__popcll(m_p);
-                if (plain2) store_entry(x.entry(kXq - pq_cnt - n_p + lane_rank(m_p)), q);
-                pq_cnt += n_p;
-                qa = spec2; qid = id2; qt = t2;
-                n_stay = (uint32_t)__popcll(__ballot(spec2));
-                overflow = overflow || sq_cnt + pq_cnt + n_stay > kXq;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            } while (n_stay + sq_cnt >= kSplitStayMin || (n_stay + sq_cnt != 0u && !plain_work()));
-            // what stays below the threshold waits on the special stack for the next batch, like a special a plain iteration found
-            if (n_stay != 0u) {
-                const unsigned long long m_s = __ballot(qa);
-                if (qa) {
-                    float4* de = x.entry(sq_cnt + lane_rank(m_s));
-                    store_entry(de, q);
-                    *reinterpret_cast<float2*>(de + 4) = make_float2(__int_as_float(qid), qt);
-                }
-                sq_cnt += n_stay;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            }
-#else
             do {
                 const uint32_t n = sq_cnt < 64u ? sq_cnt : 64u;
                 const bool qa = lane < n;
@@ -1675,7 +1352,7 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
                 const uint32_t sample = a.s_base + q.s_local;
                 wave_vertices += n;
                 Vertex v;
-                vertex_begin<MIS, PT_SPLIT_BATCH_MATS>(sc, q, qa, qid, qt, sample, kx, py, v);
+                vertex_begin<MIS, kMatsAll>(sc, q, qa, qid, qt, sample, kx, py, v);
                 bool visible = false;
                 if (MIS) {
                     const unsigned long long sm = __ballot(v.need_shadow);
@@ -1683,12 +1360,12 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
                         f3 sdir = v.need_shadow ? v.light_dir : parked_dir();
                         f3 sorg = v.need_shadow ? v.hit.point : parked_origin();
                         int sid; float st;
-                        scan_closest<kModeLds, true, PT_PAIR_PREFETCH>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);
+                        scan_closest<kModeLds, true, kSplitPairPrefetch>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);
                         visible = v.need_shadow && sid < 0;
                         wave_shadow += (uint32_t)__popcll(sm);
                     }
                 }
-                const bool qalive = vertex_end<MIS, PT_SPLIT_BATCH_MATS, true>(sc, q, v, visible, sample, kx, py, a.min_depth, a.max_depth);
+                const bool qalive = vertex_end<MIS, kMatsAll, true>(sc, q, v, visible, sample, kx, py, a.min_depth, a.max_depth);
                 if (qa && !qalive) {
                     a.lsamp[q.s_local * a.np + q.yl * W + q.px] = Rgb{q.L.x, q.L.y, q.L.z};
                     dmax = q.depth > dmax ? q.depth : dmax;
@@ -1697,7 +1374,7 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
                 const f3 so = qalive ? q.o : parked_origin(), sd = qalive ? q.d : parked_dir();
                 asm volatile("" ::: "memory");
                 int id2; float t2;
-                scan_closest<kModeLds, false, PT_PAIR_PREFETCH>(sc, so, sd, a.t_min, kInf, id2, t2);
+                scan_closest<kModeLds, false, kSplitPairPrefetch>(sc, so, sd, a.t_min, kInf, id2, t2);
                 const bool spec2 = qalive && id2 >= 0 && is_mirror_obj(sc, id2);
                 const bool plain2 = qalive && !spec2;
                 const unsigned long long m_s = __ballot(spec2), m_p = __ballot(plain2);
@@ -1706,14 +1383,13 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
                     const uint32_t dst = spec2 ? sq_cnt + lane_rank(m_s) : kXq - pq_cnt - n_p + lane_rank(m_p);
                     float4* de = x.entry(dst);
                     store_entry(de, q);
-                    if (spec2 || PT_SPLIT_REPLACE) *reinterpret_cast<float2*>(de + 4) = make_float2(__int_as_float(id2), t2);
+                    *reinterpret_cast<float2*>(de + 4) = make_float2(__int_as_float(id2), t2);
                 }
                 sq_cnt += (uint32_t)__popcll(m_s);
                 pq_cnt += n_p;
                 overflow = overflow || sq_cnt + pq_cnt > kXq;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             } while (sq_cnt >= 64u || (sq_cnt != 0u && !plain_work()));
-#endif
             p = unpack_state(park[0][lane], park[1][lane], park[2][lane], park[3][lane]);
         }
     }
@@ -1742,15 +1418,9 @@ __global__ void __launch_bounds__(kBlock, kRegenWavesSplit) k_paths_regen_split(
 // with has_ray == 0 is skipped; t_max itself may be anything, also negative or NaN -- the scan's semantics
 // decide), else plane1[slot] = (d.y, d.z, -, -) and t_max = inf.  ANY: out[slot].z = 1 if anything is hit, else 0 (visibility).  Otherwise
 // out[slot].xy = (id, t) of the closest hit.  Semantics of one ray: bvh_scan.
-#ifndef PT_BVH_POSTPONE
-#define PT_BVH_POSTPONE 1
-#endif
-// order: null, or the order in which the slots are handed out -- order[k].w holds (as bits) the slot of the k-th ray
-// (sort_segment below); results still land in out[slot].
 template <bool TMAX_IN_RAY, bool ANY>
 PT_DEV void traverse_segment(const SceneRef& sc, const float4* __restrict__ plane0, const float4* __restrict__ plane1,
-                             float4* __restrict__ out, uint32_t n, float t_min, uint32_t refill_below, uint32_t leaf_batch,
-                             const float4* order = nullptr) {
+                             float4* __restrict__ out, uint32_t n, float t_min, uint32_t refill_below, uint32_t leaf_batch) {
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long lt = (1ull << lane) - 1ull;
     uint32_t* stk = sc.stack + threadIdx.x;
@@ -1767,16 +1437,13 @@ PT_DEV void traverse_segment(const SceneRef& sc, const float4* __restrict__ plan
     const f3 gcell = mk(sc.bvh.grid_cell[0], sc.bvh.grid_cell[1], sc.bvh.grid_cell[2]);
     float closest = 0.0f;
     int id = -1;
-#if PT_BVH_POSTPONE
     uint32_t pend = 0xFFFFFFFFu;                // a leaf this lane has put aside (none: the sentinel)
-#endif
     for (;;) {
         // ---- hand the next slots to the idle lanes, in lane order
         const unsigned long long idle = __ballot(!has);
         if (next < n && idle != 0ull) {
             uint32_t cand = next + (uint32_t)__popcll(idle & lt);
             if (!has && cand < n) {
-                if (order) cand = __float_as_uint(order[cand].w);
                 const float4 r0 = plane0[cand], r1 = plane1[cand];
                 const float t_max = TMAX_IN_RAY ? r1.z : kInf;
                 if (!TMAX_IN_RAY || r1.w != 0.0f) {
@@ -1859,7 +1526,6 @@ PT_DEV void traverse_segment(const SceneRef& sc, const float4* __restrict__ plan
                     node = stk[sp * kBlock];
                 }
             }
-#if PT_BVH_POSTPONE
             // A lane that reaches a leaf puts it aside (one per lane) and goes on with its stack: it keeps working on inner
             // nodes while the wave collects enough leaves for a dense batch of primitive tests.  (The tests run later than
             // in stack order, so `closest` may shrink later: a few more visits, never another answer.)
@@ -1870,10 +1536,6 @@ PT_DEV void traverse_segment(const SceneRef& sc, const float4* __restrict__ plan
             }
             const bool at_leaf = has && pend != 0xFFFFFFFFu;
             const uint32_t leaf = pend;
-#else
-            const bool at_leaf = has && (int)node < 0 && node != 0xFFFFFFFFu;
-            const uint32_t leaf = node;
-#endif
             const unsigned long long leafs = __ballot(at_leaf);
             if (leafs != 0ull && ((uint32_t)__popcll(leafs) >= leaf_batch || __ballot(has && (int)node >= 0) == 0ull)) {
                 if (at_leaf) {
@@ -1897,24 +1559,11 @@ PT_DEV void traverse_segment(const SceneRef& sc, const float4* __restrict__ plan
                             }
                         }
                     }
-#if PT_BVH_POSTPONE
                     pend = 0xFFFFFFFFu;
                     if (ANY && id >= 0) node = 0xFFFFFFFFu;
-#else
-                    if (ANY && id >= 0) {
-                        node = 0xFFFFFFFFu;
-                    } else {
-                        --sp;
-                        node = stk[sp * kBlock];
-                    }
-#endif
                 }
             }
-#if PT_BVH_POSTPONE
             if (has && node == 0xFFFFFFFFu && pend == 0xFFFFFFFFu) {   // this ray is done
-#else
-            if (has && node == 0xFFFFFFFFu) {            // this ray is done
-#endif
                 if (ANY) out[slot].z = id >= 0 ? 1.0f : 0.0f;
                 else *reinterpret_cast<float2*>(&out[slot]) = make_float2(__int_as_float(id), closest);
                 has = false;
@@ -1923,63 +1572,18 @@ PT_DEV void traverse_segment(const SceneRef& sc, const float4* __restrict__ plan
     }
 }
 
-// Rays that share a wave should look alike: the lanes of a wave take the segment's rays in handing-out
-// order, so that order is made one of similar rays -- a counting sort of the wave's segment by a 6-bit key, direction octant
-// (the order in which a traversal visits the children of a node) x octant of the origin about the scene's centre.  Two
-// passes over the ray planes: histogram in LDS, wave-wide exclusive prefix, then every slot takes the next position of its
-// bucket (LDS atomic; the order inside a bucket is whatever the atomics give -- results are written by slot and the film by
-// pixel, so nothing depends on it).  The order goes into the spare .w of the per-slot result records (aux), which the
-// traversal does not touch.  Slots without a ray (shadow stage) sort into the last bucket; the traversal skips them as before.
-#ifndef PT_BVH_SORT
-#define PT_BVH_SORT 0        // measured (round 4, C4 accel 1, ms per launch): no sort 48.1, closest-hit stage sorted 50.4, both stages 53.0 -- rejected, kept as a measurement variant (1: stage 1, 2: both)
-#endif
-template <bool TMAX_IN_RAY>
-PT_DEV void sort_segment(const SceneRef& sc, const float4* __restrict__ plane0, const float4* __restrict__ plane1, float4* __restrict__ aux,
-                         uint32_t n, uint32_t* hist) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const f3 ctr = mk(__builtin_fmaf(32767.5f, sc.bvh.grid_cell[0], sc.bvh.grid_min[0]), __builtin_fmaf(32767.5f, sc.bvh.grid_cell[1], sc.bvh.grid_min[1]),
-                      __builtin_fmaf(32767.5f, sc.bvh.grid_cell[2], sc.bvh.grid_min[2]));
-    auto key_of = [&](uint32_t s) -> uint32_t {
-        const float4 r0 = plane0[s], r1 = plane1[s];
-        if (TMAX_IN_RAY && r1.w == 0.0f) return 63u;
-        return (r0.w < 0.0f ? 1u : 0u) | (r1.x < 0.0f ? 2u : 0u) | (r1.y < 0.0f ? 4u : 0u) |
-               (r0.x > ctr.x ? 8u : 0u) | (r0.y > ctr.y ? 16u : 0u) | (r0.z > ctr.z ? 32u : 0u);
-    };
-    hist[lane] = 0u;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    for (uint32_t s = lane; s < n; s += 64u) atomicAdd(&hist[key_of(s)], 1u);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    // exclusive prefix over the 64 buckets, one bucket per lane
-    uint32_t v = hist[lane], incl = v;
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, off); if ((int)lane >= off) incl += up; }
-    __builtin_amdgcn_wave_barrier();
-    hist[lane] = incl - v;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    for (uint32_t s = lane; s < n; s += 64u) {
-        const uint32_t pos = atomicAdd(&hist[key_of(s)], 1u);
-        aux[pos].w = __uint_as_float(s);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 #ifndef PT_BVH_WAVES
 #define PT_BVH_WAVES 5      // measured on C4: 4 -> 74.0 ms, 5 -> 70.2 ms, 6 (spills) -> 72.8 ms
 #endif
 template <bool MIS, bool OVF, bool DIFFUSE, bool LIST>
 __global__ void __launch_bounds__(kBlock, PT_BVH_WAVES) k_paths_bvh(BounceArgs a) {
     extern __shared__ float4 lds[];
-    __shared__ uint32_t s_hist[kBlock / 64][64];                 // sort_segment: bucket counters of each wave
     __shared__ WgTotals s_totals;
     if (threadIdx.x == 0u) wg_totals_init(s_totals);
     __syncthreads();                                             // (the traversal form has no barrier of its own before a wave can end)
     const SceneRef sc = stage_scene<kModeBvh>(a.sc, lds);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    uint32_t* const hist = s_hist[threadIdx.x >> 6];
     const uint32_t nw = gridDim.x * (kBlock / 64);
     uint32_t n_first, seg_cap;
     launch_shape<OVF>(a, nw, n_first, seg_cap);
@@ -2019,10 +1623,7 @@ __global__ void __launch_bounds__(kBlock, PT_BVH_WAVES) k_paths_bvh(BounceArgs a
     for (uint32_t pass = 0; n_in != 0u; ++pass) {
         const uint32_t n_iter = (n_in + 63u) >> 6;
         // ---- stage 1: closest hits (rendering.rs:41)
-        // (the camera rays of pass 0 of a level-0 launch are consecutive pixels already)
-        const bool sorted = PT_BVH_SORT && (OVF || pass != 0u) && n_in > 64u;
-        if (sorted) sort_segment<false>(sc, q.q[0], q.q[1], aux, n_in, hist);
-        traverse_segment<false, false>(sc, q.q[0], q.q[1], aux, n_in, a.t_min, a.bvh_refill, a.bvh_leaf, sorted ? aux : nullptr);
+        traverse_segment<false, false>(sc, q.q[0], q.q[1], aux, n_in, a.t_min, a.bvh_refill, a.bvh_leaf);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         if (MIS) {
             // ---- stage 2: light samples -> shadow rays (world.rs:251-267, rendering.rs:58-62)
@@ -2044,9 +1645,7 @@ __global__ void __launch_bounds__(kBlock, PT_BVH_WAVES) k_paths_bvh(BounceArgs a
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             // ---- stage 3: visibility (rendering.rs:62-65)
-            const bool ssorted = PT_BVH_SORT >= 2 && n_in > 64u;
-            if (ssorted) sort_segment<true>(sc, sr0, sr1, aux, n_in, hist);
-            traverse_segment<true, true>(sc, sr0, sr1, aux, n_in, a.t_min, a.bvh_refill, a.bvh_leaf, ssorted ? aux : nullptr);
+            traverse_segment<true, true>(sc, sr0, sr1, aux, n_in, a.t_min, a.bvh_refill, a.bvh_leaf);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         }
         // ---- stage 4: shade and compact in place
