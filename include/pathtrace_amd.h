@@ -374,6 +374,15 @@ int pt_debug_sched_render(PtSched* s, const PtSchedJob* job, uint32_t faults, ui
 int pt_debug_sched_sync(PtSched* s, uint32_t collect);        /* pt_sync: everything enqueued is complete (collect: statistics read and cleared) */
 /* Test hook: the n-th stream operation (0-based) of the NEXT render on this context fails as if its HIP call had (n < 0: none). */
 int pt_debug_fail_after(PtContext* ctx, int64_t n);
+/* Launch log: which compiled instance of the path kernels each launch took.  One code per path-kernel launch, recorded on the
+ * host as the launch is enqueued: bits 0-1 family (0 k_paths, 1 k_paths_bvh, 2 k_paths_regen, 3 k_paths_regen_split), bit 2
+ * MODE of k_paths (0 scene in LDS, 1 tiled scan), bit 3 MIS, bit 4 OVF (continuation launch), bits 5-6 material set (DIFFUSE
+ * of k_paths / k_paths_bvh; MATS of k_paths_regen and PLAIN of k_paths_regen_split: 0 all, 1 diffuse only, 2 no Mirror),
+ * bit 7 LIST (pixel list), bit 8 exact arithmetic.  pt_debug_launch_log writes the codes of the launches since its last
+ * call, in launch order (up to cap; *n = codes written), and clears them.  pt_debug_path_instances writes the table of
+ * every code the dispatch can record (up to cap; *n = the table's length; out may be NULL).                            */
+int pt_debug_launch_log(PtContext* ctx, uint32_t* out, uint32_t cap, uint32_t* n);
+int pt_debug_path_instances(uint32_t* out, uint32_t cap, uint32_t* n);
 
 /* World::render_pixel (src/world.rs:293-333) -- the seam the reference's rayon loop calls at
  * src/main.rs:55 -- for an arbitrary list of n pixels: xy = n * (x, y), y = film row (top-down, the y

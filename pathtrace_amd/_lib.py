@@ -177,6 +177,8 @@ SYMBOLS = {
     "pt_debug_sched_render": (C.c_int, [C.c_void_p, _P(PtSchedJob), C.c_uint32, C.c_uint32, _P(PtSchedOp), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
     "pt_debug_sched_sync": (C.c_int, [C.c_void_p, C.c_uint32]),
     "pt_debug_fail_after": (C.c_int, [C.c_void_p, C.c_int64]),
+    "pt_debug_launch_log": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),
+    "pt_debug_path_instances": (C.c_int, [_P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),
     "pt_multi_scene_upload": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
     "pt_multi_set_tuning": (C.c_int, [C.c_void_p, _P(PtTuning)]),
     "pt_multi_render_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_void_p, C.c_void_p]),

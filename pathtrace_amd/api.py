@@ -122,6 +122,15 @@ class Context:
         """Test hook (pt_debug_fail_after): the n-th stream operation of the NEXT render fails as a HIP call would; n < 0: none."""
         check(lib().pt_debug_fail_after(self._h, int(n)))
 
+    def launch_log(self):
+        """-> instance codes (path_instance) of the path-kernel launches enqueued since the last call, in launch order; clears
+        them (pt_debug_launch_log)."""
+        cap = 1 << 16
+        buf = (C.c_uint32 * cap)()
+        n = C.c_uint32(0)
+        check(lib().pt_debug_launch_log(self._h, buf, cap, C.byref(n)))
+        return list(buf[:n.value])
+
     def scan_layout(self):
         """-> (spheres, single triangles, triangle pairs) one linear scan of the uploaded scene tests (pt_debug_scan_layout)"""
         a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
@@ -370,6 +379,33 @@ def render_multi(devices, cam, objs, params):
     check(lib().pt_render_multi(arr, len(devices), C.byref(cam), objs, len(objs), C.byref(params),
                                 lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p)))
     return lin, rgba
+
+
+def path_instances():
+    """-> every instance code the path-kernel dispatch can record in the launch log (pt_debug_path_instances)."""
+    n = C.c_uint32(0)
+    check(lib().pt_debug_path_instances(None, 0, C.byref(n)))
+    buf = (C.c_uint32 * n.value)()
+    check(lib().pt_debug_path_instances(buf, n.value, C.byref(n)))
+    return list(buf)
+
+
+_FAMILIES = ("k_paths", "k_paths_bvh", "k_paths_regen", "k_paths_regen_split")
+
+
+def path_instance(code):
+    """Decodes a launch-log code (include/pathtrace_amd.h) -> dict of the template arguments, 'kernel' = the kernel template
+    as the compiler spells it (e.g. "k_paths_regen<false, 2, true>") and 'exact' (arithmetic mode)."""
+    fam = code & 3
+    d = dict(family=_FAMILIES[fam], mode=(code >> 2) & 1, mis=bool(code >> 3 & 1), ovf=bool(code >> 4 & 1), mats=(code >> 5) & 3,
+             list=bool(code >> 7 & 1), exact=bool(code >> 8 & 1))
+    b = lambda v: "true" if v else "false"  # noqa: E731
+    args = {0: [str(d["mode"]), b(d["mis"]), b(d["ovf"]), b(d["mats"]), b(d["list"])],
+            1: [b(d["mis"]), b(d["ovf"]), b(d["mats"]), b(d["list"])],
+            2: [b(d["mis"]), str(d["mats"]), b(d["list"])],
+            3: [b(d["mis"]), str(d["mats"])]}[fam]
+    d["kernel"] = "%s<%s>" % (_FAMILIES[fam], ", ".join(args))
+    return d
 
 
 def bvh_check(objs):

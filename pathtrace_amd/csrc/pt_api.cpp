@@ -24,8 +24,11 @@
 
 #ifdef PT_SAN_NO_KERNELS
 // The host-only sanitizer build (tests/tools/run_sanitizers.sh) links no device code; its stub file covers the launchers
-// that existed before adaptive sampling, these two are stubbed here.  Nothing that build runs reaches them.
+// that existed before adaptive sampling, these (and the path-kernel launchers of the launch log) are stubbed here.  Nothing
+// that build runs reaches them.
 namespace ptk {
+uint32_t launch_path_kernel_exact(const BounceArgs&, uint32_t, hipStream_t) { std::abort(); }
+uint32_t launch_path_kernel_fast(const BounceArgs&, uint32_t, hipStream_t) { std::abort(); }
 void launch_resolve_adaptive(const AdaptiveResolveArgs&, hipStream_t) { std::abort(); }
 void launch_adaptive_select(const uint2*, uint32_t, uint32_t, const uint32_t*, uint32_t*, uint2*, uint32_t*, hipStream_t) { std::abort(); }
 }  // namespace ptk
@@ -120,6 +123,7 @@ constexpr uint32_t kWavesPerBlock = ptk::kBlock / 64;
 // scenes: the tiled scan costs ~0.11 ms per sphere and 67 M samples -- a Moeller-Trumbore test 2.5x that --, the BVH
 // ~70 ms flat -> break-even near 600 sphere tests)
 constexpr uint32_t kAutoBvhWeight = 512;
+constexpr size_t kLaunchLogCap = 1u << 16;       // pt_debug_launch_log keeps this many codes between two reads
 
 }  // namespace
 
@@ -184,6 +188,7 @@ struct PtContext {
     uint64_t expected_samples = 0;    // tile pixels x spp of the renders enqueued since the statistics were last collected (pt_sync compares)
     uint64_t capture_gcd = 0;         // gcd of the sample counts of the renders captured into graphs (replays add multiples of them)
     int64_t debug_fail_at = -1;       // pt_debug_fail_after: the stream operation of the next render that fails (test hook)
+    std::vector<uint32_t> launch_log;  // pt_debug_launch_log: instance code of every path-kernel launch enqueued since it was last read
     DevBuf<float4> cqueue[4];
     DevBuf<float4> caux, csray[2];    // ... and, for accel = 1, its own staged-pass scratch
     DevBuf<ptk::Rgb> lsamp2;
@@ -992,9 +997,9 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
                 if (o.flags & kLaunchStaticDeal) a.regen_static = (uint32_t)(((uint64_t)nch * kRegenStatic16 / 16) / nwr) * nwr;
                 if (o.core) { a.posted = c->d_posted; a.seq = o.seq; a.core_blocks = o.core; }
             }
-            if (prm->exact_math) ptk::launch_paths_exact(a, o.grid, s);
-            else ptk::launch_paths_fast(a, o.grid, s);
+            const uint32_t inst = prm->exact_math ? ptk::launch_path_kernel_exact(a, o.grid, s) : ptk::launch_path_kernel_fast(a, o.grid, s);
             HIP_TRY(hipGetLastError());
+            if (c->launch_log.size() < kLaunchLogCap) c->launch_log.push_back(inst);
             if ((o.flags & kLaunchPrimary) && plan.profile) primary_events.push_back(pool_begin / 2u);
             return PT_OK;
         }
@@ -1134,6 +1139,47 @@ int pt_sync(PtContext* c) {
 int pt_debug_fail_after(PtContext* c, int64_t n) {
     if (!c) return fail(PT_ERR_INVALID_ARG, "null context");
     c->debug_fail_at = n;
+    return PT_OK;
+}
+
+// Debug: the instance codes (ptk::instance_code) of the path-kernel launches enqueued since the last call, in launch order (the
+// first kLaunchLogCap of them); clears the log.  *n = codes written (at most cap).
+int pt_debug_launch_log(PtContext* c, uint32_t* out, uint32_t cap, uint32_t* n) {
+    if (!c || !n || (!out && cap)) return fail(PT_ERR_INVALID_ARG, "null argument");
+    const uint32_t k = (uint32_t)std::min<size_t>(cap, c->launch_log.size());
+    std::copy(c->launch_log.begin(), c->launch_log.begin() + k, out);
+    *n = k;
+    c->launch_log.clear();
+    return PT_OK;
+}
+
+// Debug: every instance code ptk::launch_paths_* can return -- the path-kernel instances the library is built with (the
+// template arguments of the dispatch in pt_kernels.hip), each in both arithmetic modes.  *n = the table's length; up to cap
+// codes are written (out may be null to ask for the length).
+int pt_debug_path_instances(uint32_t* out, uint32_t cap, uint32_t* n) {
+    if (!n || (!out && cap)) return fail(PT_ERR_INVALID_ARG, "null argument");
+    std::vector<uint32_t> t;
+    for (const bool exact : {true, false}) {
+        for (const bool mis : {true, false}) {
+            for (const bool ovf : {false, true}) {
+                // k_paths<MODE, MIS, OVF, DIFFUSE, LIST>: the diffuse-only instances for whole-image renders out of LDS only
+                t.push_back(ptk::instance_code(ptk::kInstPaths, ptk::kModeLds, mis, ovf, true, false, exact));
+                for (const int mode : {ptk::kModeLds, ptk::kModeTiled})
+                    for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstPaths, mode, mis, ovf, false, list, exact));
+                // k_paths_bvh<MIS, OVF, DIFFUSE, LIST>: likewise
+                t.push_back(ptk::instance_code(ptk::kInstBvh, 0, mis, ovf, true, false, exact));
+                for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstBvh, 0, mis, ovf, false, list, exact));
+            }
+            // k_paths_regen<MIS, MATS, LIST> (level-0 launches only; LIST: pt_render_adaptive's passes)
+            for (const int mats : {ptk::kMatsAll, ptk::kMatsDiffuse, ptk::kMatsNoMirror})
+                for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstRegen, 0, mis, false, mats, list, exact));
+            // k_paths_regen_split<MIS, PLAIN> (level-0 launches of whole images only)
+            for (const int plain : {ptk::kMatsDiffuse, ptk::kMatsNoMirror})
+                t.push_back(ptk::instance_code(ptk::kInstRegenSplit, 0, mis, false, plain, false, exact));
+        }
+    }
+    for (size_t i = 0; i < t.size() && i < cap; ++i) out[i] = t[i];
+    *n = (uint32_t)t.size();
     return PT_OK;
 }
 

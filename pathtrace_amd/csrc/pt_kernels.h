@@ -132,6 +132,19 @@ struct BounceArgs {
 };
 
 constexpr uint32_t kBlock = 256;
+// How a linear-scan kernel finds the closest hit (pt_kernels.hip: scene_mode), and the material sets kernels are compiled for
+// (pt_kernels.hip: assume_mats).
+constexpr int kModeLds = 0, kModeTiled = 1, kModeBvh = 2;
+constexpr int kMatsAll = 0, kMatsDiffuse = 1, kMatsNoMirror = 2, kMatsMirror = 3;
+// Launch log (pt_debug_launch_log): the path-kernel instance a launch takes, one word recorded by the host as it enqueues the
+// launch.  bits 0-1 family, bit 2 MODE of k_paths (kModeLds / kModeTiled), bit 3 MIS, bit 4 OVF, bits 5-6 the material set
+// (k_paths, k_paths_bvh: DIFFUSE; k_paths_regen: MATS; k_paths_regen_split: PLAIN), bit 7 LIST, bit 8 exact arithmetic.
+// Template arguments the family does not have are 0.  pt_debug_path_instances lists every word the dispatch can record.
+enum { kInstPaths = 0, kInstBvh = 1, kInstRegen = 2, kInstRegenSplit = 3 };
+constexpr uint32_t instance_code(uint32_t family, int mode, bool mis, bool ovf, int mats, bool list, bool exact) {
+    return family | (uint32_t)mode << 2 | (uint32_t)mis << 3 | (uint32_t)ovf << 4 | (uint32_t)mats << 5 | (uint32_t)list << 7 |
+           (uint32_t)exact << 8;
+}
 // Scenes of at most kSmallObjs objects stay whole in LDS (scan + shape + material + run
 // records: at most 9 float4 per object = 18 KiB); larger scenes stream their scan array
 // through one LDS tile and gather shape/material records from global memory.
@@ -167,16 +180,17 @@ void launch_scene_setup_fast(float4* shape, float4* mat, uint32_t n_objs, hipStr
 // workgroups per CU of the regenerating level-0 kernel `a` selects (sc, integrator, xchg), with the scene's LDS blob; 0 = unknown
 uint32_t regen_blocks_per_cu_exact(const BounceArgs& a);
 uint32_t regen_blocks_per_cu_fast(const BounceArgs& a);
-void launch_paths_exact(const BounceArgs& a, uint32_t grid, hipStream_t st);
-void launch_paths_fast(const BounceArgs& a, uint32_t grid, hipStream_t st);
+// One path-kernel launch; returns the instance code (instance_code) of the kernel it enqueued, for the launch log.
+uint32_t launch_path_kernel_exact(const BounceArgs& a, uint32_t grid, hipStream_t st);
+uint32_t launch_path_kernel_fast(const BounceArgs& a, uint32_t grid, hipStream_t st);
 // between the translation units pt_kernels.hip is built as (PT_TU there; not called by the host code): k_paths_regen_split's and the
 // BVH form's launchers live with their kernels
 int regen_split_blocks_per_cu_exact(const BounceArgs& a, size_t lds);
 int regen_split_blocks_per_cu_fast(const BounceArgs& a, size_t lds);
-void launch_regen_split_exact(const BounceArgs& b, uint32_t blocks, size_t lds, hipStream_t st);
-void launch_regen_split_fast(const BounceArgs& b, uint32_t blocks, size_t lds, hipStream_t st);
-void launch_paths_bvh_exact(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st, bool diffuse, bool list);
-void launch_paths_bvh_fast(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st, bool diffuse, bool list);
+uint32_t launch_regen_split_exact(const BounceArgs& b, uint32_t blocks, size_t lds, hipStream_t st);
+uint32_t launch_regen_split_fast(const BounceArgs& b, uint32_t blocks, size_t lds, hipStream_t st);
+uint32_t launch_paths_bvh_exact(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st, bool diffuse, bool list);
+uint32_t launch_paths_bvh_fast(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st, bool diffuse, bool list);
 void launch_debug_hit_bvh_exact(const SceneView& sc, uint32_t grid, size_t lds, const float* rays6, uint32_t n, float t_min, float t_max,
                                 float4* scratch, int32_t* out_id, float* out_t, float* out_rec, hipStream_t st);
 void launch_debug_hit_bvh_fast(const SceneView& sc, uint32_t grid, size_t lds, const float* rays6, uint32_t n, float t_min, float t_max,

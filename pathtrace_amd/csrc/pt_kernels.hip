@@ -262,7 +262,7 @@ PT_DEV void scan_run(const float4* __restrict__ p, uint32_t tag, uint32_t n, int
 //   kModeTiled  larger scenes: the scan array streams through one LDS tile (block-uniform loop, barriers), the
 //               per-object records are gathered from global memory, linear scan
 //   kModeBvh    accel = 1: per-lane BVH traversal out of global memory / L2 (stack in LDS, no barriers)
-constexpr int kModeLds = 0, kModeTiled = 1, kModeBvh = 2;
+// (kModeLds = 0, kModeTiled = 1, kModeBvh = 2: pt_kernels.h, which the launch log's instance codes share)
 struct SceneRef {
     const float4* scan;     // SMALL: LDS scan array; else: the LDS tile buffer
     const float4* shape;
@@ -498,7 +498,7 @@ PT_DEV void camera_ray(const CameraF& cam, uint32_t sample, uint32_t px, uint32_
 //   kMatsNoMirror  everything but Mirror (the plain iterations of k_paths_regen_split, which hand Mirror vertices on)
 //   kMatsMirror    the object HIT is a Mirror (the batches of k_paths_regen_split: every entry of the special stack is one);
 //                  says nothing about the light's material
-constexpr int kMatsAll = 0, kMatsDiffuse = 1, kMatsNoMirror = 2, kMatsMirror = 3;
+// (kMatsAll = 0, kMatsDiffuse = 1, kMatsNoMirror = 2, kMatsMirror = 3: pt_kernels.h)
 template <int MATS>
 PT_DEV void assume_mats(uint32_t tag) {
     if (MATS == kMatsDiffuse) __builtin_assume(tag <= MAT_EMISSIVE);
@@ -1701,8 +1701,10 @@ __global__ void __launch_bounds__(kBlock, PT_BVH_WAVES) k_paths_bvh(BounceArgs a
     if (mode == kModeBvh) return (size_t)(kBvhStack + 3u) * kBlock * sizeof(uint32_t);   // + 3 rows: the traversal stores a visit's (up to) three far children before it knows how many there are
     return (mode == kModeLds ? (sc.blob_f4 ? sc.blob_f4 : 1u) : kTileF4) * sizeof(float4);
 }
+// the launchers return the instance code (pt_kernels.h) of the kernel they enqueue
+constexpr bool kExactMath = PT_MATH_EXACT != 0;
 template <int MODE, bool DIFFUSE, bool LIST>
-[[maybe_unused]] static void launch_paths_mode(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st) {
+[[maybe_unused]] static uint32_t launch_paths_mode(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st) {
     const bool mis = a.integrator == 0;
     const bool ovf = a.src_mode != 0u;     // continuation launch
     const dim3 g(grid), b(kBlock);
@@ -1710,10 +1712,11 @@ template <int MODE, bool DIFFUSE, bool LIST>
     else if (mis) hipLaunchKernelGGL((k_paths<MODE, true, true, DIFFUSE, LIST>), g, b, lds, st, a);
     else if (!ovf) hipLaunchKernelGGL((k_paths<MODE, false, false, DIFFUSE, LIST>), g, b, lds, st, a);
     else hipLaunchKernelGGL((k_paths<MODE, false, true, DIFFUSE, LIST>), g, b, lds, st, a);
+    return instance_code(kInstPaths, MODE, mis, ovf, DIFFUSE, LIST, kExactMath);
 }
 #if PT_TU_BVH
 template <bool DIFFUSE, bool LIST>
-static void launch_paths_bvh_t(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st) {
+static uint32_t launch_paths_bvh_t(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st) {
     const bool mis = a.integrator == 0;
     const bool ovf = a.src_mode != 0u;
     const dim3 g(grid), b(kBlock);
@@ -1721,6 +1724,7 @@ static void launch_paths_bvh_t(const BounceArgs& a, uint32_t grid, size_t lds, h
     else if (mis) hipLaunchKernelGGL((k_paths_bvh<true, true, DIFFUSE, LIST>), g, b, lds, st, a);
     else if (!ovf) hipLaunchKernelGGL((k_paths_bvh<false, false, DIFFUSE, LIST>), g, b, lds, st, a);
     else hipLaunchKernelGGL((k_paths_bvh<false, true, DIFFUSE, LIST>), g, b, lds, st, a);
+    return instance_code(kInstBvh, 0, mis, ovf, DIFFUSE, LIST, kExactMath);
 }
 #endif
 
@@ -1728,17 +1732,19 @@ static void launch_paths_bvh_t(const BounceArgs& a, uint32_t grid, size_t lds, h
 namespace ptk {
 using namespace PTK_IMPL;
 #if PT_TU_BVH
-void PT_LAUNCH(launch_paths_bvh)(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st, bool diffuse, bool list) {
-    if (list) launch_paths_bvh_t<false, true>(a, grid, lds, st);        // pixel lists: the generic kernels only
-    else if (diffuse) launch_paths_bvh_t<true, false>(a, grid, lds, st);
-    else launch_paths_bvh_t<false, false>(a, grid, lds, st);
+uint32_t PT_LAUNCH(launch_paths_bvh)(const BounceArgs& a, uint32_t grid, size_t lds, hipStream_t st, bool diffuse, bool list) {
+    if (list) return launch_paths_bvh_t<false, true>(a, grid, lds, st);        // pixel lists: the generic kernels only
+    if (diffuse) return launch_paths_bvh_t<true, false>(a, grid, lds, st);
+    return launch_paths_bvh_t<false, false>(a, grid, lds, st);
 }
 #endif
 #if PT_TU_SPLIT
 // k_paths_regen_split for the scene's material set (the plain iterations': no OrenNayar either / no Mirror)
 typedef void (*RegenSplitKernel)(BounceArgs);
-static RegenSplitKernel regen_split_kernel(const BounceArgs& a) {
+static RegenSplitKernel regen_split_kernel(const BounceArgs& a, uint32_t* code = nullptr) {
     const bool mis = a.integrator == 0;
+    const int plain = a.sc.no_oren_nayar ? kMatsDiffuse : kMatsNoMirror;
+    if (code) *code = instance_code(kInstRegenSplit, 0, mis, false, plain, false, kExactMath);
     if (a.sc.no_oren_nayar) return mis ? k_paths_regen_split<true, kMatsDiffuse> : k_paths_regen_split<false, kMatsDiffuse>;
     return mis ? k_paths_regen_split<true, kMatsNoMirror> : k_paths_regen_split<false, kMatsNoMirror>;
 }
@@ -1747,16 +1753,20 @@ int PT_LAUNCH(regen_split_blocks_per_cu)(const BounceArgs& a, size_t lds) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, regen_split_kernel(a), (int)kBlock, lds) != hipSuccess) return -1;
     return n;
 }
-void PT_LAUNCH(launch_regen_split)(const BounceArgs& b, uint32_t blocks, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL(regen_split_kernel(b), dim3(blocks), dim3(kBlock), lds, st, b);
+uint32_t PT_LAUNCH(launch_regen_split)(const BounceArgs& b, uint32_t blocks, size_t lds, hipStream_t st) {
+    uint32_t code = 0;
+    hipLaunchKernelGGL(regen_split_kernel(b, &code), dim3(blocks), dim3(kBlock), lds, st, b);
+    return code;
 }
 #endif
 #if PT_TU_MAIN
 // the regenerating level-0 kernel a launch takes: compiled for the scene's material set; with the Mirror vertices batched
 // (k_paths_regen_split, its own translation unit) when the host passes exchange memory
 typedef void (*RegenKernel)(BounceArgs);
-static RegenKernel regen_kernel(const BounceArgs& a) {
+static RegenKernel regen_kernel(const BounceArgs& a, uint32_t* code = nullptr) {
     const bool mis = a.integrator == 0;
+    if (code) *code = instance_code(kInstRegen, 0, mis, false, a.sc.diffuse_only ? kMatsDiffuse : a.sc.no_mirror ? kMatsNoMirror : kMatsAll,
+                                    a.pixels != nullptr, kExactMath);
     if (a.pixels) {          // pt_render_adaptive's list passes
         if (a.sc.diffuse_only) return mis ? k_paths_regen<true, kMatsDiffuse, true> : k_paths_regen<false, kMatsDiffuse, true>;
         if (a.sc.no_mirror) return mis ? k_paths_regen<true, kMatsNoMirror, true> : k_paths_regen<false, kMatsNoMirror, true>;
@@ -1778,28 +1788,28 @@ uint32_t PT_LAUNCH(regen_blocks_per_cu)(const BounceArgs& a) {
     if (n < 0) return 0u;
     return (uint32_t)n * block / kBlock;                         // in units of four waves, like the grid the host passes
 }
-void PT_LAUNCH(launch_paths)(const BounceArgs& a, uint32_t grid, hipStream_t st) {
+uint32_t PT_LAUNCH(launch_path_kernel)(const BounceArgs& a, uint32_t grid, hipStream_t st) {
     const int mode = scene_mode(a.sc, a.accel);
     const size_t lds = scene_lds_bytes(a.sc, mode);
     const bool diffuse = a.sc.diffuse_only != 0u;
     if (a.pixels && !(mode == kModeLds && a.chunk_counter)) {   // pixel-list renders: the generic kernels (debug / replay entries)
-        if (mode == kModeLds) launch_paths_mode<kModeLds, false, true>(a, grid, lds, st);
-        else if (mode == kModeTiled) launch_paths_mode<kModeTiled, false, true>(a, grid, lds, st);
-        else PT_LAUNCH(launch_paths_bvh)(a, grid, lds, st, false, true);
-        return;
+        if (mode == kModeLds) return launch_paths_mode<kModeLds, false, true>(a, grid, lds, st);
+        if (mode == kModeTiled) return launch_paths_mode<kModeTiled, false, true>(a, grid, lds, st);
+        return PT_LAUNCH(launch_paths_bvh)(a, grid, lds, st, false, true);
     }
     if (mode == kModeLds && a.chunk_counter) {   // level-0 launch of a large batch: paths stay in registers (k_paths_regen*)
         const uint32_t block = a.xchg ? kBlock : kRegenBlock;    // grid = number of 4-wave units
         BounceArgs b = a;
         b.core_blocks = a.core_blocks * kBlock / block;          // (given in four-wave units like the grid)
         const uint32_t blocks = std::max(1u, grid * kBlock / block);
-        if (a.xchg) PT_LAUNCH(launch_regen_split)(b, blocks, lds, st);
-        else hipLaunchKernelGGL(regen_kernel(a), dim3(blocks), dim3(block), lds, st, b);
-        return;
+        if (a.xchg) return PT_LAUNCH(launch_regen_split)(b, blocks, lds, st);
+        uint32_t code = 0;
+        hipLaunchKernelGGL(regen_kernel(a, &code), dim3(blocks), dim3(block), lds, st, b);
+        return code;
     }
-    if (mode == kModeLds) { if (diffuse) launch_paths_mode<kModeLds, true, false>(a, grid, lds, st); else launch_paths_mode<kModeLds, false, false>(a, grid, lds, st); }
-    else if (mode == kModeTiled) launch_paths_mode<kModeTiled, false, false>(a, grid, lds, st);   // scan-dominated: the variant buys nothing (measured)
-    else PT_LAUNCH(launch_paths_bvh)(a, grid, lds, st, diffuse, false);
+    if (mode == kModeLds) return diffuse ? launch_paths_mode<kModeLds, true, false>(a, grid, lds, st) : launch_paths_mode<kModeLds, false, false>(a, grid, lds, st);
+    if (mode == kModeTiled) return launch_paths_mode<kModeTiled, false, false>(a, grid, lds, st);   // scan-dominated: the variant buys nothing (measured)
+    return PT_LAUNCH(launch_paths_bvh)(a, grid, lds, st, diffuse, false);
 }
 #endif
 }  // namespace ptk

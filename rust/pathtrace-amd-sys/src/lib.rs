@@ -220,6 +220,8 @@ extern "C" {
     pub fn pt_debug_sched_render(s: *mut PtSched, job: *const PtSchedJob, faults: u32, fail_after: u32, ops: *mut PtSchedOp, cap: u32, n_ops: *mut u32, lanes: *mut u32) -> c_int;
     pub fn pt_debug_sched_sync(s: *mut PtSched, collect: u32) -> c_int;
     pub fn pt_debug_fail_after(ctx: *mut PtContext, n: i64) -> c_int;
+    pub fn pt_debug_launch_log(ctx: *mut PtContext, out: *mut u32, cap: u32, n: *mut u32) -> c_int;
+    pub fn pt_debug_path_instances(out: *mut u32, cap: u32, n: *mut u32) -> c_int;
     pub fn pt_multi_scene_upload(m: *mut PtMulti, objs: *const PtObject, n_objs: u32) -> c_int;
     pub fn pt_multi_set_tuning(m: *mut PtMulti, tuning: *const PtTuning) -> c_int;
     pub fn pt_multi_render_device(m: *mut PtMulti, cam: *const PtCamera, params: *const PtRenderParams, d_linear_rgb: *mut f32, d_rgba8: *mut u8) -> c_int;

@@ -39,13 +39,31 @@ def _pixel_parity(ctx, cam, prm, lin, rgba, spp, n_sample=512, seed=0):
         assert np.array_equal(prgba, rgba[ys[sel], xs[sel]]), f"spp {n}: RGBA8 differs from pt_render_pixels"
 
 
-@pytest.mark.parametrize("scene,exact", [(2, 0), (2, 1), (1, 0), (1, 1)])
+def _scene(pt, scene):
+    """"<id>": builtin scene; "oren_nayar": the ten-sphere box with OrenNayar walls and spheres (no Mirror: the adaptive passes
+    take k_paths_regen<MIS, kMatsNoMirror, true>); a "/brdf" suffix: integrator = 1 (BrdfOnlyStrategy)."""
+    name, _, strategy = str(scene).partition("/")
+    integrator = 1 if strategy == "brdf" else 0
+    if name != "oren_nayar":
+        return pt.builtin_scene(int(name)), integrator
+    objs = list(pt.builtin_scene(2))
+    for k, o in enumerate(objs):
+        if o.mat_tag == 0:
+            o.mat_tag = 3
+            o.mat[3] = [0.0, 0.3, 0.6, 1.0][k % 4]
+    return (pt._lib.PtObject * len(objs))(*objs), integrator
+
+
+@pytest.mark.parametrize("scene,exact", [(2, 0), (2, 1), (1, 0), (1, 1), ("2/brdf", 0), ("2/brdf", 1), ("1/brdf", 0), ("1/brdf", 1),
+                                         ("oren_nayar", 0), ("oren_nayar", 1), ("oren_nayar/brdf", 0), ("oren_nayar/brdf", 1)])
 def test_no_tolerance_is_the_uniform_render(pt, gpu_ctx, scene, exact):
     """rel_tol = 0: every pixel runs to spp_max, and the film is the uniform one bit for bit.  spp_max = 45 is not
-    spp_min + k * spp_step (8, 24, 40): the last pass is cut to 5 samples."""
-    gpu_ctx.upload(pt.builtin_scene(scene))
+    spp_min + k * spp_step (8, 24, 40): the last pass is cut to 5 samples.  Each integrator, and the three material sets
+    the regenerating list kernels are compiled for (diffuse only, no Mirror, every material)."""
+    objs, integrator = _scene(pt, scene)
+    gpu_ctx.upload(objs)
     cam = pt.camera_new(width=128, height=128)
-    prm = pt.default_params(spp=45, exact_math=exact, spp_offset=3)
+    prm = pt.default_params(spp=45, exact_math=exact, spp_offset=3, integrator=integrator)
     lin, rgba, spp, err = gpu_ctx.render_adaptive(cam, prm, spp_min=8, spp_step=16, rel_tol=0.0)
     assert (spp == 45).all()
     ulin, urgba = _uniform(gpu_ctx, cam, prm)
@@ -114,11 +132,23 @@ def test_the_rule_restated_in_numpy(pt, gpu_ctx):
     assert tested >= 48
 
 
-@pytest.mark.parametrize("form", ["tiled", "bvh", "batches"])
+@pytest.mark.parametrize("form", ["tiled", "bvh", "batches", "brdf", "brdf_tiled", "brdf_bvh", "oren_nayar", "oren_nayar_brdf"])
 def test_other_kernel_forms(pt, gpu_ctx, form):
     """A scene of more than 128 objects (tiled scan), the BVH, and a max_paths_in_flight that cuts every pass into
-    several sample batches: each pixel still equals pt_render_pixels at its spp."""
-    if form == "tiled":
+    several sample batches; integrator = 1 (BrdfOnlyStrategy) on the reference scene, the tiled scan and the BVH; an
+    OrenNayar scene without Mirror (either integrator): each pixel still equals pt_render_pixels at its spp."""
+    if form in ("brdf", "oren_nayar", "oren_nayar_brdf"):
+        objs, _ = _scene(pt, "1" if form == "brdf" else "oren_nayar")
+        gpu_ctx.upload(objs)
+        cam = pt.camera_new(width=128, height=128)                 # first pass 128 * 128 * 8 paths: a regenerating launch
+        prm = pt.default_params(spp=96, integrator=0 if form == "oren_nayar" else 1)
+    elif form == "brdf_tiled":
+        gpu_ctx.upload(pt.builtin_scene(4, 200))
+        cam, prm = pt.camera_new(width=96, height=96), pt.default_params(spp=96, accel=0, integrator=1)
+    elif form == "brdf_bvh":
+        gpu_ctx.upload(pt.builtin_scene(1))
+        cam, prm = pt.camera_new(width=96, height=96), pt.default_params(spp=96, accel=1, integrator=1)
+    elif form == "tiled":
         gpu_ctx.upload(pt.builtin_scene(4, 200))
         cam, prm = pt.camera_new(width=96, height=96), pt.default_params(spp=96, accel=0)
     elif form == "bvh":

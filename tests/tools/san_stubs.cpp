@@ -8,8 +8,6 @@ void launch_scene_setup_exact(float4*, float4*, uint32_t, hipStream_t) { std::ab
 void launch_scene_setup_fast(float4*, float4*, uint32_t, hipStream_t) { std::abort(); }
 uint32_t regen_blocks_per_cu_exact(const BounceArgs&) { return 0; }
 uint32_t regen_blocks_per_cu_fast(const BounceArgs&) { return 0; }
-void launch_paths_exact(const BounceArgs&, uint32_t, hipStream_t) { std::abort(); }
-void launch_paths_fast(const BounceArgs&, uint32_t, hipStream_t) { std::abort(); }
 void launch_resolve(const ResolveArgs&, hipStream_t) { std::abort(); }
 void launch_debug_hit_exact(const SceneView&, uint32_t, const float*, uint32_t, float, float, float4*, int32_t*, float*, float*, hipStream_t) { std::abort(); }
 void launch_debug_hit_fast(const SceneView&, uint32_t, const float*, uint32_t, float, float, float4*, int32_t*, float*, float*, hipStream_t) { std::abort(); }
