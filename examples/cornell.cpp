@@ -3,6 +3,7 @@
 // World.data instead of blitting it to a winit/pixels surface (out of scope).
 //
 //   ./cornell [width height spp [out_prefix [exact_math]]]        defaults: 400 400 64 cornell 0
+//   CORNELL_DENOISE=n: render_denoised with n feature samples (pt_render_denoised) instead of render()
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -45,7 +46,9 @@ int main(int argc, char** argv) {
         world.params().spp = spp;
         world.params().exact_math = exact_math;
         const auto t0 = std::chrono::steady_clock::now();
-        if (std::getenv("CORNELL_PROGRESSIVE"))      // live-preview form: one line per increment
+        if (std::getenv("CORNELL_DENOISE"))          // denoised form: CORNELL_DENOISE = feature samples
+            world.render_denoised((uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
+        else if (std::getenv("CORNELL_PROGRESSIVE"))      // live-preview form: one line per increment
             world.render_progressive(std::max(1u, spp / 4), [&](uint32_t done) {
                 std::printf("  preview after %u spp: centre pixel rgb = %u %u %u\n", done, world.data[(h / 2) * w + w / 2].r,
                             world.data[(h / 2) * w + w / 2].g, world.data[(h / 2) * w + w / 2].b);

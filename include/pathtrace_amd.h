@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 5
+#define PT_ABI_VERSION 6
 
 typedef enum {
     PT_OK = 0,
@@ -417,6 +417,53 @@ typedef struct {
 } PtAdaptive;
 int pt_render_adaptive(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, const PtAdaptive* ad,
                        float* out_linear_rgb, uint8_t* out_rgba8, uint32_t* out_spp, float* out_rel_err);
+
+/* First-hit feature buffers: one 32-byte record per image pixel, row-major, whole image, 16-byte aligned:
+ *   {albedo r, g, b, emitter, normal x, y, z, depth}
+ * For samples spp_offset .. spp_offset + n_samples - 1 the pass takes the primary ray the path kernels take (same key, same
+ * jitter draws), finds its closest hit in [t_min, inf) with the scan or BVH params->accel selects, and maps it to a record:
+ *   Lambert / OrenNayar: albedo clamped to [0, 1], emitter 0;  Mirror: color clamped to [0, 1], emitter 0;
+ *   Emissive: albedo (1, 1, 1), emitter 1;  the three with the face-forwarded HitRecord normal and depth = t;
+ *   miss: albedo (1, 1, 1), emitter 0, normal 0, depth 0.
+ * The records are summed in sample order in f32 and each sum is divided by n_samples; params->exact_math selects the
+ * arithmetic mode (exact: bit-identical to the f32 oracle's camera rays and hit records).  Asynchronous on the context's
+ * stream like pt_render_device; the scratch (a bounded batch of rays and hits) is context-owned and grows on first use.
+ * PT_ERR_INVALID_ARG: n_samples = 0, band_count > 1 (the pass works on the whole image only).                         */
+int pt_render_features_device(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t n_samples,
+                              float* d_features);
+
+/* Edge-avoiding a-trous wavelet denoiser guided by variance (spatial SVGF, no temporal part).  Per pixel p, with c the
+ * linear film and the feature records above:
+ *   demodulate   a = max(albedo, 1e-3) per channel, u = c / a, L(u) = 0.2126 r + 0.7152 g + 0.0722 b
+ *   variance     var = the 3x3 population variance of L(u); taps outside the image are skipped
+ *   iteration i = 0 .. iterations-1, step h = 2^i: 5x5 taps at (dx, dy) h, B3-spline weights
+ *                k = [1/16, 1/4, 3/8, 1/4, 1/16] (x) same, taps outside the image skipped;
+ *                g_p = sqrt(3x3 Gaussian [1/4, 1/2, 1/4] (x) same of var, renormalised over the in-image taps);
+ *                q != p:  w = k max(0, n_p.n_q)^sigma_n exp(-|L_p - L_q| / (sigma_l g_p + 1e-10)
+ *                                                    -|d_p - d_q| / (sigma_d h max(d_p, 1e-3) + 1e-10)),
+ *                         w = 0 when emitter_p > 0 or emitter_q > 0;  the centre tap: w = k;
+ *                u' = sum w u_q / sum w,  var' = sum w^2 var_q / (sum w)^2
+ *   remodulate   c' = u a; the RGBA8 plane is c' through the sqrt-gamma / clamp / `as u8` steps of every render.
+ * iterations = 0 gives u a of the input.  The device computes in f32 (the sums as u_p + sum w (u_q - u_p) / sum w).
+ * pt_default_denoise: 5 iterations, sigma_l 4, sigma_n 128, sigma_d 0.025.                                            */
+typedef struct {
+    uint32_t iterations;
+    float sigma_l;           /* luminance edge stop, in units of the local standard deviation */
+    float sigma_n;           /* normal exponent                                                */
+    float sigma_d;           /* depth edge stop, relative to the depth per unit step           */
+} PtDenoise;
+void pt_default_denoise(PtDenoise* out);
+/* Device buffers: d_linear_rgb width*height*3 floats, d_features width*height*8 floats (16-byte aligned), d_out_linear
+ * width*height*3 floats (not the input), d_out_rgba8 width*height*4 bytes or NULL (4-byte aligned).  Asynchronous on the
+ * context's stream; two context-owned float4 planes of (u, var) grow on first use.  Needs no scene.                   */
+int pt_denoise_device(PtContext* ctx, uint32_t width, uint32_t height, const float* d_linear_rgb, const float* d_features,
+                      const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba8);
+/* One call with HOST buffers (blocking): the render of params, then the feature pass of min(feature_samples, params->spp)
+ * samples from params->spp_offset, then the filter.  out_rgba8, out_noisy_linear (the render's linear film) and out_features
+ * (width*height*8 floats) may be NULL.  The whole image only (band_count = 1).                                         */
+int pt_render_denoised(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
+                       const PtDenoise* dn, float* out_linear_rgb, uint8_t* out_rgba8, float* out_noisy_linear,
+                       float* out_features);
 
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on

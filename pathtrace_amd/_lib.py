@@ -92,6 +92,15 @@ class PtAdaptive(C.Structure):
     ]
 
 
+class PtDenoise(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("sigma_l", C.c_float),
+        ("sigma_n", C.c_float),
+        ("sigma_d", C.c_float),
+    ]
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -161,6 +170,11 @@ SYMBOLS = {
     "pt_render_pixels": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(C.c_uint32), C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
     "pt_render_adaptive": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtAdaptive), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "pt_render_features_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, C.c_void_p]),
+    "pt_default_denoise": (None, [_P(PtDenoise)]),
+    "pt_denoise_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _P(PtDenoise), C.c_void_p, C.c_void_p]),
+    "pt_render_denoised": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),

@@ -41,6 +41,16 @@ def default_params(**over):
     return p
 
 
+def default_denoise(**over):
+    """pt_default_denoise with keyword overrides (None keeps the default)."""
+    d = _lib.PtDenoise()
+    lib().pt_default_denoise(C.byref(d))
+    for k, v in over.items():
+        if v is not None:
+            setattr(d, k, v)
+    return d
+
+
 def builtin_scene(scene_id, arg=0):
     """Scenes of SURVEY 8(d): 1 reference Cornell box, 2 ten-sphere Cornell, 4 random spheres (arg = n)."""
     n = C.c_uint32(0)
@@ -288,6 +298,50 @@ class _ContextFunctions:
                                        rgba.ctypes.data_as(C.c_void_p), spp.ctypes.data_as(C.c_void_p),
                                        err.ctypes.data_as(C.c_void_p)))
         return lin, rgba, spp, err
+
+    def render_features(self, cam, params, n_samples):
+        """pt_render_features_device: first-hit records of samples spp_offset .. spp_offset + n_samples - 1.
+        -> f32[H,W,8] = albedo rgb, emitter, normal xyz, depth"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        feat = torch.empty((cam.height, cam.width, 8), dtype=torch.float32, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_render_features_device(self._h, C.byref(cam), C.byref(params), n_samples, C.c_void_p(feat.data_ptr())))
+        self.sync()
+        return feat.cpu().numpy()
+
+    def denoise(self, linear, features, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
+        """pt_denoise_device on a film (f32[H,W,3]) and its features (f32[H,W,8]); unset parameters take pt_default_denoise.
+        -> (linear f32[H,W,3], rgba u8[H,W,4])"""
+        import torch
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        linear = np.ascontiguousarray(linear, dtype=np.float32)
+        features = np.ascontiguousarray(features, dtype=np.float32)
+        H, W = linear.shape[:2]
+        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8)
+        dev = torch.device("cuda", self.device)
+        d_lin, d_feat = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev)
+        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_denoise_device(self._h, W, H, C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()), C.byref(dn),
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
+        self.sync()
+        return out.cpu().numpy(), rgba.cpu().numpy()
+
+    def render_denoised(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
+        """pt_render_denoised (host buffers, blocking).  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3],
+        features f32[H,W,8])"""
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        H, W = cam.height, cam.width
+        lin = np.empty((H, W, 3), dtype=np.float32)
+        rgba = np.empty((H, W, 4), dtype=np.uint8)
+        noisy = np.empty((H, W, 3), dtype=np.float32)
+        feat = np.empty((H, W, 8), dtype=np.float32)
+        check(lib().pt_render_denoised(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn),
+                                       lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
+                                       noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p)))
+        return lin, rgba, noisy, feat
 
     def ray_color(self, params, rays, xy):
         """pt_ray_color = RenderingStrategy::ray_color(world, ray, 0, rng(key xy, sample spp_offset), 1) -> f32[n,3]"""

@@ -31,6 +31,11 @@ uint32_t launch_path_kernel_exact(const BounceArgs&, uint32_t, hipStream_t) { st
 uint32_t launch_path_kernel_fast(const BounceArgs&, uint32_t, hipStream_t) { std::abort(); }
 void launch_resolve_adaptive(const AdaptiveResolveArgs&, hipStream_t) { std::abort(); }
 void launch_adaptive_select(const uint2*, uint32_t, uint32_t, const uint32_t*, uint32_t*, uint2*, uint32_t*, hipStream_t) { std::abort(); }
+void launch_feature_rays_exact(const CameraF&, uint32_t, uint32_t, float*, hipStream_t) { std::abort(); }
+void launch_feature_rays_fast(const CameraF&, uint32_t, uint32_t, float*, hipStream_t) { std::abort(); }
+void launch_feature_resolve_exact(const FeatureResolveArgs&, hipStream_t) { std::abort(); }
+void launch_feature_resolve_fast(const FeatureResolveArgs&, hipStream_t) { std::abort(); }
+void launch_denoise(const DenoiseArgs&, bool, hipStream_t) { std::abort(); }
 }  // namespace ptk
 #endif
 
@@ -124,6 +129,7 @@ constexpr uint32_t kWavesPerBlock = ptk::kBlock / 64;
 // ~70 ms flat -> break-even near 600 sphere tests)
 constexpr uint32_t kAutoBvhWeight = 512;
 constexpr size_t kLaunchLogCap = 1u << 16;       // pt_debug_launch_log keeps this many codes between two reads
+constexpr uint64_t kFeatureRays = 1ull << 21;    // pt_render_features_device: rays per batch (108 B of scratch each with the BVH)
 
 }  // namespace
 
@@ -219,6 +225,12 @@ struct PtContext {
     DevBuf<uint32_t> ad_count, ad_conv, ad_words;
     DevBuf<float> ad_err;
     DevBuf<uint2> ad_list[2];
+    // pt_render_features_device: one batch of rays, their hits (ids, records) and the BVH scratch of launch_debug_hit;
+    // pt_denoise_device: the two (u, var) ping-pong planes; pt_render_denoised: device staging of the features and the output
+    DevBuf<float> ft_rays, ft_t, ft_rec;      // (launch_debug_hit writes t for every ray: ft_t)
+    DevBuf<int32_t> ft_ids;
+    DevBuf<float4> ft_scratch, dn_plane[2], dn_feat;
+    DevBuf<float> dn_lin;
 };
 
 namespace {
@@ -473,6 +485,8 @@ int pt_context_destroy(PtContext* c) {
     c->pixel_list.release(); c->fn_in.release(); c->fn_out.release(); c->fn_words.release();
     c->ad_sums.release(); c->ad_count.release(); c->ad_conv.release(); c->ad_words.release(); c->ad_err.release();
     c->ad_list[0].release(); c->ad_list[1].release();
+    c->ft_rays.release(); c->ft_t.release(); c->ft_rec.release(); c->ft_ids.release(); c->ft_scratch.release();
+    c->dn_plane[0].release(); c->dn_plane[1].release(); c->dn_feat.release(); c->dn_lin.release();
     for (auto& b : c->inject) b.release();
     if (c->h_dstats) (void)hipHostFree(c->h_dstats);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1624,6 +1638,136 @@ int pt_render_adaptive(PtContext* c, const PtCamera* cam, const PtRenderParams* 
     if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * (size_t)np, hipMemcpyDeviceToHost));
     if (out_spp) HIP_TRY(hipMemcpy(out_spp, c->ad_count.p, (size_t)np * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (out_rel_err) HIP_TRY(hipMemcpy(out_rel_err, c->ad_err.p, (size_t)np * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// First-hit features: per batch of samples, k_feature_rays writes the camera rays, launch_debug_hit (the scan or BVH of the
+// parity entries) finds their hits, k_feature_resolve adds the records to the per-pixel sums in d_features.
+int pt_render_features_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t n_samples, float* d_features) {
+    if (!c || !cam || !prm || !d_features) return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: null argument");
+    if (n_samples == 0) return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: n_samples must be > 0");
+    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
+        return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: works on the whole image (band_count = 1)");
+    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: d_features must be 16-byte aligned");
+    if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
+    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
+    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    const uint64_t np64 = (uint64_t)cam->width * cam->height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_render_features_device: %llu pixels", (unsigned long long)np64);
+    const uint32_t np = (uint32_t)np64;
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t accel = prm->accel;
+    if (accel == PT_ACCEL_AUTO) {
+        const std::string keep = g_err;
+        accel = (c->auto_bvh && !c->bvh_refused && !c->bvh_failed && ensure_bvh(c) == PT_OK) ? PT_ACCEL_BVH : PT_ACCEL_LINEAR;
+        if (!accel) g_err = keep;
+    }
+    int rc;
+    if (accel && (rc = ensure_bvh(c))) return rc;
+    const uint32_t nb_max = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_samples, kFeatureRays / np));
+    const size_t n_rays = (size_t)nb_max * np;
+    if ((rc = c->ft_rays.ensure(6 * n_rays)) || (rc = c->ft_ids.ensure(n_rays)) || (rc = c->ft_t.ensure(n_rays)) || (rc = c->ft_rec.ensure(8 * n_rays)) ||
+        (accel && (rc = c->ft_scratch.ensure(3 * n_rays))))
+        return rc;
+    const ptk::SceneView sv = view_for(c, prm->exact_math);
+    ptk::CameraF cf{};
+    for (int k = 0; k < 3; ++k) {
+        cf.origin[k] = (float)cam->origin[k]; cf.lower_left[k] = (float)cam->lower_left[k];
+        cf.horizontal[k] = (float)cam->horizontal[k]; cf.vertical[k] = (float)cam->vertical[k];
+    }
+    cf.width = cam->width; cf.height = cam->height;
+    const hipStream_t st = c->stream;
+    const float t_min = (float)prm->t_min, t_max = INFINITY;
+    for (uint32_t done = 0; done < n_samples;) {
+        const uint32_t nb = std::min(nb_max, n_samples - done);
+        const uint32_t s_base = prm->spp_offset + done;
+        ptk::FeatureResolveArgs a{};
+        a.mat = sv.mat; a.ids = c->ft_ids.p; a.rec = c->ft_rec.p; a.out = reinterpret_cast<float4*>(d_features);
+        a.np = np; a.nb = nb; a.n_samples = n_samples; a.load = done > 0; a.finalize = done + nb == n_samples;
+        if (prm->exact_math) {
+            ptk::launch_feature_rays_exact(cf, s_base, nb, c->ft_rays.p, st);
+            ptk::launch_debug_hit_exact(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
+            ptk::launch_feature_resolve_exact(a, st);
+        } else {
+            ptk::launch_feature_rays_fast(cf, s_base, nb, c->ft_rays.p, st);
+            ptk::launch_debug_hit_fast(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
+            ptk::launch_feature_resolve_fast(a, st);
+        }
+        HIP_TRY(hipGetLastError());
+        done += nb;
+    }
+    return PT_OK;
+}
+
+void pt_default_denoise(PtDenoise* out) {
+    if (!out) return;
+    out->iterations = 5; out->sigma_l = 4.0f; out->sigma_n = 128.0f; out->sigma_d = 0.025f;
+}
+
+// The filter: k_denoise_init (u, var) into plane 0, then one k_denoise_step per iteration between the two planes; the last
+// launch writes the film planes.
+int pt_denoise_device(PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,
+                      const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba) {
+    if (!c || !dn || !d_linear || !d_features || !d_out_linear) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: null argument");
+    if (width == 0 || height == 0) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: image %ux%u", width, height);
+    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: %u iterations (at most 16)", dn->iterations);
+    if (!(dn->sigma_l >= 0.0f) || !(dn->sigma_n >= 0.0f) || !(dn->sigma_d >= 0.0f) || !std::isfinite(dn->sigma_l) ||
+        !std::isfinite(dn->sigma_n) || !std::isfinite(dn->sigma_d))
+        return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: sigma_l, sigma_n and sigma_d must be finite and >= 0");
+    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: d_features must be 16-byte aligned");
+    if ((uintptr_t)d_linear % 4u || (uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u)
+        return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: the film buffers must be 4-byte aligned");
+    if (d_out_linear == d_linear) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: the output must not be the input");
+    const uint64_t np64 = (uint64_t)width * height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_denoise_device: %llu pixels", (unsigned long long)np64);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->dn_plane[0].ensure(np64)) || (rc = c->dn_plane[1].ensure(np64))) return rc;
+    ptk::DenoiseArgs a{};
+    a.linear = d_linear; a.feat = reinterpret_cast<const float4*>(d_features);
+    a.out_linear = d_out_linear; a.out_rgba = d_out_rgba;
+    a.width = width; a.height = height;
+    a.sigma_l = dn->sigma_l; a.sigma_n = dn->sigma_n; a.sigma_d = dn->sigma_d;
+    a.dst = c->dn_plane[0].p; a.finalize = dn->iterations == 0;
+    ptk::launch_denoise(a, true, c->stream);
+    HIP_TRY(hipGetLastError());
+    for (uint32_t i = 0; i < dn->iterations; ++i) {
+        a.src = c->dn_plane[i & 1u].p; a.dst = c->dn_plane[(i + 1u) & 1u].p;
+        a.step = 1u << i; a.finalize = i + 1u == dn->iterations;
+        ptk::launch_denoise(a, false, c->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return PT_OK;
+}
+
+int pt_render_denoised(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
+                       float* out_linear, uint8_t* out_rgba, float* out_noisy, float* out_features) {
+    if (!c || !cam || !prm || !dn || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised: null argument");
+    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
+        return fail(PT_ERR_INVALID_ARG, "pt_render_denoised: renders the whole image (band_count = 1)");
+    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised: feature_samples must be > 0");
+    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
+    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    const uint64_t np64 = (uint64_t)cam->width * cam->height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_render_denoised: %llu pixels", (unsigned long long)np64);
+    const size_t np = (size_t)np64;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) ||
+        (rc = c->dn_lin.ensure(3 * np)))
+        return rc;
+    PtRenderParams p = *prm;
+    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
+    float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
+    if ((rc = render_impl(c, cam, &p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
+        (rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat)) ||
+        (rc = pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, feat, dn, c->dn_lin.p, out_rgba ? c->host_rgba.p : nullptr)) ||
+        (rc = pt_sync(c)))
+        return rc;
+    HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
+    if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_features) HIP_TRY(hipMemcpy(out_features, feat, 8 * np * sizeof(float), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -276,4 +276,36 @@ struct DebugFnArgs {
 void launch_debug_fn_exact(const DebugFnArgs& a, hipStream_t st);
 void launch_debug_fn_fast(const DebugFnArgs& a, hipStream_t st);
 
+
+// First-hit feature buffers (pt_render_features_device).  launch_feature_rays: the camera rays of samples s_base .. s_base + nb - 1
+// of every image pixel, ray s_local * np + p, as the rays6 launch_debug_hit reads.  launch_feature_resolve: the hits of that batch
+// (launch_debug_hit's ids and records) -> 32-byte records (albedo rgb, emitter | normal xyz, depth), summed per pixel in sample
+// order into out (2 float4 per pixel; load: add to the sums there); finalize divides by n_samples.
+struct FeatureResolveArgs {
+    const float4* mat;        // material records of the arithmetic mode's scene view
+    const int32_t* ids;       // nb * np
+    const float* rec;         // nb * np * 8 (t, point3, normal3, front_face)
+    float4* out;
+    uint32_t np, nb, n_samples, load, finalize;
+};
+void launch_feature_rays_exact(const CameraF& cam, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
+void launch_feature_rays_fast(const CameraF& cam, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
+void launch_feature_resolve_exact(const FeatureResolveArgs& a, hipStream_t st);
+void launch_feature_resolve_fast(const FeatureResolveArgs& a, hipStream_t st);
+
+// Edge-avoiding a-trous denoiser (pt_denoise_device; rule: include/pathtrace_amd.h PtDenoise).  init: the film -> the state
+// plane dst (u.rgb, var); a step (init = false): src -> dst with the taps at distance `step`.  finalize: the launch writes
+// c' = u * a to out_linear and its RGBA8 word to out_rgba (may be null) instead of dst.
+struct DenoiseArgs {
+    const float* linear;      // width * height * 3, the noisy film
+    const float4* feat;       // width * height * 2, the feature records
+    const float4* src;
+    float4* dst;
+    float* out_linear;
+    uint8_t* out_rgba;
+    uint32_t width, height, step, finalize;
+    float sigma_l, sigma_n, sigma_d;
+};
+void launch_denoise(const DenoiseArgs& a, bool init, hipStream_t st);
+
 }  // namespace ptk

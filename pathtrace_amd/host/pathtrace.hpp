@@ -11,6 +11,7 @@
 //   Object::new(shape, material)              src/objects/object.rs:22-24
 //   World::new()  (the Cornell box)           src/world.rs:65-241
 //   World::render()  == the closure of main() src/main.rs:43-60  (new name)
+//   World::render_denoised()  render() + first-hit features + the a-trous denoiser (beyond the reference)
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -433,6 +434,26 @@ public:
         check(pt_render_adaptive(ctx_, &camera_.pod(), &p, &ad, lin.data(), rgba.data(), spp ? spp->data() : nullptr,
                                  rel_err ? rel_err->data() : nullptr));
         unpack(lin, rgba);
+    }
+    // Denoised form of render() (pt_render_denoised): the render of params(), the first-hit features of min(feature_samples, spp)
+    // samples from spp_offset, then the edge-avoiding a-trous filter with dn (pt_default_denoise when null).  data /
+    // luminance_data hold the denoised film; noisy (optional) receives the render's own linear film, y*W+x.
+    void render_denoised(uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, std::vector<Vector3>* noisy = nullptr, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtDenoise d{};
+        if (dn) d = *dn; else pt_default_denoise(&d);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3), raw(noisy ? n * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_denoised(ctx_, &camera_.pod(), &p, feature_samples, &d, lin.data(), rgba.data(), noisy ? raw.data() : nullptr, nullptr));
+        unpack(lin, rgba);
+        if (noisy) {
+            noisy->resize(n);
+            for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+        }
     }
     PtStats stats() { PtStats s{}; if (ctx_) check(pt_get_stats(ctx_, &s)); return s; }
 

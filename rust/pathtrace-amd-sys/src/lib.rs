@@ -1,9 +1,9 @@
-//! Raw declarations of `include/pathtrace_amd.h` (ABI version 4).  Field order, types and names follow the
+//! Raw declarations of `include/pathtrace_amd.h` (ABI version 6).  Field order, types and names follow the
 //! header exactly; `tests/test_rust_binding.py` checks that.
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const PT_ABI_VERSION: u32 = 5;
+pub const PT_ABI_VERSION: u32 = 6;
 
 pub const PT_OK: c_int = 0;
 pub const PT_ERR_INVALID_ARG: c_int = 1;
@@ -84,6 +84,16 @@ pub struct PtAdaptive {
     pub spp_step: u32,
     pub rel_tol: f64,
     pub abs_floor: f64,
+}
+
+/// pt_denoise_device: the edge-avoiding a-trous filter's parameters (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtDenoise {
+    pub iterations: u32,
+    pub sigma_l: f32,
+    pub sigma_n: f32,
+    pub sigma_d: f32,
 }
 
 #[repr(C)]
@@ -234,6 +244,10 @@ extern "C" {
     pub fn pt_debug_multi_emulate(ctx: *mut PtContext, n_virtual: u32, cam: *const PtCamera, params: *const PtRenderParams, out_linear_rgb: *mut f32, out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_pixels(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, xy: *const u32, n: u32, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_samples: *mut f32) -> c_int;
     pub fn pt_render_adaptive(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, ad: *const PtAdaptive, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_spp: *mut u32, out_rel_err: *mut f32) -> c_int;
+    pub fn pt_render_features_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, n_samples: u32, d_features: *mut f32) -> c_int;
+    pub fn pt_default_denoise(out: *mut PtDenoise);
+    pub fn pt_denoise_device(ctx: *mut PtContext, width: u32, height: u32, d_linear_rgb: *const f32, d_features: *const f32, dn: *const PtDenoise, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_denoised(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
     pub fn pt_ray_color(ctx: *mut PtContext, params: *const PtRenderParams, rays: *const f64, xy: *const u32, n: u32, out_rgb: *mut f32) -> c_int;
     pub fn pt_debug_hit_scene(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_t: *mut f32) -> c_int;
     pub fn pt_debug_hit_records(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_rec: *mut f32) -> c_int;
