@@ -4,6 +4,8 @@
 //
 //   ./cornell [width height spp [out_prefix [exact_math]]]        defaults: 400 400 64 cornell 0
 //   CORNELL_DENOISE=n: render_denoised with n feature samples (pt_render_denoised) instead of render()
+//   CORNELL_TEMPORAL=k: k frames of render_denoised_temporal (4 feature samples), frame i at spp_offset i*spp with the camera
+//                       origin moved by (0.01 i, 0.005 i, 0); the files hold the last frame
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -46,7 +48,14 @@ int main(int argc, char** argv) {
         world.params().spp = spp;
         world.params().exact_math = exact_math;
         const auto t0 = std::chrono::steady_clock::now();
-        if (std::getenv("CORNELL_DENOISE"))          // denoised form: CORNELL_DENOISE = feature samples
+        if (std::getenv("CORNELL_TEMPORAL")) {       // temporal form: CORNELL_TEMPORAL = frames
+            const uint32_t frames = (uint32_t)std::atoi(std::getenv("CORNELL_TEMPORAL"));
+            for (uint32_t i = 0; i < frames; ++i) {
+                world.set_camera(Camera::new_(Vector3(0.01 * i, 0.005 * i, 2.0), w, h, 1.0, 35.0));
+                world.params().spp_offset = i * spp;
+                world.render_denoised_temporal(4);
+            }
+        } else if (std::getenv("CORNELL_DENOISE"))   // denoised form: CORNELL_DENOISE = feature samples
             world.render_denoised((uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
         else if (std::getenv("CORNELL_PROGRESSIVE"))      // live-preview form: one line per increment
             world.render_progressive(std::max(1u, spp / 4), [&](uint32_t done) {

@@ -465,6 +465,47 @@ int pt_render_denoised(PtContext* ctx, const PtCamera* cam, const PtRenderParams
                        const PtDenoise* dn, float* out_linear_rgb, uint8_t* out_rgba8, float* out_noisy_linear,
                        float* out_features);
 
+/* Temporal accumulation with camera reprojection in front of the a-trous filter (the temporal half of SVGF).
+ * Per-frame history that the context owns.  Image W x H, film row y top-down; the frame's camera (o, l, hz, vt) =
+ * PtCamera.origin / lower_left / horizontal / vertical, the history's (o', l', hz', vt'); c the linear film, the pixel's
+ * feature record {albedo, emitter, normal n, depth d}; a = max(albedo, 1e-3), u_c = c / a, L_c = L(u_c) as above.
+ *   1 fresh        a pixel has no history when the history is empty (after pt_temporal_reset, on first use, after a
+ *                  pt_scene_upload, or when W or H changed), when d_p = 0 (a miss), or when the reprojection fails
+ *   2 reprojection s = (x + 0.5)/(W - 1), t = (H - 1 - y + 0.5)/(H - 1), D = l + s hz + t vt - o, P = o + d_p D/|D|;
+ *                  solve s' hz' + t' vt' - lambda (P - o') = o' - l' for (s', t', lambda): fails when singular or lambda <= 0;
+ *                  x' = s'(W - 1) - 0.5, y' = H - 0.5 - t'(H - 1), d_exp = |P - o'|.  When the camera equals the history's
+ *                  field by field: x' = x, y' = y, d_exp = d_p exactly.
+ *   3 taps         the bilinear 2x2 taps around (x', y') with the usual weights; tap q is valid iff it lies inside the
+ *                  image, d_q > 0, |d_q - d_exp| <= depth_tol d_exp, n_p.n_q >= normal_tol and (emitter_p > 0) ==
+ *                  (emitter_q > 0), with d_q, n_q, emitter_q of the history's frame.  S = the sum of the valid weights;
+ *                  S < 1e-2: fresh; else u_h, m1_h, m2_h, n_h = the valid-weighted means / S.  A fresh pixel has n_h = 0.
+ *   4 accumulate   (f32) n = n_h + 1, alpha' = max(alpha, 1/n), u = u_h + alpha'(u_c - u_h), m1 = m1_h + alpha'(L_c - m1_h),
+ *                  m2 = m2_h + alpha'(L_c^2 - m2_h); a fresh pixel: u = u_c exactly
+ *   5 variance     n >= 4: var = max(0, m2 - m1^2); else the 3x3 spatial variance of pt_denoise_device
+ *   6 filter       (u, var) through the a-trous iterations and the remodulation of pt_denoise_device (current albedo)
+ *   7 store        the history keeps the unfiltered (u, m1, m2, n), the frame's normal, depth and emitter flag, and the camera
+ * The first frame after a reset is bit-identical to pt_denoise_device.  The device computes the reprojection in f64, the
+ * rest in f32.  pt_default_temporal: alpha 0.2, depth_tol 0.1, normal_tol 0.9.                                          */
+typedef struct {
+    float alpha;             /* least blend weight of the new frame, in [0, 1]; 0 = running mean     */
+    float depth_tol;         /* relative depth tolerance of a history tap                            */
+    float normal_tol;        /* least cosine between the pixel's normal and a history tap's normal   */
+} PtTemporal;
+void pt_default_temporal(PtTemporal* out);
+/* Empties the context's history: the next frame is fresh everywhere. */
+int pt_temporal_reset(PtContext* ctx);
+/* Device buffers as pt_denoise_device, the image size = cam->width x cam->height (at least 2 x 2).  Asynchronous on the
+ * context's stream; needs no scene.  Context-owned memory, grown on first use and freed with the context: the two (u, var)
+ * planes of pt_denoise_device and two history buffers of 48 bytes per pixel (double-buffered: 96 bytes per pixel).
+ * PT_ERR_INVALID_ARG as pt_denoise_device, and alpha not in [0, 1], a negative or non-finite tolerance.                 */
+int pt_denoise_temporal_device(PtContext* ctx, const PtCamera* cam, const float* d_linear_rgb, const float* d_features,
+                               const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba8);
+/* One frame with HOST buffers (blocking), the temporal counterpart of pt_render_denoised: the render of params, the feature
+ * pass of min(feature_samples, params->spp) samples from params->spp_offset, then pt_denoise_temporal_device.         */
+int pt_render_denoised_temporal(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
+                                const PtDenoise* dn, const PtTemporal* tp, float* out_linear_rgb, uint8_t* out_rgba8,
+                                float* out_noisy_linear, float* out_features);
+
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on
  * entry like Ray::new (camera.rs:10-16); xy = n * (x, y) = the RNG key of each ray's stream, and the

@@ -101,6 +101,14 @@ class PtDenoise(C.Structure):
     ]
 
 
+class PtTemporal(C.Structure):
+    _fields_ = [
+        ("alpha", C.c_float),
+        ("depth_tol", C.c_float),
+        ("normal_tol", C.c_float),
+    ]
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -176,6 +184,12 @@ SYMBOLS = {
     "pt_denoise_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _P(PtDenoise), C.c_void_p, C.c_void_p]),
     "pt_render_denoised": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "pt_default_temporal": (None, [_P(PtTemporal)]),
+    "pt_temporal_reset": (C.c_int, [C.c_void_p]),
+    "pt_denoise_temporal_device": (C.c_int, [C.c_void_p, _P(PtCamera), C.c_void_p, C.c_void_p, _P(PtDenoise), _P(PtTemporal), C.c_void_p,
+                                             C.c_void_p]),
+    "pt_render_denoised_temporal": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

@@ -51,6 +51,16 @@ def default_denoise(**over):
     return d
 
 
+def default_temporal(**over):
+    """pt_default_temporal with keyword overrides (None keeps the default)."""
+    t = _lib.PtTemporal()
+    lib().pt_default_temporal(C.byref(t))
+    for k, v in over.items():
+        if v is not None:
+            setattr(t, k, v)
+    return t
+
+
 def builtin_scene(scene_id, arg=0):
     """Scenes of SURVEY 8(d): 1 reference Cornell box, 2 ten-sphere Cornell, 4 random spheres (arg = n)."""
     n = C.c_uint32(0)
@@ -341,6 +351,47 @@ class _ContextFunctions:
         check(lib().pt_render_denoised(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn),
                                        lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
                                        noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p)))
+        return lin, rgba, noisy, feat
+
+    def temporal_reset(self):
+        """pt_temporal_reset: the next temporal frame starts without history."""
+        check(lib().pt_temporal_reset(self._h))
+
+    def denoise_temporal(self, cam, linear, features, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None, alpha=None,
+                         depth_tol=None, normal_tol=None):
+        """pt_denoise_temporal_device on a film (f32[H,W,3]) of camera cam and its features (f32[H,W,8]), against the
+        context's history; unset parameters take pt_default_denoise / pt_default_temporal.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
+        import torch
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
+        linear = np.ascontiguousarray(linear, dtype=np.float32)
+        features = np.ascontiguousarray(features, dtype=np.float32)
+        H, W = cam.height, cam.width
+        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8)
+        dev = torch.device("cuda", self.device)
+        d_lin, d_feat = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev)
+        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_denoise_temporal_device(self._h, C.byref(cam), C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()),
+                                               C.byref(dn), C.byref(tp), C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
+        self.sync()
+        return out.cpu().numpy(), rgba.cpu().numpy()
+
+    def render_denoised_temporal(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
+                                 alpha=None, depth_tol=None, normal_tol=None):
+        """pt_render_denoised_temporal (host buffers, blocking): one frame of the temporal denoiser.  -> (linear f32[H,W,3],
+        rgba u8[H,W,4], noisy linear f32[H,W,3], features f32[H,W,8])"""
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
+        H, W = cam.height, cam.width
+        lin = np.empty((H, W, 3), dtype=np.float32)
+        rgba = np.empty((H, W, 4), dtype=np.uint8)
+        noisy = np.empty((H, W, 3), dtype=np.float32)
+        feat = np.empty((H, W, 8), dtype=np.float32)
+        check(lib().pt_render_denoised_temporal(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp),
+                                                lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
+                                                noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p)))
         return lin, rgba, noisy, feat
 
     def ray_color(self, params, rays, xy):

@@ -36,6 +36,7 @@ void launch_feature_rays_fast(const CameraF&, uint32_t, uint32_t, float*, hipStr
 void launch_feature_resolve_exact(const FeatureResolveArgs&, hipStream_t) { std::abort(); }
 void launch_feature_resolve_fast(const FeatureResolveArgs&, hipStream_t) { std::abort(); }
 void launch_denoise(const DenoiseArgs&, bool, hipStream_t) { std::abort(); }
+void launch_denoise_temporal(const TemporalArgs&, hipStream_t) { std::abort(); }
 }  // namespace ptk
 #endif
 
@@ -231,6 +232,12 @@ struct PtContext {
     DevBuf<int32_t> ft_ids;
     DevBuf<float4> ft_scratch, dn_plane[2], dn_feat;
     DevBuf<float> dn_lin;
+    // pt_denoise_temporal_device: two history buffers of 3 float4 per pixel (ptk::TemporalArgs), tm_hist[tm_cur] holds the
+    // last frame's when tm_valid; the camera and size of that frame
+    DevBuf<float4> tm_hist[2];
+    uint32_t tm_cur = 0;
+    bool tm_valid = false;
+    PtCamera tm_cam{};
 };
 
 namespace {
@@ -487,6 +494,7 @@ int pt_context_destroy(PtContext* c) {
     c->ad_list[0].release(); c->ad_list[1].release();
     c->ft_rays.release(); c->ft_t.release(); c->ft_rec.release(); c->ft_ids.release(); c->ft_scratch.release();
     c->dn_plane[0].release(); c->dn_plane[1].release(); c->dn_feat.release(); c->dn_lin.release();
+    c->tm_hist[0].release(); c->tm_hist[1].release();
     for (auto& b : c->inject) b.release();
     if (c->h_dstats) (void)hipHostFree(c->h_dstats);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -669,6 +677,7 @@ int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) {
     c->h_shape_tag.resize(n);
     for (uint32_t i = 0; i < n; ++i) c->h_shape_tag[i] = objs[i].shape_tag;
     c->has_scene = true;
+    c->tm_valid = false;              // object motion is out of scope: a new scene starts the temporal history afresh
     return PT_OK;
 }
 
@@ -1704,6 +1713,57 @@ void pt_default_denoise(PtDenoise* out) {
     out->iterations = 5; out->sigma_l = 4.0f; out->sigma_n = 128.0f; out->sigma_d = 0.025f;
 }
 
+}  // extern "C"
+
+namespace {
+// The a-trous iterations of pt_denoise_device and pt_denoise_temporal_device: (u, var) waits in plane 0; one k_denoise_step
+// per iteration between the two planes, the last launch writes the film planes.
+// pt_render_denoised and pt_render_denoised_temporal (tp != null): render, features, filter; host buffers, blocking
+int render_denoised_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
+                         const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                         float* out_features) {
+    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
+        return fail(PT_ERR_INVALID_ARG, "%s: renders the whole image (band_count = 1)", who);
+    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
+    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
+    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    const uint64_t np64 = (uint64_t)cam->width * cam->height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    const size_t np = (size_t)np64;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) ||
+        (rc = c->dn_lin.ensure(3 * np)))
+        return rc;
+    PtRenderParams p = *prm;
+    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
+    float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
+    uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
+    if ((rc = render_impl(c, cam, &p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
+        (rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat)) ||
+        (rc = tp ? pt_denoise_temporal_device(c, cam, c->host_lin.p, feat, dn, tp, c->dn_lin.p, rgba)
+                 : pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, feat, dn, c->dn_lin.p, rgba)) ||
+        (rc = pt_sync(c)))
+        return rc;
+    HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
+    if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_features) HIP_TRY(hipMemcpy(out_features, feat, 8 * np * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+int denoise_steps(PtContext* c, ptk::DenoiseArgs a, uint32_t iterations) {
+    for (uint32_t i = 0; i < iterations; ++i) {
+        a.src = c->dn_plane[i & 1u].p; a.dst = c->dn_plane[(i + 1u) & 1u].p;
+        a.step = 1u << i; a.finalize = i + 1u == iterations;
+        ptk::launch_denoise(a, false, c->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return PT_OK;
+}
+}  // namespace
+
+extern "C" {
+
 // The filter: k_denoise_init (u, var) into plane 0, then one k_denoise_step per iteration between the two planes; the last
 // launch writes the film planes.
 int pt_denoise_device(PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,
@@ -1731,44 +1791,87 @@ int pt_denoise_device(PtContext* c, uint32_t width, uint32_t height, const float
     a.dst = c->dn_plane[0].p; a.finalize = dn->iterations == 0;
     ptk::launch_denoise(a, true, c->stream);
     HIP_TRY(hipGetLastError());
-    for (uint32_t i = 0; i < dn->iterations; ++i) {
-        a.src = c->dn_plane[i & 1u].p; a.dst = c->dn_plane[(i + 1u) & 1u].p;
-        a.step = 1u << i; a.finalize = i + 1u == dn->iterations;
-        ptk::launch_denoise(a, false, c->stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return PT_OK;
+    return denoise_steps(c, a, dn->iterations);
 }
 
 int pt_render_denoised(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
                        float* out_linear, uint8_t* out_rgba, float* out_noisy, float* out_features) {
     if (!c || !cam || !prm || !dn || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised: null argument");
-    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "pt_render_denoised: renders the whole image (band_count = 1)");
-    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised: feature_samples must be > 0");
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    return render_denoised_impl("pt_render_denoised", c, cam, prm, feature_samples, dn, nullptr, out_linear, out_rgba, out_noisy,
+                                out_features);
+}
+
+void pt_default_temporal(PtTemporal* out) {
+    if (!out) return;
+    out->alpha = 0.2f; out->depth_tol = 0.1f; out->normal_tol = 0.9f;
+}
+
+int pt_temporal_reset(PtContext* c) {
+    if (!c) return fail(PT_ERR_INVALID_ARG, "pt_temporal_reset: null context");
+    c->tm_valid = false;
+    return PT_OK;
+}
+
+// Temporal accumulation: k_denoise_temporal (history -> (u, var) in plane 0 and the next history), then the a-trous steps of
+// pt_denoise_device.  The arguments are checked before the context is looked at.
+int pt_denoise_temporal_device(PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features,
+                               const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba) {
+    if (!cam || !dn || !tp || !d_linear || !d_features || !d_out_linear)
+        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: null argument");
+    if (cam->width < 2 || cam->height < 2)
+        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: %u iterations (at most 16)", dn->iterations);
+    if (!(dn->sigma_l >= 0.0f) || !(dn->sigma_n >= 0.0f) || !(dn->sigma_d >= 0.0f) || !std::isfinite(dn->sigma_l) ||
+        !std::isfinite(dn->sigma_n) || !std::isfinite(dn->sigma_d))
+        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: sigma_l, sigma_n and sigma_d must be finite and >= 0");
+    if (!(tp->alpha >= 0.0f && tp->alpha <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: alpha %g not in [0, 1]", tp->alpha);
+    if (!(tp->depth_tol >= 0.0f) || !(tp->normal_tol >= 0.0f) || !std::isfinite(tp->depth_tol) || !std::isfinite(tp->normal_tol))
+        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: depth_tol and normal_tol must be finite and >= 0");
+    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: d_features must be 16-byte aligned");
+    if ((uintptr_t)d_linear % 4u || (uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u)
+        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: the film buffers must be 4-byte aligned");
+    if (d_out_linear == d_linear) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: the output must not be the input");
     const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_render_denoised: %llu pixels", (unsigned long long)np64);
-    const size_t np = (size_t)np64;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_denoise_temporal_device: %llu pixels", (unsigned long long)np64);
+    if (!c) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: null context");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) ||
-        (rc = c->dn_lin.ensure(3 * np)))
+    if ((rc = c->dn_plane[0].ensure(np64)) || (rc = c->dn_plane[1].ensure(np64)) || (rc = c->tm_hist[0].ensure(3 * np64)) ||
+        (rc = c->tm_hist[1].ensure(3 * np64)))
         return rc;
-    PtRenderParams p = *prm;
-    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
-    float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
-    if ((rc = render_impl(c, cam, &p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
-        (rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat)) ||
-        (rc = pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, feat, dn, c->dn_lin.p, out_rgba ? c->host_rgba.p : nullptr)) ||
-        (rc = pt_sync(c)))
-        return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_features) HIP_TRY(hipMemcpy(out_features, feat, 8 * np * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    const bool have = c->tm_valid && c->tm_cam.width == cam->width && c->tm_cam.height == cam->height;
+    bool same = have;
+    for (int k = 0; k < 3; ++k)
+        same = same && c->tm_cam.origin[k] == cam->origin[k] && c->tm_cam.lower_left[k] == cam->lower_left[k] &&
+               c->tm_cam.horizontal[k] == cam->horizontal[k] && c->tm_cam.vertical[k] == cam->vertical[k];
+    ptk::TemporalArgs t{};
+    ptk::DenoiseArgs& a = t.dn;
+    a.linear = d_linear; a.feat = reinterpret_cast<const float4*>(d_features);
+    a.out_linear = d_out_linear; a.out_rgba = d_out_rgba;
+    a.width = cam->width; a.height = cam->height;
+    a.sigma_l = dn->sigma_l; a.sigma_n = dn->sigma_n; a.sigma_d = dn->sigma_d;
+    a.dst = c->dn_plane[0].p; a.finalize = dn->iterations == 0;
+    t.hist_src = have ? c->tm_hist[c->tm_cur].p : nullptr;
+    t.hist_dst = c->tm_hist[c->tm_cur ^ 1u].p;
+    for (int k = 0; k < 3; ++k) {
+        t.cur[k] = cam->origin[k]; t.cur[3 + k] = cam->lower_left[k]; t.cur[6 + k] = cam->horizontal[k]; t.cur[9 + k] = cam->vertical[k];
+        t.prev[k] = c->tm_cam.origin[k]; t.prev[3 + k] = c->tm_cam.lower_left[k];
+        t.prev[6 + k] = c->tm_cam.horizontal[k]; t.prev[9 + k] = c->tm_cam.vertical[k];
+    }
+    t.same_camera = same;
+    t.alpha = tp->alpha; t.depth_tol = tp->depth_tol; t.normal_tol = tp->normal_tol;
+    ptk::launch_denoise_temporal(t, c->stream);
+    HIP_TRY(hipGetLastError());
+    c->tm_cur ^= 1u; c->tm_valid = true; c->tm_cam = *cam;
+    return denoise_steps(c, a, dn->iterations);
+}
+
+int pt_render_denoised_temporal(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
+                                const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                                float* out_features) {
+    if (!c || !cam || !prm || !dn || !tp || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised_temporal: null argument");
+    return render_denoised_impl("pt_render_denoised_temporal", c, cam, prm, feature_samples, dn, tp, out_linear, out_rgba, out_noisy,
+                                out_features);
 }
 
 int pt_ray_color(PtContext* c, const PtRenderParams* prm, const double* rays, const uint32_t* xy, uint32_t n, float* out_rgb) {

@@ -308,4 +308,18 @@ struct DenoiseArgs {
 };
 void launch_denoise(const DenoiseArgs& a, bool init, hipStream_t st);
 
+// Temporal accumulation in front of the a-trous steps (pt_denoise_temporal_device; rule: include/pathtrace_amd.h PtTemporal).
+// One launch per frame in place of k_denoise_init: reads the film, the features and the history hist_src (null: none), writes
+// (u.rgb, var) to dn.dst (or, dn.finalize, the film planes) and the frame's history to hist_dst.  History record, 3 float4 per
+// pixel: (u.rgb, m1), (m2, n, emitter, 0), (normal xyz, depth).  Cameras in f64: the reprojection is computed in f64.
+struct TemporalArgs {
+    DenoiseArgs dn;
+    const float4* hist_src;
+    float4* hist_dst;
+    double cur[12], prev[12];  // origin, lower_left, horizontal, vertical of the frame's and of the history's camera
+    uint32_t same_camera;      // the two cameras are equal field by field: x' = x, y' = y, d_exp = d_p exactly
+    float alpha, depth_tol, normal_tol;
+};
+void launch_denoise_temporal(const TemporalArgs& a, hipStream_t st);
+
 }  // namespace ptk

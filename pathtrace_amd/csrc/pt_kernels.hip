@@ -2296,6 +2296,29 @@ PT_DEV float3 dn_demod(const DenoiseArgs& a, size_t q) {
     const float4 f0 = a.feat[2 * q];
     return make_float3(a.linear[3 * q] / dn_albedo(f0.x), a.linear[3 * q + 1] / dn_albedo(f0.y), a.linear[3 * q + 2] / dn_albedo(f0.z));
 }
+// the 3 x 3 population variance of L(u) around pixel (x, y), taps outside the image skipped: k_denoise_temporal's variance
+// of a pixel with fewer than 4 frames of history.  The statements are k_denoise_init's, in its order, so the value is the
+// same bits (tests/test_gpu_temporal.py); k_denoise_init keeps its own text because calling this function there changes
+// the instructions the compiler schedules for that kernel.
+PT_DEV float dn_spatial_var(const DenoiseArgs& a, uint32_t x, uint32_t y) {
+    float Ls[9];
+    uint32_t cnt = 0;
+    float sum = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = (int)x + dx, qy = (int)y + dy;
+            if (qx < 0 || qy < 0 || qx >= (int)a.width || qy >= (int)a.height) continue;
+            const float3 uq = dn_demod(a, (size_t)qy * a.width + qx);
+            Ls[cnt] = dn_lum(uq.x, uq.y, uq.z);
+            sum += Ls[cnt];
+            ++cnt;
+        }
+    const float mu = sum / (float)cnt;
+    float var = 0.0f;
+    for (uint32_t k = 0; k < cnt; ++k) var += (Ls[k] - mu) * (Ls[k] - mu);
+    var /= (float)cnt;
+    return var;
+}
 // first launch: u and the 3 x 3 population variance of L(u) (taps outside the image skipped); finalize: iterations = 0
 __global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_init(DenoiseArgs a) {
     const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
@@ -2381,6 +2404,108 @@ void launch_denoise(const DenoiseArgs& a, bool init, hipStream_t st) {
     const dim3 g((a.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy), b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
     if (init) hipLaunchKernelGGL(PTK_IMPL::k_denoise_init, g, b, 0, st, a);
     else hipLaunchKernelGGL(PTK_IMPL::k_denoise_step, g, b, 0, st, a);
+}
+}  // namespace ptk
+
+// ------------------------------------------------------------------ temporal accumulation (pt_denoise_temporal_device)
+// The rule is stated in include/pathtrace_amd.h (PtTemporal) and DESIGN.md 5c.  One thread per pixel, in place of k_denoise_init.
+// The reprojection runs in f64: an f32 solve puts x' about 1e-4 pixel off at 1024^2, and a bilinear tap of that weight moves
+// a dim pixel next to a bright one by far more than the accumulation's own rounding.  Everything after it is f32.
+namespace PTK_IMPL {
+PT_DEV double tm_dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+PT_DEV void tm_cross(const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+// pixel (x, y) at depth d seen from the frame's camera -> (x', y') in the history's image and d_exp; false: no reprojection
+PT_DEV bool tm_reproject(const TemporalArgs& a, uint32_t x, uint32_t y, float d, double& xr, double& yr, double& dexp) {
+    const double* o = a.cur; const double* l = a.cur + 3; const double* hz = a.cur + 6; const double* vt = a.cur + 9;
+    const double* o2 = a.prev; const double* l2 = a.prev + 3; const double* hz2 = a.prev + 6; const double* vt2 = a.prev + 9;
+    const double W1 = (double)(a.dn.width - 1u), H1 = (double)(a.dn.height - 1u);
+    const double s = ((double)x + 0.5) / W1, t = ((double)(a.dn.height - 1u - y) + 0.5) / H1;      // camera.rs:139-147, world.rs:299
+    double D[3], P[3], c[3], r[3], bc[3], rc[3], br[3];
+    for (int k = 0; k < 3; ++k) D[k] = l[k] + s * hz[k] + t * vt[k] - o[k];
+    const double inv_len = 1.0 / __builtin_sqrt(tm_dot(D, D));
+    for (int k = 0; k < 3; ++k) {
+        P[k] = o[k] + (double)d * (D[k] * inv_len);
+        c[k] = o2[k] - P[k];                 // -(P - o')
+        r[k] = o2[k] - l2[k];
+    }
+    // s' hz' + t' vt' + lambda c = r by Cramer's rule
+    tm_cross(vt2, c, bc);
+    const double det = tm_dot(hz2, bc);
+    if (!(det != 0.0) || !__builtin_isfinite(det)) return false;
+    tm_cross(r, c, rc);
+    tm_cross(vt2, r, br);
+    const double inv = 1.0 / det;
+    const double s2 = tm_dot(r, bc) * inv, t2 = tm_dot(hz2, rc) * inv, lam = tm_dot(hz2, br) * inv;
+    if (!(lam > 0.0) || !__builtin_isfinite(s2) || !__builtin_isfinite(t2) || !__builtin_isfinite(lam)) return false;
+    xr = s2 * W1 - 0.5;
+    yr = (double)a.dn.height - 0.5 - t2 * H1;
+    dexp = __builtin_sqrt(tm_dot(c, c));
+    return true;
+}
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_temporal(TemporalArgs a) {
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.dn.width || y >= a.dn.height) return;
+    const int W = (int)a.dn.width, H = (int)a.dn.height;
+    const size_t p = (size_t)y * a.dn.width + x;
+    const float4 f0p = a.dn.feat[2 * p], f1p = a.dn.feat[2 * p + 1];
+    const float3 uc = dn_demod(a.dn, p);
+    const float Lc = dn_lum(uc.x, uc.y, uc.z);
+    // the valid-weighted history of the 2 x 2 bilinear taps around (x', y')
+    float S = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hm1 = 0.0f, hm2 = 0.0f, hn = 0.0f;
+    if (a.hist_src && f1p.w > 0.0f) {
+        double xr = x, yr = y, dexp = f1p.w;
+        const bool ok = a.same_camera || tm_reproject(a, x, y, f1p.w, xr, yr, dexp);
+        if (ok && xr > -1.0 && xr < (double)W && yr > -1.0 && yr < (double)H) {      // else no tap lies inside the image
+            const int x0 = (int)__builtin_floor(xr), y0 = (int)__builtin_floor(yr);
+            const float fx = (float)(xr - x0), fy = (float)(yr - y0);
+            const float de = (float)dexp, dmax = a.depth_tol * de;
+            const bool em = f0p.w > 0.0f;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int qx = x0 + i, qy = y0 + j;
+                    const float w = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+                    if (!(w > 0.0f) || qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+                    const size_t q = (size_t)qy * W + qx;
+                    const float4 h2 = a.hist_src[3 * q + 2];
+                    if (!(h2.w > 0.0f) || !(fabsf(h2.w - de) <= dmax)) continue;
+                    if (!(f1p.x * h2.x + f1p.y * h2.y + f1p.z * h2.z >= a.normal_tol)) continue;
+                    const float4 h1 = a.hist_src[3 * q + 1];
+                    if (em != (h1.z > 0.0f)) continue;
+                    const float4 h0 = a.hist_src[3 * q];
+                    S += w;
+                    hr += w * h0.x; hg += w * h0.y; hb += w * h0.z; hm1 += w * h0.w;
+                    hm2 += w * h1.x; hn += w * h1.y;
+                }
+        }
+    }
+    float3 u = uc;
+    float m1 = Lc, m2 = Lc * Lc, n = 1.0f;            // a fresh pixel
+    if (S >= 1e-2f) {
+        const float inv = 1.0f / S;
+        const float ur = hr * inv, ug = hg * inv, ub = hb * inv, um1 = hm1 * inv, um2 = hm2 * inv;
+        n = hn * inv + 1.0f;
+        const float al = fmaxf(a.alpha, 1.0f / n);
+        u = make_float3(ur + al * (uc.x - ur), ug + al * (uc.y - ug), ub + al * (uc.z - ub));
+        m1 = um1 + al * (Lc - um1);
+        m2 = um2 + al * (Lc * Lc - um2);
+    }
+    const float var = n >= 4.0f ? fmaxf(0.0f, m2 - m1 * m1) : dn_spatial_var(a.dn, x, y);
+    a.hist_dst[3 * p] = make_float4(u.x, u.y, u.z, m1);
+    a.hist_dst[3 * p + 1] = make_float4(m2, n, f0p.w, 0.0f);
+    a.hist_dst[3 * p + 2] = f1p;
+    if (a.dn.finalize) dn_store(a.dn, p, u.x, u.y, u.z, f0p);
+    else a.dn.dst[p] = make_float4(u.x, u.y, u.z, var);
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_denoise_temporal(const TemporalArgs& a, hipStream_t st) {
+    const dim3 g((a.dn.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.dn.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy),
+        b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
+    hipLaunchKernelGGL(PTK_IMPL::k_denoise_temporal, g, b, 0, st, a);
 }
 }  // namespace ptk
 #endif      // !PT_MATH_EXACT

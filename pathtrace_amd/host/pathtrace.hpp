@@ -12,6 +12,7 @@
 //   World::new()  (the Cornell box)           src/world.rs:65-241
 //   World::render()  == the closure of main() src/main.rs:43-60  (new name)
 //   World::render_denoised()  render() + first-hit features + the a-trous denoiser (beyond the reference)
+//   World::render_denoised_temporal()  the same with temporal accumulation over the frames of the persistent context
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -455,6 +456,33 @@ public:
             for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
         }
     }
+    // Temporal form of render_denoised() (pt_render_denoised_temporal): one frame of a sequence; the history lives in the
+    // World's persistent context and follows camera moves (set_camera) by reprojection.  tp: pt_default_temporal when null.
+    void render_denoised_temporal(uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, const PtTemporal* tp = nullptr,
+                                  std::vector<Vector3>* noisy = nullptr, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtDenoise d{};
+        if (dn) d = *dn; else pt_default_denoise(&d);
+        PtTemporal t{};
+        if (tp) t = *tp; else pt_default_temporal(&t);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3), raw(noisy ? n * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_denoised_temporal(ctx_, &camera_.pod(), &p, feature_samples, &d, &t, lin.data(), rgba.data(),
+                                          noisy ? raw.data() : nullptr, nullptr));
+        unpack(lin, rgba);
+        if (noisy) {
+            noisy->resize(n);
+            for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+        }
+    }
+    // the next render_denoised_temporal starts without history (pt_temporal_reset)
+    void temporal_reset() { if (ctx_) check(pt_temporal_reset(ctx_)); }
+    // moves the camera (the film follows its size); the temporal history stays and is reprojected
+    void set_camera(const Camera& camera) { camera_ = camera; resize_film(); }
     PtStats stats() { PtStats s{}; if (ctx_) check(pt_get_stats(ctx_, &s)); return s; }
 
     // World::draw (world.rs:335-341): blit RGBA8 into a frame of 4*W*H bytes

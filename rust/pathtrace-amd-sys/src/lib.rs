@@ -96,6 +96,15 @@ pub struct PtDenoise {
     pub sigma_d: f32,
 }
 
+/// pt_denoise_temporal_device: temporal accumulation with camera reprojection (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtTemporal {
+    pub alpha: f32,
+    pub depth_tol: f32,
+    pub normal_tol: f32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct PtStats {
@@ -248,6 +257,10 @@ extern "C" {
     pub fn pt_default_denoise(out: *mut PtDenoise);
     pub fn pt_denoise_device(ctx: *mut PtContext, width: u32, height: u32, d_linear_rgb: *const f32, d_features: *const f32, dn: *const PtDenoise, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_denoised(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
+    pub fn pt_default_temporal(out: *mut PtTemporal);
+    pub fn pt_temporal_reset(ctx: *mut PtContext) -> c_int;
+    pub fn pt_denoise_temporal_device(ctx: *mut PtContext, cam: *const PtCamera, d_linear_rgb: *const f32, d_features: *const f32, dn: *const PtDenoise, tp: *const PtTemporal, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_denoised_temporal(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, tp: *const PtTemporal, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
     pub fn pt_ray_color(ctx: *mut PtContext, params: *const PtRenderParams, rays: *const f64, xy: *const u32, n: u32, out_rgb: *mut f32) -> c_int;
     pub fn pt_debug_hit_scene(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_t: *mut f32) -> c_int;
     pub fn pt_debug_hit_records(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_rec: *mut f32) -> c_int;
