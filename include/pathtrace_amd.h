@@ -552,6 +552,15 @@ int pt_debug_light_point(PtContext* ctx, const double* from3, const uint32_t* wo
 int pt_debug_camera_rays(PtContext* ctx, const PtCamera* cam, const uint32_t* xys, uint32_t n, uint32_t exact_math,
                          float* out8);
 
+/* Debug/parity entry: the two-ray scan of the regenerating path kernel (a visibility ray and a path ray from one origin
+ * through the scene records in one pass) beside the two single-ray scans it stands for.  Scenes that live in LDS only
+ * (PT_ERR_UNSUPPORTED otherwise).  rays10 = n * (origin3, dir_a3, dir_b3, t_max_a); directions are taken as given (not
+ * normalised).  out6 = n * 6 raw 32-bit words: joint scan (hit on ray a as 0/1, object on ray b or -1, bound of ray b
+ * after the scan as f32), then the same three from the separate any-hit and closest-hit scans.  Equal words = equal
+ * results.                                                                                                            */
+int pt_debug_joint_scan(PtContext* ctx, const double* rays10, uint32_t n, double t_min, double t_max_b,
+                        uint32_t exact_math, float* out6);
+
 /* Debug entry, host only (no GPU needed): build the accel = 1 BVH of a scene and verify it -- every object in
  * exactly one leaf slot with its scan record, every child box encloses the boxes beneath it, depth within the
  * traversal stack.  Returns PT_OK and the tree's size, or PT_ERR_UNSUPPORTED with the violated invariant in

@@ -174,6 +174,7 @@ SYMBOLS = {
                                         C.c_uint32, _P(C.c_float)]),
     "pt_debug_light_point": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_uint32, _P(C.c_float)]),
     "pt_debug_camera_rays": (C.c_int, [C.c_void_p, _P(PtCamera), _P(C.c_uint32), C.c_uint32, C.c_uint32, _P(C.c_float)]),
+    "pt_debug_joint_scan": (C.c_int, [C.c_void_p, _P(C.c_double), C.c_uint32, C.c_double, C.c_double, C.c_uint32, _P(C.c_float)]),
     "pt_debug_bvh_check": (C.c_int, [_P(PtObject), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "pt_render_pixels": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(C.c_uint32), C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),

@@ -1369,6 +1369,18 @@ int pt_debug_camera_rays(PtContext* c, const PtCamera* cam, const uint32_t* xys,
     return debug_fn(c, ptk::kFnCameraRay, 0, std::vector<float>(), 1, w.data(), n, 8, exact_math, cam, out8);
 }
 
+int pt_debug_joint_scan(PtContext* c, const double* rays10, uint32_t n, double t_min, double t_max_b, uint32_t exact_math, float* out6) {
+    if (!rays10 && n) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (c && c->has_scene && (c->view.n_objs > ptk::kSmallObjs || c->view.blob_f4 == 0))
+        return fail(PT_ERR_UNSUPPORTED, "pt_debug_joint_scan: the scene (%u objects) does not live in LDS", c->view.n_objs);
+    std::vector<float> in(12 * (size_t)n);
+    for (size_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 10; ++k) in[12 * i + k] = (float)rays10[10 * i + k];
+        in[12 * i + 10] = (float)t_min; in[12 * i + 11] = (float)t_max_b;
+    }
+    return debug_fn(c, ptk::kFnJointScan, 0, in, 12, nullptr, n, 6, exact_math, nullptr, out6);
+}
+
 int pt_debug_bvh_check(const PtObject* objs, uint32_t n, uint32_t* depth, uint32_t* n_nodes, uint32_t* n_leaf_slots) {
     if (!objs && n) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_check: null objects");
     if (n >= (1u << 28)) return fail(PT_ERR_UNSUPPORTED, "accel: %u objects exceed the 2^28 leaf slots", n);

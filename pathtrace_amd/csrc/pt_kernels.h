@@ -263,7 +263,8 @@ void launch_debug_hit_fast(const SceneView& sc, uint32_t accel, const float* ray
                            float4* scratch, int32_t* out_id, float* out_t, float* out_rec, hipStream_t st);
 
 // The per-vertex functions on arbitrary inputs (debug/parity entries; layouts at k_debug_fn in pt_kernels.hip).
-enum { kFnBsdfEval = 0, kFnBsdfSample = 1, kFnShapeSample = 2, kFnLightPoint = 3, kFnCameraRay = 4 };
+enum { kFnBsdfEval = 0, kFnBsdfSample = 1, kFnShapeSample = 2, kFnLightPoint = 3, kFnCameraRay = 4,
+       kFnJointScan = 5 };     // (a kernel of its own: the scene staged in LDS; scenes of <= kSmallObjs objects)
 struct DebugFnArgs {
     SceneView sc;
     CameraF cam;              // kFnCameraRay only

@@ -18,6 +18,7 @@
 //                             world.rs:299) or, in a continuation launch (OVF), takes over the overflow queue.
 //   k_paths_regen<MIS, MATS>  level-0 launch of a batch of > 2^17 paths over a scene in LDS: a path stays in its lane's registers,
 //                             a lane whose path ends takes the batch's next one (chunk counters); compiled per material set.
+//                             A vertex's visibility ray and the next path ray go through the scene in one pass (scan_closest2).
 //   k_paths_regen_split<..>   the same for scenes with a few Mirror objects (the reference's own): a wave's Mirror vertices are
 //                             set aside on a per-wave stack and shaded 64 at a time.
 //   k_paths_bvh<MIS, OVF>     the queue form for PtRenderParams.accel = 1: hit_scene by traversal of a 4-wide BVH, each pass cut
@@ -343,6 +344,87 @@ PT_DEV void scan_closest(const SceneRef& sc, f3 o, f3 d, float t_min, float t_ma
     id_out = id;
     t_out = closest;
 }
+// ------------------------------------------------------------------ two rays from one origin in one pass over the scene
+// k_paths_regen's visibility ray of vertex k and path ray of vertex k + 1 both start at the hit point of vertex k.  scan_closest2
+// takes them through the records together: ray A is the visibility query (ANY: fixed bound t_max_a, only "anything accepted":
+// id_a >= 0), ray B the closest-hit query (shrinking bound, (id, t)).  Per record and per ray the operations are those of
+// scan_run<false, true> / scan_run<false, false>, in the same order, with the same NaN and tie rules; shared are the record read
+// and oc = o - centre (s = o - v0 for triangles): the same subtraction of the same operands, so identical bits.  The scheduler gets
+// two independent dependency chains per record.
+PT_DEV void sphere_pre2(float4 s, f3 o, f3 da, f3 db, float& half_a, float& disc_a, float& half_b, float& disc_b) {
+    const f3 oc = o - mk(s.x, s.y, s.z);
+    half_a = dot(oc, da);
+    half_b = dot(oc, db);
+    const f3 la = madd(da, -half_a, oc);
+    const f3 lb = madd(db, -half_b, oc);
+    disc_a = s.w - dot(la, la);
+    disc_b = s.w - dot(lb, lb);
+}
+// (the root parts stay two branches: both behind one branch "either discriminant accepted" interleaves the chains in the ISA and
+// was measured slower -- docs/EXPERIMENTS.md, "One scene pass for shadow ray and next path ray")
+PT_DEV void sphere_post2(float ha, float da, float hb, float db, float t_min, float bound_a, int& id_a, float& closest, int& id, int obj) {
+    sphere_post<true>(ha, da, t_min, bound_a, id_a, obj);
+    sphere_post<false>(hb, db, t_min, closest, id, obj);
+}
+PT_DEV void scan_run2(const float4* __restrict__ p, uint32_t tag, uint32_t n, int first_obj, f3 o, f3 da, f3 db, float t_min,
+                      float bound_a, int& id_a, float& closest, int& id) {
+    if (tag == SHAPE_SPHERE) {
+        uint32_t i = 0;
+        for (; i + 4u <= n; i += 4u) {
+            const float4 s0 = p[i], s1 = p[i + 1], s2 = p[i + 2], s3 = p[i + 3];
+            float ha0, ha1, ha2, ha3, da0, da1, da2, da3, hb0, hb1, hb2, hb3, db0, db1, db2, db3;
+            sphere_pre2(s0, o, da, db, ha0, da0, hb0, db0); sphere_pre2(s1, o, da, db, ha1, da1, hb1, db1);
+            sphere_pre2(s2, o, da, db, ha2, da2, hb2, db2); sphere_pre2(s3, o, da, db, ha3, da3, hb3, db3);
+            sphere_post2(ha0, da0, hb0, db0, t_min, bound_a, id_a, closest, id, first_obj + (int)i);
+            sphere_post2(ha1, da1, hb1, db1, t_min, bound_a, id_a, closest, id, first_obj + (int)i + 1);
+            sphere_post2(ha2, da2, hb2, db2, t_min, bound_a, id_a, closest, id, first_obj + (int)i + 2);
+            sphere_post2(ha3, da3, hb3, db3, t_min, bound_a, id_a, closest, id, first_obj + (int)i + 3);
+        }
+        if (i + 2u <= n) {
+            const float4 s0 = p[i], s1 = p[i + 1];
+            float ha0, ha1, da0, da1, hb0, hb1, db0, db1;
+            sphere_pre2(s0, o, da, db, ha0, da0, hb0, db0); sphere_pre2(s1, o, da, db, ha1, da1, hb1, db1);
+            sphere_post2(ha0, da0, hb0, db0, t_min, bound_a, id_a, closest, id, first_obj + (int)i);
+            sphere_post2(ha1, da1, hb1, db1, t_min, bound_a, id_a, closest, id, first_obj + (int)i + 1);
+            i += 2u;
+        }
+        for (; i < n; ++i) {
+            float ha0, da0, hb0, db0;
+            sphere_pre2(p[i], o, da, db, ha0, da0, hb0, db0);
+            sphere_post2(ha0, da0, hb0, db0, t_min, bound_a, id_a, closest, id, first_obj + (int)i);
+        }
+    } else if (tag == kRunTriangle) {
+        // one record read, the two existing tests (their s = o - v0 is one common subexpression)
+        for (uint32_t i = 0; i < n; ++i) {
+            const float4 a0 = p[3 * i], a1 = p[3 * i + 1], a2 = p[3 * i + 2];
+            float ca = bound_a;
+            triangle_test<false, true>(a0, a1, a2, o, da, t_min, ca, id_a, first_obj + (int)i);
+            triangle_test<false, false>(a0, a1, a2, o, db, t_min, closest, id, first_obj + (int)i);
+        }
+    } else {
+        for (uint32_t i = 0; i < n; ++i) {
+            const float4 a0 = p[5 * i], a1 = p[5 * i + 1], a2 = p[5 * i + 2], a3 = p[5 * i + 3], a4 = p[5 * i + 4];
+            float ca = bound_a;
+            tripair_test<true>(a0, a1, a2, a3, a4, o, da, t_min, ca, id_a, first_obj + 2 * (int)i);
+            tripair_test<false>(a0, a1, a2, a3, a4, o, db, t_min, closest, id, first_obj + 2 * (int)i);
+        }
+    }
+}
+// id_a >= 0: something lies on ray A inside [t_min, t_max_a]; (id_b, t_b): World::hit_scene of ray B, as scan_closest gives it
+template <int MODE>
+PT_DEV void scan_closest2(const SceneRef& sc, f3 o, f3 da, float t_max_a, f3 db, float t_min, float t_max_b, int& id_a, int& id_b,
+                          float& t_b) {
+    static_assert(MODE == kModeLds, "the whole scan array in LDS");
+    float closest = t_max_b;
+    int ia = -1, ib = -1;
+    for (uint32_t r = 0; r < sc.n_runs; ++r) {
+        Run run = sc.runs[r];
+        run.tag = __builtin_amdgcn_readfirstlane(run.tag); run.first_obj = __builtin_amdgcn_readfirstlane(run.first_obj);
+        run.count = __builtin_amdgcn_readfirstlane(run.count); run.off4 = __builtin_amdgcn_readfirstlane(run.off4);
+        scan_run2(sc.scan + run.off4, run.tag, run.count, (int)run.first_obj, o, da, db, t_min, t_max_a, ia, closest, ib);
+    }
+    id_a = ia; id_b = ib; t_b = closest;
+}
 // the same scan with every record read from global memory (no LDS, no barrier: any subset of lanes may call it)
 PT_DEV void scan_global(const SceneRef& sc, f3 o, f3 d, float t_min, float t_max, int& id_out, float& t_out) {
     float closest = t_max;
@@ -578,9 +660,25 @@ PT_DEV void vertex_begin(const SceneRef& sc, PathState& p, bool active, int id, 
 // REMAT (scene in LDS): the material of the hit object and the light's emission are read again here instead of
 // being carried across the visibility scan -- two broadcast LDS reads instead of ~6 live registers, which is what
 // keeps the kernel at 80 VGPRs without spills.
-template <bool MIS, int DIFFUSE, bool REMAT>
+// DEFER (k_paths_regen, whose visibility scan runs together with the next closest-hit scan): `visible` is not known yet.  The NEE
+// term is evaluated as if visible and, where the original adds it to L, handed to `pd` together with the throughput it is to
+// be multiplied with; vertex_finish adds it -- or exactly 0 -- once the scan is through.  Nothing else of the vertex reads
+// `visible`, and nothing touches L in between, so a path's arithmetic is unchanged.  A path that ends here with its term
+// pending (black throughput, depth limit) keeps the hit point as p.o: its visibility ray starts there.
+struct Pending {
+    bool on;                 // L = L + beta * (visible ? direct : 0) is still to be done
+    f3 beta, direct;
+};
+PT_DEV void vertex_finish(PathState& p, Pending& pd, bool visible) {
+    if (pd.on) {
+        const f3 direct = visible ? pd.direct : mk(0.f, 0.f, 0.f);
+        p.L = p.L + pd.beta * direct;
+        pd.on = false;
+    }
+}
+template <bool MIS, int DIFFUSE, bool REMAT, bool DEFER = false>
 PT_DEV bool vertex_end(const SceneRef& sc, PathState& p, const Vertex& vin, bool visible, uint32_t sample, uint32_t kx,
-                       uint32_t py, uint32_t min_depth, uint32_t max_depth) {
+                       uint32_t py, uint32_t min_depth, uint32_t max_depth, Pending* pd = nullptr) {
     const uint32_t n_lights = sc.n_lights;
     Vertex v = vin;
     if (REMAT) {
@@ -599,7 +697,7 @@ PT_DEV bool vertex_end(const SceneRef& sc, PathState& p, const Vertex& vin, bool
         }
     }
     f3 direct = mk(0.f, 0.f, 0.f);
-    if (MIS && visible) {
+    if (MIS && (DEFER ? vin.need_shadow : visible)) {
         float cos_theta = __builtin_fabsf(dot(v.hit.normal, v.light_dir));    // rendering.rs:68
         f3 bsdf; float pdf_bsdf;
         bsdf_pdf(v.m, p.d, p.eta_in, v.light_dir, v.hit.normal, bsdf, pdf_bsdf);   // :71-72 (stale eta, Q5)
@@ -627,10 +725,12 @@ PT_DEV bool vertex_end(const SceneRef& sc, PathState& p, const Vertex& vin, bool
         if (u01(w_rr) > rr) {                                                 // :100-102 (drops direct, Q1)
             alive = false;
         } else {
-            p.L = p.L + p.beta * direct;
+            if (DEFER) { pd->on = true; pd->beta = p.beta; pd->direct = direct; }
+            else p.L = p.L + p.beta * direct;
             p.beta = rr == 1.0f ? next_tp : next_tp / rr;                     // :129 (x * (1/1) == x exactly)
             if (is_zero(p.beta) || p.depth >= 65534u) {                       // Q7: nothing downstream contributes
                 alive = false;
+                if (DEFER) p.o = v.hit.point;
             } else {
                 p.pdf_prev = pdf;
                 p.o = v.hit.point;
@@ -894,8 +994,21 @@ k_paths(BounceArgs a) {
 //     threshold it appends what is alive below it to the overflow queue, as k_paths does (measured: not faster).
 //   * The results do not depend on which lane traced which path: the RNG is addressed by (pixel, sample, depth), every
 //     sample has its own slot of lsamp, and the statistics are sums.
-// Occupancy the variants are compiled for (pt_kernels.h: the host sizes the grid by it): the DIFFUSE variant needs 79 VGPRs
-// (6 waves per SIMD), the generic one 93 (5; reached only with PtTuning.level0_form = 2).
+//   * Order of an iteration (MIS instances).  The visibility ray of vertex k and the path ray of vertex k + 1 both start at the
+//     hit point of vertex k, and nothing of vertex k but its NEE term reads `visible` (the BSDF sample, throughput and roulette
+//     do not).  So the two rays share ONE pass over the scene (scan_closest2), at the top of the NEXT iteration:
+//         refill vacant lanes -> joint scan (A: pending visibility ray, B: path ray) -> vertex_finish: the pending term of
+//         vertex k, L += beta_k * (visible ? direct : 0) -> vertex_begin of vertex k + 1 -> vertex_end<DEFER>: everything else
+//         of vertex k + 1; its own term (old beta, direct as if visible) goes into LDS (s_park) until the next scan is through.
+//     Per path the operations and their operands are those of k_paths, which keeps the two scans apart (the bit-exactness
+//     oracle: test_level0_forms_give_the_same_film, the fuzz and instance tests, tests/test_gpu_joint_scan.py).  A path that
+//     ends by miss, emitter or roulette has no term pending and retires at once; one that ends WITH a term pending (black
+//     throughput, depth limit) keeps its lane for one more scan -- the lane is not vacant and counts as busy -- and retires
+//     after vertex_finish.  When the loop ends, the terms still pending get a visibility scan of their own before the hand-over,
+//     so the state a continuation launch resumes is what it always was.  wave_shadow counts a ray where its vertex asks for it.
+//     BRDF-only instances have no visibility ray: one scan per iteration, as before.
+// Occupancy the variants are compiled for (pt_kernels.h: the host sizes the grid by it): the DIFFUSE variant needs 80 VGPRs
+// (6 waves per SIMD), the generic ones 95-96 (5; reached only with PtTuning.level0_form = 2); none spills.
 // Finished samples (stats[4]; pt_sync compares the sum with pixels x spp).  The queue-form kernels count the lanes that write their
 // radiance to the sample buffer (a ballot at the store).  In the regenerating kernels a lane's ONLY transition from "has a path" to
 // "has none" is that store, and paths enter a wave only from its ring, so finished = (entries taken from the ring) - (paths handed
@@ -925,6 +1038,9 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
     __shared__ float4 s_pool_d[kRegenBlock / 64][kPool];      // (d.x, d.y, d.z, bits(tile_row << 16 | x))
     __shared__ uint32_t s_pool_s[kRegenBlock / 64][kPool];    // s_local << 16 (depth 0)
     __shared__ WgTotals s_totals;
+    // MIS: the pending NEE term of every lane (Pending::beta, ::direct) sits here during the joint scan instead of in six registers
+    // (2 KB per wave; a lane reads only what it wrote itself: no barrier)
+    __shared__ float4 s_park[MIS ? kRegenBlock / 64 : 1][2][64];
     if (threadIdx.x == 0u) wg_totals_init(s_totals);
     // Spare workgroups (BounceArgs.posted): in a sequence of overlapping launches only the first core_blocks of a launch work -- two
     // launches then sit side by side and the third fills the slots the first frees while it runs dry -- but the LAST launches of
@@ -941,6 +1057,8 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
     const uint32_t wib = threadIdx.x >> 6;
     float4* const pool_d = s_pool_d[wib];
     uint32_t* const pool_s = s_pool_s[wib];
+    float4* const park0 = &s_park[MIS ? wib : 0u][0][lane];
+    float4* const park1 = &s_park[MIS ? wib : 0u][1][lane];
     const uint32_t n_first = a.n_first;
     const uint32_t n_chunks = (n_first + 63u) >> 6;
     const uint32_t W = a.film_w;
@@ -956,6 +1074,28 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
     uint32_t dmax = 0;                     // per lane: deepest vertex of the paths this lane finished
     PathState p = parked_state();
     bool alive = false;
+    // MIS: the NEE term of the lane's previous vertex, waiting for the visibility its ray (sdir, bound smax, from p.o) finds in
+    // the joint scan of the next iteration.  pd.on && !alive: the path ended at that vertex; the lane takes no new path until the
+    // term is in and the radiance stored.
+    Pending pd;
+    pd.on = false; pd.beta = mk(0.f, 0.f, 0.f); pd.direct = mk(0.f, 0.f, 0.f);
+    f3 sdir = parked_dir();
+    float smax = -1.0f;
+    // a finished path: radiance to its sample slot, the lane parked until it gets its next path (end of the batch: for good)
+    auto park = [&]() {
+        *park0 = make_float4(pd.beta.x, pd.beta.y, pd.beta.z, pd.direct.x);
+        *park1 = make_float4(pd.direct.y, pd.direct.z, 0.0f, 0.0f);
+    };
+    auto unpark = [&]() {
+        asm volatile("" ::: "memory");          // a real read after the scan, not the values kept alive across it
+        const float4 k0 = *park0, k1 = *park1;
+        pd.beta = mk(k0.x, k0.y, k0.z); pd.direct = mk(k0.w, k1.x, k1.y);
+    };
+    auto retire = [&]() {
+        a.lsamp[p.s_local * a.np + p.yl * W + p.px] = Rgb{p.L.x, p.L.y, p.L.z};
+        dmax = p.depth > dmax ? p.depth : dmax;
+        p.o = parked_origin(); p.d = parked_dir();
+    };
 #ifdef PT_DRAIN_TIMING      // measurement build: when does the batch run out under the waves, when does the last wave end
     const unsigned long long t_begin = wall_clock64();
     unsigned long long t_exhausted = 0ull;
@@ -1001,9 +1141,10 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
         __builtin_amdgcn_wave_barrier();
         // ---- lanes without a path take the ring's next entries, in lane order
         {
-            const unsigned long long need = __ballot(!alive);
+            const bool vacant = !alive && !(MIS && pd.on);
+            const unsigned long long need = __ballot(vacant);
             const uint32_t r = lane_rank(need);
-            if (!alive && r < pool_cnt) {
+            if (vacant && r < pool_cnt) {
                 const uint32_t e = (pool_head + r) & (kPool - 1u);
                 const float4 q = pool_d[e];
                 const uint32_t sd = pool_s[e];
@@ -1022,8 +1163,10 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
         }
         __builtin_amdgcn_wave_barrier();
         const uint32_t n_alive = (uint32_t)__popcll(__ballot(alive));
-        // running dry (only once the batch is exhausted): hand the rest over
-        if (n_alive < a.export_below) break;           // export_below >= 1: a wave without paths ends
+        // running dry (only once the batch is exhausted): hand the rest over.  A lane that still owes its ended path the NEE term
+        // counts as busy: it took no new path above, and that must not look like the batch running out.
+        const uint32_t n_busy = MIS ? (uint32_t)__popcll(__ballot(alive || pd.on)) : n_alive;
+        if (n_busy < a.export_below) break;            // export_below >= 1: a wave without paths ends
 
         const bool active = alive;
         uint32_t kx = p.px, py = image_row(a.tile, p.yl);
@@ -1031,30 +1174,51 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
         const uint32_t sample = a.s_base + p.s_local;
         wave_vertices += n_alive;
 
-        // ---- scan #1: closest hit of the path ray (rendering.rs:41)
-        int id; float t;
-        scan_closest<kModeLds, false>(sc, p.o, p.d, a.t_min, kInf, id, t);
-        Vertex v;
-        vertex_begin<MIS, DIFFUSE>(sc, p, active, id, t, sample, kx, py, v);
-
-        // ---- scan #2: visibility (rendering.rs:62-65)
-        bool visible = false;
-        if (MIS) {
-            const unsigned long long sm = __ballot(v.need_shadow);
-            if (sm != 0ull) {
-                f3 sdir = v.need_shadow ? v.light_dir : parked_dir();
-                f3 sorg = v.need_shadow ? v.hit.point : parked_origin();
-                int sid; float st;
-                scan_closest<kModeLds, true>(sc, sorg, sdir, a.t_min, v.distance - a.t_min, sid, st);
-                visible = v.need_shadow && sid < 0;
-                wave_shadow += (uint32_t)__popcll(sm);
-            }
+        if constexpr (MIS) {
+            // ---- ONE pass over the scene for two rays from p.o: A = visibility of the previous vertex's light point (rendering.rs:62-65),
+            // B = closest hit of the path ray (rendering.rs:41).  A lane with nothing pending sends its path ray as A with an empty
+            // range (nothing is accepted, and its discriminants are B's: no root part runs that B's would not run anyway).
+            const bool shadow = pd.on && sc.n_lights > 0u;
+            int id, sid = -1; float t;
+            if (__ballot(shadow) != 0ull)
+                scan_closest2<kModeLds>(sc, p.o, shadow ? sdir : p.d, shadow ? smax : -1.0f, p.d, a.t_min, kInf, sid, id, t);
+            else
+                scan_closest<kModeLds, false>(sc, p.o, p.d, a.t_min, kInf, id, t);
+            // ---- the previous vertex's NEE term, now that its visibility is known; a path that ended there retires
+            const bool ended = pd.on && !alive;
+            unpark();
+            vertex_finish(p, pd, shadow && sid < 0);
+            if (ended) retire();
+            // ---- the new vertex up to the point where its own visibility is needed
+            Vertex v;
+            vertex_begin<MIS, DIFFUSE>(sc, p, active, id, t, sample, kx, py, v);
+            wave_shadow += (uint32_t)__popcll(__ballot(v.need_shadow));
+            alive = vertex_end<MIS, DIFFUSE, true, true>(sc, p, v, false, sample, kx, py, a.min_depth, a.max_depth, &pd);
+            sdir = v.light_dir; smax = v.distance - a.t_min;
+            park();
+            if (active && !alive && !pd.on) retire();
+        } else {
+            int id; float t;
+            scan_closest<kModeLds, false>(sc, p.o, p.d, a.t_min, kInf, id, t);
+            Vertex v;
+            vertex_begin<MIS, DIFFUSE>(sc, p, active, id, t, sample, kx, py, v);
+            alive = vertex_end<MIS, DIFFUSE, true>(sc, p, v, false, sample, kx, py, a.min_depth, a.max_depth);
+            if (active && !alive) retire();
         }
-        alive = vertex_end<MIS, DIFFUSE, true>(sc, p, v, visible, sample, kx, py, a.min_depth, a.max_depth);
-        if (active && !alive) {
-            a.lsamp[p.s_local * a.np + p.yl * W + p.px] = Rgb{p.L.x, p.L.y, p.L.z};
-            dmax = p.depth > dmax ? p.depth : dmax;
-            p.o = parked_origin(); p.d = parked_dir();  // until the lane gets its next path (end of the batch: for good)
+    }
+
+    // ---- the terms still pending when the loop ends (the batch ran out, or a path ended at the wave's last vertex): their
+    // visibility scan on its own, as k_paths runs it
+    if constexpr (MIS) {
+        if (__ballot(pd.on) != 0ull) {
+            const bool shadow = pd.on && sc.n_lights > 0u;
+            int sid = -1; float st;
+            if (__ballot(shadow) != 0ull)
+                scan_closest<kModeLds, true>(sc, shadow ? p.o : parked_origin(), shadow ? sdir : parked_dir(), a.t_min, smax, sid, st);
+            const bool ended = pd.on && !alive;
+            unpark();
+            vertex_finish(p, pd, shadow && sid < 0);
+            if (ended) retire();
         }
     }
 
@@ -2157,6 +2321,33 @@ __global__ void __launch_bounds__(kBlock) k_debug_fn(DebugFnArgs a) {
     }
 }
 
+// kFnJointScan: scan_closest2 (k_paths_regen's joint scan) beside the two scans it stands for, on arbitrary ray pairs out of LDS.
+//   in[12] = origin3, dir_a3, dir_b3 (taken as given: not normalised), t_max_a, t_min, t_max_b
+//   -> out[6] = joint (bits(id_a >= 0), bits(id_b), t_b), separate (bits(id >= 0) of scan_closest<ANY>, bits(id), t of scan_closest)
+__global__ void __launch_bounds__(kBlock) k_debug_scan2(DebugFnArgs a) {
+    extern __shared__ float4 lds[];
+    const SceneRef sc = stage_scene<kModeLds>(a.sc, lds);
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool active = i < a.n;
+    f3 o = parked_origin(), da = parked_dir(), db = parked_dir();
+    float t_max_a = -1.0f, t_min = 0.0f, t_max_b = kInf;
+    if (active) {
+        const float* in = a.in + (size_t)i * a.in_stride;
+        o = mk(in[0], in[1], in[2]); da = mk(in[3], in[4], in[5]); db = mk(in[6], in[7], in[8]);
+        t_max_a = in[9]; t_min = in[10]; t_max_b = in[11];
+    }
+    int ja, jb, sa, sb; float jt, st, unused;
+    scan_closest2<kModeLds>(sc, o, da, t_max_a, db, t_min, t_max_b, ja, jb, jt);
+    asm volatile("" ::: "memory");
+    scan_closest<kModeLds, true>(sc, o, da, t_min, t_max_a, sa, unused);
+    scan_closest<kModeLds, false>(sc, o, db, t_min, t_max_b, sb, st);
+    if (active) {
+        float* out = a.out + (size_t)i * a.out_stride;
+        out[0] = __int_as_float(ja >= 0 ? 1 : 0); out[1] = __int_as_float(jb); out[2] = jt;
+        out[3] = __int_as_float(sa >= 0 ? 1 : 0); out[4] = __int_as_float(sb); out[5] = st;
+    }
+}
+
 // ------------------------------------------------------------------ per-object constants (pt_scene_upload)
 // One thread per object: a triangle's unit normal into the spare w components of its shape record, 1 / area into the spare
 // component of its material record (pt_device.h "scene records").  Evaluated by the expressions the per-vertex code
@@ -2192,6 +2383,10 @@ void PT_LAUNCH(launch_scene_setup)(float4* shape, float4* mat, uint32_t n, hipSt
 }
 void PT_LAUNCH(launch_debug_fn)(const DebugFnArgs& a, hipStream_t st) {
     if (a.n == 0u) return;
+    if (a.op == kFnJointScan) {
+        hipLaunchKernelGGL(k_debug_scan2, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), scene_lds_bytes(a.sc, kModeLds), st, a);
+        return;
+    }
     hipLaunchKernelGGL(k_debug_fn, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
 }
 void PT_LAUNCH(launch_debug_hit)(const SceneView& sc, uint32_t accel, const float* rays6, uint32_t n, float t_min,

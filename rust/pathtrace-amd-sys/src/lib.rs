@@ -269,6 +269,7 @@ extern "C" {
     pub fn pt_debug_shape_sample(ctx: *mut PtContext, obj: u32, from3: *const f64, target3: *const f64, r12: *const f64, n: u32, exact_math: u32, out8: *mut f32) -> c_int;
     pub fn pt_debug_light_point(ctx: *mut PtContext, from3: *const f64, words4: *const u32, n: u32, exact_math: u32, out8: *mut f32) -> c_int;
     pub fn pt_debug_camera_rays(ctx: *mut PtContext, cam: *const PtCamera, xys: *const u32, n: u32, exact_math: u32, out8: *mut f32) -> c_int;
+    pub fn pt_debug_joint_scan(ctx: *mut PtContext, rays10: *const f64, n: u32, t_min: f64, t_max_b: f64, exact_math: u32, out6: *mut f32) -> c_int;
     pub fn pt_debug_bvh_check(objs: *const PtObject, n_objs: u32, depth: *mut u32, n_nodes: *mut u32, n_leaf_slots: *mut u32) -> c_int;
     pub fn pt_last_error() -> *const c_char;
     pub fn pt_abi_version() -> u32;
