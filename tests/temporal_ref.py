@@ -2,10 +2,17 @@
 pt_denoise_temporal_device), in f64, rules 1-7 as the header states them.  The a-trous part is
 denoise_ref's.
 
-A history is a dict: u f64[H,W,3], m1, m2, n f64[H,W], normal f64[H,W,3], depth f64[H,W], emitter f64[H,W], cam (the
-camera's fields as a tuple).  step() returns the output film, the next history and, per pixel, the fresh mask and the
+A history is a dict: u f64[H,W,3], m1, m2, n f64[H,W], normal f64[H,W,3], depth f64[H,W], emitter f64[H,W], n_exact
+bool[H,W] (below), cam (the camera's fields as a tuple).  step() returns the output film, the next history and, per pixel, the fresh mask and the
 margin of every decision: how far its input is from the value at which the decision would flip.  A pixel whose margins
-all exceed a bound gets the same decisions from any computation of the rule within that bound."""
+all exceed a bound gets the same decisions from any computation of the rule within that bound.
+
+The margin of the variance hand-over, |n - 4|, is 0 at n = 4, yet n = 4 is not always ill-conditioned.  Where the camera
+equals the history's field for field, x' = x and y' = y: one tap of weight exactly 1, S = 1, n = hn + 1, and if hn is an
+integer that both arithmetics hold exactly, so is n.  The history therefore carries n_exact: True at a fresh pixel
+(n = 1) and at a pixel that took its own exactly counted history through an unmoved camera.  There margins["n"] is inf;
+everywhere else (any reprojected tap: its weights and the division by S round differently in f32) it stays |n - 4|, also
+in later frames of an unmoved camera that inherit such a mixed count."""
 import numpy as np
 
 import denoise_ref as dr
@@ -125,13 +132,16 @@ def step(c, feat, hist, cam, alpha=0.2, depth_tol=0.1, normal_tol=0.9, iteration
     u = np.where(fresh[..., None], uc, uh + al[..., None] * (uc - uh))
     m1 = np.where(fresh, Lc, m1h + al * (Lc - m1h))
     m2 = np.where(fresh, Lc * Lc, m2h + al * (Lc * Lc - m2h))
-    margins["n"] = np.abs(n - 4)
+    n_exact = fresh.copy()
+    if have and same:
+        n_exact |= hist.get("n_exact", np.zeros((H, W), bool))
+    margins["n"] = np.where(n_exact, np.inf, np.abs(n - 4))
     var = np.where(n >= 4, np.maximum(0.0, m2 - m1 * m1), dr.initial_variance(uc))
     for it in range(iterations):
         u_f, var = dr.atrous_step(u if it == 0 else u_f, var, feat, 1 << it, sigma_l, sigma_n, sigma_d)
     out = (u_f if iterations else u) * a
     nxt = {"u": u, "m1": m1, "m2": m2, "n": n, "normal": nrm.copy(), "depth": dep.copy(), "emitter": em.copy(),
-           "cam": cam_fields(cam)}
+           "n_exact": n_exact, "cam": cam_fields(cam)}
     info = {"fresh": fresh, "margins": margins}
     return out, nxt, info
 
