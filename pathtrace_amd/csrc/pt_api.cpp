@@ -563,7 +563,7 @@ int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) {
     // Two consecutive triangles whose records carry the SAME vertex v0 and the SAME plane normal bit for bit -- the two
     // halves of a parallelogram fanned from one corner, like every wall of World::new() (world.rs:82-182) -- form a PAIR:
     // determinant, t, the range test and the hit point are then literally the same numbers for both, and the scan
-    // computes them once (tripair_test, pt_kernels.hip).  Nothing changes in any result.
+    // computes them once (tripair_test, pt_kernels_scan.h).  Nothing changes in any result.
     for (uint32_t i = 0; i < n;) {
         const bool tri = objs[i].shape_tag == PT_SHAPE_TRIANGLE;
         bool pair = false;
@@ -1177,7 +1177,7 @@ int pt_debug_launch_log(PtContext* c, uint32_t* out, uint32_t cap, uint32_t* n) 
 }
 
 // Debug: every instance code ptk::launch_paths_* can return -- the path-kernel instances the library is built with (the
-// template arguments of the dispatch in pt_kernels.hip), each in both arithmetic modes.  *n = the table's length; up to cap
+// template arguments of the dispatch in pt_kernels_*.hip), each in both arithmetic modes.  *n = the table's length; up to cap
 // codes are written (out may be null to ask for the length).
 int pt_debug_path_instances(uint32_t* out, uint32_t cap, uint32_t* n) {
     if (!n || (!out && cap)) return fail(PT_ERR_INVALID_ARG, "null argument");

@@ -64,7 +64,7 @@ struct Built {
     uint32_t non_finite = 0;
 };
 
-// Scan record of a triangle (what the primitive test reads; pt_kernels.hip triangle_test): the f32 specification of
+// Scan record of a triangle (what the primitive test reads; pt_kernels_scan.h triangle_test): the f32 specification of
 // TriangleShape::hit (shape.rs:161-192) works on the triangle's plane and two barycentric gradients instead of
 // re-deriving them per ray from the edges as Moeller-Trumbore does -- same real-number u, v, t:
 //     n  = e1 x e2                 t = -(s.n) / (d.n),  s = o - v0      (a = e1.(d x e2) = -(d.n), t = f e2.(s x e1) = f s.n)

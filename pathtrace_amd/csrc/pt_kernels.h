@@ -1,5 +1,5 @@
 // pt_kernels.h -- launch interface between the host driver (pt_api.cpp) and the
-// HIP kernels (pt_kernels.hip).  Plain structs, no HIP types besides float4 and
+// HIP kernels (pt_kernels_*.hip).  Plain structs, no HIP types besides float4 and
 // hipStream_t.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -132,8 +132,8 @@ struct BounceArgs {
 };
 
 constexpr uint32_t kBlock = 256;
-// How a linear-scan kernel finds the closest hit (pt_kernels.hip: scene_mode), and the material sets kernels are compiled for
-// (pt_kernels.hip: assume_mats).
+// How a linear-scan kernel finds the closest hit (pt_kernels_main.hip: scene_mode), and the material sets kernels are compiled for
+// (pt_kernels_vertex.h: assume_mats).
 constexpr int kModeLds = 0, kModeTiled = 1, kModeBvh = 2;
 constexpr int kMatsAll = 0, kMatsDiffuse = 1, kMatsNoMirror = 2, kMatsMirror = 3;
 // Launch log (pt_debug_launch_log): the path-kernel instance a launch takes, one word recorded by the host as it enqueues the
@@ -183,8 +183,8 @@ uint32_t regen_blocks_per_cu_fast(const BounceArgs& a);
 // One path-kernel launch; returns the instance code (instance_code) of the kernel it enqueued, for the launch log.
 uint32_t launch_path_kernel_exact(const BounceArgs& a, uint32_t grid, hipStream_t st);
 uint32_t launch_path_kernel_fast(const BounceArgs& a, uint32_t grid, hipStream_t st);
-// between the translation units pt_kernels.hip is built as (PT_TU there; not called by the host code): k_paths_regen_split's and the
-// BVH form's launchers live with their kernels
+// between the kernel translation units (pt_kernels_unit.h; not called by the host code): k_paths_regen_split's and the BVH form's
+// launchers live with their kernels, in pt_kernels_split.hip and pt_kernels_bvh.hip
 int regen_split_blocks_per_cu_exact(const BounceArgs& a, size_t lds);
 int regen_split_blocks_per_cu_fast(const BounceArgs& a, size_t lds);
 uint32_t launch_regen_split_exact(const BounceArgs& b, uint32_t blocks, size_t lds, hipStream_t st);
@@ -262,7 +262,7 @@ void launch_debug_hit_exact(const SceneView& sc, uint32_t accel, const float* ra
 void launch_debug_hit_fast(const SceneView& sc, uint32_t accel, const float* rays6, uint32_t n, float t_min, float t_max,
                            float4* scratch, int32_t* out_id, float* out_t, float* out_rec, hipStream_t st);
 
-// The per-vertex functions on arbitrary inputs (debug/parity entries; layouts at k_debug_fn in pt_kernels.hip).
+// The per-vertex functions on arbitrary inputs (debug/parity entries; layouts at k_debug_fn in pt_kernels_main.hip).
 enum { kFnBsdfEval = 0, kFnBsdfSample = 1, kFnShapeSample = 2, kFnLightPoint = 3, kFnCameraRay = 4,
        kFnJointScan = 5 };     // (a kernel of its own: the scene staged in LDS; scenes of <= kSmallObjs objects)
 struct DebugFnArgs {

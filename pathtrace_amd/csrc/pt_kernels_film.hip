@@ -1,0 +1,405 @@
+// pt_kernels_film.hip -- the kernels that work on the film, not on paths: multi-GPU film exchange, adaptive sampling, the
+// a-trous denoiser and its temporal accumulation.  None of them has a division or square root whose result depends on the
+// arithmetic mode, so the unit is compiled once, in fast mode (its kernels live in ptk_fast_impl), and serves both modes.
+#include "pt_kernels_scan.h"
+#include "pt_adaptive.h"
+#if PT_MATH_EXACT
+#error "pt_kernels_film.hip is built once, with -DPT_MATH_EXACT=0"
+#endif
+
+namespace PTK_IMPL {
+// ------------------------------------------------------------------ multi-GPU film exchange (pt_multi.cpp)
+// A device's tile -> one 16-byte record per pixel (12 B linear RGB + 4 B RGBA8), so that both film planes travel in
+// ONE gather; rows beyond the tile (tiles are padded to the largest one) are left untouched.
+__global__ void __launch_bounds__(kBlock) k_film_pack(const float* __restrict__ lin, const uint8_t* __restrict__ rgba,
+                                                      uint32_t np, uint4* __restrict__ packed) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= np) return;
+    uint4 v;
+    v.x = __float_as_uint(lin[3 * (size_t)p]); v.y = __float_as_uint(lin[3 * (size_t)p + 1]); v.z = __float_as_uint(lin[3 * (size_t)p + 2]);
+    v.w = rgba ? *reinterpret_cast<const uint32_t*>(rgba + 4 * (size_t)p) : 0u;
+    packed[p] = v;
+}
+// The gathered tiles (device g's padded tile at recv + g * max_rows * W) -> the frame in image order.  Image row y lies
+// in band y / band_rows, which device (band % n_dev) rendered as its tile row (band / n_dev) * band_rows + y % band_rows.
+__global__ void __launch_bounds__(kBlock) k_film_unpack(const uint4* __restrict__ recv, uint32_t W, uint32_t H, uint32_t band_rows,
+                                                        uint32_t n_dev, uint32_t max_rows, float* __restrict__ lin,
+                                                        uint8_t* __restrict__ rgba) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= W * H) return;
+    const uint32_t y = p / W, x = p - y * W;
+    const uint32_t band = y / band_rows, g = band % n_dev;
+    const uint32_t k = (band / n_dev) * band_rows + (y - band * band_rows);
+    const uint4 v = recv[((size_t)g * max_rows + k) * W + x];
+    lin[3 * (size_t)p] = __uint_as_float(v.x); lin[3 * (size_t)p + 1] = __uint_as_float(v.y); lin[3 * (size_t)p + 2] = __uint_as_float(v.z);
+    if (rgba) *reinterpret_cast<uint32_t*>(rgba + 4 * (size_t)p) = v.w;
+}
+
+// ------------------------------------------------------------------ adaptive sampling (pt_render_adaptive, rule: pt_adaptive.h)
+// k_resolve for one sample batch of an adaptive pass: list slot i -> image pixel pix, whose f64 sums (R, G, B and the
+// luminance sums S1, S2) take the batch's samples in sample order.  A pixel's sums are thus exactly the ones k_resolve forms
+// for it in a uniform render of as many samples, and its mean, gamma and RGBA8 are the same expressions (world.rs:311-332).
+__global__ void __launch_bounds__(kBlock) k_resolve_adaptive(AdaptiveResolveArgs a) {
+    if (blockIdx.x == 0u && a.zero_words)
+        for (uint32_t k = threadIdx.x; k < a.n_zero; k += kBlock) a.zero_words[k] = 0u;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    uint32_t pix = i;
+    if (a.pixels) { const uint2 xy = a.pixels[i]; pix = xy.y * a.width + xy.x; }
+    double* const sp = a.f.sums + 5 * (size_t)pix;
+    double r = 0.0, g = 0.0, b = 0.0, s1 = 0.0, s2 = 0.0;
+    if (a.load) { r = sp[0]; g = sp[1]; b = sp[2]; s1 = sp[3]; s2 = sp[4]; }
+    auto add = [&](const Rgb& v) {
+        r += (double)v.r; g += (double)v.g; b += (double)v.b;                     // world.rs:311
+        const double L = ptad::luminance(v.r, v.g, v.b);
+        s1 += L; s2 += L * L;
+    };
+    uint32_t s = 0;
+    for (; s + 4u <= a.nb; s += 4u) {              // four samples' loads in flight before the ordered additions (as k_resolve)
+        Rgb v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = a.lsamp[(size_t)(s + k) * a.n + i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) add(v[k]);
+    }
+    for (; s < a.nb; ++s) add(a.lsamp[(size_t)s * a.n + i]);
+    sp[0] = r; sp[1] = g; sp[2] = b; sp[3] = s1; sp[4] = s2;
+    if (!a.finalize) return;
+    const double dn = (double)a.n_total;
+    const double c[3] = {r / dn, g / dn, b / dn};                                 // world.rs:315
+    uint32_t q8 = 0xFF000000u;                                                    // alpha 255, world.rs:331
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double gm = __builtin_sqrt(c[k]);                                   // gamma 2.0, world.rs:322-324
+        const double cl = gm < 0.0 ? 0.0 : (gm > 1.0 ? 1.0 : gm);                 // clamp keeps NaN
+        const double q = cl * 255.0;
+        q8 |= (uint32_t)((q != q) ? (uint8_t)0 : (uint8_t)q) << (8 * k);          // `as u8`: truncation, NaN -> 0
+        a.f.out_linear[3 * (size_t)pix + k] = (float)c[k];
+    }
+    *reinterpret_cast<uint32_t*>(a.f.out_rgba + 4 * (size_t)pix) = q8;
+    double rel;
+    const bool conv = ptad::check(s1, s2, a.n_total, a.f.rel_tol, a.f.abs_floor, &rel);
+    a.f.count[pix] = a.n_total;
+    a.f.rel_err[pix] = (float)rel;
+    a.f.conv[pix] = conv ? 1u : 0u;
+}
+
+// The list's pixels that failed their last check, compacted in list order.  Workgroup b owns the kSelectTile slots from
+// b * kSelectTile; k_adaptive_count leaves its survivor count in block_counts[b], and k_adaptive_select adds up the counts
+// of the workgroups before it (its output offset), then writes its survivors by wave ballot + prefix popcount.
+constexpr uint32_t kSelectRounds = kSelectTile / kBlock;
+PT_DEV uint2 select_pixel(const uint2* pixels, uint32_t width, uint32_t i) {
+    return pixels ? pixels[i] : make_uint2(i % width, i / width);
+}
+PT_DEV bool select_keep(const uint2* pixels, uint32_t n, uint32_t width, const uint32_t* conv, uint32_t i, uint2& xy) {
+    if (i >= n) return false;
+    xy = select_pixel(pixels, width, i);
+    return conv[xy.y * width + xy.x] == 0u;
+}
+__global__ void __launch_bounds__(kBlock) k_adaptive_count(const uint2* __restrict__ pixels, uint32_t n, uint32_t width,
+                                                           const uint32_t* __restrict__ conv, uint32_t* __restrict__ block_counts) {
+    __shared__ uint32_t s_wave[kBlock / 64];
+    const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
+    uint32_t cnt = 0;                              // wave-uniform
+    for (uint32_t r = 0; r < kSelectRounds; ++r) {
+        uint2 xy;
+        const bool keep = select_keep(pixels, n, width, conv, blockIdx.x * kSelectTile + r * kBlock + threadIdx.x, xy);
+        cnt += (uint32_t)__popcll(__ballot(keep));
+    }
+    if (lane == 0u) s_wave[wib] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < kBlock / 64; ++w) t += s_wave[w];
+        block_counts[blockIdx.x] = t;
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_adaptive_select(const uint2* __restrict__ pixels, uint32_t n, uint32_t width,
+                                                            const uint32_t* __restrict__ conv, const uint32_t* __restrict__ block_counts,
+                                                            uint2* __restrict__ out, uint32_t* __restrict__ out_n) {
+    __shared__ uint32_t s_wave[kBlock / 64];
+    const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
+    // output offset of this workgroup: survivors of the workgroups before it
+    uint32_t part = 0;
+    for (uint32_t k = threadIdx.x; k < blockIdx.x; k += kBlock) part += block_counts[k];
+    for (int off = 32; off > 0; off >>= 1) part += (uint32_t)__shfl_xor((int)part, off);
+    if (lane == 0u) s_wave[wib] = part;
+    __syncthreads();
+    uint32_t base = 0;
+    for (uint32_t w = 0; w < kBlock / 64; ++w) base += s_wave[w];
+    for (uint32_t r = 0; r < kSelectRounds; ++r) {
+        __syncthreads();                           // (everybody has read s_wave)
+        uint2 xy;
+        const bool keep = select_keep(pixels, n, width, conv, blockIdx.x * kSelectTile + r * kBlock + threadIdx.x, xy);
+        const unsigned long long mask = __ballot(keep);
+        if (lane == 0u) s_wave[wib] = (uint32_t)__popcll(mask);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < kBlock / 64; ++w) { before += w < wib ? s_wave[w] : 0u; total += s_wave[w]; }
+        if (keep) out[base + before + lane_rank(mask)] = xy;
+        base += total;
+    }
+    if (blockIdx.x + 1u == gridDim.x && threadIdx.x == 0u) *out_n = base;
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_resolve_adaptive(const AdaptiveResolveArgs& a, hipStream_t st) {
+    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_resolve_adaptive, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+void launch_adaptive_select(const uint2* pixels, uint32_t n, uint32_t width, const uint32_t* conv, uint32_t* block_counts,
+                            uint2* out, uint32_t* out_n, hipStream_t st) {
+    if (n == 0u) { (void)hipMemsetAsync(out_n, 0, sizeof(uint32_t), st); return; }
+    const dim3 g((n + kSelectTile - 1) / kSelectTile), b(kBlock);
+    hipLaunchKernelGGL(PTK_IMPL::k_adaptive_count, g, b, 0, st, pixels, n, width, conv, block_counts);
+    hipLaunchKernelGGL(PTK_IMPL::k_adaptive_select, g, b, 0, st, pixels, n, width, conv, (const uint32_t*)block_counts, out, out_n);
+}
+void launch_film_pack(const float* lin, const uint8_t* rgba, uint32_t np, void* packed, hipStream_t st) {
+    if (np) hipLaunchKernelGGL(PTK_IMPL::k_film_pack, dim3((np + kBlock - 1) / kBlock), dim3(kBlock), 0, st, lin, rgba, np, (uint4*)packed);
+}
+void launch_film_unpack(const void* recv, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_dev, uint32_t max_rows, float* lin,
+                        uint8_t* rgba, hipStream_t st) {
+    if (W * H) hipLaunchKernelGGL(PTK_IMPL::k_film_unpack, dim3((W * H + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const uint4*)recv, W, H,
+                                  band_rows, n_dev, max_rows, lin, rgba);
+}
+}  // namespace ptk
+
+// ------------------------------------------------------------------ edge-avoiding a-trous denoiser (pt_denoise_device)
+// The rule is stated in include/pathtrace_amd.h (PtDenoise) and DESIGN.md 5b.  One thread per pixel, one launch per step.
+// State plane: float4 (u.rgb, var) per pixel, u = colour / max(albedo, 1e-3); the features: (albedo rgb, emitter),
+// (normal xyz, depth).  Every tap is three 16-byte loads; at 1024^2 the 48 MB of the three planes stay in the Infinity Cache.
+// The sums are formed as u_p + sum w (u_q - u_p) / sum w (the rule's sum w u_q / sum w): a flat region stays exactly flat.
+namespace PTK_IMPL {
+constexpr uint32_t kDnBx = 32, kDnBy = 8;      // a wave covers 32 x 2 pixels: its 5 x 5 taps touch few cache lines
+PT_DEV float dn_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+PT_DEV float dn_albedo(float a) { return fmaxf(a, 1e-3f); }
+// c' = u * a, and the RGBA8 word of c' through k_resolve's gamma / clamp / `as u8` (world.rs:322-331)
+PT_DEV void dn_store(const DenoiseArgs& a, size_t p, float ur, float ug, float ub, float4 f0) {
+    const float c[3] = {ur * dn_albedo(f0.x), ug * dn_albedo(f0.y), ub * dn_albedo(f0.z)};
+    uint32_t q8 = 0xFF000000u;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.out_linear[3 * p + k] = c[k];
+        const double gm = __builtin_sqrt((double)c[k]);
+        const double cl = gm < 0.0 ? 0.0 : (gm > 1.0 ? 1.0 : gm);
+        const double q = cl * 255.0;
+        q8 |= (uint32_t)((q != q) ? (uint8_t)0 : (uint8_t)q) << (8 * k);
+    }
+    if (a.out_rgba) *reinterpret_cast<uint32_t*>(a.out_rgba + 4 * p) = q8;
+}
+// demodulated colour of pixel q straight from the film
+PT_DEV float3 dn_demod(const DenoiseArgs& a, size_t q) {
+    const float4 f0 = a.feat[2 * q];
+    return make_float3(a.linear[3 * q] / dn_albedo(f0.x), a.linear[3 * q + 1] / dn_albedo(f0.y), a.linear[3 * q + 2] / dn_albedo(f0.z));
+}
+// the 3 x 3 population variance of L(u) around pixel (x, y), taps outside the image skipped: k_denoise_temporal's variance
+// of a pixel with fewer than 4 frames of history.  The statements are k_denoise_init's, in its order, so the value is the
+// same bits (tests/test_gpu_temporal.py); k_denoise_init keeps its own text because calling this function there changes
+// the instructions the compiler schedules for that kernel.
+PT_DEV float dn_spatial_var(const DenoiseArgs& a, uint32_t x, uint32_t y) {
+    float Ls[9];
+    uint32_t cnt = 0;
+    float sum = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = (int)x + dx, qy = (int)y + dy;
+            if (qx < 0 || qy < 0 || qx >= (int)a.width || qy >= (int)a.height) continue;
+            const float3 uq = dn_demod(a, (size_t)qy * a.width + qx);
+            Ls[cnt] = dn_lum(uq.x, uq.y, uq.z);
+            sum += Ls[cnt];
+            ++cnt;
+        }
+    const float mu = sum / (float)cnt;
+    float var = 0.0f;
+    for (uint32_t k = 0; k < cnt; ++k) var += (Ls[k] - mu) * (Ls[k] - mu);
+    var /= (float)cnt;
+    return var;
+}
+// first launch: u and the 3 x 3 population variance of L(u) (taps outside the image skipped); finalize: iterations = 0
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_init(DenoiseArgs a) {
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    const size_t p = (size_t)y * a.width + x;
+    const float3 u = dn_demod(a, p);
+    float Ls[9];
+    uint32_t cnt = 0;
+    float sum = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = (int)x + dx, qy = (int)y + dy;
+            if (qx < 0 || qy < 0 || qx >= (int)a.width || qy >= (int)a.height) continue;
+            const float3 uq = dn_demod(a, (size_t)qy * a.width + qx);
+            Ls[cnt] = dn_lum(uq.x, uq.y, uq.z);
+            sum += Ls[cnt];
+            ++cnt;
+        }
+    const float mu = sum / (float)cnt;
+    float var = 0.0f;
+    for (uint32_t k = 0; k < cnt; ++k) var += (Ls[k] - mu) * (Ls[k] - mu);
+    var /= (float)cnt;
+    if (a.finalize) dn_store(a, p, u.x, u.y, u.z, a.feat[2 * p]);
+    else a.dst[p] = make_float4(u.x, u.y, u.z, var);
+}
+// one a-trous step of size h: the 3 x 3 Gaussian of var (renormalised over the in-image taps) gives g_p, then the 5 x 5
+// B3-spline taps at (dx, dy) h with the edge-stopping weights; finalize: remodulate and write both film planes
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_step(DenoiseArgs a) {
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    const int W = (int)a.width, H = (int)a.height, h = (int)a.step;
+    const size_t p = (size_t)y * a.width + x;
+    const float4 sp = a.src[p], f0p = a.feat[2 * p], f1p = a.feat[2 * p + 1];
+    float4 res = sp;
+    if (!(f0p.w > 0.0f)) {                     // an emitter pixel takes no other tap: it keeps (u, var)
+        float gs = 0.0f, gw = 0.0f;
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int qx = (int)x + dx, qy = (int)y + dy;
+                if (qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+                const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
+                gs += k * a.src[(size_t)qy * W + qx].w;
+                gw += k;
+            }
+        const float g = __builtin_sqrtf(gs / gw);
+        const float Lp = dn_lum(sp.x, sp.y, sp.z);
+        const float inv_l = 1.0f / (a.sigma_l * g + 1e-10f);
+        const float inv_d = 1.0f / (a.sigma_d * (float)h * fmaxf(f1p.w, 1e-3f) + 1e-10f);
+        constexpr float kB3[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+        const float kc = kB3[2] * kB3[2];
+        float wsum = kc, ar = 0.0f, ag = 0.0f, ab = 0.0f, av = kc * kc * sp.w;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const int qy = (int)y + (j - 2) * h;
+            if (qy < 0 || qy >= H) continue;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                if (i == 2 && j == 2) continue;
+                const int qx = (int)x + (i - 2) * h;
+                if (qx < 0 || qx >= W) continue;
+                const size_t q = (size_t)qy * W + qx;
+                const float4 sq = a.src[q], f0q = a.feat[2 * q], f1q = a.feat[2 * q + 1];
+                const float nd = f1p.x * f1q.x + f1p.y * f1q.y + f1p.z * f1q.z;
+                if (!(nd > 0.0f) || f0q.w > 0.0f) continue;
+                const float el = fabsf(Lp - dn_lum(sq.x, sq.y, sq.z)) * inv_l;
+                const float ed = fabsf(f1p.w - f1q.w) * inv_d;
+                // k * nd^sigma_n * exp(-el - ed), as one exp2
+                const float w = kB3[j] * kB3[i] * exp2f(a.sigma_n * log2f(nd) - (el + ed) * 1.44269504f);
+                wsum += w;
+                ar += w * (sq.x - sp.x); ag += w * (sq.y - sp.y); ab += w * (sq.z - sp.z);
+                av += w * w * sq.w;
+            }
+        }
+        const float inv = 1.0f / wsum;
+        res = make_float4(sp.x + ar * inv, sp.y + ag * inv, sp.z + ab * inv, av * inv * inv);
+    }
+    if (a.finalize) dn_store(a, p, res.x, res.y, res.z, f0p);
+    else a.dst[p] = res;
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_denoise(const DenoiseArgs& a, bool init, hipStream_t st) {
+    const dim3 g((a.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy), b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
+    if (init) hipLaunchKernelGGL(PTK_IMPL::k_denoise_init, g, b, 0, st, a);
+    else hipLaunchKernelGGL(PTK_IMPL::k_denoise_step, g, b, 0, st, a);
+}
+}  // namespace ptk
+
+// ------------------------------------------------------------------ temporal accumulation (pt_denoise_temporal_device)
+// The rule is stated in include/pathtrace_amd.h (PtTemporal) and DESIGN.md 5c.  One thread per pixel, in place of k_denoise_init.
+// The reprojection runs in f64: an f32 solve puts x' about 1e-4 pixel off at 1024^2, and a bilinear tap of that weight moves
+// a dim pixel next to a bright one by far more than the accumulation's own rounding.  Everything after it is f32.
+namespace PTK_IMPL {
+PT_DEV double tm_dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+PT_DEV void tm_cross(const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+// pixel (x, y) at depth d seen from the frame's camera -> (x', y') in the history's image and d_exp; false: no reprojection
+PT_DEV bool tm_reproject(const TemporalArgs& a, uint32_t x, uint32_t y, float d, double& xr, double& yr, double& dexp) {
+    const double* o = a.cur; const double* l = a.cur + 3; const double* hz = a.cur + 6; const double* vt = a.cur + 9;
+    const double* o2 = a.prev; const double* l2 = a.prev + 3; const double* hz2 = a.prev + 6; const double* vt2 = a.prev + 9;
+    const double W1 = (double)(a.dn.width - 1u), H1 = (double)(a.dn.height - 1u);
+    const double s = ((double)x + 0.5) / W1, t = ((double)(a.dn.height - 1u - y) + 0.5) / H1;      // camera.rs:139-147, world.rs:299
+    double D[3], P[3], c[3], r[3], bc[3], rc[3], br[3];
+    for (int k = 0; k < 3; ++k) D[k] = l[k] + s * hz[k] + t * vt[k] - o[k];
+    const double inv_len = 1.0 / __builtin_sqrt(tm_dot(D, D));
+    for (int k = 0; k < 3; ++k) {
+        P[k] = o[k] + (double)d * (D[k] * inv_len);
+        c[k] = o2[k] - P[k];                 // -(P - o')
+        r[k] = o2[k] - l2[k];
+    }
+    // s' hz' + t' vt' + lambda c = r by Cramer's rule
+    tm_cross(vt2, c, bc);
+    const double det = tm_dot(hz2, bc);
+    if (!(det != 0.0) || !__builtin_isfinite(det)) return false;
+    tm_cross(r, c, rc);
+    tm_cross(vt2, r, br);
+    const double inv = 1.0 / det;
+    const double s2 = tm_dot(r, bc) * inv, t2 = tm_dot(hz2, rc) * inv, lam = tm_dot(hz2, br) * inv;
+    if (!(lam > 0.0) || !__builtin_isfinite(s2) || !__builtin_isfinite(t2) || !__builtin_isfinite(lam)) return false;
+    xr = s2 * W1 - 0.5;
+    yr = (double)a.dn.height - 0.5 - t2 * H1;
+    dexp = __builtin_sqrt(tm_dot(c, c));
+    return true;
+}
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_temporal(TemporalArgs a) {
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.dn.width || y >= a.dn.height) return;
+    const int W = (int)a.dn.width, H = (int)a.dn.height;
+    const size_t p = (size_t)y * a.dn.width + x;
+    const float4 f0p = a.dn.feat[2 * p], f1p = a.dn.feat[2 * p + 1];
+    const float3 uc = dn_demod(a.dn, p);
+    const float Lc = dn_lum(uc.x, uc.y, uc.z);
+    // the valid-weighted history of the 2 x 2 bilinear taps around (x', y')
+    float S = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hm1 = 0.0f, hm2 = 0.0f, hn = 0.0f;
+    if (a.hist_src && f1p.w > 0.0f) {
+        double xr = x, yr = y, dexp = f1p.w;
+        const bool ok = a.same_camera || tm_reproject(a, x, y, f1p.w, xr, yr, dexp);
+        if (ok && xr > -1.0 && xr < (double)W && yr > -1.0 && yr < (double)H) {      // else no tap lies inside the image
+            const int x0 = (int)__builtin_floor(xr), y0 = (int)__builtin_floor(yr);
+            const float fx = (float)(xr - x0), fy = (float)(yr - y0);
+            const float de = (float)dexp, dmax = a.depth_tol * de;
+            const bool em = f0p.w > 0.0f;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int qx = x0 + i, qy = y0 + j;
+                    const float w = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+                    if (!(w > 0.0f) || qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+                    const size_t q = (size_t)qy * W + qx;
+                    const float4 h2 = a.hist_src[3 * q + 2];
+                    if (!(h2.w > 0.0f) || !(fabsf(h2.w - de) <= dmax)) continue;
+                    if (!(f1p.x * h2.x + f1p.y * h2.y + f1p.z * h2.z >= a.normal_tol)) continue;
+                    const float4 h1 = a.hist_src[3 * q + 1];
+                    if (em != (h1.z > 0.0f)) continue;
+                    const float4 h0 = a.hist_src[3 * q];
+                    S += w;
+                    hr += w * h0.x; hg += w * h0.y; hb += w * h0.z; hm1 += w * h0.w;
+                    hm2 += w * h1.x; hn += w * h1.y;
+                }
+        }
+    }
+    float3 u = uc;
+    float m1 = Lc, m2 = Lc * Lc, n = 1.0f;            // a fresh pixel
+    if (S >= 1e-2f) {
+        const float inv = 1.0f / S;
+        const float ur = hr * inv, ug = hg * inv, ub = hb * inv, um1 = hm1 * inv, um2 = hm2 * inv;
+        n = hn * inv + 1.0f;
+        const float al = fmaxf(a.alpha, 1.0f / n);
+        u = make_float3(ur + al * (uc.x - ur), ug + al * (uc.y - ug), ub + al * (uc.z - ub));
+        m1 = um1 + al * (Lc - um1);
+        m2 = um2 + al * (Lc * Lc - um2);
+    }
+    const float var = n >= 4.0f ? fmaxf(0.0f, m2 - m1 * m1) : dn_spatial_var(a.dn, x, y);
+    a.hist_dst[3 * p] = make_float4(u.x, u.y, u.z, m1);
+    a.hist_dst[3 * p + 1] = make_float4(m2, n, f0p.w, 0.0f);
+    a.hist_dst[3 * p + 2] = f1p;
+    if (a.dn.finalize) dn_store(a.dn, p, u.x, u.y, u.z, f0p);
+    else a.dn.dst[p] = make_float4(u.x, u.y, u.z, var);
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_denoise_temporal(const TemporalArgs& a, hipStream_t st) {
+    const dim3 g((a.dn.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.dn.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy),
+        b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
+    hipLaunchKernelGGL(PTK_IMPL::k_denoise_temporal, g, b, 0, st, a);
+}
+}  // namespace ptk

@@ -1,6 +1,6 @@
 """The instance table of the launch log (pt_debug_path_instances) is the set of path kernels the library ships.
 
-The path kernels are templates; the dispatch in pt_kernels.hip picks one instance per launch and the launch log records
+The path kernels are templates; the dispatch in pt_kernels_*.hip picks one instance per launch and the launch log records
 which (include/pathtrace_amd.h).  tests/test_gpu_kernel_instances.py runs one job per table entry, so a kernel instance
 that is compiled into the library but missing from the table would ship untested: this test lists the kernels of the
 gfx950 code objects inside libpathtrace_amd.so and requires them to be the table, one to one."""
@@ -30,7 +30,7 @@ def _shipped_path_kernels(pt, tmp_path):
     # --offloading writes one file per bundle entry next to its (relative) input: run it in tmp_path
     subprocess.run([objdump, "--offloading", so.name], cwd=tmp_path, check=True, capture_output=True)
     objs = sorted(p for p in os.listdir(tmp_path) if p.endswith("gfx950"))
-    assert len(objs) == 6, objs             # the six kernel units: main, split, BVH, each exact and fast
+    assert len(objs) == 7, objs             # the kernel units: main, split, BVH, each exact and fast, and film (fast only)
     found = []
     for o in objs:
         out = subprocess.run([readelf, "--syms", "--demangle", "-W", o], cwd=tmp_path, check=True, capture_output=True,

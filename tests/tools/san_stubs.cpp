@@ -1,4 +1,4 @@
-// Link stubs for the sanitizer driver: the kernel launchers live in pt_kernels.hip (device code), which a host-only
+// Link stubs for the sanitizer driver: the kernel launchers live in pt_kernels_*.hip (device code), which a host-only
 // sanitizer build does not contain.  Nothing in san_driver.cpp reaches them (every caller needs a HIP device first).
 #include <cstdlib>
 

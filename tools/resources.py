@@ -1,17 +1,20 @@
 #!/usr/bin/env python3
-"""Register / spill / occupancy table of every kernel of pt_kernels.hip (fast arithmetic build unless --exact).
+"""Register / spill / occupancy table of every kernel of the library (fast arithmetic build unless --exact).
     python tools/resources.py [--exact] [extra hipcc -D flags]"""
-import re, subprocess, sys, os
+import re, shlex, subprocess, sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "pathtrace_amd", "csrc")
 exact = "--exact" in sys.argv
 extra = [a for a in sys.argv[1:] if a != "--exact"]
-# the three translation units of the library's build, each with its options (pathtrace_amd/csrc/Makefile)
-base = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-        f"-DPT_MATH_EXACT={1 if exact else 0}", "-Rpass-analysis=kernel-resource-usage", "-c", "pt_kernels.hip", "-o", "/dev/null"]
-units = [["-fno-slp-vectorize", "-DPT_TU=1"], ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-DPT_TU=2"], ["-DPT_TU=3"]]
+# the kernel units of the library's build, compiled by the commands of the Makefile's own rules (make -n prints them): "... -c <unit> -o <object>"
+mode = "exact" if exact else "fast"
+objs = [f"pt_kernels_{u}_{mode}.o" for u in ("main", "split", "bvh")] + ([] if exact else ["pt_kernels_film.o"])
+cmds = subprocess.run(["make", "-n", "-B", "KDEFS=" + " ".join(extra)] + objs, cwd=CSRC, stdout=subprocess.PIPE, text=True, check=True).stdout
 out = ""
-for u in units:
-    out += subprocess.run(base + u + extra, cwd=os.path.join(ROOT, "pathtrace_amd", "csrc"), stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True).stderr
+for c in cmds.splitlines():
+    args = shlex.split(c)
+    assert args[-2] == "-o", c
+    out += subprocess.run(args[:-2] + ["-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null"], cwd=CSRC, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
     m = re.search(r"remark: +(.*?) \[-Rpass", line)

@@ -5,7 +5,7 @@
 //   k_one : one ray per lane, launch_bounds(256, 6);  k_two : two rays per lane, launch_bounds(256, 3), half the workgroups.
 // Each lane runs ITERS closest-hit scans + ITERS any-hit scans (the two scans of a vertex) on rays that change every iteration
 // (so nothing hoists), over the C2 scene's scan records (pt_scenes.cpp scene 2), with the kernel's own arithmetic
-// (sphere_pre / sphere_post of pt_kernels.hip, groups of four).  Output: ns per ray-scan.
+// (sphere_pre / sphere_post of pt_kernels_scan.h, groups of four).  Output: ns per ray-scan.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/ubench/scan2.hip -o tools/ubench/scan2 && tools/ubench/scan2
 #include <hip/hip_runtime.h>
 #include <cstdio>
