@@ -506,6 +506,53 @@ int pt_render_denoised_temporal(PtContext* ctx, const PtCamera* cam, const PtRen
                                 const PtDenoise* dn, const PtTemporal* tp, float* out_linear_rgb, uint8_t* out_rgba8,
                                 float* out_noisy_linear, float* out_features);
 
+/* Moving objects in the temporal denoiser (additive to ABI 6).  pt_scene_upload empties the history; these
+ * entries change the scene and keep it.
+ *
+ * pt_scene_update makes the scene pt_scene_upload would make of the same objects (same records, same lazy BVH rebuild, same
+ * restart of the statistics: a render after it is bit-identical to one after pt_scene_upload) and keeps the temporal history.
+ * It needs an uploaded scene with the same n_objs and the same shape_tag at every index: otherwise PT_ERR_INVALID_ARG, and the
+ * context is untouched.  The context keeps the f64 shape[9] of every object twice: of the current scene, and of the HISTORY
+ * POSE, the scene as it was at the most recent temporal call (either entry) that stored a history frame.  Any number of
+ * updates may lie between two temporal frames.                                                                          */
+int pt_scene_update(PtContext* ctx, const PtObject* objs, uint32_t n_objs);
+/* The motion map of object k, x -> A x + b in f64, carries a point of the current pose to the same material point of the
+ * history pose:  sphere (c, r) now, (c', r') then: A = (r'/r) I, b = c' - (r'/r) c;  triangle (v0, v1, v2) now, primed then:
+ * e1 = v1 - v0, e2 = v2 - v0, n = (e1 x e2)/|e1 x e2|, E = [e1 e2 n] as columns, A = E' E^-1, b = v0' - A v0.
+ * INVALID: a radius <= 0, a triangle of zero area, or a non-finite entry.  IDENTITY: the nine shape fields are bitwise equal
+ * now and then (decided on the fields; then A = I, b = 0 exactly).
+ * Host only, needs no GPU: out_maps n x 12 doubles (A row-major, then b), out_flags n words (bit 0 identity, bit 1 invalid). */
+int pt_debug_motion_maps(const PtObject* prev_objs, const PtObject* cur_objs, uint32_t n, double* out_maps, uint32_t* out_flags);
+/* One int32 per image pixel, row-major: the object index hit by the primary ray of sample params->spp_offset, -1 for a miss.
+ * The ray, its key and jitter, [t_min, inf), params->accel and params->exact_math are the feature pass's (its first sample's
+ * hit ids, copied out of the pass's scratch).  Whole image only; asynchronous on the context's stream.                  */
+int pt_render_feature_ids_device(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, int32_t* d_ids);
+/* pt_denoise_temporal_device plus d_ids (width*height int32, 4-byte aligned): per call the maps current pose -> history pose
+ * go to a context-owned device buffer on the context's stream, out of host staging that the context owns (no wait for the stream).
+ * Rules 1-3 and 7 above are amended, 4-6 are untouched:
+ *   1' fresh, additionally: id_p < 0, id_p >= n_objs, or the map of id_p is invalid (the ids are the caller's: the device
+ *                  checks them against n_objs before it reads a map)
+ *   2' reprojection P as in 2, k = id_p, P_h = A_k P + b_k in f64; the system of 2 is solved with P_h in place of P and
+ *                  d_exp = |P_h - o'|;  n_h = A_k n_p normalised in f64 and rounded to f32 (n_p when its length is 0).
+ *                  Map k the identity: P_h = P and n_h = n_p exactly; the camera also equal to the history's field by
+ *                  field: x' = x, y' = y, d_exp = d_p exactly (the shortcut of 2, per pixel)
+ *   3' taps        the conditions of 3 with n_h in the normal gate, and the id gate: the tap's stored id is unknown, or equals
+ *                  id_p, or neither the map of id_p nor the map of the tap's id is anything but the identity.  (The last
+ *                  clause keeps a scene in which nothing moved bit-identical to pt_denoise_temporal_device under a moving
+ *                  camera: two objects that both stand still gate each other by depth and normal alone, as there.)
+ *   7' store       the history's second record is (m2, n, emitter, id_p + 1 as float); 0 = unknown, which is what
+ *                  pt_denoise_temporal_device stores (the lane is read by nothing else), and what a pixel with id_p < 0 or
+ *                  id_p >= n_objs stores.  The two entries may be mixed freely on one context.
+ * Needs a scene (PT_ERR_INVALID_ARG without); PT_ERR_UNSUPPORTED for more than 2^24 - 2 objects (id + 1 is kept in f32).
+ * Lighting that changes because an object moved is forgotten at the rate alpha, as under a moving camera.               */
+int pt_denoise_temporal_motion_device(PtContext* ctx, const PtCamera* cam, const float* d_linear_rgb, const float* d_features,
+                                      const int32_t* d_ids, const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear,
+                                      uint8_t* d_out_rgba8);
+/* pt_render_denoised_temporal with the ids pass and the motion entry; out_ids (width*height int32) may be NULL. */
+int pt_render_denoised_motion(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
+                              const PtDenoise* dn, const PtTemporal* tp, float* out_linear_rgb, uint8_t* out_rgba8,
+                              float* out_noisy_linear, float* out_features, int32_t* out_ids);
+
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on
  * entry like Ray::new (camera.rs:10-16); xy = n * (x, y) = the RNG key of each ray's stream, and the

@@ -191,6 +191,13 @@ SYMBOLS = {
                                              C.c_void_p]),
     "pt_render_denoised_temporal": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_scene_update": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
+    "pt_debug_motion_maps": (C.c_int, [_P(PtObject), _P(PtObject), C.c_uint32, _P(C.c_double), _P(C.c_uint32)]),
+    "pt_render_feature_ids_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_void_p]),
+    "pt_denoise_temporal_motion_device": (C.c_int, [C.c_void_p, _P(PtCamera), C.c_void_p, C.c_void_p, C.c_void_p, _P(PtDenoise),
+                                                    _P(PtTemporal), C.c_void_p, C.c_void_p]),
+    "pt_render_denoised_motion": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

@@ -118,6 +118,11 @@ class Context:
         self._objs = objs   # keep alive
         check(lib().pt_scene_upload(self._h, objs, len(objs)))
 
+    def scene_update(self, objs):
+        """pt_scene_update: the scene of upload(objs) with the temporal history kept (same object count and shape tags)."""
+        check(lib().pt_scene_update(self._h, objs, len(objs)))
+        self._objs = objs
+
     def set_stream(self, hip_stream_ptr):
         """Render on a caller-owned stream.  0 is the handle of HIP's legacy default stream (torch's default stream):
         it is passed on as PT_STREAM_LEGACY_DEFAULT, so the render is ordered against the caller's other work there;
@@ -394,6 +399,57 @@ class _ContextFunctions:
                                                 noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p)))
         return lin, rgba, noisy, feat
 
+    def feature_ids(self, cam, params):
+        """pt_render_feature_ids_device: the object hit by the primary ray of sample spp_offset, -1 for a miss -> i32[H,W]"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        ids = torch.empty((cam.height, cam.width), dtype=torch.int32, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_render_feature_ids_device(self._h, C.byref(cam), C.byref(params), C.c_void_p(ids.data_ptr())))
+        self.sync()
+        return ids.cpu().numpy()
+
+    def denoise_temporal_motion(self, cam, linear, features, ids, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
+                                alpha=None, depth_tol=None, normal_tol=None):
+        """pt_denoise_temporal_motion_device: denoise_temporal with the per-pixel object ids (i32[H,W]); the history follows
+        the objects moved by scene_update since the last temporal frame.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
+        import torch
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
+        linear = np.ascontiguousarray(linear, dtype=np.float32)
+        features = np.ascontiguousarray(features, dtype=np.float32)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        H, W = cam.height, cam.width
+        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8) and ids.shape == (H, W)
+        dev = torch.device("cuda", self.device)
+        d_lin, d_feat, d_ids = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev), torch.from_numpy(ids).to(dev)
+        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_denoise_temporal_motion_device(self._h, C.byref(cam), C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()),
+                                                      C.c_void_p(d_ids.data_ptr()), C.byref(dn), C.byref(tp),
+                                                      C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
+        self.sync()
+        return out.cpu().numpy(), rgba.cpu().numpy()
+
+    def render_denoised_motion(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
+                               alpha=None, depth_tol=None, normal_tol=None):
+        """pt_render_denoised_motion (host buffers, blocking): one frame of the temporal denoiser that follows moving objects.
+        -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3], features f32[H,W,8], ids i32[H,W])"""
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
+        H, W = cam.height, cam.width
+        lin = np.empty((H, W, 3), dtype=np.float32)
+        rgba = np.empty((H, W, 4), dtype=np.uint8)
+        noisy = np.empty((H, W, 3), dtype=np.float32)
+        feat = np.empty((H, W, 8), dtype=np.float32)
+        ids = np.empty((H, W), dtype=np.int32)
+        check(lib().pt_render_denoised_motion(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp),
+                                              lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
+                                              noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p),
+                                              ids.ctypes.data_as(C.c_void_p)))
+        return lin, rgba, noisy, feat, ids
+
     def ray_color(self, params, rays, xy):
         """pt_ray_color = RenderingStrategy::ray_color(world, ray, 0, rng(key xy, sample spp_offset), 1) -> f32[n,3]"""
         rays = _f64(rays, 6)
@@ -511,6 +567,17 @@ def path_instance(code):
             3: [b(d["mis"]), str(d["mats"])]}[fam]
     d["kernel"] = "%s<%s>" % (_FAMILIES[fam], ", ".join(args))
     return d
+
+
+def motion_maps(prev_objs, cur_objs):
+    """pt_debug_motion_maps (host only): per object the map current pose -> previous pose.
+    -> (A f64[n,3,3], b f64[n,3], flags u32[n]: bit 0 identity, bit 1 invalid)"""
+    n = len(cur_objs)
+    assert len(prev_objs) == n
+    maps = np.zeros((n, 12), dtype=np.float64)
+    flags = np.zeros(n, dtype=np.uint32)
+    check(lib().pt_debug_motion_maps(prev_objs, cur_objs, n, _pd(maps), _pu(flags)))
+    return maps[:, :9].reshape(n, 3, 3).copy(), maps[:, 9:].copy(), flags
 
 
 def bvh_check(objs):

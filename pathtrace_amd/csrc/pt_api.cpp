@@ -20,6 +20,7 @@
 #include "../../include/pathtrace_amd.h"
 #include "pt_bvh.h"
 #include "pt_kernels.h"
+#include "pt_motion.h"
 #include "pt_sched.h"
 
 #ifdef PT_SAN_NO_KERNELS
@@ -37,6 +38,7 @@ void launch_feature_resolve_exact(const FeatureResolveArgs&, hipStream_t) { std:
 void launch_feature_resolve_fast(const FeatureResolveArgs&, hipStream_t) { std::abort(); }
 void launch_denoise(const DenoiseArgs&, bool, hipStream_t) { std::abort(); }
 void launch_denoise_temporal(const TemporalArgs&, hipStream_t) { std::abort(); }
+void launch_denoise_temporal_motion(const TemporalMotionArgs&, hipStream_t) { std::abort(); }
 }  // namespace ptk
 #endif
 
@@ -238,6 +240,18 @@ struct PtContext {
     uint32_t tm_cur = 0;
     bool tm_valid = false;
     PtCamera tm_cam{};
+    // pt_scene_update / pt_denoise_temporal_motion_device: the f64 shape fields (9 per object) of the current scene and of the
+    // HISTORY POSE, the scene as it was when a temporal entry last stored a history frame; pose_gen counts the scene changes,
+    // tm_pose_gen is its value at that snapshot, and mo_key names the pair of poses the device maps were computed from
+    std::vector<double> pose, tm_pose;
+    uint64_t pose_gen = 0, tm_pose_gen = 0, mo_key[2] = {~0ull, ~0ull};
+    // two host staging vectors, used in turn: mo_staged[k] is recorded behind the copy out of h_maps[k], so a new set of maps
+    // waits only for the copy of two sets ago, not for the stream
+    std::vector<ptk::MotionMap> h_maps[2];
+    hipEvent_t mo_staged[2] = {nullptr, nullptr};
+    uint32_t mo_slot = 0;
+    DevBuf<ptk::MotionMap> mo_maps;
+    DevBuf<int32_t> dn_ids;                   // pt_render_denoised_motion: device staging of the ids
 };
 
 namespace {
@@ -495,6 +509,8 @@ int pt_context_destroy(PtContext* c) {
     c->ft_rays.release(); c->ft_t.release(); c->ft_rec.release(); c->ft_ids.release(); c->ft_scratch.release();
     c->dn_plane[0].release(); c->dn_plane[1].release(); c->dn_feat.release(); c->dn_lin.release();
     c->tm_hist[0].release(); c->tm_hist[1].release();
+    c->mo_maps.release(); c->dn_ids.release();
+    for (int k = 0; k < 2; ++k) if (c->mo_staged[k]) (void)hipEventDestroy(c->mo_staged[k]);
     for (auto& b : c->inject) b.release();
     if (c->h_dstats) (void)hipHostFree(c->h_dstats);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -526,9 +542,20 @@ int pt_context_set_tuning(PtContext* c, const PtTuning* t) {
     return PT_OK;
 }
 
-// World::new's tail (world.rs:213-225) + flattening of Box<dyn Shape>/Box<dyn Material>.
-int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) {
-    if (!c || (!objs && n)) return fail(PT_ERR_INVALID_ARG, "pt_scene_upload: null argument");
+}  // extern "C"
+
+namespace {
+// World::new's tail (world.rs:213-225) + flattening of Box<dyn Shape>/Box<dyn Material>: the body of pt_scene_upload and of
+// pt_scene_update (keep_history: same object count and shape tags as the uploaded scene, and the temporal history stays).
+int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, bool keep_history) {
+    if (!c || (!objs && n)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if (keep_history) {
+        if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
+        if (n != c->view.n_objs) return fail(PT_ERR_INVALID_ARG, "%s: %u objects, the uploaded scene has %u", who, n, c->view.n_objs);
+        for (uint32_t i = 0; i < n; ++i)
+            if (objs[i].shape_tag != c->h_shape_tag[i])
+                return fail(PT_ERR_INVALID_ARG, "%s: object %u: shape_tag %u, the uploaded scene has %u", who, i, objs[i].shape_tag, c->h_shape_tag[i]);
+    }
     HIP_TRY(hipSetDevice(c->device));
     std::vector<float4> scan, shape(3 * (size_t)n + 1), mat(2 * (size_t)n + 1), obj_scan(3 * (size_t)n + 1);
     std::vector<int> obj_ns(n + 1, 0);
@@ -677,7 +704,26 @@ int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) {
     c->h_shape_tag.resize(n);
     for (uint32_t i = 0; i < n; ++i) c->h_shape_tag[i] = objs[i].shape_tag;
     c->has_scene = true;
-    c->tm_valid = false;              // object motion is out of scope: a new scene starts the temporal history afresh
+    c->pose.resize(9 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) std::memcpy(&c->pose[9 * (size_t)i], objs[i].shape, 9 * sizeof(double));
+    ++c->pose_gen;
+    if (!keep_history) c->tm_valid = false;   // a new scene starts the temporal history afresh; pt_scene_update keeps it
+    return PT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_upload", c, objs, n, false); }
+int pt_scene_update(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_update", c, objs, n, true); }
+
+int pt_debug_motion_maps(const PtObject* prev_objs, const PtObject* cur_objs, uint32_t n, double* out_maps, uint32_t* out_flags) {
+    if (n && (!prev_objs || !cur_objs || !out_maps || !out_flags)) return fail(PT_ERR_INVALID_ARG, "pt_debug_motion_maps: null argument");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (prev_objs[i].shape_tag > PT_SHAPE_TRIANGLE || prev_objs[i].shape_tag != cur_objs[i].shape_tag)
+            return fail(PT_ERR_INVALID_ARG, "pt_debug_motion_maps: object %u: shape tags %u and %u", i, prev_objs[i].shape_tag, cur_objs[i].shape_tag);
+        out_flags[i] = ptmo::motion_map(cur_objs[i].shape_tag == PT_SHAPE_TRIANGLE, cur_objs[i].shape, prev_objs[i].shape, out_maps + 12 * (size_t)i);
+    }
     return PT_OK;
 }
 
@@ -1664,17 +1710,23 @@ int pt_render_adaptive(PtContext* c, const PtCamera* cam, const PtRenderParams* 
 
 // First-hit features: per batch of samples, k_feature_rays writes the camera rays, launch_debug_hit (the scan or BVH of the
 // parity entries) finds their hits, k_feature_resolve adds the records to the per-pixel sums in d_features.
-int pt_render_features_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t n_samples, float* d_features) {
-    if (!c || !cam || !prm || !d_features) return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: null argument");
-    if (n_samples == 0) return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: n_samples must be > 0");
+// pt_render_feature_ids_device is the same pass over the one sample spp_offset without the resolve: the hit ids of that batch,
+// copied out of the scratch (d_features null, d_ids set).
+}  // extern "C"
+namespace {
+int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t n_samples, float* d_features,
+                  int32_t* d_ids) {
+    if (!c || !cam || !prm || (!d_features && !d_ids)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if (n_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: n_samples must be > 0", who);
     if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: works on the whole image (band_count = 1)");
-    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: d_features must be 16-byte aligned");
+        return fail(PT_ERR_INVALID_ARG, "%s: works on the whole image (band_count = 1)", who);
+    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
+    if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
     if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
     if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
     if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
     const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_render_features_device: %llu pixels", (unsigned long long)np64);
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
     const uint32_t np = (uint32_t)np64;
     HIP_TRY(hipSetDevice(c->device));
     uint32_t accel = prm->accel;
@@ -1708,16 +1760,29 @@ int pt_render_features_device(PtContext* c, const PtCamera* cam, const PtRenderP
         if (prm->exact_math) {
             ptk::launch_feature_rays_exact(cf, s_base, nb, c->ft_rays.p, st);
             ptk::launch_debug_hit_exact(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
-            ptk::launch_feature_resolve_exact(a, st);
+            if (d_features) ptk::launch_feature_resolve_exact(a, st);
         } else {
             ptk::launch_feature_rays_fast(cf, s_base, nb, c->ft_rays.p, st);
             ptk::launch_debug_hit_fast(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
-            ptk::launch_feature_resolve_fast(a, st);
+            if (d_features) ptk::launch_feature_resolve_fast(a, st);
         }
         HIP_TRY(hipGetLastError());
+        if (d_ids && done == 0) HIP_TRY(hipMemcpyAsync(d_ids, c->ft_ids.p, (size_t)np * sizeof(int32_t), hipMemcpyDeviceToDevice, st));   // sample spp_offset
         done += nb;
     }
     return PT_OK;
+}
+}  // namespace
+extern "C" {
+
+int pt_render_features_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t n_samples, float* d_features) {
+    if (!d_features) return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: null argument");
+    return features_impl("pt_render_features_device", c, cam, prm, n_samples, d_features, nullptr);
+}
+
+int pt_render_feature_ids_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, int32_t* d_ids) {
+    if (!d_ids) return fail(PT_ERR_INVALID_ARG, "pt_render_feature_ids_device: null argument");
+    return features_impl("pt_render_feature_ids_device", c, cam, prm, 1, nullptr, d_ids);
 }
 
 void pt_default_denoise(PtDenoise* out) {
@@ -1730,10 +1795,11 @@ void pt_default_denoise(PtDenoise* out) {
 namespace {
 // The a-trous iterations of pt_denoise_device and pt_denoise_temporal_device: (u, var) waits in plane 0; one k_denoise_step
 // per iteration between the two planes, the last launch writes the film planes.
-// pt_render_denoised and pt_render_denoised_temporal (tp != null): render, features, filter; host buffers, blocking
+// pt_render_denoised, pt_render_denoised_temporal (tp != null) and pt_render_denoised_motion (motion: the ids pass and the
+// motion entry): render, features, filter; host buffers, blocking
 int render_denoised_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                          const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                         float* out_features) {
+                         float* out_features, bool motion = false, int32_t* out_ids = nullptr) {
     if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
         return fail(PT_ERR_INVALID_ARG, "%s: renders the whole image (band_count = 1)", who);
     if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
@@ -1745,7 +1811,7 @@ int render_denoised_impl(const char* who, PtContext* c, const PtCamera* cam, con
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) ||
-        (rc = c->dn_lin.ensure(3 * np)))
+        (rc = c->dn_lin.ensure(3 * np)) || (motion && (rc = c->dn_ids.ensure(np))))
         return rc;
     PtRenderParams p = *prm;
     p.band_count = 1; p.band_index = 0; p.band_rows = 0;
@@ -1753,14 +1819,17 @@ int render_denoised_impl(const char* who, PtContext* c, const PtCamera* cam, con
     uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
     if ((rc = render_impl(c, cam, &p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
         (rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat)) ||
-        (rc = tp ? pt_denoise_temporal_device(c, cam, c->host_lin.p, feat, dn, tp, c->dn_lin.p, rgba)
-                 : pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, feat, dn, c->dn_lin.p, rgba)) ||
+        (motion && (rc = pt_render_feature_ids_device(c, cam, &p, c->dn_ids.p))) ||
+        (rc = motion ? pt_denoise_temporal_motion_device(c, cam, c->host_lin.p, feat, c->dn_ids.p, dn, tp, c->dn_lin.p, rgba)
+              : tp   ? pt_denoise_temporal_device(c, cam, c->host_lin.p, feat, dn, tp, c->dn_lin.p, rgba)
+                     : pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, feat, dn, c->dn_lin.p, rgba)) ||
         (rc = pt_sync(c)))
         return rc;
     HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
     if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
     if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
     if (out_features) HIP_TRY(hipMemcpy(out_features, feat, 8 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_ids) HIP_TRY(hipMemcpy(out_ids, c->dn_ids.p, np * sizeof(int32_t), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 int denoise_steps(PtContext* c, ptk::DenoiseArgs a, uint32_t iterations) {
@@ -1824,30 +1893,68 @@ int pt_temporal_reset(PtContext* c) {
     return PT_OK;
 }
 
+}  // extern "C"
+namespace {
+// The maps current pose -> history pose of every object into c->mo_maps, on the context's stream.  Unchanged poses since the
+// last call: the buffer already holds them.
+int upload_motion_maps(PtContext* c) {
+    const uint32_t n = c->view.n_objs;
+    int rc;
+    if ((rc = c->mo_maps.ensure((size_t)n + 1))) return rc;
+    const bool hist = c->tm_valid && c->tm_pose.size() == c->pose.size();     // no history: every pixel is fresh anyway
+    const uint64_t key[2] = {c->pose_gen, hist ? c->tm_pose_gen : ~0ull};
+    if (key[0] == c->mo_key[0] && key[1] == c->mo_key[1]) return PT_OK;
+    // (the copy below reads the staging vector when the stream reaches it: the copy that last read this vector must be through;
+    // the stream's order keeps the kernels that read the device maps ahead of the copy that replaces them)
+    const uint32_t slot = c->mo_slot ^= 1u;
+    if (!c->mo_staged[slot]) HIP_TRY(hipEventCreateWithFlags(&c->mo_staged[slot], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(c->mo_staged[slot]));
+    std::vector<ptk::MotionMap>& h_maps = c->h_maps[slot];
+    h_maps.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        ptk::MotionMap& m = h_maps[i];
+        const double* cur = &c->pose[9 * (size_t)i];
+        double out[12];
+        m.flags = ptmo::motion_map(c->h_shape_tag[i] == PT_SHAPE_TRIANGLE, cur, hist ? &c->tm_pose[9 * (size_t)i] : cur, out);
+        m.pad = 0;
+        std::memcpy(m.a, out, 9 * sizeof(double)); std::memcpy(m.b, out + 9, 3 * sizeof(double));
+    }
+    if (n) HIP_TRY(hipMemcpyAsync(c->mo_maps.p, h_maps.data(), (size_t)n * sizeof(ptk::MotionMap), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->mo_staged[slot], c->stream));
+    c->mo_key[0] = key[0]; c->mo_key[1] = key[1];
+    return PT_OK;
+}
+
 // Temporal accumulation: k_denoise_temporal (history -> (u, var) in plane 0 and the next history), then the a-trous steps of
-// pt_denoise_device.  The arguments are checked before the context is looked at.
-int pt_denoise_temporal_device(PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features,
-                               const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba) {
-    if (!cam || !dn || !tp || !d_linear || !d_features || !d_out_linear)
-        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: null argument");
+// pt_denoise_device.  The arguments are checked before the context is looked at.  d_ids: the motion entry, whose kernel is
+// k_denoise_temporal_motion.  Both store a history frame, and with it the scene's pose becomes the history pose.
+int temporal_impl(const char* who, PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features, const int32_t* d_ids,
+                  bool motion, const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba) {
+    if (!cam || !dn || !tp || !d_linear || !d_features || !d_out_linear || (motion && !d_ids))
+        return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (cam->width < 2 || cam->height < 2)
-        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: camera %ux%u: width and height must be >= 2", cam->width, cam->height);
-    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: %u iterations (at most 16)", dn->iterations);
+        return fail(PT_ERR_INVALID_ARG, "%s: camera %ux%u: width and height must be >= 2", who, cam->width, cam->height);
+    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "%s: %u iterations (at most 16)", who, dn->iterations);
     if (!(dn->sigma_l >= 0.0f) || !(dn->sigma_n >= 0.0f) || !(dn->sigma_d >= 0.0f) || !std::isfinite(dn->sigma_l) ||
         !std::isfinite(dn->sigma_n) || !std::isfinite(dn->sigma_d))
-        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: sigma_l, sigma_n and sigma_d must be finite and >= 0");
-    if (!(tp->alpha >= 0.0f && tp->alpha <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: alpha %g not in [0, 1]", tp->alpha);
+        return fail(PT_ERR_INVALID_ARG, "%s: sigma_l, sigma_n and sigma_d must be finite and >= 0", who);
+    if (!(tp->alpha >= 0.0f && tp->alpha <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "%s: alpha %g not in [0, 1]", who, tp->alpha);
     if (!(tp->depth_tol >= 0.0f) || !(tp->normal_tol >= 0.0f) || !std::isfinite(tp->depth_tol) || !std::isfinite(tp->normal_tol))
-        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: depth_tol and normal_tol must be finite and >= 0");
-    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: d_features must be 16-byte aligned");
+        return fail(PT_ERR_INVALID_ARG, "%s: depth_tol and normal_tol must be finite and >= 0", who);
+    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
     if ((uintptr_t)d_linear % 4u || (uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u)
-        return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: the film buffers must be 4-byte aligned");
-    if (d_out_linear == d_linear) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: the output must not be the input");
+        return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
+    if (d_out_linear == d_linear) return fail(PT_ERR_INVALID_ARG, "%s: the output must not be the input", who);
     const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_denoise_temporal_device: %llu pixels", (unsigned long long)np64);
-    if (!c) return fail(PT_ERR_INVALID_ARG, "pt_denoise_temporal_device: null context");
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
+    if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
+    if (motion && !c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
+    if (motion && c->view.n_objs > (1u << 24) - 2u)
+        return fail(PT_ERR_UNSUPPORTED, "%s: %u objects (an id + 1 must be exact in the history's f32 lane: at most 2^24 - 2)", who, c->view.n_objs);
     HIP_TRY(hipSetDevice(c->device));
     int rc;
+    if (motion && (rc = upload_motion_maps(c))) return rc;
     if ((rc = c->dn_plane[0].ensure(np64)) || (rc = c->dn_plane[1].ensure(np64)) || (rc = c->tm_hist[0].ensure(3 * np64)) ||
         (rc = c->tm_hist[1].ensure(3 * np64)))
         return rc;
@@ -1872,11 +1979,41 @@ int pt_denoise_temporal_device(PtContext* c, const PtCamera* cam, const float* d
     }
     t.same_camera = same;
     t.alpha = tp->alpha; t.depth_tol = tp->depth_tol; t.normal_tol = tp->normal_tol;
-    ptk::launch_denoise_temporal(t, c->stream);
+    if (motion) {
+        ptk::TemporalMotionArgs m{};
+        m.t = t; m.ids = d_ids; m.maps = c->mo_maps.p; m.n_objs = c->view.n_objs;
+        ptk::launch_denoise_temporal_motion(m, c->stream);
+    } else {
+        ptk::launch_denoise_temporal(t, c->stream);
+    }
     HIP_TRY(hipGetLastError());
     c->tm_cur ^= 1u; c->tm_valid = true; c->tm_cam = *cam;
+    if (!c->has_scene) c->tm_pose.clear();
+    else if (c->tm_pose_gen != c->pose_gen || c->tm_pose.size() != c->pose.size()) c->tm_pose = c->pose;
+    c->tm_pose_gen = c->pose_gen;
     return denoise_steps(c, a, dn->iterations);
 }
+}  // namespace
+extern "C" {
+
+int pt_denoise_temporal_device(PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features,
+                               const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba) {
+    return temporal_impl("pt_denoise_temporal_device", c, cam, d_linear, d_features, nullptr, false, dn, tp, d_out_linear, d_out_rgba);
+}
+
+int pt_denoise_temporal_motion_device(PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features, const int32_t* d_ids,
+                                      const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba) {
+    return temporal_impl("pt_denoise_temporal_motion_device", c, cam, d_linear, d_features, d_ids, true, dn, tp, d_out_linear, d_out_rgba);
+}
+
+int pt_render_denoised_motion(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
+                              const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy, float* out_features,
+                              int32_t* out_ids) {
+    if (!c || !cam || !prm || !dn || !tp || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised_motion: null argument");
+    return render_denoised_impl("pt_render_denoised_motion", c, cam, prm, feature_samples, dn, tp, out_linear, out_rgba, out_noisy,
+                                out_features, true, out_ids);
+}
+
 
 int pt_render_denoised_temporal(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                                 const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,

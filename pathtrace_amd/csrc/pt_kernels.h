@@ -323,4 +323,20 @@ struct TemporalArgs {
 };
 void launch_denoise_temporal(const TemporalArgs& a, hipStream_t st);
 
+// Temporal accumulation that follows moving objects (pt_denoise_temporal_motion_device; rule: include/pathtrace_amd.h, rules
+// 1', 2', 3', 7').  k_denoise_temporal_motion in place of k_denoise_temporal: additionally reads the pixel's object id and that
+// object's motion map (current pose -> history pose, pt_motion.h), and keeps id + 1 in the history's free lane:
+// (m2, n, emitter, id + 1 as float; 0 = unknown, which is what k_denoise_temporal stores).
+struct MotionMap {             // 104 bytes
+    double a[9], b[3];         // x -> a x + b, a row-major
+    uint32_t flags, pad;       // bit 0 identity, bit 1 invalid (ptmo::kIdentity, kInvalid)
+};
+struct TemporalMotionArgs {
+    TemporalArgs t;
+    const int32_t* ids;        // width * height, the caller's: bounds-checked against n_objs before a map is read
+    const MotionMap* maps;     // n_objs
+    uint32_t n_objs;
+};
+void launch_denoise_temporal_motion(const TemporalMotionArgs& a, hipStream_t st);
+
 }  // namespace ptk

@@ -403,3 +403,128 @@ void launch_denoise_temporal(const TemporalArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(PTK_IMPL::k_denoise_temporal, g, b, 0, st, a);
 }
 }  // namespace ptk
+
+// ------------------------------------------------------------------ ... that follows moving objects (pt_denoise_temporal_motion_device)
+// Rules 1', 2', 3' and 7' of include/pathtrace_amd.h and DESIGN.md 5d.  k_denoise_temporal with three additions: the pixel's
+// point goes back along its object's motion map (f64) before the camera reprojection, the normal gate takes the normal
+// carried by that map, and a tap of another object's history is taken only when neither object moved.  A pixel whose map
+// is the identity runs k_denoise_temporal's statements in their order: with the unknown ids that kernel stores, or in a
+// scene where nothing moved, the two kernels write the same bits.  The functions are this kernel's own copies.
+namespace PTK_IMPL {
+// tm_reproject with P carried to the history pose by mp first (mp null: the identity, P as it is)
+PT_DEV bool tmm_reproject(const TemporalArgs& a, const MotionMap* mp, uint32_t x, uint32_t y, float d, double& xr, double& yr, double& dexp) {
+    const double* o = a.cur; const double* l = a.cur + 3; const double* hz = a.cur + 6; const double* vt = a.cur + 9;
+    const double* o2 = a.prev; const double* l2 = a.prev + 3; const double* hz2 = a.prev + 6; const double* vt2 = a.prev + 9;
+    const double W1 = (double)(a.dn.width - 1u), H1 = (double)(a.dn.height - 1u);
+    const double s = ((double)x + 0.5) / W1, t = ((double)(a.dn.height - 1u - y) + 0.5) / H1;
+    double D[3], P[3], c[3], r[3], bc[3], rc[3], br[3];
+    for (int k = 0; k < 3; ++k) D[k] = l[k] + s * hz[k] + t * vt[k] - o[k];
+    const double inv_len = 1.0 / __builtin_sqrt(tm_dot(D, D));
+    for (int k = 0; k < 3; ++k) P[k] = o[k] + (double)d * (D[k] * inv_len);
+    if (mp) {
+        double Ph[3];
+        for (int k = 0; k < 3; ++k) Ph[k] = mp->a[3 * k] * P[0] + mp->a[3 * k + 1] * P[1] + mp->a[3 * k + 2] * P[2] + mp->b[k];
+        for (int k = 0; k < 3; ++k) P[k] = Ph[k];
+    }
+    for (int k = 0; k < 3; ++k) {
+        c[k] = o2[k] - P[k];                 // -(P_h - o')
+        r[k] = o2[k] - l2[k];
+    }
+    tm_cross(vt2, c, bc);
+    const double det = tm_dot(hz2, bc);
+    if (!(det != 0.0) || !__builtin_isfinite(det)) return false;
+    tm_cross(r, c, rc);
+    tm_cross(vt2, r, br);
+    const double inv = 1.0 / det;
+    const double s2 = tm_dot(r, bc) * inv, t2 = tm_dot(hz2, rc) * inv, lam = tm_dot(hz2, br) * inv;
+    if (!(lam > 0.0) || !__builtin_isfinite(s2) || !__builtin_isfinite(t2) || !__builtin_isfinite(lam)) return false;
+    xr = s2 * W1 - 0.5;
+    yr = (double)a.dn.height - 0.5 - t2 * H1;
+    dexp = __builtin_sqrt(tm_dot(c, c));
+    return true;
+}
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_temporal_motion(TemporalMotionArgs m) {
+    const TemporalArgs& a = m.t;
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.dn.width || y >= a.dn.height) return;
+    const int W = (int)a.dn.width, H = (int)a.dn.height;
+    const size_t p = (size_t)y * a.dn.width + x;
+    const float4 f0p = a.dn.feat[2 * p], f1p = a.dn.feat[2 * p + 1];
+    const float3 uc = dn_demod(a.dn, p);
+    const float Lc = dn_lum(uc.x, uc.y, uc.z);
+    // the caller's id: checked against the scene before it indexes the maps
+    const int32_t id = m.ids[p];
+    const bool known = id >= 0 && (uint32_t)id < m.n_objs;
+    const uint32_t flags = known ? m.maps[id].flags : 2u;
+    const bool ident = flags == 1u;
+    const float idf = known ? (float)(id + 1) : 0.0f;       // n_objs <= 2^24 - 2: exact
+    float S = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hm1 = 0.0f, hm2 = 0.0f, hn = 0.0f;
+    if (a.hist_src && f1p.w > 0.0f && !(flags & 2u)) {
+        double xr = x, yr = y, dexp = f1p.w;
+        float nx = f1p.x, ny = f1p.y, nz = f1p.z;
+        bool ok = true;
+        if (!(ident && a.same_camera)) {
+            const MotionMap* mp = ident ? nullptr : m.maps + id;
+            ok = tmm_reproject(a, mp, x, y, f1p.w, xr, yr, dexp);
+            if (mp) {                         // n_h = A n_p, normalised in f64 (n_p when its length is 0)
+                double v[3];
+                for (int k = 0; k < 3; ++k) v[k] = mp->a[3 * k] * (double)f1p.x + mp->a[3 * k + 1] * (double)f1p.y + mp->a[3 * k + 2] * (double)f1p.z;
+                const double len = __builtin_sqrt(tm_dot(v, v));
+                if (len > 0.0) { nx = (float)(v[0] / len); ny = (float)(v[1] / len); nz = (float)(v[2] / len); }
+            }
+        }
+        if (ok && xr > -1.0 && xr < (double)W && yr > -1.0 && yr < (double)H) {
+            const int x0 = (int)__builtin_floor(xr), y0 = (int)__builtin_floor(yr);
+            const float fx = (float)(xr - x0), fy = (float)(yr - y0);
+            const float de = (float)dexp, dmax = a.depth_tol * de;
+            const bool em = f0p.w > 0.0f;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int qx = x0 + i, qy = y0 + j;
+                    const float w = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+                    if (!(w > 0.0f) || qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+                    const size_t q = (size_t)qy * W + qx;
+                    const float4 h2 = a.hist_src[3 * q + 2];
+                    if (!(h2.w > 0.0f) || !(fabsf(h2.w - de) <= dmax)) continue;
+                    if (!(nx * h2.x + ny * h2.y + nz * h2.z >= a.normal_tol)) continue;
+                    const float4 h1 = a.hist_src[3 * q + 1];
+                    if (em != (h1.z > 0.0f)) continue;
+                    if (h1.w != 0.0f && h1.w != idf) {       // another object's history: only when neither object moved
+                        if (!ident || !(h1.w >= 1.0f && h1.w <= (float)m.n_objs)) continue;
+                        if (m.maps[(uint32_t)h1.w - 1u].flags != 1u) continue;
+                    }
+                    const float4 h0 = a.hist_src[3 * q];
+                    S += w;
+                    hr += w * h0.x; hg += w * h0.y; hb += w * h0.z; hm1 += w * h0.w;
+                    hm2 += w * h1.x; hn += w * h1.y;
+                }
+        }
+    }
+    float3 u = uc;
+    float m1 = Lc, m2 = Lc * Lc, n = 1.0f;            // a fresh pixel
+    if (S >= 1e-2f) {
+        const float inv = 1.0f / S;
+        const float ur = hr * inv, ug = hg * inv, ub = hb * inv, um1 = hm1 * inv, um2 = hm2 * inv;
+        n = hn * inv + 1.0f;
+        const float al = fmaxf(a.alpha, 1.0f / n);
+        u = make_float3(ur + al * (uc.x - ur), ug + al * (uc.y - ug), ub + al * (uc.z - ub));
+        m1 = um1 + al * (Lc - um1);
+        m2 = um2 + al * (Lc * Lc - um2);
+    }
+    const float var = n >= 4.0f ? fmaxf(0.0f, m2 - m1 * m1) : dn_spatial_var(a.dn, x, y);
+    a.hist_dst[3 * p] = make_float4(u.x, u.y, u.z, m1);
+    a.hist_dst[3 * p + 1] = make_float4(m2, n, f0p.w, idf);
+    a.hist_dst[3 * p + 2] = f1p;
+    if (a.dn.finalize) dn_store(a.dn, p, u.x, u.y, u.z, f0p);
+    else a.dn.dst[p] = make_float4(u.x, u.y, u.z, var);
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_denoise_temporal_motion(const TemporalMotionArgs& a, hipStream_t st) {
+    const dim3 g((a.t.dn.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.t.dn.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy),
+        b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
+    hipLaunchKernelGGL(PTK_IMPL::k_denoise_temporal_motion, g, b, 0, st, a);
+}
+}  // namespace ptk

@@ -13,6 +13,7 @@
 //   World::render()  == the closure of main() src/main.rs:43-60  (new name)
 //   World::render_denoised()  render() + first-hit features + the a-trous denoiser (beyond the reference)
 //   World::render_denoised_temporal()  the same with temporal accumulation over the frames of the persistent context
+//   World::render_denoised_motion()    ... whose history also follows objects moved with set_object() + scene_update()
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -309,7 +310,7 @@ public:
             if (ctx_) pt_context_destroy(ctx_);
             camera_ = o.camera_; objects_ = std::move(o.objects_); params_ = o.params_;
             data = std::move(o.data); luminance_data = std::move(o.luminance_data);
-            ctx_ = o.ctx_; o.ctx_ = nullptr; uploaded_ = o.uploaded_;
+            ctx_ = o.ctx_; o.ctx_ = nullptr; uploaded_ = o.uploaded_; moved_ = o.moved_;
         }
         return *this;
     }
@@ -479,6 +480,31 @@ public:
             for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
         }
     }
+    // Replaces object i (same kind of shape).  The next call that uses the scene re-sends the object list through
+    // pt_scene_update, which keeps the temporal history (push() and the first use go through pt_scene_upload, which empties
+    // it); scene_update() does so at once.
+    void set_object(size_t i, const Object& o) { objects_.at(i) = o.pod(); moved_ = true; }
+    void scene_update(int device = 0) { scene(device); }
+    // render_denoised_temporal() whose history also follows the objects moved by set_object() + scene_update()
+    // (pt_render_denoised_motion).  ids (optional) receives the object index of every pixel's first hit, -1 for a miss.
+    void render_denoised_motion(uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, const PtTemporal* tp = nullptr,
+                                std::vector<int32_t>* ids = nullptr, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtDenoise d{};
+        if (dn) d = *dn; else pt_default_denoise(&d);
+        PtTemporal t{};
+        if (tp) t = *tp; else pt_default_temporal(&t);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3);
+        std::vector<uint8_t> rgba(n * 4);
+        if (ids) ids->resize(n);
+        check(pt_render_denoised_motion(ctx_, &camera_.pod(), &p, feature_samples, &d, &t, lin.data(), rgba.data(), nullptr, nullptr,
+                                        ids ? ids->data() : nullptr));
+        unpack(lin, rgba);
+    }
     // the next render_denoised_temporal starts without history (pt_temporal_reset)
     void temporal_reset() { if (ctx_) check(pt_temporal_reset(ctx_)); }
     // moves the camera (the film follows its size); the temporal history stays and is reprojected
@@ -553,6 +579,7 @@ private:
     PtRenderParams params_{};
     PtContext* ctx_ = nullptr;
     bool uploaded_ = false;
+    bool moved_ = false;      // set_object() since the scene was last sent
     PtRenderParams tmp_params_{};
 
     // the context with this World's objects on it (uploaded again after push())
@@ -560,6 +587,8 @@ private:
         check_abi();
         if (!ctx_) check(pt_context_create(device, &ctx_));
         if (!uploaded_) { check(pt_scene_upload(ctx_, objects_.data(), (uint32_t)objects_.size())); uploaded_ = true; }
+        else if (moved_) check(pt_scene_update(ctx_, objects_.data(), (uint32_t)objects_.size()));
+        moved_ = false;
         return ctx_;
     }
     const PtRenderParams& whole_image_params() {

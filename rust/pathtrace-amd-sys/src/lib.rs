@@ -261,6 +261,11 @@ extern "C" {
     pub fn pt_temporal_reset(ctx: *mut PtContext) -> c_int;
     pub fn pt_denoise_temporal_device(ctx: *mut PtContext, cam: *const PtCamera, d_linear_rgb: *const f32, d_features: *const f32, dn: *const PtDenoise, tp: *const PtTemporal, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_denoised_temporal(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, tp: *const PtTemporal, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
+    pub fn pt_scene_update(ctx: *mut PtContext, objs: *const PtObject, n_objs: u32) -> c_int;
+    pub fn pt_debug_motion_maps(prev_objs: *const PtObject, cur_objs: *const PtObject, n: u32, out_maps: *mut f64, out_flags: *mut u32) -> c_int;
+    pub fn pt_render_feature_ids_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, d_ids: *mut i32) -> c_int;
+    pub fn pt_denoise_temporal_motion_device(ctx: *mut PtContext, cam: *const PtCamera, d_linear_rgb: *const f32, d_features: *const f32, d_ids: *const i32, dn: *const PtDenoise, tp: *const PtTemporal, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_denoised_motion(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, tp: *const PtTemporal, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32, out_ids: *mut i32) -> c_int;
     pub fn pt_ray_color(ctx: *mut PtContext, params: *const PtRenderParams, rays: *const f64, xy: *const u32, n: u32, out_rgb: *mut f32) -> c_int;
     pub fn pt_debug_hit_scene(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_t: *mut f32) -> c_int;
     pub fn pt_debug_hit_records(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_rec: *mut f32) -> c_int;

@@ -1,13 +1,20 @@
 #!/usr/bin/env python3
 """Temporal denoiser on one GPU: a C2 camera fly-through at 1024^2, 1 spp and 1 feature sample per frame; one JSON line.
     python tools/temporal_bench.py [--frames N] [--size S] [--images DIR]
+    python tools/temporal_bench.py --moving [--frames N] [--size S]
 
 Per frame, on the context's stream between device events: render (pt_render_device), features
 (pt_render_features_device), the temporal kernel and the a-trous steps (pt_denoise_temporal_device with iterations = 0,
 and with the default 5 iterations; the steps are the difference), medians over the frames after the first.  fresh: the
 fraction of fresh pixels per frame, read from a second pass over the same frames with a zero film followed by a film of
 ones (a fresh pixel shows 1, a pixel with history 1 - alpha').  static_fresh: the same on frames of a camera that does not
-move, with misses counted apart.  --images DIR writes noisy | spatial | temporal | 4096-spp reference of the last frame."""
+move, with misses counted apart.  --images DIR writes noisy | spatial | temporal | 4096-spp reference of the last frame.
+
+--moving: a static camera on C2 while the smallest sphere crosses the floor (pt_scene_update per frame).  The same film,
+features and ids go to k_denoise_temporal_motion on one context and to k_denoise_temporal on a second one (iterations = 0: the
+kernel alone, the motion entry's map upload included), device events, medians; then the motion kernel on a scene in which
+nothing moves; then the host time of pt_scene_update against pt_scene_upload, alone and with the first 64 x 64 x 1 render
+after it (which rebuilds the BVH where accel = 1), on C2 and on 10 000 spheres."""
 import argparse
 import ctypes as C
 import json
@@ -30,12 +37,89 @@ def fly(i, S):
     return pt.camera_look_at((4 * math.sin(phi), 0.01 * i, -2 + 4 * math.cos(phi)), (0.0, 0.0, -2.0), (0.0, 1.0, 0.0), S, S, 35.0)
 
 
+def moving(args):
+    import time
+    dev = torch.device("cuda", 0)
+    S, N = args.size, args.frames
+    a, b = pt.Context(0), pt.Context(0)
+    stream = torch.cuda.current_stream(dev)
+    a.set_stream(stream.cuda_stream)
+    b.set_stream(stream.cuda_stream)
+    lin = torch.empty((S, S, 3), dtype=torch.float32, device=dev)
+    feat = torch.empty((S, S, 8), dtype=torch.float32, device=dev)
+    ids = torch.empty((S, S), dtype=torch.int32, device=dev)
+    out = torch.empty((S, S, 3), dtype=torch.float32, device=dev)
+    rgba = torch.empty((S, S, 4), dtype=torch.uint8, device=dev)
+    base = pt.builtin_scene(2)
+    ball = min((k for k, o in enumerate(base) if o.shape_tag == 0 and o.mat_tag != 1), key=lambda k: base[k].shape[3])
+    cam = pt.camera_new(width=S, height=S)
+    dn0, tp = pt.default_denoise(iterations=0), pt.default_temporal()
+
+    def ev():
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    def frame(i, move):
+        objs = (pt._lib.PtObject * len(base))(*base)
+        if move:
+            objs[ball].shape[0] += 0.02 * (i - N // 2)
+        a.scene_update(objs)
+        p = pt.default_params(spp=1, spp_offset=i)
+        check(lib().pt_render_device(a._h, C.byref(cam), C.byref(p), C.c_void_p(lin.data_ptr()), C.c_void_p(rgba.data_ptr())))
+        check(lib().pt_render_features_device(a._h, C.byref(cam), C.byref(p), 1, C.c_void_p(feat.data_ptr())))
+        check(lib().pt_render_feature_ids_device(a._h, C.byref(cam), C.byref(p), C.c_void_p(ids.data_ptr())))
+        e0 = ev()
+        check(lib().pt_denoise_temporal_motion_device(a._h, C.byref(cam), C.c_void_p(lin.data_ptr()), C.c_void_p(feat.data_ptr()),
+                                                      C.c_void_p(ids.data_ptr()), C.byref(dn0), C.byref(tp), C.c_void_p(out.data_ptr()),
+                                                      C.c_void_p(rgba.data_ptr())))
+        e1 = ev()
+        check(lib().pt_denoise_temporal_device(b._h, C.byref(cam), C.c_void_p(lin.data_ptr()), C.c_void_p(feat.data_ptr()), C.byref(dn0),
+                                               C.byref(tp), C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
+        e2 = ev()
+        e2.synchronize()
+        return e0.elapsed_time(e1), e1.elapsed_time(e2)
+
+    res = {"size": S, "frames": N}
+    a.upload(base)
+    for name, move in (("moving", True), ("standing", False)):
+        a.temporal_reset()
+        b.temporal_reset()
+        t = [frame(i, move) for i in range(N)][1:]
+        res[name + "_motion_kernel_ms"] = round(statistics.median(x[0] for x in t), 4)
+        res[name + "_temporal_kernel_ms"] = round(statistics.median(x[1] for x in t), 4)
+    small = pt.camera_new(width=64, height=64)
+    for name, objs, accel in (("c2", base, 0), ("spheres_10000", pt.builtin_scene(4, 10000), 1)):
+        p = pt.default_params(spp=1, accel=accel)
+        a.upload(objs)
+        a.render(small, p)
+        for entry in ("upload", "update"):
+            call, total = [], []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                (a.upload if entry == "upload" else a.scene_update)(objs)
+                t1 = time.perf_counter()
+                a.render(small, p)
+                a.sync()
+                t2 = time.perf_counter()
+                call.append((t1 - t0) * 1e3)
+                total.append((t2 - t0) * 1e3)
+            res[f"{name}_{entry}_ms"] = round(statistics.median(call), 3)
+            res[f"{name}_{entry}_and_first_render_ms"] = round(statistics.median(total), 3)
+    a.close()
+    b.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--images", default=None)
+    ap.add_argument("--moving", action="store_true", help="the motion entry against the existing one, and pt_scene_update against pt_scene_upload")
     args = ap.parse_args()
+    if args.moving:
+        return moving(args)
     dev = torch.device("cuda", 0)
     S, N = args.size, args.frames
     ctx = pt.Context(0)
