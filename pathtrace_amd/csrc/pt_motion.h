@@ -1,5 +1,5 @@
 // pt_motion.h -- the per-object motion maps of pt_denoise_temporal_motion_device, written once for the library
-// (pt_api.cpp, pt_debug_motion_maps) and for host compilers of tests.  Plain f64 host arithmetic, no device code; build
+// (pt_denoise.cpp; pt_debug_motion_maps, pt_host.cpp) and for host compilers of tests.  Plain f64 host arithmetic, no device code; build
 // with -ffp-contract=off like the rest of the library.
 //
 // For object k the affine map x -> A x + b carries a point of the object's CURRENT pose to the same material point of its

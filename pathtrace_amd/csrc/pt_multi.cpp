@@ -42,14 +42,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pathtrace_amd.h"
+#include "pt_context.h"
 #include "pt_feeder.h"
-#include "pt_kernels.h"
-
-// defined in pt_api.cpp
-int pt_internal_fail(int code, const char* fmt, ...);
-void pt_internal_register_atexit(void);
-hipStream_t pt_internal_stream(PtContext* c);
 
 namespace {
 
@@ -91,13 +85,6 @@ int load_rccl() {
     return PT_OK;
 }
 
-#define HIP_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return pt_internal_fail(e_ == hipErrorOutOfMemory ? PT_ERR_OOM : PT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
-                                    hipGetErrorString(e_), __FILE__, __LINE__);                               \
-    } while (0)
 #define NCCL_TRY(expr)                                                                                        \
     do {                                                                                                      \
         ncclResult_t r_ = (expr);                                                                             \

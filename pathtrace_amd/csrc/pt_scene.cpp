@@ -1,0 +1,146 @@
+// pt_scene.cpp -- the device half of a scene upload: the records of ptscene::build (pt_scene_records.h) into the context's
+// buffers, k_scene_setup over them, the LDS blob; and the BVH of the uploaded scene, built at first use.
+#include <cstring>
+
+#include "pt_bvh.h"
+#include "pt_context.h"
+#include "pt_scene_records.h"
+
+// The scene as a launch in the given arithmetic mode sees it (the records carry constants evaluated in that mode)
+ptk::SceneView view_for(const PtContext* c, uint32_t exact_math) {
+    ptk::SceneView v = c->view;
+    if (exact_math) {
+        v.shape = c->shape_x.p; v.mat = c->mat_x.p;
+        if (v.blob) v.blob = c->blob_x.p;
+    }
+    return v;
+}
+
+// Build and upload the BVH of the uploaded scene (once per scene).
+int ensure_bvh(PtContext* c) {
+    if (c->has_bvh) return PT_OK;
+    if (c->bvh_refused) return fail(PT_ERR_UNSUPPORTED, "accel: the scene has object(s) with a NaN/inf coordinate; use the linear scan");
+    if (c->bvh_failed) return fail(PT_ERR_UNSUPPORTED, "accel: the BVH of this scene is deeper than the traversal stack; use the linear scan");
+    if (c->view.n_objs >= (1u << 28)) return fail(PT_ERR_UNSUPPORTED, "accel: %u objects exceed the 2^28 leaf slots", c->view.n_objs);
+    ptbvh::Built b = ptbvh::build(c->h_shape.data(), c->h_shape_tag.data(), c->view.n_objs);
+    static_assert(ptbvh::kStackDepth == ptk::kBvhStack, "traversal stack depth");
+    static_assert(ptbvh::kMaxLeaf == ptk::kBvhMaxLeaf, "leaf size the traversal unrolls for");
+    if (b.non_finite) {
+        c->bvh_refused = true;
+        return fail(PT_ERR_UNSUPPORTED, "accel: %u object(s) with a NaN/inf coordinate; the linear scan's answer for them "
+                                        "depends on the scan order, use the linear scan", b.non_finite);
+    }
+    if (b.depth + 2u > ptbvh::kStackDepth || b.stack_need > ptbvh::kStackDepth) {
+        c->bvh_failed = true;        // a property of the scene: do not rebuild on every render
+        return fail(PT_ERR_UNSUPPORTED, "accel: BVH (depth %u, stack need %u) exceeds the traversal stack", b.depth, b.stack_need);
+    }
+    int rc;
+    if ((rc = c->bvh_nodes.ensure(b.qnodes.size() + 2)) || (rc = c->bvh_rec.ensure(b.leaf_rec.size() + 3)) ||
+        (rc = c->bvh_ids.ensure(b.leaf_ids.size() + 4)) || (rc = c->bvh_lead.ensure(b.leaf_lead.size() + 4)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!b.qnodes.empty()) HIP_TRY(hipMemcpy(c->bvh_nodes.p, b.qnodes.data(), b.qnodes.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    if (!b.leaf_rec.empty()) HIP_TRY(hipMemcpy(c->bvh_rec.p, b.leaf_rec.data(), b.leaf_rec.size() * sizeof(float4), hipMemcpyHostToDevice));
+    if (!b.leaf_ids.empty()) HIP_TRY(hipMemcpy(c->bvh_ids.p, b.leaf_ids.data(), b.leaf_ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!b.leaf_lead.empty()) HIP_TRY(hipMemcpy(c->bvh_lead.p, b.leaf_lead.data(), b.leaf_lead.size() * sizeof(float4), hipMemcpyHostToDevice));
+    c->view.bvh.nodes = c->bvh_nodes.p; c->view.bvh.rec = c->bvh_rec.p; c->view.bvh.ids = c->bvh_ids.p; c->view.bvh.lead = c->bvh_lead.p;
+    c->view.bvh.root = b.root;
+    c->view.bvh.scene_abs = b.scene_abs;
+    for (int k = 0; k < 3; ++k) { c->view.bvh.grid_min[k] = b.grid_min[k]; c->view.bvh.grid_cell[k] = b.grid_cell[k]; }
+    c->bvh_depth = b.depth;
+    c->has_bvh = true;
+    return PT_OK;
+}
+
+namespace {
+
+// The body of pt_scene_upload and of pt_scene_update (keep_history: same object count and shape tags as the uploaded scene,
+// and the temporal history stays).  The records are built on the host first (ptscene::build); the context is touched only
+// once that has succeeded.
+int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, bool keep_history) {
+    if (!c || (!objs && n)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if (keep_history) {
+        if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
+        if (n != c->view.n_objs) return fail(PT_ERR_INVALID_ARG, "%s: %u objects, the uploaded scene has %u", who, n, c->view.n_objs);
+        for (uint32_t i = 0; i < n; ++i)
+            if (objs[i].shape_tag != c->h_shape_tag[i])
+                return fail(PT_ERR_INVALID_ARG, "%s: object %u: shape_tag %u, the uploaded scene has %u", who, i, objs[i].shape_tag, c->h_shape_tag[i]);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    ptscene::Records rec;
+    int rc;
+    if ((rc = ptscene::build(objs, n, &rec))) return rc;
+    const std::vector<float4>&scan = rec.scan, &shape = rec.shape, &mat = rec.mat, &blob = rec.blob;
+    const std::vector<ptk::Run>& runs = rec.runs;
+    const std::vector<uint32_t>& lights = rec.lights;
+    if ((rc = c->scan.ensure(scan.size() + 1))) return rc;
+    if ((rc = c->shape.ensure(shape.size()))) return rc;
+    if ((rc = c->mat.ensure(mat.size()))) return rc;
+    if ((rc = c->shape_x.ensure(shape.size()))) return rc;
+    if ((rc = c->mat_x.ensure(mat.size()))) return rc;
+    if ((rc = c->runs.ensure(runs.size() + 1))) return rc;
+    if ((rc = c->lights.ensure(lights.size() + 1))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the previous scene may still be in use
+    ptsched::on_scene(c->sched);                 // statistics of renders of the previous scene do not carry over
+    c->expected_samples = 0;
+    // (the statistics words are zero whenever no render is pending; on the context's stream, which is idle here: a plain hipMemset
+    // runs on the legacy default stream, which a non-blocking stream does not wait for)
+    if (c->ovf_count.p && hipMemsetAsync(c->ovf_count.p, 0, kStatsWords * sizeof(uint32_t), c->stream) == hipSuccess &&
+        hipStreamSynchronize(c->stream) == hipSuccess)
+        c->sched.stats_clean = 1;
+    c->capture_gcd = 0;                          // (graphs captured over the previous scene must not be replayed any more: its buffers are gone)
+    std::memset(c->regen_occ, 0, sizeof c->regen_occ);
+    if (!scan.empty()) HIP_TRY(hipMemcpy(c->scan.p, scan.data(), scan.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->shape.p, shape.data(), shape.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->mat.p, mat.data(), mat.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->shape_x.p, shape.data(), shape.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->mat_x.p, mat.data(), mat.size() * sizeof(float4), hipMemcpyHostToDevice));
+    // a triangle's unit normal and 1 / area, once per object and arithmetic mode, by the device's own expressions
+    ptk::launch_scene_setup_fast(c->shape.p, c->mat.p, n, c->stream);
+    ptk::launch_scene_setup_exact(c->shape_x.p, c->mat_x.p, n, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!runs.empty()) HIP_TRY(hipMemcpy(c->runs.p, runs.data(), runs.size() * sizeof(ptk::Run), hipMemcpyHostToDevice));
+    if (!lights.empty()) HIP_TRY(hipMemcpy(c->lights.p, lights.data(), lights.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->view.scan = c->scan.p; c->view.shape = c->shape.p; c->view.mat = c->mat.p;
+    c->view.runs = c->runs.p; c->view.lights = c->lights.p;
+    c->view.blob = nullptr; c->view.blob_f4 = 0;
+    if (rec.has_blob) {
+        if ((rc = c->blob.ensure(blob.size() + 1)) || (rc = c->blob_x.ensure(blob.size() + 1))) return rc;
+        for (float4* dst : {c->blob.p, c->blob_x.p}) {
+            if (!blob.empty()) HIP_TRY(hipMemcpy(dst, blob.data(), blob.size() * sizeof(float4), hipMemcpyHostToDevice));
+            // shape and material records as k_scene_setup left them in this mode's arrays
+            const bool x = dst == c->blob_x.p;
+            if (n) HIP_TRY(hipMemcpy(dst + scan.size(), x ? c->shape_x.p : c->shape.p, 3 * (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice));
+            if (n) HIP_TRY(hipMemcpy(dst + scan.size() + 3 * (size_t)n, x ? c->mat_x.p : c->mat.p, 2 * (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice));
+        }
+        c->view.blob = c->blob.p;
+        c->view.blob_f4 = (uint32_t)blob.size();
+    }
+    c->view.scan_f4 = (uint32_t)scan.size();
+    c->view.n_runs = (uint32_t)runs.size(); c->view.n_objs = n; c->view.n_lights = (uint32_t)lights.size();
+    c->view.diffuse_only = rec.diffuse_only; c->view.no_mirror = rec.no_mirror; c->view.no_oren_nayar = rec.no_oren_nayar;
+    c->split_ok = rec.split_ok;
+    std::memcpy(c->scan_counts, rec.scan_counts, sizeof c->scan_counts);
+    c->view.bvh = ptk::BvhView{};
+    c->has_bvh = false;
+    c->bvh_refused = false;
+    c->bvh_failed = false;
+    c->auto_bvh = rec.auto_bvh;
+    c->h_shape.assign(shape.begin(), shape.begin() + 3 * (size_t)n);
+    c->h_shape_tag = std::move(rec.shape_tag);
+    c->has_scene = true;
+    c->pose = std::move(rec.pose);
+    ++c->pose_gen;
+    if (!keep_history) c->tm_valid = false;   // a new scene starts the temporal history afresh; pt_scene_update keeps it
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_upload", c, objs, n, false); }
+int pt_scene_update(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_update", c, objs, n, true); }
+
+}  // extern "C"

@@ -7,6 +7,8 @@
 #include "../../include/pathtrace_amd.h"
 #include "pt_sched.h"
 
+// pt_host.cpp; declared here and not through pt_context.h: this file also builds on its own with a plain host compiler and no
+// HIP headers (tests/test_sched_mutants_cpu.py)
 int pt_internal_fail(int code, const char* fmt, ...);
 
 struct PtSched {

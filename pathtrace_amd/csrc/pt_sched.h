@@ -51,7 +51,7 @@ static_assert(kSets >= 3 && kSets <= 4, "PT_SETS: 3 or 4");
 constexpr uint32_t kLaneGrid24 = PT_LANE_GRID24, kLaneGrid24Split = PT_LANE_GRID24_SPLIT;
 constexpr uint32_t kMaxProfiledLaunches = 1u << 14;      // bound of the HIP-event pool (profile = 1) between two collections of the statistics
 
-// ---- streams and events of a context (indices; pt_api.cpp maps them to its hipStream_t / hipEvent_t)
+// ---- streams and events of a context (indices; pt_api.cpp maps them to the streams and events PtContext owns, pt_context.h)
 enum : uint32_t { kStreamCaller = 0, kStreamSide = 1, kStreamLane0 = 2 };            // kStreamLane0 + lane
 enum : uint32_t {
     kEvBegin = 0, kEvEnd = 1,       // first / last operation of the renders since the statistics were last collected (total_ms)
