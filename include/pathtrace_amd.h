@@ -516,6 +516,28 @@ int pt_render_denoised_temporal(PtContext* ctx, const PtCamera* cam, const PtRen
  * POSE, the scene as it was at the most recent temporal call (either entry) that stored a history frame.  Any number of
  * updates may lie between two temporal frames.                                                                          */
 int pt_scene_update(PtContext* ctx, const PtObject* objs, uint32_t n_objs);
+/* Device-side BVH refit (additive to ABI 6).
+ *
+ * pt_scene_refit is pt_scene_update in every respect but one: same argument checks, same records, same restart of the
+ * statistics, the temporal history kept -- but a BVH the context holds is NOT dropped.  It is refitted on the device, on the
+ * context's stream behind the new records: the tree keeps its topology (which objects share a leaf, which nodes are children
+ * of which), and the leaf records, every child box and the quantisation grid are recomputed from the new shapes.  No tree
+ * array crosses PCIe and the binned-SAH builder does not run.  Without a tree (no accel = 1 render yet, or the BVH was
+ * refused or failed) the call IS pt_scene_update: the tree is built at first use.  A pose with a NaN/inf coordinate drops the
+ * tree and refuses the BVH as building it would: accel = 1 then fails with PT_ERR_UNSUPPORTED, PT_ACCEL_AUTO takes the scan.
+ * pt_scene_upload, pt_scene_update and pt_scene_refit may be mixed freely on one context.
+ *
+ * THE FILM NEVER DEPENDS ON THE REFIT.  The tree only decides which primitives a ray is tested against; every box of a
+ * refitted tree encloses what is beneath it, so a render over it is bit-identical to the linear scan's, however far the
+ * objects moved.  Only the traversal TIME depends on it: objects that were neighbours when the tree was built and have
+ * drifted apart leave large, overlapping boxes.  pt_scene_bvh_cost measures that:
+ *   cost = the sum, over every used child slot of every node, of the half-area of the child box the device traverses
+ * (exact integer sums on the 16-bit grid, scaled by the grid cell in f64).  cost_now is the tree as it is (the call waits
+ * for the context's stream), cost_at_build the tree as the builder left it, refits the refits since then.  A caller who sees
+ * cost_now / cost_at_build grow calls pt_scene_update ONCE: the next render rebuilds the tree for the current pose.
+ * Any output may be NULL.  PT_ERR_INVALID_ARG when the context holds no tree.                                            */
+int pt_scene_refit(PtContext* ctx, const PtObject* objs, uint32_t n_objs);
+int pt_scene_bvh_cost(PtContext* ctx, double* cost_now, double* cost_at_build, uint32_t* refits);
 /* The motion map of object k, x -> A x + b in f64, carries a point of the current pose to the same material point of the
  * history pose:  sphere (c, r) now, (c', r') then: A = (r'/r) I, b = c' - (r'/r) c;  triangle (v0, v1, v2) now, primed then:
  * e1 = v1 - v0, e2 = v2 - v0, n = (e1 x e2)/|e1 x e2|, E = [e1 e2 n] as columns, A = E' E^-1, b = v0' - A v0.
@@ -614,6 +636,24 @@ int pt_debug_joint_scan(PtContext* ctx, const double* rays10, uint32_t n, double
  * pt_last_error().  Any of the three outputs may be NULL.                                                    */
 int pt_debug_bvh_check(const PtObject* objs, uint32_t n_objs, uint32_t* depth, uint32_t* n_nodes,
                        uint32_t* n_leaf_slots);
+
+/* Debug entry, host only (no GPU needed): build the tree of prev_objs, refit it to cur_objs on the host (the specification of
+ * the device-side refit) and run the invariants of pt_debug_bvh_check on the result against cur_objs -- every object in one
+ * slot with its CURRENT scan record, every child box encloses what is beneath it --, and that child codes and leaf ids are
+ * the build's.  Both poses have the same n_objs and shape tags (PT_ERR_INVALID_ARG otherwise); PT_ERR_UNSUPPORTED for a
+ * NaN/inf coordinate or a violated invariant.  refit = 0 skips the refit: the tree as built from prev_objs, verified against
+ * prev_objs (what a refit to the pose of the build must reproduce bit for bit).  Optional outputs, the tree: out_qnodes (16 words per node, up to
+ * cap_nodes nodes), out_leaf_rec (12 floats per leaf slot), out_leaf_lead (4 per slot), out_leaf_ids (1 per slot; up to
+ * cap_slots slots), the counts, out_grid = grid_min[3], grid_cell[3], scene_abs, the root's child code, and the three cost
+ * sums (dx dy, dy dz, dz dx in grid units) now and at build.                                                          */
+int pt_debug_bvh_refit_check(const PtObject* prev_objs, const PtObject* cur_objs, uint32_t n_objs, uint32_t refit,
+                             uint32_t* out_qnodes, uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead, uint32_t* out_leaf_ids,
+                             uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots, float* out_grid, uint32_t* root,
+                             uint64_t* cost_now, uint64_t* cost_at_build);
+/* The context's device tree copied back into the same outputs (blocking).  PT_ERR_INVALID_ARG when it holds no tree. */
+int pt_debug_bvh_read(PtContext* ctx, uint32_t* out_qnodes, uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead,
+                      uint32_t* out_leaf_ids, uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots, float* out_grid,
+                      uint32_t* root, uint64_t* cost_now);
 
 const char* pt_last_error(void);
 uint32_t pt_abi_version(void);

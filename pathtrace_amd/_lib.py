@@ -192,6 +192,13 @@ SYMBOLS = {
     "pt_render_denoised_temporal": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_scene_update": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
+    "pt_scene_refit": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
+    "pt_scene_bvh_cost": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_uint32)]),
+    "pt_debug_bvh_refit_check": (C.c_int, [_P(PtObject), _P(PtObject), C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_float), _P(C.c_float),
+                                           _P(C.c_uint32), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_float), _P(C.c_uint32),
+                                           _P(C.c_uint64), _P(C.c_uint64)]),
+    "pt_debug_bvh_read": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_uint32), C.c_uint32,
+                                    _P(C.c_uint32), _P(C.c_uint32), _P(C.c_float), _P(C.c_uint32), _P(C.c_uint64)]),
     "pt_debug_motion_maps": (C.c_int, [_P(PtObject), _P(PtObject), C.c_uint32, _P(C.c_double), _P(C.c_uint32)]),
     "pt_render_feature_ids_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_void_p]),
     "pt_denoise_temporal_motion_device": (C.c_int, [C.c_void_p, _P(PtCamera), C.c_void_p, C.c_void_p, C.c_void_p, _P(PtDenoise),

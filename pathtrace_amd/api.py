@@ -123,6 +123,26 @@ class Context:
         check(lib().pt_scene_update(self._h, objs, len(objs)))
         self._objs = objs
 
+    def scene_refit(self, objs):
+        """pt_scene_refit: scene_update(objs), but a BVH the context holds is refitted on the device instead of dropped."""
+        check(lib().pt_scene_refit(self._h, objs, len(objs)))
+        self._objs = objs
+
+    def bvh_cost(self):
+        """pt_scene_bvh_cost -> (cost_now, cost_at_build, refits since the build); PtError without a tree."""
+        now, built, refits = C.c_double(0), C.c_double(0), C.c_uint32(0)
+        check(lib().pt_scene_bvh_cost(self._h, C.byref(now), C.byref(built), C.byref(refits)))
+        return now.value, built.value, refits.value
+
+    def debug_bvh_read(self):
+        """pt_debug_bvh_read: the context's device tree -> dict as bvh_refit_check's (without cost_at_build)."""
+        nn, ns = C.c_uint32(0), C.c_uint32(0)
+        check(lib().pt_debug_bvh_read(self._h, None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None))
+        t = _BvhArrays(nn.value, ns.value)
+        check(lib().pt_debug_bvh_read(self._h, _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids), ns.value,
+                                      C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now)))
+        return t.as_dict()
+
     def set_stream(self, hip_stream_ptr):
         """Render on a caller-owned stream.  0 is the handle of HIP's legacy default stream (torch's default stream):
         it is passed on as PT_STREAM_LEGACY_DEFAULT, so the render is ordered against the caller's other work there;
@@ -225,6 +245,29 @@ def _pu(a):
 
 def _pf(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _pu64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+class _BvhArrays:
+    """Output arrays of pt_debug_bvh_refit_check / pt_debug_bvh_read for a tree of the given size."""
+
+    def __init__(self, n_nodes, n_slots):
+        self.qnodes = np.zeros((n_nodes, 16), dtype=np.uint32)
+        self.leaf_rec = np.zeros((n_slots, 12), dtype=np.float32)
+        self.leaf_lead = np.zeros((n_slots, 4), dtype=np.float32)
+        self.leaf_ids = np.zeros(n_slots, dtype=np.uint32)
+        self.grid = np.zeros(7, dtype=np.float32)
+        self.root = C.c_uint32(0)
+        self.cost_now = np.zeros(3, dtype=np.uint64)
+        self.cost_at_build = np.zeros(3, dtype=np.uint64)
+
+    def as_dict(self):
+        return dict(qnodes=self.qnodes, leaf_rec=self.leaf_rec, leaf_lead=self.leaf_lead, leaf_ids=self.leaf_ids, grid_min=self.grid[:3].copy(),
+                    grid_cell=self.grid[3:6].copy(), scene_abs=self.grid[6:7].copy(), root=self.root.value, cost_now=self.cost_now,
+                    cost_at_build=self.cost_at_build)
 
 
 class _ContextFunctions:
@@ -585,6 +628,28 @@ def bvh_check(objs):
     d, nn, nl = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
     check(lib().pt_debug_bvh_check(objs, len(objs), C.byref(d), C.byref(nn), C.byref(nl)))
     return d.value, nn.value, nl.value
+
+
+def bvh_refit_check(prev_objs, cur_objs, refit=True):
+    """pt_debug_bvh_refit_check (host only): the tree of prev_objs refitted to cur_objs by the host reference of the
+    device-side refit, verified (refit=False: the tree as built from prev_objs).  -> dict: qnodes u32[nodes,16], leaf_rec f32[slots,12], leaf_lead f32[slots,4], leaf_ids
+    u32[slots], grid_min f32[3], grid_cell f32[3], scene_abs f32[1], root, cost_now u64[3], cost_at_build u64[3]"""
+    n = len(cur_objs)
+    assert len(prev_objs) == n
+    nn, ns = C.c_uint32(0), C.c_uint32(0)
+    check(lib().pt_debug_bvh_refit_check(prev_objs, cur_objs, n, int(refit), None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None, None))
+    t = _BvhArrays(nn.value, ns.value)
+    check(lib().pt_debug_bvh_refit_check(prev_objs, cur_objs, n, int(refit), _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids),
+                                         ns.value, C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now),
+                                         _pu64(t.cost_at_build)))
+    return t.as_dict()
+
+
+def bvh_cost_value(sums, grid_cell):
+    """The cost pt_scene_bvh_cost reports, from the three integer sums and the grid cell (f64, the library's expression)."""
+    c = [float(x) for x in grid_cell]
+    s = [float(int(x)) for x in sums]
+    return s[0] * (c[0] * c[1]) + s[1] * (c[1] * c[2]) + s[2] * (c[2] * c[0])
 
 
 def render_host(cam, objs, params):

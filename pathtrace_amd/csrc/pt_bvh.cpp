@@ -25,6 +25,14 @@ struct Box {
 float down(double v) { float f = (float)v; return (double)f > v ? std::nextafterf(f, -std::numeric_limits<float>::infinity()) : f; }
 float up(double v) { float f = (float)v; return (double)f < v ? std::nextafterf(f, std::numeric_limits<float>::infinity()) : f; }
 
+// Leaf records of object o as the scan reads them: sphere (c, r^2), -, - ; triangle: triangle_scan_record
+void leaf_records(const float4* shape, bool tri, uint32_t o, float4 out[3]) {
+    float4 r0 = shape[3 * (size_t)o], r1 = shape[3 * (size_t)o + 1], r2 = shape[3 * (size_t)o + 2];
+    if (!tri) { r0.w = r0.w * r0.w; r1 = make_float4(0, 0, 0, 0); r2 = r1; }   // (c, r^2): the scan record of a sphere
+    else { float4 t[3]; triangle_scan_record(r0, r1, r2, t); r0 = t[0]; r1 = t[1]; r2 = t[2]; }
+    out[0] = r0; out[1] = r1; out[2] = r2;
+}
+
 struct Prim {
     Box box;
     float cen[3];
@@ -74,11 +82,10 @@ struct Builder {
             const uint32_t o = prims[first + i].obj;
             const bool tri = tag[o] != 0;
             out.leaf_ids.push_back(o | (tri ? kTriangleBit : 0u));
-            float4 r0 = shape[3 * (size_t)o], r1 = shape[3 * (size_t)o + 1], r2 = shape[3 * (size_t)o + 2];
-            if (!tri) { r0.w = r0.w * r0.w; r1 = make_float4(0, 0, 0, 0); r2 = r1; }   // (c, r^2): the scan record of a sphere
-            else { float4 t[3]; triangle_scan_record(r0, r1, r2, t); r0 = t[0]; r1 = t[1]; r2 = t[2]; }
-            out.leaf_rec.push_back(r0); out.leaf_rec.push_back(r1); out.leaf_rec.push_back(r2);
-            out.leaf_lead.push_back(r0);
+            float4 r[3];
+            leaf_records(shape, tri, o, r);
+            out.leaf_rec.push_back(r[0]); out.leaf_rec.push_back(r[1]); out.leaf_rec.push_back(r[2]);
+            out.leaf_lead.push_back(r[0]);
             out.leaf_prims++;
         }
         out.depth = std::max(out.depth, depth);
@@ -209,20 +216,26 @@ struct Builder {
     }
 };
 
-// Child boxes -> 16-bit grid coordinates over the bounds of all child boxes (see pt_bvh.h).
+// The grid over the bounds lo .. hi of all boxes (see pt_bvh.h)
+void grid_over(const double lo[3], const double hi[3], float grid_min[3], float grid_cell[3]) {
+    for (int a = 0; a < 3; ++a) {
+        grid_min[a] = down(lo[a]);
+        const double ext = std::max(hi[a] - (double)grid_min[a], 1e-30);
+        grid_cell[a] = up(ext / 65535.0 * (1.0 + 1e-6));          // 65535 cells reach past the upper bound
+    }
+}
+
+// Child boxes -> 16-bit grid coordinates over the bounds of all child boxes (see pt_bvh.h), and the cost sums of the result.
 void quantise(Built& t) {
     const size_t n_nodes = t.wide.size();
     t.qnodes.assign(4 * n_nodes, make_uint4(0, 0, 0, 0));
+    t.cost[0] = t.cost[1] = t.cost[2] = 0;
     if (n_nodes == 0) return;
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     for (const WideNode& w : t.wide)
         for (uint32_t c = 0; c < w.n; ++c)
             for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], (double)w.lo[c][a]); hi[a] = std::max(hi[a], (double)w.hi[c][a]); }
-    for (int a = 0; a < 3; ++a) {
-        t.grid_min[a] = down(lo[a]);
-        const double ext = std::max(hi[a] - (double)t.grid_min[a], 1e-30);
-        t.grid_cell[a] = up(ext / 65535.0 * (1.0 + 1e-6));          // 65535 cells reach past the upper bound
-    }
+    grid_over(lo, hi, t.grid_min, t.grid_cell);
     auto decode = [&](int a, uint32_t q) { return std::fmaf((float)q, t.grid_cell[a], t.grid_min[a]); };
     auto q_lo = [&](int a, float v) {
         long q = (long)std::floor(((double)v - t.grid_min[a]) / t.grid_cell[a]);
@@ -244,6 +257,8 @@ void quantise(Built& t) {
             const uint32_t lx = q_lo(0, w.lo[c][0]), ly = q_lo(1, w.lo[c][1]), lz = q_lo(2, w.lo[c][2]);
             const uint32_t hx = q_hi(0, w.hi[c][0]), hy = q_hi(1, w.hi[c][1]), hz = q_hi(2, w.hi[c][2]);
             v[c][0] = lx | (ly << 16); v[c][1] = lz | (hx << 16); v[c][2] = hy | (hz << 16);
+            const uint64_t dx = hx - lx, dy = hy - ly, dz = hz - lz;          // (uint32 differences: hi >= lo for a box that is not inverted)
+            t.cost[0] += dx * dy; t.cost[1] += dy * dz; t.cost[2] += dz * dx;
         }
         t.qnodes[4 * k] = make_uint4(v[0][0], v[0][1], v[0][2], v[1][0]);
         t.qnodes[4 * k + 1] = make_uint4(v[1][1], v[1][2], v[2][0], v[2][1]);
@@ -252,44 +267,52 @@ void quantise(Built& t) {
     }
 }
 
+// Heights of the wide nodes and their order by height (pt_bvh.h).  collapse() numbers a node before the nodes beneath it, so
+// one pass from the last node to the first sees every child node before its parent.
+void order_by_height(Built& t) {
+    const size_t n_nodes = t.wide.size();
+    t.node_height.assign(n_nodes, 0u);
+    uint32_t top = 0;
+    for (size_t k = n_nodes; k-- > 0;) {
+        uint32_t h = 0;
+        for (uint32_t c = 0; c < t.wide[k].n; ++c) {
+            const uint32_t code = t.wide[k].code[c];
+            if (!(code & kLeafBit)) h = std::max(h, 1u + t.node_height[code]);
+        }
+        t.node_height[k] = h;
+        top = std::max(top, h);
+    }
+    t.height_first.assign(n_nodes ? top + 2u : 1u, 0u);
+    for (size_t k = 0; k < n_nodes; ++k) t.height_first[t.node_height[k] + 1u]++;
+    for (size_t h = 1; h < t.height_first.size(); ++h) t.height_first[h] += t.height_first[h - 1];
+    t.height_order.assign(n_nodes, 0u);
+    std::vector<uint32_t> at(t.height_first.begin(), t.height_first.end());
+    for (size_t k = 0; k < n_nodes; ++k) t.height_order[at[t.node_height[k]]++] = (uint32_t)k;
+}
+
+// largest |coordinate| per axis over the finite boxes -> scene_abs
+struct AbsMax {
+    double a[3] = {0, 0, 0};
+    void add(const float lo[3], const float hi[3]) {
+        for (int k = 0; k < 3; ++k) a[k] = std::max(a[k], std::max(std::fabs((double)lo[k]), std::fabs((double)hi[k])));
+    }
+    float scene_abs() const { return up(a[0] + a[1] + a[2]); }
+};
+
 }  // namespace
 
 Built build(const float4* shape, const uint32_t* shape_tag, uint32_t n) {
     Builder b;
     b.shape = shape; b.tag = shape_tag;
     b.prims.resize(n);
-    double amax[3] = {0, 0, 0};
+    AbsMax amax;
     for (uint32_t i = 0; i < n; ++i) {
         Prim& p = b.prims[i];
         p.obj = i;
-        const float4 r0 = shape[3 * (size_t)i], r1 = shape[3 * (size_t)i + 1], r2 = shape[3 * (size_t)i + 2];
-        if (shape_tag[i] == 0) {
-            // the scan tests against r2 = fl(r*r); bound the sphere of radius sqrt(r2), rounded outward
-            const float r2f = r0.w * r0.w;
-            const double r = std::sqrt((double)r2f) * (1.0 + 1e-7);
-            const double c[3] = {r0.x, r0.y, r0.z};
-            for (int k = 0; k < 3; ++k) { p.box.lo[k] = down(c[k] - r); p.box.hi[k] = up(c[k] + r); }
-        } else {
-            const double v0[3] = {r0.x, r0.y, r0.z}, e1[3] = {r1.x, r1.y, r1.z}, e2[3] = {r2.x, r2.y, r2.z};
-            for (int k = 0; k < 3; ++k) {
-                const double a = v0[k], bq = v0[k] + e1[k], c = v0[k] + e2[k];
-                p.box.lo[k] = down(std::min(a, std::min(bq, c)));
-                p.box.hi[k] = up(std::max(a, std::max(bq, c)));
-            }
-        }
-        bool finite = true;
-        for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(p.box.lo[k]) && std::isfinite(p.box.hi[k]);
+        const bool finite = primitive_box(shape[3 * (size_t)i], shape[3 * (size_t)i + 1], shape[3 * (size_t)i + 2], shape_tag[i] != 0, p.box.lo, p.box.hi);
         if (!finite) b.out.non_finite++;
-        for (int k = 0; k < 3; ++k) {
-            // a non-finite box would poison every ancestor: make it cover everything (the caller refuses the scene anyway)
-            if (!finite) {
-                p.box.lo[k] = -std::numeric_limits<float>::max(); p.box.hi[k] = std::numeric_limits<float>::max();
-                p.cen[k] = 0.f;
-            } else {
-                p.cen[k] = (float)(0.5 * ((double)p.box.lo[k] + p.box.hi[k]));
-                amax[k] = std::max(amax[k], std::max(std::fabs((double)p.box.lo[k]), std::fabs((double)p.box.hi[k])));
-            }
-        }
+        else amax.add(p.box.lo, p.box.hi);
+        for (int k = 0; k < 3; ++k) p.cen[k] = finite ? (float)(0.5 * ((double)p.box.lo[k] + p.box.hi[k])) : 0.f;
     }
     b.bin.reserve(n);
     b.out.leaf_ids.reserve(n);
@@ -305,14 +328,93 @@ Built build(const float4* shape, const uint32_t* shape_tag, uint32_t n) {
         }
         b.out.root = r;
     }
-    b.out.scene_abs = up(amax[0] + amax[1] + amax[2]);
+    b.out.scene_abs = amax.scene_abs();
     while (b.out.leaf_ids.size() % 4u != 0u) {                   // the last leaf's 16-byte id load stays in bounds
         b.out.leaf_ids.push_back(kDone);
         b.out.leaf_lead.push_back(make_float4(0, 0, 0, 0));
         for (int k = 0; k < 3; ++k) b.out.leaf_rec.push_back(make_float4(0, 0, 0, 0));
     }
     quantise(b.out);
+    order_by_height(b.out);
     return std::move(b.out);
+}
+
+bool primitive_box(const float4& r0, const float4& r1, const float4& r2, bool triangle, float lo[3], float hi[3]) {
+    if (!triangle) {
+        // the scan tests against r2 = fl(r*r); bound the sphere of radius sqrt(r2), rounded outward
+        const float r2f = r0.w * r0.w;
+        const double r = std::sqrt((double)r2f) * (1.0 + 1e-7);
+        const double c[3] = {r0.x, r0.y, r0.z};
+        for (int k = 0; k < 3; ++k) { lo[k] = down(c[k] - r); hi[k] = up(c[k] + r); }
+    } else {
+        const double v0[3] = {r0.x, r0.y, r0.z}, e1[3] = {r1.x, r1.y, r1.z}, e2[3] = {r2.x, r2.y, r2.z};
+        for (int k = 0; k < 3; ++k) {
+            const double a = v0[k], bq = v0[k] + e1[k], c = v0[k] + e2[k];
+            lo[k] = down(std::min(a, std::min(bq, c)));
+            hi[k] = up(std::max(a, std::max(bq, c)));
+        }
+    }
+    bool finite = true;
+    for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(lo[k]) && std::isfinite(hi[k]);
+    // a non-finite box would poison every ancestor: make it cover everything (the caller refuses the scene anyway)
+    if (!finite)
+        for (int k = 0; k < 3; ++k) { lo[k] = -std::numeric_limits<float>::max(); hi[k] = std::numeric_limits<float>::max(); }
+    return finite;
+}
+
+Bounds scene_bounds(const float4* shape, const uint32_t* shape_tag, uint32_t n, bool has_nodes) {
+    Bounds out;
+    AbsMax amax;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (uint32_t i = 0; i < n; ++i) {
+        float bl[3], bh[3];
+        if (!primitive_box(shape[3 * (size_t)i], shape[3 * (size_t)i + 1], shape[3 * (size_t)i + 2], shape_tag[i] != 0, bl, bh)) out.non_finite++;
+        else amax.add(bl, bh);
+        // every primitive lies beneath some child box, and a box is the union of what is beneath it: the bounds of all child
+        // boxes (quantise) are the bounds of all primitive boxes
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], (double)bl[a]); hi[a] = std::max(hi[a], (double)bh[a]); }
+    }
+    out.scene_abs = amax.scene_abs();
+    if (has_nodes && n != 0) grid_over(lo, hi, out.grid_min, out.grid_cell);
+    return out;
+}
+
+void refit(Built& t, const float4* shape, const uint32_t* shape_tag, uint32_t n) {
+    const size_t n_slots = t.leaf_ids.size(), n_nodes = t.wide.size();
+    std::vector<Box> slot_box(n_slots), node_box(n_nodes);
+    AbsMax amax;
+    t.non_finite = 0;
+    for (size_t i = 0; i < n_slots; ++i) {
+        const uint32_t w = t.leaf_ids[i];
+        if (w == kDone) continue;                                // padding slot: zero records, as build() left them
+        const uint32_t o = w & ~kTriangleBit;
+        if (o >= n) continue;
+        const bool tri = shape_tag[o] != 0;
+        float4 r[3];
+        leaf_records(shape, tri, o, r);
+        t.leaf_rec[3 * i] = r[0]; t.leaf_rec[3 * i + 1] = r[1]; t.leaf_rec[3 * i + 2] = r[2];
+        t.leaf_lead[i] = r[0];
+        if (!primitive_box(shape[3 * (size_t)o], shape[3 * (size_t)o + 1], shape[3 * (size_t)o + 2], tri, slot_box[i].lo, slot_box[i].hi)) t.non_finite++;
+        else amax.add(slot_box[i].lo, slot_box[i].hi);
+    }
+    t.scene_abs = amax.scene_abs();
+    for (const uint32_t k : t.height_order) {                    // bottom-up: the child nodes of k come earlier in the order
+        WideNode& wn = t.wide[k];
+        node_box[k].reset();
+        for (uint32_t c = 0; c < wn.n; ++c) {
+            Box b; b.reset();
+            const uint32_t code = wn.code[c];
+            if (code & kLeafBit) {
+                const uint32_t first = code & 0x0FFFFFFFu, cnt = ((code >> 28) & 7u) + 1u;
+                for (uint32_t i = first; i < first + cnt; ++i) b.grow(slot_box[i]);
+            } else {
+                b = node_box[code];
+            }
+            for (int a = 0; a < 3; ++a) { wn.lo[c][a] = b.lo[a]; wn.hi[c][a] = b.hi[a]; }
+            node_box[k].grow(b);
+        }
+    }
+    quantise(t);
 }
 
 }  // namespace ptbvh

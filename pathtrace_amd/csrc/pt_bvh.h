@@ -62,7 +62,34 @@ struct Built {
     // scan order (a NaN t is "accepted" and then lets every later hit through, world.rs:281-287), which no
     // traversal order reproduces: callers refuse accel = 1 for such scenes.
     uint32_t non_finite = 0;
+    // For ptbvh::refit and the device-side refit (pt_scene_refit), which keep the topology.  Height of a wide node: 0 = all its
+    // children are leaves, otherwise 1 + the largest height of a child node.  A node's boxes depend only on nodes of lower
+    // height, so the nodes of one height can be refitted together once the lower heights are done.
+    std::vector<uint32_t> node_height;    // per wide node
+    std::vector<uint32_t> height_order;   // the node indices ordered by height, ties by index
+    std::vector<uint32_t> height_first;   // height h = positions [height_first[h], height_first[h + 1]) of height_order (last entry: the node count)
+    // Cost of the tree as the device traverses it: over every used child slot of every node the half-area of the quantised
+    // child box, as three exact integer sums in grid units, d = q_hi - q_lo per axis: sum dx dy, sum dy dz, sum dz dx.
+    // cost = s[0] cell.x cell.y + s[1] cell.y cell.z + s[2] cell.z cell.x.
+    uint64_t cost[3] = {0, 0, 0};
 };
+// the cost in scene units from the three sums and the grid they were counted in
+inline double cost_value(const uint64_t s[3], const float cell[3]) {
+    return (double)s[0] * ((double)cell[0] * cell[1]) + (double)s[1] * ((double)cell[1] * cell[2]) + (double)s[2] * ((double)cell[2] * cell[0]);
+}
+
+// The f32 box of one primitive from its gather records, rounded outward: a sphere as the ball of radius sqrt(fl(r * r)) (what
+// the scan tests against) widened by 1e-7, a triangle as the min / max of its corners v0, v0 + e1, v0 + e2.  Returns false, and
+// a box that covers everything, when a coordinate is NaN or inf (Built::non_finite counts those objects).
+bool primitive_box(const float4& r0, const float4& r1, const float4& r2, bool triangle, float lo[3], float hi[3]);
+// What the scene's boxes decide besides the tree: the quantisation grid (over the bounds of all boxes; left zero when the
+// tree has no node, has_nodes = false), scene_abs and the count of non-finite objects -- one pass over the objects.
+struct Bounds {
+    float grid_min[3] = {0.f, 0.f, 0.f}, grid_cell[3] = {0.f, 0.f, 0.f};
+    float scene_abs = 0.0f;
+    uint32_t non_finite = 0;
+};
+Bounds scene_bounds(const float4* shape, const uint32_t* shape_tag, uint32_t n, bool has_nodes);
 
 // Scan record of a triangle (what the primitive test reads; pt_kernels_scan.h triangle_test): the f32 specification of
 // TriangleShape::hit (shape.rs:161-192) works on the triangle's plane and two barycentric gradients instead of
@@ -74,7 +101,7 @@ struct Built {
 // Packing, 3 float4, in the order the test reads them -- one aligned 16-byte read per stage (round 5; rounds 3-4 packed v0 first
 // and the compiler read the normal as two 8-byte halves of two float4): (n.x, n.y, n.z, N1.x) (v0.x, v0.y, v0.z, N1.y)
 // (N1.z, N2.x, N2.y, N2.z).
-inline void triangle_scan_record(const float4& v0, const float4& e1f, const float4& e2f, float4 out[3]) {
+__host__ __device__ inline void triangle_scan_record(const float4& v0, const float4& e1f, const float4& e2f, float4 out[3]) {
     const double e1[3] = {e1f.x, e1f.y, e1f.z}, e2[3] = {e2f.x, e2f.y, e2f.z};
     const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
     const double nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
@@ -88,5 +115,14 @@ inline void triangle_scan_record(const float4& v0, const float4& e1f, const floa
 // shape: 3 float4 per object in the gather form of pt_device.h (sphere: (c, r), (1/r,..), -; triangle: v0, e1, e2);
 // scan_w: for spheres the r^2 the scan record carries.  Throws nothing; n may be 0.
 Built build(const float4* shape, const uint32_t* shape_tag, uint32_t n);
+
+// The tree of build() carried to a new pose of the same objects (same n, same shape tags): topology, child codes and
+// leaf_ids stay.  Recomputed: leaf_rec and leaf_lead from the new records as build() writes them; every wide node's child
+// boxes bottom-up (a leaf child: the union of its primitives' boxes; a node child: the union of that node's child boxes);
+// grid_min / grid_cell by build()'s rule over the new boxes; qnodes, cost, scene_abs and non_finite.  Refitting to the pose
+// the tree was built from returns build()'s arrays bit for bit.  The tree stays CORRECT however far the objects moved (every
+// box encloses what is beneath it); only its quality -- cost -- degrades.  This function is the specification of the
+// device-side refit (k_bvh_refit_leaves, k_bvh_refit_level).
+void refit(Built& t, const float4* shape, const uint32_t* shape_tag, uint32_t n);
 
 }  // namespace ptbvh

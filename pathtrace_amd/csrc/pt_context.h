@@ -101,6 +101,16 @@ struct PtContext {
     bool bvh_failed = false;          // the BVH builder refused this scene (depth): PT_ACCEL_AUTO stays with the scan
     bool auto_bvh = false;            // PT_ACCEL_AUTO would take the BVH for this scene (ptscene::kAutoBvhWeight)
     uint32_t bvh_depth = 0;
+    // pt_scene_refit: what the device-side refit needs beyond the tree -- the node indices by height (uploaded with the tree)
+    // and the first position of every height in that order (one launch per height), scratch for the f32 boxes (2 float4 per
+    // leaf slot, 2 per node), the three cost sums (pt_scene_bvh_cost) on the device and as the builder computed them
+    DevBuf<uint32_t> bvh_order;
+    std::vector<uint32_t> bvh_height_first;
+    DevBuf<float4> bvh_slot_box, bvh_node_box;
+    DevBuf<unsigned long long> bvh_cost;
+    uint32_t bvh_n_nodes = 0, bvh_n_slots = 0;
+    double bvh_cost_build = 0.0;      // cost of the tree as built, in the grid it was built with
+    uint32_t bvh_refits = 0;          // refits since the build
     // wavefront state
     DevBuf<float4> xchg;              // k_paths_regen_split: exchange stacks of every wave, one region per lane (stride: sched.xchg_stride)
     DevBuf<float4> queue[4];

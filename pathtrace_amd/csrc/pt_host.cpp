@@ -154,102 +154,24 @@ int build(const PtObject* objs, uint32_t n, Records* out) {
 
 using ptscene::shape_records;
 
-extern "C" {
+namespace {
 
-const char* pt_last_error(void) { return g_err.c_str(); }
-uint32_t pt_abi_version(void) { return PT_ABI_VERSION; }
-
-void pt_default_params(PtRenderParams* p) {
-    if (!p) return;
-    std::memset(p, 0, sizeof *p);
-    p->spp = 3000;          // world.rs:18
-    p->spp_offset = 0;
-    p->min_depth = 4;       // rendering.rs:6
-    p->max_depth = 50;      // rendering.rs:7
-    p->integrator = PT_INTEGRATOR_MIS;   // Cargo.toml:7 default feature
-    p->t_min = 0.001;       // rendering.rs:41
-    p->band_rows = 0;
-    p->band_index = 0;
-    p->band_count = 1;
-    p->max_paths_in_flight = 0;
-    p->profile = 0;
-    p->accel = PT_ACCEL_AUTO;
-    p->n_devices = 1;
-}
-
-uint32_t pt_tile_rows(uint32_t height, uint32_t band_rows, uint32_t band_index, uint32_t band_count) {
-    if (band_rows == 0) band_rows = height ? height : 1;
-    if (band_count == 0) band_count = 1;
-    uint32_t rows = 0;
-    for (uint32_t y = 0; y < height; ++y) rows += (y / band_rows) % band_count == band_index;
-    return rows;
-}
-
-void pt_default_denoise(PtDenoise* out) {
-    if (!out) return;
-    out->iterations = 5; out->sigma_l = 4.0f; out->sigma_n = 128.0f; out->sigma_d = 0.025f;
-}
-
-void pt_default_temporal(PtTemporal* out) {
-    if (!out) return;
-    out->alpha = 0.2f; out->depth_tol = 0.1f; out->normal_tol = 0.9f;
-}
-
-int pt_debug_motion_maps(const PtObject* prev_objs, const PtObject* cur_objs, uint32_t n, double* out_maps, uint32_t* out_flags) {
-    if (n && (!prev_objs || !cur_objs || !out_maps || !out_flags)) return fail(PT_ERR_INVALID_ARG, "pt_debug_motion_maps: null argument");
+// gather records, scan records and shape tags of the objects, as an upload forms them
+int bvh_records(const char* who, const PtObject* objs, uint32_t n, std::vector<float4>& shape, std::vector<float4>& scan, std::vector<uint32_t>& tag) {
+    shape.assign(3 * (size_t)n + 1, make_float4(0, 0, 0, 0)); scan.assign(3 * (size_t)n + 1, make_float4(0, 0, 0, 0));
+    tag.assign(n + 1, 0u);
     for (uint32_t i = 0; i < n; ++i) {
-        if (prev_objs[i].shape_tag > PT_SHAPE_TRIANGLE || prev_objs[i].shape_tag != cur_objs[i].shape_tag)
-            return fail(PT_ERR_INVALID_ARG, "pt_debug_motion_maps: object %u: shape tags %u and %u", i, prev_objs[i].shape_tag, cur_objs[i].shape_tag);
-        out_flags[i] = ptmo::motion_map(cur_objs[i].shape_tag == PT_SHAPE_TRIANGLE, cur_objs[i].shape, prev_objs[i].shape, out_maps + 12 * (size_t)i);
-    }
-    return PT_OK;
-}
-
-// Debug: every instance code ptk::launch_paths_* can return -- the path-kernel instances the library is built with (the
-// template arguments of the dispatch in pt_kernels_*.hip), each in both arithmetic modes.  *n = the table's length; up to cap
-// codes are written (out may be null to ask for the length).
-int pt_debug_path_instances(uint32_t* out, uint32_t cap, uint32_t* n) {
-    if (!n || (!out && cap)) return fail(PT_ERR_INVALID_ARG, "null argument");
-    std::vector<uint32_t> t;
-    for (const bool exact : {true, false}) {
-        for (const bool mis : {true, false}) {
-            for (const bool ovf : {false, true}) {
-                // k_paths<MODE, MIS, OVF, DIFFUSE, LIST>: the diffuse-only instances for whole-image renders out of LDS only
-                t.push_back(ptk::instance_code(ptk::kInstPaths, ptk::kModeLds, mis, ovf, true, false, exact));
-                for (const int mode : {ptk::kModeLds, ptk::kModeTiled})
-                    for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstPaths, mode, mis, ovf, false, list, exact));
-                // k_paths_bvh<MIS, OVF, DIFFUSE, LIST>: likewise
-                t.push_back(ptk::instance_code(ptk::kInstBvh, 0, mis, ovf, true, false, exact));
-                for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstBvh, 0, mis, ovf, false, list, exact));
-            }
-            // k_paths_regen<MIS, MATS, LIST> (level-0 launches only; LIST: pt_render_adaptive's passes)
-            for (const int mats : {ptk::kMatsAll, ptk::kMatsDiffuse, ptk::kMatsNoMirror})
-                for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstRegen, 0, mis, false, mats, list, exact));
-            // k_paths_regen_split<MIS, PLAIN> (level-0 launches of whole images only)
-            for (const int plain : {ptk::kMatsDiffuse, ptk::kMatsNoMirror})
-                t.push_back(ptk::instance_code(ptk::kInstRegenSplit, 0, mis, false, plain, false, exact));
-        }
-    }
-    for (size_t i = 0; i < t.size() && i < cap; ++i) out[i] = t[i];
-    *n = (uint32_t)t.size();
-    return PT_OK;
-}
-
-int pt_debug_bvh_check(const PtObject* objs, uint32_t n, uint32_t* depth, uint32_t* n_nodes, uint32_t* n_leaf_slots) {
-    if (!objs && n) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_check: null objects");
-    if (n >= (1u << 28)) return fail(PT_ERR_UNSUPPORTED, "accel: %u objects exceed the 2^28 leaf slots", n);
-    std::vector<float4> shape(3 * (size_t)n + 1), scan(3 * (size_t)n + 1);
-    std::vector<uint32_t> tag(n + 1);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (objs[i].shape_tag > PT_SHAPE_TRIANGLE) return fail(PT_ERR_INVALID_ARG, "object %u: bad shape_tag %u", i, objs[i].shape_tag);
+        if (objs[i].shape_tag > PT_SHAPE_TRIANGLE) return fail(PT_ERR_INVALID_ARG, "%s: object %u: bad shape_tag %u", who, i, objs[i].shape_tag);
         int ns = 0;
         shape_records(objs[i], &shape[3 * (size_t)i], &scan[3 * (size_t)i], &ns);
         tag[i] = objs[i].shape_tag;
     }
-    const ptbvh::Built b = ptbvh::build(shape.data(), tag.data(), n);
-    if (depth) *depth = b.depth;
-    if (n_nodes) *n_nodes = (uint32_t)b.wide.size();
-    if (n_leaf_slots) *n_leaf_slots = b.leaf_prims;          // slots that hold a primitive (leaves are padded to multiples of 4 slots)
+    return PT_OK;
+}
+
+// The invariants of a tree over the n objects with these records (pt_debug_bvh_check, pt_debug_bvh_refit_check): PT_OK, or
+// PT_ERR_UNSUPPORTED with the violated one in pt_last_error().
+int bvh_verify(const ptbvh::Built& b, const std::vector<float4>& shape, const std::vector<float4>& scan, const std::vector<uint32_t>& tag, uint32_t n) {
     if (b.non_finite) return fail(PT_ERR_UNSUPPORTED, "accel: %u object(s) with a NaN/inf coordinate", b.non_finite);
     if (b.depth + 2u > ptbvh::kStackDepth || b.stack_need > ptbvh::kStackDepth)
         return fail(PT_ERR_UNSUPPORTED, "BVH (depth %u, stack need %u) exceeds the traversal stack", b.depth, b.stack_need);
@@ -343,6 +265,158 @@ int pt_debug_bvh_check(const PtObject* objs, uint32_t n, uint32_t* depth, uint32
     double amax = 0.0;
     for (int k = 0; k < 3; ++k) amax += std::max(std::fabs(lo[k]), std::fabs(hi[k]));
     if (!((double)b.scene_abs >= amax)) return fail(PT_ERR_UNSUPPORTED, "BVH invariant: scene_abs %g below the scene extent %g", (double)b.scene_abs, amax);
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* pt_last_error(void) { return g_err.c_str(); }
+uint32_t pt_abi_version(void) { return PT_ABI_VERSION; }
+
+void pt_default_params(PtRenderParams* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);
+    p->spp = 3000;          // world.rs:18
+    p->spp_offset = 0;
+    p->min_depth = 4;       // rendering.rs:6
+    p->max_depth = 50;      // rendering.rs:7
+    p->integrator = PT_INTEGRATOR_MIS;   // Cargo.toml:7 default feature
+    p->t_min = 0.001;       // rendering.rs:41
+    p->band_rows = 0;
+    p->band_index = 0;
+    p->band_count = 1;
+    p->max_paths_in_flight = 0;
+    p->profile = 0;
+    p->accel = PT_ACCEL_AUTO;
+    p->n_devices = 1;
+}
+
+uint32_t pt_tile_rows(uint32_t height, uint32_t band_rows, uint32_t band_index, uint32_t band_count) {
+    if (band_rows == 0) band_rows = height ? height : 1;
+    if (band_count == 0) band_count = 1;
+    uint32_t rows = 0;
+    for (uint32_t y = 0; y < height; ++y) rows += (y / band_rows) % band_count == band_index;
+    return rows;
+}
+
+void pt_default_denoise(PtDenoise* out) {
+    if (!out) return;
+    out->iterations = 5; out->sigma_l = 4.0f; out->sigma_n = 128.0f; out->sigma_d = 0.025f;
+}
+
+void pt_default_temporal(PtTemporal* out) {
+    if (!out) return;
+    out->alpha = 0.2f; out->depth_tol = 0.1f; out->normal_tol = 0.9f;
+}
+
+int pt_debug_motion_maps(const PtObject* prev_objs, const PtObject* cur_objs, uint32_t n, double* out_maps, uint32_t* out_flags) {
+    if (n && (!prev_objs || !cur_objs || !out_maps || !out_flags)) return fail(PT_ERR_INVALID_ARG, "pt_debug_motion_maps: null argument");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (prev_objs[i].shape_tag > PT_SHAPE_TRIANGLE || prev_objs[i].shape_tag != cur_objs[i].shape_tag)
+            return fail(PT_ERR_INVALID_ARG, "pt_debug_motion_maps: object %u: shape tags %u and %u", i, prev_objs[i].shape_tag, cur_objs[i].shape_tag);
+        out_flags[i] = ptmo::motion_map(cur_objs[i].shape_tag == PT_SHAPE_TRIANGLE, cur_objs[i].shape, prev_objs[i].shape, out_maps + 12 * (size_t)i);
+    }
+    return PT_OK;
+}
+
+// Debug: every instance code ptk::launch_paths_* can return -- the path-kernel instances the library is built with (the
+// template arguments of the dispatch in pt_kernels_*.hip), each in both arithmetic modes.  *n = the table's length; up to cap
+// codes are written (out may be null to ask for the length).
+int pt_debug_path_instances(uint32_t* out, uint32_t cap, uint32_t* n) {
+    if (!n || (!out && cap)) return fail(PT_ERR_INVALID_ARG, "null argument");
+    std::vector<uint32_t> t;
+    for (const bool exact : {true, false}) {
+        for (const bool mis : {true, false}) {
+            for (const bool ovf : {false, true}) {
+                // k_paths<MODE, MIS, OVF, DIFFUSE, LIST>: the diffuse-only instances for whole-image renders out of LDS only
+                t.push_back(ptk::instance_code(ptk::kInstPaths, ptk::kModeLds, mis, ovf, true, false, exact));
+                for (const int mode : {ptk::kModeLds, ptk::kModeTiled})
+                    for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstPaths, mode, mis, ovf, false, list, exact));
+                // k_paths_bvh<MIS, OVF, DIFFUSE, LIST>: likewise
+                t.push_back(ptk::instance_code(ptk::kInstBvh, 0, mis, ovf, true, false, exact));
+                for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstBvh, 0, mis, ovf, false, list, exact));
+            }
+            // k_paths_regen<MIS, MATS, LIST> (level-0 launches only; LIST: pt_render_adaptive's passes)
+            for (const int mats : {ptk::kMatsAll, ptk::kMatsDiffuse, ptk::kMatsNoMirror})
+                for (const bool list : {false, true}) t.push_back(ptk::instance_code(ptk::kInstRegen, 0, mis, false, mats, list, exact));
+            // k_paths_regen_split<MIS, PLAIN> (level-0 launches of whole images only)
+            for (const int plain : {ptk::kMatsDiffuse, ptk::kMatsNoMirror})
+                t.push_back(ptk::instance_code(ptk::kInstRegenSplit, 0, mis, false, plain, false, exact));
+        }
+    }
+    for (size_t i = 0; i < t.size() && i < cap; ++i) out[i] = t[i];
+    *n = (uint32_t)t.size();
+    return PT_OK;
+}
+
+int pt_debug_bvh_check(const PtObject* objs, uint32_t n, uint32_t* depth, uint32_t* n_nodes, uint32_t* n_leaf_slots) {
+    if (!objs && n) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_check: null objects");
+    if (n >= (1u << 28)) return fail(PT_ERR_UNSUPPORTED, "accel: %u objects exceed the 2^28 leaf slots", n);
+    std::vector<float4> shape, scan;
+    std::vector<uint32_t> tag;
+    if (int rc = bvh_records("pt_debug_bvh_check", objs, n, shape, scan, tag)) return rc;
+    const ptbvh::Built b = ptbvh::build(shape.data(), tag.data(), n);
+    if (depth) *depth = b.depth;
+    if (n_nodes) *n_nodes = (uint32_t)b.wide.size();
+    if (n_leaf_slots) *n_leaf_slots = b.leaf_prims;          // slots that hold a primitive (leaves are padded to multiples of 4 slots)
+    return bvh_verify(b, shape, scan, tag, n);
+}
+
+int pt_debug_bvh_refit_check(const PtObject* prev_objs, const PtObject* cur_objs, uint32_t n, uint32_t refit, uint32_t* out_qnodes, uint32_t cap_nodes,
+                             float* out_leaf_rec, float* out_leaf_lead, uint32_t* out_leaf_ids, uint32_t cap_slots, uint32_t* n_nodes,
+                             uint32_t* n_slots, float* out_grid, uint32_t* root, uint64_t* cost_now, uint64_t* cost_at_build) {
+    if (n && (!prev_objs || !cur_objs)) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_refit_check: null objects");
+    if ((cap_nodes && !out_qnodes) || (cap_slots && (!out_leaf_rec || !out_leaf_lead || !out_leaf_ids)))
+        return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_refit_check: null output array with a non-zero capacity");
+    if (n >= (1u << 28)) return fail(PT_ERR_UNSUPPORTED, "accel: %u objects exceed the 2^28 leaf slots", n);
+    for (uint32_t i = 0; i < n; ++i)
+        if (prev_objs[i].shape_tag != cur_objs[i].shape_tag)
+            return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_refit_check: object %u: shape tags %u and %u", i, prev_objs[i].shape_tag, cur_objs[i].shape_tag);
+    std::vector<float4> shape, scan;
+    std::vector<uint32_t> tag;
+    if (int rc = bvh_records("pt_debug_bvh_refit_check", prev_objs, n, shape, scan, tag)) return rc;
+    ptbvh::Built b = ptbvh::build(shape.data(), tag.data(), n);
+    if (b.non_finite) return fail(PT_ERR_UNSUPPORTED, "accel: %u object(s) of the build pose with a NaN/inf coordinate", b.non_finite);
+    const std::vector<uint32_t> ids0 = b.leaf_ids;
+    std::vector<uint32_t> codes0;
+    for (const ptbvh::WideNode& w : b.wide) codes0.insert(codes0.end(), w.code, w.code + ptbvh::kWidth);
+    const uint32_t root0 = b.root;
+    const uint64_t cost0[3] = {b.cost[0], b.cost[1], b.cost[2]};
+    if (refit) {                                                 // (0: the tree as built, verified against prev_objs)
+        if (int rc = bvh_records("pt_debug_bvh_refit_check", cur_objs, n, shape, scan, tag)) return rc;
+        ptbvh::refit(b, shape.data(), tag.data(), n);
+    }
+    if (n_nodes) *n_nodes = (uint32_t)b.wide.size();
+    if (n_slots) *n_slots = (uint32_t)b.leaf_ids.size();
+    if (int rc = bvh_verify(b, shape, scan, tag, n)) return rc;
+    // the topology is the build's
+    if (b.root != root0 || b.leaf_ids != ids0) return fail(PT_ERR_UNSUPPORTED, "BVH refit: root or leaf ids differ from the build's");
+    for (size_t k = 0; k < b.wide.size(); ++k)
+        if (std::memcmp(b.wide[k].code, &codes0[ptbvh::kWidth * k], sizeof b.wide[k].code) != 0)
+            return fail(PT_ERR_UNSUPPORTED, "BVH refit: node %zu carries other child codes than the build's", k);
+    // the same bounds from one pass over the objects (what pt_scene_refit computes on the host)
+    const ptbvh::Bounds bd = ptbvh::scene_bounds(shape.data(), tag.data(), n, !b.wide.empty());
+    if (std::memcmp(bd.grid_min, b.grid_min, sizeof bd.grid_min) != 0 || std::memcmp(bd.grid_cell, b.grid_cell, sizeof bd.grid_cell) != 0 ||
+        std::memcmp(&bd.scene_abs, &b.scene_abs, sizeof(float)) != 0 || bd.non_finite != b.non_finite)
+        return fail(PT_ERR_UNSUPPORTED, "BVH refit: the bounds of the objects differ from the bounds of the child boxes");
+    const size_t nn = std::min<size_t>(b.wide.size(), cap_nodes), nsl = std::min<size_t>(b.leaf_ids.size(), cap_slots);
+    if (nn) std::memcpy(out_qnodes, b.qnodes.data(), nn * 4 * sizeof(uint4));
+    if (nsl) {
+        std::memcpy(out_leaf_rec, b.leaf_rec.data(), nsl * 3 * sizeof(float4));
+        std::memcpy(out_leaf_lead, b.leaf_lead.data(), nsl * sizeof(float4));
+        std::memcpy(out_leaf_ids, b.leaf_ids.data(), nsl * sizeof(uint32_t));
+    }
+    if (out_grid) {
+        for (int k = 0; k < 3; ++k) { out_grid[k] = b.grid_min[k]; out_grid[3 + k] = b.grid_cell[k]; }
+        out_grid[6] = b.scene_abs;
+    }
+    if (root) *root = b.root;
+    for (int k = 0; k < 3; ++k) {
+        if (cost_now) cost_now[k] = b.cost[k];
+        if (cost_at_build) cost_at_build[k] = cost0[k];
+    }
     return PT_OK;
 }
 

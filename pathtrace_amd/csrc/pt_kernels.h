@@ -339,4 +339,25 @@ struct TemporalMotionArgs {
 };
 void launch_denoise_temporal_motion(const TemporalMotionArgs& a, hipStream_t st);
 
+// Device-side BVH refit (pt_scene_refit; rule: ptbvh::refit in pt_bvh.h, whose arrays these launches reproduce bit for bit).
+// The topology -- ids, child codes, the order of the nodes by height -- stays; leaf records, child boxes and their quantisation
+// are recomputed from the scene's gather records.  The grid is the host's (one O(n) pass over its copy of the records) and
+// travels by value.  launch_bvh_refit_leaves first, then launch_bvh_refit_level once per height from 0 upward, all on one
+// stream: a node reads what the launches before it wrote, so nothing waits inside a kernel.
+struct BvhRefitArgs {
+    const float4* shape;      // gather records, 3 float4 per object (the .w lanes of a triangle's records are not read)
+    const uint32_t* ids;      // object index per leaf slot (bit 31: triangle; 0xFFFFFFFF: padding slot)
+    float4* rec;              // 3 float4 per leaf slot, written
+    float4* lead;             // 1 float4 per leaf slot, written
+    float4* slot_box;         // scratch, 2 float4 per leaf slot: the primitive's f32 box (lo, -) (hi, -)
+    uint4* nodes;             // 4 uint4 per node: the three box words rewritten, the code word kept
+    float4* node_box;         // scratch, 2 float4 per node: the union of the node's child boxes, for its parent
+    const uint32_t* order;    // node indices by height (0 = all children are leaves), ties by index
+    unsigned long long* cost; // 3 words: sums over the used child slots of dx dy, dy dz, dz dx in grid units (d = q_hi - q_lo)
+    float grid_min[3], grid_cell[3];
+    uint32_t n_slots;
+};
+void launch_bvh_refit_leaves(const BvhRefitArgs& a, hipStream_t st);   // also zeroes the three cost words
+void launch_bvh_refit_level(const BvhRefitArgs& a, uint32_t first, uint32_t count, hipStream_t st);   // nodes order[first, first + count)
+
 }  // namespace ptk

@@ -528,3 +528,171 @@ void launch_denoise_temporal_motion(const TemporalMotionArgs& a, hipStream_t st)
     hipLaunchKernelGGL(PTK_IMPL::k_denoise_temporal_motion, g, b, 0, st, a);
 }
 }  // namespace ptk
+
+// ------------------------------------------------------------------ device-side BVH refit (pt_scene_refit)
+// The rule is ptbvh::refit (pt_bvh.h / pt_bvh.cpp) and DESIGN.md 5e; these kernels reproduce its arrays bit for bit.  That is a
+// requirement: the grid comes from the HOST's boxes and the quantisation clamps to it, so a device box one ulp outside the
+// host's would be quantised to a box that no longer encloses it.  Hence f64 + - * / sqrt floor ceil (correctly rounded on the
+// device as on the host), no contraction, the host's compare-and-step outward rounding, and fmaf for the decode as there.
+// None of it depends on the arithmetic mode.
+#include "pt_bvh.h"
+namespace PTK_IMPL {
+// ptbvh's down() / up(): the f32 at or below / at or above v
+PT_DEV float refit_down(double v) {
+    float f = (float)v;
+    if ((double)f > v) {                       // step to the next f32 below (nextafterf(f, -inf))
+        const uint32_t b = __float_as_uint(f);
+        f = f > 0.0f ? __uint_as_float(b - 1u) : f == 0.0f ? __uint_as_float(0x80000001u) : __uint_as_float(b + 1u);
+    }
+    return f;
+}
+PT_DEV float refit_up(double v) {
+    float f = (float)v;
+    if ((double)f < v) {                       // nextafterf(f, +inf)
+        const uint32_t b = __float_as_uint(f);
+        f = f < 0.0f ? __uint_as_float(b - 1u) : f == 0.0f ? __uint_as_float(0x00000001u) : __uint_as_float(b + 1u);
+    }
+    return f;
+}
+// ptbvh::primitive_box for a finite primitive (the host drops the tree before any launch when an object is not finite)
+PT_DEV void refit_primitive_box(const float4& r0, const float4& r1, const float4& r2, bool tri, float lo[3], float hi[3]) {
+#pragma clang fp contract(off)
+    if (!tri) {
+        const float r2f = r0.w * r0.w;
+        const double r = __builtin_sqrt((double)r2f) * (1.0 + 1e-7);
+        const double c[3] = {r0.x, r0.y, r0.z};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = refit_down(c[k] - r); hi[k] = refit_up(c[k] + r); }
+    } else {
+        const double v0[3] = {r0.x, r0.y, r0.z}, e1[3] = {r1.x, r1.y, r1.z}, e2[3] = {r2.x, r2.y, r2.z};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double a = v0[k], b = v0[k] + e1[k], c = v0[k] + e2[k];
+            const double mn_bc = c < b ? c : b, mx_bc = b < c ? c : b;      // std::min / std::max
+            lo[k] = refit_down(mn_bc < a ? mn_bc : a);
+            hi[k] = refit_up(a < mx_bc ? mx_bc : a);
+        }
+    }
+}
+// Box::grow
+PT_DEV void refit_grow(float lo[3], float hi[3], const float4& blo, const float4& bhi) {
+    lo[0] = blo.x < lo[0] ? blo.x : lo[0]; lo[1] = blo.y < lo[1] ? blo.y : lo[1]; lo[2] = blo.z < lo[2] ? blo.z : lo[2];
+    hi[0] = hi[0] < bhi.x ? bhi.x : hi[0]; hi[1] = hi[1] < bhi.y ? bhi.y : hi[1]; hi[2] = hi[2] < bhi.z ? bhi.z : hi[2];
+}
+// quantise()'s q_lo / q_hi: the grid plane at or below / at or above v, by the decode the traversal evaluates
+PT_DEV uint32_t refit_q_lo(float v, float gmin, float cell) {
+#pragma clang fp contract(off)
+    long long q = (long long)__builtin_floor(((double)v - (double)gmin) / (double)cell);
+    q = q < 0 ? 0 : q > 65535 ? 65535 : q;
+    while (q > 0 && __builtin_fmaf((float)(uint32_t)q, cell, gmin) > v) --q;
+    return (uint32_t)q;
+}
+PT_DEV uint32_t refit_q_hi(float v, float gmin, float cell) {
+#pragma clang fp contract(off)
+    long long q = (long long)__builtin_ceil(((double)v - (double)gmin) / (double)cell);
+    q = q < 0 ? 0 : q > 65535 ? 65535 : q;
+    while (q < 65535 && __builtin_fmaf((float)(uint32_t)q, cell, gmin) < v) ++q;
+    return (uint32_t)q;
+}
+
+// One thread per leaf slot: the slot's scan records (make_leaf's) and the primitive's f32 box.  Padding slots keep their zeros.
+__global__ void __launch_bounds__(kBlock) k_bvh_refit_leaves(BvhRefitArgs a) {
+    if (blockIdx.x == 0u && threadIdx.x < 3u) a.cost[threadIdx.x] = 0ull;      // the level launches add to them
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= a.n_slots) return;
+    const uint32_t w = a.ids[slot];
+    if (w == ptbvh::kDone) return;
+    const uint32_t o = w & ~ptbvh::kTriangleBit;
+    const bool tri = (w & ptbvh::kTriangleBit) != 0u;
+    const float4 r0 = a.shape[3 * (size_t)o], r1 = a.shape[3 * (size_t)o + 1], r2 = a.shape[3 * (size_t)o + 2];
+    float4 rec[3];
+    if (tri) {
+        ptbvh::triangle_scan_record(r0, r1, r2, rec);
+    } else {
+        rec[0] = make_float4(r0.x, r0.y, r0.z, r0.w * r0.w);                   // (c, r^2)
+        rec[1] = make_float4(0.f, 0.f, 0.f, 0.f); rec[2] = rec[1];
+    }
+    a.rec[3 * (size_t)slot] = rec[0]; a.rec[3 * (size_t)slot + 1] = rec[1]; a.rec[3 * (size_t)slot + 2] = rec[2];
+    a.lead[slot] = rec[0];
+    float lo[3], hi[3];
+    refit_primitive_box(r0, r1, r2, tri, lo, hi);
+    a.slot_box[2 * (size_t)slot] = make_float4(lo[0], lo[1], lo[2], 0.f);
+    a.slot_box[2 * (size_t)slot + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
+}
+
+// The nodes order[first, first + count) -- one height --, four lanes per node, one per child slot.  A lane forms its child's
+// f32 box (a leaf: the union of its slots' boxes; a node: that node's stored union, written by an earlier launch), the four
+// lanes' union is stored for the parent, each lane quantises its box, and the twelve box words are regrouped across the
+// four lanes into the node's three 16-byte stores.  The cost terms are summed over the wave before one 64-bit atomic add
+// per sum and wave: integer sums, so the result does not depend on the order.
+__global__ void __launch_bounds__(kBlock) k_bvh_refit_level(BvhRefitArgs a, uint32_t first, uint32_t count) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x, pos = t >> 2, c = t & 3u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool node_ok = pos < count;
+    uint32_t k = 0u, code = ptbvh::kDone;
+    uint4 codes = make_uint4(ptbvh::kDone, ptbvh::kDone, ptbvh::kDone, ptbvh::kDone);
+    if (node_ok) {
+        k = a.order[first + pos];
+        codes = a.nodes[4 * (size_t)k + 3];
+        code = c == 0u ? codes.x : c == 1u ? codes.y : c == 2u ? codes.z : codes.w;
+    }
+    const bool used = code != ptbvh::kDone;    // the builder fills the child slots from 0 and gives the rest the sentinel
+    const float inf = __builtin_inff();
+    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+    if (used) {
+        if (code & ptbvh::kLeafBit) {
+            const uint32_t s0 = code & 0x0FFFFFFFu, cnt = ((code >> 28) & 7u) + 1u;
+            for (uint32_t i = s0; i < s0 + cnt && i < a.n_slots; ++i) refit_grow(lo, hi, a.slot_box[2 * (size_t)i], a.slot_box[2 * (size_t)i + 1]);
+        } else {
+            refit_grow(lo, hi, a.node_box[2 * (size_t)code], a.node_box[2 * (size_t)code + 1]);
+        }
+    }
+    // the node's own union (an unused slot's box is empty: it changes nothing)
+    float ulo[3], uhi[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        ulo[d] = fminf(lo[d], __shfl_xor(lo[d], 1)); ulo[d] = fminf(ulo[d], __shfl_xor(ulo[d], 2));
+        uhi[d] = fmaxf(hi[d], __shfl_xor(hi[d], 1)); uhi[d] = fmaxf(uhi[d], __shfl_xor(uhi[d], 2));
+    }
+    if (node_ok && c == 0u) {
+        a.node_box[2 * (size_t)k] = make_float4(ulo[0], ulo[1], ulo[2], 0.f);
+        a.node_box[2 * (size_t)k + 1] = make_float4(uhi[0], uhi[1], uhi[2], 0.f);
+    }
+    uint32_t w0 = 0u, w1 = 0u, w2 = 0u;        // unused slot: zero words
+    unsigned long long sxy = 0ull, syz = 0ull, szx = 0ull;
+    if (used) {
+        const uint32_t lx = refit_q_lo(lo[0], a.grid_min[0], a.grid_cell[0]), ly = refit_q_lo(lo[1], a.grid_min[1], a.grid_cell[1]),
+                       lz = refit_q_lo(lo[2], a.grid_min[2], a.grid_cell[2]);
+        const uint32_t hx = refit_q_hi(hi[0], a.grid_min[0], a.grid_cell[0]), hy = refit_q_hi(hi[1], a.grid_min[1], a.grid_cell[1]),
+                       hz = refit_q_hi(hi[2], a.grid_min[2], a.grid_cell[2]);
+        w0 = lx | (ly << 16); w1 = lz | (hx << 16); w2 = hy | (hz << 16);
+        const unsigned long long dx = hx - lx, dy = hy - ly, dz = hz - lz;
+        sxy = dx * dy; syz = dy * dz; szx = dz * dx;
+    }
+    // word j of the node (j < 12) = word j % 3 of child j / 3; lane c < 3 stores uint4 c = words 4c .. 4c + 3, which lie in
+    // children c and c + 1: (w0 w1 w2 | w0'), (w1 w2 | w0' w1'), (w2 | w0' w1' w2')
+    const uint32_t base = lane & ~3u, src_a = base + (c < 3u ? c : 0u), src_b = base + (c < 3u ? c + 1u : 0u);
+    const uint32_t a0 = __shfl(w0, src_a), a1 = __shfl(w1, src_a), a2 = __shfl(w2, src_a);
+    const uint32_t b0 = __shfl(w0, src_b), b1 = __shfl(w1, src_b), b2 = __shfl(w2, src_b);
+    if (node_ok && c < 3u) {
+        const uint4 v = c == 0u ? make_uint4(a0, a1, a2, b0) : c == 1u ? make_uint4(a1, a2, b0, b1) : make_uint4(a2, b0, b1, b2);
+        a.nodes[4 * (size_t)k + c] = v;
+    }
+    if (node_ok && c == 3u) a.nodes[4 * (size_t)k + 3] = codes;                 // the code word, carried over
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sxy += __shfl_xor(sxy, off); syz += __shfl_xor(syz, off); szx += __shfl_xor(szx, off);
+    }
+    if (lane == 0u && (sxy | syz | szx) != 0ull) {
+        atomicAdd(a.cost, sxy); atomicAdd(a.cost + 1, syz); atomicAdd(a.cost + 2, szx);
+    }
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_bvh_refit_leaves(const BvhRefitArgs& a, hipStream_t st) {
+    if (a.n_slots) hipLaunchKernelGGL(PTK_IMPL::k_bvh_refit_leaves, dim3((a.n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+void launch_bvh_refit_level(const BvhRefitArgs& a, uint32_t first, uint32_t count, hipStream_t st) {
+    if (count) hipLaunchKernelGGL(PTK_IMPL::k_bvh_refit_level, dim3((uint32_t)(((uint64_t)count * 4u + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, first, count);
+}
+}  // namespace ptk

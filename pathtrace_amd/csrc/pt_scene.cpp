@@ -1,5 +1,6 @@
 // pt_scene.cpp -- the device half of a scene upload: the records of ptscene::build (pt_scene_records.h) into the context's
-// buffers, k_scene_setup over them, the LDS blob; and the BVH of the uploaded scene, built at first use.
+// buffers, k_scene_setup over them, the LDS blob; and the BVH of the uploaded scene, built at first use and, for
+// pt_scene_refit, refitted on the device when the objects move.
 #include <cstring>
 
 #include "pt_bvh.h"
@@ -36,13 +37,23 @@ int ensure_bvh(PtContext* c) {
     }
     int rc;
     if ((rc = c->bvh_nodes.ensure(b.qnodes.size() + 2)) || (rc = c->bvh_rec.ensure(b.leaf_rec.size() + 3)) ||
-        (rc = c->bvh_ids.ensure(b.leaf_ids.size() + 4)) || (rc = c->bvh_lead.ensure(b.leaf_lead.size() + 4)))
+        (rc = c->bvh_ids.ensure(b.leaf_ids.size() + 4)) || (rc = c->bvh_lead.ensure(b.leaf_lead.size() + 4)) ||
+        (rc = c->bvh_order.ensure(b.height_order.size() + 1)) || (rc = c->bvh_cost.ensure(4)))
         return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!b.qnodes.empty()) HIP_TRY(hipMemcpy(c->bvh_nodes.p, b.qnodes.data(), b.qnodes.size() * sizeof(uint4), hipMemcpyHostToDevice));
     if (!b.leaf_rec.empty()) HIP_TRY(hipMemcpy(c->bvh_rec.p, b.leaf_rec.data(), b.leaf_rec.size() * sizeof(float4), hipMemcpyHostToDevice));
     if (!b.leaf_ids.empty()) HIP_TRY(hipMemcpy(c->bvh_ids.p, b.leaf_ids.data(), b.leaf_ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!b.leaf_lead.empty()) HIP_TRY(hipMemcpy(c->bvh_lead.p, b.leaf_lead.data(), b.leaf_lead.size() * sizeof(float4), hipMemcpyHostToDevice));
+    // for pt_scene_refit: the order of the nodes by height, and the cost sums of the tree as built
+    if (!b.height_order.empty()) HIP_TRY(hipMemcpy(c->bvh_order.p, b.height_order.data(), b.height_order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "cost words");
+    HIP_TRY(hipMemcpy(c->bvh_cost.p, b.cost, sizeof b.cost, hipMemcpyHostToDevice));
+    c->bvh_height_first = std::move(b.height_first);
+    c->bvh_n_nodes = (uint32_t)b.wide.size();
+    c->bvh_n_slots = (uint32_t)b.leaf_ids.size();
+    c->bvh_cost_build = ptbvh::cost_value(b.cost, b.grid_cell);
+    c->bvh_refits = 0;
     c->view.bvh.nodes = c->bvh_nodes.p; c->view.bvh.rec = c->bvh_rec.p; c->view.bvh.ids = c->bvh_ids.p; c->view.bvh.lead = c->bvh_lead.p;
     c->view.bvh.root = b.root;
     c->view.bvh.scene_abs = b.scene_abs;
@@ -54,10 +65,11 @@ int ensure_bvh(PtContext* c) {
 
 namespace {
 
-// The body of pt_scene_upload and of pt_scene_update (keep_history: same object count and shape tags as the uploaded scene,
-// and the temporal history stays).  The records are built on the host first (ptscene::build); the context is touched only
-// once that has succeeded.
-int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, bool keep_history) {
+// The body of pt_scene_upload, pt_scene_update and pt_scene_refit (keep_history: same object count and shape tags as the
+// uploaded scene, and the temporal history stays).  The records are built on the host first (ptscene::build); the context is
+// touched only once that has succeeded.  keep_tree (pt_scene_refit): a BVH the context holds is not dropped but refitted on
+// the device to the new records -- same topology, so the tree arrays never cross PCIe again.
+int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, bool keep_history, bool keep_tree = false) {
     if (!c || (!objs && n)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (keep_history) {
         if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
@@ -80,6 +92,16 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
     if ((rc = c->mat_x.ensure(mat.size()))) return rc;
     if ((rc = c->runs.ensure(runs.size() + 1))) return rc;
     if ((rc = c->lights.ensure(lights.size() + 1))) return rc;
+    // The refit's share of the host work: one pass over the new gather records for the grid, scene_abs and the non-finite rule
+    // (ptbvh::scene_bounds: the boxes ptbvh::refit would form).  The kernels reproduce the host's boxes bit for bit, so the
+    // grid encloses every box they quantise.
+    const bool refit = keep_tree && c->has_bvh;
+    ptbvh::Bounds bounds;
+    if (refit) {
+        bounds = ptbvh::scene_bounds(shape.data(), rec.shape_tag.data(), n, c->bvh_n_nodes != 0);
+        if (!bounds.non_finite && ((rc = c->bvh_slot_box.ensure(2 * (size_t)c->bvh_n_slots + 1)) || (rc = c->bvh_node_box.ensure(2 * (size_t)c->bvh_n_nodes + 1))))
+            return rc;
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));   // the previous scene may still be in use
     ptsched::on_scene(c->sched);                 // statistics of renders of the previous scene do not carry over
     c->expected_samples = 0;
@@ -122,10 +144,28 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
     c->view.diffuse_only = rec.diffuse_only; c->view.no_mirror = rec.no_mirror; c->view.no_oren_nayar = rec.no_oren_nayar;
     c->split_ok = rec.split_ok;
     std::memcpy(c->scan_counts, rec.scan_counts, sizeof c->scan_counts);
-    c->view.bvh = ptk::BvhView{};
-    c->has_bvh = false;
-    c->bvh_refused = false;
-    c->bvh_failed = false;
+    if (refit && !bounds.non_finite) {
+        // behind the records and k_scene_setup on the context's stream; nothing here waits for the device
+        ptk::BvhRefitArgs ra{};
+        ra.shape = c->shape.p; ra.ids = c->bvh_ids.p; ra.rec = c->bvh_rec.p; ra.lead = c->bvh_lead.p;
+        ra.slot_box = c->bvh_slot_box.p; ra.nodes = c->bvh_nodes.p; ra.node_box = c->bvh_node_box.p;
+        ra.order = c->bvh_order.p; ra.cost = c->bvh_cost.p;
+        ra.n_slots = c->bvh_n_slots;
+        for (int k = 0; k < 3; ++k) { ra.grid_min[k] = bounds.grid_min[k]; ra.grid_cell[k] = bounds.grid_cell[k]; }
+        ptk::launch_bvh_refit_leaves(ra, c->stream);
+        for (size_t h = 0; h + 1 < c->bvh_height_first.size(); ++h)
+            ptk::launch_bvh_refit_level(ra, c->bvh_height_first[h], c->bvh_height_first[h + 1] - c->bvh_height_first[h], c->stream);
+        HIP_TRY(hipGetLastError());
+        for (int k = 0; k < 3; ++k) { c->view.bvh.grid_min[k] = bounds.grid_min[k]; c->view.bvh.grid_cell[k] = bounds.grid_cell[k]; }
+        c->view.bvh.scene_abs = bounds.scene_abs;
+        ++c->bvh_refits;
+    } else {
+        c->view.bvh = ptk::BvhView{};
+        c->has_bvh = false;
+        // a pose with a NaN/inf coordinate takes the tree away for good, as ensure_bvh would on building it
+        c->bvh_refused = refit && bounds.non_finite;
+        c->bvh_failed = false;
+    }
     c->auto_bvh = rec.auto_bvh;
     c->h_shape.assign(shape.begin(), shape.begin() + 3 * (size_t)n);
     c->h_shape_tag = std::move(rec.shape_tag);
@@ -142,5 +182,19 @@ extern "C" {
 
 int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_upload", c, objs, n, false); }
 int pt_scene_update(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_update", c, objs, n, true); }
+int pt_scene_refit(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_refit", c, objs, n, true, true); }
+
+int pt_scene_bvh_cost(PtContext* c, double* cost_now, double* cost_at_build, uint32_t* refits) {
+    if (!c) return fail(PT_ERR_INVALID_ARG, "pt_scene_bvh_cost: null context");
+    if (!c->has_bvh) return fail(PT_ERR_INVALID_ARG, "pt_scene_bvh_cost: the context holds no BVH (none built yet, or dropped by a scene change)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint64_t now[3];
+    HIP_TRY(hipMemcpy(now, c->bvh_cost.p, sizeof now, hipMemcpyDeviceToHost));
+    if (cost_now) *cost_now = ptbvh::cost_value(now, c->view.bvh.grid_cell);
+    if (cost_at_build) *cost_at_build = c->bvh_cost_build;
+    if (refits) *refits = c->bvh_refits;
+    return PT_OK;
+}
 
 }  // extern "C"

@@ -485,6 +485,17 @@ public:
     // it); scene_update() does so at once.
     void set_object(size_t i, const Object& o) { objects_.at(i) = o.pod(); moved_ = true; }
     void scene_update(int device = 0) { scene(device); }
+    // The same through pt_scene_refit: a BVH the context holds is refitted on the device to the moved objects instead of
+    // dropped and rebuilt on the host.  The film is the same bit for bit; bvh_cost() tells when a rebuild (scene_update()
+    // after the next set_object()) is due: {cost now, cost at build, refits since the build}.
+    void scene_refit(int device = 0) { scene(device, true); }
+    struct BvhCost { double now, at_build; uint32_t refits; };
+    BvhCost bvh_cost() {
+        BvhCost b{};
+        if (!ctx_) throw std::runtime_error("bvh_cost: no context");
+        check(pt_scene_bvh_cost(ctx_, &b.now, &b.at_build, &b.refits));
+        return b;
+    }
     // render_denoised_temporal() whose history also follows the objects moved by set_object() + scene_update()
     // (pt_render_denoised_motion).  ids (optional) receives the object index of every pixel's first hit, -1 for a miss.
     void render_denoised_motion(uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, const PtTemporal* tp = nullptr,
@@ -583,11 +594,11 @@ private:
     PtRenderParams tmp_params_{};
 
     // the context with this World's objects on it (uploaded again after push())
-    PtContext* scene(int device) {
+    PtContext* scene(int device, bool refit = false) {
         check_abi();
         if (!ctx_) check(pt_context_create(device, &ctx_));
         if (!uploaded_) { check(pt_scene_upload(ctx_, objects_.data(), (uint32_t)objects_.size())); uploaded_ = true; }
-        else if (moved_) check(pt_scene_update(ctx_, objects_.data(), (uint32_t)objects_.size()));
+        else if (moved_) check((refit ? pt_scene_refit : pt_scene_update)(ctx_, objects_.data(), (uint32_t)objects_.size()));
         moved_ = false;
         return ctx_;
     }
