@@ -538,6 +538,23 @@ int pt_scene_update(PtContext* ctx, const PtObject* objs, uint32_t n_objs);
  * Any output may be NULL.  PT_ERR_INVALID_ARG when the context holds no tree.                                            */
 int pt_scene_refit(PtContext* ctx, const PtObject* objs, uint32_t n_objs);
 int pt_scene_bvh_cost(PtContext* ctx, double* cost_now, double* cost_at_build, uint32_t* refits);
+/* Device-side BVH build (additive to ABI 6).
+ *
+ * pt_scene_rebuild is pt_scene_update in every respect but one: same argument checks with the context untouched on failure,
+ * same records, same restart of the statistics, the temporal history kept -- but the context afterwards HOLDS A TREE FOR THE NEW
+ * POSE, built on the device, on the context's stream behind the new records, whether or not it held one before.  The tree is
+ * the Morton tree of DESIGN.md 5f: the objects ordered along a Morton curve over the scene's grid (keys and a radix sort on the
+ * device), four consecutive objects per leaf, and a topology that depends on the object count alone (planned on the host once
+ * per count and cached on the device), filled in by the launches of the refit.  No tree array crosses PCIe, the binned-SAH
+ * builder does not run, and the call adds no wait for the device of its own.  Called with the uploaded objects right after
+ * pt_scene_upload it is a first build without the host builder.  A later pt_scene_refit refits this tree; cost_at_build of
+ * pt_scene_bvh_cost is the cost after this build, refits restarts at 0.
+ * A pose with a NaN/inf coordinate drops the tree and refuses the BVH exactly as pt_scene_refit does.  An object count for
+ * which no tree fits the traversal stack (more than 2^25 objects) gives PT_ERR_UNSUPPORTED with the context untouched: use
+ * pt_scene_update.  pt_scene_upload, pt_scene_update, pt_scene_refit and pt_scene_rebuild may be mixed freely.
+ * THE FILM NEVER DEPENDS ON THE BUILDER.  A Morton tree is built faster and traversed somewhat slower than the host's SAH
+ * tree (docs/EXPERIMENTS.md, "Device-side build"); when to refit, rebuild here or rebuild on the host is the caller's policy. */
+int pt_scene_rebuild(PtContext* ctx, const PtObject* objs, uint32_t n_objs);
 /* The motion map of object k, x -> A x + b in f64, carries a point of the current pose to the same material point of the
  * history pose:  sphere (c, r) now, (c', r') then: A = (r'/r) I, b = c' - (r'/r) c;  triangle (v0, v1, v2) now, primed then:
  * e1 = v1 - v0, e2 = v2 - v0, n = (e1 x e2)/|e1 x e2|, E = [e1 e2 n] as columns, A = E' E^-1, b = v0' - A v0.
@@ -650,6 +667,24 @@ int pt_debug_bvh_refit_check(const PtObject* prev_objs, const PtObject* cur_objs
                              uint32_t* out_qnodes, uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead, uint32_t* out_leaf_ids,
                              uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots, float* out_grid, uint32_t* root,
                              uint64_t* cost_now, uint64_t* cost_at_build);
+/* Debug entry, host only (no GPU needed): build the Morton tree of objs on the host (ptbvh::build_morton, the specification of
+ * the device-side build) and run the invariants of pt_debug_bvh_check on it, and that the slots hold the objects in ascending
+ * (key, index) order.  refit_objs (optional; same n_objs and shape tags): the tree of objs is then refitted to that pose by the
+ * host refit and verified against it -- what pt_scene_refit after pt_scene_rebuild must reproduce; keys and order stay those
+ * of objs.  PT_ERR_UNSUPPORTED for a NaN/inf coordinate, a violated invariant or an object count without a plan.
+ * Optional outputs: the tree as pt_debug_bvh_refit_check returns it, and per object (up to cap_objs) its 30-bit key and the
+ * sorted order (out_order[p] = object at sorted position p).                                                             */
+int pt_debug_bvh_morton_check(const PtObject* objs, const PtObject* refit_objs, uint32_t n_objs, uint32_t* out_qnodes,
+                              uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead, uint32_t* out_leaf_ids, uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots,
+                              float* out_grid, uint32_t* root, uint64_t* cost_now, uint32_t* out_keys, uint32_t* out_order,
+                              uint32_t cap_objs);
+/* Debug entry, host only: the topology of the Morton tree over n_objs objects, which depends on the count alone.
+ * Optional outputs: per node (up to cap_nodes) its four child codes, its height and the node order by height; the first
+ * position of every height in that order (n_heights entries, the last one the node count); the counts, the root's child code,
+ * the stack entries a traversal can need and the deepest leaf.  PT_ERR_UNSUPPORTED when no tree fits the traversal stack.  */
+int pt_debug_bvh_morton_topology(uint32_t n_objs, uint32_t* out_codes, uint32_t* out_height, uint32_t* out_order, uint32_t cap_nodes,
+                                 uint32_t* out_height_first, uint32_t cap_heights, uint32_t* n_nodes, uint32_t* n_heights,
+                                 uint32_t* n_slots, uint32_t* root, uint32_t* stack_need, uint32_t* depth);
 /* The context's device tree copied back into the same outputs (blocking).  PT_ERR_INVALID_ARG when it holds no tree. */
 int pt_debug_bvh_read(PtContext* ctx, uint32_t* out_qnodes, uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead,
                       uint32_t* out_leaf_ids, uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots, float* out_grid,

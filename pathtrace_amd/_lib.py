@@ -194,6 +194,12 @@ SYMBOLS = {
     "pt_scene_update": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
     "pt_scene_refit": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
     "pt_scene_bvh_cost": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_uint32)]),
+    "pt_scene_rebuild": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
+    "pt_debug_bvh_morton_check": (C.c_int, [_P(PtObject), _P(PtObject), C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_uint32),
+                                            C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_float), _P(C.c_uint32), _P(C.c_uint64),
+                                            _P(C.c_uint32), _P(C.c_uint32), C.c_uint32]),
+    "pt_debug_bvh_morton_topology": (C.c_int, [C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, _P(C.c_uint32), C.c_uint32,
+                                               _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "pt_debug_bvh_refit_check": (C.c_int, [_P(PtObject), _P(PtObject), C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_float), _P(C.c_float),
                                            _P(C.c_uint32), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_float), _P(C.c_uint32),
                                            _P(C.c_uint64), _P(C.c_uint64)]),

@@ -128,6 +128,11 @@ class Context:
         check(lib().pt_scene_refit(self._h, objs, len(objs)))
         self._objs = objs
 
+    def scene_rebuild(self, objs):
+        """pt_scene_rebuild: scene_update(objs), and the context then holds the Morton tree of objs, built on the device."""
+        check(lib().pt_scene_rebuild(self._h, objs, len(objs)))
+        self._objs = objs
+
     def bvh_cost(self):
         """pt_scene_bvh_cost -> (cost_now, cost_at_build, refits since the build); PtError without a tree."""
         now, built, refits = C.c_double(0), C.c_double(0), C.c_uint32(0)
@@ -643,6 +648,39 @@ def bvh_refit_check(prev_objs, cur_objs, refit=True):
                                          ns.value, C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now),
                                          _pu64(t.cost_at_build)))
     return t.as_dict()
+
+
+def bvh_morton_check(objs, refit_to=None):
+    """pt_debug_bvh_morton_check (host only): the Morton tree of objs by the host reference of the device-side build
+    (pt_scene_rebuild), verified; refit_to: then refitted to that pose of the same objects by the host refit.  -> dict as bvh_refit_check's (without cost_at_build) plus keys u32[n] (the 30-bit Morton key
+    of every object) and order u32[n] (the object at every sorted position)."""
+    n = len(objs)
+    nn, ns = C.c_uint32(0), C.c_uint32(0)
+    assert refit_to is None or len(refit_to) == n
+    check(lib().pt_debug_bvh_morton_check(objs, refit_to, n, None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None, None, None, 0))
+    t = _BvhArrays(nn.value, ns.value)
+    keys, order = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    check(lib().pt_debug_bvh_morton_check(objs, refit_to, n, _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids), ns.value,
+                                          C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now), _pu(keys), _pu(order), n))
+    d = t.as_dict()
+    del d["cost_at_build"]
+    d.update(keys=keys, order=order)
+    return d
+
+
+def bvh_morton_topology(n):
+    """pt_debug_bvh_morton_topology (host only): the topology of the Morton tree over n objects -> dict: codes u32[nodes,4],
+    node_height u32[nodes], height_order u32[nodes], height_first u32[heights + 1], n_slots, root, stack_need, depth.
+    PtError (PT_ERR_UNSUPPORTED) when no tree over n objects fits the traversal stack."""
+    nn, nh, ns, root, need, depth = (C.c_uint32(0) for _ in range(6))
+    check(lib().pt_debug_bvh_morton_topology(n, None, None, None, 0, None, 0, C.byref(nn), C.byref(nh), C.byref(ns), C.byref(root), C.byref(need),
+                                             C.byref(depth)))
+    codes = np.zeros((nn.value, 4), dtype=np.uint32)
+    height, order = np.zeros(nn.value, dtype=np.uint32), np.zeros(nn.value, dtype=np.uint32)
+    first = np.zeros(nh.value, dtype=np.uint32)
+    check(lib().pt_debug_bvh_morton_topology(n, _pu(codes), _pu(height), _pu(order), nn.value, _pu(first), nh.value, None, None, None, None, None, None))
+    return dict(codes=codes, node_height=height, height_order=order, height_first=first, n_slots=ns.value, root=root.value,
+                stack_need=need.value, depth=depth.value)
 
 
 def bvh_cost_value(sums, grid_cell):

@@ -417,4 +417,124 @@ void refit(Built& t, const float4* shape, const uint32_t* shape_tag, uint32_t n)
     quantise(t);
 }
 
+namespace {
+
+uint32_t ceil_log2(uint64_t x) {             // x >= 1
+    uint32_t l = 0;
+    while (((uint64_t)1 << l) < x) ++l;
+    return l;
+}
+
+struct MortonPlanner {
+    Topology& t;
+    uint32_t n;
+    uint32_t leaf_code(uint32_t j) const { return kLeafBit | ((std::min(kMaxLeaf, n - 4u * j) - 1u) << 28) | (4u * j); }
+    // the arity of a node over m leaves with budget B (0: none fits)
+    static uint32_t arity(uint32_t m, uint32_t budget) {
+        for (uint32_t a = kWidth; a >= 2u; --a)
+            if (a <= m && (a - 1u) + ceil_log2((m + a - 1u) / a) <= budget) return a;
+        return 0u;
+    }
+    // node over the leaves [b, e), e - b >= 2; returns its index; *need = stack entries below the node's parent, *levels = binary levels
+    uint32_t node(uint32_t b, uint32_t e, uint32_t budget, uint32_t* need, uint32_t* levels) {
+        const uint32_t m = e - b, a = arity(m, budget);
+        const uint32_t k = (uint32_t)(t.codes.size() / kWidth);
+        t.codes.insert(t.codes.end(), kWidth, kDone);
+        t.node_height.push_back(0u);
+        uint32_t need_below = 0, levels_below = 0, height = 0;
+        for (uint32_t i = 0; i < a; ++i) {
+            const uint32_t cb = b + (uint32_t)((uint64_t)i * m / a), ce = b + (uint32_t)((uint64_t)(i + 1u) * m / a);
+            uint32_t code;
+            if (ce - cb == 1u) {
+                code = leaf_code(cb);
+            } else {
+                uint32_t nd = 0, lv = 0;
+                code = node(cb, ce, budget - (a - 1u), &nd, &lv);
+                need_below = std::max(need_below, nd);
+                levels_below = std::max(levels_below, lv);
+                height = std::max(height, 1u + t.node_height[code]);
+            }
+            t.codes[kWidth * (size_t)k + i] = code;
+        }
+        t.node_height[k] = height;
+        *need = (a - 1u) + need_below;
+        *levels = (a == 2u ? 1u : 2u) + levels_below;
+        return k;
+    }
+};
+
+}  // namespace
+
+Topology morton_topology(uint32_t n) {
+    Topology t;
+    const uint32_t n_leaves = n / 4u + (n % 4u != 0u);
+    t.n_slots = 4u * n_leaves;
+    MortonPlanner p{t, n};
+    if (n_leaves == 1u) {
+        t.root = p.leaf_code(0);
+    } else if (n_leaves > 1u) {
+        if (!MortonPlanner::arity(n_leaves, kStackDepth - 1u)) { t.ok = false; t.n_slots = 0; return t; }
+        t.codes.reserve(kWidth * (size_t)n_leaves);              // (a tree over L leaves has fewer than L nodes)
+        t.node_height.reserve(n_leaves);
+        uint32_t need = 0, levels = 0;
+        t.root = p.node(0, n_leaves, kStackDepth - 1u, &need, &levels);
+        t.stack_need = 1u + need;
+        t.depth = levels;
+    }
+    // the order by height, as order_by_height() forms it
+    const size_t n_nodes = t.node_height.size();
+    uint32_t top = 0;
+    for (const uint32_t h : t.node_height) top = std::max(top, h);
+    t.height_first.assign(n_nodes ? top + 2u : 1u, 0u);
+    for (size_t k = 0; k < n_nodes; ++k) t.height_first[t.node_height[k] + 1u]++;
+    for (size_t h = 1; h < t.height_first.size(); ++h) t.height_first[h] += t.height_first[h - 1];
+    t.height_order.assign(n_nodes, 0u);
+    std::vector<uint32_t> at(t.height_first.begin(), t.height_first.end());
+    for (size_t k = 0; k < n_nodes; ++k) t.height_order[at[t.node_height[k]]++] = (uint32_t)k;
+    return t;
+}
+
+bool build_morton(Built& out, const float4* shape, const uint32_t* shape_tag, uint32_t n, std::vector<uint32_t>* keys_out, std::vector<uint32_t>* order_out) {
+    out = Built{};
+    Topology t = morton_topology(n);
+    if (keys_out) keys_out->clear();
+    if (order_out) order_out->clear();
+    if (!t.ok) return false;
+    const size_t n_nodes = t.node_height.size();
+    const Bounds bd = scene_bounds(shape, shape_tag, n, n_nodes != 0);
+    std::vector<uint32_t> keys(n, 0u), order(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        order[i] = i;
+        if (n_nodes == 0) continue;                              // no node, no grid: every key is 0
+        float lo[3], hi[3];
+        primitive_box(shape[3 * (size_t)i], shape[3 * (size_t)i + 1], shape[3 * (size_t)i + 2], shape_tag[i] != 0, lo, hi);
+        keys[i] = morton_key(lo, hi, bd.grid_min, bd.grid_cell);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b] || (keys[a] == keys[b] && a < b); });
+    out.leaf_ids.assign(t.n_slots, kDone);
+    for (uint32_t p = 0; p < n; ++p) out.leaf_ids[p] = order[p] | (shape_tag[order[p]] != 0 ? kTriangleBit : 0u);
+    out.leaf_rec.assign(3 * (size_t)t.n_slots, make_float4(0, 0, 0, 0));
+    out.leaf_lead.assign(t.n_slots, make_float4(0, 0, 0, 0));
+    out.leaf_prims = n;
+    out.root = t.root;
+    out.depth = t.depth;
+    out.stack_need = t.stack_need;
+    out.wide.resize(n_nodes);
+    for (size_t k = 0; k < n_nodes; ++k) {
+        WideNode& w = out.wide[k];
+        w.n = 0;
+        for (uint32_t c = 0; c < kWidth; ++c) {
+            w.code[c] = t.codes[kWidth * k + c];
+            if (w.code[c] != kDone) w.n = c + 1u;
+        }
+    }
+    out.node_height = std::move(t.node_height);
+    out.height_order = std::move(t.height_order);
+    out.height_first = std::move(t.height_first);
+    refit(out, shape, shape_tag, n);
+    if (keys_out) *keys_out = std::move(keys);
+    if (order_out) *order_out = std::move(order);
+    return true;
+}
+
 }  // namespace ptbvh

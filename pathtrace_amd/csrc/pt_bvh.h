@@ -125,4 +125,47 @@ Built build(const float4* shape, const uint32_t* shape_tag, uint32_t n);
 // device-side refit (k_bvh_refit_leaves, k_bvh_refit_level).
 void refit(Built& t, const float4* shape, const uint32_t* shape_tag, uint32_t n);
 
+// ---- the Morton build (pt_scene_rebuild): a tree whose TOPOLOGY is a pure function of the object count, so
+// that a build is "order the objects along a Morton curve, write leaf_ids, refit".
+//
+// Leaves: L = ceil(n / 4); leaf j is the slots [4j, 4j + 4) and holds the sorted positions 4j .. min(4j + 4, n) - 1 (padding
+// slots: kDone).  n = 0: no slot, root = kDone; L = 1: root = that leaf's code, no node -- what build() makes of such scenes.
+// Nodes: a node over the leaf range [b, e), m = e - b >= 2, with stack budget B (the root: kStackDepth - 1) has `a` children,
+// a = the largest of 4, 3, 2 with a <= m and (a - 1) + ceil(log2(ceil(m / a))) <= B (what is left covers an all-binary subtree
+// over the largest child); child i is the range [b + floor(i m / a), b + floor((i + 1) m / a)): one leaf = that leaf's code,
+// more = a node with budget B - (a - 1).  Unused child slots carry kDone, a node is numbered before the nodes beneath it.
+struct Topology {
+    bool ok = true;                       // false: no arity fits at the root (L > 2^(kStackDepth - 1)); nothing else is filled in
+    std::vector<uint32_t> codes;          // kWidth child codes per node
+    std::vector<uint32_t> node_height, height_order, height_first;   // as in Built
+    uint32_t root = kDone;
+    uint32_t n_slots = 0;                 // 4 L
+    uint32_t stack_need = 1;
+    uint32_t depth = 0;                   // deepest leaf in binary levels: a node of 2 children counts 1 level, of 3 or 4 counts 2
+};
+Topology morton_topology(uint32_t n);
+
+// The 30-bit Morton key of a box on the grid: per axis k the cell g = floor((((double)lo[k] + (double)hi[k]) * 0.5 -
+// (double)grid_min[k]) / (double)grid_cell[k]) in f64 without contraction, clamped to [0, 65535]; c_k = g >> 6 (10 bits); bit
+// 3 j + k of the key is bit j of c_k.  k_bvh_morton evaluates the same expression on the device.
+__host__ __device__ inline uint32_t morton_key(const float lo[3], const float hi[3], const float grid_min[3], const float grid_cell[3]) {
+#pragma clang fp contract(off)
+    uint32_t key = 0u;
+    for (int k = 0; k < 3; ++k) {
+        double g = __builtin_floor((((double)lo[k] + (double)hi[k]) * 0.5 - (double)grid_min[k]) / (double)grid_cell[k]);
+        g = !(g >= 0.0) ? 0.0 : g > 65535.0 ? 65535.0 : g;
+        const uint32_t c = (uint32_t)g >> 6;
+        for (int j = 0; j < 10; ++j) key |= ((c >> j) & 1u) << (3 * j + k);
+    }
+    return key;
+}
+
+// The tree of the pose: boxes by primitive_box, grid by scene_bounds(.., has_nodes = L > 1), keys by morton_key (all 0 when
+// there is no node, hence no grid), objects ordered ascending by (key, object index), leaf_ids from that order, the topology of
+// morton_topology(n), and everything else -- leaf records, child boxes, qnodes, cost, scene_abs, non_finite -- by refit().
+// keys / order (optional): the key of every object and the sorted object indices.  Returns false, and an empty tree, when
+// morton_topology(n) has no plan.  With a non-finite object the tree is formed all the same (non_finite > 0; callers refuse it).
+bool build_morton(Built& out, const float4* shape, const uint32_t* shape_tag, uint32_t n, std::vector<uint32_t>* keys = nullptr,
+                  std::vector<uint32_t>* order = nullptr);
+
 }  // namespace ptbvh

@@ -111,6 +111,24 @@ struct PtContext {
     uint32_t bvh_n_nodes = 0, bvh_n_slots = 0;
     double bvh_cost_build = 0.0;      // cost of the tree as built, in the grid it was built with
     uint32_t bvh_refits = 0;          // refits since the build
+    // pt_scene_rebuild (the Morton build on the device): the shape tags on the device (uploaded with the scene; no
+    // later call can change them), the (key, index) pairs and digit histograms of the sort, and the topology of
+    // ptbvh::morton_topology(bvh_topo_n) -- child codes and the order by height on the device, the rest here --, kept until
+    // the object count changes.  bvh_is_morton: the code words of bvh_nodes and bvh_order hold that topology (the host builder
+    // writes another).  A device build leaves the cost sums of the tree as built on the device (bvh_cost_built, copied on the
+    // stream behind the last level launch) and the grid cell they were counted in here; bvh_cost_on_device says which holds.
+    DevBuf<uint32_t> shape_tag;
+    DevBuf<uint2> bvh_pairs[2];
+    DevBuf<uint32_t> bvh_hist;
+    DevBuf<uint4> bvh_topo_codes;
+    DevBuf<uint32_t> bvh_topo_order;
+    std::vector<uint32_t> bvh_topo_height_first;
+    int64_t bvh_topo_n = -1;
+    uint32_t bvh_topo_nodes = 0, bvh_topo_slots = 0, bvh_topo_root = 0, bvh_topo_depth = 0;
+    bool bvh_is_morton = false;
+    DevBuf<unsigned long long> bvh_cost_built;
+    float bvh_cost_cell[3] = {0.f, 0.f, 0.f};
+    bool bvh_cost_on_device = false;
     // wavefront state
     DevBuf<float4> xchg;              // k_paths_regen_split: exchange stacks of every wave, one region per lane (stride: sched.xchg_stride)
     DevBuf<float4> queue[4];

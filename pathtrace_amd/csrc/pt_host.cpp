@@ -420,4 +420,81 @@ int pt_debug_bvh_refit_check(const PtObject* prev_objs, const PtObject* cur_objs
     return PT_OK;
 }
 
+int pt_debug_bvh_morton_check(const PtObject* objs, const PtObject* refit_objs, uint32_t n, uint32_t* out_qnodes, uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead,
+                              uint32_t* out_leaf_ids, uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots, float* out_grid, uint32_t* root,
+                              uint64_t* cost_now, uint32_t* out_keys, uint32_t* out_order, uint32_t cap_objs) {
+    if (n && !objs) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_morton_check: null objects");
+    if ((cap_nodes && !out_qnodes) || (cap_slots && (!out_leaf_rec || !out_leaf_lead || !out_leaf_ids)) || (cap_objs && (!out_keys || !out_order)))
+        return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_morton_check: null output array with a non-zero capacity");
+    std::vector<float4> shape, scan;
+    std::vector<uint32_t> tag, keys, order;
+    if (int rc = bvh_records("pt_debug_bvh_morton_check", objs, n, shape, scan, tag)) return rc;
+    ptbvh::Built b;
+    if (!ptbvh::build_morton(b, shape.data(), tag.data(), n, &keys, &order))
+        return fail(PT_ERR_UNSUPPORTED, "pt_debug_bvh_morton_check: no tree over %u objects fits the traversal stack (%u entries)", n, ptbvh::kStackDepth);
+    if (n_nodes) *n_nodes = (uint32_t)b.wide.size();
+    if (n_slots) *n_slots = (uint32_t)b.leaf_ids.size();
+    if (int rc = bvh_verify(b, shape, scan, tag, n)) return rc;
+    if (refit_objs) {                                            // the tree of objs carried to another pose of the same objects
+        for (uint32_t i = 0; i < n; ++i)
+            if (objs[i].shape_tag != refit_objs[i].shape_tag)
+                return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_morton_check: object %u: shape tags %u and %u", i, objs[i].shape_tag, refit_objs[i].shape_tag);
+        if (int rc = bvh_records("pt_debug_bvh_morton_check", refit_objs, n, shape, scan, tag)) return rc;
+        ptbvh::refit(b, shape.data(), tag.data(), n);
+        if (int rc = bvh_verify(b, shape, scan, tag, n)) return rc;
+    }
+    // the order is ascending by (key, index), and slot p holds sorted position p
+    for (uint32_t p = 0; p < n; ++p) {
+        if (p && !(keys[order[p - 1]] < keys[order[p]] || (keys[order[p - 1]] == keys[order[p]] && order[p - 1] < order[p])))
+            return fail(PT_ERR_UNSUPPORTED, "BVH build: sorted positions %u and %u are out of order", p - 1, p);
+        if ((b.leaf_ids[p] & ~ptbvh::kTriangleBit) != order[p]) return fail(PT_ERR_UNSUPPORTED, "BVH build: slot %u does not hold sorted position %u", p, p);
+    }
+    const size_t nn = std::min<size_t>(b.wide.size(), cap_nodes), nsl = std::min<size_t>(b.leaf_ids.size(), cap_slots), no = std::min<size_t>(n, cap_objs);
+    if (nn) std::memcpy(out_qnodes, b.qnodes.data(), nn * 4 * sizeof(uint4));
+    if (nsl) {
+        std::memcpy(out_leaf_rec, b.leaf_rec.data(), nsl * 3 * sizeof(float4));
+        std::memcpy(out_leaf_lead, b.leaf_lead.data(), nsl * sizeof(float4));
+        std::memcpy(out_leaf_ids, b.leaf_ids.data(), nsl * sizeof(uint32_t));
+    }
+    if (no) {
+        std::memcpy(out_keys, keys.data(), no * sizeof(uint32_t));
+        std::memcpy(out_order, order.data(), no * sizeof(uint32_t));
+    }
+    if (out_grid) {
+        for (int k = 0; k < 3; ++k) { out_grid[k] = b.grid_min[k]; out_grid[3 + k] = b.grid_cell[k]; }
+        out_grid[6] = b.scene_abs;
+    }
+    if (root) *root = b.root;
+    for (int k = 0; k < 3; ++k)
+        if (cost_now) cost_now[k] = b.cost[k];
+    return PT_OK;
+}
+
+int pt_debug_bvh_morton_topology(uint32_t n, uint32_t* out_codes, uint32_t* out_height, uint32_t* out_order, uint32_t cap_nodes, uint32_t* out_height_first,
+                                 uint32_t cap_heights, uint32_t* n_nodes, uint32_t* n_heights, uint32_t* n_slots, uint32_t* root, uint32_t* stack_need,
+                                 uint32_t* depth) {
+    if ((cap_nodes && (!out_codes || !out_height || !out_order)) || (cap_heights && !out_height_first))
+        return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_morton_topology: null output array with a non-zero capacity");
+    // (callers ask twice, for the sizes and then for the arrays: the plan of the last count is kept per thread)
+    static thread_local ptbvh::Topology t;
+    static thread_local int64_t t_n = -1;
+    if (t_n != (int64_t)n) { t = ptbvh::morton_topology(n); t_n = (int64_t)n; }
+    if (!t.ok) return fail(PT_ERR_UNSUPPORTED, "pt_debug_bvh_morton_topology: no tree over %u objects fits the traversal stack (%u entries)", n, ptbvh::kStackDepth);
+    const size_t nn = std::min<size_t>(t.node_height.size(), cap_nodes), nh = std::min<size_t>(t.height_first.size(), cap_heights);
+    if (nn) {
+        std::memcpy(out_codes, t.codes.data(), nn * ptbvh::kWidth * sizeof(uint32_t));
+        std::memcpy(out_height, t.node_height.data(), nn * sizeof(uint32_t));
+        std::memcpy(out_order, t.height_order.data(), nn * sizeof(uint32_t));
+    }
+    if (nh) std::memcpy(out_height_first, t.height_first.data(), nh * sizeof(uint32_t));
+    if (n_nodes) *n_nodes = (uint32_t)t.node_height.size();
+    if (n_heights) *n_heights = (uint32_t)t.height_first.size();
+    if (n_slots) *n_slots = t.n_slots;
+    if (root) *root = t.root;
+    if (stack_need) *stack_need = t.stack_need;
+    if (depth) *depth = t.depth;
+    if (nn && nn == t.node_height.size()) { t = ptbvh::Topology{}; t_n = -1; }   // delivered in full: let the memory go
+    return PT_OK;
+}
+
 }  // extern "C"

@@ -360,4 +360,31 @@ struct BvhRefitArgs {
 void launch_bvh_refit_leaves(const BvhRefitArgs& a, hipStream_t st);   // also zeroes the three cost words
 void launch_bvh_refit_level(const BvhRefitArgs& a, uint32_t first, uint32_t count, hipStream_t st);   // nodes order[first, first + count)
 
+// Device-side BVH build (pt_scene_rebuild; rule: ptbvh::build_morton in pt_bvh.h).  What is new beside the refit
+// is which object sits in which leaf slot: the objects ordered by (Morton key, index).  All launches on one stream, in this order:
+//   launch_bvh_morton      pairs[0][i] = (key of object i, i)
+//   launch_bvh_sort        least-significant-digit radix sort of the pairs by key, 8-bit digits, four passes; every pass is
+//                          stable, so equal keys stay in index order.  The result is in pairs[0] again.
+//   launch_bvh_write_ids   leaf_ids from the order (pairs = nullptr: the index order), padding slots kDone with zero records
+//   launch_bvh_codes       (only when the tree arrays hold another topology) the child codes into qnodes[4k + 3]
+// and then the refit launches.  No kernel waits for another; the stream orders them.
+constexpr uint32_t kSortTile = 2048;       // pairs per workgroup and pass
+constexpr uint32_t kSortDigits = 256;
+struct BvhBuildArgs {
+    const float4* shape;      // gather records, 3 float4 per object
+    const uint32_t* tags;     // shape tag per object (0 sphere)
+    uint2* pairs[2];          // (key, object index), ping-pong, n each
+    uint32_t* hist;           // kSortDigits * tiles words: hist[digit * tiles + tile]
+    uint32_t* ids;            // leaf_ids, n_slots
+    float4* rec;              // 3 float4 per leaf slot (zeroed for padding slots)
+    float4* lead;             // 1 float4 per leaf slot (likewise)
+    float grid_min[3], grid_cell[3];
+    uint32_t n, n_slots;
+};
+inline uint32_t bvh_sort_tiles(uint32_t n) { return (n + kSortTile - 1) / kSortTile; }
+void launch_bvh_morton(const BvhBuildArgs& a, hipStream_t st);
+void launch_bvh_sort(const BvhBuildArgs& a, hipStream_t st);
+void launch_bvh_write_ids(const BvhBuildArgs& a, bool sorted, hipStream_t st);
+void launch_bvh_codes(uint4* nodes, const uint4* codes, uint32_t n_nodes, hipStream_t st);
+
 }  // namespace ptk

@@ -696,3 +696,162 @@ void launch_bvh_refit_level(const BvhRefitArgs& a, uint32_t first, uint32_t coun
     if (count) hipLaunchKernelGGL(PTK_IMPL::k_bvh_refit_level, dim3((uint32_t)(((uint64_t)count * 4u + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, first, count);
 }
 }  // namespace ptk
+
+// ------------------------------------------------------------------ device-side BVH build (pt_scene_rebuild)
+// The rule is ptbvh::build_morton (pt_bvh.h) and DESIGN.md 5f.  The topology is a function of the object count and comes from
+// the host once; what these kernels decide is the order of the objects: (Morton key, index) ascending.  The key is the host's
+// expression on the host's boxes (refit_primitive_box) and the host's grid, in correctly rounded f64; the order is total, so a
+// correct sort reproduces the host's leaf_ids bit for bit.
+namespace PTK_IMPL {
+static_assert(kBlock == 256 && kSortDigits == kBlock, "one thread per digit");
+constexpr uint32_t kSortRounds = kSortTile / kBlock;
+constexpr uint32_t kSortWaves = kBlock / 64;
+constexpr uint32_t kScanBlock = 1024;      // k_bvh_sort_scan: one workgroup, four words per thread and step
+
+__global__ void __launch_bounds__(kBlock) k_bvh_morton(BvhBuildArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float4 r0 = a.shape[3 * (size_t)i], r1 = a.shape[3 * (size_t)i + 1], r2 = a.shape[3 * (size_t)i + 2];
+    float lo[3], hi[3];
+    refit_primitive_box(r0, r1, r2, a.tags[i] != 0u, lo, hi);
+    const float gmin[3] = {a.grid_min[0], a.grid_min[1], a.grid_min[2]}, cell[3] = {a.grid_cell[0], a.grid_cell[1], a.grid_cell[2]};
+    a.pairs[0][i] = make_uint2(ptbvh::morton_key(lo, hi, gmin, cell), i);
+}
+
+// One pass of the sort, part 1: how many keys of tile blockIdx.x carry each value of the pass's digit -> hist[digit * tiles + tile]
+__global__ void __launch_bounds__(kBlock) k_bvh_sort_hist(const uint2* __restrict__ in, uint32_t* __restrict__ hist, uint32_t n, uint32_t tiles, uint32_t shift) {
+    __shared__ uint32_t h[kSortDigits];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t base = blockIdx.x * kSortTile;
+    for (uint32_t r = 0; r < kSortRounds; ++r) {
+        const uint32_t i = base + r * kBlock + threadIdx.x;
+        if (i < n) atomicAdd(&h[(in[i].x >> shift) & (kSortDigits - 1u)], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)threadIdx.x * tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// Part 2: the exclusive prefix sum over hist as one array (digit-major: all tiles of digit 0, then of digit 1, ...), in place:
+// afterwards hist[digit * tiles + tile] is where that tile's first key with that digit goes.  One workgroup walks the array
+// with a running carry; `total` = 256 * tiles is a multiple of 4 and the array is 16-byte aligned.
+__global__ void __launch_bounds__(kScanBlock) k_bvh_sort_scan(uint32_t* hist, uint32_t total) {
+    __shared__ uint32_t wsum[kScanBlock / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t carry = 0u;
+    for (uint32_t base = 0; base < total; base += 4u * kScanBlock) {
+        const uint32_t i = base + 4u * threadIdx.x;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (i < total) v = *reinterpret_cast<const uint4*>(hist + i);
+        const uint32_t s = v.x + v.y + v.z + v.w;
+        uint32_t x = s;                                          // inclusive scan over the wave
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t y = __shfl_up(x, off);
+            if (lane >= off) x += y;
+        }
+        if (lane == 63u) wsum[wave] = x;
+        __syncthreads();
+        uint32_t before = 0u, all = 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < kScanBlock / 64; ++w) { const uint32_t t = wsum[w]; before += w < wave ? t : 0u; all += t; }
+        if (i < total) {
+            const uint32_t e = carry + before + x - s;
+            *reinterpret_cast<uint4*>(hist + i) = make_uint4(e, e + v.x, e + v.x + v.y, e + v.x + v.y + v.z);
+        }
+        carry += all;
+        __syncthreads();
+    }
+}
+
+// Part 3: every key of the tile to its place.  The tile is taken in rounds of one key per thread, in index order.  Within a
+// round a key's rank among the keys with the same digit is: the lanes below it in its wave with that digit (the lanes that
+// agree on all eight digit bits, by eight ballots) + the counts of that digit in the waves before (through LDS); base[digit]
+// then moves on by the round's count.  Input order is kept among equal digits: the pass is stable.
+__global__ void __launch_bounds__(kBlock) k_bvh_sort_scatter(const uint2* __restrict__ in, uint2* __restrict__ out, const uint32_t* __restrict__ hist, uint32_t n,
+                                                             uint32_t tiles, uint32_t shift) {
+    __shared__ uint32_t base[kSortDigits];
+    __shared__ uint32_t wcnt[kSortWaves][kSortDigits];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    base[tid] = hist[(size_t)tid * tiles + blockIdx.x];
+#pragma unroll
+    for (uint32_t w = 0; w < kSortWaves; ++w) wcnt[w][tid] = 0u;
+    __syncthreads();
+    const uint32_t first = blockIdx.x * kSortTile;
+    for (uint32_t r = 0; r < kSortRounds; ++r) {
+        if (first + r * kBlock >= n) break;                      // (the same for every thread of the workgroup)
+        const uint32_t i = first + r * kBlock + tid;
+        const bool valid = i < n;
+        const uint2 kv = valid ? in[i] : make_uint2(0u, 0u);
+        const uint32_t d = (kv.x >> shift) & (kSortDigits - 1u);
+        unsigned long long same = __ballot(valid);
+#pragma unroll
+        for (uint32_t b = 0; b < 8u; ++b) {
+            const bool bit = ((d >> b) & 1u) != 0u;
+            const unsigned long long m = __ballot(bit);
+            same &= bit ? m : ~m;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull)), cnt = (uint32_t)__popcll(same);
+        if (valid && rank == 0u) wcnt[wave][d] = cnt;            // one lane per digit present in the wave
+        __syncthreads();
+        if (valid) {
+            uint32_t pos = base[d] + rank;
+#pragma unroll
+            for (uint32_t w = 0; w < kSortWaves; ++w) pos += w < wave ? wcnt[w][d] : 0u;
+            if (pos < n) out[pos] = kv;
+        }
+        __syncthreads();
+        uint32_t add = 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < kSortWaves; ++w) { add += wcnt[w][tid]; wcnt[w][tid] = 0u; }
+        base[tid] += add;
+        __syncthreads();
+    }
+}
+
+// One thread per leaf slot: the object of sorted position p (pairs == nullptr: object p) with its triangle bit; the padding
+// slots behind the last object get the sentinel and zero records, as build() leaves them.
+__global__ void __launch_bounds__(kBlock) k_bvh_write_ids(BvhBuildArgs a, const uint2* pairs) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= a.n_slots) return;
+    uint32_t w = ptbvh::kDone;
+    if (p < a.n) {
+        const uint32_t o = pairs ? pairs[p].y : p;
+        if (o < a.n) w = o | (a.tags[o] != 0u ? ptbvh::kTriangleBit : 0u);
+    }
+    a.ids[p] = w;
+    if (w == ptbvh::kDone) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        a.rec[3 * (size_t)p] = z; a.rec[3 * (size_t)p + 1] = z; a.rec[3 * (size_t)p + 2] = z;
+        a.lead[p] = z;
+    }
+}
+
+// The child codes of the cached topology into the code words of the node array
+__global__ void __launch_bounds__(kBlock) k_bvh_codes(uint4* nodes, const uint4* __restrict__ codes, uint32_t n_nodes) {
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k < n_nodes) nodes[4 * (size_t)k + 3] = codes[k];
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_bvh_morton(const BvhBuildArgs& a, hipStream_t st) {
+    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_bvh_morton, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+void launch_bvh_sort(const BvhBuildArgs& a, hipStream_t st) {
+    if (!a.n) return;
+    const uint32_t tiles = bvh_sort_tiles(a.n);
+    for (uint32_t pass = 0; pass < 4u; ++pass) {                 // an even number of passes: the result is in pairs[0]
+        const uint2* in = a.pairs[pass & 1u];
+        uint2* out = a.pairs[(pass & 1u) ^ 1u];
+        hipLaunchKernelGGL(PTK_IMPL::k_bvh_sort_hist, dim3(tiles), dim3(kBlock), 0, st, in, a.hist, a.n, tiles, 8u * pass);
+        hipLaunchKernelGGL(PTK_IMPL::k_bvh_sort_scan, dim3(1), dim3(PTK_IMPL::kScanBlock), 0, st, a.hist, kSortDigits * tiles);
+        hipLaunchKernelGGL(PTK_IMPL::k_bvh_sort_scatter, dim3(tiles), dim3(kBlock), 0, st, in, out, (const uint32_t*)a.hist, a.n, tiles, 8u * pass);
+    }
+}
+void launch_bvh_write_ids(const BvhBuildArgs& a, bool sorted, hipStream_t st) {
+    if (a.n_slots) hipLaunchKernelGGL(PTK_IMPL::k_bvh_write_ids, dim3((a.n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a, sorted ? (const uint2*)a.pairs[0] : (const uint2*)nullptr);
+}
+void launch_bvh_codes(uint4* nodes, const uint4* codes, uint32_t n_nodes, hipStream_t st) {
+    if (n_nodes) hipLaunchKernelGGL(PTK_IMPL::k_bvh_codes, dim3((n_nodes + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nodes, codes, n_nodes);
+}
+}  // namespace ptk

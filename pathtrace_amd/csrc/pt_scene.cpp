@@ -1,6 +1,6 @@
 // pt_scene.cpp -- the device half of a scene upload: the records of ptscene::build (pt_scene_records.h) into the context's
-// buffers, k_scene_setup over them, the LDS blob; and the BVH of the uploaded scene, built at first use and, for
-// pt_scene_refit, refitted on the device when the objects move.
+// buffers, k_scene_setup over them, the LDS blob; and the BVH of the uploaded scene, built at first use on the host, refitted on
+// the device when the objects move (pt_scene_refit) or built there for the new pose (pt_scene_rebuild).
 #include <cstring>
 
 #include "pt_bvh.h"
@@ -53,6 +53,8 @@ int ensure_bvh(PtContext* c) {
     c->bvh_n_nodes = (uint32_t)b.wide.size();
     c->bvh_n_slots = (uint32_t)b.leaf_ids.size();
     c->bvh_cost_build = ptbvh::cost_value(b.cost, b.grid_cell);
+    c->bvh_cost_on_device = false;
+    c->bvh_is_morton = false;                    // the arrays hold the host builder's topology now
     c->bvh_refits = 0;
     c->view.bvh.nodes = c->bvh_nodes.p; c->view.bvh.rec = c->bvh_rec.p; c->view.bvh.ids = c->bvh_ids.p; c->view.bvh.lead = c->bvh_lead.p;
     c->view.bvh.root = b.root;
@@ -68,8 +70,11 @@ namespace {
 // The body of pt_scene_upload, pt_scene_update and pt_scene_refit (keep_history: same object count and shape tags as the
 // uploaded scene, and the temporal history stays).  The records are built on the host first (ptscene::build); the context is
 // touched only once that has succeeded.  keep_tree (pt_scene_refit): a BVH the context holds is not dropped but refitted on
-// the device to the new records -- same topology, so the tree arrays never cross PCIe again.
-int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, bool keep_history, bool keep_tree = false) {
+// the device to the new records -- same topology, so the tree arrays never cross PCIe again.  kTreeRebuild
+// (pt_scene_rebuild): whether or not a tree is held, the context afterwards holds the Morton tree of the new records, built on
+// the device behind them: keys, sort, leaf ids, then the launches of the refit.
+enum Tree { kTreeDrop, kTreeRefit, kTreeRebuild };
+int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, bool keep_history, Tree tree = kTreeDrop) {
     if (!c || (!objs && n)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (keep_history) {
         if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
@@ -78,6 +83,16 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
             if (objs[i].shape_tag != c->h_shape_tag[i])
                 return fail(PT_ERR_INVALID_ARG, "%s: object %u: shape_tag %u, the uploaded scene has %u", who, i, objs[i].shape_tag, c->h_shape_tag[i]);
     }
+    // the topology of a rebuild is a function of n: planned once per object count, and refused before anything is touched
+    const bool rebuild = tree == kTreeRebuild;
+    ptbvh::Topology topo;
+    const bool new_topo = rebuild && c->bvh_topo_n != (int64_t)n;
+    if (new_topo) {
+        topo = ptbvh::morton_topology(n);
+        if (!topo.ok)
+            return fail(PT_ERR_UNSUPPORTED, "%s: no tree over %u objects fits the traversal stack (%u entries); use pt_scene_update", who, n, ptbvh::kStackDepth);
+    }
+    const uint32_t mt_nodes = new_topo ? (uint32_t)topo.node_height.size() : c->bvh_topo_nodes, mt_slots = new_topo ? topo.n_slots : c->bvh_topo_slots;
     HIP_TRY(hipSetDevice(c->device));
     ptscene::Records rec;
     int rc;
@@ -92,15 +107,38 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
     if ((rc = c->mat_x.ensure(mat.size()))) return rc;
     if ((rc = c->runs.ensure(runs.size() + 1))) return rc;
     if ((rc = c->lights.ensure(lights.size() + 1))) return rc;
+    if (!keep_history && (rc = c->shape_tag.ensure((size_t)n + 1))) return rc;
     // The refit's share of the host work: one pass over the new gather records for the grid, scene_abs and the non-finite rule
     // (ptbvh::scene_bounds: the boxes ptbvh::refit would form).  The kernels reproduce the host's boxes bit for bit, so the
     // grid encloses every box they quantise.
-    const bool refit = keep_tree && c->has_bvh;
+    const bool refit = tree == kTreeRefit && c->has_bvh;
     ptbvh::Bounds bounds;
     if (refit) {
         bounds = ptbvh::scene_bounds(shape.data(), rec.shape_tag.data(), n, c->bvh_n_nodes != 0);
         if (!bounds.non_finite && ((rc = c->bvh_slot_box.ensure(2 * (size_t)c->bvh_n_slots + 1)) || (rc = c->bvh_node_box.ensure(2 * (size_t)c->bvh_n_nodes + 1))))
             return rc;
+    }
+    if (rebuild) {
+        bounds = ptbvh::scene_bounds(shape.data(), rec.shape_tag.data(), n, mt_nodes != 0);
+        if (!bounds.non_finite) {
+            // the tree arrays at the size of the Morton tree (a held tree's arrays may be too small: growing one drops its content)
+            const uint4* nodes0 = c->bvh_nodes.p;
+            const uint32_t* order0 = c->bvh_order.p;
+            if ((rc = c->bvh_nodes.ensure(4 * (size_t)mt_nodes + 2)) || (rc = c->bvh_rec.ensure(3 * (size_t)mt_slots + 3)) ||
+                (rc = c->bvh_ids.ensure((size_t)mt_slots + 4)) || (rc = c->bvh_lead.ensure((size_t)mt_slots + 4)) ||
+                (rc = c->bvh_order.ensure((size_t)mt_nodes + 1)) || (rc = c->bvh_cost.ensure(4)) || (rc = c->bvh_cost_built.ensure(4)) ||
+                (rc = c->bvh_slot_box.ensure(2 * (size_t)mt_slots + 1)) || (rc = c->bvh_node_box.ensure(2 * (size_t)mt_nodes + 1)) ||
+                (rc = c->bvh_pairs[0].ensure((size_t)n + 1)) || (rc = c->bvh_pairs[1].ensure((size_t)n + 1)) ||
+                (rc = c->bvh_hist.ensure((size_t)ptk::kSortDigits * ptk::bvh_sort_tiles(n) + 4)) ||
+                (rc = c->bvh_topo_codes.ensure((size_t)mt_nodes + 1)) || (rc = c->bvh_topo_order.ensure((size_t)mt_nodes + 1))) {
+                c->view.bvh = ptk::BvhView{};        // (an array of the held tree may be gone)
+                c->has_bvh = false;
+                c->bvh_is_morton = false;
+                c->bvh_topo_n = -1;
+                return rc;
+            }
+            if (c->bvh_nodes.p != nodes0 || c->bvh_order.p != order0) c->bvh_is_morton = false;
+        }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));   // the previous scene may still be in use
     ptsched::on_scene(c->sched);                 // statistics of renders of the previous scene do not carry over
@@ -124,6 +162,7 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!runs.empty()) HIP_TRY(hipMemcpy(c->runs.p, runs.data(), runs.size() * sizeof(ptk::Run), hipMemcpyHostToDevice));
     if (!lights.empty()) HIP_TRY(hipMemcpy(c->lights.p, lights.data(), lights.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!keep_history && n) HIP_TRY(hipMemcpy(c->shape_tag.p, rec.shape_tag.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
     c->view.scan = c->scan.p; c->view.shape = c->shape.p; c->view.mat = c->mat.p;
     c->view.runs = c->runs.p; c->view.lights = c->lights.p;
     c->view.blob = nullptr; c->view.blob_f4 = 0;
@@ -144,7 +183,47 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
     c->view.diffuse_only = rec.diffuse_only; c->view.no_mirror = rec.no_mirror; c->view.no_oren_nayar = rec.no_oren_nayar;
     c->split_ok = rec.split_ok;
     std::memcpy(c->scan_counts, rec.scan_counts, sizeof c->scan_counts);
-    if (refit && !bounds.non_finite) {
+    if (rebuild && !bounds.non_finite) {
+        if (new_topo) {
+            // once per object count (the stream is idle here): the child codes and the order by height
+            static_assert(sizeof(uint4) == ptbvh::kWidth * sizeof(uint32_t), "code words of a node");
+            c->bvh_topo_n = -1;
+            c->bvh_is_morton = false;
+            if (mt_nodes) {
+                HIP_TRY(hipMemcpy(c->bvh_topo_codes.p, topo.codes.data(), (size_t)mt_nodes * sizeof(uint4), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(c->bvh_topo_order.p, topo.height_order.data(), (size_t)mt_nodes * sizeof(uint32_t), hipMemcpyHostToDevice));
+            }
+            c->bvh_topo_height_first = std::move(topo.height_first);
+            c->bvh_topo_nodes = mt_nodes; c->bvh_topo_slots = mt_slots; c->bvh_topo_root = topo.root; c->bvh_topo_depth = topo.depth;
+            c->bvh_topo_n = (int64_t)n;
+        }
+        // behind the records and k_scene_setup on the context's stream; nothing here waits for the device
+        ptk::BvhBuildArgs ba{};
+        ba.shape = c->shape.p; ba.tags = c->shape_tag.p;
+        ba.pairs[0] = c->bvh_pairs[0].p; ba.pairs[1] = c->bvh_pairs[1].p; ba.hist = c->bvh_hist.p;
+        ba.ids = c->bvh_ids.p; ba.rec = c->bvh_rec.p; ba.lead = c->bvh_lead.p;
+        ba.n = n; ba.n_slots = mt_slots;
+        for (int k = 0; k < 3; ++k) { ba.grid_min[k] = bounds.grid_min[k]; ba.grid_cell[k] = bounds.grid_cell[k]; }
+        if (mt_nodes) {                          // (without a node there is no grid: every key ties, the order is the index order)
+            ptk::launch_bvh_morton(ba, c->stream);
+            ptk::launch_bvh_sort(ba, c->stream);
+        }
+        ptk::launch_bvh_write_ids(ba, mt_nodes != 0, c->stream);
+        if (!c->bvh_is_morton && mt_nodes) {
+            ptk::launch_bvh_codes(c->bvh_nodes.p, c->bvh_topo_codes.p, mt_nodes, c->stream);
+            HIP_TRY(hipMemcpyAsync(c->bvh_order.p, c->bvh_topo_order.p, (size_t)mt_nodes * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        }
+        if (!mt_slots) HIP_TRY(hipMemsetAsync(c->bvh_cost.p, 0, 3 * sizeof(unsigned long long), c->stream));   // (no leaf launch zeroes them)
+        HIP_TRY(hipGetLastError());
+        c->bvh_is_morton = true;
+        c->bvh_height_first = c->bvh_topo_height_first;
+        c->bvh_n_nodes = mt_nodes; c->bvh_n_slots = mt_slots; c->bvh_depth = c->bvh_topo_depth;
+        c->view.bvh.nodes = c->bvh_nodes.p; c->view.bvh.rec = c->bvh_rec.p; c->view.bvh.ids = c->bvh_ids.p; c->view.bvh.lead = c->bvh_lead.p;
+        c->view.bvh.root = c->bvh_topo_root;
+        c->has_bvh = true;
+        c->bvh_refused = false; c->bvh_failed = false;
+    }
+    if ((refit || rebuild) && !bounds.non_finite) {
         // behind the records and k_scene_setup on the context's stream; nothing here waits for the device
         ptk::BvhRefitArgs ra{};
         ra.shape = c->shape.p; ra.ids = c->bvh_ids.p; ra.rec = c->bvh_rec.p; ra.lead = c->bvh_lead.p;
@@ -158,12 +237,20 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
         HIP_TRY(hipGetLastError());
         for (int k = 0; k < 3; ++k) { c->view.bvh.grid_min[k] = bounds.grid_min[k]; c->view.bvh.grid_cell[k] = bounds.grid_cell[k]; }
         c->view.bvh.scene_abs = bounds.scene_abs;
-        ++c->bvh_refits;
+        if (rebuild) {
+            // the cost of the tree as built stays on the device (pt_scene_bvh_cost reads it there)
+            HIP_TRY(hipMemcpyAsync(c->bvh_cost_built.p, c->bvh_cost.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+            for (int k = 0; k < 3; ++k) c->bvh_cost_cell[k] = bounds.grid_cell[k];
+            c->bvh_cost_on_device = true;
+            c->bvh_refits = 0;
+        } else {
+            ++c->bvh_refits;
+        }
     } else {
         c->view.bvh = ptk::BvhView{};
         c->has_bvh = false;
         // a pose with a NaN/inf coordinate takes the tree away for good, as ensure_bvh would on building it
-        c->bvh_refused = refit && bounds.non_finite;
+        c->bvh_refused = (refit || rebuild) && bounds.non_finite;
         c->bvh_failed = false;
     }
     c->auto_bvh = rec.auto_bvh;
@@ -182,7 +269,8 @@ extern "C" {
 
 int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_upload", c, objs, n, false); }
 int pt_scene_update(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_update", c, objs, n, true); }
-int pt_scene_refit(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_refit", c, objs, n, true, true); }
+int pt_scene_refit(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_refit", c, objs, n, true, kTreeRefit); }
+int pt_scene_rebuild(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_rebuild", c, objs, n, true, kTreeRebuild); }
 
 int pt_scene_bvh_cost(PtContext* c, double* cost_now, double* cost_at_build, uint32_t* refits) {
     if (!c) return fail(PT_ERR_INVALID_ARG, "pt_scene_bvh_cost: null context");
@@ -192,7 +280,14 @@ int pt_scene_bvh_cost(PtContext* c, double* cost_now, double* cost_at_build, uin
     uint64_t now[3];
     HIP_TRY(hipMemcpy(now, c->bvh_cost.p, sizeof now, hipMemcpyDeviceToHost));
     if (cost_now) *cost_now = ptbvh::cost_value(now, c->view.bvh.grid_cell);
-    if (cost_at_build) *cost_at_build = c->bvh_cost_build;
+    if (cost_at_build) {
+        *cost_at_build = c->bvh_cost_build;
+        if (c->bvh_cost_on_device) {             // a device build: the sums it left behind, in the grid of that build
+            uint64_t built[3];
+            HIP_TRY(hipMemcpy(built, c->bvh_cost_built.p, sizeof built, hipMemcpyDeviceToHost));
+            *cost_at_build = ptbvh::cost_value(built, c->bvh_cost_cell);
+        }
+    }
     if (refits) *refits = c->bvh_refits;
     return PT_OK;
 }

@@ -488,7 +488,11 @@ public:
     // The same through pt_scene_refit: a BVH the context holds is refitted on the device to the moved objects instead of
     // dropped and rebuilt on the host.  The film is the same bit for bit; bvh_cost() tells when a rebuild (scene_update()
     // after the next set_object()) is due: {cost now, cost at build, refits since the build}.
-    void scene_refit(int device = 0) { scene(device, true); }
+    void scene_refit(int device = 0) { scene(device, kRefit); }
+    // pt_scene_rebuild: the scene is sent (moved or not) and the context then holds a tree for it, built on the device -- the
+    // repair for a refitted tree whose bvh_cost() has grown, and, right after the first push(), a first build without the
+    // host builder.  The film is the same bit for bit.
+    void scene_rebuild(int device = 0) { scene(device, kRebuild); }
     struct BvhCost { double now, at_build; uint32_t refits; };
     BvhCost bvh_cost() {
         BvhCost b{};
@@ -594,11 +598,13 @@ private:
     PtRenderParams tmp_params_{};
 
     // the context with this World's objects on it (uploaded again after push())
-    PtContext* scene(int device, bool refit = false) {
+    enum SceneMode { kUpdate, kRefit, kRebuild };
+    PtContext* scene(int device, SceneMode mode = kUpdate) {
         check_abi();
         if (!ctx_) check(pt_context_create(device, &ctx_));
         if (!uploaded_) { check(pt_scene_upload(ctx_, objects_.data(), (uint32_t)objects_.size())); uploaded_ = true; }
-        else if (moved_) check((refit ? pt_scene_refit : pt_scene_update)(ctx_, objects_.data(), (uint32_t)objects_.size()));
+        else if (moved_ && mode != kRebuild) check((mode == kRefit ? pt_scene_refit : pt_scene_update)(ctx_, objects_.data(), (uint32_t)objects_.size()));
+        if (mode == kRebuild) check(pt_scene_rebuild(ctx_, objects_.data(), (uint32_t)objects_.size()));
         moved_ = false;
         return ctx_;
     }
