@@ -4,6 +4,8 @@
 //
 //   ./cornell [width height spp [out_prefix [exact_math]]]        defaults: 400 400 64 cornell 0
 //   CORNELL_DENOISE=n: render_denoised with n feature samples (pt_render_denoised) instead of render()
+//   CORNELL_ADAPTIVE_DENOISE=n: render_adaptive_denoised with n feature samples (pt_render_adaptive_denoised): spp is spp_max,
+//                       spp_min 4, spp_step 4, rel_tol 0.1
 //   CORNELL_TEMPORAL=k: k frames of render_denoised_temporal (4 feature samples), frame i at spp_offset i*spp with the camera
 //                       origin moved by (0.01 i, 0.005 i, 0); the files hold the last frame
 #include <algorithm>
@@ -55,7 +57,9 @@ int main(int argc, char** argv) {
                 world.params().spp_offset = i * spp;
                 world.render_denoised_temporal(4);
             }
-        } else if (std::getenv("CORNELL_DENOISE"))   // denoised form: CORNELL_DENOISE = feature samples
+        } else if (std::getenv("CORNELL_ADAPTIVE_DENOISE"))   // adaptive denoised form: CORNELL_ADAPTIVE_DENOISE = feature samples
+            world.render_adaptive_denoised(4, 4, 0.1, 1e-3, (uint32_t)std::atoi(std::getenv("CORNELL_ADAPTIVE_DENOISE")));
+        else if (std::getenv("CORNELL_DENOISE"))   // denoised form: CORNELL_DENOISE = feature samples
             world.render_denoised((uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
         else if (std::getenv("CORNELL_PROGRESSIVE"))      // live-preview form: one line per increment
             world.render_progressive(std::max(1u, spp / 4), [&](uint32_t done) {

@@ -465,6 +465,41 @@ int pt_render_denoised(PtContext* ctx, const PtCamera* cam, const PtRenderParams
                        const PtDenoise* dn, float* out_linear_rgb, uint8_t* out_rgba8, float* out_noisy_linear,
                        float* out_features);
 
+/* The filter guided by each pixel's MEASURED variance (additive to ABI 6).  pt_render_adaptive already measures,
+ * per pixel, the squared standard error of the mean luminance its stopping rule tests; the three entries below hand it to the
+ * a-trous filter in place of the 3x3 guess, which mistakes texture and edges for noise and, after an adaptive render, compares
+ * neighbours with different sample counts.
+ *
+ * pt_denoise_var_device is pt_denoise_device in every rule but "variance": per pixel, var = d_var[p] when that is finite and
+ * >= 0; any other entry (NaN, +-inf, negative: "no measurement") takes the 3x3 population variance of pt_denoise_device.  With
+ * every entry NaN it is bit-identical to pt_denoise_device; with iterations = 0 the plane is not read.  d_var: width*height
+ * floats on the device, 4-byte aligned, in units of L(u)^2 (the DEMODULATED luminance).  Buffers, argument checks,
+ * context-owned planes and asynchrony as pt_denoise_device; PT_ERR_INVALID_ARG also for a NULL d_var.  Needs no scene. */
+int pt_denoise_var_device(PtContext* ctx, uint32_t width, uint32_t height, const float* d_linear_rgb, const float* d_features,
+                          const float* d_var, const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba8);
+/* The variance plane of the last pt_render_adaptive (or pt_render_adaptive_denoised) this context COMPLETED.  The context keeps
+ * that render's per-pixel f64 sums (sum R, sum G, sum B, S1 = sum L, S2 = sum L^2) and sample counts n on the device until
+ * the next adaptive render is asked for; one that returns an error, for whatever reason, leaves none; pt_scene_upload and
+ * the other scene entries do not touch them.  Per pixel, with the albedo of its feature record (pathtrace_amd/csrc/pt_denoise_var.h, f64):
+ *   mean = S1 / n,  var_c = max(0, (S2 - S1 mean) / (n - 1)) / n          (se^2 of the stopping rule)
+ *   c_k = sum_k / n,  a_k = max(albedo_k, 1e-3),  L_u = 0.2126 c_0/a_0 + 0.7152 c_1/a_1 + 0.0722 c_2/a_2
+ *   var_u = var_c (L_u / mean)^2
+ * d_var[p] = (float)var_u when mean > 0 and L_u, var_u are finite; NaN when S1 or S2 is not finite; else 0 (a black pixel,
+ * a miss; a pixel whose samples are all equal, e.g. one that sees the light directly, has var_c = 0).  The squared ratio of
+ * the two mean luminances carries the film's variance to the demodulated colour the filter works on: exact for a grey
+ * albedo, an approximation otherwise.  d_features as pt_render_features_device writes them (16-byte aligned), d_var
+ * width*height floats (4-byte aligned).  Asynchronous on the context's stream; needs no scene.  PT_ERR_INVALID_ARG: the
+ * context holds no completed adaptive render, or width x height is not that render's size.                               */
+int pt_adaptive_variance_device(PtContext* ctx, uint32_t width, uint32_t height, const float* d_features, float* d_var);
+/* One call with HOST buffers (blocking), the adaptive counterpart of pt_render_denoised: pt_render_adaptive(params, ad), then
+ * pt_render_features_device of min(feature_samples, ad->spp_min) samples from params->spp_offset (the samples every pixel
+ * has), pt_adaptive_variance_device and pt_denoise_var_device; bit-identical to calling the four.  out_linear_rgb is the
+ * denoised film; out_rgba8 (of the denoised film), out_noisy_linear (the adaptive render's film), out_spp and out_rel_err
+ * (as pt_render_adaptive) and out_var (the variance plane, width*height floats) may be NULL.  The whole image only.      */
+int pt_render_adaptive_denoised(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, const PtAdaptive* ad,
+                                uint32_t feature_samples, const PtDenoise* dn, float* out_linear_rgb, uint8_t* out_rgba8,
+                                float* out_noisy_linear, uint32_t* out_spp, float* out_rel_err, float* out_var);
+
 /* Temporal accumulation with camera reprojection in front of the a-trous filter (the temporal half of SVGF).
  * Per-frame history that the context owns.  Image W x H, film row y top-down; the frame's camera (o, l, hz, vt) =
  * PtCamera.origin / lower_left / horizontal / vertical, the history's (o', l', hz', vt'); c the linear film, the pixel's

@@ -185,6 +185,11 @@ SYMBOLS = {
     "pt_denoise_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _P(PtDenoise), C.c_void_p, C.c_void_p]),
     "pt_render_denoised": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "pt_denoise_var_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, _P(PtDenoise), C.c_void_p,
+                                        C.c_void_p]),
+    "pt_adaptive_variance_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pt_render_adaptive_denoised": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtAdaptive), C.c_uint32, _P(PtDenoise),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_default_temporal": (None, [_P(PtTemporal)]),
     "pt_temporal_reset": (C.c_int, [C.c_void_p]),
     "pt_denoise_temporal_device": (C.c_int, [C.c_void_p, _P(PtCamera), C.c_void_p, C.c_void_p, _P(PtDenoise), _P(PtTemporal), C.c_void_p,

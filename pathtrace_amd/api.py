@@ -406,6 +406,61 @@ class _ContextFunctions:
                                        noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p)))
         return lin, rgba, noisy, feat
 
+    def denoise_var(self, linear, features, var, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
+        """pt_denoise_var_device: denoise() with a variance plane (f32[H,W], in units of the demodulated luminance squared); an
+        entry that is NaN, infinite or negative takes the filter's own 3x3 variance.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
+        import torch
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        linear = np.ascontiguousarray(linear, dtype=np.float32)
+        features = np.ascontiguousarray(features, dtype=np.float32)
+        var = np.ascontiguousarray(var, dtype=np.float32)
+        H, W = linear.shape[:2]
+        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8) and var.shape == (H, W)
+        dev = torch.device("cuda", self.device)
+        d_lin, d_feat, d_var = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev), torch.from_numpy(var).to(dev)
+        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_denoise_var_device(self._h, W, H, C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()),
+                                          C.c_void_p(d_var.data_ptr()), C.byref(dn), C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(rgba.data_ptr())))
+        self.sync()
+        return out.cpu().numpy(), rgba.cpu().numpy()
+
+    def adaptive_variance(self, features):
+        """pt_adaptive_variance_device: the variance plane of the context's last completed render_adaptive, whose size
+        features (f32[H,W,8]) must have.  -> f32[H,W]"""
+        import torch
+        features = np.ascontiguousarray(features, dtype=np.float32)
+        H, W = features.shape[:2]
+        assert features.shape == (H, W, 8)
+        dev = torch.device("cuda", self.device)
+        d_feat = torch.from_numpy(features).to(dev)
+        var = torch.empty((H, W), dtype=torch.float32, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_adaptive_variance_device(self._h, W, H, C.c_void_p(d_feat.data_ptr()), C.c_void_p(var.data_ptr())))
+        self.sync()
+        return var.cpu().numpy()
+
+    def render_adaptive_denoised(self, cam, params, spp_min, spp_step, rel_tol, abs_floor=1e-3, feature_samples=4, iterations=None,
+                                 sigma_l=None, sigma_n=None, sigma_d=None, extras=True):
+        """pt_render_adaptive_denoised (host buffers, blocking): render_adaptive, the features, the measured variance plane and
+        denoise_var in one call.  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3], spp u32[H,W],
+        rel_err f32[H,W], var f32[H,W]); extras=False asks for the denoised linear film alone (the others are None)."""
+        ad = _lib.PtAdaptive(spp_min, spp_step, rel_tol, abs_floor)
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        H, W = cam.height, cam.width
+        lin = np.empty((H, W, 3), dtype=np.float32)
+        rgba = np.empty((H, W, 4), dtype=np.uint8) if extras else None
+        noisy = np.empty((H, W, 3), dtype=np.float32) if extras else None
+        spp = np.empty((H, W), dtype=np.uint32) if extras else None
+        err = np.empty((H, W), dtype=np.float32) if extras else None
+        var = np.empty((H, W), dtype=np.float32) if extras else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        check(lib().pt_render_adaptive_denoised(self._h, C.byref(cam), C.byref(params), C.byref(ad), feature_samples, C.byref(dn),
+                                                ptr(lin), ptr(rgba), ptr(noisy), ptr(spp), ptr(err), ptr(var)))
+        return lin, rgba, noisy, spp, err, var
+
     def temporal_reset(self):
         """pt_temporal_reset: the next temporal frame starts without history."""
         check(lib().pt_temporal_reset(self._h))

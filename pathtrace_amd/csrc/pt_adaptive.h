@@ -24,13 +24,20 @@ PT_AD_HD double luminance(float r, float g, float b) {
 
 PT_AD_HD bool finite(double v) { return v - v == 0.0; }      // false for NaN and +-inf
 
-// Check at n >= 2 samples.  rel_err = se / max(mean, abs_floor) (NaN when a sum is not finite).
-PT_AD_HD bool check(double s1, double s2, unsigned n, double rel_tol, double abs_floor, double* rel_err) {
+// mean and var / n (= se^2) at n >= 2 samples: the rule's first line, for check() and for pt_denoise_var.h
+PT_AD_HD double mean_var(double s1, double s2, unsigned n, double* mean_out) {
     const double dn = (double)n;
     const double mean = s1 / dn;
     double var = (s2 - s1 * mean) / (dn - 1.0);
     var = var > 0.0 ? var : 0.0;
-    const double se = __builtin_sqrt(var / dn);
+    *mean_out = mean;
+    return var / dn;
+}
+
+// Check at n >= 2 samples.  rel_err = se / max(mean, abs_floor) (NaN when a sum is not finite).
+PT_AD_HD bool check(double s1, double s2, unsigned n, double rel_tol, double abs_floor, double* rel_err) {
+    double mean;
+    const double se = __builtin_sqrt(mean_var(s1, s2, n, &mean));
     const double scale = mean > abs_floor ? mean : abs_floor;
     const bool ok = finite(s1) && finite(s2);
     *rel_err = ok ? se / scale : __builtin_nan("");

@@ -581,14 +581,18 @@ int pt_render_pixels(PtContext* c, const PtCamera* cam, const PtRenderParams* pr
     return PT_OK;
 }
 
+}  // extern "C"
+
 // Adaptive sampling: pass 0 gives every pixel spp_min samples (the full-frame kernels); then, while pixels are left whose
 // last check failed (pt_adaptive.h), k_adaptive_select compacts them into a list and the next pass gives them spp_step more
 // (the regenerating kernel's LIST instances where the scene takes that kernel).  Every pass is a render_impl whose resolve
 // is k_resolve_adaptive.  A pixel's samples are spp_offset .. spp_offset + n - 1 and its f64 sums are added in sample order,
 // so it is bit-identical to a uniform render of that pixel with spp = n.
-int pt_render_adaptive(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad, float* out_linear,
-                       uint8_t* out_rgba, uint32_t* out_spp, float* out_rel_err) {
-    if (!c || !cam || !prm || !ad || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: null argument");
+// The passes are waited for: the film is left in c->host_lin / c->host_rgba and the per-pixel state in
+// c->ad_* on the device.  The context holds that state (ad_valid, ad_width, ad_height) for pt_adaptive_variance_device
+// until the next adaptive render is asked for; one that fails, on its arguments or later, leaves none.
+int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad) {
+    c->ad_valid = false;
     if (ad->spp_min < 2) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: spp_min %u < 2 (the variance needs two samples)", ad->spp_min);
     if (ad->spp_step == 0) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: spp_step must be > 0");
     if (prm->spp < ad->spp_min) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: spp (= spp_max) %u < spp_min %u", prm->spp, ad->spp_min);
@@ -639,10 +643,22 @@ int pt_render_adaptive(PtContext* c, const PtCamera* cam, const PtRenderParams* 
         cur = c->ad_list[which].p; n_cur = n_next; which ^= 1u;
     }
     if ((rc = pt_sync(c))) return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, 3 * (size_t)np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * (size_t)np, hipMemcpyDeviceToHost));
-    if (out_spp) HIP_TRY(hipMemcpy(out_spp, c->ad_count.p, (size_t)np * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_rel_err) HIP_TRY(hipMemcpy(out_rel_err, c->ad_err.p, (size_t)np * sizeof(float), hipMemcpyDeviceToHost));
+    c->ad_valid = true; c->ad_width = cam->width; c->ad_height = cam->height;
+    return PT_OK;
+}
+
+extern "C" {
+
+int pt_render_adaptive(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad, float* out_linear,
+                       uint8_t* out_rgba, uint32_t* out_spp, float* out_rel_err) {
+    if (!c || !cam || !prm || !ad || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: null argument");
+    int rc;
+    if ((rc = render_adaptive_impl(c, cam, prm, ad))) return rc;
+    const size_t np = (size_t)cam->width * cam->height;
+    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
+    if (out_spp) HIP_TRY(hipMemcpy(out_spp, c->ad_count.p, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_rel_err) HIP_TRY(hipMemcpy(out_rel_err, c->ad_err.p, np * sizeof(float), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -182,12 +182,16 @@ struct PtContext {
     DevBuf<uint32_t> ad_count, ad_conv, ad_words;
     DevBuf<float> ad_err;
     DevBuf<uint2> ad_list[2];
+    // ... which stays behind a completed render for pt_adaptive_variance_device: ad_valid with that render's image size
+    bool ad_valid = false;
+    uint32_t ad_width = 0, ad_height = 0;
     // pt_render_features_device: one batch of rays, their hits (ids, records) and the BVH scratch of launch_debug_hit;
     // pt_denoise_device: the two (u, var) ping-pong planes; pt_render_denoised: device staging of the features and the output
     DevBuf<float> ft_rays, ft_t, ft_rec;      // (launch_debug_hit writes t for every ray: ft_t)
     DevBuf<int32_t> ft_ids;
     DevBuf<float4> ft_scratch, dn_plane[2], dn_feat;
     DevBuf<float> dn_lin;
+    DevBuf<float> dn_var;                     // pt_render_adaptive_denoised: device staging of the variance plane
     DevBuf<int32_t> dn_ids;                   // pt_render_denoised_motion: device staging of the ids
     // pt_denoise_temporal_device: two history buffers of 3 float4 per pixel (ptk::TemporalArgs), tm_hist[tm_cur] holds the
     // last frame's when tm_valid; the camera and size of that frame
@@ -232,6 +236,7 @@ struct AdaptivePass {
 // ---- functions that cross files
 int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
                 float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr);   // pt_api.cpp
+int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad);   // pt_api.cpp
 ptk::SceneView view_for(const PtContext* c, uint32_t exact_math);   // pt_scene.cpp
 int ensure_bvh(PtContext* c);                                       // pt_scene.cpp
 hipStream_t pt_internal_stream(PtContext* c);                       // pt_context.cpp

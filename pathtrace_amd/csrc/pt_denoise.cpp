@@ -1,5 +1,6 @@
-// pt_denoise.cpp -- the first-hit feature pass and the denoisers: a-trous, temporal accumulation with camera reprojection,
-// and the motion form that follows moving objects (pt_motion.h); device entries and the host entries that render first.
+// pt_denoise.cpp -- the first-hit feature pass and the denoisers: a-trous (with its own or the adaptive pass's variance),
+// temporal accumulation with camera reprojection, and the motion form that follows moving objects (pt_motion.h); device
+// entries and the host entries that render first.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -223,6 +224,39 @@ int temporal_impl(const char* who, PtContext* c, const PtCamera* cam, const floa
     return denoise_steps(c, a, dn->iterations);
 }
 
+// The filter of pt_denoise_device and pt_denoise_var_device (with_var: k_denoise_init_var and the caller's variance plane in
+// place of k_denoise_init): (u, var) into plane 0, then one k_denoise_step per iteration between the two planes; the last
+// launch writes the film planes.
+int denoise_impl(const char* who, PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,
+                 const float* d_var, bool with_var, const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba) {
+    if (!c || !dn || !d_linear || !d_features || !d_out_linear || (with_var && !d_var)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if (width == 0 || height == 0) return fail(PT_ERR_INVALID_ARG, "%s: image %ux%u", who, width, height);
+    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "%s: %u iterations (at most 16)", who, dn->iterations);
+    if (!(dn->sigma_l >= 0.0f) || !(dn->sigma_n >= 0.0f) || !(dn->sigma_d >= 0.0f) || !std::isfinite(dn->sigma_l) ||
+        !std::isfinite(dn->sigma_n) || !std::isfinite(dn->sigma_d))
+        return fail(PT_ERR_INVALID_ARG, "%s: sigma_l, sigma_n and sigma_d must be finite and >= 0", who);
+    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
+    if ((uintptr_t)d_linear % 4u || (uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u)
+        return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
+    if ((uintptr_t)d_var % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_var must be 4-byte aligned", who);
+    if (d_out_linear == d_linear) return fail(PT_ERR_INVALID_ARG, "%s: the output must not be the input", who);
+    const uint64_t np64 = (uint64_t)width * height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->dn_plane[0].ensure(np64)) || (rc = c->dn_plane[1].ensure(np64))) return rc;
+    ptk::DenoiseArgs a{};
+    a.linear = d_linear; a.feat = reinterpret_cast<const float4*>(d_features);
+    a.out_linear = d_out_linear; a.out_rgba = d_out_rgba;
+    a.width = width; a.height = height;
+    a.sigma_l = dn->sigma_l; a.sigma_n = dn->sigma_n; a.sigma_d = dn->sigma_d;
+    a.dst = c->dn_plane[0].p; a.finalize = dn->iterations == 0;
+    if (with_var) ptk::launch_denoise_init_var(a, d_var, c->stream);
+    else ptk::launch_denoise(a, true, c->stream);
+    HIP_TRY(hipGetLastError());
+    return denoise_steps(c, a, dn->iterations);
+}
+
 }  // namespace
 
 extern "C" {
@@ -237,34 +271,57 @@ int pt_render_feature_ids_device(PtContext* c, const PtCamera* cam, const PtRend
     return features_impl("pt_render_feature_ids_device", c, cam, prm, 1, nullptr, d_ids);
 }
 
-// The filter: k_denoise_init (u, var) into plane 0, then one k_denoise_step per iteration between the two planes; the last
-// launch writes the film planes.
 int pt_denoise_device(PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,
                       const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba) {
-    if (!c || !dn || !d_linear || !d_features || !d_out_linear) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: null argument");
-    if (width == 0 || height == 0) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: image %ux%u", width, height);
-    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: %u iterations (at most 16)", dn->iterations);
-    if (!(dn->sigma_l >= 0.0f) || !(dn->sigma_n >= 0.0f) || !(dn->sigma_d >= 0.0f) || !std::isfinite(dn->sigma_l) ||
-        !std::isfinite(dn->sigma_n) || !std::isfinite(dn->sigma_d))
-        return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: sigma_l, sigma_n and sigma_d must be finite and >= 0");
-    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: d_features must be 16-byte aligned");
-    if ((uintptr_t)d_linear % 4u || (uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u)
-        return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: the film buffers must be 4-byte aligned");
-    if (d_out_linear == d_linear) return fail(PT_ERR_INVALID_ARG, "pt_denoise_device: the output must not be the input");
-    const uint64_t np64 = (uint64_t)width * height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_denoise_device: %llu pixels", (unsigned long long)np64);
+    return denoise_impl("pt_denoise_device", c, width, height, d_linear, d_features, nullptr, false, dn, d_out_linear, d_out_rgba);
+}
+
+int pt_denoise_var_device(PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,
+                          const float* d_var, const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba) {
+    return denoise_impl("pt_denoise_var_device", c, width, height, d_linear, d_features, d_var, true, dn, d_out_linear, d_out_rgba);
+}
+
+// k_adaptive_variance over the state the last completed pt_render_adaptive left in the context
+int pt_adaptive_variance_device(PtContext* c, uint32_t width, uint32_t height, const float* d_features, float* d_var) {
+    if (!c || !d_features || !d_var) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_variance_device: null argument");
+    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_variance_device: d_features must be 16-byte aligned");
+    if ((uintptr_t)d_var % 4u) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_variance_device: d_var must be 4-byte aligned");
+    if (!c->ad_valid) return fail(PT_ERR_INVALID_ARG, "pt_adaptive_variance_device: the context holds no completed pt_render_adaptive");
+    if (width != c->ad_width || height != c->ad_height)
+        return fail(PT_ERR_INVALID_ARG, "pt_adaptive_variance_device: image %ux%u, the last pt_render_adaptive was %ux%u", width, height,
+                    c->ad_width, c->ad_height);
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->dn_plane[0].ensure(np64)) || (rc = c->dn_plane[1].ensure(np64))) return rc;
-    ptk::DenoiseArgs a{};
-    a.linear = d_linear; a.feat = reinterpret_cast<const float4*>(d_features);
-    a.out_linear = d_out_linear; a.out_rgba = d_out_rgba;
-    a.width = width; a.height = height;
-    a.sigma_l = dn->sigma_l; a.sigma_n = dn->sigma_n; a.sigma_d = dn->sigma_d;
-    a.dst = c->dn_plane[0].p; a.finalize = dn->iterations == 0;
-    ptk::launch_denoise(a, true, c->stream);
+    ptk::launch_adaptive_variance(c->ad_sums.p, c->ad_count.p, reinterpret_cast<const float4*>(d_features), width * height, d_var, c->stream);
     HIP_TRY(hipGetLastError());
-    return denoise_steps(c, a, dn->iterations);
+    return PT_OK;
+}
+
+// pt_render_adaptive's passes (the film stays in host_lin), the feature pass, the variance plane, the filter; host buffers, blocking
+int pt_render_adaptive_denoised(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad, uint32_t feature_samples,
+                                const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy, uint32_t* out_spp,
+                                float* out_rel_err, float* out_var) {
+    if (!c || !cam || !prm || !ad || !dn || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive_denoised: null argument");
+    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive_denoised: feature_samples must be > 0");
+    int rc;
+    if ((rc = render_adaptive_impl(c, cam, prm, ad))) return rc;
+    const size_t np = (size_t)cam->width * cam->height;
+    if ((rc = c->dn_feat.ensure(2 * np)) || (rc = c->dn_lin.ensure(3 * np)) || (rc = c->dn_var.ensure(np))) return rc;
+    PtRenderParams p = *prm;
+    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
+    float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
+    uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
+    if ((rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, ad->spp_min), feat)) ||
+        (rc = pt_adaptive_variance_device(c, cam->width, cam->height, feat, c->dn_var.p)) ||
+        (rc = pt_denoise_var_device(c, cam->width, cam->height, c->host_lin.p, feat, c->dn_var.p, dn, c->dn_lin.p, rgba)) ||
+        (rc = pt_sync(c)))
+        return rc;
+    HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
+    if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_spp) HIP_TRY(hipMemcpy(out_spp, c->ad_count.p, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_rel_err) HIP_TRY(hipMemcpy(out_rel_err, c->ad_err.p, np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_var) HIP_TRY(hipMemcpy(out_var, c->dn_var.p, np * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 int pt_render_denoised(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,

@@ -248,6 +248,9 @@ void launch_resolve_adaptive(const AdaptiveResolveArgs& a, hipStream_t st);
 constexpr uint32_t kSelectTile = 1024;
 void launch_adaptive_select(const uint2* pixels, uint32_t n, uint32_t width, const uint32_t* conv, uint32_t* block_counts,
                             uint2* out, uint32_t* out_n, hipStream_t st);
+// The variance plane of pt_denoise_var_device from that state (pt_adaptive_variance_device; the rule in pt_denoise_var.h):
+// sums 5 doubles and count one word per image pixel, feat the 2 float4 feature records; var one float per pixel.
+void launch_adaptive_variance(const double* sums, const uint32_t* count, const float4* feat, uint32_t np, float* var, hipStream_t st);
 
 // Multi-GPU film exchange (pt_multi.cpp): tile -> 16 B per pixel (linear RGB + RGBA8) before the gather, gathered
 // padded tiles -> frame in image order after it.
@@ -308,6 +311,8 @@ struct DenoiseArgs {
     float sigma_l, sigma_n, sigma_d;
 };
 void launch_denoise(const DenoiseArgs& a, bool init, hipStream_t st);
+// init with a variance plane of the caller's (pt_denoise_var_device): var[p] where it is finite and >= 0, else the 3 x 3 variance
+void launch_denoise_init_var(const DenoiseArgs& a, const float* var, hipStream_t st);
 
 // Temporal accumulation in front of the a-trous steps (pt_denoise_temporal_device; rule: include/pathtrace_amd.h PtTemporal).
 // One launch per frame in place of k_denoise_init: reads the film, the features and the history hist_src (null: none), writes

@@ -3,6 +3,7 @@
 // arithmetic mode, so the unit is compiled once, in fast mode (its kernels live in ptk_fast_impl), and serves both modes.
 #include "pt_kernels_scan.h"
 #include "pt_adaptive.h"
+#include "pt_denoise_var.h"
 #if PT_MATH_EXACT
 #error "pt_kernels_film.hip is built once, with -DPT_MATH_EXACT=0"
 #endif
@@ -141,6 +142,18 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_select(const uint2* __restr
     }
     if (blockIdx.x + 1u == gridDim.x && threadIdx.x == 0u) *out_n = base;
 }
+
+// pt_adaptive_variance_device: the state a completed pt_render_adaptive left (sums and count of every image pixel) and the
+// pixel's feature albedo -> the variance plane of pt_denoise_var_device.  The rule is pt_denoise_var.h; one thread per pixel.
+__global__ void __launch_bounds__(kBlock) k_adaptive_variance(const double* __restrict__ sums, const uint32_t* __restrict__ count,
+                                                              const float4* __restrict__ feat, uint32_t np, float* __restrict__ var) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= np) return;
+    const double* const sp = sums + 5 * (size_t)p;
+    const double s[5] = {sp[0], sp[1], sp[2], sp[3], sp[4]};
+    const float4 f0 = feat[2 * (size_t)p];
+    var[p] = ptdv::pixel_variance(s, count[p], f0.x, f0.y, f0.z);
+}
 }  // namespace PTK_IMPL
 namespace ptk {
 void launch_resolve_adaptive(const AdaptiveResolveArgs& a, hipStream_t st) {
@@ -152,6 +165,9 @@ void launch_adaptive_select(const uint2* pixels, uint32_t n, uint32_t width, con
     const dim3 g((n + kSelectTile - 1) / kSelectTile), b(kBlock);
     hipLaunchKernelGGL(PTK_IMPL::k_adaptive_count, g, b, 0, st, pixels, n, width, conv, block_counts);
     hipLaunchKernelGGL(PTK_IMPL::k_adaptive_select, g, b, 0, st, pixels, n, width, conv, (const uint32_t*)block_counts, out, out_n);
+}
+void launch_adaptive_variance(const double* sums, const uint32_t* count, const float4* feat, uint32_t np, float* var, hipStream_t st) {
+    if (np) hipLaunchKernelGGL(PTK_IMPL::k_adaptive_variance, dim3((np + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sums, count, feat, np, var);
 }
 void launch_film_pack(const float* lin, const uint8_t* rgba, uint32_t np, void* packed, hipStream_t st) {
     if (np) hipLaunchKernelGGL(PTK_IMPL::k_film_pack, dim3((np + kBlock - 1) / kBlock), dim3(kBlock), 0, st, lin, rgba, np, (uint4*)packed);
@@ -293,12 +309,28 @@ __global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_step(DenoiseArgs a) {
     if (a.finalize) dn_store(a, p, res.x, res.y, res.z, f0p);
     else a.dst[p] = res;
 }
+// k_denoise_init with the caller's variance plane (pt_denoise_var_device): var = var_in[p] when that is finite and >= 0; a
+// lane whose entry is NaN, infinite or negative walks the 9 taps of dn_spatial_var instead, the others skip them.
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_init_var(DenoiseArgs a, const float* __restrict__ var_in) {
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    const size_t p = (size_t)y * a.width + x;
+    const float3 u = dn_demod(a, p);
+    if (a.finalize) { dn_store(a, p, u.x, u.y, u.z, a.feat[2 * p]); return; }
+    float var = var_in[p];
+    if (!(var >= 0.0f && var <= 3.402823466e+38f)) var = dn_spatial_var(a, x, y);
+    a.dst[p] = make_float4(u.x, u.y, u.z, var);
+}
 }  // namespace PTK_IMPL
 namespace ptk {
 void launch_denoise(const DenoiseArgs& a, bool init, hipStream_t st) {
     const dim3 g((a.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy), b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
     if (init) hipLaunchKernelGGL(PTK_IMPL::k_denoise_init, g, b, 0, st, a);
     else hipLaunchKernelGGL(PTK_IMPL::k_denoise_step, g, b, 0, st, a);
+}
+void launch_denoise_init_var(const DenoiseArgs& a, const float* var, hipStream_t st) {
+    const dim3 g((a.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy), b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
+    hipLaunchKernelGGL(PTK_IMPL::k_denoise_init_var, g, b, 0, st, a, var);
 }
 }  // namespace ptk
 

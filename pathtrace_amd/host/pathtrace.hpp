@@ -457,6 +457,34 @@ public:
             for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
         }
     }
+    // Adaptive form of render_denoised() (pt_render_adaptive_denoised): render_adaptive(), the first-hit features of
+    // min(feature_samples, spp_min) samples, and the a-trous filter guided by each pixel's measured variance (the squared
+    // standard error of the stopping rule) instead of the 3x3 guess.  data / luminance_data hold the denoised film; noisy, spp,
+    // rel_err and var (all optional, y*W+x) receive the adaptive render's film, samples, relative error and the variance plane.
+    void render_adaptive_denoised(uint32_t spp_min, uint32_t spp_step, double rel_tol, double abs_floor = 1e-3, uint32_t feature_samples = 4,
+                                  const PtDenoise* dn = nullptr, std::vector<Vector3>* noisy = nullptr, std::vector<uint32_t>* spp = nullptr,
+                                  std::vector<float>* rel_err = nullptr, std::vector<float>* var = nullptr, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtDenoise d{};
+        if (dn) d = *dn; else pt_default_denoise(&d);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3), raw(noisy ? n * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        if (spp) spp->assign(n, 0u);
+        if (rel_err) rel_err->assign(n, 0.0f);
+        if (var) var->assign(n, 0.0f);
+        PtAdaptive ad{spp_min, spp_step, rel_tol, abs_floor};
+        check(pt_render_adaptive_denoised(ctx_, &camera_.pod(), &p, &ad, feature_samples, &d, lin.data(), rgba.data(), noisy ? raw.data() : nullptr,
+                                          spp ? spp->data() : nullptr, rel_err ? rel_err->data() : nullptr, var ? var->data() : nullptr));
+        unpack(lin, rgba);
+        if (noisy) {
+            noisy->resize(n);
+            for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+        }
+    }
     // Temporal form of render_denoised() (pt_render_denoised_temporal): one frame of a sequence; the history lives in the
     // World's persistent context and follows camera moves (set_camera) by reprojection.  tp: pt_default_temporal when null.
     void render_denoised_temporal(uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, const PtTemporal* tp = nullptr,

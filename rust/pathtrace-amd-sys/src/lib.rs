@@ -257,6 +257,9 @@ extern "C" {
     pub fn pt_default_denoise(out: *mut PtDenoise);
     pub fn pt_denoise_device(ctx: *mut PtContext, width: u32, height: u32, d_linear_rgb: *const f32, d_features: *const f32, dn: *const PtDenoise, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_denoised(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
+    pub fn pt_denoise_var_device(ctx: *mut PtContext, width: u32, height: u32, d_linear_rgb: *const f32, d_features: *const f32, d_var: *const f32, dn: *const PtDenoise, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_adaptive_variance_device(ctx: *mut PtContext, width: u32, height: u32, d_features: *const f32, d_var: *mut f32) -> c_int;
+    pub fn pt_render_adaptive_denoised(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, ad: *const PtAdaptive, feature_samples: u32, dn: *const PtDenoise, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_spp: *mut u32, out_rel_err: *mut f32, out_var: *mut f32) -> c_int;
     pub fn pt_default_temporal(out: *mut PtTemporal);
     pub fn pt_temporal_reset(ctx: *mut PtContext) -> c_int;
     pub fn pt_denoise_temporal_device(ctx: *mut PtContext, cam: *const PtCamera, d_linear_rgb: *const f32, d_features: *const f32, dn: *const PtDenoise, tp: *const PtTemporal, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
