@@ -1,0 +1,52 @@
+// gradient_frames.cpp -- a few frames of the temporal denoiser with temporal gradients through the C++ mirror:
+// World::new(), its first sphere moved by (0.05, 0, 0) per frame with set_object() + scene_update(), every frame one
+// render_denoised_gradient(2) at spp_offset = frame * spp.  Writes <out_prefix>.ppm of the last frame and
+// <out_prefix>_alpha.txt: per frame the pixels whose blend weight was measured (not NaN) and those where it was raised.
+//
+//   ./gradient_frames [width height spp frames [out_prefix]]        defaults: 48 32 2 3 gradient
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+#include "../pathtrace_amd/host/pathtrace.hpp"
+
+using namespace pathtrace;
+
+int main(int argc, char** argv) {
+    const uint32_t w = argc > 4 ? (uint32_t)std::atoi(argv[1]) : 48, h = argc > 4 ? (uint32_t)std::atoi(argv[2]) : 32;
+    const uint32_t spp = argc > 4 ? (uint32_t)std::atoi(argv[3]) : 2, frames = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 3;
+    const std::string prefix = argc > 5 ? argv[5] : "gradient";
+    try {
+        World world = World::new_();
+        world.set_camera(Camera::new_(Vector3(0.0, 0.0, 2.0), w, h, 1.0, 35.0));
+        world.params().spp = spp;
+        size_t ball = 0;
+        while (world.object(ball).pod().shape_tag != PT_SHAPE_SPHERE) ++ball;
+        const PtObject start = world.object(ball).pod();
+        PtTemporal tp{};
+        pt_default_temporal(&tp);
+        FILE* f = std::fopen((prefix + "_alpha.txt").c_str(), "w");
+        if (!f) throw std::runtime_error("cannot create " + prefix + "_alpha.txt");
+        for (uint32_t i = 0; i < frames; ++i) {
+            PtObject o = start;
+            o.shape[0] = start.shape[0] + 0.05 * i;
+            world.set_object(ball, Object::from_pod(o));
+            world.scene_update();
+            world.params().spp_offset = i * spp;
+            std::vector<float> alpha;
+            world.render_denoised_gradient(2, nullptr, &tp, nullptr, nullptr, &alpha);
+            size_t measured = 0, raised = 0;
+            for (float a : alpha) {
+                measured += !std::isnan(a);
+                raised += a > tp.alpha;
+            }
+            std::fprintf(f, "%zu %zu\n", measured, raised);
+        }
+        std::fclose(f);
+        world.write_ppm(prefix + ".ppm");
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

@@ -618,7 +618,8 @@ int pt_render_feature_ids_device(PtContext* ctx, const PtCamera* cam, const PtRe
  *                  pt_denoise_temporal_device stores (the lane is read by nothing else), and what a pixel with id_p < 0 or
  *                  id_p >= n_objs stores.  The two entries may be mixed freely on one context.
  * Needs a scene (PT_ERR_INVALID_ARG without); PT_ERR_UNSUPPORTED for more than 2^24 - 2 objects (id + 1 is kept in f32).
- * Lighting that changes because an object moved is forgotten at the rate alpha, as under a moving camera.               */
+ * Lighting that changes because an object moved is forgotten at the rate alpha, as under a moving camera -- unless the
+ * caller raises alpha where it changed: the temporal gradients below.                                                     */
 int pt_denoise_temporal_motion_device(PtContext* ctx, const PtCamera* cam, const float* d_linear_rgb, const float* d_features,
                                       const int32_t* d_ids, const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear,
                                       uint8_t* d_out_rgba8);
@@ -626,6 +627,66 @@ int pt_denoise_temporal_motion_device(PtContext* ctx, const PtCamera* cam, const
 int pt_render_denoised_motion(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
                               const PtDenoise* dn, const PtTemporal* tp, float* out_linear_rgb, uint8_t* out_rgba8,
                               float* out_noisy_linear, float* out_features, int32_t* out_ids);
+
+/* Temporal gradients: a per-pixel blend weight where the LIGHTING changed (additive to ABI 6; after the temporal
+ * gradient of A-SVGF, Schied et al. 2018).  The motion entry above follows an object's geometry; the shadow it left behind, or
+ * a light that was dimmed, fades at the rate alpha.  These entries measure where the radiance changed and raise alpha there.
+ *
+ * Samples are addressed by (pixel, sample index) and a pixel-list render is bit-identical to the same pixel of a full render,
+ * so the PREVIOUS frame's sample re-traced in the CURRENT scene is one list render with the previous frame's parameters; on
+ * an unchanged scene it reproduces the previous film bit for bit and the gradient is exactly 0.  The rule
+ * (pathtrace_amd/csrc/pt_gradient.h, f64), image W x H:
+ *   strata       3 x 3 blocks, SW = ceil(W/3) by SH = ceil(H/3), clipped at the right and bottom edges; stratum (bx, by) has
+ *                one gradient pixel (min(3 bx + seed % 3, W - 1), min(3 by + (seed / 3) % 3, H - 1)); the caller advances seed
+ *                per frame so that the gradient pixel walks through its block
+ *   record       c_new the gradient pixel's re-traced film, c_old its film in d_prev_linear, L(c) = 0.2126 r + 0.7152 g +
+ *                0.0722 b:  delta = |L_new - L_old|, N = max(L_new, L_old); not finite when either L is not
+ *   per pixel    over the strata (x/3 + i, y/3 + j), |i|, |j| <= radius, inside the grid, row-major: D = sum delta, Nn = sum N;
+ *                lambda = 1 when a record of the window is not finite, min(1, scale D / Nn) when Nn > 0, else 0;
+ *                d_alpha[p] = (float)(alpha_min + lambda (1 - alpha_min));  D = 0 gives alpha_min exactly
+ * pt_default_gradient: radius 1, scale 1.
+ *
+ * pt_temporal_gradient_device: d_prev_linear is the previous frame's noisy linear film (W*H*3 floats on the device, 4-byte
+ * aligned), rendered with prev_params and this camera before the scene changed: the caller guarantees that prev_params holds
+ * that render's spp, spp_offset, depths, integrator, t_min and exact_math (accel and the scheduling fields may differ: the film
+ * never depends on them) and that the camera is the same.  Consecutive frames must use different spp_offsets (temporal
+ * accumulation needs that anyway: equal samples add nothing); the re-trace then shares no sample with the current frame.
+ * d_alpha: W*H floats, 4-byte aligned.  The strata's pixel list, their re-traced film and their records live in context-owned
+ * buffers that grow on first use.  Asynchronous on the context's stream; needs a scene; the whole image only.
+ * PT_ERR_INVALID_ARG: a null argument, a misaligned plane, band_count > 1, radius > 8, a scale that is negative or not finite,
+ * alpha_min outside [0, 1], an image smaller than 2 x 2; the context is then untouched.                                     */
+typedef struct {
+    uint32_t radius;         /* the window: (2 radius + 1)^2 strata around the pixel's, at most 8   */
+    float scale;             /* lambda = min(1, scale D / Nn); finite, >= 0                         */
+} PtGradient;
+void pt_default_gradient(PtGradient* out);
+int pt_temporal_gradient_device(PtContext* ctx, const PtCamera* cam, const PtRenderParams* prev_params, uint32_t seed,
+                                const float* d_prev_linear, const PtGradient* g, float alpha_min, float* d_alpha);
+/* Debug: the strata of the last pt_temporal_gradient_device of a width x height image on this context, copied back (blocking):
+ * out_xy SW*SH (x, y) pairs, out_film SW*SH*3 floats (the re-traced film), out_rec SW*SH (delta, N) pairs of doubles, stratum
+ * by * SW + bx; any may be NULL.                                                                                            */
+int pt_debug_gradient_strata(PtContext* ctx, uint32_t width, uint32_t height, uint32_t* out_xy, float* out_film, double* out_rec);
+/* pt_denoise_temporal_motion_device with a per-pixel blend weight: d_alpha, width*height floats on the device, 4-byte aligned,
+ * not NULL.  Rule 4 alone changes: alpha' = max(alpha_p, 1/n) with alpha_p = d_alpha[p] when that is finite and in [0, 1];
+ * any other entry (NaN, +-inf, out of range: "no measurement") takes tp->alpha.  With every entry NaN it is bit-identical to
+ * the motion entry, with a constant plane c to the motion entry called with tp->alpha = c.  The history layout is the same:
+ * the three temporal entries may be mixed freely on one context.                                                           */
+int pt_denoise_temporal_alpha_device(PtContext* ctx, const PtCamera* cam, const float* d_linear_rgb, const float* d_features,
+                                     const int32_t* d_ids, const float* d_alpha, const PtDenoise* dn, const PtTemporal* tp,
+                                     float* d_out_linear, uint8_t* d_out_rgba8);
+/* One frame with HOST buffers (blocking), the counterpart of pt_render_denoised_motion: the render, the feature pass, the ids
+ * pass, the alpha plane, pt_denoise_temporal_alpha_device; bit-identical to calling the parts.  The alpha plane is
+ * pt_temporal_gradient_device's, with alpha_min = tp->alpha and seed = the number of frames this entry completed on the
+ * context since its previous frame was last dropped, when the context holds a usable PREVIOUS FRAME; otherwise every entry is
+ * NaN and the frame is bit-identical to pt_render_denoised_motion.  The context keeps every completed frame's noisy film on
+ * the device (12 bytes per pixel) with its parameters and camera.  That frame is usable when the size is the same, the camera
+ * is equal field by field and the temporal history is valid; pt_temporal_reset and pt_scene_upload drop it, pt_scene_update,
+ * pt_scene_refit and pt_scene_rebuild keep it.  A moving camera thus gets no gradient (it would need the previous frame's
+ * surface samples projected forward).  out_alpha (width*height floats) and the outputs that may be NULL there may be NULL. */
+int pt_render_denoised_gradient(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
+                                const PtDenoise* dn, const PtTemporal* tp, const PtGradient* g, float* out_linear_rgb,
+                                uint8_t* out_rgba8, float* out_noisy_linear, float* out_features, int32_t* out_ids,
+                                float* out_alpha);
 
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on

@@ -109,6 +109,13 @@ class PtTemporal(C.Structure):
     ]
 
 
+class PtGradient(C.Structure):
+    _fields_ = [
+        ("radius", C.c_uint32),
+        ("scale", C.c_float),
+    ]
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -216,6 +223,14 @@ SYMBOLS = {
                                                     _P(PtTemporal), C.c_void_p, C.c_void_p]),
     "pt_render_denoised_motion": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_default_gradient": (None, [_P(PtGradient)]),
+    "pt_temporal_gradient_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, C.c_void_p, _P(PtGradient), C.c_float,
+                                              C.c_void_p]),
+    "pt_debug_gradient_strata": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_denoise_temporal_alpha_device": (C.c_int, [C.c_void_p, _P(PtCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(PtDenoise),
+                                                   _P(PtTemporal), C.c_void_p, C.c_void_p]),
+    "pt_render_denoised_gradient": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
+                                              _P(PtGradient), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

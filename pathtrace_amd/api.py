@@ -61,6 +61,16 @@ def default_temporal(**over):
     return t
 
 
+def default_gradient(**over):
+    """pt_default_gradient with keyword overrides (None keeps the default)."""
+    g = _lib.PtGradient()
+    lib().pt_default_gradient(C.byref(g))
+    for k, v in over.items():
+        if v is not None:
+            setattr(g, k, v)
+    return g
+
+
 def builtin_scene(scene_id, arg=0):
     """Scenes of SURVEY 8(d): 1 reference Cornell box, 2 ten-sphere Cornell, 4 random spheres (arg = n)."""
     n = C.c_uint32(0)
@@ -552,6 +562,80 @@ class _ContextFunctions:
                                               noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p),
                                               ids.ctypes.data_as(C.c_void_p)))
         return lin, rgba, noisy, feat, ids
+
+    def temporal_gradient(self, cam, prev_params, seed, prev_linear, alpha_min=0.2, radius=None, scale=None):
+        """pt_temporal_gradient_device: the previous frame's samples (prev_params, film prev_linear f32[H,W,3]) re-traced in
+        the current scene on one pixel per 3 x 3 stratum -> the per-pixel blend weight f32[H,W] for denoise_temporal_alpha."""
+        import torch
+        g = default_gradient(radius=radius, scale=scale)
+        prev_linear = np.ascontiguousarray(prev_linear, dtype=np.float32)
+        H, W = cam.height, cam.width
+        assert prev_linear.shape == (H, W, 3)
+        dev = torch.device("cuda", self.device)
+        d_prev = torch.from_numpy(prev_linear).to(dev)
+        alpha = torch.empty((H, W), dtype=torch.float32, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_temporal_gradient_device(self._h, C.byref(cam), C.byref(prev_params), seed, C.c_void_p(d_prev.data_ptr()), C.byref(g),
+                                                alpha_min, C.c_void_p(alpha.data_ptr())))
+        self.sync()
+        return alpha.cpu().numpy()
+
+    def debug_gradient_strata(self, width, height):
+        """pt_debug_gradient_strata: the strata of the last temporal_gradient of a width x height image -> (xy u32[SH,SW,2],
+        re-traced film f32[SH,SW,3], records f64[SH,SW,2] = delta, N)"""
+        SW, SH = (width + 2) // 3, (height + 2) // 3
+        xy = np.empty((SH, SW, 2), dtype=np.uint32)
+        film = np.empty((SH, SW, 3), dtype=np.float32)
+        rec = np.empty((SH, SW, 2), dtype=np.float64)
+        check(lib().pt_debug_gradient_strata(self._h, width, height, xy.ctypes.data_as(C.c_void_p), film.ctypes.data_as(C.c_void_p),
+                                             rec.ctypes.data_as(C.c_void_p)))
+        return xy, film, rec
+
+    def denoise_temporal_alpha(self, cam, linear, features, ids, alpha_plane, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
+                               alpha=None, depth_tol=None, normal_tol=None):
+        """pt_denoise_temporal_alpha_device: denoise_temporal_motion with a per-pixel blend weight (f32[H,W]); an entry that is
+        not finite or outside [0, 1] takes alpha.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
+        import torch
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
+        linear = np.ascontiguousarray(linear, dtype=np.float32)
+        features = np.ascontiguousarray(features, dtype=np.float32)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        alpha_plane = np.ascontiguousarray(alpha_plane, dtype=np.float32)
+        H, W = cam.height, cam.width
+        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8) and ids.shape == (H, W) and alpha_plane.shape == (H, W)
+        dev = torch.device("cuda", self.device)
+        d_lin, d_feat, d_ids = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev), torch.from_numpy(ids).to(dev)
+        d_alpha = torch.from_numpy(alpha_plane).to(dev)
+        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_denoise_temporal_alpha_device(self._h, C.byref(cam), C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()),
+                                                     C.c_void_p(d_ids.data_ptr()), C.c_void_p(d_alpha.data_ptr()), C.byref(dn), C.byref(tp),
+                                                     C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
+        self.sync()
+        return out.cpu().numpy(), rgba.cpu().numpy()
+
+    def render_denoised_gradient(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
+                                 alpha=None, depth_tol=None, normal_tol=None, radius=None, scale=None):
+        """pt_render_denoised_gradient (host buffers, blocking): render_denoised_motion whose blend weight rises where the
+        lighting changed since the previous call.  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3], features
+        f32[H,W,8], ids i32[H,W], alpha f32[H,W]; all NaN without a usable previous frame)"""
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
+        g = default_gradient(radius=radius, scale=scale)
+        H, W = cam.height, cam.width
+        lin = np.empty((H, W, 3), dtype=np.float32)
+        rgba = np.empty((H, W, 4), dtype=np.uint8)
+        noisy = np.empty((H, W, 3), dtype=np.float32)
+        feat = np.empty((H, W, 8), dtype=np.float32)
+        ids = np.empty((H, W), dtype=np.int32)
+        plane = np.empty((H, W), dtype=np.float32)
+        check(lib().pt_render_denoised_gradient(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp), C.byref(g),
+                                                lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
+                                                noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p),
+                                                ids.ctypes.data_as(C.c_void_p), plane.ctypes.data_as(C.c_void_p)))
+        return lin, rgba, noisy, feat, ids, plane
 
     def ray_color(self, params, rays, xy):
         """pt_ray_color = RenderingStrategy::ray_color(world, ray, 0, rng(key xy, sample spp_offset), 1) -> f32[n,3]"""

@@ -210,6 +210,19 @@ struct PtContext {
     Event mo_staged[2];
     uint32_t mo_slot = 0;
     DevBuf<ptk::MotionMap> mo_maps;
+    // pt_temporal_gradient_device: the strata's pixel list, their re-traced film (3 floats per stratum) and records (2 doubles)
+    DevBuf<uint2> gr_list;
+    DevBuf<float> gr_film;
+    DevBuf<double> gr_rec;
+    // pt_render_denoised_gradient: device staging of the alpha plane, and the previous frame -- the noisy film of the last
+    // frame this entry completed (gr_prev, 12 B per pixel) with its parameters and camera, held while gr_valid
+    // (pt_scene_upload and pt_temporal_reset drop it); gr_frame counts the frames completed since it was last dropped (the
+    // seed of the strata)
+    DevBuf<float> gr_alpha, gr_prev;
+    bool gr_valid = false;
+    PtRenderParams gr_params{};
+    PtCamera gr_cam{};
+    uint32_t gr_frame = 0;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "pt_context.h"
+#include "pt_gradient.h"
 #include "pt_motion.h"
 
 namespace {
@@ -157,10 +158,12 @@ int upload_motion_maps(PtContext* c) {
 
 // Temporal accumulation: k_denoise_temporal (history -> (u, var) in plane 0 and the next history), then the a-trous steps of
 // pt_denoise_device.  The arguments are checked before the context is looked at.  d_ids: the motion entry, whose kernel is
-// k_denoise_temporal_motion.  Both store a history frame, and with it the scene's pose becomes the history pose.
+// k_denoise_temporal_motion; with_alpha (a motion entry too): the alpha entry with its per-pixel plane, k_denoise_temporal_alpha.
+// All store a history frame, and with it the scene's pose becomes the history pose.
 int temporal_impl(const char* who, PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features, const int32_t* d_ids,
-                  bool motion, const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba) {
-    if (!cam || !dn || !tp || !d_linear || !d_features || !d_out_linear || (motion && !d_ids))
+                  bool motion, const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba,
+                  const float* d_alpha = nullptr, bool with_alpha = false) {
+    if (!cam || !dn || !tp || !d_linear || !d_features || !d_out_linear || (motion && !d_ids) || (with_alpha && !d_alpha))
         return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (cam->width < 2 || cam->height < 2)
         return fail(PT_ERR_INVALID_ARG, "%s: camera %ux%u: width and height must be >= 2", who, cam->width, cam->height);
@@ -178,6 +181,7 @@ int temporal_impl(const char* who, PtContext* c, const PtCamera* cam, const floa
     const uint64_t np64 = (uint64_t)cam->width * cam->height;
     if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
     if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
+    if ((uintptr_t)d_alpha % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_alpha must be 4-byte aligned", who);
     if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
     if (motion && !c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
     if (motion && c->view.n_objs > (1u << 24) - 2u)
@@ -212,7 +216,13 @@ int temporal_impl(const char* who, PtContext* c, const PtCamera* cam, const floa
     if (motion) {
         ptk::TemporalMotionArgs m{};
         m.t = t; m.ids = d_ids; m.maps = c->mo_maps.p; m.n_objs = c->view.n_objs;
-        ptk::launch_denoise_temporal_motion(m, c->stream);
+        if (with_alpha) {
+            ptk::TemporalAlphaArgs g{};
+            g.m = m; g.alpha = d_alpha;
+            ptk::launch_denoise_temporal_alpha(g, c->stream);
+        } else {
+            ptk::launch_denoise_temporal_motion(m, c->stream);
+        }
     } else {
         ptk::launch_denoise_temporal(t, c->stream);
     }
@@ -334,6 +344,7 @@ int pt_render_denoised(PtContext* c, const PtCamera* cam, const PtRenderParams* 
 int pt_temporal_reset(PtContext* c) {
     if (!c) return fail(PT_ERR_INVALID_ARG, "pt_temporal_reset: null context");
     c->tm_valid = false;
+    c->gr_valid = false; c->gr_frame = 0;
     return PT_OK;
 }
 
@@ -355,6 +366,135 @@ int pt_render_denoised_motion(PtContext* c, const PtCamera* cam, const PtRenderP
                                 out_features, true, out_ids);
 }
 
+
+int pt_denoise_temporal_alpha_device(PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features, const int32_t* d_ids,
+                                     const float* d_alpha, const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear,
+                                     uint8_t* d_out_rgba) {
+    return temporal_impl("pt_denoise_temporal_alpha_device", c, cam, d_linear, d_features, d_ids, true, dn, tp, d_out_linear, d_out_rgba,
+                         d_alpha, true);
+}
+
+void pt_default_gradient(PtGradient* out) {
+    if (!out) return;
+    out->radius = 1;
+    out->scale = 1.0f;
+}
+
+// The strata's pixel list (k_gradient_list), its render with the previous frame's parameters in the current scene (a list
+// render that may take the regenerating kernel, as pt_render_adaptive's passes do), the records and the plane.  The
+// arguments are checked before the context is looked at, and everything the list render checks is checked before the first
+// launch: a refused call leaves the context as it was.
+int pt_temporal_gradient_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prev, uint32_t seed, const float* d_prev,
+                                const PtGradient* g, float alpha_min, float* d_alpha) {
+    const char* const who = "pt_temporal_gradient_device";
+    if (!cam || !prev || !d_prev || !g || !d_alpha) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if ((uintptr_t)d_prev % 4u || (uintptr_t)d_alpha % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_prev_linear and d_alpha must be 4-byte aligned", who);
+    if ((prev->band_count ? prev->band_count : 1) != 1 || prev->band_index != 0)
+        return fail(PT_ERR_INVALID_ARG, "%s: works on the whole image (band_count = 1)", who);
+    if (g->radius > ptgr::kMaxRadius) return fail(PT_ERR_INVALID_ARG, "%s: radius %u (at most %u)", who, g->radius, ptgr::kMaxRadius);
+    if (!(g->scale >= 0.0f) || !std::isfinite(g->scale)) return fail(PT_ERR_INVALID_ARG, "%s: scale must be finite and >= 0", who);
+    if (!(alpha_min >= 0.0f && alpha_min <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "%s: alpha_min %g not in [0, 1]", who, alpha_min);
+    if (cam->width < 2 || cam->height < 2)
+        return fail(PT_ERR_INVALID_ARG, "%s: camera %ux%u: width and height must be >= 2", who, cam->width, cam->height);
+    if (prev->spp == 0) return fail(PT_ERR_INVALID_ARG, "%s: spp must be > 0", who);
+    if (prev->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "%s: unknown integrator %u", who, prev->integrator);
+    if (prev->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "%s: unknown accel %u", who, prev->accel);
+    const uint64_t np64 = (uint64_t)cam->width * cam->height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
+    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t ns = (size_t)ptgr::strata(cam->width) * ptgr::strata(cam->height);
+    int rc;
+    if ((rc = c->gr_list.ensure(ns)) || (rc = c->gr_film.ensure(3 * ns)) || (rc = c->gr_rec.ensure(2 * ns))) return rc;
+    ptk::GradientArgs a{};
+    a.retraced = c->gr_film.p; a.prev = d_prev; a.list = c->gr_list.p; a.rec = c->gr_rec.p; a.alpha = d_alpha;
+    a.width = cam->width; a.height = cam->height; a.seed = seed; a.radius = g->radius;
+    a.scale = g->scale; a.alpha_min = alpha_min;
+    ptk::launch_gradient_list(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    PtRenderParams p = *prev;
+    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
+    ListRender lr;
+    lr.d_pixels = c->gr_list.p; lr.n = (uint32_t)ns; lr.regen = true;
+    if ((rc = render_impl(c, cam, &p, FilmState{}, &lr, c->gr_film.p, nullptr))) return rc;
+    ptk::launch_gradient_strata(a, c->stream);
+    ptk::launch_gradient_alpha(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+// Debug: the strata of the last pt_temporal_gradient_device on this context copied back (blocking): per stratum its gradient
+// pixel, its re-traced film and its record.
+int pt_debug_gradient_strata(PtContext* c, uint32_t width, uint32_t height, uint32_t* out_xy, float* out_film, double* out_rec) {
+    if (!c) return fail(PT_ERR_INVALID_ARG, "pt_debug_gradient_strata: null context");
+    const size_t ns = (size_t)ptgr::strata(width) * ptgr::strata(height);
+    if (ns == 0 || c->gr_list.cap < ns || c->gr_film.cap < 3 * ns || c->gr_rec.cap < 2 * ns)
+        return fail(PT_ERR_INVALID_ARG, "pt_debug_gradient_strata: the context holds no strata of a %ux%u image", width, height);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (out_xy) HIP_TRY(hipMemcpy(out_xy, c->gr_list.p, ns * sizeof(uint2), hipMemcpyDeviceToHost));
+    if (out_film) HIP_TRY(hipMemcpy(out_film, c->gr_film.p, 3 * ns * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_rec) HIP_TRY(hipMemcpy(out_rec, c->gr_rec.p, 2 * ns * sizeof(double), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// pt_render_denoised_motion with the alpha plane between the ids pass and the accumulation, and the frame's noisy film kept
+// for the next call
+int pt_render_denoised_gradient(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
+                                const PtTemporal* tp, const PtGradient* g, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                                float* out_features, int32_t* out_ids, float* out_alpha) {
+    const char* const who = "pt_render_denoised_gradient";
+    if (!c || !cam || !prm || !dn || !tp || !g || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
+        return fail(PT_ERR_INVALID_ARG, "%s: renders the whole image (band_count = 1)", who);
+    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
+    if (g->radius > ptgr::kMaxRadius) return fail(PT_ERR_INVALID_ARG, "%s: radius %u (at most %u)", who, g->radius, ptgr::kMaxRadius);
+    if (!(g->scale >= 0.0f) || !std::isfinite(g->scale)) return fail(PT_ERR_INVALID_ARG, "%s: scale must be finite and >= 0", who);
+    if (!(tp->alpha >= 0.0f && tp->alpha <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "%s: alpha %g not in [0, 1]", who, tp->alpha);
+    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
+    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    const uint64_t np64 = (uint64_t)cam->width * cam->height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    const size_t np = (size_t)np64;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) ||
+        (rc = c->dn_lin.ensure(3 * np)) || (rc = c->dn_ids.ensure(np)) || (rc = c->gr_alpha.ensure(np)))
+        return rc;
+    // the previous frame is usable: this entry completed it, at this size, through this camera, and the history it went into is there
+    bool usable = c->gr_valid && c->tm_valid && c->gr_prev.cap >= 3 * np && c->gr_cam.width == cam->width && c->gr_cam.height == cam->height;
+    for (int k = 0; k < 3; ++k)
+        usable = usable && c->gr_cam.origin[k] == cam->origin[k] && c->gr_cam.lower_left[k] == cam->lower_left[k] &&
+                 c->gr_cam.horizontal[k] == cam->horizontal[k] && c->gr_cam.vertical[k] == cam->vertical[k];
+    c->gr_valid = false;                      // (a frame that fails from here on leaves none)
+    PtRenderParams p = *prm;
+    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
+    float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
+    uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
+    if ((rc = render_impl(c, cam, &p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
+        (rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat)) ||
+        (rc = pt_render_feature_ids_device(c, cam, &p, c->dn_ids.p)))
+        return rc;
+    if (usable) {
+        if ((rc = pt_temporal_gradient_device(c, cam, &c->gr_params, c->gr_frame, c->gr_prev.p, g, tp->alpha, c->gr_alpha.p))) return rc;
+    } else {
+        HIP_TRY(hipMemsetAsync(c->gr_alpha.p, 0xFF, np * sizeof(float), c->stream));      // every entry a NaN: no measurement
+    }
+    if ((rc = pt_denoise_temporal_alpha_device(c, cam, c->host_lin.p, feat, c->dn_ids.p, c->gr_alpha.p, dn, tp, c->dn_lin.p, rgba)) ||
+        (rc = c->gr_prev.ensure(3 * np)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->gr_prev.p, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = pt_sync(c))) return rc;
+    c->gr_valid = true; c->gr_params = p; c->gr_cam = *cam; ++c->gr_frame;
+    HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
+    if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_features) HIP_TRY(hipMemcpy(out_features, feat, 8 * np * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_ids) HIP_TRY(hipMemcpy(out_ids, c->dn_ids.p, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_alpha) HIP_TRY(hipMemcpy(out_alpha, c->gr_alpha.p, np * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
 
 int pt_render_denoised_temporal(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                                 const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,

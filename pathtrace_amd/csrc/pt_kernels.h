@@ -344,6 +344,31 @@ struct TemporalMotionArgs {
 };
 void launch_denoise_temporal_motion(const TemporalMotionArgs& a, hipStream_t st);
 
+// The motion form with a per-pixel blend weight (pt_denoise_temporal_alpha_device; rule 4 of include/pathtrace_amd.h with
+// alpha[p] in place of t.alpha where that entry is finite and in [0, 1]).  k_denoise_temporal_alpha.
+struct TemporalAlphaArgs {
+    TemporalMotionArgs m;
+    const float* alpha;        // width * height
+};
+void launch_denoise_temporal_alpha(const TemporalAlphaArgs& a, hipStream_t st);
+
+// Temporal gradients (pt_temporal_gradient_device; rule: pt_gradient.h).  One gradient pixel per 3 x 3 stratum of the image:
+// launch_gradient_list writes the strata's pixels (the list the re-trace renders), launch_gradient_strata turns the re-traced
+// film (one RGB per stratum, list order) and the previous frame's film into the records (delta, N), launch_gradient_alpha
+// sums every pixel's window of records into its blend weight.
+struct GradientArgs {
+    const float* retraced;     // strata * 3
+    const float* prev;         // width * height * 3
+    uint2* list;               // strata
+    double* rec;               // strata * 2
+    float* alpha;              // width * height
+    uint32_t width, height, seed, radius;
+    float scale, alpha_min;
+};
+void launch_gradient_list(const GradientArgs& a, hipStream_t st);
+void launch_gradient_strata(const GradientArgs& a, hipStream_t st);
+void launch_gradient_alpha(const GradientArgs& a, hipStream_t st);
+
 // Device-side BVH refit (pt_scene_refit; rule: ptbvh::refit in pt_bvh.h, whose arrays these launches reproduce bit for bit).
 // The topology -- ids, child codes, the order of the nodes by height -- stays; leaf records, child boxes and their quantisation
 // are recomputed from the scene's gather records.  The grid is the host's (one O(n) pass over its copy of the records) and

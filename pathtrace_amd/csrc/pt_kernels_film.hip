@@ -887,3 +887,149 @@ void launch_bvh_codes(uint4* nodes, const uint4* codes, uint32_t n_nodes, hipStr
     if (n_nodes) hipLaunchKernelGGL(PTK_IMPL::k_bvh_codes, dim3((n_nodes + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nodes, codes, n_nodes);
 }
 }  // namespace ptk
+
+// ------------------------------------------------------------------ temporal gradients (pt_temporal_gradient_device)
+// The rule is pt_gradient.h and DESIGN.md 5h: one gradient pixel per 3 x 3 stratum, re-traced in the current scene with the
+// previous frame's samples (a pixel-list render between k_gradient_list and k_gradient_strata), its change of luminance
+// spread over a window of strata into every pixel's blend weight.  f64 + - * / and comparisons only: the same bits as the
+// host compiler's.
+#include "pt_gradient.h"
+namespace PTK_IMPL {
+// one thread per stratum: its gradient pixel, list slot = by * SW + bx
+__global__ void __launch_bounds__(kBlock) k_gradient_list(GradientArgs a) {
+    const uint32_t SW = ptgr::strata(a.width), SH = ptgr::strata(a.height);
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= SW * SH) return;
+    uint32_t x, y;
+    ptgr::stratum_pixel(s % SW, s / SW, a.width, a.height, a.seed, &x, &y);
+    a.list[s] = make_uint2(x, y);
+}
+// one thread per stratum: the record of its gradient pixel
+__global__ void __launch_bounds__(kBlock) k_gradient_strata(GradientArgs a) {
+    const uint32_t SW = ptgr::strata(a.width), SH = ptgr::strata(a.height);
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= SW * SH) return;
+    uint32_t x, y;
+    ptgr::stratum_pixel(s % SW, s / SW, a.width, a.height, a.seed, &x, &y);
+    const size_t p = (size_t)y * a.width + x;
+    const float cn[3] = {a.retraced[3 * (size_t)s], a.retraced[3 * (size_t)s + 1], a.retraced[3 * (size_t)s + 2]};
+    const float co[3] = {a.prev[3 * p], a.prev[3 * p + 1], a.prev[3 * p + 2]};
+    double rec[2];
+    ptgr::stratum_record(cn, co, rec);
+    a.rec[2 * (size_t)s] = rec[0]; a.rec[2 * (size_t)s + 1] = rec[1];
+}
+// one thread per pixel: its window of records -> alpha_p
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_gradient_alpha(GradientArgs a) {
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    a.alpha[(size_t)y * a.width + x] = ptgr::pixel_alpha(a.rec, ptgr::strata(a.width), ptgr::strata(a.height), x, y, a.radius, a.scale, a.alpha_min);
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_gradient_list(const GradientArgs& a, hipStream_t st) {
+    const uint32_t ns = ptgr::strata(a.width) * ptgr::strata(a.height);
+    if (ns) hipLaunchKernelGGL(PTK_IMPL::k_gradient_list, dim3((ns + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+void launch_gradient_strata(const GradientArgs& a, hipStream_t st) {
+    const uint32_t ns = ptgr::strata(a.width) * ptgr::strata(a.height);
+    if (ns) hipLaunchKernelGGL(PTK_IMPL::k_gradient_strata, dim3((ns + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+void launch_gradient_alpha(const GradientArgs& a, hipStream_t st) {
+    const dim3 g((a.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy), b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
+    hipLaunchKernelGGL(PTK_IMPL::k_gradient_alpha, g, b, 0, st, a);
+}
+}  // namespace ptk
+
+// ------------------------------------------------------------------ ... and the temporal accumulation that takes them (pt_denoise_temporal_alpha_device)
+// k_denoise_temporal_motion with one change: rule 4's least blend weight is alpha[p] where that entry is finite and in
+// [0, 1], t.alpha elsewhere.  The other statements are that kernel's, in its order (the kernel's own text, as
+// k_denoise_temporal_motion has its own copy of k_denoise_temporal's): with a plane that holds no usable entry, or one
+// constant c against t.alpha = c, the two kernels write the same bits.
+namespace PTK_IMPL {
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_denoise_temporal_alpha(TemporalAlphaArgs g) {
+    const TemporalMotionArgs& m = g.m;
+    const TemporalArgs& a = m.t;
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.dn.width || y >= a.dn.height) return;
+    const int W = (int)a.dn.width, H = (int)a.dn.height;
+    const size_t p = (size_t)y * a.dn.width + x;
+    const float4 f0p = a.dn.feat[2 * p], f1p = a.dn.feat[2 * p + 1];
+    const float3 uc = dn_demod(a.dn, p);
+    const float Lc = dn_lum(uc.x, uc.y, uc.z);
+    // the caller's id: checked against the scene before it indexes the maps
+    const int32_t id = m.ids[p];
+    const bool known = id >= 0 && (uint32_t)id < m.n_objs;
+    const uint32_t flags = known ? m.maps[id].flags : 2u;
+    const bool ident = flags == 1u;
+    const float idf = known ? (float)(id + 1) : 0.0f;       // n_objs <= 2^24 - 2: exact
+    float S = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hm1 = 0.0f, hm2 = 0.0f, hn = 0.0f;
+    if (a.hist_src && f1p.w > 0.0f && !(flags & 2u)) {
+        double xr = x, yr = y, dexp = f1p.w;
+        float nx = f1p.x, ny = f1p.y, nz = f1p.z;
+        bool ok = true;
+        if (!(ident && a.same_camera)) {
+            const MotionMap* mp = ident ? nullptr : m.maps + id;
+            ok = tmm_reproject(a, mp, x, y, f1p.w, xr, yr, dexp);
+            if (mp) {                         // n_h = A n_p, normalised in f64 (n_p when its length is 0)
+                double v[3];
+                for (int k = 0; k < 3; ++k) v[k] = mp->a[3 * k] * (double)f1p.x + mp->a[3 * k + 1] * (double)f1p.y + mp->a[3 * k + 2] * (double)f1p.z;
+                const double len = __builtin_sqrt(tm_dot(v, v));
+                if (len > 0.0) { nx = (float)(v[0] / len); ny = (float)(v[1] / len); nz = (float)(v[2] / len); }
+            }
+        }
+        if (ok && xr > -1.0 && xr < (double)W && yr > -1.0 && yr < (double)H) {
+            const int x0 = (int)__builtin_floor(xr), y0 = (int)__builtin_floor(yr);
+            const float fx = (float)(xr - x0), fy = (float)(yr - y0);
+            const float de = (float)dexp, dmax = a.depth_tol * de;
+            const bool em = f0p.w > 0.0f;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int qx = x0 + i, qy = y0 + j;
+                    const float w = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+                    if (!(w > 0.0f) || qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+                    const size_t q = (size_t)qy * W + qx;
+                    const float4 h2 = a.hist_src[3 * q + 2];
+                    if (!(h2.w > 0.0f) || !(fabsf(h2.w - de) <= dmax)) continue;
+                    if (!(nx * h2.x + ny * h2.y + nz * h2.z >= a.normal_tol)) continue;
+                    const float4 h1 = a.hist_src[3 * q + 1];
+                    if (em != (h1.z > 0.0f)) continue;
+                    if (h1.w != 0.0f && h1.w != idf) {       // another object's history: only when neither object moved
+                        if (!ident || !(h1.w >= 1.0f && h1.w <= (float)m.n_objs)) continue;
+                        if (m.maps[(uint32_t)h1.w - 1u].flags != 1u) continue;
+                    }
+                    const float4 h0 = a.hist_src[3 * q];
+                    S += w;
+                    hr += w * h0.x; hg += w * h0.y; hb += w * h0.z; hm1 += w * h0.w;
+                    hm2 += w * h1.x; hn += w * h1.y;
+                }
+        }
+    }
+    float3 u = uc;
+    float m1 = Lc, m2 = Lc * Lc, n = 1.0f;            // a fresh pixel
+    if (S >= 1e-2f) {
+        const float inv = 1.0f / S;
+        const float ur = hr * inv, ug = hg * inv, ub = hb * inv, um1 = hm1 * inv, um2 = hm2 * inv;
+        n = hn * inv + 1.0f;
+        const float ap = g.alpha[p];
+        const float al = fmaxf(ap >= 0.0f && ap <= 1.0f ? ap : a.alpha, 1.0f / n);      // (NaN fails both comparisons)
+        u = make_float3(ur + al * (uc.x - ur), ug + al * (uc.y - ug), ub + al * (uc.z - ub));
+        m1 = um1 + al * (Lc - um1);
+        m2 = um2 + al * (Lc * Lc - um2);
+    }
+    const float var = n >= 4.0f ? fmaxf(0.0f, m2 - m1 * m1) : dn_spatial_var(a.dn, x, y);
+    a.hist_dst[3 * p] = make_float4(u.x, u.y, u.z, m1);
+    a.hist_dst[3 * p + 1] = make_float4(m2, n, f0p.w, idf);
+    a.hist_dst[3 * p + 2] = f1p;
+    if (a.dn.finalize) dn_store(a.dn, p, u.x, u.y, u.z, f0p);
+    else a.dn.dst[p] = make_float4(u.x, u.y, u.z, var);
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void launch_denoise_temporal_alpha(const TemporalAlphaArgs& a, hipStream_t st) {
+    const dim3 g((a.m.t.dn.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.m.t.dn.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy),
+        b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
+    hipLaunchKernelGGL(PTK_IMPL::k_denoise_temporal_alpha, g, b, 0, st, a);
+}
+}  // namespace ptk

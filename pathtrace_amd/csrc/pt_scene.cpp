@@ -259,7 +259,10 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
     c->has_scene = true;
     c->pose = std::move(rec.pose);
     ++c->pose_gen;
-    if (!keep_history) c->tm_valid = false;   // a new scene starts the temporal history afresh; pt_scene_update keeps it
+    if (!keep_history) {                      // a new scene starts the temporal history afresh; pt_scene_update keeps it
+        c->tm_valid = false;
+        c->gr_valid = false; c->gr_frame = 0;   // ... and pt_render_denoised_gradient's previous frame
+    }
     return PT_OK;
 }
 

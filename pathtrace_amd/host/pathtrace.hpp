@@ -14,6 +14,7 @@
 //   World::render_denoised()  render() + first-hit features + the a-trous denoiser (beyond the reference)
 //   World::render_denoised_temporal()  the same with temporal accumulation over the frames of the persistent context
 //   World::render_denoised_motion()    ... whose history also follows objects moved with set_object() + scene_update()
+//   World::render_denoised_gradient()  ... and forgets faster where the lighting changed (temporal gradients)
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -546,6 +547,32 @@ public:
         if (ids) ids->resize(n);
         check(pt_render_denoised_motion(ctx_, &camera_.pod(), &p, feature_samples, &d, &t, lin.data(), rgba.data(), nullptr, nullptr,
                                         ids ? ids->data() : nullptr));
+        unpack(lin, rgba);
+    }
+    // render_denoised_motion() whose blend weight rises where the lighting changed since the previous call
+    // (pt_render_denoised_gradient): the previous frame's samples are re-traced in the current scene on one pixel per 3 x 3
+    // block.  gr: pt_default_gradient when null.  alpha (optional) receives the per-pixel blend weight, NaN where the call had
+    // no usable previous frame (the first frame, after set_camera(), temporal_reset() or a push()).
+    void render_denoised_gradient(uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, const PtTemporal* tp = nullptr,
+                                  const PtGradient* gr = nullptr, std::vector<int32_t>* ids = nullptr, std::vector<float>* alpha = nullptr,
+                                  int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtDenoise d{};
+        if (dn) d = *dn; else pt_default_denoise(&d);
+        PtTemporal t{};
+        if (tp) t = *tp; else pt_default_temporal(&t);
+        PtGradient g{};
+        if (gr) g = *gr; else pt_default_gradient(&g);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3);
+        std::vector<uint8_t> rgba(n * 4);
+        if (ids) ids->resize(n);
+        if (alpha) alpha->resize(n);
+        check(pt_render_denoised_gradient(ctx_, &camera_.pod(), &p, feature_samples, &d, &t, &g, lin.data(), rgba.data(), nullptr, nullptr,
+                                          ids ? ids->data() : nullptr, alpha ? alpha->data() : nullptr));
         unpack(lin, rgba);
     }
     // the next render_denoised_temporal starts without history (pt_temporal_reset)
