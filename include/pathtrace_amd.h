@@ -590,6 +590,20 @@ int pt_scene_bvh_cost(PtContext* ctx, double* cost_now, double* cost_at_build, u
  * THE FILM NEVER DEPENDS ON THE BUILDER.  A Morton tree is built faster and traversed somewhat slower than the host's SAH
  * tree (docs/EXPERIMENTS.md, "Device-side build"); when to refit, rebuild here or rebuild on the host is the caller's policy. */
 int pt_scene_rebuild(PtContext* ctx, const PtObject* objs, uint32_t n_objs);
+/* Device-side BVH build in a chosen order (additive to ABI 6).
+ *
+ * order = PT_BVH_ORDER_MORTON: pt_scene_rebuild, bit for bit.
+ * order = PT_BVH_ORDER_MEDIAN: pt_scene_rebuild in every respect -- checks, records, statistics, kept history, refits = 0,
+ * cost_at_build, the NaN/inf rule, PT_ERR_UNSUPPORTED for a count without a plan, the topology, the leaf layout and the refit
+ * launches -- except the order in which the objects fill the leaf slots: instead of a sort along a Morton curve, a recursive
+ * median split along the child boundaries of the count-only topology (per step: the widest axis of the objects' grid cells,
+ * the range ordered by (cell on that axis, object index); ptbvh::build_median is the specification).  A node's children are
+ * then boxes side by side instead of stretches of a curve, which roughly halves the tree's cost (docs/EXPERIMENTS.md,
+ * "Device-side build: median order").  The split plan depends on the object count alone: planned on the host once per count
+ * and kept on the device; the call adds no wait for the device.
+ * Any other order: PT_ERR_INVALID_ARG, context untouched.  THE FILM NEVER DEPENDS ON THE ORDER.                            */
+enum { PT_BVH_ORDER_MORTON = 0, PT_BVH_ORDER_MEDIAN = 1 };
+int pt_scene_rebuild_ordered(PtContext* ctx, const PtObject* objs, uint32_t n_objs, uint32_t order);
 /* The motion map of object k, x -> A x + b in f64, carries a point of the current pose to the same material point of the
  * history pose:  sphere (c, r) now, (c', r') then: A = (r'/r) I, b = c' - (r'/r) c;  triangle (v0, v1, v2) now, primed then:
  * e1 = v1 - v0, e2 = v2 - v0, n = (e1 x e2)/|e1 x e2|, E = [e1 e2 n] as columns, A = E' E^-1, b = v0' - A v0.
@@ -781,6 +795,18 @@ int pt_debug_bvh_morton_check(const PtObject* objs, const PtObject* refit_objs, 
 int pt_debug_bvh_morton_topology(uint32_t n_objs, uint32_t* out_codes, uint32_t* out_height, uint32_t* out_order, uint32_t cap_nodes,
                                  uint32_t* out_height_first, uint32_t cap_heights, uint32_t* n_nodes, uint32_t* n_heights,
                                  uint32_t* n_slots, uint32_t* root, uint32_t* stack_need, uint32_t* depth);
+/* pt_debug_bvh_morton_check for the median order (ptbvh::build_median, the specification of pt_scene_rebuild_ordered with
+ * PT_BVH_ORDER_MEDIAN): the same invariants, outputs and errors, except that out_keys holds the three grid cells g of every
+ * object (3 words per object, up to cap_objs objects) and that the order check is "the slots hold the order the rule gives",
+ * by a second evaluation of the steps.                                                                                   */
+int pt_debug_bvh_median_check(const PtObject* objs, const PtObject* refit_objs, uint32_t n_objs, uint32_t* out_qnodes,
+                              uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead, uint32_t* out_leaf_ids, uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots,
+                              float* out_grid, uint32_t* root, uint64_t* cost_now, uint32_t* out_keys, uint32_t* out_order,
+                              uint32_t cap_objs);
+/* Debug entry, host only: the split plan of the median order over n_objs objects, which depends on the count alone.  Optional
+ * outputs: the steps, four words each (level, P, Q, cut), ascending by (level, P), up to cap_steps; their number; and T, the
+ * largest step the device runs inside one workgroup.  PT_ERR_UNSUPPORTED when no tree fits the traversal stack.          */
+int pt_debug_bvh_median_plan(uint32_t n_objs, uint32_t* out_steps, uint32_t cap_steps, uint32_t* n_steps, uint32_t* tile);
 /* The context's device tree copied back into the same outputs (blocking).  PT_ERR_INVALID_ARG when it holds no tree. */
 int pt_debug_bvh_read(PtContext* ctx, uint32_t* out_qnodes, uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead,
                       uint32_t* out_leaf_ids, uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots, float* out_grid,

@@ -207,6 +207,11 @@ SYMBOLS = {
     "pt_scene_refit": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
     "pt_scene_bvh_cost": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_uint32)]),
     "pt_scene_rebuild": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32]),
+    "pt_scene_rebuild_ordered": (C.c_int, [C.c_void_p, _P(PtObject), C.c_uint32, C.c_uint32]),
+    "pt_debug_bvh_median_check": (C.c_int, [_P(PtObject), _P(PtObject), C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_uint32),
+                                            C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_float), _P(C.c_uint32), _P(C.c_uint64),
+                                            _P(C.c_uint32), _P(C.c_uint32), C.c_uint32]),
+    "pt_debug_bvh_median_plan": (C.c_int, [C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
     "pt_debug_bvh_morton_check": (C.c_int, [_P(PtObject), _P(PtObject), C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_uint32),
                                             C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_float), _P(C.c_uint32), _P(C.c_uint64),
                                             _P(C.c_uint32), _P(C.c_uint32), C.c_uint32]),

@@ -138,9 +138,13 @@ class Context:
         check(lib().pt_scene_refit(self._h, objs, len(objs)))
         self._objs = objs
 
-    def scene_rebuild(self, objs):
-        """pt_scene_rebuild: scene_update(objs), and the context then holds the Morton tree of objs, built on the device."""
-        check(lib().pt_scene_rebuild(self._h, objs, len(objs)))
+    def scene_rebuild(self, objs, order="morton"):
+        """pt_scene_rebuild: scene_update(objs), and the context then holds the Morton tree of objs, built on the device.
+        order="median" (or a PT_BVH_ORDER_* number): pt_scene_rebuild_ordered, the tree in median-split order."""
+        if order == "morton":
+            check(lib().pt_scene_rebuild(self._h, objs, len(objs)))
+        else:
+            check(lib().pt_scene_rebuild_ordered(self._h, objs, len(objs), BVH_ORDERS.get(order, order)))
         self._objs = objs
 
     def bvh_cost(self):
@@ -767,6 +771,9 @@ def motion_maps(prev_objs, cur_objs):
     return maps[:, :9].reshape(n, 3, 3).copy(), maps[:, 9:].copy(), flags
 
 
+BVH_ORDERS = {"morton": 0, "median": 1}      # PT_BVH_ORDER_*
+
+
 def bvh_check(objs):
     """pt_debug_bvh_check (host only): build + verify the accel = 1 BVH; returns (depth, nodes, leaf slots)."""
     d, nn, nl = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
@@ -805,6 +812,34 @@ def bvh_morton_check(objs, refit_to=None):
     del d["cost_at_build"]
     d.update(keys=keys, order=order)
     return d
+
+
+def bvh_median_check(objs, refit_to=None):
+    """pt_debug_bvh_median_check (host only): bvh_morton_check for the median order (pt_scene_rebuild_ordered).  -> the same
+    dict with g u32[n,3] (the grid cells of every object) in place of keys."""
+    n = len(objs)
+    nn, ns = C.c_uint32(0), C.c_uint32(0)
+    assert refit_to is None or len(refit_to) == n
+    check(lib().pt_debug_bvh_median_check(objs, refit_to, n, None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None, None, None, 0))
+    t = _BvhArrays(nn.value, ns.value)
+    g, order = np.zeros((n, 3), dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    check(lib().pt_debug_bvh_median_check(objs, refit_to, n, _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids), ns.value,
+                                          C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now), _pu(g), _pu(order), n))
+    d = t.as_dict()
+    del d["cost_at_build"]
+    d.update(g=g, order=order)
+    return d
+
+
+def bvh_median_plan(n):
+    """pt_debug_bvh_median_plan (host only): the split plan of the median order over n objects -> (steps u32[k,4] = (level, P,
+    Q, cut) ascending by (level, P), T = the largest step the device runs inside one workgroup)."""
+    ns, tile = C.c_uint32(0), C.c_uint32(0)
+    check(lib().pt_debug_bvh_median_plan(n, None, 0, C.byref(ns), C.byref(tile)))
+    steps = np.zeros((ns.value, 4), dtype=np.uint32)
+    if ns.value:
+        check(lib().pt_debug_bvh_median_plan(n, _pu(steps), ns.value, None, None))
+    return steps, tile.value
 
 
 def bvh_morton_topology(n):

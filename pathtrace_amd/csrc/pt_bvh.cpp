@@ -494,23 +494,10 @@ Topology morton_topology(uint32_t n) {
     return t;
 }
 
-bool build_morton(Built& out, const float4* shape, const uint32_t* shape_tag, uint32_t n, std::vector<uint32_t>* keys_out, std::vector<uint32_t>* order_out) {
-    out = Built{};
-    Topology t = morton_topology(n);
-    if (keys_out) keys_out->clear();
-    if (order_out) order_out->clear();
-    if (!t.ok) return false;
+namespace {
+// the tree of the count-only topology t over the objects in the given order: leaf_ids, the nodes' codes, and the rest by refit()
+void fill_ordered(Built& out, Topology& t, const std::vector<uint32_t>& order, const float4* shape, const uint32_t* shape_tag, uint32_t n) {
     const size_t n_nodes = t.node_height.size();
-    const Bounds bd = scene_bounds(shape, shape_tag, n, n_nodes != 0);
-    std::vector<uint32_t> keys(n, 0u), order(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        order[i] = i;
-        if (n_nodes == 0) continue;                              // no node, no grid: every key is 0
-        float lo[3], hi[3];
-        primitive_box(shape[3 * (size_t)i], shape[3 * (size_t)i + 1], shape[3 * (size_t)i + 2], shape_tag[i] != 0, lo, hi);
-        keys[i] = morton_key(lo, hi, bd.grid_min, bd.grid_cell);
-    }
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b] || (keys[a] == keys[b] && a < b); });
     out.leaf_ids.assign(t.n_slots, kDone);
     for (uint32_t p = 0; p < n; ++p) out.leaf_ids[p] = order[p] | (shape_tag[order[p]] != 0 ? kTriangleBit : 0u);
     out.leaf_rec.assign(3 * (size_t)t.n_slots, make_float4(0, 0, 0, 0));
@@ -532,7 +519,170 @@ bool build_morton(Built& out, const float4* shape, const uint32_t* shape_tag, ui
     out.height_order = std::move(t.height_order);
     out.height_first = std::move(t.height_first);
     refit(out, shape, shape_tag, n);
+}
+}  // namespace
+
+bool build_morton(Built& out, const float4* shape, const uint32_t* shape_tag, uint32_t n, std::vector<uint32_t>* keys_out, std::vector<uint32_t>* order_out) {
+    out = Built{};
+    Topology t = morton_topology(n);
+    if (keys_out) keys_out->clear();
+    if (order_out) order_out->clear();
+    if (!t.ok) return false;
+    const size_t n_nodes = t.node_height.size();
+    const Bounds bd = scene_bounds(shape, shape_tag, n, n_nodes != 0);
+    std::vector<uint32_t> keys(n, 0u), order(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        order[i] = i;
+        if (n_nodes == 0) continue;                              // no node, no grid: every key is 0
+        float lo[3], hi[3];
+        primitive_box(shape[3 * (size_t)i], shape[3 * (size_t)i + 1], shape[3 * (size_t)i + 2], shape_tag[i] != 0, lo, hi);
+        keys[i] = morton_key(lo, hi, bd.grid_min, bd.grid_cell);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b] || (keys[a] == keys[b] && a < b); });
+    fill_ordered(out, t, order, shape, shape_tag, n);
     if (keys_out) *keys_out = std::move(keys);
+    if (order_out) *order_out = std::move(order);
+    return true;
+}
+
+MedianPlan median_plan(uint32_t n) {
+    MedianPlan pl;
+    const Topology t = morton_topology(n);
+    if (!t.ok) { pl.ok = false; return pl; }
+    while (pl.index_bits < 32u && ((uint64_t)1 << pl.index_bits) < (uint64_t)n) ++pl.index_bits;
+    const size_t n_nodes = t.node_height.size();
+    if (n_nodes == 0) return pl;
+    // the leaf range of every node: a node is numbered before the nodes beneath it
+    std::vector<uint32_t> first(n_nodes), last(n_nodes);
+    const auto child_range = [&](uint32_t code, uint32_t* b, uint32_t* e) {
+        if (code & kLeafBit) { *b = (code & 0x0FFFFFFFu) / 4u; *e = *b + 1u; }
+        else { *b = first[code]; *e = last[code]; }
+    };
+    for (size_t k = n_nodes; k-- > 0;) {
+        uint32_t b = 0, e = 0, e_last = 0;
+        child_range(t.codes[kWidth * k], &first[k], &e_last);
+        for (uint32_t c = 0; c < kWidth && t.codes[kWidth * k + c] != kDone; ++c) { child_range(t.codes[kWidth * k + c], &b, &e); e_last = e; }
+        last[k] = e_last;
+    }
+    // the steps, depth first (the recursion is as deep as the tree's binary levels)
+    struct Planner {
+        const Topology& t;
+        const std::vector<uint32_t>&first, &last;
+        uint32_t n;
+        std::vector<MedianStep>& steps;
+        std::vector<uint32_t>& tile_of;                          // per step: the tile it belongs to (kDone: above T)
+        uint32_t n_tiles = 0;
+        uint32_t pos(uint32_t leaf) const { return (uint32_t)std::min<uint64_t>(4ull * leaf, n); }
+        uint32_t begin(uint32_t code) const { return code & kLeafBit ? (code & 0x0FFFFFFFu) / 4u : first[code]; }
+        void node(uint32_t k, uint32_t level, uint32_t tile) {
+            uint32_t c[kWidth + 1], a = 0;
+            for (; a < kWidth && t.codes[kWidth * (size_t)k + a] != kDone; ++a) c[a] = begin(t.codes[kWidth * (size_t)k + a]);
+            c[a] = last[k];
+            split(k, c, 0, a, level, tile);
+        }
+        void split(uint32_t k, const uint32_t* c, uint32_t lo, uint32_t hi, uint32_t level, uint32_t tile) {
+            if (hi - lo == 1u) {
+                const uint32_t code = t.codes[kWidth * (size_t)k + lo];
+                if (!(code & kLeafBit)) node(code, level, tile);
+                return;
+            }
+            const uint32_t mid = lo + (hi - lo + 1u) / 2u;
+            const MedianStep s{level, pos(c[lo]), pos(c[hi]), pos(c[mid])};
+            if (tile == kDone && s.Q - s.P <= kMedianTile) tile = n_tiles++;   // the highest step of at most T positions
+            steps.push_back(s);
+            tile_of.push_back(tile);
+            split(k, c, lo, mid, level + 1u, tile);
+            split(k, c, mid, hi, level + 1u, tile);
+        }
+    };
+    std::vector<MedianStep> found;
+    std::vector<uint32_t> tile_of;
+    Planner planner{t, first, last, n, found, tile_of};
+    planner.node(t.root, 0u, kDone);
+    std::vector<uint32_t> by(found.size());                      // ascending by (level, P); depth first found them ascending by P per level
+    for (size_t k = 0; k < by.size(); ++k) by[k] = (uint32_t)k;
+    std::stable_sort(by.begin(), by.end(), [&](uint32_t a, uint32_t b) { return found[a].level < found[b].level; });
+    pl.steps.reserve(found.size());
+    for (const uint32_t k : by) pl.steps.push_back(found[k]);
+    // the device's view: levels of steps above T, then the tiles
+    size_t i = 0;
+    while (i < pl.steps.size()) {
+        const uint32_t level = pl.steps[i].level;
+        MedianPlan::Level lv{(uint32_t)pl.group_start.size(), 0u, 0u};
+        uint32_t at = 0;                                         // first position not yet in a group
+        const auto gap_to = [&](uint32_t to) {
+            while (at < to) { pl.group_start.push_back(at); ++lv.groups; at = (uint32_t)std::min<uint64_t>((uint64_t)at + kMedianChunk, to); }
+        };
+        for (; i < pl.steps.size() && pl.steps[i].level == level; ++i) {
+            const MedianStep& s = pl.steps[i];
+            if (s.Q - s.P <= kMedianTile) continue;
+            gap_to(s.P);
+            pl.group_start.push_back(s.P | 0x80000000u);
+            ++lv.groups;
+            at = s.Q;
+        }
+        if (at == 0u) { pl.group_start.resize(lv.first); break; }   // no step of this level is above T, so none beneath is
+        gap_to(n);
+        pl.group_start.push_back(n);
+        while (((uint64_t)1 << lv.bits) < (uint64_t)lv.groups) ++lv.bits;
+        pl.max_groups = std::max(pl.max_groups, lv.groups);
+        pl.levels.push_back(lv);
+    }
+    // the tiles (depth first numbered them ascending by P), each with its steps ascending by (level, P)
+    pl.tiles.assign(planner.n_tiles, make_uint4(0u, 0u, 0u, 0u));
+    for (const uint32_t k : by)
+        if (tile_of[k] != kDone) pl.tiles[tile_of[k]].w++;
+    uint32_t total = 0;
+    for (uint4& tl : pl.tiles) { tl.z = total; total += tl.w; tl.w = 0u; }
+    pl.tile_steps.resize(total);
+    std::vector<uint32_t> level0(planner.n_tiles, 0u);
+    for (const uint32_t k : by) {
+        if (tile_of[k] == kDone) continue;
+        uint4& tl = pl.tiles[tile_of[k]];
+        const MedianStep& s = found[k];
+        if (tl.w == 0u) { tl.x = s.P; tl.y = s.Q; level0[tile_of[k]] = s.level; }   // the tile's own step comes first
+        pl.tile_steps[tl.z + tl.w++] = make_uint2((s.P - tl.x) | ((s.level - level0[tile_of[k]]) << 16), s.Q - tl.x);
+    }
+    return pl;
+}
+
+bool build_median(Built& out, const float4* shape, const uint32_t* shape_tag, uint32_t n, std::vector<uint32_t>* g_out, std::vector<uint32_t>* order_out) {
+    out = Built{};
+    Topology t = morton_topology(n);
+    if (g_out) g_out->clear();
+    if (order_out) order_out->clear();
+    if (!t.ok) return false;
+    const size_t n_nodes = t.node_height.size();
+    const Bounds bd = scene_bounds(shape, shape_tag, n, n_nodes != 0);
+    std::vector<uint32_t> g(3 * (size_t)n, 0u), order(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        order[i] = i;
+        if (n_nodes == 0) continue;                              // no node, no grid, no step
+        float lo[3], hi[3];
+        primitive_box(shape[3 * (size_t)i], shape[3 * (size_t)i + 1], shape[3 * (size_t)i + 2], shape_tag[i] != 0, lo, hi);
+        for (int k = 0; k < 3; ++k) g[3 * (size_t)i + k] = grid_coord(lo, hi, bd.grid_min, bd.grid_cell, k);
+    }
+    const MedianPlan pl = median_plan(n);
+    for (const MedianStep& s : pl.steps) {                       // by level: a parent before its children
+        uint32_t gmin[3] = {65535u, 65535u, 65535u}, gmax[3] = {0u, 0u, 0u};
+        for (uint32_t p = s.P; p < s.Q; ++p)
+            for (int k = 0; k < 3; ++k) {
+                const uint32_t v = g[3 * (size_t)order[p] + k];
+                gmin[k] = std::min(gmin[k], v); gmax[k] = std::max(gmax[k], v);
+            }
+        int axis = 0;
+        double widest = (double)(gmax[0] - gmin[0]) * (double)bd.grid_cell[0];
+        for (int k = 1; k < 3; ++k) {
+            const double w = (double)(gmax[k] - gmin[k]) * (double)bd.grid_cell[k];
+            if (w > widest) { widest = w; axis = k; }
+        }
+        std::sort(order.begin() + s.P, order.begin() + s.Q, [&](uint32_t a, uint32_t b) {
+            const uint32_t ga = g[3 * (size_t)a + axis], gb = g[3 * (size_t)b + axis];
+            return ga < gb || (ga == gb && a < b);
+        });
+    }
+    fill_ordered(out, t, order, shape, shape_tag, n);
+    if (g_out) *g_out = std::move(g);
     if (order_out) *order_out = std::move(order);
     return true;
 }

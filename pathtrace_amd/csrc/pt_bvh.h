@@ -145,16 +145,20 @@ struct Topology {
 };
 Topology morton_topology(uint32_t n);
 
-// The 30-bit Morton key of a box on the grid: per axis k the cell g = floor((((double)lo[k] + (double)hi[k]) * 0.5 -
-// (double)grid_min[k]) / (double)grid_cell[k]) in f64 without contraction, clamped to [0, 65535]; c_k = g >> 6 (10 bits); bit
-// 3 j + k of the key is bit j of c_k.  k_bvh_morton evaluates the same expression on the device.
-__host__ __device__ inline uint32_t morton_key(const float lo[3], const float hi[3], const float grid_min[3], const float grid_cell[3]) {
+// The grid coordinate of a box on axis k: the cell of its centre, g = floor((((double)lo[k] + (double)hi[k]) * 0.5 -
+// (double)grid_min[k]) / (double)grid_cell[k]) in f64 without contraction, clamped to [0, 65535].
+__host__ __device__ inline uint32_t grid_coord(const float lo[3], const float hi[3], const float grid_min[3], const float grid_cell[3], int k) {
 #pragma clang fp contract(off)
+    double g = __builtin_floor((((double)lo[k] + (double)hi[k]) * 0.5 - (double)grid_min[k]) / (double)grid_cell[k]);
+    g = !(g >= 0.0) ? 0.0 : g > 65535.0 ? 65535.0 : g;
+    return (uint32_t)g;
+}
+// The 30-bit Morton key of a box on the grid: per axis k, c_k = grid_coord >> 6 (10 bits); bit 3 j + k of the key is bit j of
+// c_k.  k_bvh_morton evaluates the same expression on the device.
+__host__ __device__ inline uint32_t morton_key(const float lo[3], const float hi[3], const float grid_min[3], const float grid_cell[3]) {
     uint32_t key = 0u;
     for (int k = 0; k < 3; ++k) {
-        double g = __builtin_floor((((double)lo[k] + (double)hi[k]) * 0.5 - (double)grid_min[k]) / (double)grid_cell[k]);
-        g = !(g >= 0.0) ? 0.0 : g > 65535.0 ? 65535.0 : g;
-        const uint32_t c = (uint32_t)g >> 6;
+        const uint32_t c = grid_coord(lo, hi, grid_min, grid_cell, k) >> 6;
         for (int j = 0; j < 10; ++j) key |= ((c >> j) & 1u) << (3 * j + k);
     }
     return key;
@@ -166,6 +170,45 @@ __host__ __device__ inline uint32_t morton_key(const float lo[3], const float hi
 // keys / order (optional): the key of every object and the sorted object indices.  Returns false, and an empty tree, when
 // morton_topology(n) has no plan.  With a non-finite object the tree is formed all the same (non_finite > 0; callers refuse it).
 bool build_morton(Built& out, const float4* shape, const uint32_t* shape_tag, uint32_t n, std::vector<uint32_t>* keys = nullptr,
+                  std::vector<uint32_t>* order = nullptr);
+
+// ---- the median build (pt_scene_rebuild_ordered, PT_BVH_ORDER_MEDIAN): the Morton build with another order.  The
+// topology, the leaves and the refit are those above; the objects reach their positions by a recursive median split along the
+// nodes' child boundaries instead of a sort along a curve, so that a node's children are boxes side by side.
+//
+// The split plan is a pure function of n.  A node over the leaf range [b, e) has the child leaf boundaries c_0 = b < .. < c_a = e.
+// split(c_lo .. c_hi) over more than one child is one step: its positions are [P, Q) = [min(4 c_lo, n), min(4 c_hi, n)), its cut
+// is the boundary c_mid, mid = lo + ceil((hi - lo) / 2), at position min(4 c_mid, n); then split(c_lo .. c_mid) and
+// split(c_mid .. c_hi) one level down.  A split over a single child that is a node runs that node's split (at the level it has
+// reached); a single leaf ends the recursion.
+// A step: per axis the minimum and maximum of grid_coord over the objects now at [P, Q); the axis is the k with the largest
+// (double)(gmax_k - gmin_k) * (double)grid_cell[k], ties to the lowest k; [P, Q) is reordered ascending by (g_axis, object
+// index).  Steps run parent before child, from the index order (position p = object p).
+constexpr uint32_t kMedianTile = 2048;       // T: a step over at most T positions, and every step beneath it, is one workgroup's work in LDS
+constexpr uint32_t kMedianChunk = 65536;     // positions of a level that no step above T covers are cut into groups of at most this many
+struct MedianStep { uint32_t level, P, Q, cut; };
+struct MedianPlan {
+    bool ok = true;                          // false: morton_topology(n) has no plan
+    std::vector<MedianStep> steps;           // ascending by (level, P)
+    // What the device walks (pt_kernels.h, launch_bvh_median).  Steps over more than T positions run level by level over the whole
+    // array: a level's positions fall into groups in position order, a step or a stretch of at most kMedianChunk positions
+    // that no step of the level covers.  group_start holds, level after level, the groups' first positions (bit 31: a step) and
+    // one closing entry n.  The highest steps of at most T positions are the tiles: (P, Q, first, count) with the tile's own
+    // step and every step beneath it at tile_steps[first, first + count) as (P - tile P | local level << 16, Q - tile P),
+    // ascending by (level, P).
+    struct Level { uint32_t first, groups, bits; };   // group_start[first, first + groups]; bits to number the groups
+    std::vector<Level> levels;
+    std::vector<uint32_t> group_start;
+    std::vector<uint4> tiles;
+    std::vector<uint2> tile_steps;
+    uint32_t index_bits = 0;                 // bits to hold an object index < n
+    uint32_t max_groups = 0;
+};
+MedianPlan median_plan(uint32_t n);
+
+// build_morton with the order of the rule above.  g (optional): grid_coord of every object, 3 per object (all 0 without a
+// node); order (optional): the object at every position.
+bool build_median(Built& out, const float4* shape, const uint32_t* shape_tag, uint32_t n, std::vector<uint32_t>* g = nullptr,
                   std::vector<uint32_t>* order = nullptr);
 
 }  // namespace ptbvh

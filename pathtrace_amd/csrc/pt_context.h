@@ -129,6 +129,15 @@ struct PtContext {
     DevBuf<unsigned long long> bvh_cost_built;
     float bvh_cost_cell[3] = {0.f, 0.f, 0.f};
     bool bvh_cost_on_device = false;
+    // pt_scene_rebuild_ordered, the median order: the objects' grid cells, the bound words of a level's steps,
+    // and the split plan of ptbvh::median_plan(bvh_med_n) on the device (its levels here), kept until the object count changes
+    DevBuf<uint2> bvh_cells;
+    DevBuf<uint32_t> bvh_med_bounds, bvh_med_groups;
+    DevBuf<uint4> bvh_med_tiles;
+    DevBuf<uint2> bvh_med_tsteps;
+    std::vector<ptk::BvhMedianLevel> bvh_med_levels;
+    int64_t bvh_med_n = -1;
+    uint32_t bvh_med_n_tiles = 0, bvh_med_index_bits = 0;
     // wavefront state
     DevBuf<float4> xchg;              // k_paths_regen_split: exchange stacks of every wave, one region per lane (stride: sched.xchg_stride)
     DevBuf<float4> queue[4];

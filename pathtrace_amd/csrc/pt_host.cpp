@@ -497,4 +497,88 @@ int pt_debug_bvh_morton_topology(uint32_t n, uint32_t* out_codes, uint32_t* out_
     return PT_OK;
 }
 
+int pt_debug_bvh_median_check(const PtObject* objs, const PtObject* refit_objs, uint32_t n, uint32_t* out_qnodes, uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead,
+                              uint32_t* out_leaf_ids, uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots, float* out_grid, uint32_t* root,
+                              uint64_t* cost_now, uint32_t* out_keys, uint32_t* out_order, uint32_t cap_objs) {
+    if (n && !objs) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_median_check: null objects");
+    if ((cap_nodes && !out_qnodes) || (cap_slots && (!out_leaf_rec || !out_leaf_lead || !out_leaf_ids)) || (cap_objs && (!out_keys || !out_order)))
+        return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_median_check: null output array with a non-zero capacity");
+    std::vector<float4> shape, scan;
+    std::vector<uint32_t> tag, g, order;
+    if (int rc = bvh_records("pt_debug_bvh_median_check", objs, n, shape, scan, tag)) return rc;
+    ptbvh::Built b;
+    if (!ptbvh::build_median(b, shape.data(), tag.data(), n, &g, &order))
+        return fail(PT_ERR_UNSUPPORTED, "pt_debug_bvh_median_check: no tree over %u objects fits the traversal stack (%u entries)", n, ptbvh::kStackDepth);
+    if (n_nodes) *n_nodes = (uint32_t)b.wide.size();
+    if (n_slots) *n_slots = (uint32_t)b.leaf_ids.size();
+    if (int rc = bvh_verify(b, shape, scan, tag, n)) return rc;
+    const float cell[3] = {b.grid_cell[0], b.grid_cell[1], b.grid_cell[2]};    // the grid of the build pose
+    if (refit_objs) {                                            // the tree of objs carried to another pose of the same objects
+        for (uint32_t i = 0; i < n; ++i)
+            if (objs[i].shape_tag != refit_objs[i].shape_tag)
+                return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_median_check: object %u: shape tags %u and %u", i, objs[i].shape_tag, refit_objs[i].shape_tag);
+        if (int rc = bvh_records("pt_debug_bvh_median_check", refit_objs, n, shape, scan, tag)) return rc;
+        ptbvh::refit(b, shape.data(), tag.data(), n);
+        if (int rc = bvh_verify(b, shape, scan, tag, n)) return rc;
+    }
+    // the slots hold the order the rule gives: the steps once more, each as "the range in index order, then a stable sort by
+    // the axis' coordinate" -- another route to the same total order
+    {
+        std::vector<uint32_t> again(n);
+        for (uint32_t i = 0; i < n; ++i) again[i] = i;
+        const ptbvh::MedianPlan pl = ptbvh::median_plan(n);
+        for (const ptbvh::MedianStep& st : pl.steps) {
+            if (!(st.P < st.cut && st.cut < st.Q && st.Q <= n)) return fail(PT_ERR_UNSUPPORTED, "BVH build: step [%u, %u) with its cut at %u", st.P, st.Q, st.cut);
+            std::sort(again.begin() + st.P, again.begin() + st.Q);
+            int axis = 0;
+            double widest = -1.0;
+            for (int k = 0; k < 3; ++k) {
+                uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+                for (uint32_t p = st.P; p < st.Q; ++p) { mn = std::min(mn, g[3 * (size_t)again[p] + k]); mx = std::max(mx, g[3 * (size_t)again[p] + k]); }
+                const double w = (double)(mx - mn) * (double)cell[k];
+                if (k == 0 || w > widest) { widest = w; axis = k; }
+            }
+            std::stable_sort(again.begin() + st.P, again.begin() + st.Q, [&](uint32_t x, uint32_t y) { return g[3 * (size_t)x + axis] < g[3 * (size_t)y + axis]; });
+        }
+        for (uint32_t p = 0; p < n; ++p)
+            if (again[p] != order[p] || (b.leaf_ids[p] & ~ptbvh::kTriangleBit) != order[p])
+                return fail(PT_ERR_UNSUPPORTED, "BVH build: slot %u does not hold the object the median rule puts at position %u", p, p);
+    }
+    const size_t nn = std::min<size_t>(b.wide.size(), cap_nodes), nsl = std::min<size_t>(b.leaf_ids.size(), cap_slots), no = std::min<size_t>(n, cap_objs);
+    if (nn) std::memcpy(out_qnodes, b.qnodes.data(), nn * 4 * sizeof(uint4));
+    if (nsl) {
+        std::memcpy(out_leaf_rec, b.leaf_rec.data(), nsl * 3 * sizeof(float4));
+        std::memcpy(out_leaf_lead, b.leaf_lead.data(), nsl * sizeof(float4));
+        std::memcpy(out_leaf_ids, b.leaf_ids.data(), nsl * sizeof(uint32_t));
+    }
+    if (no) {
+        std::memcpy(out_keys, g.data(), no * 3 * sizeof(uint32_t));
+        std::memcpy(out_order, order.data(), no * sizeof(uint32_t));
+    }
+    if (out_grid) {
+        for (int k = 0; k < 3; ++k) { out_grid[k] = b.grid_min[k]; out_grid[3 + k] = b.grid_cell[k]; }
+        out_grid[6] = b.scene_abs;
+    }
+    if (root) *root = b.root;
+    for (int k = 0; k < 3; ++k)
+        if (cost_now) cost_now[k] = b.cost[k];
+    return PT_OK;
+}
+
+int pt_debug_bvh_median_plan(uint32_t n, uint32_t* out_steps, uint32_t cap_steps, uint32_t* n_steps, uint32_t* tile) {
+    if (cap_steps && !out_steps) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_median_plan: null output array with a non-zero capacity");
+    // (callers ask twice, for the size and then for the array: the plan of the last count is kept per thread)
+    static thread_local ptbvh::MedianPlan pl;
+    static thread_local int64_t pl_n = -1;
+    if (pl_n != (int64_t)n) { pl = ptbvh::median_plan(n); pl_n = (int64_t)n; }
+    if (!pl.ok) return fail(PT_ERR_UNSUPPORTED, "pt_debug_bvh_median_plan: no tree over %u objects fits the traversal stack (%u entries)", n, ptbvh::kStackDepth);
+    static_assert(sizeof(ptbvh::MedianStep) == 4 * sizeof(uint32_t), "a step is four words");
+    const size_t ns = std::min<size_t>(pl.steps.size(), cap_steps);
+    if (ns) std::memcpy(out_steps, pl.steps.data(), ns * sizeof(ptbvh::MedianStep));
+    if (n_steps) *n_steps = (uint32_t)pl.steps.size();
+    if (tile) *tile = ptbvh::kMedianTile;
+    if (ns && ns == pl.steps.size()) { pl = ptbvh::MedianPlan{}; pl_n = -1; }   // delivered in full: let the memory go
+    return PT_OK;
+}
+
 }  // extern "C"

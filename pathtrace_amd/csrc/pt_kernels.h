@@ -417,4 +417,28 @@ void launch_bvh_sort(const BvhBuildArgs& a, hipStream_t st);
 void launch_bvh_write_ids(const BvhBuildArgs& a, bool sorted, hipStream_t st);
 void launch_bvh_codes(uint4* nodes, const uint4* codes, uint32_t n_nodes, hipStream_t st);
 
+// The median order (pt_scene_rebuild_ordered; rule: ptbvh::build_median in pt_bvh.h) in place of launch_bvh_morton
+// and launch_bvh_sort.  The plan (ptbvh::MedianPlan) is on the device; all launches on one stream:
+//   k_bvh_cells            cells[i] = the three grid cells of object i, pairs[0][p] = p (the index order)
+//   per level of steps above T positions (BvhMedianLevel):
+//     k_bvh_median_bounds  per step of the level the minimum and maximum cell per axis over its positions (bounds, zeroed before)
+//     k_bvh_median_keys    the 64-bit key of every position, (group << (16 + index_bits)) | (v << index_bits) | object, v = the
+//                          object's cell on the step's axis, or in a group no step covers the offset inside it: those stay
+//     the radix sort over as many 8-bit digits as the key has.  The object index is the lowest part of the key, so the order
+//     is (group, cell, index) however the objects stood before.
+//   k_bvh_median_unpack    the other pair buffer = (0, object) per position
+//   k_bvh_median_tile      one workgroup per tile: its step and every step beneath it in LDS, the result into that buffer
+// Returns which pair buffer launch_bvh_write_ids has to read.
+struct BvhMedianLevel { uint32_t first, groups, bits; };       // group_start[first, first + groups]; bits to number the groups
+struct BvhMedianArgs {
+    BvhBuildArgs b;                  // shape, tags, pairs, hist, the grid, n
+    uint2* cells;                    // n: (g0 | g1 << 16, g2)
+    uint32_t* bounds;                // 6 words per group of the widest level: 65535 - min per axis, max per axis
+    const uint32_t* group_start;     // ptbvh::MedianPlan::group_start
+    const uint4* tiles;              // ... ::tiles
+    const uint2* tile_steps;         // ... ::tile_steps
+    uint32_t n_tiles, index_bits;
+};
+uint32_t launch_bvh_median(const BvhMedianArgs& a, const BvhMedianLevel* levels, uint32_t n_levels, hipStream_t st);
+
 }  // namespace ptk

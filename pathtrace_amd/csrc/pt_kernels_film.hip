@@ -740,6 +740,11 @@ constexpr uint32_t kSortRounds = kSortTile / kBlock;
 constexpr uint32_t kSortWaves = kBlock / 64;
 constexpr uint32_t kScanBlock = 1024;      // k_bvh_sort_scan: one workgroup, four words per thread and step
 
+// digit of a pass: the pair as one 64-bit key, .x the low word (shift is a multiple of 8: a digit lies in one word)
+PT_DEV uint32_t sort_digit(const uint2& kv, uint32_t shift) {
+    return ((shift < 32u ? kv.x >> shift : kv.y >> (shift - 32u))) & (kSortDigits - 1u);
+}
+
 __global__ void __launch_bounds__(kBlock) k_bvh_morton(BvhBuildArgs a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
@@ -758,7 +763,7 @@ __global__ void __launch_bounds__(kBlock) k_bvh_sort_hist(const uint2* __restric
     const uint32_t base = blockIdx.x * kSortTile;
     for (uint32_t r = 0; r < kSortRounds; ++r) {
         const uint32_t i = base + r * kBlock + threadIdx.x;
-        if (i < n) atomicAdd(&h[(in[i].x >> shift) & (kSortDigits - 1u)], 1u);
+        if (i < n) atomicAdd(&h[sort_digit(in[i], shift)], 1u);
     }
     __syncthreads();
     hist[(size_t)threadIdx.x * tiles + blockIdx.x] = h[threadIdx.x];
@@ -815,7 +820,7 @@ __global__ void __launch_bounds__(kBlock) k_bvh_sort_scatter(const uint2* __rest
         const uint32_t i = first + r * kBlock + tid;
         const bool valid = i < n;
         const uint2 kv = valid ? in[i] : make_uint2(0u, 0u);
-        const uint32_t d = (kv.x >> shift) & (kSortDigits - 1u);
+        const uint32_t d = sort_digit(kv, shift);
         unsigned long long same = __ballot(valid);
 #pragma unroll
         for (uint32_t b = 0; b < 8u; ++b) {
@@ -869,22 +874,242 @@ namespace ptk {
 void launch_bvh_morton(const BvhBuildArgs& a, hipStream_t st) {
     if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_bvh_morton, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
 }
-void launch_bvh_sort(const BvhBuildArgs& a, hipStream_t st) {
-    if (!a.n) return;
+// `passes` stable passes over the digits from bit 0 upward, from pairs[src]; returns the buffer that holds the result
+static uint32_t bvh_sort_passes(const BvhBuildArgs& a, uint32_t src, uint32_t passes, hipStream_t st) {
     const uint32_t tiles = bvh_sort_tiles(a.n);
-    for (uint32_t pass = 0; pass < 4u; ++pass) {                 // an even number of passes: the result is in pairs[0]
-        const uint2* in = a.pairs[pass & 1u];
-        uint2* out = a.pairs[(pass & 1u) ^ 1u];
+    for (uint32_t pass = 0; pass < passes; ++pass, src ^= 1u) {
+        const uint2* in = a.pairs[src];
+        uint2* out = a.pairs[src ^ 1u];
         hipLaunchKernelGGL(PTK_IMPL::k_bvh_sort_hist, dim3(tiles), dim3(kBlock), 0, st, in, a.hist, a.n, tiles, 8u * pass);
         hipLaunchKernelGGL(PTK_IMPL::k_bvh_sort_scan, dim3(1), dim3(PTK_IMPL::kScanBlock), 0, st, a.hist, kSortDigits * tiles);
         hipLaunchKernelGGL(PTK_IMPL::k_bvh_sort_scatter, dim3(tiles), dim3(kBlock), 0, st, in, out, (const uint32_t*)a.hist, a.n, tiles, 8u * pass);
     }
+    return src;
+}
+void launch_bvh_sort(const BvhBuildArgs& a, hipStream_t st) {
+    if (a.n) bvh_sort_passes(a, 0u, 4u, st);                     // the 32-bit key; an even number of passes: the result is in pairs[0]
 }
 void launch_bvh_write_ids(const BvhBuildArgs& a, bool sorted, hipStream_t st) {
     if (a.n_slots) hipLaunchKernelGGL(PTK_IMPL::k_bvh_write_ids, dim3((a.n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a, sorted ? (const uint2*)a.pairs[0] : (const uint2*)nullptr);
 }
 void launch_bvh_codes(uint4* nodes, const uint4* codes, uint32_t n_nodes, hipStream_t st) {
     if (n_nodes) hipLaunchKernelGGL(PTK_IMPL::k_bvh_codes, dim3((n_nodes + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nodes, codes, n_nodes);
+}
+}  // namespace ptk
+
+// ------------------------------------------------------------------ device-side BVH build, median order (pt_scene_rebuild_ordered)
+// The rule is ptbvh::build_median (pt_bvh.h) and DESIGN.md 5i.  Every step orders its positions by (cell on the step's axis,
+// object index), a total order: whatever sorts correctly reproduces the host's leaf_ids bit for bit.  Steps above T positions
+// go through the radix sort, level by level; a step of at most T positions and everything beneath it is one workgroup's work.
+namespace PTK_IMPL {
+constexpr uint32_t kMedianT = ptbvh::kMedianTile;
+constexpr uint32_t kMedianBlock = 1024;
+constexpr uint32_t kMedianPer = kMedianT / kMedianBlock;     // positions per thread
+constexpr uint32_t kMedianMaxSteps = 512;                    // a tile has at most T / 4 leaves, so fewer steps than that
+static_assert(kMedianT % kMedianBlock == 0 && kMedianT / 4 <= kMedianMaxSteps && kMedianT < 65536, "tile steps are 16-bit offsets");
+struct MedianCell { float c[3]; };
+
+__global__ void __launch_bounds__(kBlock) k_bvh_cells(BvhBuildArgs a, uint2* __restrict__ cells) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float4 r0 = a.shape[3 * (size_t)i], r1 = a.shape[3 * (size_t)i + 1], r2 = a.shape[3 * (size_t)i + 2];
+    float lo[3], hi[3];
+    refit_primitive_box(r0, r1, r2, a.tags[i] != 0u, lo, hi);
+    const float gmin[3] = {a.grid_min[0], a.grid_min[1], a.grid_min[2]}, cell[3] = {a.grid_cell[0], a.grid_cell[1], a.grid_cell[2]};
+    const uint32_t g0 = ptbvh::grid_coord(lo, hi, gmin, cell, 0), g1 = ptbvh::grid_coord(lo, hi, gmin, cell, 1), g2 = ptbvh::grid_coord(lo, hi, gmin, cell, 2);
+    cells[i] = make_uint2(g0 | (g1 << 16), g2);
+    a.pairs[0][i] = make_uint2(i, 0u);
+}
+
+// the group of position p: the last one that starts at or before it (the first group starts at 0)
+PT_DEV uint32_t median_group(const uint32_t* __restrict__ gs, uint32_t groups, uint32_t p) {
+    uint32_t lo = 0u, hi = groups;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((gs[mid] & 0x7FFFFFFFu) <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// the rule's axis from the six bound words of a step
+PT_DEV uint32_t median_axis(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t mx, uint32_t my, uint32_t mz, const MedianCell& cell) {
+#pragma clang fp contract(off)
+    // n* = 65535 - minimum: maximum - minimum = m + n - 65535
+    const double wx = (double)(mx + nx - 65535u) * (double)cell.c[0], wy = (double)(my + ny - 65535u) * (double)cell.c[1],
+                 wz = (double)(mz + nz - 65535u) * (double)cell.c[2];
+    uint32_t axis = 0u;
+    double widest = wx;
+    if (wy > widest) { widest = wy; axis = 1u; }
+    if (wz > widest) axis = 2u;
+    return axis;
+}
+
+__global__ void __launch_bounds__(kBlock) k_bvh_median_bounds(const uint2* __restrict__ pairs, const uint2* __restrict__ cells, const uint32_t* __restrict__ gs,
+                                                              uint32_t groups, uint32_t* bounds, uint32_t n, uint32_t mask) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = p < n;
+    const uint32_t grp = median_group(gs, groups, valid ? p : n - 1u);
+    const bool step = (gs[grp] >> 31) != 0u;
+    uint32_t v[6] = {0u, 0u, 0u, 0u, 0u, 0u};                     // 0 changes no maximum
+    if (valid && step) {
+        const uint32_t o = pairs[p].x & mask;
+        if (o < n) {
+            const uint2 c = cells[o];
+            const uint32_t g0 = c.x & 0xFFFFu, g1 = c.x >> 16, g2 = c.y & 0xFFFFu;
+            v[0] = 65535u - g0; v[1] = 65535u - g1; v[2] = 65535u - g2; v[3] = g0; v[4] = g1; v[5] = g2;
+        }
+    }
+    const uint32_t grp0 = __builtin_amdgcn_readfirstlane(grp);
+    if (__ballot(grp != grp0) == 0ull) {                         // one group in the wave: six atomics for all of it
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            for (int off = 32; off > 0; off >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v[k], off); v[k] = w > v[k] ? w : v[k]; }
+        if ((threadIdx.x & 63u) == 0u && step)
+            for (int k = 0; k < 6; ++k) atomicMax(&bounds[6 * (size_t)grp + k], v[k]);
+    } else if (valid && step) {
+        for (int k = 0; k < 6; ++k) atomicMax(&bounds[6 * (size_t)grp + k], v[k]);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_bvh_median_keys(uint2* pairs, const uint2* __restrict__ cells, const uint32_t* __restrict__ gs, uint32_t groups,
+                                                            const uint32_t* __restrict__ bounds, MedianCell cell, uint32_t n, uint32_t index_bits, uint32_t mask) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t o = pairs[p].x & mask;
+    const uint32_t grp = median_group(gs, groups, p);
+    const uint32_t start = gs[grp];
+    uint32_t v = p - (start & 0x7FFFFFFFu);                      // no step: the position stays (a group has at most 65536)
+    if ((start >> 31) != 0u) {
+        const uint32_t* b = bounds + 6 * (size_t)grp;
+        const uint32_t axis = median_axis(b[0], b[1], b[2], b[3], b[4], b[5], cell);
+        const uint2 c = cells[o < n ? o : 0u];
+        v = axis == 0u ? c.x & 0xFFFFu : axis == 1u ? c.x >> 16 : c.y & 0xFFFFu;
+    }
+    const unsigned long long key = ((unsigned long long)grp << (16u + index_bits)) | ((unsigned long long)(v & 0xFFFFu) << index_bits) | o;
+    pairs[p] = make_uint2((uint32_t)key, (uint32_t)(key >> 32));
+}
+
+__global__ void __launch_bounds__(kBlock) k_bvh_median_unpack(const uint2* __restrict__ in, uint2* __restrict__ out, uint32_t n, uint32_t mask) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p < n) out[p] = make_uint2(0u, in[p].x & mask);
+}
+
+// One workgroup per tile.  The tile's objects (cells and index) stand in LDS in position order; level by level every step of
+// the tile takes its bounds (LDS atomics), its axis, and then every position its rank among the keys (cell << 32 | index) of
+// its step -- the keys differ, so the ranks are the new positions.  Positions no step of a level covers stay.
+__global__ void __launch_bounds__(kMedianBlock) k_bvh_median_tile(const uint2* __restrict__ in, uint2* __restrict__ out, const uint2* __restrict__ cells,
+                                                                  const uint4* __restrict__ tiles, const uint2* __restrict__ tile_steps, MedianCell cell,
+                                                                  uint32_t n, uint32_t mask) {
+    __shared__ uint32_t e_g01[kMedianT], e_g2[kMedianT], e_obj[kMedianT];
+    __shared__ unsigned long long key[kMedianT];
+    __shared__ uint2 steps[kMedianMaxSteps];
+    __shared__ uint32_t bnd[6 * kMedianMaxSteps];
+    __shared__ uint32_t axis_of[kMedianMaxSteps];
+    const uint32_t tid = threadIdx.x;
+    const uint4 tl = tiles[blockIdx.x];
+    const uint32_t p0 = tl.x;
+    if (tl.y > n || tl.y <= p0) return;                          // (uniform; the plan never says so)
+    const uint32_t size = tl.y - p0 < kMedianT ? tl.y - p0 : kMedianT;
+    const uint32_t n_steps = tl.w < kMedianMaxSteps ? tl.w : kMedianMaxSteps;
+    for (uint32_t s = tid; s < n_steps; s += kMedianBlock) steps[s] = tile_steps[tl.z + s];
+    for (uint32_t p = tid; p < size; p += kMedianBlock) {
+        uint32_t o = in[p0 + p].x & mask;
+        o = o < n ? o : 0u;
+        const uint2 c = cells[o];
+        e_g01[p] = c.x; e_g2[p] = c.y & 0xFFFFu; e_obj[p] = o;
+    }
+    __syncthreads();
+    for (uint32_t s0 = 0u; s0 < n_steps;) {
+        const uint32_t level = steps[s0].x >> 16;
+        uint32_t s1 = s0 + 1u;
+        while (s1 < n_steps && (steps[s1].x >> 16) == level) ++s1;
+        const uint32_t cnt = s1 - s0;
+        for (uint32_t k = tid; k < 6u * cnt; k += kMedianBlock) bnd[k] = 0u;
+        __syncthreads();
+        // the step of each of this thread's positions: the last one of the level that starts at or before it, if it reaches it
+        uint32_t mine[kMedianPer];
+#pragma unroll
+        for (uint32_t e = 0; e < kMedianPer; ++e) {
+            const uint32_t p = tid + e * kMedianBlock;
+            mine[e] = 0xFFFFFFFFu;
+            if (p < size && (steps[s0].x & 0xFFFFu) <= p) {
+                uint32_t lo = s0, hi = s1;
+                while (hi - lo > 1u) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if ((steps[mid].x & 0xFFFFu) <= p) lo = mid; else hi = mid;
+                }
+                if (p < steps[lo].y && steps[lo].y <= size) {
+                    mine[e] = lo - s0;
+                    const uint32_t g01 = e_g01[p], g0 = g01 & 0xFFFFu, g1 = g01 >> 16, g2 = e_g2[p];
+                    uint32_t* b = bnd + 6u * mine[e];
+                    atomicMax(b, 65535u - g0); atomicMax(b + 1, 65535u - g1); atomicMax(b + 2, 65535u - g2);
+                    atomicMax(b + 3, g0); atomicMax(b + 4, g1); atomicMax(b + 5, g2);
+                }
+            }
+        }
+        __syncthreads();
+        for (uint32_t k = tid; k < cnt; k += kMedianBlock) {
+            const uint32_t* b = bnd + 6u * k;
+            axis_of[k] = median_axis(b[0], b[1], b[2], b[3], b[4], b[5], cell);
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t e = 0; e < kMedianPer; ++e) {
+            const uint32_t p = tid + e * kMedianBlock;
+            if (mine[e] != 0xFFFFFFFFu) {
+                const uint32_t axis = axis_of[mine[e]], g01 = e_g01[p];
+                const uint32_t v = axis == 0u ? g01 & 0xFFFFu : axis == 1u ? g01 >> 16 : e_g2[p];
+                key[p] = ((unsigned long long)v << 32) | e_obj[p];
+            }
+        }
+        __syncthreads();
+        uint32_t to[kMedianPer], m_g01[kMedianPer], m_g2[kMedianPer], m_obj[kMedianPer];
+#pragma unroll
+        for (uint32_t e = 0; e < kMedianPer; ++e) {
+            const uint32_t p = tid + e * kMedianBlock;
+            to[e] = 0xFFFFFFFFu; m_g01[e] = 0u; m_g2[e] = 0u; m_obj[e] = 0u;
+            if (mine[e] != 0xFFFFFFFFu) {
+                const uint2 st = steps[s0 + mine[e]];
+                const uint32_t first = st.x & 0xFFFFu, last = st.y;
+                const unsigned long long mk = key[p];
+                uint32_t rank = 0u;
+                for (uint32_t j = first; j < last; ++j) rank += key[j] < mk ? 1u : 0u;
+                to[e] = first + rank;                            // < last: the position's own key is not below itself
+                m_g01[e] = e_g01[p]; m_g2[e] = e_g2[p]; m_obj[e] = e_obj[p];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t e = 0; e < kMedianPer; ++e)
+            if (to[e] < size) { e_g01[to[e]] = m_g01[e]; e_g2[to[e]] = m_g2[e]; e_obj[to[e]] = m_obj[e]; }
+        __syncthreads();
+        s0 = s1;
+    }
+    for (uint32_t p = tid; p < size; p += kMedianBlock) out[p0 + p] = make_uint2(0u, e_obj[p]);
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+uint32_t launch_bvh_median(const BvhMedianArgs& a, const BvhMedianLevel* levels, uint32_t n_levels, hipStream_t st) {
+    const BvhBuildArgs& b = a.b;
+    if (!b.n) return 0u;
+    const dim3 grid((b.n + kBlock - 1) / kBlock), block(kBlock);
+    const uint32_t mask = a.index_bits >= 32u ? 0xFFFFFFFFu : (1u << a.index_bits) - 1u;
+    const PTK_IMPL::MedianCell cell = {{b.grid_cell[0], b.grid_cell[1], b.grid_cell[2]}};
+    hipLaunchKernelGGL(PTK_IMPL::k_bvh_cells, grid, block, 0, st, b, a.cells);
+    uint32_t cur = 0u;
+    for (uint32_t l = 0; l < n_levels; ++l) {
+        const BvhMedianLevel& lv = levels[l];
+        const uint32_t* gs = a.group_start + lv.first;
+        (void)hipMemsetAsync(a.bounds, 0, 6 * (size_t)lv.groups * sizeof(uint32_t), st);
+        hipLaunchKernelGGL(PTK_IMPL::k_bvh_median_bounds, grid, block, 0, st, (const uint2*)b.pairs[cur], (const uint2*)a.cells, gs, lv.groups, a.bounds, b.n, mask);
+        hipLaunchKernelGGL(PTK_IMPL::k_bvh_median_keys, grid, block, 0, st, b.pairs[cur], (const uint2*)a.cells, gs, lv.groups, (const uint32_t*)a.bounds, cell, b.n,
+                           a.index_bits, mask);
+        cur = bvh_sort_passes(b, cur, (a.index_bits + 16u + lv.bits + 7u) / 8u, st);
+    }
+    hipLaunchKernelGGL(PTK_IMPL::k_bvh_median_unpack, grid, block, 0, st, (const uint2*)b.pairs[cur], b.pairs[cur ^ 1u], b.n, mask);
+    if (a.n_tiles)
+        hipLaunchKernelGGL(PTK_IMPL::k_bvh_median_tile, dim3(a.n_tiles), dim3(PTK_IMPL::kMedianBlock), 0, st, (const uint2*)b.pairs[cur], b.pairs[cur ^ 1u],
+                           (const uint2*)a.cells, a.tiles, a.tile_steps, cell, b.n, mask);
+    return cur ^ 1u;
 }
 }  // namespace ptk
 

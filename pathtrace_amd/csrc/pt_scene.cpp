@@ -2,6 +2,7 @@
 // buffers, k_scene_setup over them, the LDS blob; and the BVH of the uploaded scene, built at first use on the host, refitted on
 // the device when the objects move (pt_scene_refit) or built there for the new pose (pt_scene_rebuild).
 #include <cstring>
+#include <utility>
 
 #include "pt_bvh.h"
 #include "pt_context.h"
@@ -72,10 +73,12 @@ namespace {
 // touched only once that has succeeded.  keep_tree (pt_scene_refit): a BVH the context holds is not dropped but refitted on
 // the device to the new records -- same topology, so the tree arrays never cross PCIe again.  kTreeRebuild
 // (pt_scene_rebuild): whether or not a tree is held, the context afterwards holds the Morton tree of the new records, built on
-// the device behind them: keys, sort, leaf ids, then the launches of the refit.
+// the device behind them: keys, sort, leaf ids, then the launches of the refit.  order (pt_scene_rebuild_ordered):
+// PT_BVH_ORDER_MEDIAN puts the median-split order of DESIGN.md 5i in the place of keys and sort; nothing else differs.
 enum Tree { kTreeDrop, kTreeRefit, kTreeRebuild };
-int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, bool keep_history, Tree tree = kTreeDrop) {
+int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, bool keep_history, Tree tree = kTreeDrop, uint32_t order = PT_BVH_ORDER_MORTON) {
     if (!c || (!objs && n)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if (order != PT_BVH_ORDER_MORTON && order != PT_BVH_ORDER_MEDIAN) return fail(PT_ERR_INVALID_ARG, "%s: order %u (PT_BVH_ORDER_MORTON or PT_BVH_ORDER_MEDIAN)", who, order);
     if (keep_history) {
         if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
         if (n != c->view.n_objs) return fail(PT_ERR_INVALID_ARG, "%s: %u objects, the uploaded scene has %u", who, n, c->view.n_objs);
@@ -92,6 +95,11 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
         if (!topo.ok)
             return fail(PT_ERR_UNSUPPORTED, "%s: no tree over %u objects fits the traversal stack (%u entries); use pt_scene_update", who, n, ptbvh::kStackDepth);
     }
+    // the median order's split plan likewise (the same counts have one)
+    const bool median = rebuild && order == PT_BVH_ORDER_MEDIAN;
+    ptbvh::MedianPlan plan;
+    const bool new_plan = median && c->bvh_med_n != (int64_t)n;
+    if (new_plan) plan = ptbvh::median_plan(n);
     const uint32_t mt_nodes = new_topo ? (uint32_t)topo.node_height.size() : c->bvh_topo_nodes, mt_slots = new_topo ? topo.n_slots : c->bvh_topo_slots;
     HIP_TRY(hipSetDevice(c->device));
     ptscene::Records rec;
@@ -130,11 +138,15 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
                 (rc = c->bvh_slot_box.ensure(2 * (size_t)mt_slots + 1)) || (rc = c->bvh_node_box.ensure(2 * (size_t)mt_nodes + 1)) ||
                 (rc = c->bvh_pairs[0].ensure((size_t)n + 1)) || (rc = c->bvh_pairs[1].ensure((size_t)n + 1)) ||
                 (rc = c->bvh_hist.ensure((size_t)ptk::kSortDigits * ptk::bvh_sort_tiles(n) + 4)) ||
-                (rc = c->bvh_topo_codes.ensure((size_t)mt_nodes + 1)) || (rc = c->bvh_topo_order.ensure((size_t)mt_nodes + 1))) {
+                (rc = c->bvh_topo_codes.ensure((size_t)mt_nodes + 1)) || (rc = c->bvh_topo_order.ensure((size_t)mt_nodes + 1)) ||
+                (median && ((rc = c->bvh_cells.ensure((size_t)n + 1)) ||
+                            (new_plan && ((rc = c->bvh_med_bounds.ensure(6 * (size_t)plan.max_groups + 1)) || (rc = c->bvh_med_groups.ensure(plan.group_start.size() + 1)) ||
+                                          (rc = c->bvh_med_tiles.ensure(plan.tiles.size() + 1)) || (rc = c->bvh_med_tsteps.ensure(plan.tile_steps.size() + 1))))))) {
                 c->view.bvh = ptk::BvhView{};        // (an array of the held tree may be gone)
                 c->has_bvh = false;
                 c->bvh_is_morton = false;
                 c->bvh_topo_n = -1;
+                c->bvh_med_n = -1;
                 return rc;
             }
             if (c->bvh_nodes.p != nodes0 || c->bvh_order.p != order0) c->bvh_is_morton = false;
@@ -197,6 +209,17 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
             c->bvh_topo_nodes = mt_nodes; c->bvh_topo_slots = mt_slots; c->bvh_topo_root = topo.root; c->bvh_topo_depth = topo.depth;
             c->bvh_topo_n = (int64_t)n;
         }
+        if (new_plan) {
+            // once per object count as well: the groups of the levels above T, the tiles and their steps
+            c->bvh_med_n = -1;
+            if (!plan.group_start.empty()) HIP_TRY(hipMemcpy(c->bvh_med_groups.p, plan.group_start.data(), plan.group_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            if (!plan.tiles.empty()) HIP_TRY(hipMemcpy(c->bvh_med_tiles.p, plan.tiles.data(), plan.tiles.size() * sizeof(uint4), hipMemcpyHostToDevice));
+            if (!plan.tile_steps.empty()) HIP_TRY(hipMemcpy(c->bvh_med_tsteps.p, plan.tile_steps.data(), plan.tile_steps.size() * sizeof(uint2), hipMemcpyHostToDevice));
+            c->bvh_med_levels.clear();
+            for (const ptbvh::MedianPlan::Level& lv : plan.levels) c->bvh_med_levels.push_back(ptk::BvhMedianLevel{lv.first, lv.groups, lv.bits});
+            c->bvh_med_n_tiles = (uint32_t)plan.tiles.size(); c->bvh_med_index_bits = plan.index_bits;
+            c->bvh_med_n = (int64_t)n;
+        }
         // behind the records and k_scene_setup on the context's stream; nothing here waits for the device
         ptk::BvhBuildArgs ba{};
         ba.shape = c->shape.p; ba.tags = c->shape_tag.p;
@@ -204,7 +227,14 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
         ba.ids = c->bvh_ids.p; ba.rec = c->bvh_rec.p; ba.lead = c->bvh_lead.p;
         ba.n = n; ba.n_slots = mt_slots;
         for (int k = 0; k < 3; ++k) { ba.grid_min[k] = bounds.grid_min[k]; ba.grid_cell[k] = bounds.grid_cell[k]; }
-        if (mt_nodes) {                          // (without a node there is no grid: every key ties, the order is the index order)
+        if (mt_nodes && median) {                // (without a node there is no grid and no step: the order is the index order)
+            ptk::BvhMedianArgs ma{};
+            ma.b = ba;
+            ma.cells = c->bvh_cells.p; ma.bounds = c->bvh_med_bounds.p; ma.group_start = c->bvh_med_groups.p;
+            ma.tiles = c->bvh_med_tiles.p; ma.tile_steps = c->bvh_med_tsteps.p;
+            ma.n_tiles = c->bvh_med_n_tiles; ma.index_bits = c->bvh_med_index_bits;
+            if (ptk::launch_bvh_median(ma, c->bvh_med_levels.data(), (uint32_t)c->bvh_med_levels.size(), c->stream)) std::swap(ba.pairs[0], ba.pairs[1]);
+        } else if (mt_nodes) {                   // (... every key ties)
             ptk::launch_bvh_morton(ba, c->stream);
             ptk::launch_bvh_sort(ba, c->stream);
         }
@@ -274,6 +304,9 @@ int pt_scene_upload(PtContext* c, const PtObject* objs, uint32_t n) { return sce
 int pt_scene_update(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_update", c, objs, n, true); }
 int pt_scene_refit(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_refit", c, objs, n, true, kTreeRefit); }
 int pt_scene_rebuild(PtContext* c, const PtObject* objs, uint32_t n) { return scene_set("pt_scene_rebuild", c, objs, n, true, kTreeRebuild); }
+int pt_scene_rebuild_ordered(PtContext* c, const PtObject* objs, uint32_t n, uint32_t order) {
+    return scene_set("pt_scene_rebuild_ordered", c, objs, n, true, kTreeRebuild, order);
+}
 
 int pt_scene_bvh_cost(PtContext* c, double* cost_now, double* cost_at_build, uint32_t* refits) {
     if (!c) return fail(PT_ERR_INVALID_ARG, "pt_scene_bvh_cost: null context");

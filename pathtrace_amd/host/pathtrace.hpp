@@ -522,6 +522,10 @@ public:
     // repair for a refitted tree whose bvh_cost() has grown, and, right after the first push(), a first build without the
     // host builder.  The film is the same bit for bit.
     void scene_rebuild(int device = 0) { scene(device, kRebuild); }
+    // pt_scene_rebuild_ordered: the same with the order the objects fill the leaves in chosen -- BvhOrder::Median gives a tree
+    // of about half the cost for a somewhat longer build (a tree worth keeping, where Morton's is for poses that do not last).
+    enum class BvhOrder : uint32_t { Morton = PT_BVH_ORDER_MORTON, Median = PT_BVH_ORDER_MEDIAN };
+    void scene_rebuild(BvhOrder order, int device = 0) { scene(device, kRebuild, (uint32_t)order); }
     struct BvhCost { double now, at_build; uint32_t refits; };
     BvhCost bvh_cost() {
         BvhCost b{};
@@ -654,12 +658,12 @@ private:
 
     // the context with this World's objects on it (uploaded again after push())
     enum SceneMode { kUpdate, kRefit, kRebuild };
-    PtContext* scene(int device, SceneMode mode = kUpdate) {
+    PtContext* scene(int device, SceneMode mode = kUpdate, uint32_t order = PT_BVH_ORDER_MORTON) {
         check_abi();
         if (!ctx_) check(pt_context_create(device, &ctx_));
         if (!uploaded_) { check(pt_scene_upload(ctx_, objects_.data(), (uint32_t)objects_.size())); uploaded_ = true; }
         else if (moved_ && mode != kRebuild) check((mode == kRefit ? pt_scene_refit : pt_scene_update)(ctx_, objects_.data(), (uint32_t)objects_.size()));
-        if (mode == kRebuild) check(pt_scene_rebuild(ctx_, objects_.data(), (uint32_t)objects_.size()));
+        if (mode == kRebuild) check(pt_scene_rebuild_ordered(ctx_, objects_.data(), (uint32_t)objects_.size(), order));
         moved_ = false;
         return ctx_;
     }

@@ -23,6 +23,8 @@ pub const PT_INTEGRATOR_BRDF_ONLY: u32 = 1;
 pub const PT_ACCEL_LINEAR: u32 = 0;
 pub const PT_ACCEL_BVH: u32 = 1;
 pub const PT_ACCEL_AUTO: u32 = 2;
+pub const PT_BVH_ORDER_MORTON: u32 = 0;
+pub const PT_BVH_ORDER_MEDIAN: u32 = 1;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -276,6 +278,7 @@ extern "C" {
     pub fn pt_scene_refit(ctx: *mut PtContext, objs: *const PtObject, n_objs: u32) -> c_int;
     pub fn pt_scene_bvh_cost(ctx: *mut PtContext, cost_now: *mut f64, cost_at_build: *mut f64, refits: *mut u32) -> c_int;
     pub fn pt_scene_rebuild(ctx: *mut PtContext, objs: *const PtObject, n_objs: u32) -> c_int;
+    pub fn pt_scene_rebuild_ordered(ctx: *mut PtContext, objs: *const PtObject, n_objs: u32, order: u32) -> c_int;
     pub fn pt_debug_motion_maps(prev_objs: *const PtObject, cur_objs: *const PtObject, n: u32, out_maps: *mut f64, out_flags: *mut u32) -> c_int;
     pub fn pt_render_feature_ids_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, d_ids: *mut i32) -> c_int;
     pub fn pt_denoise_temporal_motion_device(ctx: *mut PtContext, cam: *const PtCamera, d_linear_rgb: *const f32, d_features: *const f32, d_ids: *const i32, dn: *const PtDenoise, tp: *const PtTemporal, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
@@ -297,6 +300,8 @@ extern "C" {
     pub fn pt_debug_bvh_check(objs: *const PtObject, n_objs: u32, depth: *mut u32, n_nodes: *mut u32, n_leaf_slots: *mut u32) -> c_int;
     pub fn pt_debug_bvh_refit_check(prev_objs: *const PtObject, cur_objs: *const PtObject, n_objs: u32, refit: u32, out_qnodes: *mut u32, cap_nodes: u32, out_leaf_rec: *mut f32, out_leaf_lead: *mut f32, out_leaf_ids: *mut u32, cap_slots: u32, n_nodes: *mut u32, n_slots: *mut u32, out_grid: *mut f32, root: *mut u32, cost_now: *mut u64, cost_at_build: *mut u64) -> c_int;
     pub fn pt_debug_bvh_morton_check(objs: *const PtObject, refit_objs: *const PtObject, n_objs: u32, out_qnodes: *mut u32, cap_nodes: u32, out_leaf_rec: *mut f32, out_leaf_lead: *mut f32, out_leaf_ids: *mut u32, cap_slots: u32, n_nodes: *mut u32, n_slots: *mut u32, out_grid: *mut f32, root: *mut u32, cost_now: *mut u64, out_keys: *mut u32, out_order: *mut u32, cap_objs: u32) -> c_int;
+    pub fn pt_debug_bvh_median_check(objs: *const PtObject, refit_objs: *const PtObject, n_objs: u32, out_qnodes: *mut u32, cap_nodes: u32, out_leaf_rec: *mut f32, out_leaf_lead: *mut f32, out_leaf_ids: *mut u32, cap_slots: u32, n_nodes: *mut u32, n_slots: *mut u32, out_grid: *mut f32, root: *mut u32, cost_now: *mut u64, out_keys: *mut u32, out_order: *mut u32, cap_objs: u32) -> c_int;
+    pub fn pt_debug_bvh_median_plan(n_objs: u32, out_steps: *mut u32, cap_steps: u32, n_steps: *mut u32, tile: *mut u32) -> c_int;
     pub fn pt_debug_bvh_morton_topology(n_objs: u32, out_codes: *mut u32, out_height: *mut u32, out_order: *mut u32, cap_nodes: u32, out_height_first: *mut u32, cap_heights: u32, n_nodes: *mut u32, n_heights: *mut u32, n_slots: *mut u32, root: *mut u32, stack_need: *mut u32, depth: *mut u32) -> c_int;
     pub fn pt_debug_bvh_read(ctx: *mut PtContext, out_qnodes: *mut u32, cap_nodes: u32, out_leaf_rec: *mut f32, out_leaf_lead: *mut f32, out_leaf_ids: *mut u32, cap_slots: u32, n_nodes: *mut u32, n_slots: *mut u32, out_grid: *mut f32, root: *mut u32, cost_now: *mut u64) -> c_int;
     pub fn pt_last_error() -> *const c_char;

@@ -11,8 +11,11 @@ Prints one JSON line.  Every timing is taken --repeats times after one untimed r
   motion: 100 frames of motion, per frame one scene call and one 256 x 256 x 2 render: "refit" every frame, or a rebuild every k-th
           frame and a refit otherwise -- wall_ms of the 100 frames, and render_last_ms / cost_ratio_last of the tree at the end
 --trace-loop N: nothing but N rebuilds of moving poses, for a kernel trace (the split into keys, sort, ids and refit)
+--order median: the device builds are pt_scene_rebuild_ordered(PT_BVH_ORDER_MEDIAN) -- the drain, the motion table and the trace
+          loop --, the alternating entries gain "rebuild_median" beside "rebuild" (Morton), and "tree" gains render_median_ms and
+          cost_median beside the Morton and the SAH tree of the same pose
 
-    python tools/rebuild_bench.py [--objects 10000] [--step 0.004] [--repeats 7]
+    python tools/rebuild_bench.py [--objects 10000] [--step 0.004] [--repeats 7] [--order morton|median]
 """
 import argparse
 import json
@@ -38,7 +41,9 @@ def main():
     ap.add_argument("--step", type=float, default=0.004, help="largest move of a sphere per frame and axis")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--trace-loop", type=int, default=0)
+    ap.add_argument("--order", choices=("morton", "median"), default="morton")
     args = ap.parse_args()
+    median = args.order == "median"
     base = pt.builtin_scene(4, args.objects)
     n = len(base)
     rng = np.random.default_rng(1)
@@ -54,20 +59,22 @@ def main():
     small, big = pt.camera_new(width=64, height=64), pt.camera_new(width=256, height=256)
     p1, p2 = pt.default_params(spp=1, accel=1), pt.default_params(spp=2, accel=1)
     a, b = pt.Context(0), pt.Context(0)
+    a.scene_rebuild_median = lambda objs: a.scene_rebuild(objs, order="median")
+    rebuild = a.scene_rebuild_median if median else a.scene_rebuild      # the device build of --order
 
     if args.trace_loop:
         a.upload(base)
         for f in range(args.trace_loop):
-            a.scene_rebuild(pose(f))
+            rebuild(pose(f))
         a.sync()
         a.close()
         b.close()
         return
 
-    res = {"objects": n, "step": args.step, "repeats": args.repeats}
+    res = {"objects": n, "step": args.step, "repeats": args.repeats, "order": args.order}
 
     # ---- the scene call + the first render, the three entries alternating
-    entries = ("rebuild", "update", "refit")
+    entries = (("rebuild_median",) if median else ()) + ("rebuild", "update", "refit")
     a.upload(base)
     a.render(small, p1)
     t = {e: ([], []) for e in entries}
@@ -91,7 +98,7 @@ def main():
     drain = []
     for _ in range(args.repeats):
         frame += 1
-        a.scene_rebuild(pose(frame))
+        rebuild(pose(frame))
         t1 = time.perf_counter()
         a.sync()
         drain.append((time.perf_counter() - t1) * 1e3)
@@ -116,25 +123,28 @@ def main():
     b.render(small, p1)
     res["tree"] = {"render_morton_ms": stat(render_ms(a), 4), "render_sah_ms": stat(render_ms(b), 4),
                    "cost_morton": a.bvh_cost()[0], "cost_sah": b.bvh_cost()[0]}
+    if median:
+        a.scene_rebuild_median(objs)
+        res["tree"].update(render_median_ms=stat(render_ms(a), 4), cost_median=a.bvh_cost()[0])
 
     # ---- 100 frames of motion
     poses = [pose(f) for f in range(101)]
     res["motion"] = {}
     for every in (0, 10, 25, 50):
         a.upload(poses[0])
-        a.scene_rebuild(poses[0])
+        rebuild(poses[0])
         a.render(big, p2)
         a.sync()
         t0 = time.perf_counter()
         for f in range(1, 101):
-            (a.scene_rebuild if every and f % every == 0 else a.scene_refit)(poses[f])
+            (rebuild if every and f % every == 0 else a.scene_refit)(poses[f])
             a.render(big, p2)
         a.sync()
         wall = (time.perf_counter() - t0) * 1e3
         # the tree at the end, with the last rebuild's cost carried to this pose's grid by a fresh build of the same pose
         now = a.bvh_cost()[0]
         last = render_ms(a)
-        a.scene_rebuild(poses[100])
+        rebuild(poses[100])
         res["motion"]["refit only" if not every else "rebuild every %d" % every] = {
             "wall_ms": round(wall, 2), "render_last_ms": stat(last, 4), "cost_ratio_last": round(now / a.bvh_cost()[0], 4)}
     a.close()
