@@ -695,12 +695,46 @@ int pt_denoise_temporal_alpha_device(PtContext* ctx, const PtCamera* cam, const 
  * NaN and the frame is bit-identical to pt_render_denoised_motion.  The context keeps every completed frame's noisy film on
  * the device (12 bytes per pixel) with its parameters and camera.  That frame is usable when the size is the same, the camera
  * is equal field by field and the temporal history is valid; pt_temporal_reset and pt_scene_upload drop it, pt_scene_update,
- * pt_scene_refit and pt_scene_rebuild keep it.  A moving camera thus gets no gradient (it would need the previous frame's
- * surface samples projected forward).  out_alpha (width*height floats) and the outputs that may be NULL there may be NULL. */
+ * pt_scene_refit and pt_scene_rebuild keep it.  A moved camera thus drops the previous frame here; a host whose camera moves
+ * calls pt_render_denoised_gradient_camera below, which keeps it.  out_alpha (width*height floats) and the outputs that may
+ * be NULL there may be NULL.                                                                                                */
 int pt_render_denoised_gradient(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
                                 const PtDenoise* dn, const PtTemporal* tp, const PtGradient* g, float* out_linear_rgb,
                                 uint8_t* out_rgba8, float* out_noisy_linear, float* out_features, int32_t* out_ids,
                                 float* out_alpha);
+
+/* Temporal gradients under a MOVING CAMERA (additive to ABI 6).  A pixel-list render is bit-identical to the same
+ * pixel of a full render for any camera, so the previous frame's samples re-traced in the current scene are a list render
+ * through the PREVIOUS camera; and the temporal kernels already compute where a current pixel's first-hit point lay in the
+ * previous image (rule 2 of PtTemporal).  The rule (pathtrace_amd/csrc/pt_gradient.h), cam and prev_cam of one size W x H:
+ *   strata       as above, in the PREVIOUS frame's image: the gradient pixel of stratum (bx, by) is a pixel of that image,
+ *                c_new its film through prev_cam with prev_params in the current scene, c_old d_prev_linear at that pixel
+ *   lookup       pixel p = (x, y) of cam with depth d_p from d_features.  cam equal to prev_cam field by field: (xi, yi) =
+ *                (x, y) for every pixel, misses included.  Otherwise d_alpha[p] = NaN ("no measurement") when d_p is not > 0
+ *                or the reprojection of rule 2 fails; else xi = floor(x' + 0.5), yi = floor(y' + 0.5), and d_alpha[p] = NaN
+ *                when (xi, yi) lies outside the image
+ *   weight       d_alpha[p] = the per-pixel rule above around the stratum of (xi, yi)
+ * The lookup uses the cameras alone, not the object motion maps: the re-trace runs in the current scene, so the stratum that
+ * measured the world point a pixel sees is the one where that point projects through prev_cam in the current pose.  A NaN
+ * entry is what pt_denoise_temporal_alpha_device reads as "take tp->alpha"; a pixel that falls outside the previous image is
+ * fresh there anyway, and a point that was occluded in the previous view fails that kernel's tap gates.
+ *
+ * pt_temporal_gradient_camera_device: pt_temporal_gradient_device's arguments, checks, buffers and asynchrony, with prev_cam
+ * (the camera d_prev_linear was rendered through) and d_features (the CURRENT frame's feature records of cam, 16-byte
+ * aligned).  Additionally PT_ERR_INVALID_ARG for a NULL prev_cam or d_features, a misaligned d_features and a prev_cam whose
+ * width or height differs from cam's; the context is then untouched.  With prev_cam equal to cam field by field d_alpha is
+ * bit-identical to pt_temporal_gradient_device's.  pt_debug_gradient_strata reads its strata, xy in the previous image.    */
+int pt_temporal_gradient_camera_device(PtContext* ctx, const PtCamera* cam, const PtCamera* prev_cam,
+                                       const PtRenderParams* prev_params, uint32_t seed, const float* d_prev_linear,
+                                       const float* d_features, const PtGradient* g, float alpha_min, float* d_alpha);
+/* pt_render_denoised_gradient with one difference: the previous frame is usable when the size is the same and the temporal
+ * history is valid -- the cameras need not be equal -- and the plane is pt_temporal_gradient_camera_device's with the previous
+ * frame's camera.  Both entries keep the previous frame in the same context state and may be mixed freely on one context;
+ * with an unmoved camera this one is bit-identical to pt_render_denoised_gradient.                                          */
+int pt_render_denoised_gradient_camera(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
+                                       const PtDenoise* dn, const PtTemporal* tp, const PtGradient* g, float* out_linear_rgb,
+                                       uint8_t* out_rgba8, float* out_noisy_linear, float* out_features, int32_t* out_ids,
+                                       float* out_alpha);
 
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on

@@ -236,6 +236,10 @@ SYMBOLS = {
                                                    _P(PtTemporal), C.c_void_p, C.c_void_p]),
     "pt_render_denoised_gradient": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
                                               _P(PtGradient), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_temporal_gradient_camera_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtCamera), _P(PtRenderParams), C.c_uint32, C.c_void_p,
+                                                     C.c_void_p, _P(PtGradient), C.c_float, C.c_void_p]),
+    "pt_render_denoised_gradient_camera": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
+                                                     _P(PtGradient), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

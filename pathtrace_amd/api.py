@@ -584,6 +584,26 @@ class _ContextFunctions:
         self.sync()
         return alpha.cpu().numpy()
 
+    def temporal_gradient_camera(self, cam, prev_cam, prev_params, seed, prev_linear, features, alpha_min=0.2, radius=None, scale=None):
+        """pt_temporal_gradient_camera_device: temporal_gradient under a moving camera.  prev_linear (f32[H,W,3]) is the previous
+        frame's film through prev_cam, features (f32[H,W,8]) the current frame's through cam -> the blend weight f32[H,W] of
+        cam's pixels, NaN where a pixel has no counterpart in the previous image."""
+        import torch
+        g = default_gradient(radius=radius, scale=scale)
+        prev_linear = np.ascontiguousarray(prev_linear, dtype=np.float32)
+        features = np.ascontiguousarray(features, dtype=np.float32)
+        H, W = cam.height, cam.width
+        assert prev_linear.shape == (H, W, 3) and features.shape == (H, W, 8)
+        dev = torch.device("cuda", self.device)
+        d_prev, d_feat = torch.from_numpy(prev_linear).to(dev), torch.from_numpy(features).to(dev)
+        alpha = torch.empty((H, W), dtype=torch.float32, device=dev)
+        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib().pt_temporal_gradient_camera_device(self._h, C.byref(cam), C.byref(prev_cam), C.byref(prev_params), seed,
+                                                       C.c_void_p(d_prev.data_ptr()), C.c_void_p(d_feat.data_ptr()), C.byref(g), alpha_min,
+                                                       C.c_void_p(alpha.data_ptr())))
+        self.sync()
+        return alpha.cpu().numpy()
+
     def debug_gradient_strata(self, width, height):
         """pt_debug_gradient_strata: the strata of the last temporal_gradient of a width x height image -> (xy u32[SH,SW,2],
         re-traced film f32[SH,SW,3], records f64[SH,SW,2] = delta, N)"""
@@ -621,7 +641,7 @@ class _ContextFunctions:
         return out.cpu().numpy(), rgba.cpu().numpy()
 
     def render_denoised_gradient(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
-                                 alpha=None, depth_tol=None, normal_tol=None, radius=None, scale=None):
+                                 alpha=None, depth_tol=None, normal_tol=None, radius=None, scale=None, _entry="pt_render_denoised_gradient"):
         """pt_render_denoised_gradient (host buffers, blocking): render_denoised_motion whose blend weight rises where the
         lighting changed since the previous call.  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3], features
         f32[H,W,8], ids i32[H,W], alpha f32[H,W]; all NaN without a usable previous frame)"""
@@ -635,11 +655,16 @@ class _ContextFunctions:
         feat = np.empty((H, W, 8), dtype=np.float32)
         ids = np.empty((H, W), dtype=np.int32)
         plane = np.empty((H, W), dtype=np.float32)
-        check(lib().pt_render_denoised_gradient(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp), C.byref(g),
-                                                lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
-                                                noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p),
-                                                ids.ctypes.data_as(C.c_void_p), plane.ctypes.data_as(C.c_void_p)))
+        check(getattr(lib(), _entry)(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp), C.byref(g),
+                                     lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
+                                     noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p),
+                                     ids.ctypes.data_as(C.c_void_p), plane.ctypes.data_as(C.c_void_p)))
         return lin, rgba, noisy, feat, ids, plane
+
+    def render_denoised_gradient_camera(self, cam, params, feature_samples=4, **kw):
+        """pt_render_denoised_gradient_camera: render_denoised_gradient that keeps its previous frame when the camera moved
+        (same arguments and results; NaN entries where a pixel has no counterpart in the previous image)."""
+        return self.render_denoised_gradient(cam, params, feature_samples, _entry="pt_render_denoised_gradient_camera", **kw)
 
     def ray_color(self, params, rays, xy):
         """pt_ray_color = RenderingStrategy::ray_color(world, ray, 0, rng(key xy, sample spp_offset), 1) -> f32[n,3]"""

@@ -384,11 +384,19 @@ void pt_default_gradient(PtGradient* out) {
 // render that may take the regenerating kernel, as pt_render_adaptive's passes do), the records and the plane.  The
 // arguments are checked before the context is looked at, and everything the list render checks is checked before the first
 // launch: a refused call leaves the context as it was.
-int pt_temporal_gradient_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prev, uint32_t seed, const float* d_prev,
-                                const PtGradient* g, float alpha_min, float* d_alpha) {
-    const char* const who = "pt_temporal_gradient_device";
-    if (!cam || !prev || !d_prev || !g || !d_alpha) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+//
+// with_camera (pt_temporal_gradient_camera_device): the strata lie in the image of prev_cam, whose re-trace
+// this is, and k_gradient_alpha_camera looks every pixel of cam up in them through d_features.
+static int gradient_impl(const char* who, PtContext* c, const PtCamera* cam, const PtCamera* prev_cam, bool with_camera,
+                         const PtRenderParams* prev, uint32_t seed, const float* d_prev, const float* d_features, const PtGradient* g,
+                         float alpha_min, float* d_alpha) {
+    if (!cam || !prev || !d_prev || !g || !d_alpha || (with_camera && (!prev_cam || !d_features)))
+        return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if ((uintptr_t)d_prev % 4u || (uintptr_t)d_alpha % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_prev_linear and d_alpha must be 4-byte aligned", who);
+    if (with_camera && (uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
+    if (with_camera && (prev_cam->width != cam->width || prev_cam->height != cam->height))
+        return fail(PT_ERR_INVALID_ARG, "%s: the previous camera is %ux%u, the camera %ux%u", who, prev_cam->width, prev_cam->height,
+                    cam->width, cam->height);
     if ((prev->band_count ? prev->band_count : 1) != 1 || prev->band_index != 0)
         return fail(PT_ERR_INVALID_ARG, "%s: works on the whole image (band_count = 1)", who);
     if (g->radius > ptgr::kMaxRadius) return fail(PT_ERR_INVALID_ARG, "%s: radius %u (at most %u)", who, g->radius, ptgr::kMaxRadius);
@@ -417,11 +425,37 @@ int pt_temporal_gradient_device(PtContext* c, const PtCamera* cam, const PtRende
     p.band_count = 1; p.band_index = 0; p.band_rows = 0;
     ListRender lr;
     lr.d_pixels = c->gr_list.p; lr.n = (uint32_t)ns; lr.regen = true;
-    if ((rc = render_impl(c, cam, &p, FilmState{}, &lr, c->gr_film.p, nullptr))) return rc;
+    if ((rc = render_impl(c, with_camera ? prev_cam : cam, &p, FilmState{}, &lr, c->gr_film.p, nullptr))) return rc;
     ptk::launch_gradient_strata(a, c->stream);
-    ptk::launch_gradient_alpha(a, c->stream);
+    if (with_camera) {
+        ptk::TemporalArgs t{};
+        t.dn.feat = reinterpret_cast<const float4*>(d_features);
+        t.dn.width = cam->width; t.dn.height = cam->height;
+        bool same = true;
+        for (int k = 0; k < 3; ++k) {
+            t.cur[k] = cam->origin[k]; t.cur[3 + k] = cam->lower_left[k]; t.cur[6 + k] = cam->horizontal[k]; t.cur[9 + k] = cam->vertical[k];
+            t.prev[k] = prev_cam->origin[k]; t.prev[3 + k] = prev_cam->lower_left[k];
+            t.prev[6 + k] = prev_cam->horizontal[k]; t.prev[9 + k] = prev_cam->vertical[k];
+            same = same && prev_cam->origin[k] == cam->origin[k] && prev_cam->lower_left[k] == cam->lower_left[k] &&
+                   prev_cam->horizontal[k] == cam->horizontal[k] && prev_cam->vertical[k] == cam->vertical[k];
+        }
+        t.same_camera = same;
+        ptk::launch_gradient_alpha_camera(a, t, c->stream);
+    } else {
+        ptk::launch_gradient_alpha(a, c->stream);
+    }
     HIP_TRY(hipGetLastError());
     return PT_OK;
+}
+
+int pt_temporal_gradient_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prev, uint32_t seed, const float* d_prev,
+                                const PtGradient* g, float alpha_min, float* d_alpha) {
+    return gradient_impl("pt_temporal_gradient_device", c, cam, nullptr, false, prev, seed, d_prev, nullptr, g, alpha_min, d_alpha);
+}
+
+int pt_temporal_gradient_camera_device(PtContext* c, const PtCamera* cam, const PtCamera* prev_cam, const PtRenderParams* prev, uint32_t seed,
+                                       const float* d_prev, const float* d_features, const PtGradient* g, float alpha_min, float* d_alpha) {
+    return gradient_impl("pt_temporal_gradient_camera_device", c, cam, prev_cam, true, prev, seed, d_prev, d_features, g, alpha_min, d_alpha);
 }
 
 // Debug: the strata of the last pt_temporal_gradient_device on this context copied back (blocking): per stratum its gradient
@@ -440,11 +474,11 @@ int pt_debug_gradient_strata(PtContext* c, uint32_t width, uint32_t height, uint
 }
 
 // pt_render_denoised_motion with the alpha plane between the ids pass and the accumulation, and the frame's noisy film kept
-// for the next call
-int pt_render_denoised_gradient(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
-                                const PtTemporal* tp, const PtGradient* g, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                                float* out_features, int32_t* out_ids, float* out_alpha) {
-    const char* const who = "pt_render_denoised_gradient";
+// for the next call.  any_camera (pt_render_denoised_gradient_camera): the previous frame stays usable when the camera moved,
+// and the plane is pt_temporal_gradient_camera_device's.
+static int render_gradient_impl(const char* who, bool any_camera, PtContext* c, const PtCamera* cam, const PtRenderParams* prm,
+                                uint32_t feature_samples, const PtDenoise* dn, const PtTemporal* tp, const PtGradient* g, float* out_linear,
+                                uint8_t* out_rgba, float* out_noisy, float* out_features, int32_t* out_ids, float* out_alpha) {
     if (!c || !cam || !prm || !dn || !tp || !g || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
         return fail(PT_ERR_INVALID_ARG, "%s: renders the whole image (band_count = 1)", who);
@@ -462,11 +496,13 @@ int pt_render_denoised_gradient(PtContext* c, const PtCamera* cam, const PtRende
     if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) ||
         (rc = c->dn_lin.ensure(3 * np)) || (rc = c->dn_ids.ensure(np)) || (rc = c->gr_alpha.ensure(np)))
         return rc;
-    // the previous frame is usable: this entry completed it, at this size, through this camera, and the history it went into is there
+    // the previous frame is usable: one of the two entries completed it, at this size, through this camera (any_camera: through
+    // any), and the history it went into is there
     bool usable = c->gr_valid && c->tm_valid && c->gr_prev.cap >= 3 * np && c->gr_cam.width == cam->width && c->gr_cam.height == cam->height;
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < 3 && !any_camera; ++k)
         usable = usable && c->gr_cam.origin[k] == cam->origin[k] && c->gr_cam.lower_left[k] == cam->lower_left[k] &&
                  c->gr_cam.horizontal[k] == cam->horizontal[k] && c->gr_cam.vertical[k] == cam->vertical[k];
+    const PtCamera prev_cam = c->gr_cam;
     c->gr_valid = false;                      // (a frame that fails from here on leaves none)
     PtRenderParams p = *prm;
     p.band_count = 1; p.band_index = 0; p.band_rows = 0;
@@ -477,7 +513,10 @@ int pt_render_denoised_gradient(PtContext* c, const PtCamera* cam, const PtRende
         (rc = pt_render_feature_ids_device(c, cam, &p, c->dn_ids.p)))
         return rc;
     if (usable) {
-        if ((rc = pt_temporal_gradient_device(c, cam, &c->gr_params, c->gr_frame, c->gr_prev.p, g, tp->alpha, c->gr_alpha.p))) return rc;
+        if ((rc = any_camera ? pt_temporal_gradient_camera_device(c, cam, &prev_cam, &c->gr_params, c->gr_frame, c->gr_prev.p, feat, g,
+                                                                  tp->alpha, c->gr_alpha.p)
+                             : pt_temporal_gradient_device(c, cam, &c->gr_params, c->gr_frame, c->gr_prev.p, g, tp->alpha, c->gr_alpha.p)))
+            return rc;
     } else {
         HIP_TRY(hipMemsetAsync(c->gr_alpha.p, 0xFF, np * sizeof(float), c->stream));      // every entry a NaN: no measurement
     }
@@ -494,6 +533,20 @@ int pt_render_denoised_gradient(PtContext* c, const PtCamera* cam, const PtRende
     if (out_ids) HIP_TRY(hipMemcpy(out_ids, c->dn_ids.p, np * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (out_alpha) HIP_TRY(hipMemcpy(out_alpha, c->gr_alpha.p, np * sizeof(float), hipMemcpyDeviceToHost));
     return PT_OK;
+}
+
+int pt_render_denoised_gradient(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
+                                const PtTemporal* tp, const PtGradient* g, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                                float* out_features, int32_t* out_ids, float* out_alpha) {
+    return render_gradient_impl("pt_render_denoised_gradient", false, c, cam, prm, feature_samples, dn, tp, g, out_linear, out_rgba, out_noisy,
+                                out_features, out_ids, out_alpha);
+}
+
+int pt_render_denoised_gradient_camera(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
+                                       const PtDenoise* dn, const PtTemporal* tp, const PtGradient* g, float* out_linear, uint8_t* out_rgba,
+                                       float* out_noisy, float* out_features, int32_t* out_ids, float* out_alpha) {
+    return render_gradient_impl("pt_render_denoised_gradient_camera", true, c, cam, prm, feature_samples, dn, tp, g, out_linear, out_rgba,
+                                out_noisy, out_features, out_ids, out_alpha);
 }
 
 int pt_render_denoised_temporal(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,

@@ -1,5 +1,5 @@
 // pt_gradient.h -- the temporal gradient of pt_temporal_gradient_device, written once for the kernels
-// (k_gradient_list, k_gradient_strata, k_gradient_alpha in pt_kernels_film.hip), the host and the host compilers of the CPU
+// (k_gradient_list, k_gradient_strata, k_gradient_alpha, k_gradient_alpha_camera in pt_kernels_film.hip), the host and the host compilers of the CPU
 // tests (tests/test_gradient_cpu.py).  Plain f64 arithmetic, like pt_adaptive.h; build with -ffp-contract=off.
 //
 // Strata: the image W x H is cut into 3 x 3 blocks, SW = ceil(W / 3) by SH = ceil(H / 3) of them, clipped at the right and
@@ -13,6 +13,13 @@
 //   lambda = 1 when a record of the window is not finite;  min(1, scale D / Nn) when Nn > 0;  0 otherwise
 //   alpha_p = (float)(alpha_min + lambda (1 - alpha_min))        (alpha_min, scale widened to f64 first)
 // D = 0 gives alpha_p == alpha_min exactly.
+//
+// Under a moving camera (pt_temporal_gradient_camera_device, k_gradient_alpha_camera) the strata, their list,
+// re-trace and records are those above in the PREVIOUS frame's image (rendered through the previous camera), and a pixel of
+// the current image takes the window around the stratum of the previous-image pixel its first-hit point projects to: with
+// (x', y') the reprojection of rule 2 of PtTemporal, (xi, yi) = (floor(x' + 0.5), floor(y' + 0.5)) -- lookup_pixel -- and
+// alpha_p = pixel_alpha(rec, SW, SH, xi, yi, ...).  No measurement (NaN) where the pixel has no depth, the reprojection fails
+// or (xi, yi) lies outside the image.  Cameras equal field by field: (xi, yi) = (x, y) for every pixel, misses included.
 #pragma once
 #include "pt_adaptive.h"
 
@@ -62,6 +69,15 @@ PT_AD_HD float pixel_alpha(const double* rec, unsigned SW, unsigned SH, unsigned
     }
     const double a = (double)alpha_min;
     return (float)(a + lambda * (1.0 - a));
+}
+
+// The nearest pixel of the previous image to (xr, yr); false when it lies outside the W x H image (or a coordinate is NaN).
+PT_AD_HD bool lookup_pixel(double xr, double yr, unsigned W, unsigned H, unsigned* xi, unsigned* yi) {
+    const double fx = __builtin_floor(xr + 0.5), fy = __builtin_floor(yr + 0.5);
+    if (!(fx >= 0.0 && fx < (double)W && fy >= 0.0 && fy < (double)H)) return false;
+    *xi = (unsigned)fx;
+    *yi = (unsigned)fy;
+    return true;
 }
 
 }  // namespace ptgr

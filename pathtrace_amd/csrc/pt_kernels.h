@@ -368,6 +368,10 @@ struct GradientArgs {
 void launch_gradient_list(const GradientArgs& a, hipStream_t st);
 void launch_gradient_strata(const GradientArgs& a, hipStream_t st);
 void launch_gradient_alpha(const GradientArgs& a, hipStream_t st);
+// ... under a moving camera (pt_temporal_gradient_camera_device): the strata lie in the previous frame's image,
+// and k_gradient_alpha_camera in place of k_gradient_alpha looks every current pixel's stratum up through the temporal
+// reprojection.  Of t it reads dn.feat, dn.width, dn.height, cur (the frame's camera), prev (the previous frame's) and same_camera.
+void launch_gradient_alpha_camera(const GradientArgs& a, const TemporalArgs& t, hipStream_t st);
 
 // Device-side BVH refit (pt_scene_refit; rule: ptbvh::refit in pt_bvh.h, whose arrays these launches reproduce bit for bit).
 // The topology -- ids, child codes, the order of the nodes by height -- stays; leaf records, child boxes and their quantisation

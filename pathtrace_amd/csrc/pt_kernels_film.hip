@@ -1149,6 +1149,23 @@ __global__ void __launch_bounds__(kDnBx * kDnBy) k_gradient_alpha(GradientArgs a
     if (x >= a.width || y >= a.height) return;
     a.alpha[(size_t)y * a.width + x] = ptgr::pixel_alpha(a.rec, ptgr::strata(a.width), ptgr::strata(a.height), x, y, a.radius, a.scale, a.alpha_min);
 }
+// ... under a moving camera: the records are those of the previous frame's image; the pixel's first-hit point
+// goes through tm_reproject (f64, the temporal kernel's own lookup) to the previous-image pixel whose stratum measured it.
+// One float4 of features, the solve, then the window of 16-byte records; NaN where there is nothing to look up.
+__global__ void __launch_bounds__(kDnBx * kDnBy) k_gradient_alpha_camera(GradientArgs a, TemporalArgs t) {
+    const uint32_t x = blockIdx.x * kDnBx + threadIdx.x, y = blockIdx.y * kDnBy + threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    const size_t p = (size_t)y * a.width + x;
+    uint32_t xi = x, yi = y;
+    bool ok = true;
+    if (!t.same_camera) {
+        const float d = t.dn.feat[2 * p + 1].w;
+        double xr = 0.0, yr = 0.0, dexp = 0.0;
+        ok = d > 0.0f && tm_reproject(t, x, y, d, xr, yr, dexp) && ptgr::lookup_pixel(xr, yr, a.width, a.height, &xi, &yi);
+    }
+    a.alpha[p] = ok ? ptgr::pixel_alpha(a.rec, ptgr::strata(a.width), ptgr::strata(a.height), xi, yi, a.radius, a.scale, a.alpha_min)
+                    : __builtin_nanf("");
+}
 }  // namespace PTK_IMPL
 namespace ptk {
 void launch_gradient_list(const GradientArgs& a, hipStream_t st) {
@@ -1162,6 +1179,10 @@ void launch_gradient_strata(const GradientArgs& a, hipStream_t st) {
 void launch_gradient_alpha(const GradientArgs& a, hipStream_t st) {
     const dim3 g((a.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy), b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
     hipLaunchKernelGGL(PTK_IMPL::k_gradient_alpha, g, b, 0, st, a);
+}
+void launch_gradient_alpha_camera(const GradientArgs& a, const TemporalArgs& t, hipStream_t st) {
+    const dim3 g((a.width + PTK_IMPL::kDnBx - 1) / PTK_IMPL::kDnBx, (a.height + PTK_IMPL::kDnBy - 1) / PTK_IMPL::kDnBy), b(PTK_IMPL::kDnBx, PTK_IMPL::kDnBy);
+    hipLaunchKernelGGL(PTK_IMPL::k_gradient_alpha_camera, g, b, 0, st, a, t);
 }
 }  // namespace ptk
 

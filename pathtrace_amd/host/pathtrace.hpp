@@ -15,6 +15,7 @@
 //   World::render_denoised_temporal()  the same with temporal accumulation over the frames of the persistent context
 //   World::render_denoised_motion()    ... whose history also follows objects moved with set_object() + scene_update()
 //   World::render_denoised_gradient()  ... and forgets faster where the lighting changed (temporal gradients)
+//   World::render_denoised_gradient_camera()  ... also while the camera moves
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -560,6 +561,19 @@ public:
     void render_denoised_gradient(uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, const PtTemporal* tp = nullptr,
                                   const PtGradient* gr = nullptr, std::vector<int32_t>* ids = nullptr, std::vector<float>* alpha = nullptr,
                                   int device = 0) {
+        render_gradient(false, feature_samples, dn, tp, gr, ids, alpha, device);
+    }
+    // render_denoised_gradient() that keeps its previous frame across set_camera() (pt_render_denoised_gradient_camera): the
+    // previous frame's samples are re-traced through the previous camera and every pixel looks its block up through the
+    // temporal reprojection.  alpha is NaN where a pixel has no counterpart in the previous image.  The two may be mixed.
+    void render_denoised_gradient_camera(uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, const PtTemporal* tp = nullptr,
+                                         const PtGradient* gr = nullptr, std::vector<int32_t>* ids = nullptr,
+                                         std::vector<float>* alpha = nullptr, int device = 0) {
+        render_gradient(true, feature_samples, dn, tp, gr, ids, alpha, device);
+    }
+private:
+    void render_gradient(bool any_camera, uint32_t feature_samples, const PtDenoise* dn, const PtTemporal* tp, const PtGradient* gr,
+                         std::vector<int32_t>* ids, std::vector<float>* alpha, int device) {
         scene(device);
         resize_film();
         PtRenderParams p = params_;
@@ -575,10 +589,13 @@ public:
         std::vector<uint8_t> rgba(n * 4);
         if (ids) ids->resize(n);
         if (alpha) alpha->resize(n);
-        check(pt_render_denoised_gradient(ctx_, &camera_.pod(), &p, feature_samples, &d, &t, &g, lin.data(), rgba.data(), nullptr, nullptr,
-                                          ids ? ids->data() : nullptr, alpha ? alpha->data() : nullptr));
+        int32_t* const pi = ids ? ids->data() : nullptr;
+        float* const pa = alpha ? alpha->data() : nullptr;
+        if (any_camera) check(pt_render_denoised_gradient_camera(ctx_, &camera_.pod(), &p, feature_samples, &d, &t, &g, lin.data(), rgba.data(), nullptr, nullptr, pi, pa));
+        else check(pt_render_denoised_gradient(ctx_, &camera_.pod(), &p, feature_samples, &d, &t, &g, lin.data(), rgba.data(), nullptr, nullptr, pi, pa));
         unpack(lin, rgba);
     }
+public:
     // the next render_denoised_temporal starts without history (pt_temporal_reset)
     void temporal_reset() { if (ctx_) check(pt_temporal_reset(ctx_)); }
     // moves the camera (the film follows its size); the temporal history stays and is reprojected

@@ -288,6 +288,8 @@ extern "C" {
     pub fn pt_debug_gradient_strata(ctx: *mut PtContext, width: u32, height: u32, out_xy: *mut u32, out_film: *mut f32, out_rec: *mut f64) -> c_int;
     pub fn pt_denoise_temporal_alpha_device(ctx: *mut PtContext, cam: *const PtCamera, d_linear_rgb: *const f32, d_features: *const f32, d_ids: *const i32, d_alpha: *const f32, dn: *const PtDenoise, tp: *const PtTemporal, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_denoised_gradient(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, tp: *const PtTemporal, g: *const PtGradient, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32, out_ids: *mut i32, out_alpha: *mut f32) -> c_int;
+    pub fn pt_temporal_gradient_camera_device(ctx: *mut PtContext, cam: *const PtCamera, prev_cam: *const PtCamera, prev_params: *const PtRenderParams, seed: u32, d_prev_linear: *const f32, d_features: *const f32, g: *const PtGradient, alpha_min: f32, d_alpha: *mut f32) -> c_int;
+    pub fn pt_render_denoised_gradient_camera(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, tp: *const PtTemporal, g: *const PtGradient, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32, out_ids: *mut i32, out_alpha: *mut f32) -> c_int;
     pub fn pt_ray_color(ctx: *mut PtContext, params: *const PtRenderParams, rays: *const f64, xy: *const u32, n: u32, out_rgb: *mut f32) -> c_int;
     pub fn pt_debug_hit_scene(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_t: *mut f32) -> c_int;
     pub fn pt_debug_hit_records(ctx: *mut PtContext, rays: *const f64, n: u32, t_min: f64, t_max: f64, exact_math: u32, accel: u32, out_id: *mut i32, out_rec: *mut f32) -> c_int;

@@ -12,7 +12,17 @@ iterations = 0 (one kernel each) on the same buffers.
 quality: relMSE per frame against a 1024-spp reference of the frame's scene (samples from 10^6), non-emitter pixels, for
 both calls on (a) "moving": C2, the smallest sphere crosses the floor by 0.02 per frame (the sequence of
 tools/temporal_bench.py --moving) and (b) "dimmed": C2, eight static frames, then every emission x 0.25 and twelve more.
-frames_to_steady: frames after the change until relMSE is back within 1.25 x the median of the four frames before it."""
+frames_to_steady: frames after the change until relMSE is back within 1.25 x the median of the four frames before it.
+
+    python tools/gradient_bench.py --camera [--size 1024] [--paths fixed,orbit] [--quality-size 128] [--skip-quality]
+--camera: the moving-camera entry (pt_render_denoised_gradient_camera).  cost: C2 at --size, static scene, 2 spp; per path a
+context of its own: "existing" pt_render_denoised_gradient and "fixed" the new entry under one camera, "orbit" the new entry
+under the orbit of examples/gradient_frames.cpp --camera (one step per frame, so k_gradient_alpha_camera solves the
+reprojection).  A round is three frames of every path, the paths alternating frame by frame; one untimed round, then seven
+timed: wall ms per frame as median [min, max] of the rounds.  --paths limits the new entry's paths (a kernel trace of
+--paths orbit holds only reprojecting dispatches of k_gradient_alpha_camera).  quality: C2, the orbit, the light dimmed to a
+quarter from frame 8 of 20: relMSE per frame (non-emitter pixels, against 1024 spp through the frame's camera) of the motion
+entry, the existing gradient entry and the new one."""
 import argparse
 import ctypes as C
 import json
@@ -135,13 +145,100 @@ def quality(name, S):
     return res
 
 
+def orbit(k, S, step=0.006):
+    """examples/gradient_frames.cpp --camera: the point of the circle of radius 2 whose half-angle tangent is step * k"""
+    t = step * k
+    q = 1.0 + t * t
+    return pt.camera_look_at((2.0 * (2.0 * t) / q, 0.0, 2.0 * (1.0 - t * t) / q), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), S, S, 35.0)
+
+
+def camera_cost(S, paths, rounds=7, per_round=3):
+    objs = pt.builtin_scene(2)
+    calls = {"existing": "render_denoised_gradient"}
+    calls.update({p: "render_denoised_gradient_camera" for p in paths})
+    ctx = {name: pt.Context(0) for name in calls}
+    for c in ctx.values():
+        c.upload(objs)
+    times = {name: [] for name in calls}
+    measured = {}
+    frame = 0
+    for r in range(rounds + 1):
+        spent = {name: 0.0 for name in calls}
+        for _ in range(per_round):
+            p = pt.default_params(spp=2, spp_offset=2 * frame)
+            for name, call in calls.items():
+                cam = orbit(frame if name == "orbit" else 0, S)
+                t0 = time.perf_counter()
+                f = getattr(ctx[name], call)(cam, p, 2)
+                spent[name] += time.perf_counter() - t0
+                measured[name] = round(float(np.mean(~np.isnan(f[5]))), 4)
+            frame += 1
+        if r:
+            for name in calls:
+                times[name].append(spent[name] / per_round * 1e3)
+    for c in ctx.values():
+        c.close()
+    return {name: {"frame_ms_median": round(statistics.median(t), 3), "frame_ms_min": round(min(t), 3), "frame_ms_max": round(max(t), 3),
+                   "measured_last_frame": measured[name]} for name, t in times.items()}
+
+
+def camera_quality(S, N=20, change=8):
+    base = pt.builtin_scene(2)
+    dim = copy(base)
+    for o in dim:
+        if o.mat_tag == 1:
+            for k in range(3):
+                o.mat[k] *= 0.25
+    calls = {"motion": "render_denoised_motion", "gradient": "render_denoised_gradient", "gradient_camera": "render_denoised_gradient_camera"}
+    ctx = {name: pt.Context(0) for name in calls}
+    r = pt.Context(0)
+    for c in list(ctx.values()) + [r]:
+        c.upload(base)
+    rel = {name: [] for name in calls}
+    measured, raised = [], []
+    for i in range(N):
+        cam = orbit(i, S)
+        if i == change:
+            for c in list(ctx.values()) + [r]:
+                c.scene_update(dim)
+        ref = r.render(cam, pt.default_params(spp=1024, spp_offset=10 ** 6))[0].cpu().numpy().astype(np.float64)
+        p = pt.default_params(spp=2, spp_offset=2 * i)
+        for name, call in calls.items():
+            f = getattr(ctx[name], call)(cam, p, 2)
+            keep = f[3][..., 3] == 0
+            rel[name].append(round(float(np.mean(((f[0].astype(np.float64) - ref) ** 2 / (ref ** 2 + 0.01))[keep])), 5))
+            if name == "gradient":
+                assert np.isnan(f[5]).all()                     # the camera moved: the existing entry measures nothing
+            if name == "gradient_camera":
+                measured.append(round(float(np.mean(~np.isnan(f[5]))), 4))
+                raised.append(round(float(np.mean(f[5] > np.float32(0.2))), 4))
+    res = {"frames": N, "change_at": change, "measured": measured, "alpha_raised": raised}
+    for name in calls:
+        steady = statistics.median(rel[name][change - 4:change])
+        res["relmse_" + name] = rel[name]
+        res["steady_" + name] = steady
+        res["frames_to_steady_" + name] = next((k for k, v in enumerate(rel[name][change:]) if v <= 1.25 * steady), None)
+    for c in list(ctx.values()) + [r]:
+        c.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--camera", action="store_true")
+    ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--paths", default="fixed,orbit")
     ap.add_argument("--frames", type=int, default=14)
     ap.add_argument("--sizes", default="128,1024")
     ap.add_argument("--quality-size", type=int, default=128)
     ap.add_argument("--skip-quality", action="store_true")
     args = ap.parse_args()
+    if args.camera:
+        res = {"spp_per_frame": 2, "feature_samples": 2, "camera_cost": {f"c2_{args.size}": camera_cost(args.size, args.paths.split(","))}}
+        if not args.skip_quality:
+            res["camera_quality"] = camera_quality(args.quality_size)
+        print(json.dumps(res))
+        return
     res = {"spp_per_frame": 2, "feature_samples": 2, "cost": {}}
     for scene, label in ((2, "c2"), (1, "world_new")):
         for S in (int(s) for s in args.sizes.split(",")):
