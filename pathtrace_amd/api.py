@@ -376,84 +376,79 @@ class _ContextFunctions:
                                        err.ctypes.data_as(C.c_void_p)))
         return lin, rgba, spp, err
 
+    # ---- the denoiser entries.  What their bindings share: device entries upload host arrays, run on torch's current stream
+    # and hand back host arrays; blocking render entries fill host planes.
+    def _upload(self, a, dtype, shape):
+        """a host array as dtype, which must have this shape -> the device tensor"""
+        import torch
+        a = np.ascontiguousarray(a, dtype=dtype)
+        assert a.shape == shape, (a.shape, shape)
+        return torch.from_numpy(a).to(torch.device("cuda", self.device))
+
+    def _empty(self, shape, dtype="float32"):
+        import torch
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=torch.device("cuda", self.device))
+
+    def _film_pair(self, H, W):
+        """-> the device tensors (linear f32[H,W,3], rgba u8[H,W,4]) a filter entry writes"""
+        return self._empty((H, W, 3)), self._empty((H, W, 4), "uint8")
+
+    def _on_stream(self, entry, *args):
+        """entry(context, *args) on torch's current stream, checked, then pt_sync; a tensor passes as its device address"""
+        import torch
+        self.set_stream(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        check(entry(self._h, *[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]))
+        self.sync()
+
+    @staticmethod
+    def _host_planes(H, W, *specs):
+        """specs (channels, dtype; 0 channels: [H,W]) -> (the uninitialised arrays, their addresses); None stays None in both"""
+        planes = [None if s is None else np.empty((H, W, s[0]) if s[0] else (H, W), dtype=s[1]) for s in specs]
+        return tuple(planes), [None if a is None else a.ctypes.data_as(C.c_void_p) for a in planes]
+
     def render_features(self, cam, params, n_samples):
         """pt_render_features_device: first-hit records of samples spp_offset .. spp_offset + n_samples - 1.
         -> f32[H,W,8] = albedo rgb, emitter, normal xyz, depth"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        feat = torch.empty((cam.height, cam.width, 8), dtype=torch.float32, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_render_features_device(self._h, C.byref(cam), C.byref(params), n_samples, C.c_void_p(feat.data_ptr())))
-        self.sync()
+        feat = self._empty((cam.height, cam.width, 8))
+        self._on_stream(lib().pt_render_features_device, C.byref(cam), C.byref(params), n_samples, feat)
         return feat.cpu().numpy()
 
     def denoise(self, linear, features, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
         """pt_denoise_device on a film (f32[H,W,3]) and its features (f32[H,W,8]); unset parameters take pt_default_denoise.
         -> (linear f32[H,W,3], rgba u8[H,W,4])"""
-        import torch
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
-        linear = np.ascontiguousarray(linear, dtype=np.float32)
-        features = np.ascontiguousarray(features, dtype=np.float32)
-        H, W = linear.shape[:2]
-        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8)
-        dev = torch.device("cuda", self.device)
-        d_lin, d_feat = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev)
-        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_denoise_device(self._h, W, H, C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()), C.byref(dn),
-                                      C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
-        self.sync()
+        H, W = np.shape(linear)[:2]
+        d_lin, d_feat = self._upload(linear, np.float32, (H, W, 3)), self._upload(features, np.float32, (H, W, 8))
+        out, rgba = self._film_pair(H, W)
+        self._on_stream(lib().pt_denoise_device, W, H, d_lin, d_feat, C.byref(dn), out, rgba)
         return out.cpu().numpy(), rgba.cpu().numpy()
 
     def render_denoised(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
         """pt_render_denoised (host buffers, blocking).  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3],
         features f32[H,W,8])"""
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
-        H, W = cam.height, cam.width
-        lin = np.empty((H, W, 3), dtype=np.float32)
-        rgba = np.empty((H, W, 4), dtype=np.uint8)
-        noisy = np.empty((H, W, 3), dtype=np.float32)
-        feat = np.empty((H, W, 8), dtype=np.float32)
-        check(lib().pt_render_denoised(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn),
-                                       lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
-                                       noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p)))
-        return lin, rgba, noisy, feat
+        planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32))
+        check(lib().pt_render_denoised(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), *ptrs))
+        return planes
 
     def denoise_var(self, linear, features, var, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
         """pt_denoise_var_device: denoise() with a variance plane (f32[H,W], in units of the demodulated luminance squared); an
         entry that is NaN, infinite or negative takes the filter's own 3x3 variance.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
-        import torch
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
-        linear = np.ascontiguousarray(linear, dtype=np.float32)
-        features = np.ascontiguousarray(features, dtype=np.float32)
-        var = np.ascontiguousarray(var, dtype=np.float32)
-        H, W = linear.shape[:2]
-        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8) and var.shape == (H, W)
-        dev = torch.device("cuda", self.device)
-        d_lin, d_feat, d_var = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev), torch.from_numpy(var).to(dev)
-        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_denoise_var_device(self._h, W, H, C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()),
-                                          C.c_void_p(d_var.data_ptr()), C.byref(dn), C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(rgba.data_ptr())))
-        self.sync()
+        H, W = np.shape(linear)[:2]
+        d_lin, d_feat = self._upload(linear, np.float32, (H, W, 3)), self._upload(features, np.float32, (H, W, 8))
+        d_var = self._upload(var, np.float32, (H, W))
+        out, rgba = self._film_pair(H, W)
+        self._on_stream(lib().pt_denoise_var_device, W, H, d_lin, d_feat, d_var, C.byref(dn), out, rgba)
         return out.cpu().numpy(), rgba.cpu().numpy()
 
     def adaptive_variance(self, features):
         """pt_adaptive_variance_device: the variance plane of the context's last completed render_adaptive, whose size
         features (f32[H,W,8]) must have.  -> f32[H,W]"""
-        import torch
-        features = np.ascontiguousarray(features, dtype=np.float32)
-        H, W = features.shape[:2]
-        assert features.shape == (H, W, 8)
-        dev = torch.device("cuda", self.device)
-        d_feat = torch.from_numpy(features).to(dev)
-        var = torch.empty((H, W), dtype=torch.float32, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_adaptive_variance_device(self._h, W, H, C.c_void_p(d_feat.data_ptr()), C.c_void_p(var.data_ptr())))
-        self.sync()
+        H, W = np.shape(features)[:2]
+        d_feat = self._upload(features, np.float32, (H, W, 8))
+        var = self._empty((H, W))
+        self._on_stream(lib().pt_adaptive_variance_device, W, H, d_feat, var)
         return var.cpu().numpy()
 
     def render_adaptive_denoised(self, cam, params, spp_min, spp_step, rel_tol, abs_floor=1e-3, feature_samples=4, iterations=None,
@@ -463,17 +458,10 @@ class _ContextFunctions:
         rel_err f32[H,W], var f32[H,W]); extras=False asks for the denoised linear film alone (the others are None)."""
         ad = _lib.PtAdaptive(spp_min, spp_step, rel_tol, abs_floor)
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
-        H, W = cam.height, cam.width
-        lin = np.empty((H, W, 3), dtype=np.float32)
-        rgba = np.empty((H, W, 4), dtype=np.uint8) if extras else None
-        noisy = np.empty((H, W, 3), dtype=np.float32) if extras else None
-        spp = np.empty((H, W), dtype=np.uint32) if extras else None
-        err = np.empty((H, W), dtype=np.float32) if extras else None
-        var = np.empty((H, W), dtype=np.float32) if extras else None
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        check(lib().pt_render_adaptive_denoised(self._h, C.byref(cam), C.byref(params), C.byref(ad), feature_samples, C.byref(dn),
-                                                ptr(lin), ptr(rgba), ptr(noisy), ptr(spp), ptr(err), ptr(var)))
-        return lin, rgba, noisy, spp, err, var
+        more = ((4, np.uint8), (3, np.float32), (0, np.uint32), (0, np.float32), (0, np.float32)) if extras else (None,) * 5
+        planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), *more)
+        check(lib().pt_render_adaptive_denoised(self._h, C.byref(cam), C.byref(params), C.byref(ad), feature_samples, C.byref(dn), *ptrs))
+        return planes
 
     def temporal_reset(self):
         """pt_temporal_reset: the next temporal frame starts without history."""
@@ -483,21 +471,12 @@ class _ContextFunctions:
                          depth_tol=None, normal_tol=None):
         """pt_denoise_temporal_device on a film (f32[H,W,3]) of camera cam and its features (f32[H,W,8]), against the
         context's history; unset parameters take pt_default_denoise / pt_default_temporal.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
-        import torch
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
         tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
-        linear = np.ascontiguousarray(linear, dtype=np.float32)
-        features = np.ascontiguousarray(features, dtype=np.float32)
         H, W = cam.height, cam.width
-        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8)
-        dev = torch.device("cuda", self.device)
-        d_lin, d_feat = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev)
-        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_denoise_temporal_device(self._h, C.byref(cam), C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()),
-                                               C.byref(dn), C.byref(tp), C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
-        self.sync()
+        d_lin, d_feat = self._upload(linear, np.float32, (H, W, 3)), self._upload(features, np.float32, (H, W, 8))
+        out, rgba = self._film_pair(H, W)
+        self._on_stream(lib().pt_denoise_temporal_device, C.byref(cam), d_lin, d_feat, C.byref(dn), C.byref(tp), out, rgba)
         return out.cpu().numpy(), rgba.cpu().numpy()
 
     def render_denoised_temporal(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
@@ -506,47 +485,27 @@ class _ContextFunctions:
         rgba u8[H,W,4], noisy linear f32[H,W,3], features f32[H,W,8])"""
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
         tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
-        H, W = cam.height, cam.width
-        lin = np.empty((H, W, 3), dtype=np.float32)
-        rgba = np.empty((H, W, 4), dtype=np.uint8)
-        noisy = np.empty((H, W, 3), dtype=np.float32)
-        feat = np.empty((H, W, 8), dtype=np.float32)
-        check(lib().pt_render_denoised_temporal(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp),
-                                                lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
-                                                noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p)))
-        return lin, rgba, noisy, feat
+        planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32))
+        check(lib().pt_render_denoised_temporal(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp), *ptrs))
+        return planes
 
     def feature_ids(self, cam, params):
         """pt_render_feature_ids_device: the object hit by the primary ray of sample spp_offset, -1 for a miss -> i32[H,W]"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        ids = torch.empty((cam.height, cam.width), dtype=torch.int32, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_render_feature_ids_device(self._h, C.byref(cam), C.byref(params), C.c_void_p(ids.data_ptr())))
-        self.sync()
+        ids = self._empty((cam.height, cam.width), "int32")
+        self._on_stream(lib().pt_render_feature_ids_device, C.byref(cam), C.byref(params), ids)
         return ids.cpu().numpy()
 
     def denoise_temporal_motion(self, cam, linear, features, ids, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
                                 alpha=None, depth_tol=None, normal_tol=None):
         """pt_denoise_temporal_motion_device: denoise_temporal with the per-pixel object ids (i32[H,W]); the history follows
         the objects moved by scene_update since the last temporal frame.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
-        import torch
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
         tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
-        linear = np.ascontiguousarray(linear, dtype=np.float32)
-        features = np.ascontiguousarray(features, dtype=np.float32)
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
         H, W = cam.height, cam.width
-        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8) and ids.shape == (H, W)
-        dev = torch.device("cuda", self.device)
-        d_lin, d_feat, d_ids = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev), torch.from_numpy(ids).to(dev)
-        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_denoise_temporal_motion_device(self._h, C.byref(cam), C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()),
-                                                      C.c_void_p(d_ids.data_ptr()), C.byref(dn), C.byref(tp),
-                                                      C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
-        self.sync()
+        d_lin, d_feat = self._upload(linear, np.float32, (H, W, 3)), self._upload(features, np.float32, (H, W, 8))
+        d_ids = self._upload(ids, np.int32, (H, W))
+        out, rgba = self._film_pair(H, W)
+        self._on_stream(lib().pt_denoise_temporal_motion_device, C.byref(cam), d_lin, d_feat, d_ids, C.byref(dn), C.byref(tp), out, rgba)
         return out.cpu().numpy(), rgba.cpu().numpy()
 
     def render_denoised_motion(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
@@ -555,116 +514,74 @@ class _ContextFunctions:
         -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3], features f32[H,W,8], ids i32[H,W])"""
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
         tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
-        H, W = cam.height, cam.width
-        lin = np.empty((H, W, 3), dtype=np.float32)
-        rgba = np.empty((H, W, 4), dtype=np.uint8)
-        noisy = np.empty((H, W, 3), dtype=np.float32)
-        feat = np.empty((H, W, 8), dtype=np.float32)
-        ids = np.empty((H, W), dtype=np.int32)
-        check(lib().pt_render_denoised_motion(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp),
-                                              lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
-                                              noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p),
-                                              ids.ctypes.data_as(C.c_void_p)))
-        return lin, rgba, noisy, feat, ids
+        planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32), (0, np.int32))
+        check(lib().pt_render_denoised_motion(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp), *ptrs))
+        return planes
 
     def temporal_gradient(self, cam, prev_params, seed, prev_linear, alpha_min=0.2, radius=None, scale=None):
         """pt_temporal_gradient_device: the previous frame's samples (prev_params, film prev_linear f32[H,W,3]) re-traced in
         the current scene on one pixel per 3 x 3 stratum -> the per-pixel blend weight f32[H,W] for denoise_temporal_alpha."""
-        import torch
         g = default_gradient(radius=radius, scale=scale)
-        prev_linear = np.ascontiguousarray(prev_linear, dtype=np.float32)
         H, W = cam.height, cam.width
-        assert prev_linear.shape == (H, W, 3)
-        dev = torch.device("cuda", self.device)
-        d_prev = torch.from_numpy(prev_linear).to(dev)
-        alpha = torch.empty((H, W), dtype=torch.float32, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_temporal_gradient_device(self._h, C.byref(cam), C.byref(prev_params), seed, C.c_void_p(d_prev.data_ptr()), C.byref(g),
-                                                alpha_min, C.c_void_p(alpha.data_ptr())))
-        self.sync()
+        d_prev = self._upload(prev_linear, np.float32, (H, W, 3))
+        alpha = self._empty((H, W))
+        self._on_stream(lib().pt_temporal_gradient_device, C.byref(cam), C.byref(prev_params), seed, d_prev, C.byref(g), alpha_min, alpha)
         return alpha.cpu().numpy()
 
     def temporal_gradient_camera(self, cam, prev_cam, prev_params, seed, prev_linear, features, alpha_min=0.2, radius=None, scale=None):
         """pt_temporal_gradient_camera_device: temporal_gradient under a moving camera.  prev_linear (f32[H,W,3]) is the previous
         frame's film through prev_cam, features (f32[H,W,8]) the current frame's through cam -> the blend weight f32[H,W] of
         cam's pixels, NaN where a pixel has no counterpart in the previous image."""
-        import torch
         g = default_gradient(radius=radius, scale=scale)
-        prev_linear = np.ascontiguousarray(prev_linear, dtype=np.float32)
-        features = np.ascontiguousarray(features, dtype=np.float32)
         H, W = cam.height, cam.width
-        assert prev_linear.shape == (H, W, 3) and features.shape == (H, W, 8)
-        dev = torch.device("cuda", self.device)
-        d_prev, d_feat = torch.from_numpy(prev_linear).to(dev), torch.from_numpy(features).to(dev)
-        alpha = torch.empty((H, W), dtype=torch.float32, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_temporal_gradient_camera_device(self._h, C.byref(cam), C.byref(prev_cam), C.byref(prev_params), seed,
-                                                       C.c_void_p(d_prev.data_ptr()), C.c_void_p(d_feat.data_ptr()), C.byref(g), alpha_min,
-                                                       C.c_void_p(alpha.data_ptr())))
-        self.sync()
+        d_prev, d_feat = self._upload(prev_linear, np.float32, (H, W, 3)), self._upload(features, np.float32, (H, W, 8))
+        alpha = self._empty((H, W))
+        self._on_stream(lib().pt_temporal_gradient_camera_device, C.byref(cam), C.byref(prev_cam), C.byref(prev_params), seed, d_prev, d_feat,
+                        C.byref(g), alpha_min, alpha)
         return alpha.cpu().numpy()
 
     def debug_gradient_strata(self, width, height):
         """pt_debug_gradient_strata: the strata of the last temporal_gradient of a width x height image -> (xy u32[SH,SW,2],
         re-traced film f32[SH,SW,3], records f64[SH,SW,2] = delta, N)"""
-        SW, SH = (width + 2) // 3, (height + 2) // 3
-        xy = np.empty((SH, SW, 2), dtype=np.uint32)
-        film = np.empty((SH, SW, 3), dtype=np.float32)
-        rec = np.empty((SH, SW, 2), dtype=np.float64)
-        check(lib().pt_debug_gradient_strata(self._h, width, height, xy.ctypes.data_as(C.c_void_p), film.ctypes.data_as(C.c_void_p),
-                                             rec.ctypes.data_as(C.c_void_p)))
-        return xy, film, rec
+        planes, ptrs = self._host_planes((height + 2) // 3, (width + 2) // 3, (2, np.uint32), (3, np.float32), (2, np.float64))
+        check(lib().pt_debug_gradient_strata(self._h, width, height, *ptrs))
+        return planes
 
     def denoise_temporal_alpha(self, cam, linear, features, ids, alpha_plane, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
                                alpha=None, depth_tol=None, normal_tol=None):
         """pt_denoise_temporal_alpha_device: denoise_temporal_motion with a per-pixel blend weight (f32[H,W]); an entry that is
         not finite or outside [0, 1] takes alpha.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
-        import torch
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
         tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
-        linear = np.ascontiguousarray(linear, dtype=np.float32)
-        features = np.ascontiguousarray(features, dtype=np.float32)
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
-        alpha_plane = np.ascontiguousarray(alpha_plane, dtype=np.float32)
         H, W = cam.height, cam.width
-        assert linear.shape == (H, W, 3) and features.shape == (H, W, 8) and ids.shape == (H, W) and alpha_plane.shape == (H, W)
-        dev = torch.device("cuda", self.device)
-        d_lin, d_feat, d_ids = torch.from_numpy(linear).to(dev), torch.from_numpy(features).to(dev), torch.from_numpy(ids).to(dev)
-        d_alpha = torch.from_numpy(alpha_plane).to(dev)
-        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-        rgba = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
-        self.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().pt_denoise_temporal_alpha_device(self._h, C.byref(cam), C.c_void_p(d_lin.data_ptr()), C.c_void_p(d_feat.data_ptr()),
-                                                     C.c_void_p(d_ids.data_ptr()), C.c_void_p(d_alpha.data_ptr()), C.byref(dn), C.byref(tp),
-                                                     C.c_void_p(out.data_ptr()), C.c_void_p(rgba.data_ptr())))
-        self.sync()
+        d_lin, d_feat = self._upload(linear, np.float32, (H, W, 3)), self._upload(features, np.float32, (H, W, 8))
+        d_ids, d_alpha = self._upload(ids, np.int32, (H, W)), self._upload(alpha_plane, np.float32, (H, W))
+        out, rgba = self._film_pair(H, W)
+        self._on_stream(lib().pt_denoise_temporal_alpha_device, C.byref(cam), d_lin, d_feat, d_ids, d_alpha, C.byref(dn), C.byref(tp), out, rgba)
         return out.cpu().numpy(), rgba.cpu().numpy()
 
-    def render_denoised_gradient(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
-                                 alpha=None, depth_tol=None, normal_tol=None, radius=None, scale=None, _entry="pt_render_denoised_gradient"):
-        """pt_render_denoised_gradient (host buffers, blocking): render_denoised_motion whose blend weight rises where the
-        lighting changed since the previous call.  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3], features
-        f32[H,W,8], ids i32[H,W], alpha f32[H,W]; all NaN without a usable previous frame)"""
+    def _render_gradient(self, entry, cam, params, feature_samples, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None, alpha=None,
+                         depth_tol=None, normal_tol=None, radius=None, scale=None):
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
         tp = default_temporal(alpha=alpha, depth_tol=depth_tol, normal_tol=normal_tol)
         g = default_gradient(radius=radius, scale=scale)
-        H, W = cam.height, cam.width
-        lin = np.empty((H, W, 3), dtype=np.float32)
-        rgba = np.empty((H, W, 4), dtype=np.uint8)
-        noisy = np.empty((H, W, 3), dtype=np.float32)
-        feat = np.empty((H, W, 8), dtype=np.float32)
-        ids = np.empty((H, W), dtype=np.int32)
-        plane = np.empty((H, W), dtype=np.float32)
-        check(getattr(lib(), _entry)(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp), C.byref(g),
-                                     lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p),
-                                     noisy.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p),
-                                     ids.ctypes.data_as(C.c_void_p), plane.ctypes.data_as(C.c_void_p)))
-        return lin, rgba, noisy, feat, ids, plane
+        planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32), (0, np.int32),
+                                         (0, np.float32))
+        check(entry(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), C.byref(tp), C.byref(g), *ptrs))
+        return planes
+
+    def render_denoised_gradient(self, cam, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
+                                 alpha=None, depth_tol=None, normal_tol=None, radius=None, scale=None):
+        """pt_render_denoised_gradient (host buffers, blocking): render_denoised_motion whose blend weight rises where the
+        lighting changed since the previous call.  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3], features
+        f32[H,W,8], ids i32[H,W], alpha f32[H,W]; all NaN without a usable previous frame)"""
+        return self._render_gradient(lib().pt_render_denoised_gradient, cam, params, feature_samples, iterations, sigma_l, sigma_n, sigma_d,
+                                     alpha, depth_tol, normal_tol, radius, scale)
 
     def render_denoised_gradient_camera(self, cam, params, feature_samples=4, **kw):
         """pt_render_denoised_gradient_camera: render_denoised_gradient that keeps its previous frame when the camera moved
         (same arguments and results; NaN entries where a pixel has no counterpart in the previous image)."""
-        return self.render_denoised_gradient(cam, params, feature_samples, _entry="pt_render_denoised_gradient_camera", **kw)
+        return self._render_gradient(lib().pt_render_denoised_gradient_camera, cam, params, feature_samples, **kw)
 
     def ray_color(self, params, rays, xy):
         """pt_ray_color = RenderingStrategy::ray_color(world, ray, 0, rng(key xy, sample spp_offset), 1) -> f32[n,3]"""

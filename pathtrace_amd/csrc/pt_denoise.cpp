@@ -1,6 +1,6 @@
-// pt_denoise.cpp -- the first-hit feature pass and the denoisers: a-trous (with its own or the adaptive pass's variance),
-// temporal accumulation with camera reprojection, and the motion form that follows moving objects (pt_motion.h); device
-// entries and the host entries that render first.
+// pt_denoise.cpp -- the host side of the denoisers.  Device entries: the first-hit feature and id passes, the a-trous filter (its
+// own or a given variance plane), the adaptive pass's variance plane, temporal accumulation (plain, following moving objects through
+// pt_motion.h, with a per-pixel weight) and the gradients (pt_gradient.h) that make that weight.  Host entries: pt_render_*denoised*.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,6 +13,106 @@ namespace {
 
 constexpr uint64_t kFeatureRays = 1ull << 21;    // pt_render_features_device: rays per batch (108 B of scratch each with the BVH)
 
+enum class History { none, plain, motion, alpha };   // the accumulation before the a-trous steps; motion reads d_ids, alpha d_alpha too
+enum class Variance { spatial, given };              // the filter's initial variance: its own 3 x 3 estimate, or the plane d_var
+enum class Strata { same_camera, prev_camera };      // the camera whose frame the gradient strata re-trace
+
+int check_denoise(const char* who, const PtDenoise* dn) {   // (a check answers in the entry's name, who, with the first rule broken)
+    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "%s: %u iterations (at most 16)", who, dn->iterations);
+    if (!(dn->sigma_l >= 0.0f) || !(dn->sigma_n >= 0.0f) || !(dn->sigma_d >= 0.0f) || !std::isfinite(dn->sigma_l) ||
+        !std::isfinite(dn->sigma_n) || !std::isfinite(dn->sigma_d))
+        return fail(PT_ERR_INVALID_ARG, "%s: sigma_l, sigma_n and sigma_d must be finite and >= 0", who);
+    return PT_OK;
+}
+
+int check_weight(const char* who, const char* name, float alpha) {   // PtTemporal.alpha, or the gradient entries' alpha_min
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "%s: %s %g not in [0, 1]", who, name, alpha);
+    return PT_OK;
+}
+
+int check_gradient(const char* who, const PtGradient* g) {
+    if (g->radius > ptgr::kMaxRadius) return fail(PT_ERR_INVALID_ARG, "%s: radius %u (at most %u)", who, g->radius, ptgr::kMaxRadius);
+    if (!(g->scale >= 0.0f) || !std::isfinite(g->scale)) return fail(PT_ERR_INVALID_ARG, "%s: scale must be finite and >= 0", who);
+    return PT_OK;
+}
+
+struct Film { const float* linear; const float* features; float* out_linear; uint8_t* out_rgba; };   // what a filter entry reads and writes
+int check_film_aligned(const char* who, const Film& f) {
+    if ((uintptr_t)f.features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
+    if ((uintptr_t)f.linear % 4u || (uintptr_t)f.out_linear % 4u || (uintptr_t)f.out_rgba % 4u)
+        return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
+    return PT_OK;
+}
+
+int check_film_size(const char* who, uint32_t width, uint32_t height, const Film& f) {
+    if (f.out_linear == f.linear) return fail(PT_ERR_INVALID_ARG, "%s: the output must not be the input", who);
+    if ((uint64_t)width * height > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)width * height);
+    return PT_OK;
+}
+
+int check_whole_image(const char* who, const char* verb, const PtRenderParams* prm) {   // verb: "works on" or "renders"
+    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
+        return fail(PT_ERR_INVALID_ARG, "%s: %s the whole image (band_count = 1)", who, verb);
+    return PT_OK;
+}
+
+int check_target(const char* who, const PtContext* c, const PtCamera* cam) {   // what render_impl would refuse, in its words
+    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
+    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    const uint64_t np64 = (uint64_t)cam->width * cam->height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    return PT_OK;
+}
+
+bool same_camera(const PtCamera& a, const PtCamera& b) {   // the four vectors, field by field (the sizes are the caller's to compare)
+    for (int k = 0; k < 3; ++k)
+        if (a.origin[k] != b.origin[k] || a.lower_left[k] != b.lower_left[k] || a.horizontal[k] != b.horizontal[k] || a.vertical[k] != b.vertical[k])
+            return false;
+    return true;
+}
+
+void set_cameras(ptk::TemporalArgs& t, const PtCamera& cur, const PtCamera& prev) {
+    for (int k = 0; k < 3; ++k) {
+        t.cur[k] = cur.origin[k]; t.cur[3 + k] = cur.lower_left[k]; t.cur[6 + k] = cur.horizontal[k]; t.cur[9 + k] = cur.vertical[k];
+        t.prev[k] = prev.origin[k]; t.prev[3 + k] = prev.lower_left[k]; t.prev[6 + k] = prev.horizontal[k]; t.prev[9 + k] = prev.vertical[k];
+    }
+    t.same_camera = same_camera(cur, prev);
+}
+
+// The arguments of the launch that fills plane 0 with (u, var); denoise_steps completes them per iteration.
+ptk::DenoiseArgs denoise_args(const PtContext* c, uint32_t width, uint32_t height, const Film& f, const PtDenoise* dn) {
+    ptk::DenoiseArgs a{};
+    a.linear = f.linear; a.feat = reinterpret_cast<const float4*>(f.features);
+    a.out_linear = f.out_linear; a.out_rgba = f.out_rgba;
+    a.width = width; a.height = height;
+    a.sigma_l = dn->sigma_l; a.sigma_n = dn->sigma_n; a.sigma_d = dn->sigma_d;
+    a.dst = c->dn_plane[0].p; a.finalize = dn->iterations == 0;
+    return a;
+}
+
+// The front of a pt_render_denoised* frame: staging for np pixels, then the render into host_lin, the features into dn_feat and, from
+// History::motion on, the ids into dn_ids.  History::alpha (the gradient entries): gr_alpha too, and no previous frame from here on.
+int frame_front(History form, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, size_t np, PtRenderParams* p) {
+    int rc;
+    if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) || (rc = c->dn_lin.ensure(3 * np)) ||
+        (form >= History::motion && (rc = c->dn_ids.ensure(np))) || (form == History::alpha && (rc = c->gr_alpha.ensure(np))))
+        return rc;
+    if (form == History::alpha) c->gr_valid = false;
+    *p = *prm;                                // for the whole image
+    p->band_count = 1; p->band_index = 0; p->band_rows = 0;
+    if ((rc = render_impl(c, cam, p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
+        (rc = pt_render_features_device(c, cam, p, std::min(feature_samples, p->spp), reinterpret_cast<float*>(c->dn_feat.p))))
+        return rc;
+    return form >= History::motion ? pt_render_feature_ids_device(c, cam, p, c->dn_ids.p) : PT_OK;
+}
+
+struct CopyBack { void* host; const void* dev; size_t bytes; };   // blocking, the stream is through; a null host pointer: not asked for
+int copy_back(std::initializer_list<CopyBack> copies) {
+    for (const CopyBack& k : copies)
+        if (k.host) HIP_TRY(hipMemcpy(k.host, k.dev, k.bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 // First-hit features: per batch of samples, k_feature_rays writes the camera rays, launch_debug_hit (the scan or BVH of the
 // parity entries) finds their hits, k_feature_resolve adds the records to the per-pixel sums in d_features.
 // pt_render_feature_ids_device is the same pass over the one sample spp_offset without the resolve: the hit ids of that batch,
@@ -21,16 +121,13 @@ int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRe
                   int32_t* d_ids) {
     if (!c || !cam || !prm || (!d_features && !d_ids)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (n_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: n_samples must be > 0", who);
-    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "%s: works on the whole image (band_count = 1)", who);
+    int rc;
+    if ((rc = check_whole_image(who, "works on", prm))) return rc;
     if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
     if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
     if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
-    const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
-    const uint32_t np = (uint32_t)np64;
+    if ((rc = check_target(who, c, cam))) return rc;
+    const size_t np = (size_t)cam->width * cam->height;
     HIP_TRY(hipSetDevice(c->device));
     uint32_t accel = prm->accel;
     if (accel == PT_ACCEL_AUTO) {
@@ -38,7 +135,6 @@ int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRe
         accel = (c->auto_bvh && !c->bvh_refused && !c->bvh_failed && ensure_bvh(c) == PT_OK) ? PT_ACCEL_BVH : PT_ACCEL_LINEAR;
         if (!accel) g_err = keep;
     }
-    int rc;
     if (accel && (rc = ensure_bvh(c))) return rc;
     const uint32_t nb_max = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_samples, kFeatureRays / np));
     const size_t n_rays = (size_t)nb_max * np;
@@ -88,42 +184,30 @@ int denoise_steps(PtContext* c, ptk::DenoiseArgs a, uint32_t iterations) {
     return PT_OK;
 }
 
-// pt_render_denoised, pt_render_denoised_temporal (tp != null) and pt_render_denoised_motion (motion: the ids pass and the
-// motion entry): render, features, filter; host buffers, blocking
-int render_denoised_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
+// pt_render_denoised (History::none), pt_render_denoised_temporal (plain: tp) and pt_render_denoised_motion (motion: tp, the
+// ids pass): render, features, filter; host buffers, blocking
+int render_denoised_impl(const char* who, History form, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                          const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                         float* out_features, bool motion = false, int32_t* out_ids = nullptr) {
-    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "%s: renders the whole image (band_count = 1)", who);
-    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
-    const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
-    const size_t np = (size_t)np64;
-    HIP_TRY(hipSetDevice(c->device));
+                         float* out_features, int32_t* out_ids) {
+    if (!c || !cam || !prm || !dn || (form != History::none && !tp) || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) ||
-        (rc = c->dn_lin.ensure(3 * np)) || (motion && (rc = c->dn_ids.ensure(np))))
-        return rc;
-    PtRenderParams p = *prm;
-    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
+    if ((rc = check_whole_image(who, "renders", prm))) return rc;
+    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
+    if ((rc = check_target(who, c, cam))) return rc;
+    const size_t np = (size_t)cam->width * cam->height;
+    HIP_TRY(hipSetDevice(c->device));
+    PtRenderParams p;
+    if ((rc = frame_front(form, c, cam, prm, feature_samples, np, &p))) return rc;
     float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
     uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
-    if ((rc = render_impl(c, cam, &p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
-        (rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat)) ||
-        (motion && (rc = pt_render_feature_ids_device(c, cam, &p, c->dn_ids.p))) ||
-        (rc = motion ? pt_denoise_temporal_motion_device(c, cam, c->host_lin.p, feat, c->dn_ids.p, dn, tp, c->dn_lin.p, rgba)
-              : tp   ? pt_denoise_temporal_device(c, cam, c->host_lin.p, feat, dn, tp, c->dn_lin.p, rgba)
-                     : pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, feat, dn, c->dn_lin.p, rgba)) ||
+    if ((rc = form == History::motion  ? pt_denoise_temporal_motion_device(c, cam, c->host_lin.p, feat, c->dn_ids.p, dn, tp, c->dn_lin.p, rgba)
+              : form == History::plain ? pt_denoise_temporal_device(c, cam, c->host_lin.p, feat, dn, tp, c->dn_lin.p, rgba)
+                                       : pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, feat, dn, c->dn_lin.p, rgba)) ||
         (rc = pt_sync(c)))
         return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_features) HIP_TRY(hipMemcpy(out_features, feat, 8 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_ids) HIP_TRY(hipMemcpy(out_ids, c->dn_ids.p, np * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return copy_back({{out_linear, c->dn_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np},
+                      {out_noisy, c->host_lin.p, 3 * np * sizeof(float)}, {out_features, feat, 8 * np * sizeof(float)},
+                      {out_ids, c->dn_ids.p, np * sizeof(int32_t)}});
 }
 
 // The maps current pose -> history pose of every object into c->mo_maps, on the context's stream.  Unchanged poses since the
@@ -157,29 +241,22 @@ int upload_motion_maps(PtContext* c) {
 }
 
 // Temporal accumulation: k_denoise_temporal (history -> (u, var) in plane 0 and the next history), then the a-trous steps of
-// pt_denoise_device.  The arguments are checked before the context is looked at.  d_ids: the motion entry, whose kernel is
-// k_denoise_temporal_motion; with_alpha (a motion entry too): the alpha entry with its per-pixel plane, k_denoise_temporal_alpha.
-// All store a history frame, and with it the scene's pose becomes the history pose.
-int temporal_impl(const char* who, PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features, const int32_t* d_ids,
-                  bool motion, const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba,
-                  const float* d_alpha = nullptr, bool with_alpha = false) {
-    if (!cam || !dn || !tp || !d_linear || !d_features || !d_out_linear || (motion && !d_ids) || (with_alpha && !d_alpha))
+// pt_denoise_device.  The arguments are checked before the context is looked at.  History::motion and History::alpha read
+// the ids and the motion maps, alpha its per-pixel plane as well.  All store a history frame, and with it the scene's pose
+// becomes the history pose.
+int temporal_impl(const char* who, History form, PtContext* c, const PtCamera* cam, const Film& f, const int32_t* d_ids, const float* d_alpha,
+                  const PtDenoise* dn, const PtTemporal* tp) {
+    const bool motion = form != History::plain;
+    if (!cam || !dn || !tp || !f.linear || !f.features || !f.out_linear || (motion && !d_ids) || (form == History::alpha && !d_alpha))
         return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (cam->width < 2 || cam->height < 2)
         return fail(PT_ERR_INVALID_ARG, "%s: camera %ux%u: width and height must be >= 2", who, cam->width, cam->height);
-    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "%s: %u iterations (at most 16)", who, dn->iterations);
-    if (!(dn->sigma_l >= 0.0f) || !(dn->sigma_n >= 0.0f) || !(dn->sigma_d >= 0.0f) || !std::isfinite(dn->sigma_l) ||
-        !std::isfinite(dn->sigma_n) || !std::isfinite(dn->sigma_d))
-        return fail(PT_ERR_INVALID_ARG, "%s: sigma_l, sigma_n and sigma_d must be finite and >= 0", who);
-    if (!(tp->alpha >= 0.0f && tp->alpha <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "%s: alpha %g not in [0, 1]", who, tp->alpha);
+    int rc;
+    if ((rc = check_denoise(who, dn)) || (rc = check_weight(who, "alpha", tp->alpha))) return rc;
     if (!(tp->depth_tol >= 0.0f) || !(tp->normal_tol >= 0.0f) || !std::isfinite(tp->depth_tol) || !std::isfinite(tp->normal_tol))
         return fail(PT_ERR_INVALID_ARG, "%s: depth_tol and normal_tol must be finite and >= 0", who);
-    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
-    if ((uintptr_t)d_linear % 4u || (uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u)
-        return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
-    if (d_out_linear == d_linear) return fail(PT_ERR_INVALID_ARG, "%s: the output must not be the input", who);
-    const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    if ((rc = check_film_aligned(who, f)) || (rc = check_film_size(who, cam->width, cam->height, f))) return rc;
+    const size_t np = (size_t)cam->width * cam->height;
     if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
     if ((uintptr_t)d_alpha % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_alpha must be 4-byte aligned", who);
     if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
@@ -187,84 +264,145 @@ int temporal_impl(const char* who, PtContext* c, const PtCamera* cam, const floa
     if (motion && c->view.n_objs > (1u << 24) - 2u)
         return fail(PT_ERR_UNSUPPORTED, "%s: %u objects (an id + 1 must be exact in the history's f32 lane: at most 2^24 - 2)", who, c->view.n_objs);
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
     if (motion && (rc = upload_motion_maps(c))) return rc;
-    if ((rc = c->dn_plane[0].ensure(np64)) || (rc = c->dn_plane[1].ensure(np64)) || (rc = c->tm_hist[0].ensure(3 * np64)) ||
-        (rc = c->tm_hist[1].ensure(3 * np64)))
+    if ((rc = c->dn_plane[0].ensure(np)) || (rc = c->dn_plane[1].ensure(np)) || (rc = c->tm_hist[0].ensure(3 * np)) ||
+        (rc = c->tm_hist[1].ensure(3 * np)))
         return rc;
     const bool have = c->tm_valid && c->tm_cam.width == cam->width && c->tm_cam.height == cam->height;
-    bool same = have;
-    for (int k = 0; k < 3; ++k)
-        same = same && c->tm_cam.origin[k] == cam->origin[k] && c->tm_cam.lower_left[k] == cam->lower_left[k] &&
-               c->tm_cam.horizontal[k] == cam->horizontal[k] && c->tm_cam.vertical[k] == cam->vertical[k];
-    ptk::TemporalArgs t{};
-    ptk::DenoiseArgs& a = t.dn;
-    a.linear = d_linear; a.feat = reinterpret_cast<const float4*>(d_features);
-    a.out_linear = d_out_linear; a.out_rgba = d_out_rgba;
-    a.width = cam->width; a.height = cam->height;
-    a.sigma_l = dn->sigma_l; a.sigma_n = dn->sigma_n; a.sigma_d = dn->sigma_d;
-    a.dst = c->dn_plane[0].p; a.finalize = dn->iterations == 0;
+    ptk::TemporalAlphaArgs a{};                // the three kernels' arguments, one inside the other: each launch takes its own part
+    ptk::TemporalArgs& t = a.m.t;
+    t.dn = denoise_args(c, cam->width, cam->height, f, dn);
     t.hist_src = have ? c->tm_hist[c->tm_cur].p : nullptr;
     t.hist_dst = c->tm_hist[c->tm_cur ^ 1u].p;
-    for (int k = 0; k < 3; ++k) {
-        t.cur[k] = cam->origin[k]; t.cur[3 + k] = cam->lower_left[k]; t.cur[6 + k] = cam->horizontal[k]; t.cur[9 + k] = cam->vertical[k];
-        t.prev[k] = c->tm_cam.origin[k]; t.prev[3 + k] = c->tm_cam.lower_left[k];
-        t.prev[6 + k] = c->tm_cam.horizontal[k]; t.prev[9 + k] = c->tm_cam.vertical[k];
-    }
-    t.same_camera = same;
+    set_cameras(t, *cam, c->tm_cam);
+    t.same_camera = have && t.same_camera;
     t.alpha = tp->alpha; t.depth_tol = tp->depth_tol; t.normal_tol = tp->normal_tol;
-    if (motion) {
-        ptk::TemporalMotionArgs m{};
-        m.t = t; m.ids = d_ids; m.maps = c->mo_maps.p; m.n_objs = c->view.n_objs;
-        if (with_alpha) {
-            ptk::TemporalAlphaArgs g{};
-            g.m = m; g.alpha = d_alpha;
-            ptk::launch_denoise_temporal_alpha(g, c->stream);
-        } else {
-            ptk::launch_denoise_temporal_motion(m, c->stream);
-        }
-    } else {
-        ptk::launch_denoise_temporal(t, c->stream);
-    }
+    if (motion) { a.m.ids = d_ids; a.m.maps = c->mo_maps.p; a.m.n_objs = c->view.n_objs; a.alpha = d_alpha; }
+    if (form == History::alpha) ptk::launch_denoise_temporal_alpha(a, c->stream);
+    else if (form == History::motion) ptk::launch_denoise_temporal_motion(a.m, c->stream);
+    else ptk::launch_denoise_temporal(t, c->stream);
     HIP_TRY(hipGetLastError());
     c->tm_cur ^= 1u; c->tm_valid = true; c->tm_cam = *cam;
     if (!c->has_scene) c->tm_pose.clear();
     else if (c->tm_pose_gen != c->pose_gen || c->tm_pose.size() != c->pose.size()) c->tm_pose = c->pose;
     c->tm_pose_gen = c->pose_gen;
-    return denoise_steps(c, a, dn->iterations);
+    return denoise_steps(c, t.dn, dn->iterations);
 }
 
-// The filter of pt_denoise_device and pt_denoise_var_device (with_var: k_denoise_init_var and the caller's variance plane in
-// place of k_denoise_init): (u, var) into plane 0, then one k_denoise_step per iteration between the two planes; the last
-// launch writes the film planes.
-int denoise_impl(const char* who, PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,
-                 const float* d_var, bool with_var, const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba) {
-    if (!c || !dn || !d_linear || !d_features || !d_out_linear || (with_var && !d_var)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+// The filter of pt_denoise_device and pt_denoise_var_device (Variance::given: k_denoise_init_var and the caller's variance
+// plane in place of k_denoise_init): (u, var) into plane 0, then one k_denoise_step per iteration between the two planes; the
+// last launch writes the film planes.
+int denoise_impl(const char* who, Variance form, PtContext* c, uint32_t width, uint32_t height, const Film& f, const float* d_var,
+                 const PtDenoise* dn) {
+    if (!c || !dn || !f.linear || !f.features || !f.out_linear || (form == Variance::given && !d_var))
+        return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (width == 0 || height == 0) return fail(PT_ERR_INVALID_ARG, "%s: image %ux%u", who, width, height);
-    if (dn->iterations > 16) return fail(PT_ERR_INVALID_ARG, "%s: %u iterations (at most 16)", who, dn->iterations);
-    if (!(dn->sigma_l >= 0.0f) || !(dn->sigma_n >= 0.0f) || !(dn->sigma_d >= 0.0f) || !std::isfinite(dn->sigma_l) ||
-        !std::isfinite(dn->sigma_n) || !std::isfinite(dn->sigma_d))
-        return fail(PT_ERR_INVALID_ARG, "%s: sigma_l, sigma_n and sigma_d must be finite and >= 0", who);
-    if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
-    if ((uintptr_t)d_linear % 4u || (uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u)
-        return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
-    if ((uintptr_t)d_var % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_var must be 4-byte aligned", who);
-    if (d_out_linear == d_linear) return fail(PT_ERR_INVALID_ARG, "%s: the output must not be the input", who);
-    const uint64_t np64 = (uint64_t)width * height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
-    HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = c->dn_plane[0].ensure(np64)) || (rc = c->dn_plane[1].ensure(np64))) return rc;
-    ptk::DenoiseArgs a{};
-    a.linear = d_linear; a.feat = reinterpret_cast<const float4*>(d_features);
-    a.out_linear = d_out_linear; a.out_rgba = d_out_rgba;
-    a.width = width; a.height = height;
-    a.sigma_l = dn->sigma_l; a.sigma_n = dn->sigma_n; a.sigma_d = dn->sigma_d;
-    a.dst = c->dn_plane[0].p; a.finalize = dn->iterations == 0;
-    if (with_var) ptk::launch_denoise_init_var(a, d_var, c->stream);
+    if ((rc = check_denoise(who, dn)) || (rc = check_film_aligned(who, f))) return rc;
+    if ((uintptr_t)d_var % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_var must be 4-byte aligned", who);
+    if ((rc = check_film_size(who, width, height, f))) return rc;
+    const size_t np = (size_t)width * height;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->dn_plane[0].ensure(np)) || (rc = c->dn_plane[1].ensure(np))) return rc;
+    const ptk::DenoiseArgs a = denoise_args(c, width, height, f, dn);
+    if (form == Variance::given) ptk::launch_denoise_init_var(a, d_var, c->stream);
     else ptk::launch_denoise(a, true, c->stream);
     HIP_TRY(hipGetLastError());
     return denoise_steps(c, a, dn->iterations);
+}
+
+// The strata's pixel list (k_gradient_list), its render with the previous frame's parameters in the current scene (a list
+// render that may take the regenerating kernel, as pt_render_adaptive's passes do), the records and the plane.  The
+// arguments are checked before the context is looked at, and everything the list render checks is checked before the first
+// launch: a refused call leaves the context as it was.
+//
+// Strata::prev_camera (pt_temporal_gradient_camera_device): the strata lie in the image of prev_cam, whose
+// re-trace this is, and k_gradient_alpha_camera looks every pixel of cam up in them through d_features.
+int gradient_impl(const char* who, Strata form, PtContext* c, const PtCamera* cam, const PtCamera* prev_cam, const PtRenderParams* prev,
+                  uint32_t seed, const float* d_prev, const float* d_features, const PtGradient* g, float alpha_min, float* d_alpha) {
+    const bool moved = form == Strata::prev_camera;
+    if (!cam || !prev || !d_prev || !g || !d_alpha || (moved && (!prev_cam || !d_features)))
+        return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if ((uintptr_t)d_prev % 4u || (uintptr_t)d_alpha % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_prev_linear and d_alpha must be 4-byte aligned", who);
+    if (moved && (uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
+    if (moved && (prev_cam->width != cam->width || prev_cam->height != cam->height))
+        return fail(PT_ERR_INVALID_ARG, "%s: the previous camera is %ux%u, the camera %ux%u", who, prev_cam->width, prev_cam->height,
+                    cam->width, cam->height);
+    int rc;
+    if ((rc = check_whole_image(who, "works on", prev)) || (rc = check_gradient(who, g)) || (rc = check_weight(who, "alpha_min", alpha_min))) return rc;
+    if (cam->width < 2 || cam->height < 2)
+        return fail(PT_ERR_INVALID_ARG, "%s: camera %ux%u: width and height must be >= 2", who, cam->width, cam->height);
+    if (prev->spp == 0) return fail(PT_ERR_INVALID_ARG, "%s: spp must be > 0", who);
+    if (prev->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "%s: unknown integrator %u", who, prev->integrator);
+    if (prev->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "%s: unknown accel %u", who, prev->accel);
+    const uint64_t np64 = (uint64_t)cam->width * cam->height;
+    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
+    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t ns = (size_t)ptgr::strata(cam->width) * ptgr::strata(cam->height);
+    if ((rc = c->gr_list.ensure(ns)) || (rc = c->gr_film.ensure(3 * ns)) || (rc = c->gr_rec.ensure(2 * ns))) return rc;
+    ptk::GradientArgs a{};
+    a.retraced = c->gr_film.p; a.prev = d_prev; a.list = c->gr_list.p; a.rec = c->gr_rec.p; a.alpha = d_alpha;
+    a.width = cam->width; a.height = cam->height; a.seed = seed; a.radius = g->radius;
+    a.scale = g->scale; a.alpha_min = alpha_min;
+    ptk::launch_gradient_list(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    PtRenderParams p = *prev;
+    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
+    ListRender lr;
+    lr.d_pixels = c->gr_list.p; lr.n = (uint32_t)ns; lr.regen = true;
+    if ((rc = render_impl(c, moved ? prev_cam : cam, &p, FilmState{}, &lr, c->gr_film.p, nullptr))) return rc;
+    ptk::launch_gradient_strata(a, c->stream);
+    if (moved) {
+        ptk::TemporalArgs t{};
+        t.dn.feat = reinterpret_cast<const float4*>(d_features);
+        t.dn.width = cam->width; t.dn.height = cam->height;
+        set_cameras(t, *cam, *prev_cam);
+        ptk::launch_gradient_alpha_camera(a, t, c->stream);
+    } else {
+        ptk::launch_gradient_alpha(a, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+// pt_render_denoised_motion with the alpha plane between the ids pass and the accumulation, and the frame's noisy film kept
+// for the next call.  Strata::prev_camera (pt_render_denoised_gradient_camera): the previous frame stays usable when the
+// camera moved, and the plane is pt_temporal_gradient_camera_device's.
+int render_gradient_impl(const char* who, Strata form, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
+                         const PtDenoise* dn, const PtTemporal* tp, const PtGradient* g, float* out_linear, uint8_t* out_rgba,
+                         float* out_noisy, float* out_features, int32_t* out_ids, float* out_alpha) {
+    if (!c || !cam || !prm || !dn || !tp || !g || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc;
+    if ((rc = check_whole_image(who, "renders", prm))) return rc;
+    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
+    if ((rc = check_gradient(who, g)) || (rc = check_weight(who, "alpha", tp->alpha)) || (rc = check_target(who, c, cam))) return rc;
+    const size_t np = (size_t)cam->width * cam->height;
+    HIP_TRY(hipSetDevice(c->device));
+    // the previous frame is usable: one of the two entries completed it, at this size, through this camera (prev_camera:
+    // through any), and the history it went into is there
+    const bool usable = c->gr_valid && c->tm_valid && c->gr_prev.cap >= 3 * np && c->gr_cam.width == cam->width &&
+                        c->gr_cam.height == cam->height && (form == Strata::prev_camera || same_camera(c->gr_cam, *cam));
+    const PtCamera prev_cam = c->gr_cam;
+    PtRenderParams p;
+    if ((rc = frame_front(History::alpha, c, cam, prm, feature_samples, np, &p))) return rc;
+    float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
+    uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
+    if (!usable) HIP_TRY(hipMemsetAsync(c->gr_alpha.p, 0xFF, np * sizeof(float), c->stream));      // every entry a NaN: no measurement
+    else if ((rc = form == Strata::prev_camera
+                       ? pt_temporal_gradient_camera_device(c, cam, &prev_cam, &c->gr_params, c->gr_frame, c->gr_prev.p, feat, g, tp->alpha, c->gr_alpha.p)
+                       : pt_temporal_gradient_device(c, cam, &c->gr_params, c->gr_frame, c->gr_prev.p, g, tp->alpha, c->gr_alpha.p)))
+        return rc;
+    if ((rc = pt_denoise_temporal_alpha_device(c, cam, c->host_lin.p, feat, c->dn_ids.p, c->gr_alpha.p, dn, tp, c->dn_lin.p, rgba)) ||
+        (rc = c->gr_prev.ensure(3 * np)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->gr_prev.p, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = pt_sync(c))) return rc;
+    c->gr_valid = true; c->gr_params = p; c->gr_cam = *cam; ++c->gr_frame;
+    return copy_back({{out_linear, c->dn_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np},
+                      {out_noisy, c->host_lin.p, 3 * np * sizeof(float)}, {out_features, feat, 8 * np * sizeof(float)},
+                      {out_ids, c->dn_ids.p, np * sizeof(int32_t)}, {out_alpha, c->gr_alpha.p, np * sizeof(float)}});
 }
 
 }  // namespace
@@ -272,23 +410,21 @@ int denoise_impl(const char* who, PtContext* c, uint32_t width, uint32_t height,
 extern "C" {
 
 int pt_render_features_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t n_samples, float* d_features) {
-    if (!d_features) return fail(PT_ERR_INVALID_ARG, "pt_render_features_device: null argument");
     return features_impl("pt_render_features_device", c, cam, prm, n_samples, d_features, nullptr);
 }
 
 int pt_render_feature_ids_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, int32_t* d_ids) {
-    if (!d_ids) return fail(PT_ERR_INVALID_ARG, "pt_render_feature_ids_device: null argument");
     return features_impl("pt_render_feature_ids_device", c, cam, prm, 1, nullptr, d_ids);
 }
 
 int pt_denoise_device(PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,
                       const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba) {
-    return denoise_impl("pt_denoise_device", c, width, height, d_linear, d_features, nullptr, false, dn, d_out_linear, d_out_rgba);
+    return denoise_impl("pt_denoise_device", Variance::spatial, c, width, height, {d_linear, d_features, d_out_linear, d_out_rgba}, nullptr, dn);
 }
 
 int pt_denoise_var_device(PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,
                           const float* d_var, const PtDenoise* dn, float* d_out_linear, uint8_t* d_out_rgba) {
-    return denoise_impl("pt_denoise_var_device", c, width, height, d_linear, d_features, d_var, true, dn, d_out_linear, d_out_rgba);
+    return denoise_impl("pt_denoise_var_device", Variance::given, c, width, height, {d_linear, d_features, d_out_linear, d_out_rgba}, d_var, dn);
 }
 
 // k_adaptive_variance over the state the last completed pt_render_adaptive left in the context
@@ -325,20 +461,15 @@ int pt_render_adaptive_denoised(PtContext* c, const PtCamera* cam, const PtRende
         (rc = pt_denoise_var_device(c, cam->width, cam->height, c->host_lin.p, feat, c->dn_var.p, dn, c->dn_lin.p, rgba)) ||
         (rc = pt_sync(c)))
         return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_spp) HIP_TRY(hipMemcpy(out_spp, c->ad_count.p, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_rel_err) HIP_TRY(hipMemcpy(out_rel_err, c->ad_err.p, np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_var) HIP_TRY(hipMemcpy(out_var, c->dn_var.p, np * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return copy_back({{out_linear, c->dn_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np},
+                      {out_noisy, c->host_lin.p, 3 * np * sizeof(float)}, {out_spp, c->ad_count.p, np * sizeof(uint32_t)},
+                      {out_rel_err, c->ad_err.p, np * sizeof(float)}, {out_var, c->dn_var.p, np * sizeof(float)}});
 }
 
 int pt_render_denoised(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
                        float* out_linear, uint8_t* out_rgba, float* out_noisy, float* out_features) {
-    if (!c || !cam || !prm || !dn || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised: null argument");
-    return render_denoised_impl("pt_render_denoised", c, cam, prm, feature_samples, dn, nullptr, out_linear, out_rgba, out_noisy,
-                                out_features);
+    return render_denoised_impl("pt_render_denoised", History::none, c, cam, prm, feature_samples, dn, nullptr, out_linear, out_rgba,
+                                out_noisy, out_features, nullptr);
 }
 
 int pt_temporal_reset(PtContext* c) {
@@ -350,28 +481,27 @@ int pt_temporal_reset(PtContext* c) {
 
 int pt_denoise_temporal_device(PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features,
                                const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba) {
-    return temporal_impl("pt_denoise_temporal_device", c, cam, d_linear, d_features, nullptr, false, dn, tp, d_out_linear, d_out_rgba);
+    return temporal_impl("pt_denoise_temporal_device", History::plain, c, cam, {d_linear, d_features, d_out_linear, d_out_rgba}, nullptr, nullptr, dn, tp);
 }
 
 int pt_denoise_temporal_motion_device(PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features, const int32_t* d_ids,
                                       const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear, uint8_t* d_out_rgba) {
-    return temporal_impl("pt_denoise_temporal_motion_device", c, cam, d_linear, d_features, d_ids, true, dn, tp, d_out_linear, d_out_rgba);
+    return temporal_impl("pt_denoise_temporal_motion_device", History::motion, c, cam, {d_linear, d_features, d_out_linear, d_out_rgba}, d_ids, nullptr,
+                         dn, tp);
 }
 
 int pt_render_denoised_motion(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
                               const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy, float* out_features,
                               int32_t* out_ids) {
-    if (!c || !cam || !prm || !dn || !tp || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised_motion: null argument");
-    return render_denoised_impl("pt_render_denoised_motion", c, cam, prm, feature_samples, dn, tp, out_linear, out_rgba, out_noisy,
-                                out_features, true, out_ids);
+    return render_denoised_impl("pt_render_denoised_motion", History::motion, c, cam, prm, feature_samples, dn, tp, out_linear, out_rgba,
+                                out_noisy, out_features, out_ids);
 }
-
 
 int pt_denoise_temporal_alpha_device(PtContext* c, const PtCamera* cam, const float* d_linear, const float* d_features, const int32_t* d_ids,
                                      const float* d_alpha, const PtDenoise* dn, const PtTemporal* tp, float* d_out_linear,
                                      uint8_t* d_out_rgba) {
-    return temporal_impl("pt_denoise_temporal_alpha_device", c, cam, d_linear, d_features, d_ids, true, dn, tp, d_out_linear, d_out_rgba,
-                         d_alpha, true);
+    return temporal_impl("pt_denoise_temporal_alpha_device", History::alpha, c, cam, {d_linear, d_features, d_out_linear, d_out_rgba}, d_ids, d_alpha,
+                         dn, tp);
 }
 
 void pt_default_gradient(PtGradient* out) {
@@ -380,82 +510,15 @@ void pt_default_gradient(PtGradient* out) {
     out->scale = 1.0f;
 }
 
-// The strata's pixel list (k_gradient_list), its render with the previous frame's parameters in the current scene (a list
-// render that may take the regenerating kernel, as pt_render_adaptive's passes do), the records and the plane.  The
-// arguments are checked before the context is looked at, and everything the list render checks is checked before the first
-// launch: a refused call leaves the context as it was.
-//
-// with_camera (pt_temporal_gradient_camera_device): the strata lie in the image of prev_cam, whose re-trace
-// this is, and k_gradient_alpha_camera looks every pixel of cam up in them through d_features.
-static int gradient_impl(const char* who, PtContext* c, const PtCamera* cam, const PtCamera* prev_cam, bool with_camera,
-                         const PtRenderParams* prev, uint32_t seed, const float* d_prev, const float* d_features, const PtGradient* g,
-                         float alpha_min, float* d_alpha) {
-    if (!cam || !prev || !d_prev || !g || !d_alpha || (with_camera && (!prev_cam || !d_features)))
-        return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
-    if ((uintptr_t)d_prev % 4u || (uintptr_t)d_alpha % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_prev_linear and d_alpha must be 4-byte aligned", who);
-    if (with_camera && (uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
-    if (with_camera && (prev_cam->width != cam->width || prev_cam->height != cam->height))
-        return fail(PT_ERR_INVALID_ARG, "%s: the previous camera is %ux%u, the camera %ux%u", who, prev_cam->width, prev_cam->height,
-                    cam->width, cam->height);
-    if ((prev->band_count ? prev->band_count : 1) != 1 || prev->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "%s: works on the whole image (band_count = 1)", who);
-    if (g->radius > ptgr::kMaxRadius) return fail(PT_ERR_INVALID_ARG, "%s: radius %u (at most %u)", who, g->radius, ptgr::kMaxRadius);
-    if (!(g->scale >= 0.0f) || !std::isfinite(g->scale)) return fail(PT_ERR_INVALID_ARG, "%s: scale must be finite and >= 0", who);
-    if (!(alpha_min >= 0.0f && alpha_min <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "%s: alpha_min %g not in [0, 1]", who, alpha_min);
-    if (cam->width < 2 || cam->height < 2)
-        return fail(PT_ERR_INVALID_ARG, "%s: camera %ux%u: width and height must be >= 2", who, cam->width, cam->height);
-    if (prev->spp == 0) return fail(PT_ERR_INVALID_ARG, "%s: spp must be > 0", who);
-    if (prev->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "%s: unknown integrator %u", who, prev->integrator);
-    if (prev->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "%s: unknown accel %u", who, prev->accel);
-    const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
-    if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t ns = (size_t)ptgr::strata(cam->width) * ptgr::strata(cam->height);
-    int rc;
-    if ((rc = c->gr_list.ensure(ns)) || (rc = c->gr_film.ensure(3 * ns)) || (rc = c->gr_rec.ensure(2 * ns))) return rc;
-    ptk::GradientArgs a{};
-    a.retraced = c->gr_film.p; a.prev = d_prev; a.list = c->gr_list.p; a.rec = c->gr_rec.p; a.alpha = d_alpha;
-    a.width = cam->width; a.height = cam->height; a.seed = seed; a.radius = g->radius;
-    a.scale = g->scale; a.alpha_min = alpha_min;
-    ptk::launch_gradient_list(a, c->stream);
-    HIP_TRY(hipGetLastError());
-    PtRenderParams p = *prev;
-    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
-    ListRender lr;
-    lr.d_pixels = c->gr_list.p; lr.n = (uint32_t)ns; lr.regen = true;
-    if ((rc = render_impl(c, with_camera ? prev_cam : cam, &p, FilmState{}, &lr, c->gr_film.p, nullptr))) return rc;
-    ptk::launch_gradient_strata(a, c->stream);
-    if (with_camera) {
-        ptk::TemporalArgs t{};
-        t.dn.feat = reinterpret_cast<const float4*>(d_features);
-        t.dn.width = cam->width; t.dn.height = cam->height;
-        bool same = true;
-        for (int k = 0; k < 3; ++k) {
-            t.cur[k] = cam->origin[k]; t.cur[3 + k] = cam->lower_left[k]; t.cur[6 + k] = cam->horizontal[k]; t.cur[9 + k] = cam->vertical[k];
-            t.prev[k] = prev_cam->origin[k]; t.prev[3 + k] = prev_cam->lower_left[k];
-            t.prev[6 + k] = prev_cam->horizontal[k]; t.prev[9 + k] = prev_cam->vertical[k];
-            same = same && prev_cam->origin[k] == cam->origin[k] && prev_cam->lower_left[k] == cam->lower_left[k] &&
-                   prev_cam->horizontal[k] == cam->horizontal[k] && prev_cam->vertical[k] == cam->vertical[k];
-        }
-        t.same_camera = same;
-        ptk::launch_gradient_alpha_camera(a, t, c->stream);
-    } else {
-        ptk::launch_gradient_alpha(a, c->stream);
-    }
-    HIP_TRY(hipGetLastError());
-    return PT_OK;
-}
-
 int pt_temporal_gradient_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prev, uint32_t seed, const float* d_prev,
                                 const PtGradient* g, float alpha_min, float* d_alpha) {
-    return gradient_impl("pt_temporal_gradient_device", c, cam, nullptr, false, prev, seed, d_prev, nullptr, g, alpha_min, d_alpha);
+    return gradient_impl("pt_temporal_gradient_device", Strata::same_camera, c, cam, nullptr, prev, seed, d_prev, nullptr, g, alpha_min, d_alpha);
 }
 
 int pt_temporal_gradient_camera_device(PtContext* c, const PtCamera* cam, const PtCamera* prev_cam, const PtRenderParams* prev, uint32_t seed,
                                        const float* d_prev, const float* d_features, const PtGradient* g, float alpha_min, float* d_alpha) {
-    return gradient_impl("pt_temporal_gradient_camera_device", c, cam, prev_cam, true, prev, seed, d_prev, d_features, g, alpha_min, d_alpha);
+    return gradient_impl("pt_temporal_gradient_camera_device", Strata::prev_camera, c, cam, prev_cam, prev, seed, d_prev, d_features, g, alpha_min,
+                         d_alpha);
 }
 
 // Debug: the strata of the last pt_temporal_gradient_device on this context copied back (blocking): per stratum its gradient
@@ -467,94 +530,29 @@ int pt_debug_gradient_strata(PtContext* c, uint32_t width, uint32_t height, uint
         return fail(PT_ERR_INVALID_ARG, "pt_debug_gradient_strata: the context holds no strata of a %ux%u image", width, height);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (out_xy) HIP_TRY(hipMemcpy(out_xy, c->gr_list.p, ns * sizeof(uint2), hipMemcpyDeviceToHost));
-    if (out_film) HIP_TRY(hipMemcpy(out_film, c->gr_film.p, 3 * ns * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rec) HIP_TRY(hipMemcpy(out_rec, c->gr_rec.p, 2 * ns * sizeof(double), hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-// pt_render_denoised_motion with the alpha plane between the ids pass and the accumulation, and the frame's noisy film kept
-// for the next call.  any_camera (pt_render_denoised_gradient_camera): the previous frame stays usable when the camera moved,
-// and the plane is pt_temporal_gradient_camera_device's.
-static int render_gradient_impl(const char* who, bool any_camera, PtContext* c, const PtCamera* cam, const PtRenderParams* prm,
-                                uint32_t feature_samples, const PtDenoise* dn, const PtTemporal* tp, const PtGradient* g, float* out_linear,
-                                uint8_t* out_rgba, float* out_noisy, float* out_features, int32_t* out_ids, float* out_alpha) {
-    if (!c || !cam || !prm || !dn || !tp || !g || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
-    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "%s: renders the whole image (band_count = 1)", who);
-    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
-    if (g->radius > ptgr::kMaxRadius) return fail(PT_ERR_INVALID_ARG, "%s: radius %u (at most %u)", who, g->radius, ptgr::kMaxRadius);
-    if (!(g->scale >= 0.0f) || !std::isfinite(g->scale)) return fail(PT_ERR_INVALID_ARG, "%s: scale must be finite and >= 0", who);
-    if (!(tp->alpha >= 0.0f && tp->alpha <= 1.0f)) return fail(PT_ERR_INVALID_ARG, "%s: alpha %g not in [0, 1]", who, tp->alpha);
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
-    const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
-    const size_t np = (size_t)np64;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) ||
-        (rc = c->dn_lin.ensure(3 * np)) || (rc = c->dn_ids.ensure(np)) || (rc = c->gr_alpha.ensure(np)))
-        return rc;
-    // the previous frame is usable: one of the two entries completed it, at this size, through this camera (any_camera: through
-    // any), and the history it went into is there
-    bool usable = c->gr_valid && c->tm_valid && c->gr_prev.cap >= 3 * np && c->gr_cam.width == cam->width && c->gr_cam.height == cam->height;
-    for (int k = 0; k < 3 && !any_camera; ++k)
-        usable = usable && c->gr_cam.origin[k] == cam->origin[k] && c->gr_cam.lower_left[k] == cam->lower_left[k] &&
-                 c->gr_cam.horizontal[k] == cam->horizontal[k] && c->gr_cam.vertical[k] == cam->vertical[k];
-    const PtCamera prev_cam = c->gr_cam;
-    c->gr_valid = false;                      // (a frame that fails from here on leaves none)
-    PtRenderParams p = *prm;
-    p.band_count = 1; p.band_index = 0; p.band_rows = 0;
-    float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
-    uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
-    if ((rc = render_impl(c, cam, &p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
-        (rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat)) ||
-        (rc = pt_render_feature_ids_device(c, cam, &p, c->dn_ids.p)))
-        return rc;
-    if (usable) {
-        if ((rc = any_camera ? pt_temporal_gradient_camera_device(c, cam, &prev_cam, &c->gr_params, c->gr_frame, c->gr_prev.p, feat, g,
-                                                                  tp->alpha, c->gr_alpha.p)
-                             : pt_temporal_gradient_device(c, cam, &c->gr_params, c->gr_frame, c->gr_prev.p, g, tp->alpha, c->gr_alpha.p)))
-            return rc;
-    } else {
-        HIP_TRY(hipMemsetAsync(c->gr_alpha.p, 0xFF, np * sizeof(float), c->stream));      // every entry a NaN: no measurement
-    }
-    if ((rc = pt_denoise_temporal_alpha_device(c, cam, c->host_lin.p, feat, c->dn_ids.p, c->gr_alpha.p, dn, tp, c->dn_lin.p, rgba)) ||
-        (rc = c->gr_prev.ensure(3 * np)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(c->gr_prev.p, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = pt_sync(c))) return rc;
-    c->gr_valid = true; c->gr_params = p; c->gr_cam = *cam; ++c->gr_frame;
-    HIP_TRY(hipMemcpy(out_linear, c->dn_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    if (out_noisy) HIP_TRY(hipMemcpy(out_noisy, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_features) HIP_TRY(hipMemcpy(out_features, feat, 8 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_ids) HIP_TRY(hipMemcpy(out_ids, c->dn_ids.p, np * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (out_alpha) HIP_TRY(hipMemcpy(out_alpha, c->gr_alpha.p, np * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return copy_back({{out_xy, c->gr_list.p, ns * sizeof(uint2)}, {out_film, c->gr_film.p, 3 * ns * sizeof(float)},
+                      {out_rec, c->gr_rec.p, 2 * ns * sizeof(double)}});
 }
 
 int pt_render_denoised_gradient(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtDenoise* dn,
                                 const PtTemporal* tp, const PtGradient* g, float* out_linear, uint8_t* out_rgba, float* out_noisy,
                                 float* out_features, int32_t* out_ids, float* out_alpha) {
-    return render_gradient_impl("pt_render_denoised_gradient", false, c, cam, prm, feature_samples, dn, tp, g, out_linear, out_rgba, out_noisy,
-                                out_features, out_ids, out_alpha);
+    return render_gradient_impl("pt_render_denoised_gradient", Strata::same_camera, c, cam, prm, feature_samples, dn, tp, g, out_linear, out_rgba,
+                                out_noisy, out_features, out_ids, out_alpha);
 }
 
 int pt_render_denoised_gradient_camera(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                                        const PtDenoise* dn, const PtTemporal* tp, const PtGradient* g, float* out_linear, uint8_t* out_rgba,
                                        float* out_noisy, float* out_features, int32_t* out_ids, float* out_alpha) {
-    return render_gradient_impl("pt_render_denoised_gradient_camera", true, c, cam, prm, feature_samples, dn, tp, g, out_linear, out_rgba,
-                                out_noisy, out_features, out_ids, out_alpha);
+    return render_gradient_impl("pt_render_denoised_gradient_camera", Strata::prev_camera, c, cam, prm, feature_samples, dn, tp, g, out_linear,
+                                out_rgba, out_noisy, out_features, out_ids, out_alpha);
 }
 
 int pt_render_denoised_temporal(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                                 const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,
                                 float* out_features) {
-    if (!c || !cam || !prm || !dn || !tp || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_denoised_temporal: null argument");
-    return render_denoised_impl("pt_render_denoised_temporal", c, cam, prm, feature_samples, dn, tp, out_linear, out_rgba, out_noisy,
-                                out_features);
+    return render_denoised_impl("pt_render_denoised_temporal", History::plain, c, cam, prm, feature_samples, dn, tp, out_linear, out_rgba,
+                                out_noisy, out_features, nullptr);
 }
 
 }  // extern "C"
