@@ -10,6 +10,13 @@
 // render_denoised_gradient_camera(2): the previous frame stays usable across set_camera().
 //
 //   ./gradient_frames --camera [width height spp frames [out_prefix [dim_frame]]]        dim_frame defaults to frames - 1
+//
+// --tonemap: the ten-sphere box (built-in scene 2) stands still under a fixed camera, the light is dimmed to a quarter from
+// frame dim_frame on, every frame is one render_denoised_gradient(2) and then World::tonemap() with the defaults (auto
+// exposure).  <out_prefix>_exposure.txt: per frame log2E and the mean RGBA8 luminance of the fixed sqrt transform and of the
+// tone-mapped frame; <out_prefix>.ppm is the last tone-mapped frame.
+//
+//   ./gradient_frames --tonemap [width height spp frames [out_prefix [dim_frame]]]       dim_frame defaults to frames / 2
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,13 +32,52 @@ static Camera orbit_camera(uint32_t k, uint32_t w, uint32_t h) {
     return Camera::look_at(Vector3(2.0 * (2.0 * t) / q, 0.0, 2.0 * (1.0 - t * t) / q), Vector3(0.0, 0.0, 0.0), Vector3(0.0, 1.0, 0.0), w, h, 35.0);
 }
 
+static double mean_luma8(const std::vector<Color>& data) {
+    double s = 0.0;
+    for (const Color& c : data) s += 0.2126 * c.r + 0.7152 * c.g + 0.0722 * c.b;
+    return data.empty() ? 0.0 : s / (double)data.size();
+}
+
+static int tonemap_frames(uint32_t w, uint32_t h, uint32_t spp, uint32_t frames, const std::string& prefix, uint32_t dim_frame) {
+    uint32_t n = 0;
+    if (pt_builtin_scene(2, 0, nullptr, 0, &n) != PT_OK) throw std::runtime_error(pt_last_error());
+    std::vector<PtObject> objs(n);
+    if (pt_builtin_scene(2, 0, objs.data(), n, &n) != PT_OK) throw std::runtime_error(pt_last_error());
+    World world(Camera::new_(Vector3(0.0, 0.0, 2.0), w, h, 1.0, 35.0));
+    for (const PtObject& o : objs) world.push(Object::from_pod(o));
+    world.params().spp = spp;
+    FILE* f = std::fopen((prefix + "_exposure.txt").c_str(), "w");
+    if (!f) throw std::runtime_error("cannot create " + prefix + "_exposure.txt");
+    for (uint32_t i = 0; i < frames; ++i) {
+        world.params().spp_offset = i * spp;
+        if (i == dim_frame) {
+            for (size_t k = 0; k < world.object_count(); ++k) {
+                PtObject o = world.object(k).pod();
+                if (o.mat_tag != PT_MAT_EMISSIVE) continue;
+                for (int j = 0; j < 3; ++j) o.mat[j] *= 0.25;
+                world.set_object(k, Object::from_pod(o));
+            }
+            world.scene_update();
+        }
+        world.render_denoised_gradient(2);
+        const double fixed = mean_luma8(world.data);
+        const double log2E = world.tonemap();
+        std::fprintf(f, "%.9f %.3f %.3f\n", log2E, fixed, mean_luma8(world.data));
+    }
+    std::fclose(f);
+    world.write_ppm(prefix + ".ppm");
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const bool camera = argc > 1 && std::string(argv[1]) == "--camera";
-    if (camera) { --argc; ++argv; }
+    const bool tonemap = argc > 1 && std::string(argv[1]) == "--tonemap";
+    if (camera || tonemap) { --argc; ++argv; }
     const uint32_t w = argc > 4 ? (uint32_t)std::atoi(argv[1]) : 48, h = argc > 4 ? (uint32_t)std::atoi(argv[2]) : 32;
     const uint32_t spp = argc > 4 ? (uint32_t)std::atoi(argv[3]) : 2, frames = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 3;
     const std::string prefix = argc > 5 ? argv[5] : "gradient";
     try {
+        if (tonemap) return tonemap_frames(w, h, spp, frames, prefix, argc > 6 ? (uint32_t)std::atoi(argv[6]) : frames / 2);
         World world = World::new_();
         world.set_camera(Camera::new_(Vector3(0.0, 0.0, 2.0), w, h, 1.0, 35.0));
         world.params().spp = spp;

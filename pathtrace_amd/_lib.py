@@ -116,6 +116,22 @@ class PtGradient(C.Structure):
     ]
 
 
+class PtTonemap(C.Structure):
+    _fields_ = [
+        ("mode", C.c_uint32),
+        ("curve", C.c_uint32),
+        ("transfer", C.c_uint32),
+        ("ev", C.c_float),
+        ("key", C.c_float),
+        ("pct_lo", C.c_float),
+        ("pct_hi", C.c_float),
+        ("log2_min", C.c_float),
+        ("log2_max", C.c_float),
+        ("adapt", C.c_float),
+        ("white", C.c_float),
+    ]
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -144,6 +160,9 @@ PT_EXCHANGE_RCCL, PT_EXCHANGE_COPY = 0, 1
 PT_SHAPE_SPHERE, PT_SHAPE_TRIANGLE = 0, 1
 PT_MAT_LAMBERT, PT_MAT_EMISSIVE, PT_MAT_MIRROR, PT_MAT_OREN_NAYAR = 0, 1, 2, 3
 PT_INTEGRATOR_MIS, PT_INTEGRATOR_BRDF_ONLY = 0, 1
+PT_EXPOSURE_AUTO, PT_EXPOSURE_MANUAL = 0, 1
+PT_CURVE_CLAMP, PT_CURVE_REINHARD, PT_CURVE_ACES = 0, 1, 2
+PT_TRANSFER_SQRT, PT_TRANSFER_SRGB = 0, 1
 PT_STREAM_LEGACY_DEFAULT = 1      # pt_context_set_stream: HIP's legacy default stream (handle 0 means "the context's own")
 
 # every symbol include/pathtrace_amd.h declares: name -> (restype, argtypes)
@@ -240,6 +259,16 @@ SYMBOLS = {
                                                      C.c_void_p, _P(PtGradient), C.c_float, C.c_void_p]),
     "pt_render_denoised_gradient_camera": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), _P(PtTemporal),
                                                      _P(PtGradient), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_default_tonemap": (None, [_P(PtTonemap)]),
+    "pt_film_histogram_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pt_tonemap_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _P(PtTonemap), C.c_void_p, C.c_void_p]),
+    "pt_tonemap_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _P(PtTonemap), C.c_void_p, C.c_void_p]),
+    "pt_exposure_reset": (C.c_int, [C.c_void_p]),
+    "pt_exposure_get": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_uint32)]),
+    "pt_debug_exposure_state": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_float), _P(C.c_uint32), _P(C.c_uint32)]),
+    "pt_debug_tonemap_bin": (C.c_uint32, [C.c_float]),
+    "pt_debug_tonemap_meter": (C.c_double, [_P(C.c_uint32), _P(PtTonemap), C.c_int, C.c_double]),
+    "pt_debug_tonemap_pixel": (C.c_int, [_P(PtTonemap), C.c_float, _P(C.c_float), _P(C.c_float), _P(C.c_uint8)]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

@@ -71,6 +71,24 @@ def default_gradient(**over):
     return g
 
 
+MODES = {"auto": _lib.PT_EXPOSURE_AUTO, "manual": _lib.PT_EXPOSURE_MANUAL}
+CURVES = {"clamp": _lib.PT_CURVE_CLAMP, "reinhard": _lib.PT_CURVE_REINHARD, "aces": _lib.PT_CURVE_ACES}
+TRANSFERS = {"sqrt": _lib.PT_TRANSFER_SQRT, "srgb": _lib.PT_TRANSFER_SRGB}
+
+
+def default_tonemap(**over):
+    """pt_default_tonemap with keyword overrides (None keeps the default); mode, curve and transfer also by name."""
+    t = _lib.PtTonemap()
+    lib().pt_default_tonemap(C.byref(t))
+    names = {"mode": MODES, "curve": CURVES, "transfer": TRANSFERS}
+    for k, v in over.items():
+        if v is not None:
+            if not hasattr(t, k):
+                raise AttributeError(f"PtTonemap has no field {k}")
+            setattr(t, k, names[k].get(v, v) if k in names else v)
+    return t
+
+
 def builtin_scene(scene_id, arg=0):
     """Scenes of SURVEY 8(d): 1 reference Cornell box, 2 ten-sphere Cornell, 4 random spheres (arg = n)."""
     n = C.c_uint32(0)
@@ -559,6 +577,43 @@ class _ContextFunctions:
         out, rgba = self._film_pair(H, W)
         self._on_stream(lib().pt_denoise_temporal_alpha_device, C.byref(cam), d_lin, d_feat, d_ids, d_alpha, C.byref(dn), C.byref(tp), out, rgba)
         return out.cpu().numpy(), rgba.cpu().numpy()
+
+    def film_histogram(self, linear):
+        """pt_film_histogram_device on a film (f32[H,W,3]) -> u32[258]: the 256 bins, dark, invalid"""
+        H, W = np.shape(linear)[:2]
+        d_lin = self._upload(linear, np.float32, (H, W, 3))
+        hist = self._empty((258,), "int32")
+        self._on_stream(lib().pt_film_histogram_device, W, H, d_lin, hist)
+        return hist.cpu().numpy().view(np.uint32)
+
+    def tonemap(self, linear, in_place=False, **over):
+        """pt_tonemap_device on a film (f32[H,W,3]); the keywords are default_tonemap's.  in_place: the float plane is
+        written over the uploaded film.  -> (rgba u8[H,W,4], linear f32[H,W,3] in front of the transfer)"""
+        tm = default_tonemap(**over)
+        H, W = np.shape(linear)[:2]
+        d_lin = self._upload(linear, np.float32, (H, W, 3))
+        out, rgba = self._film_pair(H, W)
+        if in_place:
+            out = d_lin
+        self._on_stream(lib().pt_tonemap_device, W, H, d_lin, C.byref(tm), out, rgba)
+        return rgba.cpu().numpy(), out.cpu().numpy()
+
+    def exposure_reset(self):
+        """pt_exposure_reset: the next auto-exposure frame jumps to its target."""
+        check(lib().pt_exposure_reset(self._h))
+
+    def exposure(self):
+        """pt_exposure_get -> (log2E, the last histogram u32[258])"""
+        v = C.c_double(0)
+        hist = np.zeros(258, dtype=np.uint32)
+        check(lib().pt_exposure_get(self._h, C.byref(v), _pu(hist)))
+        return v.value, hist
+
+    def debug_exposure_state(self):
+        """pt_debug_exposure_state -> (log2E, the device's E as np.float32, valid)"""
+        v, e, ok = C.c_double(0), C.c_float(0), C.c_uint32(0)
+        check(lib().pt_debug_exposure_state(self._h, C.byref(v), C.byref(e), C.byref(ok), None))
+        return v.value, np.float32(e.value), ok.value
 
     def _render_gradient(self, entry, cam, params, feature_samples, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None, alpha=None,
                          depth_tol=None, normal_tol=None, radius=None, scale=None):

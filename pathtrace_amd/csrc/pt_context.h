@@ -69,6 +69,14 @@ template <class T> struct Pinned {   // host words the device can reach; dev: th
     }
 };
 
+struct TonemapState {   // pt_tonemap_device: the last histogram (258 words) and the exposure state, allocated and zeroed at first use
+    DevBuf<uint32_t> hist;
+    DevBuf<ptk::ExposureState> state;
+    DevBuf<float> lin;            // pt_tonemap_host: device staging of the film (in place) and of the RGBA8 plane
+    DevBuf<uint8_t> rgba;
+    int ensure(hipStream_t st);   // pt_tonemap.cpp
+};
+
 // lanes, buffer sets and the core size of overlapping launches: pt_sched.h (the scheduler's constants)
 using ptsched::kLanes;
 using ptsched::kSets;
@@ -232,6 +240,8 @@ struct PtContext {
     PtRenderParams gr_params{};
     PtCamera gr_cam{};
     uint32_t gr_frame = 0;
+    // pt_tonemap_device: the exposure lives on the device; no scene entry touches it
+    TonemapState tone;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).

@@ -445,4 +445,31 @@ struct BvhMedianArgs {
 };
 uint32_t launch_bvh_median(const BvhMedianArgs& a, const BvhMedianLevel* levels, uint32_t n_levels, hipStream_t st);
 
+// Auto-exposure and tone mapping (pt_tonemap_device; rule: pt_tonemap.h).  All launches on one stream:
+//   launch_film_histogram   the 258 words of the film's luminance histogram, added to hist: the caller zeroes it in front
+//   launch_exposure_meter   one wave: hist and the parameters -> the context's exposure state
+//   launch_tonemap          per pixel the curve and the transfer under the exposure *e_dev (null: e_manual)
+struct ExposureState {         // device words the context owns; all zero = no exposure yet
+    double log2E;
+    float E;
+    uint32_t valid, width, height, pad[2];
+};
+struct ExposureArgs {
+    const uint32_t* hist;
+    ExposureState* state;
+    uint32_t width, height;
+    float pct_lo, pct_hi, key, log2_min, log2_max, adapt;
+};
+struct TonemapArgs {
+    const float* linear;       // width * height * 3; may be out_linear
+    float* out_linear;         // may be null
+    uint8_t* out_rgba;
+    const float* e_dev;
+    float e_manual, white;
+    uint32_t np, curve, transfer;
+};
+void launch_film_histogram(const float* linear, uint32_t np, uint32_t* hist, uint32_t n_cus, hipStream_t st);
+void launch_exposure_meter(const ExposureArgs& a, hipStream_t st);
+void launch_tonemap(const TonemapArgs& a, hipStream_t st);
+
 }  // namespace ptk

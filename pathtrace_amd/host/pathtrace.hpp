@@ -16,6 +16,7 @@
 //   World::render_denoised_motion()    ... whose history also follows objects moved with set_object() + scene_update()
 //   World::render_denoised_gradient()  ... and forgets faster where the lighting changed (temporal gradients)
 //   World::render_denoised_gradient_camera()  ... also while the camera moves
+//   World::tonemap()                   auto-exposure, curve and transfer on the film the World holds
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -596,6 +597,31 @@ private:
         unpack(lin, rgba);
     }
 public:
+    // The display transform on the film this World holds (pt_tonemap_host): luminance_data -> data, through the exposure the
+    // World's context adapts from frame to frame (tm: pt_default_tonemap when null -- auto exposure, ACES, sqrt transfer).
+    // luminance_data stays the linear film; mapped (optional) receives the tone-mapped film in front of the transfer.
+    // Returns log2 of the exposure the context holds after the frame.
+    double tonemap(const PtTonemap* tm = nullptr, std::vector<Vector3>* mapped = nullptr, int device = 0) {
+        check_abi();
+        if (!ctx_) check(pt_context_create(device, &ctx_));
+        PtTonemap t{};
+        if (tm) t = *tm; else pt_default_tonemap(&t);
+        const size_t n = luminance_data.size();
+        std::vector<float> lin(n * 3), out(mapped ? n * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        for (size_t i = 0; i < n; ++i) { lin[3 * i] = (float)luminance_data[i].x; lin[3 * i + 1] = (float)luminance_data[i].y; lin[3 * i + 2] = (float)luminance_data[i].z; }
+        check(pt_tonemap_host(ctx_, camera_.width(), camera_.height(), lin.data(), &t, mapped ? out.data() : nullptr, rgba.data()));
+        for (size_t i = 0; i < n; ++i) data[i] = Color{rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]};
+        if (mapped) {
+            mapped->resize(n);
+            for (size_t i = 0; i < n; ++i) (*mapped)[i] = Vector3(out[3 * i], out[3 * i + 1], out[3 * i + 2]);
+        }
+        double log2E = 0.0;
+        check(pt_exposure_get(ctx_, &log2E, nullptr));
+        return log2E;
+    }
+    // the next auto-exposure frame jumps to its target (pt_exposure_reset)
+    void exposure_reset() { if (ctx_) check(pt_exposure_reset(ctx_)); }
     // the next render_denoised_temporal starts without history (pt_temporal_reset)
     void temporal_reset() { if (ctx_) check(pt_temporal_reset(ctx_)); }
     // moves the camera (the film follows its size); the temporal history stays and is reprojected

@@ -115,6 +115,30 @@ pub struct PtGradient {
     pub scale: f32,
 }
 
+/// pt_tonemap_device: exposure, curve and transfer of the display transform (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtTonemap {
+    pub mode: u32,
+    pub curve: u32,
+    pub transfer: u32,
+    pub ev: f32,
+    pub key: f32,
+    pub pct_lo: f32,
+    pub pct_hi: f32,
+    pub log2_min: f32,
+    pub log2_max: f32,
+    pub adapt: f32,
+    pub white: f32,
+}
+pub const PT_EXPOSURE_AUTO: u32 = 0;
+pub const PT_EXPOSURE_MANUAL: u32 = 1;
+pub const PT_CURVE_CLAMP: u32 = 0;
+pub const PT_CURVE_REINHARD: u32 = 1;
+pub const PT_CURVE_ACES: u32 = 2;
+pub const PT_TRANSFER_SQRT: u32 = 0;
+pub const PT_TRANSFER_SRGB: u32 = 1;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct PtStats {
@@ -283,6 +307,16 @@ extern "C" {
     pub fn pt_render_feature_ids_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, d_ids: *mut i32) -> c_int;
     pub fn pt_denoise_temporal_motion_device(ctx: *mut PtContext, cam: *const PtCamera, d_linear_rgb: *const f32, d_features: *const f32, d_ids: *const i32, dn: *const PtDenoise, tp: *const PtTemporal, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_denoised_motion(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, tp: *const PtTemporal, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32, out_ids: *mut i32) -> c_int;
+    pub fn pt_default_tonemap(out: *mut PtTonemap);
+    pub fn pt_film_histogram_device(ctx: *mut PtContext, width: u32, height: u32, d_linear_rgb: *const f32, d_hist258: *mut u32) -> c_int;
+    pub fn pt_tonemap_device(ctx: *mut PtContext, width: u32, height: u32, d_linear_rgb: *const f32, tm: *const PtTonemap, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_tonemap_host(ctx: *mut PtContext, width: u32, height: u32, linear_rgb: *const f32, tm: *const PtTonemap, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_exposure_reset(ctx: *mut PtContext) -> c_int;
+    pub fn pt_exposure_get(ctx: *mut PtContext, log2e: *mut f64, hist258: *mut u32) -> c_int;
+    pub fn pt_debug_exposure_state(ctx: *mut PtContext, log2e: *mut f64, e: *mut f32, valid: *mut u32, hist258: *mut u32) -> c_int;
+    pub fn pt_debug_tonemap_bin(lum: f32) -> u32;
+    pub fn pt_debug_tonemap_meter(hist258: *const u32, tm: *const PtTonemap, fresh: c_int, log2e_prev: f64) -> f64;
+    pub fn pt_debug_tonemap_pixel(tm: *const PtTonemap, e: f32, rgb: *const f32, out_y: *mut f32, out_rgba8: *mut u8) -> c_int;
     pub fn pt_default_gradient(out: *mut PtGradient);
     pub fn pt_temporal_gradient_device(ctx: *mut PtContext, cam: *const PtCamera, prev_params: *const PtRenderParams, seed: u32, d_prev_linear: *const f32, g: *const PtGradient, alpha_min: f32, d_alpha: *mut f32) -> c_int;
     pub fn pt_debug_gradient_strata(ctx: *mut PtContext, width: u32, height: u32, out_xy: *mut u32, out_film: *mut f32, out_rec: *mut f64) -> c_int;
