@@ -372,6 +372,31 @@ void pt_debug_sched_destroy(PtSched* s);
 int pt_debug_sched_render(PtSched* s, const PtSchedJob* job, uint32_t faults, uint32_t fail_after, PtSchedOp* ops, uint32_t cap,
                           uint32_t* n_ops, uint32_t* lanes);
 int pt_debug_sched_sync(PtSched* s, uint32_t collect);        /* pt_sync: everything enqueued is complete (collect: statistics read and cleared) */
+/* The launch sizing of a render, host only (no GPU needed).  What pt_render_device* derives from the scene, the parameters, the
+ * tuning and the device before it allocates or enqueues anything -- the level-0 form, the batches, every grid, segment and queue
+ * size, the job the scheduler plans -- is a PURE function too (csrc/pt_shape.h); this entry runs it on the caller's numbers.
+ * occupancy: workgroups per CU the runtime reports for the form's regenerating kernel with the scene's LDS blob (0: unknown).
+ * out->job can be handed to pt_debug_sched_render as it is; ops (optional): n_ops operations of such a plan -- launches[k]
+ * receives the per-launch words of operation k where that is a launch, zeros otherwise.  A tile above the cap:
+ * PT_ERR_UNSUPPORTED with out->over_cap = 1 and out->cap.  Field meanings: csrc/pt_shape.h (In, Form, Shape, Launch).          */
+typedef struct {
+    uint64_t np, max_paths_in_flight;
+    uint32_t spp, workgroups, accel, profile, list, list_regen, inject, n_objs, blob_f4, diffuse_only, split_ok, n_cus;
+    uint32_t export_below, cont_workgroups, level0_form, regen_workgroups, in_order, capturing;
+} PtShapeIn;
+typedef struct {
+    uint32_t lds_job, split, regen_scene, over_cap;
+    uint64_t cap, n_paths_max, ovf_slots, q_slots_cont, q_slots;
+    uint32_t np, spp, nb_max, n_batches, export_small, paths_per_wave, small_scene, hand_off, regen, overlap;
+    uint32_t grid, nw, seg_cap, regen_per_cu, regen_capacity, regen_grid, regen_launch_grid, cont_grid, nw_cont, seg_cap_cont;
+    uint32_t regen_export, reserved;
+    PtSchedJob job;
+} PtShapeOut;
+typedef struct {
+    uint32_t s0, nb, n_first, seg_cap, src_mode, export_below, regen_static, reserved;
+} PtShapeLaunch;
+int pt_debug_render_shape(const PtShapeIn* in, uint32_t occupancy, PtShapeOut* out, const PtSchedOp* ops, uint32_t n_ops,
+                          PtShapeLaunch* launches);
 /* Test hook: the n-th stream operation (0-based) of the NEXT render on this context fails as if its HIP call had (n < 0: none). */
 int pt_debug_fail_after(PtContext* ctx, int64_t n);
 /* Launch log: which compiled instance of the path kernels each launch took.  One code per path-kernel launch, recorded on the

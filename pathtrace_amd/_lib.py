@@ -142,6 +142,24 @@ class PtSchedOp(C.Structure):
                                           "seq", "core", "flags", "zero_words", "reserved")] + [("xchg_off", C.c_uint64), ("xchg_len", C.c_uint64)]
 
 
+class PtShapeIn(C.Structure):
+    _fields_ = [("np", C.c_uint64), ("max_paths_in_flight", C.c_uint64)] + [(n, C.c_uint32) for n in (
+        "spp", "workgroups", "accel", "profile", "list", "list_regen", "inject", "n_objs", "blob_f4", "diffuse_only", "split_ok", "n_cus",
+        "export_below", "cont_workgroups", "level0_form", "regen_workgroups", "in_order", "capturing")]
+
+
+class PtShapeOut(C.Structure):
+    _fields_ = ([(n, C.c_uint32) for n in ("lds_job", "split", "regen_scene", "over_cap")] +
+                [(n, C.c_uint64) for n in ("cap", "n_paths_max", "ovf_slots", "q_slots_cont", "q_slots")] +
+                [(n, C.c_uint32) for n in ("np", "spp", "nb_max", "n_batches", "export_small", "paths_per_wave", "small_scene", "hand_off", "regen",
+                                           "overlap", "grid", "nw", "seg_cap", "regen_per_cu", "regen_capacity", "regen_grid", "regen_launch_grid",
+                                           "cont_grid", "nw_cont", "seg_cap_cont", "regen_export", "reserved")] + [("job", PtSchedJob)])
+
+
+class PtShapeLaunch(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("s0", "nb", "n_first", "seg_cap", "src_mode", "export_below", "regen_static", "reserved")]
+
+
 class PtMultiInfo(C.Structure):
     _fields_ = [
         ("n_devices", C.c_uint32),
@@ -283,6 +301,7 @@ SYMBOLS = {
     "pt_debug_sched_destroy": (None, [C.c_void_p]),
     "pt_debug_sched_render": (C.c_int, [C.c_void_p, _P(PtSchedJob), C.c_uint32, C.c_uint32, _P(PtSchedOp), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
     "pt_debug_sched_sync": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "pt_debug_render_shape": (C.c_int, [_P(PtShapeIn), C.c_uint32, _P(PtShapeOut), _P(PtSchedOp), C.c_uint32, _P(PtShapeLaunch)]),
     "pt_debug_fail_after": (C.c_int, [C.c_void_p, C.c_int64]),
     "pt_debug_launch_log": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),
     "pt_debug_path_instances": (C.c_int, [_P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),

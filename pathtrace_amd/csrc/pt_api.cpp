@@ -12,57 +12,12 @@
 #include <cstring>
 
 #include "pt_context.h"
+#include "pt_shape.h"
 
 namespace {
 
-constexpr uint64_t kDefaultMaxPaths = 1ull << 26;
-// ... where the level-0 launch keeps its paths in registers (k_paths_regen) a path in flight costs 12 bytes of sample buffer
-// instead of 76, and every batch ends in a ~0.3 ms tail: larger batches (C3: 16 instead of 64)
-constexpr uint64_t kDefaultMaxPathsRegen = 1ull << 28;
-// Default number of workgroups.  What matters is that the queue segments of the RESIDENT waves fit the 256 MiB
-// Infinity Cache (and that the dispatcher has enough workgroups to balance the end of the launch; much smaller
-// segments pay more low-occupancy tail passes).  Scene in LDS, 6 waves/SIMD = 6144 resident waves: ~672 paths
-// (42 KiB of queue) per wave -- measured at 67 M paths: 8192 workgroups 10.31 ms, 12288 10.12, 16384 9.86,
-// 24576 9.61 (best), 32768 9.69.  Tiled scan and BVH kernels (4-5 waves/SIMD): ~1024 paths per wave (measured at
-// 4 waves/SIMD: 2048 workgroups 11.6 ms, 8192 10.7, 16384 10.2 (best), 32768 10.6, 65536 11.7).
-constexpr uint32_t kPathsPerWaveLds = 672;
-constexpr uint32_t kPathsPerWave = 1024;
-constexpr uint32_t kMinGrid = 256 * 8;         // level-0 launches: at least this many workgroups (small renders)
-// continuation launches: their paths are sparse survivors, and a wave-iteration costs the same however few of its
-// lanes carry a path, so more, emptier segments cost time -- and so do too few waves (latency of ~35 dependent passes).
-// Measured on C2 / C1, ms of the continuation launch: 96 workgroups 1.75 / 5.0, 192 0.98 / 2.7, 384 0.60 / 1.6,
-// 768 0.44 / 1.16, 1024 0.46, 1536 0.51 / 1.19, 3072 0.69 (round 1: 6144 -> +0.8).
-constexpr uint32_t kContGrid = 1024;
-#ifndef PT_REGEN_EXPORT
-#define PT_REGEN_EXPORT 1
-#endif
-constexpr uint32_t kCountStride = (1 + ptk::kRegenCounters) * ptk::kRegenCounterStride;   // uint32 per batch parity: leftover count + chunk counters
-#ifndef PT_SPLIT_BY_DEFAULT
-#define PT_SPLIT_BY_DEFAULT 1
-#endif
-constexpr bool kSplitByDefault = PT_SPLIT_BY_DEFAULT != 0;   // scenes with a minority of Mirror objects: k_paths_regen_split (else the queue form)
-#ifndef PT_REGEN_STATIC16
-#define PT_REGEN_STATIC16 4
-#endif
-constexpr uint32_t kRegenStatic16 = PT_REGEN_STATIC16;   // k_paths_regen: sixteenths of a batch's chunks dealt round-robin, the rest by the counters
-constexpr uint32_t kRegenExportBelow = PT_REGEN_EXPORT;  // ... and its waves hand over once the batch is used up and fewer paths than this are alive
-                                               // (1: they run dry themselves and no continuation launch follows)
-constexpr uint32_t kExportSmall = 64;          // a wave hands its segment over when fewer paths than this are left
-                                               // (measured 32 ... 256: no difference beyond noise on C1 and C2)
-// Tail hand-off: in launches of more than kExportMinPaths paths a wave whose segment falls below one chunk
-// exports its leftovers to the overflow queue instead of walking them alone; the next launch takes them up.
-// Measured (C2 / C1 ms per 1024^2 x 64 render): no hand-off 10.33 / 18.5; threshold 2^18 (3-4 levels) 11.2 / 16.9;
-// 2^22 (2 levels) 10.28 / 15.65; exporting below 32 or 16 paths instead of 64 is slower.
-#ifndef PT_EXPORT_MIN_LOG2
-#define PT_EXPORT_MIN_LOG2 22
-#endif
-constexpr uint32_t kExportMinPaths = 1u << PT_EXPORT_MIN_LOG2;
-// batches of more paths than this take the regenerating level-0 kernel (where the scene allows it)
-#ifndef PT_REGEN_MIN_LOG2
-#define PT_REGEN_MIN_LOG2 17
-#endif
-constexpr uint32_t kRegenMinPaths = 1u << PT_REGEN_MIN_LOG2;
-constexpr uint32_t kWavesPerBlock = ptk::kBlock / 64;
+using ptshape::kCountStride;
+using ptshape::kDefaultMaxPaths;
 constexpr size_t kLaunchLogCap = 1u << 16;       // pt_debug_launch_log keeps this many codes between two reads
 
 int ensure_events(PtContext* c, size_t n) {
@@ -126,20 +81,28 @@ size_t tile_pixels(const PtCamera* cam, const PtRenderParams* prm) {
     return (size_t)pt_tile_rows(cam->height, prm->band_rows, prm->band_index, prm->band_count ? prm->band_count : 1) * cam->width;
 }
 
-}  // namespace
+// ---- render_impl's stages, in the order it runs them
 
-// The render driver behind every rendering entry: everything src/main.rs:43-60 does for the tile (or, with `list`,
-// for a pixel list / a set of given rays).  Enqueues on the context's streams and returns; no host synchronisation.
-// Three steps: PREPARE (validate, size, allocate every buffer the render will touch -- nothing is enqueued yet, so an
-// error here leaves the context as it was), PLAN (ptsched::plan on a copy of the scheduling state: pure), EXECUTE (the
-// plan's stream operations in order) and COMMIT of the copy.  A failure during EXECUTE: sched_recover.
-int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
-                float* d_linear, uint8_t* d_rgba, void* d_packed, const AdaptivePass* ad) {
-    if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "render: null argument");
+// Statistics belong to the renders enqueued since they were last collected (pt_sync / pt_get_stats): a caller that
+// pipelines several renders behind one synchronisation gets their sums (vertices, launches, kernel times), total_ms from
+// the first one's start to the last one's end.  One render per synchronisation: the statistics of that render, as ever.
+void begin_period(PtContext* c) {        // the first render since the last collection
+    std::memset(&c->stats, 0, sizeof c->stats);
+    c->primary_events.clear();
+    c->expected_samples = 0;
+}
+
+// CHECK, the part render_adaptive_impl makes too.  cam = null: the paths are given, no camera ray is generated.
+int check_scene_and_camera(const PtContext* c, const PtCamera* cam) {
     if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    const bool inject = list && list->inject[0];
-    if (!inject && (cam->width < 2 || cam->height < 2))   // get_ray_with_offset divides by width-1 / height-1 (camera.rs:140-141)
+    if (cam && (cam->width < 2 || cam->height < 2))   // get_ray_with_offset divides by width-1 / height-1 (camera.rs:140-141)
         return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    return PT_OK;
+}
+int check_render(const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const ListRender* list, const float* d_linear,
+                 const uint8_t* d_rgba) {
+    if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "render: null argument");
+    if (int rc = check_scene_and_camera(c, list && list->inject[0] ? nullptr : cam)) return rc;
     if (prm->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
     if (prm->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "unknown integrator %u", prm->integrator);
     if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
@@ -149,128 +112,62 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
     // the resolve stores a pixel's RGBA8 as one 32-bit word (a byte-offset pointer would fault on the device)
     if (d_rgba && (uintptr_t)d_rgba % 4u) return fail(PT_ERR_INVALID_ARG, "render: the RGBA8 output buffer must be 4-byte aligned");
     if (d_linear && (uintptr_t)d_linear % 4u) return fail(PT_ERR_INVALID_ARG, "render: the linear output buffer must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    PtRenderParams resolved = *prm;      // PT_ACCEL_AUTO -> what actually runs
-    if (prm->accel == PT_ACCEL_AUTO) {
-        resolved.accel = PT_ACCEL_LINEAR;
-        if (c->auto_bvh && !c->bvh_refused && !c->bvh_failed) {
-            const std::string keep = g_err;              // a refused BVH is not an error of this call
-            if (ensure_bvh(c) == PT_OK) resolved.accel = PT_ACCEL_BVH;
-            else g_err = keep;
-        }
-    }
-    prm = &resolved;
+    return PT_OK;
+}
 
-    const uint64_t np64 = list ? list->n : (uint64_t)pt_tile_rows(cam->height, prm->band_rows, prm->band_index, band_count) * cam->width;
-    const uint64_t tile_rows = list ? ((np64 + 65535u) >> 16) : np64 / cam->width;
-    // Statistics belong to the renders enqueued since they were last collected (pt_sync / pt_get_stats): a caller that
-    // pipelines several renders behind one synchronisation gets their sums (vertices, launches, kernel times), total_ms from
-    // the first one's start to the last one's end.  One render per synchronisation: the statistics of that render, as ever.
-    auto begin_period = [c]() {        // the first render since the last collection
-        std::memset(&c->stats, 0, sizeof c->stats);
-        c->primary_events.clear();
-        c->expected_samples = 0;
-    };
-    if (np64 == 0) {                   // empty tile: nothing to render
-        if (!c->sched.stats_pending) begin_period();
-        return PT_OK;
+// ACCEL: PT_ACCEL_AUTO -> what actually runs
+uint32_t resolve_accel(PtContext* c, uint32_t accel) {
+    if (accel != PT_ACCEL_AUTO) return accel;
+    if (c->auto_bvh && !c->bvh_refused && !c->bvh_failed) {
+        const std::string keep = g_err;              // a refused BVH is not an error of this call
+        if (ensure_bvh(c) == PT_OK) return PT_ACCEL_BVH;
+        g_err = keep;
     }
-    if (!d_linear && !d_packed) return fail(PT_ERR_INVALID_ARG, "render: the linear output buffer is null");
-    if (!list && (cam->width > 65535u || tile_rows > 65535u))   // (tile row, x) share one word of the path state
-        return fail(PT_ERR_UNSUPPORTED, "tile %ux%llu: width and tile rows must be < 65536", cam->width, (unsigned long long)tile_rows);
-    // scene / job that can take the regenerating level-0 kernel (decided below, once the batch size is known)
-    // level0_form 3 / default for scenes with a minority of Mirror objects: the regenerating form with the Mirror vertices batched
-    // (a list takes the regenerating kernel only where its caller asks for it, and never the split form)
-    const bool lds_job = (!list || list->regen) && !prm->accel && c->view.n_objs <= ptk::kSmallObjs && c->view.blob_f4 != 0;
-    const bool split = lds_job && !list && (c->tuning.level0_form == 3 || (c->tuning.level0_form == 0 && c->split_ok && kSplitByDefault));
-    // default (round 3): every scene in LDS takes a regenerating form -- compiled for its material set (diffuse only; no
-    // Mirror; everything); with the Mirror vertices batched where they are the exception (split, above).  The queue form
-    // is level0_form = 1 (all-Mirror Cornell scene: queue form 12.6 ms, regenerating 10.0, split 13.8; tools/r03/mirror_forms.py)
-    const bool regen_scene = split || ((c->tuning.level0_form == 2 || c->tuning.level0_form == 0) && lds_job);
-    uint64_t cap = prm->max_paths_in_flight ? prm->max_paths_in_flight : (regen_scene ? kDefaultMaxPathsRegen : kDefaultMaxPaths);
-    if (cap > (1ull << 30)) cap = 1ull << 30;
-    if (np64 > cap)
+    return PT_ACCEL_LINEAR;
+}
+
+// SIZE: the level-0 form, the batches and every grid, segment and queue size (pt_shape.h, pure).  The two things it needs from
+// the runtime are asked for here: whether the caller's stream is being captured, and -- once per scene and kernel, for scenes
+// that take a regenerating form -- that kernel's occupancy with the scene's LDS blob.
+int size_render(PtContext* c, const PtRenderParams* prm, const ListRender* list, uint64_t np64, ptshape::Shape* shape) {
+    ptshape::In in{};
+    in.np = np64; in.max_paths_in_flight = prm->max_paths_in_flight;
+    in.spp = prm->spp; in.workgroups = prm->workgroups; in.accel = prm->accel; in.profile = prm->profile;
+    in.list = list != nullptr; in.list_regen = list && list->regen; in.inject = list && list->inject[0];
+    in.n_objs = c->view.n_objs; in.blob_f4 = c->view.blob_f4; in.diffuse_only = c->view.diffuse_only;
+    in.split_ok = c->split_ok; in.n_cus = c->n_cus;
+    in.export_below = c->tuning.export_below; in.cont_workgroups = c->tuning.cont_workgroups; in.level0_form = c->tuning.level0_form;
+    in.regen_workgroups = c->tuning.regen_workgroups; in.in_order = c->tuning.in_order;
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        in.capturing = !(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone);
+        (void)hipGetLastError();
+    }
+    const ptshape::Form f = ptshape::form(in);
+    uint32_t* const occ = f.regen_scene ? &c->regen_occ[prm->exact_math ? 1 : 0][prm->integrator ? 1 : 0][f.split ? 1 : 0] : nullptr;   // per scene (pt_scene_upload clears it)
+    *shape = ptshape::shape(in, f, occ ? *occ : 0u);
+    if (shape->over_cap)
         return fail(PT_ERR_UNSUPPORTED, "tile of %llu pixels exceeds max_paths_in_flight %llu; use more bands",
-                    (unsigned long long)np64, (unsigned long long)cap);
-    const uint32_t np = (uint32_t)np64;
-    const uint32_t spp = inject ? 1u : prm->spp;
-    uint32_t nb_max = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(cap / np, 65535u), spp);
-    if (nb_max == 0) nb_max = 1;
-    const size_t n_paths_max = (size_t)np * nb_max;
-    const uint32_t n_batches = (spp + nb_max - 1) / nb_max;
-
-    // Queue segments: one per wave of the (fixed) grid; pass 0 deals 64-path chunks round-robin, so a segment holds
-    // at most ceil(chunks / waves) chunks.
-    const uint32_t export_small = c->tuning.export_below ? std::min(256u, std::max(1u, c->tuning.export_below)) : kExportSmall;
-    const uint32_t chunks_max = (uint32_t)((n_paths_max + 63) / 64);
-    uint32_t grid = prm->workgroups;
-    const bool small_scene = c->view.n_objs <= ptk::kSmallObjs || prm->accel;     // the tiled scan exports per workgroup (< 256 paths)
-    const uint32_t paths_per_wave = (c->view.n_objs <= ptk::kSmallObjs && !prm->accel) ? kPathsPerWaveLds : kPathsPerWave;
-    if (!grid) {
-        const uint64_t want = (n_paths_max + (uint64_t)paths_per_wave * kWavesPerBlock - 1) / ((uint64_t)paths_per_wave * kWavesPerBlock);
-        grid = (uint32_t)std::max<uint64_t>(want, kMinGrid);
-    }
-    grid = std::min<uint32_t>(grid, (chunks_max + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (grid == 0) grid = 1;
-    const uint32_t nw = grid * kWavesPerBlock;
-    const uint32_t seg_cap = ((chunks_max + nw - 1) / nw) * 64u;
-    // Tail hand-off: the level-0 launch of a large batch exports what its waves have left below one chunk; ONE
-    // continuation launch of fixed size takes that queue up.  It reads the count on the device.
-    // (scenes that take a regenerating level-0 kernel have their own threshold: that launch needs no continuation launch)
-    const bool hand_off = !inject && n_paths_max > (regen_scene ? kRegenMinPaths : kExportMinPaths);
-    // Such a batch over a scene in LDS takes the regenerating level-0 kernel: paths live in registers, a lane whose
-    // path ends takes the next one of the batch; grid = the waves the device holds at once (k_paths_regen).
-    const bool regen = regen_scene && hand_off;
-    // its grid = the workgroups the device holds at once: the kernel's occupancy with THIS scene's LDS blob (a 128-object
-    // scene leaves room for fewer workgroups per CU than the compile-time figure)
-    uint32_t regen_per_cu = split ? ptk::kRegenWavesSplit : c->view.diffuse_only ? ptk::kRegenWavesDiffuse : ptk::kRegenWavesGeneric;
-    if (regen_scene) {
+                    (unsigned long long)np64, (unsigned long long)shape->cap);
+    if (occ && *occ == 0u) {           // not asked yet (a refused tile never asks): the answer sizes this render and is kept
         ptk::BounceArgs q{};
         q.sc = view_for(c, prm->exact_math);
         q.integrator = prm->integrator;
-        q.xchg = split ? reinterpret_cast<float4*>(1) : nullptr;       // selects the kernel only
-        uint32_t& occ = c->regen_occ[prm->exact_math ? 1 : 0][prm->integrator ? 1 : 0][split ? 1 : 0];   // per scene (pt_scene_upload clears it)
-        if (occ == 0u) occ = prm->exact_math ? ptk::regen_blocks_per_cu_exact(q) : ptk::regen_blocks_per_cu_fast(q);
-        if (occ != 0u) regen_per_cu = std::min(regen_per_cu, occ);
+        q.xchg = f.split ? reinterpret_cast<float4*>(1) : nullptr;       // selects the kernel only
+        *occ = prm->exact_math ? ptk::regen_blocks_per_cu_exact(q) : ptk::regen_blocks_per_cu_fast(q);
+        if (*occ != 0u) *shape = ptshape::shape(in, f, *occ);
     }
-    const uint32_t regen_capacity = c->n_cus * regen_per_cu;          // workgroups the device holds at once
-    const uint32_t regen_grid = std::min(65536u, prm->workgroups ? prm->workgroups : c->tuning.regen_workgroups ? c->tuning.regen_workgroups : regen_capacity);
-    const uint32_t cont_grid = c->tuning.cont_workgroups ? std::min(65536u, c->tuning.cont_workgroups) : kContGrid;
-    const uint32_t nw_cont = cont_grid * kWavesPerBlock;
-    // leftovers per wave of the level-0 launch: < export_small from a wave-private segment, < 256 per workgroup
-    // (= 64 per wave) from a workgroup-shared one
-    const size_t ovf_slots = (size_t)(regen ? regen_grid * kWavesPerBlock : nw) * std::max(export_small, 64u) + 64u;
-    const uint32_t seg_cap_cont = (uint32_t)((((ovf_slots + 63) / 64 + nw_cont - 1) / nw_cont) * 64u);
-    const size_t q_slots_cont = hand_off ? (size_t)nw_cont * seg_cap_cont : 0;
-    const size_t q_slots = regen ? std::max<size_t>(q_slots_cont, 64) : std::max((size_t)nw * seg_cap, q_slots_cont);
-    const uint32_t regen_export = split ? 1u : c->tuning.export_below ? std::min(export_small, 64u) : kRegenExportBelow;   // the split form has no hand-over
-    // (sized by the grid the launch really takes: never more workgroups than the largest batch has chunks for)
-    const uint32_t regen_launch_grid = std::min<uint32_t>(regen_grid, (chunks_max + kWavesPerBlock - 1) / kWavesPerBlock);
+    return PT_OK;
+}
 
-    // ---- the job as the scheduler sees it (pt_sched.h)
-    ptsched::Job job;
-    job.n_batches = n_batches;
-    job.regen = regen; job.split = regen && split; job.hand_off = hand_off; job.regen_export = regen_export;
-    job.profile = prm->profile != 0; job.in_order = c->tuning.in_order != 0;
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        job.capturing = !(hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone);
-        (void)hipGetLastError();
-    }
-    job.grid = grid; job.regen_grid = regen_launch_grid; job.cont_grid = cont_grid;
-    job.regen_capacity = regen_capacity;
-    job.fixed_grid = prm->workgroups != 0 || c->tuning.regen_workgroups != 0;
-    job.counter_words = kCountStride;
-    job.xchg_need = job.split ? (size_t)regen_launch_grid * kWavesPerBlock * ptk::kRegenSplitF4PerWave + 1024 : 0;   // + slack: a violated stack invariant (reported) stays inside the buffer
-
-    // ---- PREPARE: every buffer the render will touch, before anything is enqueued
+// PREPARE: every buffer the render will touch, before anything is enqueued.  May turn the job into its in-order form.
+int prepare(PtContext* c, const PtRenderParams* prm, const FilmState& fs, const ptshape::Shape& sh, ptsched::Job& job) {
     int rc;
     if (prm->accel && (rc = ensure_bvh(c))) return rc;
     for (int k = 0; k < 4; ++k)
-        if ((rc = c->queue[k].ensure(q_slots))) return rc;
-    if (prm->accel && ((rc = c->bvh_aux.ensure(q_slots)) || (rc = c->bvh_sray[0].ensure(q_slots)) ||
-                       (rc = c->bvh_sray[1].ensure(q_slots))))
+        if ((rc = c->queue[k].ensure(sh.q_slots))) return rc;
+    if (prm->accel && ((rc = c->bvh_aux.ensure(sh.q_slots)) || (rc = c->bvh_sray[0].ensure(sh.q_slots)) ||
+                       (rc = c->bvh_sray[1].ensure(sh.q_slots))))
         return rc;
     {
         // The buffer sets the render rotates through (with lanes: up to three sample buffers of 12 B per path in flight -- 3 x 3.2 GB
@@ -280,7 +177,7 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
         uint32_t sets[4], n_sets = 0;
         ptsched::sets_of(c->sched, job, sets, &n_sets);
         for (uint32_t k = 0; k < n_sets; ++k) {
-            rc = c->lsamp[sets[k]].ensure(n_paths_max);
+            rc = c->lsamp[sets[k]].ensure(sh.n_paths_max);
             if (rc == PT_ERR_OOM && ptsched::takes_lanes(job)) {
                 job.in_order = 1;
                 ptsched::sets_of(c->sched, job, sets, &n_sets);
@@ -290,36 +187,38 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
             if (rc) return rc;
         }
     }
-    const bool overlap = n_batches > 1 && !regen;
-    if (overlap && hand_off)
+    if (sh.overlap && sh.hand_off)
         for (int k = 0; k < 4; ++k)
-            if ((rc = c->cqueue[k].ensure(q_slots_cont))) return rc;
-    if (overlap && hand_off && prm->accel && ((rc = c->caux.ensure(q_slots_cont)) || (rc = c->csray[0].ensure(q_slots_cont)) ||
-                                              (rc = c->csray[1].ensure(q_slots_cont))))
+            if ((rc = c->cqueue[k].ensure(sh.q_slots_cont))) return rc;
+    if (sh.overlap && sh.hand_off && prm->accel && ((rc = c->caux.ensure(sh.q_slots_cont)) || (rc = c->csray[0].ensure(sh.q_slots_cont)) ||
+                                                    (rc = c->csray[1].ensure(sh.q_slots_cont))))
         return rc;
     if (!c->ovf_count.p) {             // [render statistics | launch counters of buffer set 0 | 1 | ...], zero from the start
         if ((rc = c->ovf_count.ensure(kStatsWords + kSets * kCountStride))) return rc;
         // (on the caller's stream and waited for: a plain hipMemset runs on the legacy default stream, which the context's
         // non-blocking streams do not wait for -- the first render's counts raced with it, caught by pt_sync's own sample check)
-        HIP_TRY(hipMemsetAsync(c->ovf_count.p, 0, (kStatsWords + kSets * kCountStride) * sizeof(uint32_t), st));
-        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemsetAsync(c->ovf_count.p, 0, (kStatsWords + kSets * kCountStride) * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         c->sched.stats_clean = 1;
         for (int k = 0; k < kSets; ++k) c->sched.counters_clean[k] = 1;
     }
-    if (hand_off)
-        for (int par = 0; par < (overlap ? 2 : 1); ++par)
+    if (sh.hand_off)
+        for (int par = 0; par < (sh.overlap ? 2 : 1); ++par)
             for (int k = 0; k < 4; ++k)
-                if ((rc = c->ovf[par][k].ensure(ovf_slots))) return rc;
-    if ((n_batches > 1 || fs.load || fs.store) && (rc = c->film.ensure((size_t)np * 3))) return rc;
+                if ((rc = c->ovf[par][k].ensure(sh.ovf_slots))) return rc;
+    if ((sh.n_batches > 1 || fs.load || fs.store) && (rc = c->film.ensure((size_t)sh.np * 3))) return rc;
+    return PT_OK;
+}
 
+// ARGS: the words of BounceArgs that are the same for every launch of the render
+ptk::BounceArgs bounce_args(const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const ListRender* list, uint32_t np) {
     ptk::BounceArgs a{};
-    unsigned long long* const d_stats = reinterpret_cast<unsigned long long*>(c->ovf_count.p);   // hipMalloc alignment: fine for u64
-    a.stats = d_stats;
+    a.stats = reinterpret_cast<unsigned long long*>(c->ovf_count.p);   // hipMalloc alignment: fine for u64
     if (!list) {   // tile row -> image row without a table (ptk::TileMap)
         const uint32_t br = prm->band_rows ? prm->band_rows : cam->height;
         a.tile.band_rows = br;
         a.tile.band_magic = br > 1 ? (uint32_t)(((1ull << 32) + br - 1) / br) : 0u;
-        a.tile.band_stride = br * band_count;
+        a.tile.band_stride = br * (prm->band_count ? prm->band_count : 1);
         a.tile.band_first = prm->band_index * br;
     }
     a.sc = view_for(c, prm->exact_math);
@@ -340,6 +239,188 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
     a.accel = prm->accel;
     a.bvh_refill = c->tuning.bvh_refill ? std::min(64u, c->tuning.bvh_refill) : ptk::kRefillBelow;
     a.bvh_leaf = c->tuning.bvh_leaf ? c->tuning.bvh_leaf : ptk::kLeafBatch;
+    return a;
+}
+
+// EXECUTE: what the operations of one render read, and what its launches leave for the commit
+struct Exec {
+    PtContext* c;
+    const PtCamera* cam;
+    const PtRenderParams* prm;         // accel resolved
+    const FilmState& fs;
+    const ListRender* list;
+    const AdaptivePass* ad;
+    float* d_linear;
+    uint8_t* d_rgba;
+    void* d_packed;
+    const ptshape::Shape& sh;
+    const ptsched::Plan& plan;
+    const ptsched::State& next;        // the state the plan ends in
+    ptk::BounceArgs a;                 // the render's words; a launch fills in its own
+    std::vector<uint32_t> primary_events;
+    uint32_t pool_begin = 0;
+};
+uint32_t* set_counters(const PtContext* c, uint32_t set) { return c->ovf_count.p + kStatsWords + kCountStride * set; }
+
+int exec_launch(Exec& x, const ptsched::Op& o, hipStream_t s) {
+    using namespace ptsched;
+    PtContext* const c = x.c;
+    ptk::BounceArgs& a = x.a;
+    const ptshape::Launch l = ptshape::launch(x.sh, o.batch, o.grid, o.level, o.flags);
+    uint32_t* const d_count = set_counters(c, o.set);   // [0] leftovers handed over, [64 ...] chunk counters of k_paths_regen
+    const bool own = o.own_queue != 0, inject = x.sh.inject, hand_off = x.sh.hand_off;
+    a.s_base = x.prm->spp_offset + l.s0;
+    a.lsamp = c->lsamp[o.set].p;
+    a.n_first = l.n_first;
+    a.n_first_dev = o.level > 0 ? d_count : nullptr;
+    a.seg_cap = l.seg_cap;
+    a.src_mode = l.src_mode;
+    a.export_below = l.export_below;
+    a.aux = own ? c->caux.p : c->bvh_aux.p;
+    a.sray0 = own ? c->csray[0].p : c->bvh_sray[0].p;
+    a.sray1 = own ? c->csray[1].p : c->bvh_sray[1].p;
+    for (int k = 0; k < 4; ++k) {
+        a.q.q[k] = own ? c->cqueue[k].p : c->queue[k].p;
+        a.ovf_out.q[k] = hand_off ? c->ovf[o.ovf_par][k].p : nullptr;
+        a.ovf_in.q[k] = inject ? const_cast<float4*>(x.list->inject[k]) : (hand_off ? c->ovf[o.ovf_par][k].p : nullptr);
+    }
+    a.ovf_out_count = d_count;
+    a.debug_tag = o.set;
+    a.chunk_counter = nullptr;
+    a.xchg = nullptr;
+    a.posted = nullptr; a.seq = 0; a.core_blocks = 0;
+    a.regen_static = l.regen_static;
+    if (o.flags & kLaunchRegen) {
+        a.chunk_counter = d_count + ptk::kRegenCounterStride;
+        if (o.flags & kLaunchSplit) a.xchg = c->xchg.p + o.xchg_off;
+        if (o.core) { a.posted = c->h_posted.dev; a.seq = o.seq; a.core_blocks = o.core; }
+    }
+    const uint32_t inst = x.prm->exact_math ? ptk::launch_path_kernel_exact(a, o.grid, s) : ptk::launch_path_kernel_fast(a, o.grid, s);
+    HIP_TRY(hipGetLastError());
+    if (c->launch_log.size() < kLaunchLogCap) c->launch_log.push_back(inst);
+    if ((o.flags & kLaunchPrimary) && x.plan.profile) x.primary_events.push_back(x.pool_begin / 2u);
+    return PT_OK;
+}
+
+int exec_resolve(Exec& x, const ptsched::Op& o, hipStream_t s) {
+    PtContext* const c = x.c;
+    const uint32_t nb = ptshape::batch_samples(x.sh, o.batch), n_batches = x.sh.n_batches;
+    if (x.ad) {
+        ptk::AdaptiveResolveArgs r{};
+        r.f = x.ad->f;
+        r.lsamp = c->lsamp[o.set].p;
+        r.pixels = x.list ? x.list->d_pixels : nullptr;
+        r.width = x.cam->width; r.n = x.sh.np; r.nb = nb; r.n_total = x.ad->n_total;
+        r.load = o.batch > 0 || x.ad->load;
+        r.finalize = o.batch + 1 == n_batches;
+        if (o.zero_words) { r.zero_words = set_counters(c, o.set); r.n_zero = o.zero_words; }
+        ptk::launch_resolve_adaptive(r, s);
+        HIP_TRY(hipGetLastError());
+        return PT_OK;
+    }
+    ptk::ResolveArgs r{};
+    r.lsamp = c->lsamp[o.set].p;
+    r.film = c->film.p;
+    r.out_linear = x.d_linear;
+    r.out_rgba = x.d_rgba;
+    r.np = x.sh.np; r.nb = nb;
+    r.load_film = o.batch > 0 || x.fs.load;
+    r.store_film = o.batch + 1 < n_batches || x.fs.store;
+    r.finalize = o.batch + 1 == n_batches;
+    r.spp_div = x.fs.div ? x.fs.div : x.sh.spp;
+    r.out_packed = x.d_packed;
+    if (o.zero_words) { r.zero_words = set_counters(c, o.set); r.n_zero = o.zero_words; }
+    ptk::launch_resolve(r, s);
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+int exec_op(Exec& x, const ptsched::Op& o, size_t index) {
+    using namespace ptsched;
+    PtContext* const c = x.c;
+    if (c->debug_fail_at >= 0 && (size_t)c->debug_fail_at == index) {
+        c->debug_fail_at = -1;
+        return fail(PT_ERR_HIP, "injected failure at stream operation %zu of the render (pt_debug_fail_after)", index);
+    }
+    hipStream_t s = sched_stream(c, c->stream, o.stream);
+    switch (o.kind) {
+    case kOpHostSync:
+        for (int k = 0; k < kLanes; ++k) HIP_TRY(hipStreamSynchronize(c->lane_stream[k]));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return c->xchg.ensure((size_t)x.next.xchg_stride * kLanes);
+    case kOpMemsetStats:
+        HIP_TRY(hipMemsetAsync(c->ovf_count.p, 0, kStatsWords * sizeof(uint32_t), s));
+        return PT_OK;
+    case kOpMemsetCounters:
+        HIP_TRY(hipMemsetAsync(set_counters(c, o.set), 0, kCountStride * sizeof(uint32_t), s));
+        return PT_OK;
+    case kOpRecord:
+        if (o.event == kEvPool && !(o.pool & 1u)) x.pool_begin = o.pool;
+        HIP_TRY(hipEventRecord(sched_event(c, o), s));
+        return PT_OK;
+    case kOpWait:
+        HIP_TRY(hipStreamWaitEvent(s, sched_event(c, o), 0));
+        return PT_OK;
+    case kOpPost:
+        __atomic_store_n(c->h_posted.p, o.seq, __ATOMIC_RELEASE);      // before the launch is handed to the device
+        return PT_OK;
+    case kOpLaunch: return exec_launch(x, o, s);
+    case kOpResolve: return exec_resolve(x, o, s);
+    default:
+        return fail(PT_ERR_HIP, "internal: unknown stream operation %u", o.kind);
+    }
+}
+
+// COMMIT: the planned state becomes the context's; the host's share of the statistics
+void commit(PtContext* c, const Exec& x, const ptsched::Job& job) {
+    if (!x.plan.accumulate) begin_period(c);
+    c->sched = x.next;
+    // (the device-side statistics are read when they are collected -- pt_sync --, not copied back per render)
+    const uint64_t n = (uint64_t)x.sh.np * x.sh.spp;
+    if (job.capturing) {
+        // nothing ran, and the graph may be replayed any number of times: the device will have counted a multiple of these
+        uint64_t a = c->capture_gcd, b = n;
+        while (b) { const uint64_t t = a % b; a = b; b = t; }
+        c->capture_gcd = a;
+    } else {
+        c->expected_samples += n;
+    }
+    c->stats.bounce_launches += x.plan.launches;
+    c->stats.batches += x.sh.n_batches;
+    c->stats.primary_launches += x.plan.primary_launches;
+    c->primary_events.insert(c->primary_events.end(), x.primary_events.begin(), x.primary_events.end());
+}
+
+}  // namespace
+
+// The render driver behind every rendering entry: everything src/main.rs:43-60 does for the tile (or, with `list`,
+// for a pixel list / a set of given rays).  Enqueues on the context's streams and returns; no host synchronisation.
+// Its stages are the functions above: CHECK the arguments, resolve ACCEL, SIZE the render (pt_shape.h: pure), PREPARE every
+// buffer it will touch -- nothing is enqueued before PREPARE has succeeded, so an error up to there leaves the context as it
+// was --, PLAN (ptsched::plan on a copy of the scheduling state: pure), fill the ARGS, EXECUTE the plan's stream operations in
+// order and COMMIT the copy.  A failure during EXECUTE: sched_recover.
+int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
+                float* d_linear, uint8_t* d_rgba, void* d_packed, const AdaptivePass* ad) {
+    int rc;
+    if ((rc = check_render(c, cam, prm, list, d_linear, d_rgba))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    PtRenderParams resolved = *prm;
+    resolved.accel = resolve_accel(c, prm->accel);
+    prm = &resolved;
+
+    const uint64_t np64 = list ? list->n : (uint64_t)pt_tile_rows(cam->height, prm->band_rows, prm->band_index, prm->band_count ? prm->band_count : 1) * cam->width;
+    const uint64_t tile_rows = list ? ((np64 + 65535u) >> 16) : np64 / cam->width;
+    if (np64 == 0) {                   // empty tile: nothing to render
+        if (!c->sched.stats_pending) begin_period(c);
+        return PT_OK;
+    }
+    if (!d_linear && !d_packed) return fail(PT_ERR_INVALID_ARG, "render: the linear output buffer is null");
+    if (!list && (cam->width > 65535u || tile_rows > 65535u))   // (tile row, x) share one word of the path state
+        return fail(PT_ERR_UNSUPPORTED, "tile %ux%llu: width and tile rows must be < 65536", cam->width, (unsigned long long)tile_rows);
+    ptshape::Shape sh;
+    if ((rc = size_render(c, prm, list, np64, &sh))) return rc;
+    ptsched::Job job = sh.job;         // (PREPARE may fall back to its in-order form)
+    if ((rc = prepare(c, prm, fs, sh, job))) return rc;
 
     // ---- PLAN (pure; on a copy of the state)
     ptsched::State next = c->sched;
@@ -353,150 +434,16 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
         if ((rc = ensure_events(c, top))) return rc;
     }
 
-    // ---- EXECUTE
-    std::vector<uint32_t> primary_events;
-    uint32_t pool_begin = 0;
-    auto exec = [&](const ptsched::Op& o, size_t index) -> int {
-        using namespace ptsched;
-        if (c->debug_fail_at >= 0 && (size_t)c->debug_fail_at == index) {
-            c->debug_fail_at = -1;
-            return fail(PT_ERR_HIP, "injected failure at stream operation %zu of the render (pt_debug_fail_after)", index);
-        }
-        hipStream_t s = sched_stream(c, st, o.stream);
-        switch (o.kind) {
-        case kOpHostSync:
-            for (int k = 0; k < kLanes; ++k) HIP_TRY(hipStreamSynchronize(c->lane_stream[k]));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (int r2 = c->xchg.ensure((size_t)next.xchg_stride * kLanes)) return r2;
-            return PT_OK;
-        case kOpMemsetStats:
-            HIP_TRY(hipMemsetAsync(c->ovf_count.p, 0, kStatsWords * sizeof(uint32_t), s));
-            return PT_OK;
-        case kOpMemsetCounters:
-            HIP_TRY(hipMemsetAsync(c->ovf_count.p + kStatsWords + kCountStride * o.set, 0, kCountStride * sizeof(uint32_t), s));
-            return PT_OK;
-        case kOpRecord:
-            if (o.event == kEvPool && !(o.pool & 1u)) pool_begin = o.pool;
-            HIP_TRY(hipEventRecord(sched_event(c, o), s));
-            return PT_OK;
-        case kOpWait:
-            HIP_TRY(hipStreamWaitEvent(s, sched_event(c, o), 0));
-            return PT_OK;
-        case kOpPost:
-            __atomic_store_n(c->h_posted.p, o.seq, __ATOMIC_RELEASE);      // before the launch is handed to the device
-            return PT_OK;
-        case kOpLaunch: {
-            const uint32_t s0 = o.batch * nb_max, nb = std::min(nb_max, spp - s0);
-            uint32_t* const d_count = c->ovf_count.p + kStatsWords + kCountStride * o.set;   // [0] leftovers handed over, [64 ...] chunk counters of k_paths_regen
-            const bool own = o.own_queue != 0;
-            a.s_base = prm->spp_offset + s0;
-            a.lsamp = c->lsamp[o.set].p;
-            // Level 0 traces the batch's paths (every bounce, see k_paths); in a large batch its waves hand their sparse
-            // tails to the overflow queue, which level 1 -- same kernel, fixed grid, count read on the device -- finishes.
-            // (a regenerating launch whose waves run dry themselves leaves nothing for a continuation launch)
-            a.n_first = np * nb;
-            a.n_first_dev = nullptr;
-            a.seg_cap = ((((a.n_first + 63u) / 64u) + nw - 1) / nw) * 64u;
-            a.src_mode = inject ? 1u : 0u;
-            a.export_below = hand_off ? (small_scene ? export_small : ptk::kBlock) : 1u;
-            if (o.level > 0) {
-                a.n_first = 0; a.n_first_dev = d_count;
-                a.seg_cap = seg_cap_cont;
-                a.src_mode = 1u;
-                a.export_below = 1u;
-            }
-            a.aux = own ? c->caux.p : c->bvh_aux.p;
-            a.sray0 = own ? c->csray[0].p : c->bvh_sray[0].p;
-            a.sray1 = own ? c->csray[1].p : c->bvh_sray[1].p;
-            for (int k = 0; k < 4; ++k) {
-                a.q.q[k] = own ? c->cqueue[k].p : c->queue[k].p;
-                a.ovf_out.q[k] = hand_off ? c->ovf[o.ovf_par][k].p : nullptr;
-                a.ovf_in.q[k] = inject ? const_cast<float4*>(list->inject[k]) : (hand_off ? c->ovf[o.ovf_par][k].p : nullptr);
-            }
-            a.ovf_out_count = d_count;
-            a.debug_tag = o.set;
-            a.chunk_counter = nullptr;
-            a.xchg = nullptr;
-            a.posted = nullptr; a.seq = 0; a.core_blocks = 0;
-            a.regen_static = 0;
-            if (o.flags & kLaunchRegen) {
-                a.chunk_counter = d_count + ptk::kRegenCounterStride;
-                if (o.flags & kLaunchSplit) a.xchg = c->xchg.p + o.xchg_off;
-                a.export_below = regen_export;
-                // the first kRegenStatic16 / 16 of the chunks are dealt statically (none with lanes: a workgroup of this launch that
-                // only finds room when the previous launch's last waves end would carry its dealt share as a serial tail)
-                const uint32_t nwr = o.grid * kWavesPerBlock, nch = (a.n_first + 63u) / 64u;
-                if (o.flags & kLaunchStaticDeal) a.regen_static = (uint32_t)(((uint64_t)nch * kRegenStatic16 / 16) / nwr) * nwr;
-                if (o.core) { a.posted = c->h_posted.dev; a.seq = o.seq; a.core_blocks = o.core; }
-            }
-            const uint32_t inst = prm->exact_math ? ptk::launch_path_kernel_exact(a, o.grid, s) : ptk::launch_path_kernel_fast(a, o.grid, s);
-            HIP_TRY(hipGetLastError());
-            if (c->launch_log.size() < kLaunchLogCap) c->launch_log.push_back(inst);
-            if ((o.flags & kLaunchPrimary) && plan.profile) primary_events.push_back(pool_begin / 2u);
-            return PT_OK;
-        }
-        case kOpResolve: {
-            const uint32_t s0 = o.batch * nb_max, nb = std::min(nb_max, spp - s0);
-            if (ad) {
-                ptk::AdaptiveResolveArgs r{};
-                r.f = ad->f;
-                r.lsamp = c->lsamp[o.set].p;
-                r.pixels = list ? list->d_pixels : nullptr;
-                r.width = cam->width; r.n = np; r.nb = nb; r.n_total = ad->n_total;
-                r.load = o.batch > 0 || ad->load;
-                r.finalize = o.batch + 1 == n_batches;
-                if (o.zero_words) { r.zero_words = c->ovf_count.p + kStatsWords + kCountStride * o.set; r.n_zero = o.zero_words; }
-                ptk::launch_resolve_adaptive(r, s);
-                HIP_TRY(hipGetLastError());
-                return PT_OK;
-            }
-            ptk::ResolveArgs r{};
-            r.lsamp = c->lsamp[o.set].p;
-            r.film = c->film.p;
-            r.out_linear = d_linear;
-            r.out_rgba = d_rgba;
-            r.np = np; r.nb = nb;
-            r.load_film = o.batch > 0 || fs.load;
-            r.store_film = o.batch + 1 < n_batches || fs.store;
-            r.finalize = o.batch + 1 == n_batches;
-            r.spp_div = fs.div ? fs.div : spp;
-            r.out_packed = d_packed;
-            if (o.zero_words) { r.zero_words = c->ovf_count.p + kStatsWords + kCountStride * o.set; r.n_zero = o.zero_words; }
-            ptk::launch_resolve(r, s);
-            HIP_TRY(hipGetLastError());
-            return PT_OK;
-        }
-        default:
-            return fail(PT_ERR_HIP, "internal: unknown stream operation %u", o.kind);
-        }
-    };
+    Exec x{c, cam, prm, fs, list, ad, d_linear, d_rgba, d_packed, sh, plan, next, bounce_args(c, cam, prm, list, sh.np), {}, 0};
     for (size_t i = 0; i < plan.ops.size(); ++i)
-        if ((rc = exec(plan.ops[i], i))) {
+        if ((rc = exec_op(x, plan.ops[i], i))) {
             const std::string keep = g_err;
-            sched_recover(c, st, next);
+            sched_recover(c, c->stream, next);
             g_err = keep;
             return rc;
         }
-
     c->debug_fail_at = -1;              // (the hook is for ONE render)
-
-    // ---- COMMIT
-    if (!plan.accumulate) begin_period();
-    c->sched = next;
-    // (the device-side statistics are read when they are collected -- pt_sync --, not copied back per render)
-    if (job.capturing) {
-        // nothing ran, and the graph may be replayed any number of times: the device will have counted a multiple of these
-        const uint64_t n = (uint64_t)np * spp;
-        uint64_t x = c->capture_gcd, y = n;
-        while (y) { const uint64_t t = x % y; x = y; y = t; }
-        c->capture_gcd = x;
-    } else {
-        c->expected_samples += (uint64_t)np * spp;
-    }
-    c->stats.bounce_launches += plan.launches;
-    c->stats.batches += n_batches;
-    c->stats.primary_launches += plan.primary_launches;
-    c->primary_events.insert(c->primary_events.end(), primary_events.begin(), primary_events.end());
+    commit(c, x, job);
     return PT_OK;
 }
 
@@ -600,8 +547,7 @@ int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams
     if (!(ad->abs_floor > 0.0)) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: abs_floor must be > 0");
     if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
         return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: renders the whole image (band_count = 1)");
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    if (int rc = check_scene_and_camera(c, cam)) return rc;
     const uint64_t np64 = (uint64_t)cam->width * cam->height;
     if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_render_adaptive: %llu pixels", (unsigned long long)np64);
     const uint32_t np = (uint32_t)np64, spp_max = prm->spp, W = cam->width;

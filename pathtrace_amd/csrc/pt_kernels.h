@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pt_kernel_consts.h"   // kBlock, kSmallObjs, kRegenWaves*, kRegenSplitF4PerWave, kRegenCounters, kRegenCounterStride
+
 namespace ptk {
 
 // One contiguous run of same-shape objects of World.objects, in object order
@@ -131,7 +133,6 @@ struct BounceArgs {
     uint32_t debug_tag;       // measurement builds (PT_DRAIN_TIMING): plane of ovf_out that receives the per-wave stamps
 };
 
-constexpr uint32_t kBlock = 256;
 // How a linear-scan kernel finds the closest hit (pt_kernels_main.hip: scene_mode), and the material sets kernels are compiled for
 // (pt_kernels_vertex.h: assume_mats).
 constexpr int kModeLds = 0, kModeTiled = 1, kModeBvh = 2;
@@ -145,10 +146,6 @@ constexpr uint32_t instance_code(uint32_t family, int mode, bool mis, bool ovf, 
     return family | (uint32_t)mode << 2 | (uint32_t)mis << 3 | (uint32_t)ovf << 4 | (uint32_t)mats << 5 | (uint32_t)list << 7 |
            (uint32_t)exact << 8;
 }
-// Scenes of at most kSmallObjs objects stay whole in LDS (scan + shape + material + run
-// records: at most 9 float4 per object = 18 KiB); larger scenes stream their scan array
-// through one LDS tile and gather shape/material records from global memory.
-constexpr uint32_t kSmallObjs = 128;
 constexpr uint32_t kTileF4 = 1920;         // 30 KiB LDS tile (divisible by 3: whole triangles); 5 workgroups per CU (measured: 2550 / 4 -> 1214 ms, 1920 / 5 -> 1106 ms on C4)
 constexpr uint32_t kRefillBelow = 44;      // BVH traversal: hand out new rays when fewer lanes than this are tracing
 constexpr uint32_t kLeafBatch = 20;        // BVH traversal: test leaf primitives when at least this many lanes wait at a leaf
@@ -161,18 +158,6 @@ constexpr uint32_t kBvhStack = PT_BVH_STACK;         // traversal stack entries 
 // One launch traces every path of a batch to its end.  grid = number of 256-thread workgroups
 // (4 queue segments each).  _exact / _fast: the two arithmetic modes of pt_device.h
 // (PtRenderParams.exact_math).
-// occupancy k_paths_regen is compiled for (waves per SIMD = workgroups per CU): the host launches exactly that many
-#ifndef PT_REGEN_WAVES_DIFFUSE
-#define PT_REGEN_WAVES_DIFFUSE 6
-#endif
-#ifndef PT_REGEN_WAVES_SPLIT
-#define PT_REGEN_WAVES_SPLIT 5
-#endif
-constexpr uint32_t kRegenWavesDiffuse = PT_REGEN_WAVES_DIFFUSE, kRegenWavesGeneric = 5, kRegenWavesSplit = PT_REGEN_WAVES_SPLIT;
-// k_paths_regen_split: float4 of exchange memory per wave of the launch: 128 stack entries of 5 float4
-constexpr uint32_t kRegenSplitF4PerWave = 128u * 5u;
-// chunk counters of k_paths_regen: chunk_counter[c * kRegenCounterStride], c < kRegenCounters (256 bytes apart)
-constexpr uint32_t kRegenCounters = 8, kRegenCounterStride = 64;
 // pt_scene_upload: per-object constants written into the shape / material records (k_scene_setup), one call per arithmetic
 // mode on that mode's copy of the records
 void launch_scene_setup_exact(float4* shape, float4* mat, uint32_t n_objs, hipStream_t st);

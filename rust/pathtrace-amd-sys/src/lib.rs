@@ -231,6 +231,81 @@ pub struct PtSchedOp {
     pub xchg_off: u64,
     pub xchg_len: u64,
 }
+/// What the launch sizing reads (`csrc/pt_shape.h`: `In`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtShapeIn {
+    pub np: u64,
+    pub max_paths_in_flight: u64,
+    pub spp: u32,
+    pub workgroups: u32,
+    pub accel: u32,
+    pub profile: u32,
+    pub list: u32,
+    pub list_regen: u32,
+    pub inject: u32,
+    pub n_objs: u32,
+    pub blob_f4: u32,
+    pub diffuse_only: u32,
+    pub split_ok: u32,
+    pub n_cus: u32,
+    pub export_below: u32,
+    pub cont_workgroups: u32,
+    pub level0_form: u32,
+    pub regen_workgroups: u32,
+    pub in_order: u32,
+    pub capturing: u32,
+}
+/// The sizing of a render (`csrc/pt_shape.h`: `Form`, `Shape`); `job` goes to `pt_debug_sched_render` as it is.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtShapeOut {
+    pub lds_job: u32,
+    pub split: u32,
+    pub regen_scene: u32,
+    pub over_cap: u32,
+    pub cap: u64,
+    pub n_paths_max: u64,
+    pub ovf_slots: u64,
+    pub q_slots_cont: u64,
+    pub q_slots: u64,
+    pub np: u32,
+    pub spp: u32,
+    pub nb_max: u32,
+    pub n_batches: u32,
+    pub export_small: u32,
+    pub paths_per_wave: u32,
+    pub small_scene: u32,
+    pub hand_off: u32,
+    pub regen: u32,
+    pub overlap: u32,
+    pub grid: u32,
+    pub nw: u32,
+    pub seg_cap: u32,
+    pub regen_per_cu: u32,
+    pub regen_capacity: u32,
+    pub regen_grid: u32,
+    pub regen_launch_grid: u32,
+    pub cont_grid: u32,
+    pub nw_cont: u32,
+    pub seg_cap_cont: u32,
+    pub regen_export: u32,
+    pub reserved: u32,
+    pub job: PtSchedJob,
+}
+/// The per-launch words of a planned launch (`csrc/pt_shape.h`: `Launch`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtShapeLaunch {
+    pub s0: u32,
+    pub nb: u32,
+    pub n_first: u32,
+    pub seg_cap: u32,
+    pub src_mode: u32,
+    pub export_below: u32,
+    pub regen_static: u32,
+    pub reserved: u32,
+}
 
 /// `pt_context_set_stream`: HIP's legacy default stream (its handle, 0, means "the context's own stream").
 pub const PT_STREAM_LEGACY_DEFAULT: usize = 1;
@@ -272,6 +347,7 @@ extern "C" {
     pub fn pt_debug_sched_destroy(s: *mut PtSched);
     pub fn pt_debug_sched_render(s: *mut PtSched, job: *const PtSchedJob, faults: u32, fail_after: u32, ops: *mut PtSchedOp, cap: u32, n_ops: *mut u32, lanes: *mut u32) -> c_int;
     pub fn pt_debug_sched_sync(s: *mut PtSched, collect: u32) -> c_int;
+    pub fn pt_debug_render_shape(input: *const PtShapeIn, occupancy: u32, out: *mut PtShapeOut, ops: *const PtSchedOp, n_ops: u32, launches: *mut PtShapeLaunch) -> c_int;
     pub fn pt_debug_fail_after(ctx: *mut PtContext, n: i64) -> c_int;
     pub fn pt_debug_launch_log(ctx: *mut PtContext, out: *mut u32, cap: u32, n: *mut u32) -> c_int;
     pub fn pt_debug_path_instances(out: *mut u32, cap: u32, n: *mut u32) -> c_int;
