@@ -1,4 +1,4 @@
-// pt_adaptive.h -- the stopping rule of pt_render_adaptive, written once for the kernels (pt_kernels_film.hip) and the host
+// pt_adaptive.h -- the stopping rule of pt_render_adaptive, written once for the kernels (pt_film_adaptive.h) and the host
 // compilers of the CPU tests (tests/test_adaptive_rule_cpu.py).  Plain f64 arithmetic; build with -ffp-contract=off so
 // that no compiler fuses a multiply into an add the rule does not write as one.
 //

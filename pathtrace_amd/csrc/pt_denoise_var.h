@@ -1,5 +1,5 @@
 // pt_denoise_var.h -- the variance pt_adaptive_variance_device hands to pt_denoise_var_device, written once for the kernel
-// (k_adaptive_variance in pt_kernels_film.hip) and the host compilers of the CPU tests (tests/test_denoise_var_cpu.py).
+// (k_adaptive_variance in pt_film_adaptive.h) and the host compilers of the CPU tests (tests/test_denoise_var_cpu.py).
 // Plain f64 arithmetic, like pt_adaptive.h; build with -ffp-contract=off.
 //
 // Per pixel: the adaptive pass's f64 sums (sum R, sum G, sum B, S1 = sum L, S2 = sum L^2), its sample count n >= 2 and the

@@ -1,5 +1,5 @@
 // pt_gradient.h -- the temporal gradient of pt_temporal_gradient_device, written once for the kernels
-// (k_gradient_list, k_gradient_strata, k_gradient_alpha, k_gradient_alpha_camera in pt_kernels_film.hip), the host and the host compilers of the CPU
+// (k_gradient_list, k_gradient_strata, k_gradient_alpha, k_gradient_alpha_camera in pt_film_temporal.h), the host and the host compilers of the CPU
 // tests (tests/test_gradient_cpu.py).  Plain f64 arithmetic, like pt_adaptive.h; build with -ffp-contract=off.
 //
 // Strata: the image W x H is cut into 3 x 3 blocks, SW = ceil(W / 3) by SH = ceil(H / 3) of them, clipped at the right and

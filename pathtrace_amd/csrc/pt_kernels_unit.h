@@ -6,7 +6,9 @@
 //   pt_kernels_main.hip   k_paths, k_paths_regen, the debug / setup / feature kernels     -fno-slp-vectorize (C2 launch -2.6 %)
 //   pt_kernels_split.hip  k_paths_regen_split                                             -fno-slp-vectorize, scheduling strategy max-ilp (C1 -1.2 %; C2 would pay 1.6 %)
 //   pt_kernels_bvh.hip    the BVH form (k_paths_bvh, k_debug_hit_bvh)                     with the SLP vectoriser (its 4-wide box tests pack well: +2 % without)
-//   pt_kernels_film.hip   film exchange, adaptive sampling, denoiser (fast mode only)     the main unit's options
+//   pt_kernels_film.hip   the kernels on the film and the device-side BVH refit / builds  the main unit's options
+//                         (fast mode only), one header per concern: pt_film_exchange.h, _adaptive.h, _denoise.h, _temporal.h
+//                         (accumulation and gradients), _bvh.h, _tonemap.h
 // Shared device code: pt_kernels_scan.h (primitive tests, scene staging, scans), pt_kernels_vertex.h (one path vertex).
 // Kernel templates are instantiated where their launcher is; the launchers that cross units are declared in pt_kernels.h.
 #pragma once

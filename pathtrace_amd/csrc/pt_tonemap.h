@@ -1,5 +1,5 @@
 // pt_tonemap.h -- the display transform of pt_tonemap_device, written once for the kernels (k_film_histogram,
-// k_exposure_meter, k_tonemap in pt_kernels_film.hip), the host (pt_tonemap.cpp) and the host compilers of the CPU tests
+// k_exposure_meter, k_tonemap in pt_film_tonemap.h), the host (pt_tonemap.cpp) and the host compilers of the CPU tests
 // (tests/test_tonemap_cpu.py).  Build with -ffp-contract=off, like pt_adaptive.h: no compiler fuses what the rule writes apart.
 //
 // Image W x H, c the linear film (3 floats per pixel).
