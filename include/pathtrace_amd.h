@@ -829,6 +829,52 @@ uint32_t pt_debug_tonemap_bin(float L);
 double pt_debug_tonemap_meter(const uint32_t* hist258, const PtTonemap* tm, int fresh, double log2E_prev);
 int pt_debug_tonemap_pixel(const PtTonemap* tm, float E, const float* rgb, float* out_y, uint8_t* out_rgba8);
 
+/* Feature-guided upsampling (additive to ABI 6): paths traced on a w x h grid and first-hit features at the full
+ * W x H reconstruct a full-size film -- joint bilateral upsampling in the denoiser's demodulated space.  The low camera is
+ * the full camera with width / height replaced (the cached frustum fields of PtCamera do not depend on the pixel count).
+ * The rule (pathtrace_amd/csrc/pt_upsample.h), for the full-size pixel p = (x, y) with record {albedo A, emitter, normal n,
+ * depth d}; c, f the low film and its records, film row y top-down:
+ *   position    f64, multiply then divide: X = ((x + 0.5)(w - 1)) / (W - 1) - 0.5,  Y = h - 0.5 - ((H - 1 - y + 0.5)(h - 1)) /
+ *               (H - 1); X0 = floor(X), fx = X - X0, likewise Y0, fy.  w = W, h = H: X = x, Y = y exactly.
+ *   taps        the low pixels (Y0, X0), (Y0, X0 + 1), (Y0 + 1, X0), (Y0 + 1, X0 + 1) in this order; bilinear weights b_q formed
+ *               in f64, rounded to f32; a tap outside the low image or with b_q = 0 is skipped
+ *   class       miss (depth = 0), else emitter (emitter > 0), else surface.  A tap of another class than p's: w_q = 0.  Same
+ *               class: miss, emitter w_q = b_q; surface w_q = b_q max(0, n . n_q)^sigma_n exp(-|d - d_q| / (sigma_d r max(d, 1e-3)
+ *               + 1e-10)), r = max((W - 1) / (w - 1), (H - 1) / (h - 1)) in f32, w_q = 0 when n . n_q is <= 0 or NaN
+ *   anchor      a = the tap with the largest b_q among the taps of p's class, without one among all taps not skipped; ties
+ *               go to the first in the order above
+ *   value       u_q = c_q / max(albedo_q, 1e-3) per channel (f32), u = u_a + sum w_q (u_q - u_a) / (sum w_q + 1e-6) (these sums in
+ *               f64, u rounded to f32): no threshold, continuous in the weights, the anchor when nothing agrees with p;
+ *               c' = u max(A, 1e-3) (f32); the RGBA8 plane is c' through the sqrt / clamp / `as u8` steps of every render
+ * With w = W, h = H and the same records on both sides the output is pt_denoise_device's with iterations = 0, bit for bit.
+ * pt_default_upsample: the denoiser's sigma_n 128 and sigma_d 0.025.                                                       */
+typedef struct {
+    float sigma_n;           /* exponent of the normal weight; finite, >= 0                          */
+    float sigma_d;           /* depth tolerance per low pixel, relative to the depth; finite, >= 0   */
+} PtUpsample;
+void pt_default_upsample(PtUpsample* out);
+/* d_lo_linear (lo_width*lo_height*3 floats), d_lo_features (lo_width*lo_height*8 floats, 16-byte aligned) and d_features
+ * (width*height*8 floats, 16-byte aligned) -> d_out_linear (width*height*3 floats) and, when not NULL, d_out_rgba8
+ * (width*height*4 bytes); all on the device.  Asynchronous on the context's stream (the caller's after
+ * pt_context_set_stream); needs no scene, allocates nothing and touches no context state: the temporal history, the exposure
+ * and the adaptive sums stay as they are.  PT_ERR_INVALID_ARG, before the context is looked at, for a null pointer
+ * (d_out_rgba8 excepted), a misaligned plane (16 bytes for the records, 4 for the rest), a dimension below 2, a low size above
+ * the full size, an output that is one of the inputs, a sigma that is negative or not finite.                              */
+int pt_upsample_device(PtContext* ctx, uint32_t lo_width, uint32_t lo_height, const float* d_lo_linear, const float* d_lo_features,
+                       uint32_t width, uint32_t height, const float* d_features, const PtUpsample* up, float* d_out_linear,
+                       uint8_t* d_out_rgba8);
+/* The same planes in HOST memory, the same checks: the rule header run on the CPU.  Needs no device and no context. */
+int pt_upsample_host(uint32_t lo_width, uint32_t lo_height, const float* lo_linear, const float* lo_features, uint32_t width,
+                     uint32_t height, const float* features, const PtUpsample* up, float* out_linear, uint8_t* out_rgba8);
+/* One frame (host buffers, blocking, the whole image): the render of params through the low camera, the low features,
+ * pt_denoise_device on the low film, the full-size features, pt_upsample_device -- bit-identical to these five entries called
+ * in this order.  Both feature passes take min(feature_samples, params->spp) samples from params->spp_offset.  out_linear_rgb
+ * and out_rgba8 are the full-size film (width*height of cam); out_lo_linear the denoised low film (lo_width*lo_height*3
+ * floats), out_features the full-size records; every output but out_linear_rgb may be NULL.                              */
+int pt_render_denoised_upsampled(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t lo_width,
+                                 uint32_t lo_height, uint32_t feature_samples, const PtDenoise* dn, const PtUpsample* up,
+                                 float* out_linear_rgb, uint8_t* out_rgba8, float* out_lo_linear, float* out_features);
+
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on
  * entry like Ray::new (camera.rs:10-16); xy = n * (x, y) = the RNG key of each ray's stream, and the

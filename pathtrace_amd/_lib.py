@@ -132,6 +132,13 @@ class PtTonemap(C.Structure):
     ]
 
 
+class PtUpsample(C.Structure):
+    _fields_ = [
+        ("sigma_n", C.c_float),
+        ("sigma_d", C.c_float),
+    ]
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -287,6 +294,13 @@ SYMBOLS = {
     "pt_debug_tonemap_bin": (C.c_uint32, [C.c_float]),
     "pt_debug_tonemap_meter": (C.c_double, [_P(C.c_uint32), _P(PtTonemap), C.c_int, C.c_double]),
     "pt_debug_tonemap_pixel": (C.c_int, [_P(PtTonemap), C.c_float, _P(C.c_float), _P(C.c_float), _P(C.c_uint8)]),
+    "pt_default_upsample": (None, [_P(PtUpsample)]),
+    "pt_upsample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                     _P(PtUpsample), C.c_void_p, C.c_void_p]),
+    "pt_upsample_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _P(PtUpsample),
+                                   C.c_void_p, C.c_void_p]),
+    "pt_render_denoised_upsampled": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, C.c_uint32, C.c_uint32, _P(PtDenoise),
+                                               _P(PtUpsample), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

@@ -71,6 +71,41 @@ def default_gradient(**over):
     return g
 
 
+def default_upsample(**over):
+    """pt_default_upsample with keyword overrides (None keeps the default)."""
+    u = _lib.PtUpsample()
+    lib().pt_default_upsample(C.byref(u))
+    for k, v in over.items():
+        if v is not None:
+            setattr(u, k, v)
+    return u
+
+
+def upsample_host(lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
+    """pt_upsample_host: the upsampling rule on the CPU (no device, no context), on a low film (f32[h,w,3]), its features
+    (f32[h,w,8]) and the full-size features (f32[H,W,8]).  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
+    up = default_upsample(sigma_n=sigma_n, sigma_d=sigma_d)
+    h, w = np.shape(lo_linear)[:2]
+    H, W = np.shape(features)[:2]
+    lo_lin, lo_feat, feat = _aligned(lo_linear, (h, w, 3)), _aligned(lo_features, (h, w, 8)), _aligned(features, (H, W, 8))
+    out, rgba = np.empty((H, W, 3), dtype=np.float32), np.empty((H, W, 4), dtype=np.uint8)
+    check(lib().pt_upsample_host(w, h, lo_lin.ctypes.data_as(C.c_void_p), lo_feat.ctypes.data_as(C.c_void_p), W, H,
+                                 feat.ctypes.data_as(C.c_void_p), C.byref(up), out.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p)))
+    return out, rgba
+
+
+def _aligned(a, shape):
+    """a as a contiguous f32 array of this shape whose data is 16-byte aligned (numpy's own allocations are; a view may not be)"""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    assert a.shape == shape, (a.shape, shape)
+    if a.ctypes.data % 16:
+        buf = np.empty(a.size + 4, dtype=np.float32)
+        off = (-buf.ctypes.data % 16) // 4
+        buf[off:off + a.size] = a.ravel()
+        a = buf[off:off + a.size].reshape(shape)
+    return a
+
+
 MODES = {"auto": _lib.PT_EXPOSURE_AUTO, "manual": _lib.PT_EXPOSURE_MANUAL}
 CURVES = {"clamp": _lib.PT_CURVE_CLAMP, "reinhard": _lib.PT_CURVE_REINHARD, "aces": _lib.PT_CURVE_ACES}
 TRANSFERS = {"sqrt": _lib.PT_TRANSFER_SQRT, "srgb": _lib.PT_TRANSFER_SRGB}
@@ -448,6 +483,32 @@ class _ContextFunctions:
         planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32))
         check(lib().pt_render_denoised(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), *ptrs))
         return planes
+
+    def upsample(self, lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
+        """pt_upsample_device on a low film (f32[h,w,3]), its features (f32[h,w,8]) and the full-size features (f32[H,W,8]);
+        unset parameters take pt_default_upsample.  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
+        up = default_upsample(sigma_n=sigma_n, sigma_d=sigma_d)
+        h, w = np.shape(lo_linear)[:2]
+        H, W = np.shape(features)[:2]
+        d_lo, d_lo_feat = self._upload(lo_linear, np.float32, (h, w, 3)), self._upload(lo_features, np.float32, (h, w, 8))
+        d_feat = self._upload(features, np.float32, (H, W, 8))
+        out, rgba = self._film_pair(H, W)
+        self._on_stream(lib().pt_upsample_device, w, h, d_lo, d_lo_feat, W, H, d_feat, C.byref(up), out, rgba)
+        return out.cpu().numpy(), rgba.cpu().numpy()
+
+    def render_denoised_upsampled(self, cam, params, lo_size, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
+                                  up_sigma_n=None, up_sigma_d=None):
+        """pt_render_denoised_upsampled (host buffers, blocking): params rendered at lo_size = (lo_width, lo_height), denoised
+        there (iterations, sigma_*: pt_default_denoise) and upsampled to cam's size under cam's features (up_sigma_*:
+        pt_default_upsample).  -> (linear f32[H,W,3], rgba u8[H,W,4], denoised low linear f32[h,w,3], features f32[H,W,8])"""
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        up = default_upsample(sigma_n=up_sigma_n, sigma_d=up_sigma_d)
+        w, h = lo_size
+        (lin, rgba, feat), ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (8, np.float32))
+        lo = np.empty((h, w, 3), dtype=np.float32)
+        check(lib().pt_render_denoised_upsampled(self._h, C.byref(cam), C.byref(params), w, h, feature_samples, C.byref(dn), C.byref(up),
+                                                 ptrs[0], ptrs[1], lo.ctypes.data_as(C.c_void_p), ptrs[2]))
+        return lin, rgba, lo, feat
 
     def denoise_var(self, linear, features, var, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
         """pt_denoise_var_device: denoise() with a variance plane (f32[H,W], in units of the demodulated luminance squared); an

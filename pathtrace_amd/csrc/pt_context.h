@@ -210,6 +210,8 @@ struct PtContext {
     DevBuf<float> dn_lin;
     DevBuf<float> dn_var;                     // pt_render_adaptive_denoised: device staging of the variance plane
     DevBuf<int32_t> dn_ids;                   // pt_render_denoised_motion: device staging of the ids
+    DevBuf<float4> up_feat;                   // pt_render_denoised_upsampled: device staging of the full-size features and film
+    DevBuf<float> up_lin;
     // pt_denoise_temporal_device: two history buffers of 3 float4 per pixel (ptk::TemporalArgs), tm_hist[tm_cur] holds the
     // last frame's when tm_valid; the camera and size of that frame
     DevBuf<float4> tm_hist[2];
@@ -269,6 +271,8 @@ struct AdaptivePass {
 int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
                 float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr);   // pt_api.cpp
 int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad);   // pt_api.cpp
+int denoised_frame_device(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
+                          const PtDenoise* dn, PtRenderParams* p);   // pt_denoise.cpp
 ptk::SceneView view_for(const PtContext* c, uint32_t exact_math);   // pt_scene.cpp
 int ensure_bvh(PtContext* c);                                       // pt_scene.cpp
 hipStream_t pt_internal_stream(PtContext* c);                       // pt_context.cpp

@@ -407,6 +407,21 @@ int render_gradient_impl(const char* who, Strata form, PtContext* c, const PtCam
 
 }  // namespace
 
+// For pt_render_denoised_upsampled (pt_upsample.cpp): what pt_render_denoised does on the device for cam -- its checks in the
+// name who, the frame front, the filter from host_lin into dn_lin under the features in dn_feat -- without the wait and the
+// copies.  *p: the parameters of the whole image, for the passes the caller adds.
+int denoised_frame_device(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
+                          const PtDenoise* dn, PtRenderParams* p) {
+    if (!c || !cam || !prm || !dn) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc;
+    if ((rc = check_whole_image(who, "renders", prm))) return rc;
+    if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
+    if ((rc = check_denoise(who, dn)) || (rc = check_target(who, c, cam))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = frame_front(History::none, c, cam, prm, feature_samples, (size_t)cam->width * cam->height, p))) return rc;
+    return pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, reinterpret_cast<float*>(c->dn_feat.p), dn, c->dn_lin.p, nullptr);
+}
+
 extern "C" {
 
 int pt_render_features_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t n_samples, float* d_features) {

@@ -457,4 +457,17 @@ void launch_film_histogram(const float* linear, uint32_t np, uint32_t* hist, uin
 void launch_exposure_meter(const ExposureArgs& a, hipStream_t st);
 void launch_tonemap(const TonemapArgs& a, hipStream_t st);
 
+// Feature-guided upsampling (pt_upsample_device; rule: pt_upsample.h).  One launch: the low film and its feature
+// records, the full-size records -> the full-size film planes (out_rgba may be null).
+struct UpsampleArgs {
+    const float* lo_linear;    // lo_width * lo_height * 3
+    const float4* lo_feat;     // lo_width * lo_height * 2
+    const float4* feat;        // width * height * 2
+    float* out_linear;         // width * height * 3
+    uint8_t* out_rgba;
+    uint32_t width, height, lo_width, lo_height;
+    float sigma_n, sigma_d;
+};
+void launch_upsample(const UpsampleArgs& a, hipStream_t st);
+
 }  // namespace ptk

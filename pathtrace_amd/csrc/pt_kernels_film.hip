@@ -6,6 +6,7 @@
 //   pt_film_temporal.h   its temporal accumulation (one body, three entries) and the temporal gradients
 //   pt_film_bvh.h        device-side BVH refit and builds (Morton order, median order)
 //   pt_film_tonemap.h    auto-exposure and tone mapping
+//   pt_film_upsample.h   feature-guided upsampling of a low-resolution film
 // None of them has a division or square root whose result depends on the arithmetic mode, so the unit is compiled once, in
 // fast mode (its kernels live in ptk_fast_impl), and serves both modes.
 #include "pt_kernels_scan.h"
@@ -18,3 +19,4 @@
 #include "pt_film_temporal.h"
 #include "pt_film_bvh.h"
 #include "pt_film_tonemap.h"
+#include "pt_film_upsample.h"

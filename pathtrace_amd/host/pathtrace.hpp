@@ -17,6 +17,8 @@
 //   World::render_denoised_gradient()  ... and forgets faster where the lighting changed (temporal gradients)
 //   World::render_denoised_gradient_camera()  ... also while the camera moves
 //   World::tonemap()                   auto-exposure, curve and transfer on the film the World holds
+//   World::render_denoised_upsampled() paths traced at a lower resolution, the film reconstructed under full-size features
+//   World::upsample()                  that reconstruction alone, on host planes (the rule on the CPU)
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -459,6 +461,42 @@ public:
             noisy->resize(n);
             for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
         }
+    }
+    // render_denoised() that traces its paths at lo_width x lo_height and reconstructs the camera's size under the full-size
+    // first-hit features (pt_render_denoised_upsampled; up: pt_default_upsample when null).  data / luminance_data hold the
+    // full-size film; lo (optional, y*lo_width+x) receives the denoised low film.
+    void render_denoised_upsampled(uint32_t lo_width, uint32_t lo_height, uint32_t feature_samples = 4, const PtDenoise* dn = nullptr,
+                                   const PtUpsample* up = nullptr, std::vector<Vector3>* lo = nullptr, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtDenoise d{};
+        if (dn) d = *dn; else pt_default_denoise(&d);
+        PtUpsample u{};
+        if (up) u = *up; else pt_default_upsample(&u);
+        const size_t n = (size_t)camera_.width() * camera_.height(), n_lo = (size_t)lo_width * lo_height;
+        std::vector<float> lin(n * 3), raw(lo ? n_lo * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_denoised_upsampled(ctx_, &camera_.pod(), &p, lo_width, lo_height, feature_samples, &d, &u, lin.data(), rgba.data(),
+                                           lo ? raw.data() : nullptr, nullptr));
+        unpack(lin, rgba);
+        if (lo) {
+            lo->resize(n_lo);
+            for (size_t i = 0; i < n_lo; ++i) (*lo)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+        }
+    }
+    // The upsampling rule alone, on host planes and on the CPU (pt_upsample_host; needs no device): a low film (3 floats per
+    // pixel) and its feature records (8 floats per pixel, 16-byte aligned) under the full-size records -> the full-size film
+    // (and, when rgba is not null, its RGBA8 plane).
+    static void upsample(uint32_t lo_width, uint32_t lo_height, const float* lo_linear, const float* lo_features, uint32_t width,
+                         uint32_t height, const float* features, std::vector<float>& linear, std::vector<uint8_t>* rgba = nullptr,
+                         const PtUpsample* up = nullptr) {
+        PtUpsample u{};
+        if (up) u = *up; else pt_default_upsample(&u);
+        linear.resize((size_t)width * height * 3);
+        if (rgba) rgba->resize((size_t)width * height * 4);
+        check(pt_upsample_host(lo_width, lo_height, lo_linear, lo_features, width, height, features, &u, linear.data(), rgba ? rgba->data() : nullptr));
     }
     // Adaptive form of render_denoised() (pt_render_adaptive_denoised): render_adaptive(), the first-hit features of
     // min(feature_samples, spp_min) samples, and the a-trous filter guided by each pixel's measured variance (the squared

@@ -139,6 +139,14 @@ pub const PT_CURVE_ACES: u32 = 2;
 pub const PT_TRANSFER_SQRT: u32 = 0;
 pub const PT_TRANSFER_SRGB: u32 = 1;
 
+/// pt_upsample_device: the edge-stopping weights of feature-guided upsampling (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtUpsample {
+    pub sigma_n: f32,
+    pub sigma_d: f32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct PtStats {
@@ -393,6 +401,10 @@ extern "C" {
     pub fn pt_debug_tonemap_bin(lum: f32) -> u32;
     pub fn pt_debug_tonemap_meter(hist258: *const u32, tm: *const PtTonemap, fresh: c_int, log2e_prev: f64) -> f64;
     pub fn pt_debug_tonemap_pixel(tm: *const PtTonemap, e: f32, rgb: *const f32, out_y: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_default_upsample(out: *mut PtUpsample);
+    pub fn pt_upsample_device(ctx: *mut PtContext, lo_width: u32, lo_height: u32, d_lo_linear: *const f32, d_lo_features: *const f32, width: u32, height: u32, d_features: *const f32, up: *const PtUpsample, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_upsample_host(lo_width: u32, lo_height: u32, lo_linear: *const f32, lo_features: *const f32, width: u32, height: u32, features: *const f32, up: *const PtUpsample, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_denoised_upsampled(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, lo_width: u32, lo_height: u32, feature_samples: u32, dn: *const PtDenoise, up: *const PtUpsample, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_lo_linear: *mut f32, out_features: *mut f32) -> c_int;
     pub fn pt_default_gradient(out: *mut PtGradient);
     pub fn pt_temporal_gradient_device(ctx: *mut PtContext, cam: *const PtCamera, prev_params: *const PtRenderParams, seed: u32, d_prev_linear: *const f32, g: *const PtGradient, alpha_min: f32, d_alpha: *mut f32) -> c_int;
     pub fn pt_debug_gradient_strata(ctx: *mut PtContext, width: u32, height: u32, out_xy: *mut u32, out_film: *mut f32, out_rec: *mut f64) -> c_int;
