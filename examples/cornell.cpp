@@ -2,7 +2,7 @@
 // build World::new(), render every pixel, export luminance.csv, and write a PPM of
 // World.data instead of blitting it to a winit/pixels surface (out of scope).
 //
-//   ./cornell [width height spp [out_prefix [exact_math]]]        defaults: 400 400 64 cornell 0
+//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F]       defaults: 400 400 64 cornell 0, no lens
 //   CORNELL_DENOISE=n: render_denoised with n feature samples (pt_render_denoised) instead of render()
 //   CORNELL_ADAPTIVE_DENOISE=n: render_adaptive_denoised with n feature samples (pt_render_adaptive_denoised): spp is spp_max,
 //                       spp_min 4, spp_step 4, rel_tol 0.1
@@ -18,6 +18,23 @@
 using namespace pathtrace;
 
 int main(int argc, char** argv) {
+    // optional, anywhere on the line: --aperture A --focus F (a thin lens, World::render_lens; with CORNELL_DENOISE its denoised form)
+    PtLens lens;
+    pt_default_lens(&lens);
+    bool use_lens = false;
+    {
+        int keep = 1;
+        for (int i = 1; i < argc; ++i) {
+            const std::string arg = argv[i];
+            if ((arg == "--aperture" || arg == "--focus") && i + 1 < argc) {
+                (arg == "--aperture" ? lens.aperture : lens.focus_distance) = std::atof(argv[++i]);
+                use_lens = true;
+            } else {
+                argv[keep++] = argv[i];
+            }
+        }
+        argc = keep;
+    }
     const uint32_t w = argc > 2 ? (uint32_t)std::atoi(argv[1]) : WIDTH;
     const uint32_t h = argc > 2 ? (uint32_t)std::atoi(argv[2]) : HEIGHT;
     const uint32_t spp = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 64;
@@ -59,6 +76,10 @@ int main(int argc, char** argv) {
             }
         } else if (std::getenv("CORNELL_ADAPTIVE_DENOISE"))   // adaptive denoised form: CORNELL_ADAPTIVE_DENOISE = feature samples
             world.render_adaptive_denoised(4, 4, 0.1, 1e-3, (uint32_t)std::atoi(std::getenv("CORNELL_ADAPTIVE_DENOISE")));
+        else if (use_lens && std::getenv("CORNELL_DENOISE"))
+            world.render_lens_denoised(lens, (uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
+        else if (use_lens)
+            world.render_lens(lens);
         else if (std::getenv("CORNELL_DENOISE"))   // denoised form: CORNELL_DENOISE = feature samples
             world.render_denoised((uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
         else if (std::getenv("CORNELL_PROGRESSIVE"))      // live-preview form: one line per increment

@@ -383,6 +383,7 @@ typedef struct {
     uint64_t np, max_paths_in_flight;
     uint32_t spp, workgroups, accel, profile, list, list_regen, inject, n_objs, blob_f4, diffuse_only, split_ok, n_cus;
     uint32_t export_below, cont_workgroups, level0_form, regen_workgroups, in_order, capturing;
+    uint32_t inject_spp, reserved;   /* inject_spp: samples per pixel that given paths bring (0: one); additive, 0 = as before */
 } PtShapeIn;
 typedef struct {
     uint32_t lds_job, split, regen_scene, over_cap;
@@ -874,6 +875,50 @@ int pt_upsample_host(uint32_t lo_width, uint32_t lo_height, const float* lo_line
 int pt_render_denoised_upsampled(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t lo_width,
                                  uint32_t lo_height, uint32_t feature_samples, const PtDenoise* dn, const PtUpsample* up,
                                  float* out_linear_rgb, uint8_t* out_rgba8, float* out_lo_linear, float* out_features);
+
+/* Thin-lens camera (additive to ABI 6): depth of field.  The lens travels beside PtCamera; the rule
+ * (pathtrace_amd/csrc/pt_lens.h):
+ *   host, f64   C = lower_left + horizontal/2 + vertical/2 - origin, D = |C|, U = horizontal/|horizontal|, V = vertical/|vertical|;
+ *               inv_phi = D / focus_distance, Lu = (aperture/2) U, Lv = (aperture/2) V; the device receives them rounded to f32
+ *   per sample  in the render's arithmetic, from the ONE Philox block the pinhole ray draws for (x, y, sample): words 0, 1 the
+ *               pixel jitter as ever, words 2, 3 (spare until now) the lens point; `dir` the pinhole ray's direction before it
+ *               is normalised.  (a, b) = 2 u01(w2) - 1, 2 u01(w3) - 1 -> (dx, dy) on the unit disc by Shirley's concentric map;
+ *               l = dx Lu + dy Lv;  o' = origin + l;  d' = normalize(dir - l inv_phi)
+ * aperture 0: l = 0 and every entry below is its pinhole entry bit for bit.  aperture > 0: all rays of a jittered screen point
+ * meet at origin + dir / inv_phi, on the plane at focus_distance.  The path kernels do not know the lens: the rays reach them as
+ * given paths (what pt_ray_color does), each traced with key (x, y) and its own sample index.
+ * PT_ERR_INVALID_ARG, and the context untouched, for: a null argument, an aperture that is negative or not finite, a
+ * focus_distance that is not finite or not > 0, a degenerate camera (D or an axis of length 0 or not finite), and everything the
+ * pinhole entry refuses.
+ * The temporal and motion entries have no lens form: their reprojection assumes a pinhole.                                  */
+typedef struct {
+    double aperture;         /* lens diameter in world units; finite, >= 0; 0 = pinhole                                       */
+    double focus_distance;   /* distance from the origin to the plane of focus, along the view axis; finite, > 0              */
+} PtLens;
+void pt_default_lens(PtLens* out);   /* aperture 0, focus_distance 1 */
+/* pt_render_device through the lens (asynchronous on the context's stream): the film is the mean, through the ordinary resolve
+ * (f64 sums in sample order), of the lens rays' colours for samples spp_offset .. spp_offset + spp - 1.  Row bands as in
+ * pt_render_device; max_paths_in_flight cuts the job into sample batches and the film does not depend on them.  The context
+ * owns the planes the rays are written to: they grow at first use.                                                          */
+int pt_render_lens_device(PtContext* ctx, const PtCamera* cam, const PtLens* lens, const PtRenderParams* params,
+                          float* d_linear_rgb, uint8_t* d_rgba8);
+/* The same into host buffers (blocking), as pt_render_host. */
+int pt_render_lens_host(PtContext* ctx, const PtCamera* cam, const PtLens* lens, const PtRenderParams* params,
+                        float* out_linear_rgb, uint8_t* out_rgba8);
+/* pt_render_features_device with lens rays: the same records, sums and checks. */
+int pt_render_features_lens_device(PtContext* ctx, const PtCamera* cam, const PtLens* lens, const PtRenderParams* params,
+                                   uint32_t n_samples, float* d_features);
+/* pt_render_denoised through the lens (host buffers, blocking): bit-identical to pt_render_lens_device ->
+ * pt_render_features_lens_device -> pt_denoise_device.                                                                      */
+int pt_render_lens_denoised(PtContext* ctx, const PtCamera* cam, const PtLens* lens, const PtRenderParams* params,
+                            uint32_t feature_samples, const PtDenoise* dn, float* out_linear_rgb, uint8_t* out_rgba8,
+                            float* out_noisy_linear, float* out_features);
+/* Debug: the lens rays of n (x, y, sample) triples (x, y the film position, top-down) as pt_debug_camera_rays gives the
+ * pinhole rays: out8 = n * (o'3, d'3, dx, dy).  Host arrays, blocking; needs no scene.                                       */
+int pt_debug_lens_rays(PtContext* ctx, const PtCamera* cam, const PtLens* lens, const uint32_t* xys, uint32_t n,
+                       uint32_t exact_math, float* out8);
+/* Debug, host only: out7 = Lu3, Lv3, inv_phi as the device receives them.  Needs no device. */
+int pt_debug_lens_setup(const PtCamera* cam, const PtLens* lens, float* out7);
 
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on

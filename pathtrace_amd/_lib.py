@@ -139,6 +139,13 @@ class PtUpsample(C.Structure):
     ]
 
 
+class PtLens(C.Structure):
+    _fields_ = [
+        ("aperture", C.c_double),
+        ("focus_distance", C.c_double),
+    ]
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -152,7 +159,7 @@ class PtSchedOp(C.Structure):
 class PtShapeIn(C.Structure):
     _fields_ = [("np", C.c_uint64), ("max_paths_in_flight", C.c_uint64)] + [(n, C.c_uint32) for n in (
         "spp", "workgroups", "accel", "profile", "list", "list_regen", "inject", "n_objs", "blob_f4", "diffuse_only", "split_ok", "n_cus",
-        "export_below", "cont_workgroups", "level0_form", "regen_workgroups", "in_order", "capturing")]
+        "export_below", "cont_workgroups", "level0_form", "regen_workgroups", "in_order", "capturing", "inject_spp", "reserved")]
 
 
 class PtShapeOut(C.Structure):
@@ -294,6 +301,14 @@ SYMBOLS = {
     "pt_debug_tonemap_bin": (C.c_uint32, [C.c_float]),
     "pt_debug_tonemap_meter": (C.c_double, [_P(C.c_uint32), _P(PtTonemap), C.c_int, C.c_double]),
     "pt_debug_tonemap_pixel": (C.c_int, [_P(PtTonemap), C.c_float, _P(C.c_float), _P(C.c_float), _P(C.c_uint8)]),
+    "pt_default_lens": (None, [_P(PtLens)]),
+    "pt_render_lens_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtLens), _P(PtRenderParams), C.c_void_p, C.c_void_p]),
+    "pt_render_lens_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtLens), _P(PtRenderParams), C.c_void_p, C.c_void_p]),
+    "pt_render_features_lens_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtLens), _P(PtRenderParams), C.c_uint32, C.c_void_p]),
+    "pt_render_lens_denoised": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtLens), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_debug_lens_rays": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtLens), _P(C.c_uint32), C.c_uint32, C.c_uint32, _P(C.c_float)]),
+    "pt_debug_lens_setup": (C.c_int, [_P(PtCamera), _P(PtLens), _P(C.c_float)]),
     "pt_default_upsample": (None, [_P(PtUpsample)]),
     "pt_upsample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                      _P(PtUpsample), C.c_void_p, C.c_void_p]),

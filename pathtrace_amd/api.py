@@ -81,6 +81,23 @@ def default_upsample(**over):
     return u
 
 
+def default_lens(**over):
+    """pt_default_lens (aperture 0 = pinhole, focus_distance 1) with keyword overrides (None keeps the default)."""
+    l = _lib.PtLens()
+    lib().pt_default_lens(C.byref(l))
+    for k, v in over.items():
+        if v is not None:
+            setattr(l, k, v)
+    return l
+
+
+def lens_setup(cam, lens):
+    """pt_debug_lens_setup (host only): -> float32[7] = Lu3, Lv3, inv_phi as the device receives them."""
+    out = np.empty(7, dtype=np.float32)
+    check(lib().pt_debug_lens_setup(C.byref(cam), C.byref(lens), _pf(out)))
+    return out
+
+
 def upsample_host(lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
     """pt_upsample_host: the upsampling rule on the CPU (no device, no context), on a low film (f32[h,w,3]), its features
     (f32[h,w,8]) and the full-size features (f32[H,W,8]).  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
@@ -396,6 +413,13 @@ class _ContextFunctions:
         check(lib().pt_debug_camera_rays(self._h, C.byref(cam), _pu(xys), xys.shape[0], exact_math, _pf(out)))
         return out
 
+    def lens_rays(self, cam, lens, xys, exact_math=0):
+        """pt_debug_lens_rays: xys n x (x, y film row, sample) -> float32[n, 8] = origin3, direction3, dx, dy (the lens point)"""
+        xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+        out = np.empty((xys.shape[0], 8), dtype=np.float32)
+        check(lib().pt_debug_lens_rays(self._h, C.byref(cam), C.byref(lens), _pu(xys), xys.shape[0], exact_math, _pf(out)))
+        return out
+
     def multi_emulate(self, n_virtual, cam, params):
         """pt_debug_multi_emulate: the frame an n_virtual-device pt_multi render assembles, produced on this one context."""
         lin = np.empty((cam.height, cam.width, 3), dtype=np.float32)
@@ -482,6 +506,29 @@ class _ContextFunctions:
         dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
         planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32))
         check(lib().pt_render_denoised(self._h, C.byref(cam), C.byref(params), feature_samples, C.byref(dn), *ptrs))
+        return planes
+
+    def render_lens(self, cam, lens, params, want_rgba=True):
+        """pt_render_lens_device: render() through a thin lens (default_lens).  -> (linear[rows,W,3] f32, rgba[rows,W,4] u8 or
+        None), torch device tensors"""
+        rows = tile_rows(cam.height, params.band_rows, params.band_index, params.band_count or 1)
+        lin = self._empty((rows, cam.width, 3))
+        rgba = self._empty((rows, cam.width, 4), "uint8") if want_rgba else None
+        self._on_stream(lib().pt_render_lens_device, C.byref(cam), C.byref(lens), C.byref(params), lin, rgba)
+        return lin, rgba
+
+    def render_features_lens(self, cam, lens, params, n_samples):
+        """pt_render_features_lens_device: render_features with lens rays.  -> f32[H,W,8]"""
+        feat = self._empty((cam.height, cam.width, 8))
+        self._on_stream(lib().pt_render_features_lens_device, C.byref(cam), C.byref(lens), C.byref(params), n_samples, feat)
+        return feat.cpu().numpy()
+
+    def render_lens_denoised(self, cam, lens, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
+        """pt_render_lens_denoised (host buffers, blocking).  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear f32[H,W,3],
+        features f32[H,W,8])"""
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32))
+        check(lib().pt_render_lens_denoised(self._h, C.byref(cam), C.byref(lens), C.byref(params), feature_samples, C.byref(dn), *ptrs))
         return planes
 
     def upsample(self, lo_linear, lo_features, features, sigma_n=None, sigma_d=None):

@@ -102,13 +102,13 @@ int check_scene_and_camera(const PtContext* c, const PtCamera* cam) {
 int check_render(const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const ListRender* list, const float* d_linear,
                  const uint8_t* d_rgba) {
     if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "render: null argument");
-    if (int rc = check_scene_and_camera(c, list && list->inject[0] ? nullptr : cam)) return rc;
+    if (int rc = check_scene_and_camera(c, list && list->inject[0] && !list->tile ? nullptr : cam)) return rc;
     if (prm->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
     if (prm->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "unknown integrator %u", prm->integrator);
     if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
     const uint32_t band_count = prm->band_count ? prm->band_count : 1;
     if (prm->band_index >= band_count) return fail(PT_ERR_INVALID_ARG, "band_index %u >= band_count %u", prm->band_index, band_count);
-    if (list && band_count != 1) return fail(PT_ERR_INVALID_ARG, "pixel-list renders take the whole image (band_count = 1)");
+    if (list && !list->tile && band_count != 1) return fail(PT_ERR_INVALID_ARG, "pixel-list renders take the whole image (band_count = 1)");
     // the resolve stores a pixel's RGBA8 as one 32-bit word (a byte-offset pointer would fault on the device)
     if (d_rgba && (uintptr_t)d_rgba % 4u) return fail(PT_ERR_INVALID_ARG, "render: the RGBA8 output buffer must be 4-byte aligned");
     if (d_linear && (uintptr_t)d_linear % 4u) return fail(PT_ERR_INVALID_ARG, "render: the linear output buffer must be 4-byte aligned");
@@ -134,6 +134,7 @@ int size_render(PtContext* c, const PtRenderParams* prm, const ListRender* list,
     in.np = np64; in.max_paths_in_flight = prm->max_paths_in_flight;
     in.spp = prm->spp; in.workgroups = prm->workgroups; in.accel = prm->accel; in.profile = prm->profile;
     in.list = list != nullptr; in.list_regen = list && list->regen; in.inject = list && list->inject[0];
+    in.inject_spp = list ? list->inject_spp : 0u;
     in.n_objs = c->view.n_objs; in.blob_f4 = c->view.blob_f4; in.diffuse_only = c->view.diffuse_only;
     in.split_ok = c->split_ok; in.n_cus = c->n_cus;
     in.export_below = c->tuning.export_below; in.cont_workgroups = c->tuning.cont_workgroups; in.level0_form = c->tuning.level0_form;
@@ -210,29 +211,35 @@ int prepare(PtContext* c, const PtRenderParams* prm, const FilmState& fs, const 
     return PT_OK;
 }
 
+// tile row -> image row without a table (ptk::TileMap)
+ptk::TileMap tile_map(const PtCamera* cam, const PtRenderParams* prm) {
+    ptk::TileMap t{};
+    const uint32_t br = prm->band_rows ? prm->band_rows : cam->height;
+    t.band_rows = br;
+    t.band_magic = br > 1 ? (uint32_t)(((1ull << 32) + br - 1) / br) : 0u;
+    t.band_stride = br * (prm->band_count ? prm->band_count : 1);
+    t.band_first = prm->band_index * br;
+    return t;
+}
+uint32_t magic_of(uint32_t d) { return d <= 1u ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / d); }   // floor(2^32 / d) (divmod_magic)
+
 // ARGS: the words of BounceArgs that are the same for every launch of the render
 ptk::BounceArgs bounce_args(const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const ListRender* list, uint32_t np) {
     ptk::BounceArgs a{};
     a.stats = reinterpret_cast<unsigned long long*>(c->ovf_count.p);   // hipMalloc alignment: fine for u64
-    if (!list) {   // tile row -> image row without a table (ptk::TileMap)
-        const uint32_t br = prm->band_rows ? prm->band_rows : cam->height;
-        a.tile.band_rows = br;
-        a.tile.band_magic = br > 1 ? (uint32_t)(((1ull << 32) + br - 1) / br) : 0u;
-        a.tile.band_stride = br * (prm->band_count ? prm->band_count : 1);
-        a.tile.band_first = prm->band_index * br;
-    }
+    const bool tile = !list || list->tile;       // the film is the camera's tile (else: the list's slots)
+    if (tile) a.tile = tile_map(cam, prm);
     a.sc = view_for(c, prm->exact_math);
     for (int k = 0; k < 3; ++k) {
         a.cam.origin[k] = (float)cam->origin[k]; a.cam.lower_left[k] = (float)cam->lower_left[k];
         a.cam.horizontal[k] = (float)cam->horizontal[k]; a.cam.vertical[k] = (float)cam->vertical[k];
     }
     a.cam.width = cam->width; a.cam.height = cam->height;
-    a.pixels = list ? list->d_pixels : nullptr;
-    a.film_w = list ? 65536u : cam->width;
+    a.pixels = tile ? nullptr : list->d_pixels;
+    a.film_w = tile ? cam->width : 65536u;
     a.np = np;
-    auto magic = [](uint32_t d) { return d <= 1u ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / d); };
-    a.film_w_magic = magic(a.film_w);
-    a.np_magic = magic(np);
+    a.film_w_magic = magic_of(a.film_w);
+    a.np_magic = magic_of(np);
     a.min_depth = prm->min_depth; a.max_depth = prm->max_depth;
     a.t_min = (float)prm->t_min;
     a.integrator = prm->integrator;
@@ -408,14 +415,15 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
     resolved.accel = resolve_accel(c, prm->accel);
     prm = &resolved;
 
-    const uint64_t np64 = list ? list->n : (uint64_t)pt_tile_rows(cam->height, prm->band_rows, prm->band_index, prm->band_count ? prm->band_count : 1) * cam->width;
-    const uint64_t tile_rows = list ? ((np64 + 65535u) >> 16) : np64 / cam->width;
+    const bool tile = !list || list->tile;
+    const uint64_t np64 = !tile ? list->n : (uint64_t)pt_tile_rows(cam->height, prm->band_rows, prm->band_index, prm->band_count ? prm->band_count : 1) * cam->width;
+    const uint64_t tile_rows = !tile ? ((np64 + 65535u) >> 16) : np64 / cam->width;
     if (np64 == 0) {                   // empty tile: nothing to render
         if (!c->sched.stats_pending) begin_period(c);
         return PT_OK;
     }
     if (!d_linear && !d_packed) return fail(PT_ERR_INVALID_ARG, "render: the linear output buffer is null");
-    if (!list && (cam->width > 65535u || tile_rows > 65535u))   // (tile row, x) share one word of the path state
+    if (tile && (cam->width > 65535u || tile_rows > 65535u))   // (tile row, x) share one word of the path state
         return fail(PT_ERR_UNSUPPORTED, "tile %ux%llu: width and tile rows must be < 65536", cam->width, (unsigned long long)tile_rows);
     ptshape::Shape sh;
     if ((rc = size_render(c, prm, list, np64, &sh))) return rc;
@@ -447,7 +455,83 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
     return PT_OK;
 }
 
+// The thin-lens render.  The path kernels do not know the lens: per sample batch k_lens_paths writes the lens rays
+// of the tile as path states into the context's inject planes, and render_impl takes them up as given paths of the tile
+// (ListRender::tile: the launches of pt_ray_color, the film slots, keys and bands of a plain render).  One render_impl per batch
+// of nb <= max_paths_in_flight / np samples; the f64 film sums travel between the batches as they do between the increments of
+// pt_render_progressive, so the film does not depend on the batching.  Everything is checked, and the planes are there, before
+// the first launch; all launches are on the caller's stream, which orders batch k's level-0 launch (the planes' only reader)
+// before batch k + 1's k_lens_paths.
+int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,
+                     uint8_t* d_rgba) {
+    if (!c || !cam || !lens || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc;
+    ListRender lr;
+    lr.tile = true;
+    lr.inject[0] = reinterpret_cast<const float4*>(1);      // (check_render only asks whether the paths are given)
+    ptk::LensPathsArgs a{};
+    if ((rc = lens_setup(who, cam, lens, &a.lens)) || (rc = check_render(c, cam, prm, &lr, d_linear, d_rgba))) return rc;
+    const uint64_t np64 = tile_pixels(cam, prm);
+    if (np64 == 0) return render_impl(c, cam, prm, FilmState{}, nullptr, d_linear, d_rgba);      // an empty tile, as ever
+    if (!d_linear) return fail(PT_ERR_INVALID_ARG, "render: the linear output buffer is null");
+    if (cam->width > 65535u || np64 / cam->width > 65535u)
+        return fail(PT_ERR_UNSUPPORTED, "tile %ux%llu: width and tile rows must be < 65536", cam->width, (unsigned long long)(np64 / cam->width));
+    const uint64_t cap = std::min<uint64_t>(prm->max_paths_in_flight ? prm->max_paths_in_flight : kDefaultMaxPaths, ptshape::kMaxPaths);
+    if (np64 > cap)
+        return fail(PT_ERR_UNSUPPORTED, "tile of %llu pixels exceeds max_paths_in_flight %llu; use more bands", (unsigned long long)np64,
+                    (unsigned long long)cap);
+    const uint32_t np = (uint32_t)np64;
+    const uint32_t nb_max = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(cap / np, 65535u), prm->spp);
+    HIP_TRY(hipSetDevice(c->device));
+    for (int k = 0; k < 4; ++k)
+        if ((rc = c->inject[k].ensure((size_t)np * nb_max))) return rc;
+    a.cam = camera_f32(cam);
+    a.tile = tile_map(cam, prm);
+    a.np = np; a.np_magic = magic_of(np); a.w_magic = magic_of(cam->width);
+    for (int k = 0; k < 4; ++k) { a.q[k] = c->inject[k].p; lr.inject[k] = c->inject[k].p; }
+    for (uint32_t done = 0; done < prm->spp;) {
+        const uint32_t nb = std::min(nb_max, prm->spp - done);
+        PtRenderParams p = *prm;
+        p.spp = nb;
+        p.spp_offset = prm->spp_offset + done;
+        p.max_paths_in_flight = cap;      // (the cap the batches were cut for, whatever default the sizing would pick)
+        a.s_base = p.spp_offset; a.n = np * nb;
+        if (prm->exact_math) ptk::launch_lens_paths_exact(a, c->stream); else ptk::launch_lens_paths_fast(a, c->stream);
+        HIP_TRY(hipGetLastError());
+        lr.inject_spp = nb;
+        FilmState fs;
+        fs.load = done > 0;
+        fs.store = done + nb < prm->spp;
+        fs.div = prm->spp;
+        if ((rc = render_impl(c, cam, &p, fs, &lr, d_linear, d_rgba))) return rc;
+        done += nb;
+    }
+    return PT_OK;
+}
+
 extern "C" {
+
+int pt_render_lens_device(PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear, uint8_t* d_rgba) {
+    return render_lens_impl("pt_render_lens_device", c, cam, lens, prm, d_linear, d_rgba);
+}
+
+int pt_render_lens_host(PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* out_linear, uint8_t* out_rgba) {
+    if (!c || !cam || !lens || !prm || !out_linear) return fail(PT_ERR_INVALID_ARG, "pt_render_lens_host: null argument");
+    ptk::LensF checked;
+    if (int bad = lens_setup("pt_render_lens_host", cam, lens, &checked)) return bad;      // before the staging is touched
+    const size_t np = tile_pixels(cam, prm);
+    if (np == 0) return render_lens_impl("pt_render_lens_host", c, cam, lens, prm, nullptr, nullptr);   // validates, renders nothing
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->host_lin.ensure(np * 3))) return rc;
+    if (out_rgba && (rc = c->host_rgba.ensure(np * 4))) return rc;
+    rc = render_lens_impl("pt_render_lens_host", c, cam, lens, prm, c->host_lin.p, out_rgba ? c->host_rgba.p : nullptr);
+    if (!rc) rc = pt_sync(c);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, np * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, np * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
 
 int pt_render_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, float* d_linear, uint8_t* d_rgba) {
     return render_impl(c, cam, prm, FilmState{}, nullptr, d_linear, d_rgba);

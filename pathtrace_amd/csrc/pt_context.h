@@ -259,6 +259,11 @@ struct ListRender {
     uint32_t n = 0;
     const float4* inject[4] = {nullptr, nullptr, nullptr, nullptr};
     bool regen = false;       // the list may take the regenerating level-0 kernel (pt_render_adaptive's passes)
+    // inject only (pt_render_lens_device): the given paths are those of the camera's TILE -- film slot = (tile row, x), RNG key
+    // (x, image row), bands as in a plain render, no pixel list (d_pixels and n unused) --, inject_spp samples of every pixel,
+    // state s_local * np + tile pixel (0: one sample)
+    bool tile = false;
+    uint32_t inject_spp = 0;
 };
 // A pass of pt_render_adaptive: the film resolve is k_resolve_adaptive into the image-indexed state instead of k_resolve.
 struct AdaptivePass {
@@ -271,6 +276,16 @@ struct AdaptivePass {
 int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
                 float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr);   // pt_api.cpp
 int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad);   // pt_api.cpp
+// pt_render_lens_device in the name `who` (pt_api.cpp); pt_lens.cpp: the lens and the camera checked, the device's words
+int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,
+                     uint8_t* d_rgba);
+int lens_setup(const char* who, const PtCamera* cam, const PtLens* lens, ptk::LensF* out);
+ptk::CameraF camera_f32(const PtCamera* cam);                        // pt_lens.cpp
+int features_lens_device(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
+                         float* d_features);                          // pt_denoise.cpp
+int render_lens_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm,
+                              uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                              float* out_features);                   // pt_denoise.cpp
 int denoised_frame_device(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                           const PtDenoise* dn, PtRenderParams* p);   // pt_denoise.cpp
 ptk::SceneView view_for(const PtContext* c, uint32_t exact_math);   // pt_scene.cpp

@@ -470,4 +470,27 @@ struct UpsampleArgs {
 };
 void launch_upsample(const UpsampleArgs& a, hipStream_t st);
 
+// Thin-lens camera (pt_render_lens_device; rule: pt_lens.h).  LensF: ptlens::Setup as the kernels take it.
+// launch_lens_paths: the lens rays of samples s_base .. s_base + nb - 1 of every tile pixel as n = nb * np path states in the
+// queue form (state s_local * np + tile pixel), for a path-kernel launch with src_mode = 1 to take up from ovf_in.
+// launch_lens_feature_rays: launch_feature_rays with lens rays.  launch_debug_lens_rays: words = n * (x, y, sample, -) ->
+// out8 = n * (o'3, d'3, dx, dy).
+struct LensF {
+    float lu[3], lv[3], inv_phi;
+};
+struct LensPathsArgs {
+    CameraF cam;
+    LensF lens;
+    TileMap tile;
+    float4* q[4];
+    uint32_t np, np_magic, w_magic;   // tile pixels; floor(2^32 / np) and floor(2^32 / cam.width), 0xFFFFFFFF for 1
+    uint32_t s_base, n;
+};
+void launch_lens_paths_exact(const LensPathsArgs& a, hipStream_t st);
+void launch_lens_paths_fast(const LensPathsArgs& a, hipStream_t st);
+void launch_lens_feature_rays_exact(const CameraF& cam, const LensF& lens, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
+void launch_lens_feature_rays_fast(const CameraF& cam, const LensF& lens, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
+void launch_debug_lens_rays_exact(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
+void launch_debug_lens_rays_fast(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
+
 }  // namespace ptk

@@ -33,6 +33,7 @@
 // conflict-free).  Grids are persistent (one queue segment per wave), so no host round trip sits between bounces.
 #include "pt_kernels_scan.h"
 #include "pt_kernels_vertex.h"
+#include "pt_lens.h"
 
 namespace PTK_IMPL {
 
@@ -871,5 +872,88 @@ void PT_LAUNCH(launch_feature_rays)(const CameraF& cam, uint32_t s_base, uint32_
 }
 void PT_LAUNCH(launch_feature_resolve)(const FeatureResolveArgs& a, hipStream_t st) {
     if (a.np) hipLaunchKernelGGL(PTK_IMPL::k_feature_resolve, dim3((a.np + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+}  // namespace ptk
+
+// ------------------------------------------------------------------ thin-lens camera (pt_render_lens_device; rule: pt_lens.h)
+// lens_ray: camera_ray with the lens point -- the same block of draws, the same statements up to `dir`, then pt_lens.h.  The
+// path kernels do not know the lens: k_lens_paths writes the rays as path states in the queue form, and a launch with
+// src_mode = 1 takes them up as it takes up handed-over paths (what pt_ray_color does with rays of the caller's).
+//   k_lens_paths          state i = s_local * np + tile pixel (the pixel fastest): the four planes store_state writes, depth 0,
+//                         throughput 1, pdf_prev 0, no radiance, eta 1; one 16-byte store per lane and plane
+//   k_lens_feature_rays   k_feature_rays with lens rays
+//   k_debug_lens_rays     words[4] = x, y, sample, - -> out[8] = o'3, d'3, dx, dy
+namespace PTK_IMPL {
+struct LensMath {
+    static PT_DEV float div(float a, float b) { return pt_div(a, b); }
+    static PT_DEV void sincos2pi(float u, float& s, float& c) { PTD_NS::sincos2pi(u, s, c); }
+};
+PT_DEV void lens_ray(const CameraF& cam, const LensF& lens, uint32_t sample, uint32_t px, uint32_t py, f3& o, f3& d, float& dx, float& dy) {
+    uint32_t dc[4];
+    philox4x32_draw(px, py, sample, kDepthCamera, BLK_SURFACE, 0u, dc);
+    float ox = u01(dc[0]), oy = u01(dc[1]);
+    float wm1 = (float)(cam.width - 1u), hm1 = (float)(cam.height - 1u);
+    asm volatile("" : "+v"(wm1), "+v"(hm1));
+    float u = pt_div((float)px + ox, wm1);
+    float v = pt_div((float)(cam.height - 1u - py) + oy, hm1);
+    const f3 cam_o = mk(cam.origin[0], cam.origin[1], cam.origin[2]);
+    f3 dir = mk(cam.lower_left[0], cam.lower_left[1], cam.lower_left[2]) +
+             mk(cam.horizontal[0], cam.horizontal[1], cam.horizontal[2]) * u +
+             mk(cam.vertical[0], cam.vertical[1], cam.vertical[2]) * v - cam_o;
+    ptlens::disc<LensMath>(u01(dc[2]), u01(dc[3]), &dx, &dy);
+    ptlens::Setup L;
+    for (int k = 0; k < 3; ++k) { L.lu[k] = lens.lu[k]; L.lv[k] = lens.lv[k]; }
+    L.inv_phi = lens.inv_phi;
+    const float o3[3] = {cam_o.x, cam_o.y, cam_o.z}, d3[3] = {dir.x, dir.y, dir.z};
+    float oo[3], dd[3];
+    ptlens::ray(L, o3, d3, dx, dy, oo, dd);
+    o = mk(oo[0], oo[1], oo[2]);
+    d = normalize(mk(dd[0], dd[1], dd[2]));
+}
+__global__ void __launch_bounds__(kBlock) k_lens_paths(LensPathsArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    uint32_t s_local, pix, yl, px;
+    divmod_magic(i, a.np, a.np_magic, s_local, pix);
+    divmod_magic(pix, a.cam.width, a.w_magic, yl, px);
+    f3 o, d; float dx, dy;
+    lens_ray(a.cam, a.lens, a.s_base + s_local, px, image_row(a.tile, yl), o, d, dx, dy);
+    a.q[0][i] = make_float4(o.x, o.y, o.z, d.x);
+    a.q[1][i] = make_float4(d.y, d.z, __uint_as_float((yl << 16) | px), __uint_as_float(s_local << 16));
+    a.q[2][i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+    a.q[3][i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+}
+__global__ void __launch_bounds__(kBlock) k_lens_feature_rays(CameraF cam, LensF lens, uint32_t s_base, uint32_t nb, float* __restrict__ rays6) {
+    const uint32_t np = cam.width * cam.height;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nb * np) return;
+    const uint32_t s = i / np, p = i - s * np;
+    const uint32_t y = p / cam.width, x = p - y * cam.width;
+    f3 o, d; float dx, dy;
+    lens_ray(cam, lens, s_base + s, x, y, o, d, dx, dy);
+    float* r = rays6 + 6 * (size_t)i;
+    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+}
+__global__ void __launch_bounds__(kBlock) k_debug_lens_rays(CameraF cam, LensF lens, const uint32_t* __restrict__ words, uint32_t n,
+                                                            float* __restrict__ out8) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* w = words + 4 * (size_t)i;
+    f3 o, d; float dx, dy;
+    lens_ray(cam, lens, w[2], w[0], w[1], o, d, dx, dy);
+    float* out = out8 + 8 * (size_t)i;
+    out[0] = o.x; out[1] = o.y; out[2] = o.z; out[3] = d.x; out[4] = d.y; out[5] = d.z; out[6] = dx; out[7] = dy;
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void PT_LAUNCH(launch_lens_paths)(const LensPathsArgs& a, hipStream_t st) {
+    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_lens_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+void PT_LAUNCH(launch_lens_feature_rays)(const CameraF& cam, const LensF& lens, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st) {
+    const uint32_t n = nb * cam.width * cam.height;
+    if (n) hipLaunchKernelGGL(PTK_IMPL::k_lens_feature_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, lens, s_base, nb, rays6);
+}
+void PT_LAUNCH(launch_debug_lens_rays)(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(PTK_IMPL::k_debug_lens_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, lens, words, n, out8);
 }
 }  // namespace ptk

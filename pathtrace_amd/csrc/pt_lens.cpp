@@ -1,0 +1,84 @@
+// pt_lens.cpp -- the host side of the thin-lens camera that is not the render driver's (pt_api.cpp: render_lens_impl): the checks
+// and the device's words (pt_lens.h), the defaults, the debug entries, and the entries of the lens forms pt_denoise.cpp holds.
+#include "pt_context.h"
+#include "pt_lens.h"
+
+ptk::CameraF camera_f32(const PtCamera* cam) {
+    ptk::CameraF cf{};
+    for (int k = 0; k < 3; ++k) {
+        cf.origin[k] = (float)cam->origin[k]; cf.lower_left[k] = (float)cam->lower_left[k];
+        cf.horizontal[k] = (float)cam->horizontal[k]; cf.vertical[k] = (float)cam->vertical[k];
+    }
+    cf.width = cam->width; cf.height = cam->height;
+    return cf;
+}
+
+// The lens and the camera's frame checked (a check answers in the entry's name, who), Lu, Lv and inv_phi in f32.  No context.
+int lens_setup(const char* who, const PtCamera* cam, const PtLens* lens, ptk::LensF* out) {
+    ptlens::Setup s;
+    switch (ptlens::setup(cam->origin, cam->lower_left, cam->horizontal, cam->vertical, lens->aperture, lens->focus_distance, &s)) {
+    case ptlens::kOk: break;
+    case ptlens::kBadAperture: return fail(PT_ERR_INVALID_ARG, "%s: aperture %g must be finite and >= 0", who, lens->aperture);
+    case ptlens::kBadFocus: return fail(PT_ERR_INVALID_ARG, "%s: focus_distance %g must be finite and > 0", who, lens->focus_distance);
+    default:
+        return fail(PT_ERR_INVALID_ARG, "%s: degenerate camera (the view axis, horizontal and vertical must have a finite length > 0)", who);
+    }
+    for (int k = 0; k < 3; ++k) { out->lu[k] = s.lu[k]; out->lv[k] = s.lv[k]; }
+    out->inv_phi = s.inv_phi;
+    return PT_OK;
+}
+
+extern "C" {
+
+void pt_default_lens(PtLens* out) {
+    if (!out) return;
+    out->aperture = 0.0;
+    out->focus_distance = 1.0;
+}
+
+int pt_render_features_lens_device(PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
+                                   float* d_features) {
+    if (!lens) return fail(PT_ERR_INVALID_ARG, "pt_render_features_lens_device: null argument");
+    return features_lens_device("pt_render_features_lens_device", c, cam, lens, prm, n_samples, d_features);
+}
+
+int pt_render_lens_denoised(PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t feature_samples,
+                            const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy, float* out_features) {
+    if (!lens) return fail(PT_ERR_INVALID_ARG, "pt_render_lens_denoised: null argument");
+    return render_lens_denoised_host("pt_render_lens_denoised", c, cam, lens, prm, feature_samples, dn, out_linear, out_rgba, out_noisy,
+                                     out_features);
+}
+
+int pt_debug_lens_setup(const PtCamera* cam, const PtLens* lens, float* out7) {
+    if (!cam || !lens || !out7) return fail(PT_ERR_INVALID_ARG, "pt_debug_lens_setup: null argument");
+    ptk::LensF l;
+    if (int rc = lens_setup("pt_debug_lens_setup", cam, lens, &l)) return rc;
+    for (int k = 0; k < 3; ++k) { out7[k] = l.lu[k]; out7[3 + k] = l.lv[k]; }
+    out7[6] = l.inv_phi;
+    return PT_OK;
+}
+
+int pt_debug_lens_rays(PtContext* c, const PtCamera* cam, const PtLens* lens, const uint32_t* xys, uint32_t n, uint32_t exact_math,
+                       float* out8) {
+    if (!c || !cam || !lens || (n && (!xys || !out8))) return fail(PT_ERR_INVALID_ARG, "pt_debug_lens_rays: null argument");
+    ptk::LensF l;
+    if (int rc = lens_setup("pt_debug_lens_rays", cam, lens, &l)) return rc;
+    if (cam->width < 2 || cam->height < 2)
+        return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    if (n == 0) return PT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->fn_out.ensure(8 * (size_t)n)) || (rc = c->fn_words.ensure(4 * (size_t)n))) return rc;
+    std::vector<uint32_t> w(4 * (size_t)n, 0u);
+    for (size_t i = 0; i < n; ++i) { w[4 * i] = xys[3 * i]; w[4 * i + 1] = xys[3 * i + 1]; w[4 * i + 2] = xys[3 * i + 2]; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->fn_words.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (exact_math) ptk::launch_debug_lens_rays_exact(camera_f32(cam), l, c->fn_words.p, n, c->fn_out.p, c->stream);
+    else ptk::launch_debug_lens_rays_fast(camera_f32(cam), l, c->fn_words.p, n, c->fn_out.p, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out8, c->fn_out.p, 8 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+}  // extern "C"

@@ -24,7 +24,7 @@ struct PtSched {
 static_assert(sizeof(PtSchedOp) == sizeof(ptsched::Op), "PtSchedOp mirrors ptsched::Op");
 static_assert(sizeof(PtSchedJob) == 14 * sizeof(uint32_t) + sizeof(uint64_t), "PtSchedJob layout");
 #ifdef PT_HAVE_SHAPE
-static_assert(sizeof(PtShapeIn) == sizeof(ptshape::In) && sizeof(PtShapeIn) == 2 * sizeof(uint64_t) + 18 * sizeof(uint32_t), "PtShapeIn mirrors ptshape::In");
+static_assert(sizeof(PtShapeIn) == sizeof(ptshape::In) && sizeof(PtShapeIn) == 2 * sizeof(uint64_t) + 20 * sizeof(uint32_t), "PtShapeIn mirrors ptshape::In");
 static_assert(sizeof(PtShapeLaunch) == sizeof(ptshape::Launch) + sizeof(uint32_t), "PtShapeLaunch mirrors ptshape::Launch (+ 1 reserved word)");
 #endif
 

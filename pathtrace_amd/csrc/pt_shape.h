@@ -84,6 +84,8 @@ struct In {
     uint32_t n_cus;
     uint32_t export_below, cont_workgroups, level0_form, regen_workgroups, in_order;   // PtTuning
     uint32_t capturing;             // the caller's stream is being captured into a graph
+    uint32_t inject_spp;            // inject: samples per pixel the given paths bring, state s_local * np + pixel (0: one, as pt_ray_color's)
+    uint32_t reserved;
 };
 
 // Which level-0 form the scene and the job can take (decided for the render by shape(), once the batch size is known).
@@ -108,7 +110,7 @@ inline Form form(const In& in) {
 struct Shape {
     bool over_cap;                  // the tile has more pixels than cap: nothing below is filled in
     uint64_t cap;
-    uint32_t np, spp;               // spp: 1 for given paths
+    uint32_t np, spp;               // spp: inject_spp (0: 1) for given paths
     uint32_t nb_max, n_batches;     // samples per pixel in a batch; batches
     uint64_t n_paths_max;           // paths of the largest batch
     uint32_t export_small, paths_per_wave;
@@ -131,7 +133,7 @@ inline Shape shape(const In& in, const Form& f, uint32_t occupancy) {
     if (s.over_cap) return s;
     const uint32_t np = s.np = (uint32_t)in.np;
     s.inject = in.inject != 0;
-    const uint32_t spp = s.spp = s.inject ? 1u : in.spp;
+    const uint32_t spp = s.spp = s.inject ? std::max(1u, in.inject_spp) : in.spp;
     s.nb_max = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(s.cap / np, 65535u), spp);
     if (s.nb_max == 0) s.nb_max = 1;
     s.n_paths_max = (uint64_t)np * s.nb_max;

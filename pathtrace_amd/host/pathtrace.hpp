@@ -462,6 +462,39 @@ public:
             for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
         }
     }
+    // render() through a thin lens (pt_render_lens_host): depth of field.  aperture = the lens diameter in world
+    // units (0: render()'s film bit for bit), focus_distance = the distance of the plane in focus along the view axis.
+    void render_lens(const PtLens& lens, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3);
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_lens_host(ctx_, &camera_.pod(), &lens, &p, lin.data(), rgba.data()));
+        unpack(lin, rgba);
+    }
+    // render_denoised() through the lens (pt_render_lens_denoised): the features are those of the lens rays.
+    void render_lens_denoised(const PtLens& lens, uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, std::vector<Vector3>* noisy = nullptr,
+                              int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtDenoise d{};
+        if (dn) d = *dn; else pt_default_denoise(&d);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3), raw(noisy ? n * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_lens_denoised(ctx_, &camera_.pod(), &lens, &p, feature_samples, &d, lin.data(), rgba.data(), noisy ? raw.data() : nullptr,
+                                      nullptr));
+        unpack(lin, rgba);
+        if (noisy) {
+            noisy->resize(n);
+            for (size_t i = 0; i < n; ++i) (*noisy)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+        }
+    }
     // render_denoised() that traces its paths at lo_width x lo_height and reconstructs the camera's size under the full-size
     // first-hit features (pt_render_denoised_upsampled; up: pt_default_upsample when null).  data / luminance_data hold the
     // full-size film; lo (optional, y*lo_width+x) receives the denoised low film.

@@ -139,6 +139,14 @@ pub const PT_CURVE_ACES: u32 = 2;
 pub const PT_TRANSFER_SQRT: u32 = 0;
 pub const PT_TRANSFER_SRGB: u32 = 1;
 
+/// pt_render_lens_device: the thin lens beside the camera (include/pathtrace_amd.h); aperture 0 = pinhole.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtLens {
+    pub aperture: f64,
+    pub focus_distance: f64,
+}
+
 /// pt_upsample_device: the edge-stopping weights of feature-guided upsampling (include/pathtrace_amd.h).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -263,6 +271,8 @@ pub struct PtShapeIn {
     pub regen_workgroups: u32,
     pub in_order: u32,
     pub capturing: u32,
+    pub inject_spp: u32,
+    pub reserved: u32,
 }
 /// The sizing of a render (`csrc/pt_shape.h`: `Form`, `Shape`); `job` goes to `pt_debug_sched_render` as it is.
 #[repr(C)]
@@ -405,6 +415,13 @@ extern "C" {
     pub fn pt_upsample_device(ctx: *mut PtContext, lo_width: u32, lo_height: u32, d_lo_linear: *const f32, d_lo_features: *const f32, width: u32, height: u32, d_features: *const f32, up: *const PtUpsample, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
     pub fn pt_upsample_host(lo_width: u32, lo_height: u32, lo_linear: *const f32, lo_features: *const f32, width: u32, height: u32, features: *const f32, up: *const PtUpsample, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_denoised_upsampled(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, lo_width: u32, lo_height: u32, feature_samples: u32, dn: *const PtDenoise, up: *const PtUpsample, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_lo_linear: *mut f32, out_features: *mut f32) -> c_int;
+    pub fn pt_default_lens(out: *mut PtLens);
+    pub fn pt_render_lens_device(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, params: *const PtRenderParams, d_linear_rgb: *mut f32, d_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_lens_host(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, params: *const PtRenderParams, out_linear_rgb: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_features_lens_device(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, params: *const PtRenderParams, n_samples: u32, d_features: *mut f32) -> c_int;
+    pub fn pt_render_lens_denoised(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
+    pub fn pt_debug_lens_rays(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, xys: *const u32, n: u32, exact_math: u32, out8: *mut f32) -> c_int;
+    pub fn pt_debug_lens_setup(cam: *const PtCamera, lens: *const PtLens, out7: *mut f32) -> c_int;
     pub fn pt_default_gradient(out: *mut PtGradient);
     pub fn pt_temporal_gradient_device(ctx: *mut PtContext, cam: *const PtCamera, prev_params: *const PtRenderParams, seed: u32, d_prev_linear: *const f32, g: *const PtGradient, alpha_min: f32, d_alpha: *mut f32) -> c_int;
     pub fn pt_debug_gradient_strata(ctx: *mut PtContext, width: u32, height: u32, out_xy: *mut u32, out_film: *mut f32, out_rec: *mut f64) -> c_int;
