@@ -33,11 +33,14 @@ Params make_params(const PtRenderParams* p) {
     return q;
 }
 
+// lens: null = the pinhole; else the frame of a thin lens (lens_frame), given to render_pixel in R
 template <class R>
 int render_impl(const PtCamera* pc, const PtObject* objs, uint32_t n, const PtRenderParams* pp, int form, int threads,
-                double* out_lin, uint8_t* out_rgba, uint64_t* out_counters) {
+                double* out_lin, uint8_t* out_rgba, uint64_t* out_counters, const LensFrame* lens = nullptr) {
     Scene<R> scene = build_scene<R>(objs, n);
     Camera<R> cam = make_camera<R>(pc);
+    const Lens<R> lens_r = lens ? make_lens<R>(*lens) : Lens<R>();
+    const Lens<R>* lp = lens ? &lens_r : nullptr;
     Params prm = make_params(pp);
     std::vector<uint32_t> rows = tile_rows(pc->height, pp->band_rows, pp->band_index, pp->band_count);
     const uint32_t W = pc->width;
@@ -56,7 +59,7 @@ int render_impl(const PtCamera* pc, const PtObject* objs, uint32_t n, const PtRe
                 uint32_t yl = (uint32_t)(i / W), x = (uint32_t)(i % W);
                 uint32_t y = rows[yl];
                 double lin[3]; uint8_t rg[4];
-                render_pixel<R>(scene, cam, prm, (Form)form, x, y, pp->spp, pp->spp_offset, lin, rg, cn);
+                render_pixel<R>(scene, cam, prm, (Form)form, x, y, pp->spp, pp->spp_offset, lin, rg, cn, lp);
                 if (out_lin) { out_lin[i * 3] = lin[0]; out_lin[i * 3 + 1] = lin[1]; out_lin[i * 3 + 2] = lin[2]; }
                 if (out_rgba) std::memcpy(out_rgba + i * 4, rg, 4);
             }
@@ -343,9 +346,11 @@ extern "C" int orc_trace_path(const PtCamera* pc, const PtObject* objs, uint32_t
 // null); out_samples n*spp*3 (may be null) in sample order.  The replay tool of the full-size parity tests.
 template <class R>
 static void render_pixels_impl(const PtCamera* pc, const PtObject* objs, uint32_t nobj, const PtRenderParams* pp, int form,
-                               const uint32_t* xy, uint32_t n, double* out_lin, double* out_samples) {
+                               const uint32_t* xy, uint32_t n, double* out_lin, double* out_samples, const LensFrame* lens = nullptr) {
     Scene<R> scene = build_scene<R>(objs, nobj);
     Camera<R> cam = make_camera<R>(pc);
+    const Lens<R> lens_r = lens ? make_lens<R>(*lens) : Lens<R>();
+    const Lens<R>* lp = lens ? &lens_r : nullptr;
     Params prm = make_params(pp);
     Counters cn;
     for (uint32_t i = 0; i < n; ++i) {
@@ -353,7 +358,7 @@ static void render_pixels_impl(const PtCamera* pc, const PtObject* objs, uint32_
         double acc[3] = {0, 0, 0};
         for (uint32_t s = 0; s < pp->spp; ++s) {
             double lin[3]; uint8_t rg[4];
-            render_pixel<R>(scene, cam, prm, (Form)form, x, y, 1, pp->spp_offset + s, lin, rg, cn);   // one sample: mean = the sample
+            render_pixel<R>(scene, cam, prm, (Form)form, x, y, 1, pp->spp_offset + s, lin, rg, cn, lp);   // one sample: mean = the sample
             if (out_samples) std::memcpy(out_samples + ((size_t)i * pp->spp + s) * 3, lin, sizeof lin);
             for (int k = 0; k < 3; ++k) acc[k] += lin[k];
         }
@@ -365,6 +370,58 @@ extern "C" int orc_render_pixels(const PtCamera* cam, const PtObject* objs, uint
     if (!cam || !objs || !p || p->spp == 0 || (n && !xy)) return 1;
     if (precision == 64) render_pixels_impl<double>(cam, objs, nobj, p, form, xy, n, out_lin, out_samples);
     else render_pixels_impl<float>(cam, objs, nobj, p, form, xy, n, out_lin, out_samples);
+    return 0;
+}
+
+// ------------------------------------------------------------------ thin lens (pt_oracle.hpp "thin lens")
+// Every entry answers the lens_frame code (0 ok, 1 aperture, 2 focus_distance, 3 degenerate camera) before it writes anything.
+// out7 = Lu3, Lv3, inv_phi rounded to f32: the words the device receives.
+extern "C" int orc_lens_setup(const PtCamera* pc, const PtLens* ln, float* out7) {
+    if (!pc || !ln || !out7) return -1;
+    LensFrame f;
+    if (int rc = lens_frame(*pc, *ln, f)) return rc;
+    for (int k = 0; k < 3; ++k) { out7[k] = (float)f.lu[k]; out7[3 + k] = (float)f.lv[k]; }
+    out7[6] = (float)f.inv_phi;
+    return 0;
+}
+// xys n*3 = (x, y film row top-down, sample) -> out n*8 = o'3, d'3 (unit), dx, dy
+template <class R> static void lens_rays_batch(const PtCamera* pc, const LensFrame& f, uint32_t n, const uint32_t* xys, double* out) {
+    const Camera<R> cam = make_camera<R>(pc);
+    const Lens<R> L = make_lens<R>(f);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t x = xys[3 * i], y = xys[3 * i + 1];
+        Draws dr{{x, y}, xys[3 * i + 2]};
+        uint32_t dc[4];
+        dr.block(DEPTH_CAMERA, 0, dc);
+        R dx, dy;
+        const Ray<R> r = lens_ray<R>(cam, L, x, cam.height - 1 - y, dc, &dx, &dy);
+        const double v[8] = {r.origin.x, r.origin.y, r.origin.z, r.direction.x, r.direction.y, r.direction.z, (double)dx, (double)dy};
+        std::memcpy(out + 8 * (size_t)i, v, sizeof v);
+    }
+}
+extern "C" int orc_lens_rays(const PtCamera* pc, const PtLens* ln, int precision, uint32_t n, const uint32_t* xys, double* out) {
+    if (!pc || !ln || (n && (!xys || !out))) return -1;
+    LensFrame f;
+    if (int rc = lens_frame(*pc, *ln, f)) return rc;
+    if (precision == 64) lens_rays_batch<double>(pc, f, n, xys, out); else lens_rays_batch<float>(pc, f, n, xys, out);
+    return 0;
+}
+// orc_render / orc_render_pixels through the lens: bands, counters and per-sample radiances as there
+extern "C" int orc_render_lens(const PtCamera* cam, const PtLens* ln, const PtObject* objs, uint32_t n, const PtRenderParams* p,
+                               int precision, int form, int threads, double* out_lin, uint8_t* out_rgba, uint64_t* out_counters) {
+    if (!cam || !ln || !objs || !p || p->spp == 0) return -1;
+    LensFrame f;
+    if (int rc = lens_frame(*cam, *ln, f)) return rc;
+    if (precision == 64) return render_impl<double>(cam, objs, n, p, form, threads, out_lin, out_rgba, out_counters, &f);
+    return render_impl<float>(cam, objs, n, p, form, threads, out_lin, out_rgba, out_counters, &f);
+}
+extern "C" int orc_render_pixels_lens(const PtCamera* cam, const PtLens* ln, const PtObject* objs, uint32_t nobj, const PtRenderParams* p,
+                                      int precision, int form, const uint32_t* xy, uint32_t n, double* out_lin, double* out_samples) {
+    if (!cam || !ln || !objs || !p || p->spp == 0 || (n && !xy)) return -1;
+    LensFrame f;
+    if (int rc = lens_frame(*cam, *ln, f)) return rc;
+    if (precision == 64) render_pixels_impl<double>(cam, objs, nobj, p, form, xy, n, out_lin, out_samples, &f);
+    else render_pixels_impl<float>(cam, objs, nobj, p, form, xy, n, out_lin, out_samples, &f);
     return 0;
 }
 

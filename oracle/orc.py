@@ -80,6 +80,59 @@ def render_pixels(cam, objs, params, xy, precision=F64, form=RECURSIVE):
     return lin, smp
 
 
+class LensRefused(ValueError):
+    """A lens entry refused its lens or camera; `part` names what, in the words of the library's own refusals."""
+    PARTS = {1: "aperture", 2: "focus_distance", 3: "degenerate camera"}
+
+    def __init__(self, code):
+        self.code = code
+        self.part = self.PARTS.get(code, "null argument")
+        super().__init__(f"lens refused: {self.part}")
+
+
+def _lens_rc(rc):
+    if rc:
+        raise LensRefused(rc)
+
+
+def lens_setup(cam, lens):
+    """The lens frame of DESIGN.md 5m -> float32[7] = Lu3, Lv3, inv_phi as the device receives them; LensRefused otherwise."""
+    out = np.zeros(7, dtype=np.float32)
+    _lens_rc(lib().orc_lens_setup(C.byref(cam), C.byref(lens), _p(out)))
+    return out
+
+
+def lens_rays(cam, lens, xys, precision=F64):
+    """xys n x (x, y film row top-down, sample) -> float64[n, 8] = o'3, d'3 (unit), dx, dy (the lens point on the unit disc)"""
+    xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+    out = np.zeros((xys.shape[0], 8), dtype=np.float64)
+    _lens_rc(lib().orc_lens_rays(C.byref(cam), C.byref(lens), C.c_int(precision), C.c_uint32(xys.shape[0]), _p(xys), _p(out)))
+    return out
+
+
+def render_lens(cam, lens, objs, params, precision=F64, form=RECURSIVE, threads=1):
+    """render() through a thin lens -> (linear float64[rows,W,3], rgba uint8[rows,W,4], counters dict)"""
+    rows = lib().orc_tile_rows(C.c_uint32(cam.height), C.c_uint32(params.band_rows), C.c_uint32(params.band_index),
+                               C.c_uint32(params.band_count or 1))
+    lin = np.zeros((rows, cam.width, 3), dtype=np.float64)
+    rgba = np.zeros((rows, cam.width, 4), dtype=np.uint8)
+    cnt = np.zeros(4, dtype=np.uint64)
+    _lens_rc(lib().orc_render_lens(C.byref(cam), C.byref(lens), objs, C.c_uint32(len(objs)), C.byref(params), C.c_int(precision),
+                                   C.c_int(form), C.c_int(threads), _p(lin), _p(rgba), _p(cnt)))
+    return lin, rgba, {"vertices": int(cnt[0]), "shadow_rays": int(cnt[1]), "scans": int(cnt[2]), "max_depth": int(cnt[3])}
+
+
+def render_pixels_lens(cam, lens, objs, params, xy, precision=F64, form=RECURSIVE):
+    """render_pixels() through a thin lens -> (linear float64[n,3], samples float64[n,spp,3] in sample order)"""
+    xy = np.ascontiguousarray(xy, dtype=np.uint32).reshape(-1, 2)
+    n = xy.shape[0]
+    lin = np.zeros((n, 3), dtype=np.float64)
+    smp = np.zeros((n, params.spp, 3), dtype=np.float64)
+    _lens_rc(lib().orc_render_pixels_lens(C.byref(cam), C.byref(lens), objs, C.c_uint32(len(objs)), C.byref(params), C.c_int(precision),
+                                          C.c_int(form), _p(xy), C.c_uint32(n), _p(lin), _p(smp)))
+    return lin, smp
+
+
 def render_stdrng(cam, objs, params, threads=1):
     """orc.render(F64, RECURSIVE) drawing from the reference's own generator: one sequential StdRng (ChaCha12) stream
     per pixel, seeded (y << 32) | x (main.rs:51-52).  Restated from the published algorithm, unverified against the

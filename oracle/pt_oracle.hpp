@@ -197,6 +197,7 @@ struct PhiloxSampler {
     explicit PhiloxSampler(const Draws& d) : dr(d) {}
     void vertex(uint32_t depth) { dr.block(depth, BLK_SURFACE, ds); dr.block(depth, BLK_CHOICE, dc); }
     void camera(double& ox, double& oy) const { uint32_t c[4]; dr.block(DEPTH_CAMERA, 0, c); ox = u01(c[0]); oy = u01(c[1]); }
+    void camera_words(uint32_t c[4]) const { dr.block(DEPTH_CAMERA, 0, c); }      // the same block, all four words (thin lens)
     uint32_t light_index(uint32_t n) const { return (uint32_t)(((uint64_t)dc[DIM_LIGHT_INDEX] * n) >> 32); }
     double light_r1() const { return u01(ds[DIM_LIGHT_R1]); }
     double light_r2() const { return u01(ds[DIM_LIGHT_R2]); }
@@ -238,6 +239,7 @@ template <> struct Ar<double> {
     static double msub(double a, double b, double c, double d) { return a * b - c * d; }  // math.rs:31-33
     static double mad(double a, double b, double c) { return a * b + c; }
     static double rcp_div(double num, double den) { return num / den; }
+    static double div(double a, double b) { return a / b; }
     static void sincos2pi(double u, double& s, double& c) {
         double phi = 2.0 * 3.14159265358979323846 * u;   // "2.0 * PI * r" e.g. material.rs:103
         s = std::sin(phi); c = std::cos(phi);
@@ -253,6 +255,8 @@ template <> struct Ar<float> {
     // x / s is evaluated as x * (1/s) with an IEEE reciprocal (one division per
     // vector instead of three).
     static float rcp_div(float num, float den) { return num * (1.0f / den); }
+    // a scalar quotient is one IEEE division (the device's exact-mode pt_div)
+    static float div(float a, float b) { return a / b; }
     // sin/cos(2*pi*u), u in (0,1): quadrant k = rint(4u), r = u - k/4 in [-1/8,1/8],
     // t = 2*pi*r in [-pi/4,pi/4], cephes single-precision kernels, then rotate.
     static void sincos2pi(float u, float& s, float& c) {
@@ -361,11 +365,12 @@ template <class R> struct Camera {
     V3<R> origin, lower_left, horizontal, vertical;
     uint32_t width, height;
     // camera.rs:139-147
-    Ray<R> get_ray_with_offset(uint32_t x, uint32_t y, R ox, R oy) const {
+    Ray<R> get_ray_with_offset(uint32_t x, uint32_t y, R ox, R oy) const { return Ray<R>(origin, dir_with_offset(x, y, ox, oy)); }
+    // its direction before Ray::new normalises it (camera.rs:140-144)
+    V3<R> dir_with_offset(uint32_t x, uint32_t y, R ox, R oy) const {
         R u = ((R)x + ox) / (R)(width - 1);
         R v = ((R)y + oy) / (R)(height - 1);
-        V3<R> dir = lower_left + horizontal * u + vertical * v - origin;
-        return Ray<R>(origin, dir);
+        return lower_left + horizontal * u + vertical * v - origin;
     }
 };
 
@@ -400,6 +405,69 @@ inline void camera_look_at(const double o[3], const double tgt[3], const double 
     const V3<double> vv[4] = {origin, llc, hor, ver};
     for (int i = 0; i < 4; ++i) { f[i][0] = vv[i].x; f[i][1] = vv[i].y; f[i][2] = vv[i].z; }
     out->width = wd; out->height = h;
+}
+
+// ------------------------------------------------------------------ thin lens
+// Not in the reference, whose camera is a pinhole: the project's own rule, stated a second time here from the text of
+// DESIGN.md 5m and from nothing of the product's (pathtrace_amd/csrc/pt_lens.h is not included).
+//   Frame, f64, from the PtCamera:  C = lower_left + horizontal/2 + vertical/2 - origin,  D = |C|,
+//     U = horizontal/|horizontal|,  V = vertical/|vertical|,  inv_phi = D / focus_distance,  Lu = (aperture/2) U,  Lv = (aperture/2) V.
+//     Refused, in this order: an aperture that is negative or not finite; a focus_distance that is not finite or not > 0; a
+//     camera whose D or an axis has length 0 or is not finite, or whose origin is not finite.
+//     Real=float receives Lu, Lv and inv_phi rounded to f32 (what the device is handed); Real=double keeps them as they are.
+//   Sample: words 2 and 3 of the ONE camera block (DEPTH_CAMERA, block 0) whose words 0 and 1 are the pixel jitter:
+//     (a, b) = 2 u01 - 1 (exact in f32, never 0); the concentric map with the angle in revolutions
+//       |a| > |b|: r = a, rev = (b/a)/8      else: r = b, rev = 1/4 - (a/b)/8      (dx, dy) = (r cos, r sin) of 2 pi rev
+//     l = dx Lu + dy Lv,   o' = origin + l,   d' = dir - l inv_phi   (dir: the pinhole direction before it is normalised),
+//     and Ray::new normalises d' once, as it does the pinhole's.
+// Every statement is its own rounding: products and sums are written apart and the build is -ffp-contract=off, so neither
+// instantiation fuses a multiply into an add here (the rule asks for none across its statements).
+struct LensFrame { double lu[3], lv[3], inv_phi; };
+enum { LENS_OK = 0, LENS_BAD_APERTURE = 1, LENS_BAD_FOCUS = 2, LENS_BAD_CAMERA = 3 };
+inline int lens_frame(const PtCamera& c, const PtLens& ln, LensFrame& out) {
+    if (!std::isfinite(ln.aperture) || ln.aperture < 0.0) return LENS_BAD_APERTURE;
+    if (!std::isfinite(ln.focus_distance) || ln.focus_distance <= 0.0) return LENS_BAD_FOCUS;
+    const V3<double> o(c.origin[0], c.origin[1], c.origin[2]), ll(c.lower_left[0], c.lower_left[1], c.lower_left[2]);
+    const V3<double> hor(c.horizontal[0], c.horizontal[1], c.horizontal[2]), ver(c.vertical[0], c.vertical[1], c.vertical[2]);
+    const V3<double> axis = ll + hor / 2.0 + ver / 2.0 - o;
+    const double D = axis.length(), h = hor.length(), v = ver.length();
+    if (!std::isfinite(D) || !std::isfinite(h) || !std::isfinite(v) || D <= 0.0 || h <= 0.0 || v <= 0.0) return LENS_BAD_CAMERA;
+    if (!std::isfinite(o.x) || !std::isfinite(o.y) || !std::isfinite(o.z)) return LENS_BAD_CAMERA;
+    const V3<double> lu = (hor / h) * (ln.aperture / 2.0), lv = (ver / v) * (ln.aperture / 2.0);
+    out.lu[0] = lu.x; out.lu[1] = lu.y; out.lu[2] = lu.z;
+    out.lv[0] = lv.x; out.lv[1] = lv.y; out.lv[2] = lv.z;
+    out.inv_phi = D / ln.focus_distance;
+    return LENS_OK;
+}
+template <class R> struct Lens { V3<R> lu, lv; R inv_phi; };
+template <class R> inline Lens<R> make_lens(const LensFrame& f) {          // R = float: the one rounding to f32
+    Lens<R> l;
+    l.lu = V3<R>((R)f.lu[0], (R)f.lu[1], (R)f.lu[2]);
+    l.lv = V3<R>((R)f.lv[0], (R)f.lv[1], (R)f.lv[2]);
+    l.inv_phi = (R)f.inv_phi;
+    return l;
+}
+// the lens point of the camera block's words 2 and 3, on the unit disc
+template <class R> inline void lens_point(uint32_t w2, uint32_t w3, R& dx, R& dy) {
+    const R a = R(2) * (R)u01(w2) - R(1), b = R(2) * (R)u01(w3) - R(1);
+    R r, rev;
+    if (std::fabs(a) > std::fabs(b)) { r = a; rev = R(0.125) * Ar<R>::div(b, a); }
+    else { r = b; rev = R(0.25) - R(0.125) * Ar<R>::div(a, b); }
+    R s, c;
+    Ar<R>::sincos2pi(rev, s, c);
+    dx = r * c; dy = r * s;
+}
+// the lens ray of camera pixel (x, y) -- y the CAMERA row, as get_ray_with_offset takes it -- from the block's four words
+template <class R>
+inline Ray<R> lens_ray(const Camera<R>& cam, const Lens<R>& L, uint32_t x, uint32_t y, const uint32_t dc[4], R* out_dx = nullptr,
+                       R* out_dy = nullptr) {
+    const V3<R> dir = cam.dir_with_offset(x, y, (R)u01(dc[0]), (R)u01(dc[1]));
+    R dx, dy;
+    lens_point<R>(dc[2], dc[3], dx, dy);
+    if (out_dx) *out_dx = dx;
+    if (out_dy) *out_dy = dy;
+    const V3<R> l = L.lu * dx + L.lv * dy;
+    return Ray<R>(cam.origin + l, dir - l * L.inv_phi);
 }
 
 // ------------------------------------------------------------------ HitRecord (base.rs:6-34)
@@ -1258,14 +1326,22 @@ inline void film_pixel(const double acc[3], uint32_t spp, double out_lin[3], uin
 }
 template <class R>
 inline void render_pixel(const Scene<R>& w, const Camera<R>& cam, const Params& p, Form form, uint32_t x, uint32_t y,
-                         uint32_t spp, uint32_t spp_offset, double out_lin[3], uint8_t out_rgba[4], Counters& cn) {
+                         uint32_t spp, uint32_t spp_offset, double out_lin[3], uint8_t out_rgba[4], Counters& cn,
+                         const Lens<R>* lens = nullptr) {
     double acc[3] = {0, 0, 0};
     for (uint32_t s = 0; s < spp; ++s) {                                               // world.rs:296
         Draws dr{{x, y}, spp_offset + s};                                              // main.rs:51
         PhiloxSampler sm(dr);
-        double ox, oy;
-        sm.camera(ox, oy);
-        Ray<R> ray = cam.get_ray_with_offset(x, cam.height - 1 - y, (R)ox, (R)oy);     // world.rs:297-299
+        Ray<R> ray;
+        if (lens) {                                                                    // thin lens: the same block, four words
+            uint32_t dc[4];
+            sm.camera_words(dc);
+            ray = lens_ray(cam, *lens, x, cam.height - 1 - y, dc);
+        } else {
+            double ox, oy;
+            sm.camera(ox, oy);
+            ray = cam.get_ray_with_offset(x, cam.height - 1 - y, (R)ox, (R)oy);        // world.rs:297-299
+        }
         V3<R> c;
         if (form == FORM_ITERATIVE) c = ray_color_iter(w, p, ray, dr, cn);
         else if (p.integrator == PT_INTEGRATOR_MIS) c = ray_color_mis_rec(w, p, ray, 0, sm, V3<R>::one(), cn);

@@ -11,14 +11,18 @@ LW = np.array([0.2126, 0.7152, 0.0722])
 B3 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16])
 
 
-def sample_records(orc, objs, cam, sample, precision, t_min=0.001):
-    """Records (albedo rgb, emitter, normal xyz, depth) of sample `sample` of every pixel -> (f64[H,W,8], ids[H,W])."""
+def sample_records(orc, objs, cam, sample, precision, t_min=0.001, lens=None):
+    """Records (albedo rgb, emitter, normal xyz, depth) of sample `sample` of every pixel -> (f64[H,W,8], ids[H,W]).
+    lens: a PtLens -- the records of the sample's lens rays (orc.lens_rays: pt_render_features_lens_device)."""
     W, H = cam.width, cam.height
     ys, xs = np.mgrid[0:H, 0:W]
     xy = np.stack([xs.ravel(), ys.ravel()], 1)
-    off = np.array([[orc.u01(w) for w in orc.philox((int(x), int(y), int(sample), 0xFFFFFFFF), (0, 0))[:2]] for x, y in xy])
-    flipped = np.stack([xy[:, 0], H - 1 - xy[:, 1]], 1)             # world.rs:299 hands the camera row H-1-y
-    rays = orc.camera_rays(cam, flipped, off, precision)
+    if lens is not None:
+        rays = orc.lens_rays(cam, lens, np.concatenate([xy, np.full((len(xy), 1), sample)], 1), precision)[:, :6]
+    else:
+        off = np.array([[orc.u01(w) for w in orc.philox((int(x), int(y), int(sample), 0xFFFFFFFF), (0, 0))[:2]] for x, y in xy])
+        flipped = np.stack([xy[:, 0], H - 1 - xy[:, 1]], 1)         # world.rs:299 hands the camera row H-1-y
+        rays = orc.camera_rays(cam, flipped, off, precision)
     ids, ts, pn, _ = orc.hit_scene(objs, rays, t_min, float("inf"), precision)
     tag = np.array([o.mat_tag for o in objs])
     mat = np.array([list(o.mat) for o in objs])
@@ -38,11 +42,12 @@ def sample_records(orc, objs, cam, sample, precision, t_min=0.001):
     return rec.reshape(H, W, 8), ids.reshape(H, W)
 
 
-def features_f32(orc, objs, cam, spp_offset, n_samples, t_min=0.001):
-    """pt_render_features_device in exact arithmetic: f32 records summed in sample order, then / n_samples (f32)."""
+def features_f32(orc, objs, cam, spp_offset, n_samples, t_min=0.001, lens=None):
+    """pt_render_features_device (lens: pt_render_features_lens_device) in exact arithmetic: f32 records summed in sample
+    order, then / n_samples (f32)."""
     acc = np.zeros((cam.height, cam.width, 8), dtype=np.float32)
     for s in range(n_samples):
-        rec, _ = sample_records(orc, objs, cam, spp_offset + s, orc.F32, t_min)
+        rec, _ = sample_records(orc, objs, cam, spp_offset + s, orc.F32, t_min, lens)
         acc = acc + rec.astype(np.float32)
     return acc / np.float32(n_samples)
 

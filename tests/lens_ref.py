@@ -35,13 +35,14 @@ def cam_fields(cam, f32=False):
     return [v.astype(np.float32).astype(np.float64) for v in out] if f32 else out
 
 
-def setup(cam, aperture, focus_distance):
-    """The host side: -> float32[7] = Lu3, Lv3, inv_phi"""
+def setup(cam, aperture, focus_distance, f32=True):
+    """The host side: -> float32[7] = Lu3, Lv3, inv_phi (f32=False: the f64 values before that rounding)"""
     org, ll, hor, ver = cam_fields(cam)
     c = ll + hor / 2.0 + ver / 2.0 - org
     d = np.sqrt((c * c).sum())
     u, v = hor / np.sqrt((hor * hor).sum()), ver / np.sqrt((ver * ver).sum())
-    return np.concatenate([(aperture / 2.0) * u, (aperture / 2.0) * v, [d / focus_distance]]).astype(np.float32)
+    out = np.concatenate([(aperture / 2.0) * u, (aperture / 2.0) * v, [d / focus_distance]])
+    return out.astype(np.float32) if f32 else out
 
 
 def disc(w2, w3):
@@ -53,12 +54,13 @@ def disc(w2, w3):
     return r * np.cos(phi), r * np.sin(phi)
 
 
-def rays(cam, out7, xys):
+def rays(cam, out7, xys, f32=True):
     """The lens rays of xys = n x (x, y film row top-down, sample) under the device's own words out7 (Lu3, Lv3, inv_phi).
+    f32=False: the camera's fields as the PtCamera holds them, f64 (with setup(..., f32=False): the rule with no f32 anywhere).
     -> dict: o f64[n,3], d f64[n,3] (unit), dx, dy, dir (the pinhole direction before it is normalised), focus (the point
     origin + dir / inv_phi every lens ray of the sample passes)"""
     xys = np.asarray(xys, dtype=np.uint64).reshape(-1, 3)
-    org, ll, hor, ver = cam_fields(cam, f32=True)
+    org, ll, hor, ver = cam_fields(cam, f32=f32)
     out7 = np.asarray(out7, dtype=np.float64)
     lu, lv, inv_phi = out7[0:3], out7[3:6], out7[6]
     w = words(xys[:, 0], xys[:, 1], xys[:, 2])

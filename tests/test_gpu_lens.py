@@ -1,7 +1,8 @@
 """The thin-lens camera (pt_render_lens_device and friends) on the GPU: the rays against the numpy restatement
 (tests/lens_ref.py), aperture 0 against the pinhole entries bit for bit (the test that pins the whole route of given paths:
 slots, sample indices, batching, bands, resolve), batching and linearity with an open lens, the coverage of a defocused sphere
-against the restatement's own intersections, and the one-call entry against its parts."""
+against the restatement's own intersections, and the one-call entry against its parts.
+Parity of the open lens with the oracle (films, bands, batches, depth limits, features): tests/test_gpu_lens_parity.py."""
 import numpy as np
 import pytest
 
