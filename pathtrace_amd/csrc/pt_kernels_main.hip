@@ -283,6 +283,16 @@ k_paths(BounceArgs a) {
 //     after vertex_finish.  When the loop ends, the terms still pending get a visibility scan of their own before the hand-over,
 //     so the state a continuation launch resumes is what it always was.  wave_shadow counts a ray where its vertex asks for it.
 //     BRDF-only instances have no visibility ray: one scan per iteration, as before.
+//   * First vertex at the fill (DENSE0: the MIS diffuse instances, image and LIST).  A lane fresh from the ring has nothing pending:
+//     in the joint scan its ray A is empty, and one lane in 4.9 is in that state.  So the chunk a wave takes from the batch runs its
+//     first vertex on the spot -- 64 camera paths, a one-ray scan, vertex_begin, vertex_end<DEFER>: the main loop's functions and
+//     arguments, the same bits -- and the ring holds paths at their SECOND vertex (19 words, DenseWave).  A path that ends there by
+//     miss, emitter or roulette stores its radiance at once and never enters the ring (it counts as taken and finished); one that
+//     ends with its term pending enters with depth 0 and takes a lane for one scan, as ever.  A chunk is taken only when lanes are
+//     vacant and the ring is empty, so the ring never holds more than one chunk's survivors (64 entries), and while the chunk's
+//     vertex runs the empty ring keeps twelve registers of every lane's own path.  LDS 25.6 KB per workgroup + the scene: six
+//     workgroups per CU for scenes up to 78 float4 (C2: 62); VALU per launch on C2 -4.8 %, C2 +5.0 %, C3 +5.2 % (docs/EXPERIMENTS.md).
+//     The other material sets keep the loop above: their entry would need the incoming eta, and they are at 95-96 VGPRs already.
 // Occupancy the variants are compiled for (pt_kernels.h: the host sizes the grid by it): the DIFFUSE variant needs 80 VGPRs
 // (6 waves per SIMD), the generic ones 95-96 (5; reached only with PtTuning.level0_form = 2); none spills.
 // Finished samples (stats[4]; pt_sync compares the sum with pixels x spp).  The queue-form kernels count the lanes that write their
@@ -304,15 +314,23 @@ constexpr uint32_t kRegenBlock = PT_REGEN_BLOCK;
 // LIST (pt_render_adaptive's passes): the batch's paths come from a pixel list -- list slot pid % np, sample pid / np (the
 // sample-major order of every list render); film slot i = (tile_row << 16) | x of a 65536-wide film, camera pixel and RNG
 // key = pixels[i], like pixel_key<true>.
-template <bool MIS, int DIFFUSE, bool LIST = false>
-__global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenWavesDiffuse : kRegenWavesGeneric) k_paths_regen(BounceArgs a) {
+// DENSE0 (the body's own parameter; the kernel below chooses it): a path's first vertex runs where its chunk is taken from the
+// batch, all 64 lanes on camera paths with a ONE-ray scan, instead of in the main loop, where a lane fresh from the ring occupies
+// a slot of the joint scan with an empty ray A.  The ring then holds paths at their second vertex (DenseWave, pt_kernels_vertex.h).
+template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0>
+PT_DEV void paths_regen_body(const BounceArgs& a) {
+    // DENSE0 rebuilds a popped path's incoming eta (1) and its pending throughput (1, 1, 1) instead of storing them: true of a
+    // first vertex on a surface without refraction only
+    static_assert(!DENSE0 || (MIS && DIFFUSE == kMatsDiffuse), "the dense first vertex is written for the MIS diffuse instances");
     extern __shared__ float4 lds[];
-    __shared__ float4 s_pool_d[kRegenBlock / 64][kPool];      // (d.x, d.y, d.z, bits(tile_row << 16 | x))
-    __shared__ uint32_t s_pool_s[kRegenBlock / 64][kPool];    // s_local << 16 (depth 0)
+    __shared__ float4 s_pool_d[DENSE0 ? 1 : kRegenBlock / 64][DENSE0 ? 1 : kPool];      // (d.x, d.y, d.z, bits(tile_row << 16 | x))
+    __shared__ uint32_t s_pool_s[DENSE0 ? 1 : kRegenBlock / 64][DENSE0 ? 1 : kPool];    // s_local << 16 (depth 0)
     __shared__ WgTotals s_totals;
     // MIS: the pending NEE term of every lane (Pending::beta, ::direct) sits here during the joint scan instead of in six registers
     // (2 KB per wave; a lane reads only what it wrote itself: no barrier)
-    __shared__ float4 s_park[MIS ? kRegenBlock / 64 : 1][2][64];
+    __shared__ float4 s_park[MIS && !DENSE0 ? kRegenBlock / 64 : 1][2][DENSE0 ? 1 : 64];
+    // DENSE0: ring entries (paths at their second vertex) and the parked terms (six floats per lane), per wave
+    __shared__ DenseWave s_dense[DENSE0 ? kRegenBlock / 64 : 1];
     if (threadIdx.x == 0u) wg_totals_init(s_totals);
     // Spare workgroups (BounceArgs.posted): in a sequence of overlapping launches only the first core_blocks of a launch work -- two
     // launches then sit side by side and the third fills the slots the first frees while it runs dry -- but the LAST launches of
@@ -329,8 +347,10 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
     const uint32_t wib = threadIdx.x >> 6;
     float4* const pool_d = s_pool_d[wib];
     uint32_t* const pool_s = s_pool_s[wib];
-    float4* const park0 = &s_park[MIS ? wib : 0u][0][lane];
-    float4* const park1 = &s_park[MIS ? wib : 0u][1][lane];
+    float4* const park0 = DENSE0 ? &s_dense[DENSE0 ? wib : 0u].park0[lane] : &s_park[MIS && !DENSE0 ? wib : 0u][0][DENSE0 ? 0u : lane];
+    float4* const park1 = &s_park[MIS && !DENSE0 ? wib : 0u][1][DENSE0 ? 0u : lane];
+    float2* const park1d = &s_dense[DENSE0 ? wib : 0u].park1[lane];
+    DenseWave& dw = s_dense[DENSE0 ? wib : 0u];
     const uint32_t n_first = a.n_first;
     const uint32_t n_chunks = (n_first + 63u) >> 6;
     const uint32_t W = a.film_w;
@@ -356,11 +376,15 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
     // a finished path: radiance to its sample slot, the lane parked until it gets its next path (end of the batch: for good)
     auto park = [&]() {
         *park0 = make_float4(pd.beta.x, pd.beta.y, pd.beta.z, pd.direct.x);
-        *park1 = make_float4(pd.direct.y, pd.direct.z, 0.0f, 0.0f);
+        if constexpr (DENSE0) *park1d = make_float2(pd.direct.y, pd.direct.z);
+        else *park1 = make_float4(pd.direct.y, pd.direct.z, 0.0f, 0.0f);
     };
     auto unpark = [&]() {
         asm volatile("" ::: "memory");          // a real read after the scan, not the values kept alive across it
-        const float4 k0 = *park0, k1 = *park1;
+        const float4 k0 = *park0;
+        float2 k1;
+        if constexpr (DENSE0) k1 = *park1d;
+        else { const float4 k = *park1; k1 = make_float2(k.x, k.y); }
         pd.beta = mk(k0.x, k0.y, k0.z); pd.direct = mk(k0.w, k1.x, k1.y);
     };
     auto retire = [&]() {
@@ -377,24 +401,118 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
 #ifdef PT_DRAIN_TIMING
         if (exhausted && t_exhausted == 0ull) t_exhausted = wall_clock64();
 #endif
+        // the batch's next chunk for this wave (false: there is none left)
+        auto take_chunk = [&](uint32_t& chunk) {
+            if (st_next < a.regen_static) {            // dealt round-robin, like pass 0 of k_paths
+                chunk = st_next; st_next += nw;
+                return true;
+            }
+            // the shared rest: chunk regen_static + ticket * kRegenCounters + c from counter c; a wave starts at the
+            // counter of its workgroup and moves on to the next one when that is used up
+            for (;;) {
+                uint32_t got = 0;
+                if (lane == 0u) got = atomicAdd(a.chunk_counter + ctr * kRegenCounterStride, 1u);
+                chunk = a.regen_static + __builtin_amdgcn_readfirstlane(got) * kRegenCounters + ctr;
+                if (chunk < n_chunks) return true;
+                ctr = ctr + 1u == kRegenCounters ? 0u : ctr + 1u;
+                if (++ctr_dry == kRegenCounters) { exhausted = true; return false; }
+            }
+        };
+        if constexpr (DENSE0) {
+        // ---- lanes without a path take the ring's entries, in lane order; while some stay vacant, the batch's next chunk runs
+        // its first vertex here, all 64 lanes on camera paths (one-ray scan, vertex_begin, vertex_end<DEFER>: the main loop's
+        // functions and arguments at depth 0), and what goes on from there enters the (then empty) ring at depth 1.
+        for (;;) {
+            const bool vacant = !alive && !pd.on;
+            const unsigned long long need = __ballot(vacant);
+            const uint32_t r = lane_rank(need);
+            if (vacant && r < pool_cnt) {
+                const uint32_t e = pool_head + r;
+                const float4 e0 = dw.e4[0][e], e1 = dw.e4[1][e], e2 = dw.e4[2][e], e3 = dw.e4[3][e];
+                const uint32_t xy = dw.e1[1][e], sd = dw.e1[2][e];
+                p.o = mk(e0.x, e0.y, e0.z); p.d = mk(e0.w, e1.x, e1.y);
+                p.beta = mk(e1.z, e1.w, e2.x); p.pdf_prev = e2.y;
+                p.L = mk(0.f, 0.f, 0.f); p.eta_in = 1.0f;     // nothing was credited at the first vertex; no refracting surface
+                sdir = mk(e3.y, e3.z, e3.w); smax = __uint_as_float(dw.e1[0][e]);
+                p.yl = xy >> 16; p.px = xy & 0xFFFFu;
+                p.s_local = sd >> 16; p.depth = sd & 0xFFFFu;
+                alive = p.depth != 0u;                         // depth 0: the path ended at its first vertex, its term is still owed
+                pd.on = true; pd.beta = mk(1.f, 1.f, 1.f); pd.direct = mk(e2.z, e2.w, e3.x);
+                park();
+            }
+            const uint32_t n_need = (uint32_t)__popcll(need);
+            const uint32_t n_take = n_need < pool_cnt ? n_need : pool_cnt;
+            pool_head += n_take; pool_cnt -= n_take;
+            wave_taken += n_take;
+            if (n_need == n_take || exhausted) break;
+            uint32_t chunk;
+            if (!take_chunk(chunk)) break;
+            // (lanes stay vacant only when the ring ran empty: the chunk's entries start at slot 0 and never exceed 64)
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t pid = chunk * 64u + lane;
+            const uint32_t valid = n_first - chunk * 64u < 64u ? n_first - chunk * 64u : 64u;
+            const bool qa = lane < valid;
+            PathState q = parked_state();
+            uint32_t qkx = 0u, qpy = 0u;
+            if (qa) {
+                uint32_t pix;
+                divmod_magic(pid, a.np, a.np_magic, q.s_local, pix);
+                divmod_magic(pix, W, a.film_w_magic, q.yl, q.px);
+                if constexpr (LIST) { const uint2 k = a.pixels[pix]; qkx = k.x; qpy = k.y; }
+                else { qkx = q.px; qpy = image_row(a.tile, q.yl); }
+                camera_ray(a.cam, a.s_base + q.s_local, qkx, qpy, q.o, q.d);
+            }
+            // (every lane starts at the camera, so the origin stays wave-uniform through the scan; a lane past the chunk's end
+            // sends the parked direction from there, and whatever it hits is not looked at)
+            q.o = cam_o;
+            // The lanes' own paths wait in the empty ring meanwhile -- radiance, throughput, pdf, visibility ray: twelve registers
+            // the first vertex would otherwise push into scratch -- and come back before the chunk's entries are written.
+            dw.e4[0][lane] = make_float4(p.L.x, p.L.y, p.L.z, p.pdf_prev);
+            dw.e4[1][lane] = make_float4(p.beta.x, p.beta.y, p.beta.z, smax);
+            dw.e4[2][lane] = make_float4(sdir.x, sdir.y, sdir.z, 0.0f);
+            const uint32_t qsample = a.s_base + q.s_local;
+            int qid; float qt;
+            scan_closest<kModeLds, false>(sc, q.o, q.d, a.t_min, kInf, qid, qt);
+            Vertex qv;
+            vertex_begin<MIS, DIFFUSE>(sc, q, qa, qid, qt, qsample, qkx, qpy, qv);
+            wave_vertices += valid;
+            wave_shadow += (uint32_t)__popcll(__ballot(qv.need_shadow));
+            Pending qpd;
+            qpd.on = false; qpd.beta = mk(0.f, 0.f, 0.f); qpd.direct = mk(0.f, 0.f, 0.f);
+            const bool qalive = vertex_end<MIS, DIFFUSE, true, true>(sc, q, qv, false, qsample, qkx, qpy, a.min_depth, a.max_depth, &qpd);
+            // miss, emitter, roulette: the sample is finished (depth 0: dmax stays); it never was in the ring, so it counts here
+            const bool qdone = qa && !qalive && !qpd.on;
+            if (qdone) a.lsamp[q.s_local * a.np + q.yl * W + q.px] = Rgb{q.L.x, q.L.y, q.L.z};
+            wave_taken += (uint32_t)__popcll(__ballot(qdone));
+            {
+                asm volatile("" ::: "memory");          // a real read, not the values kept alive across the vertex
+                const float4 k0 = dw.e4[0][lane], k1 = dw.e4[1][lane], k2 = dw.e4[2][lane];
+                p.L = mk(k0.x, k0.y, k0.z); p.pdf_prev = k0.w;
+                p.beta = mk(k1.x, k1.y, k1.z); smax = k1.w;
+                sdir = mk(k2.x, k2.y, k2.z);
+            }
+            __builtin_amdgcn_wave_barrier();
+            const bool keep = qalive || qpd.on;
+            const unsigned long long km = __ballot(keep);
+            if (keep) {
+                const uint32_t e = lane_rank(km);
+                const f3 ld = qv.light_dir;
+                dw.e4[0][e] = make_float4(q.o.x, q.o.y, q.o.z, q.d.x);
+                dw.e4[1][e] = make_float4(q.d.y, q.d.z, q.beta.x, q.beta.y);
+                dw.e4[2][e] = make_float4(q.beta.z, q.pdf_prev, qpd.direct.x, qpd.direct.y);
+                dw.e4[3][e] = make_float4(qpd.direct.z, ld.x, ld.y, ld.z);
+                dw.e1[0][e] = __float_as_uint(qv.distance - a.t_min);
+                dw.e1[1][e] = (q.yl << 16) | q.px;
+                dw.e1[2][e] = (q.s_local << 16) | q.depth;
+            }
+            pool_head = 0u; pool_cnt = (uint32_t)__popcll(km);
+            __builtin_amdgcn_wave_barrier();
+        }
+        } else {
         // ---- keep at least one chunk of camera rays in the ring
         while (!exhausted && pool_cnt < 64u) {
             uint32_t chunk;
-            if (st_next < a.regen_static) {            // dealt round-robin, like pass 0 of k_paths
-                chunk = st_next; st_next += nw;
-            } else {
-                // the shared rest: chunk regen_static + ticket * kRegenCounters + c from counter c; a wave starts at the
-                // counter of its workgroup and moves on to the next one when that is used up
-                for (;;) {
-                    uint32_t got = 0;
-                    if (lane == 0u) got = atomicAdd(a.chunk_counter + ctr * kRegenCounterStride, 1u);
-                    chunk = a.regen_static + __builtin_amdgcn_readfirstlane(got) * kRegenCounters + ctr;
-                    if (chunk < n_chunks) break;
-                    ctr = ctr + 1u == kRegenCounters ? 0u : ctr + 1u;
-                    if (++ctr_dry == kRegenCounters) { exhausted = true; break; }
-                }
-                if (exhausted) break;
-            }
+            if (!take_chunk(chunk)) break;
             const uint32_t pid = chunk * 64u + lane;
             const uint32_t valid = n_first - chunk * 64u < 64u ? n_first - chunk * 64u : 64u;
             if (lane < valid) {
@@ -433,6 +551,7 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
             pool_head += n_take; pool_cnt -= n_take;
             wave_taken += n_take;
         }
+        }   // !DENSE0
         __builtin_amdgcn_wave_barrier();
         const uint32_t n_alive = (uint32_t)__popcll(__ballot(alive));
         // running dry (only once the batch is exhausted): hand the rest over.  A lane that still owes its ended path the NEE term
@@ -524,6 +643,11 @@ __global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenW
                                                                __uint_as_float((uint32_t)t_end), __uint_as_float(wave_vertices));
 #endif
     }
+}
+
+template <bool MIS, int DIFFUSE, bool LIST = false>
+__global__ void __launch_bounds__(kRegenBlock, DIFFUSE == kMatsDiffuse ? kRegenWavesDiffuse : kRegenWavesGeneric) k_paths_regen(BounceArgs a) {
+    paths_regen_body<MIS, DIFFUSE, LIST, MIS && DIFFUSE == kMatsDiffuse>(a);
 }
 
 static int scene_mode(const SceneView& sc, uint32_t accel) {

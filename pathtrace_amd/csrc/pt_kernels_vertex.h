@@ -305,5 +305,15 @@ PT_DEV void launch_shape(const BounceArgs& a, uint32_t nw, uint32_t& n_first, ui
 }
 // the regenerating kernels' per-wave ring of camera rays in LDS (k_paths_regen, k_paths_regen_split)
 constexpr uint32_t kPool = 128;            // ring entries per wave (>= 2 chunks: refilled whenever fewer than 64 are left)
+// k_paths_regen<.., DENSE0>: a wave's LDS.  A ring entry is a path AFTER its first vertex, 19 words: origin, direction,
+// throughput, sampling pdf, its pending NEE term, that term's visibility ray (direction, range), film position, sample | depth;
+// four 16-byte planes and three word planes.  At most one chunk's survivors are in the ring at a time (64 entries).  Behind them
+// the six parked floats of every lane.  6400 B per wave: with a scene of <= 78 float4 six workgroups still fit a CU's 160 KB.
+struct alignas(16) DenseWave {
+    float4 e4[4][64];
+    uint32_t e1[3][64];
+    float4 park0[64];
+    float2 park1[64];
+};
 
 }  // namespace PTK_IMPL
