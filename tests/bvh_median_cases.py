@@ -87,6 +87,70 @@ def median_order(g, cell, steps):
     return order.astype(np.uint32)
 
 
+# ---------------------------------------------------------------------------------------------------- the large counts
+# The sizes of the device-side build that decide which code a count reaches (tests/test_bvh_large_counts_cpu.py holds each to
+# the source, and the counts below to what they are there for).
+K_SORT_TILE = 2048           # pt_kernels.h kSortTile: pairs per workgroup and pass of the radix sort
+K_SORT_DIGITS = 256          # pt_kernels.h kSortDigits: histogram words per sort tile
+K_SCAN_BLOCK = 1024          # pt_film_bvh.h kScanBlock: k_bvh_sort_scan takes 4 * kScanBlock histogram words per loop iteration
+K_MEDIAN_TILE = 2048         # pt_bvh.h kMedianTile (T): steps above it go through the radix sort
+K_MEDIAN_CHUNK = 65536       # pt_bvh.h kMedianChunk: positions no step above T covers are cut into groups of at most this many
+
+SCAN_FULL = 32768            # 16 sort tiles: the scan's one iteration exactly full
+SCAN_CARRY = 32769           # 17 sort tiles: a second, partial iteration of the scan; the first median level above 4 passes
+MORTON_LARGE = [SCAN_FULL, SCAN_CARRY, 65537]                    # 65537: three scan iterations
+MEDIAN_LARGE = [SCAN_FULL, SCAN_CARRY, 65537, 131073, 262145]    # 131073: a gap of two chunks; 262145: four chunks, a 6-pass level
+MEDIAN_ONCE = 262145         # the slowest host reference: one rebuild, not two
+
+
+def sort_tiles(n):
+    return -(-n // K_SORT_TILE)
+
+
+def scan_iterations(n):
+    """loop iterations of k_bvh_sort_scan over the kSortDigits * tiles histogram words of one pass"""
+    return -(-(K_SORT_DIGITS * sort_tiles(n)) // (4 * K_SCAN_BLOCK))
+
+
+def index_bits(n):
+    bits = 0
+    while (1 << bits) < n:
+        bits += 1
+    return bits
+
+
+def device_levels(steps, n):
+    """The level loop of ptbvh::median_plan restated from the steps of pt.bvh_median_plan(n): for every level with a step above
+    T, in level order, a dict of
+      groups       [(start, is_step)] in position order: the steps above T, and between them the gaps cut at kMedianChunk
+      bits         the bits of a group number
+      passes       radix passes over the key (group, 16-bit cell or offset, object index): ceil((index_bits + 16 + bits) / 8)
+      longest_gap  the longest stretch of positions no step above T covers (0: none)
+      gap_chunks   the groups the longest gap is cut into"""
+    s = np.asarray(steps, dtype=np.int64).reshape(-1, 4)
+    out = []
+    for level in range(int(s[:, 0].max()) + 1 if len(s) else 0):
+        groups, gaps, at = [], [0], 0
+        for P, Q in s[s[:, 0] == level][:, 1:3].tolist() + [(n, n)]:      # (n, n): the gap behind the last step
+            if P < n and Q - P <= K_MEDIAN_TILE:
+                continue
+            if P == n and at == 0:
+                break                                            # no step of this level is above T
+            gaps.append(P - at)
+            groups += [(a, False) for a in range(at, P, K_MEDIAN_CHUNK)]
+            if P < n:
+                groups.append((P, True))
+            at = Q
+        if at == 0:
+            break
+        bits = 0
+        while (1 << bits) < len(groups):
+            bits += 1
+        out.append(dict(groups=groups, bits=bits, passes=-(-(index_bits(n) + 16 + bits) // 8), longest_gap=max(gaps),
+                        gap_chunks=-(-max(gaps) // K_MEDIAN_CHUNK)))
+    return out
+
+
 def equal_centres(pt, n):
     return spheres(pt, [(0.25, -0.5, -2.0)] * n)
 

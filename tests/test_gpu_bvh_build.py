@@ -1,9 +1,16 @@
 """pt_scene_rebuild on the GPU: the device-side build (k_bvh_morton, the radix sort, k_bvh_write_ids and the refit kernels)
 against its host reference (ptbvh::build_morton through pt_debug_bvh_morton_check) bit for bit, and the contract that the film
-never depends on the tree: hits and films over a Morton tree equal the linear scan's."""
+never depends on the tree: hits and films over a Morton tree equal the linear scan's.
+
+The counts go past one iteration of k_bvh_sort_scan (bvh_median_cases.MORTON_LARGE; tests/test_bvh_large_counts_cpu.py holds
+them to the tile sizes): 32 768 objects are 16 sort tiles, the scan's one iteration exactly full; 32 769 are 17, a second,
+partial iteration behind the carry; 65 537 take three.  With every centre equal at 32 769, all 17 tiles count into one digit
+and the order across tiles rests on the carried prefix alone.  Above 20 011 objects only the device build runs (no host-built
+tree before it), refits take one pose and hits 2 048 rays."""
 import numpy as np
 import pytest
 
+import bvh_median_cases as mc
 import bvh_refit_cases as rc
 from test_gpu_bvh import _rays
 from test_gpu_fuzz import random_scene
@@ -11,6 +18,8 @@ from test_gpu_fuzz import random_scene
 pytestmark = pytest.mark.gpu
 PT_ERR_INVALID_ARG, PT_ERR_UNSUPPORTED = 1, 5
 PT_ACCEL_LINEAR, PT_ACCEL_BVH, PT_ACCEL_AUTO = 0, 1, 2
+LARGE = ["s4_%d" % n for n in mc.MORTON_LARGE] + ["equal_centres_%d" % mc.SCAN_CARRY]
+CARRY = "s4_%d" % mc.SCAN_CARRY
 
 
 def _spheres(pt, centres, radii):
@@ -27,6 +36,9 @@ def scenes(pt):
     s["equal_centres"] = _spheres(pt, [(0.25, -0.5, -2.0)] * 37, np.linspace(0.05, 0.4, 37))
     rng = np.random.default_rng(20011)                                        # prime, ten sort tiles, above 16 384
     s["n20011"] = _spheres(pt, rng.uniform([-2, -2, -5], [2, 2, -1], (20011, 3)), rng.uniform(0.01, 0.05, 20011))
+    for n in mc.MORTON_LARGE:
+        s["s4_%d" % n] = pt.builtin_scene(4, n)
+    s["equal_centres_%d" % mc.SCAN_CARRY] = _spheres(pt, [(0.25, -0.5, -2.0)] * mc.SCAN_CARRY, np.linspace(0.05, 0.4, mc.SCAN_CARRY))
     return s
 
 
@@ -62,10 +74,12 @@ def _is_the_host_build(pt, ctx, want):
 
 
 # ------------------------------------------------------------------------------------------------ the tree, bit for bit
-@pytest.mark.parametrize("name", ["n0", "n1", "n4", "n5", "n17", "n65", "mixed200", "n1000", "equal_centres", "n20011"])
+@pytest.mark.parametrize("name", ["n0", "n1", "n4", "n5", "n17", "n65", "mixed200", "n1000", "equal_centres", "n20011"] + LARGE)
 def test_device_build_equals_the_host_build_bit_for_bit(pt, scenes, name):
     objs = scenes[name]
     want = pt.bvh_morton_check(objs)
+    if name.startswith("equal_centres_"):                # every key ties: a stable sort leaves the index order
+        assert len(np.unique(want["keys"])) == 1 and np.array_equal(want["order"], np.arange(len(objs)))
     c = pt.Context(0)                                    # a fresh context: no tree array exists yet
     try:
         c.upload(objs)
@@ -73,6 +87,8 @@ def test_device_build_equals_the_host_build_bit_for_bit(pt, scenes, name):
         _is_the_host_build(pt, c, want)
         c.scene_rebuild(objs)                            # the cached topology, the code words already in place
         _is_the_host_build(pt, c, want)
+        if name in LARGE:
+            return
         _host_tree(pt, c, objs)                          # a host-built tree before: its code words are another topology's
         assert c.bvh_cost()[2] == 0
         if len(objs) > 8:
@@ -84,15 +100,16 @@ def test_device_build_equals_the_host_build_bit_for_bit(pt, scenes, name):
 
 
 def test_rebuild_then_refits(pt, gpu_ctx, scenes):
-    for name in ("mixed200", "n1000"):
+    for name in ("mixed200", "n1000", CARRY):
         objs = scenes[name]
         rng = np.random.default_rng(3)
         base = rc.moved(pt, rng, objs)
+        poses = [rc.moved(pt, rng, objs)] if name == CARRY else [rc.moved(pt, rng, objs), rc.shifted(pt, objs, 1), rc.moved(pt, rng, objs, step=2.0)]
         gpu_ctx.upload(objs)
         gpu_ctx.scene_rebuild(base)
         _is_the_host_build(pt, gpu_ctx, pt.bvh_morton_check(base))
         at_build = gpu_ctx.bvh_cost()[1]
-        for step, pose in enumerate([rc.moved(pt, rng, objs), rc.shifted(pt, objs, 1), rc.moved(pt, rng, objs, step=2.0)]):
+        for step, pose in enumerate(poses):
             gpu_ctx.scene_refit(pose)
             want = pt.bvh_morton_check(base, refit_to=pose)
             got = gpu_ctx.debug_bvh_read()
@@ -113,14 +130,15 @@ def _poses(pt, scenes, name):
     return objs, rc.moved(pt, np.random.default_rng(21), objs, step=0.2), pt.camera_new(width=32, height=32), (0.0, 0.0, 0.0)
 
 
-@pytest.mark.parametrize("name", ["mixed200", "n20011", "outside"])
+@pytest.mark.parametrize("name", ["mixed200", "n20011", "outside", CARRY])
 def test_hits_and_film_over_a_morton_tree_equal_the_linear_scan(pt, gpu_ctx, ctx2, scenes, name):
     objs, pose, cam, off = _poses(pt, scenes, name)
+    n_rays, spp = (2048, 1) if name == CARRY else (20_000, 2)
     _host_tree(pt, gpu_ctx, objs)
     gpu_ctx.scene_rebuild(pose)
     ctx2.upload(pose)
     rng = np.random.default_rng(11)
-    rays = _rays(rng, 20_000)
+    rays = _rays(rng, n_rays)
     rays[:, :3] += off
     for t_min, t_max in ((0.001, float("inf")), (0.001, 0.4), (0.3, 1.5)):
         for exact_math in (1, 0):
@@ -130,8 +148,8 @@ def test_hits_and_film_over_a_morton_tree_equal_the_linear_scan(pt, gpu_ctx, ctx
             assert np.array_equal(t0.view(np.uint32), t1.view(np.uint32)), exact_math
             if t_max == float("inf"):
                 assert (i1 >= 0).any()
-    got = _film(gpu_ctx, cam, pt.default_params(spp=2, accel=PT_ACCEL_BVH))
-    want = _film(ctx2, cam, pt.default_params(spp=2, accel=PT_ACCEL_LINEAR))
+    got = _film(gpu_ctx, cam, pt.default_params(spp=spp, accel=PT_ACCEL_BVH))
+    want = _film(ctx2, cam, pt.default_params(spp=spp, accel=PT_ACCEL_LINEAR))
     assert _same_film(got, want)
     assert gpu_ctx.bvh_cost()[2] == 0
     assert rc.same_tree(gpu_ctx.debug_bvh_read(), pt.bvh_morton_check(pose)) is None      # (the renders used the device build)

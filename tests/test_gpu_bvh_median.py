@@ -1,7 +1,14 @@
 """pt_scene_rebuild_ordered on the GPU.  PT_BVH_ORDER_MEDIAN: the device-side build in median order (k_bvh_cells, the levels of
 k_bvh_median_bounds / k_bvh_median_keys / the radix sort, k_bvh_median_tile, then k_bvh_write_ids and the refit kernels) against
 its host reference (ptbvh::build_median through pt_debug_bvh_median_check) bit for bit, and the contract that the film never
-depends on the tree.  PT_BVH_ORDER_MORTON: pt_scene_rebuild."""
+depends on the tree.  PT_BVH_ORDER_MORTON: pt_scene_rebuild.
+
+The counts go past a 32-bit sort key and one iteration of k_bvh_sort_scan (bvh_median_cases.MEDIAN_LARGE;
+tests/test_bvh_large_counts_cpu.py holds them to the tile sizes and to the plan): 32 768 objects are the first with a 5-pass
+level, the scan's one iteration exactly full; 32 769 mix 4- and 5-pass levels (the result changes buffer between levels) behind
+a scan carry; 65 537 take 5 passes on every level; 131 073 have a gap of two chunks among the step groups; 262 145 one of four
+chunks and the only 6-pass level.  Above 10 000 objects no host-built tree stands before the device build, 262 145 are built
+once, and refits, ties, hits and films run at 32 769."""
 import os
 import subprocess
 
@@ -16,8 +23,9 @@ pytestmark = pytest.mark.gpu
 PT_ERR_INVALID_ARG, PT_ERR_UNSUPPORTED = 1, 5
 PT_ACCEL_LINEAR, PT_ACCEL_BVH, PT_ACCEL_AUTO = 0, 1, 2
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-T = 2048                                                         # pt_debug_bvh_median_plan's tile (checked below)
+T = mc.K_MEDIAN_TILE                                             # pt_debug_bvh_median_plan's tile (checked below)
 COUNTS = [0, 1, 4, 5, 17, 65, 300, T - 1, T, T + 1, 2 * T + 1, 4 * T + 3, 10000]
+CARRY = mc.SCAN_CARRY                                            # 32 769: a scan carry, 4- and 5-pass levels, a gap group
 
 
 def _scene(pt, n):
@@ -61,8 +69,7 @@ def test_the_tile_is_the_one_the_counts_are_chosen_for(pt):
 
 
 # ------------------------------------------------------------------------------------------------ the tree, bit for bit
-@pytest.mark.parametrize("before", ["no_tree", "host_tree"])
-@pytest.mark.parametrize("n", COUNTS)
+@pytest.mark.parametrize("n, before", [(n, before) for before in ("no_tree", "host_tree") for n in COUNTS] + [(n, "no_tree") for n in mc.MEDIAN_LARGE])
 def test_device_tree_equals_the_host_rule_bit_for_bit(pt, n, before):
     objs = _scene(pt, n)
     want = pt.bvh_median_check(objs)
@@ -74,13 +81,15 @@ def test_device_tree_equals_the_host_rule_bit_for_bit(pt, n, before):
             c.upload(objs)
         c.scene_rebuild(objs, order="median")
         _is_the_host_rule(pt, c, want)
+        if n == mc.MEDIAN_ONCE:
+            return
         c.scene_rebuild(objs, order="median")            # the cached plan and topology
         _is_the_host_rule(pt, c, want)
     finally:
         c.close()
 
 
-@pytest.mark.parametrize("n", [65, T + 1])
+@pytest.mark.parametrize("n", [65, T + 1, CARRY])
 @pytest.mark.parametrize("kind", ["equal_centres", "flat"])
 def test_ties_and_a_flat_scene(pt, gpu_ctx, kind, n):
     objs = mc.equal_centres(pt, n) if kind == "equal_centres" else mc.flat(pt, n)
@@ -107,7 +116,7 @@ def test_order_morton_is_pt_scene_rebuild(pt, gpu_ctx, ctx2):
 
 
 def test_median_rebuild_then_refit(pt, gpu_ctx):
-    for n in (300, 2 * T + 1):
+    for n in (300, 2 * T + 1, CARRY):
         objs = _scene(pt, n)
         rng = np.random.default_rng(3)
         base = rc.moved(pt, rng, objs)
@@ -126,13 +135,15 @@ def test_median_rebuild_then_refit(pt, gpu_ctx):
 
 
 # -------------------------------------------------------------------------------------------------------- hits and film
-@pytest.mark.parametrize("n", [300, 4 * T + 3])
+@pytest.mark.parametrize("n", [300, 4 * T + 3, CARRY])
 def test_hits_and_film_over_a_median_tree_equal_the_linear_scan(pt, gpu_ctx, ctx2, n):
     objs = _scene(pt, n)
-    cam = pt.camera_new(width=64, height=64)
-    rays = _rays(np.random.default_rng(11), 4096)
+    side, n_rays = (32, 2048) if n == CARRY else (64, 4096)
+    cam = pt.camera_new(width=side, height=side)
+    rays = _rays(np.random.default_rng(11), n_rays)
     gpu_ctx.upload(objs)
-    for pose in (objs, rc.moved(pt, np.random.default_rng(21), objs, step=0.2)):      # ... and again after the objects moved
+    poses = (objs,) if n == CARRY else (objs, rc.moved(pt, np.random.default_rng(21), objs, step=0.2))
+    for pose in poses:                                   # ... and again after the objects moved
         gpu_ctx.scene_rebuild(pose, order="median")
         ctx2.upload(pose)
         for exact_math in (1, 0):
