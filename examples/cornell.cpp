@@ -2,7 +2,8 @@
 // build World::new(), render every pixel, export luminance.csv, and write a PPM of
 // World.data instead of blitting it to a winit/pixels surface (out of scope).
 //
-//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F]       defaults: 400 400 64 cornell 0, no lens
+//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F] [--cascade]       defaults: 400 400 64 cornell 0, no lens
+//   --cascade: the film is formed by the brightness cascade (World::render_cascade, pt_default_cascade): fireflies are re-weighted
 //   CORNELL_DENOISE=n: render_denoised with n feature samples (pt_render_denoised) instead of render()
 //   CORNELL_ADAPTIVE_DENOISE=n: render_adaptive_denoised with n feature samples (pt_render_adaptive_denoised): spp is spp_max,
 //                       spp_min 4, spp_step 4, rel_tol 0.1
@@ -21,7 +22,7 @@ int main(int argc, char** argv) {
     // optional, anywhere on the line: --aperture A --focus F (a thin lens, World::render_lens; with CORNELL_DENOISE its denoised form)
     PtLens lens;
     pt_default_lens(&lens);
-    bool use_lens = false;
+    bool use_lens = false, use_cascade = false;
     {
         int keep = 1;
         for (int i = 1; i < argc; ++i) {
@@ -29,6 +30,8 @@ int main(int argc, char** argv) {
             if ((arg == "--aperture" || arg == "--focus") && i + 1 < argc) {
                 (arg == "--aperture" ? lens.aperture : lens.focus_distance) = std::atof(argv[++i]);
                 use_lens = true;
+            } else if (arg == "--cascade") {
+                use_cascade = true;
             } else {
                 argv[keep++] = argv[i];
             }
@@ -80,6 +83,8 @@ int main(int argc, char** argv) {
             world.render_lens_denoised(lens, (uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
         else if (use_lens)
             world.render_lens(lens);
+        else if (use_cascade)
+            world.render_cascade();
         else if (std::getenv("CORNELL_DENOISE"))   // denoised form: CORNELL_DENOISE = feature samples
             world.render_denoised((uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
         else if (std::getenv("CORNELL_PROGRESSIVE"))      // live-preview form: one line per increment

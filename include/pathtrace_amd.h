@@ -920,6 +920,69 @@ int pt_debug_lens_rays(PtContext* ctx, const PtCamera* cam, const PtLens* lens, 
 /* Debug, host only: out7 = Lu3, Lv3, inv_phi as the device receives them.  Needs no device. */
 int pt_debug_lens_setup(const PtCamera* cam, const PtLens* lens, float* out7);
 
+/* Brightness cascade (additive to ABI 6): a firefly-robust film.  The samples of a render are averaged into the film
+ * by an estimator that knows which of them are outliers -- the re-weighting of Zirr, Hanika and Dachsbacher (2018): every sample
+ * is split between two layers of a per-pixel cascade by its luminance, and a layer keeps its energy in full only where enough
+ * samples of that brightness landed in the pixel or its 3 x 3 neighbourhood.  The estimator is consistent: with more samples a
+ * legitimate rare event reaches the count and is kept.  No path kernel knows the cascade: k_resolve_cascade stands in for the
+ * ordinary resolve, k_cascade_reweight follows it.  The rule (pathtrace_amd/csrc/pt_cascade.h), all of it f64 with + - * /,
+ * comparisons and selects only, so that the host and the device agree bit for bit:
+ *   levels      B_0 = start, B_{j+1} = B_j base, K = layers of them (formed on the host by repeated multiplication)
+ *   split       per sample v (f32), L = 0.2126 r + 0.7152 g + 0.0722 b in f64: j = the largest index in [0, K-2] with B_j <= L,
+ *               0 when there is none (L < B_0, NaN).  !(L > B_j): w_lo = 1, w_hi = 0 (NaN, negatives, L <= B_0); else L < B_{j+1}:
+ *               q = B_j / B_{j+1}, w_lo = (B_j / L - q) / (1 - q), w_hi = 1 - w_lo; else (L >= B_{K-1}, +inf) w_lo = 0, w_hi = 1.
+ *               S_j += w_lo v and S_{j+1} += w_hi v per channel, each only when its weight is not exactly 0 (a select, not a
+ *               multiplication by zero: an infinite sample puts no NaN into the lower layer); beside them the plain sums P += v,
+ *               exactly as the ordinary resolve forms them.  Samples in sample order; the sums carry over sample batches.
+ *   count       lum_j = 0.2126 S_j.r + 0.7152 S_j.g + 0.0722 S_j.b;  T_j = lum_{j-1} + lum_j + lum_{j+1} added left to right, an
+ *               absent layer 0;  cnt_j = T_j / B_j
+ *   re-weight   wide_j(p) = the sum of cnt_j over the in-image taps of the 3 x 3 block around p, row-major from 0, divided by the
+ *               number of those taps;  r = cnt_j(p) > wide_j(p) ? cnt_j(p) : wide_j(p) (NaN when either is);  w_j(p) = 1 when
+ *               j = 0, kappa = 0, r is NaN or r >= kappa, else r / kappa
+ *   film        m = (sum over j ascending, from 0, of w_j(p) S_j(p)) / n per channel with n the samples per pixel; the linear
+ *               plane is (float)m, the RGBA8 plane m through the sqrt, clamp and `as u8` steps of every render (which start from
+ *               the f64 mean); the plain film is P / n, bit-identical to pt_render_device's
+ * Whole image only (band_count = 1): the re-weighting reads neighbours.  params->exact_math changes the path kernels only; the
+ * cascade kernels have no f32 arithmetic.  The lens, adaptive, progressive and multi-GPU renders have no cascade form, and the
+ * layers are not fed to the denoiser: the cascade film is an ordinary linear film and pt_denoise_device takes it as it is.
+ * PT_ERR_INVALID_ARG, with the context untouched, for: a null required argument, layers outside [2, 8], a start that is not
+ * finite and > 0, a base that is not finite and >= 2, a kappa that is not finite and >= 0, a level table that overflows, an
+ * image smaller than 2 x 2, band_count > 1, n = 0, a plane that is not 4-byte aligned, an output that shares memory with the
+ * samples or with another output.
+ * pt_default_cascade: 6 layers, start 1, base 8, kappa 1 (docs/EXPERIMENTS.md "Brightness cascade").                          */
+typedef struct {
+    uint32_t layers;         /* K, in [2, 8]                                                          */
+    float start;             /* B_0: luminances up to it are never re-weighted; finite, > 0           */
+    float base;              /* the ratio of consecutive levels; finite, >= 2                         */
+    float kappa;             /* the count a layer needs to be kept in full; finite, >= 0; 0 = keep all */
+} PtCascade;
+void pt_default_cascade(PtCascade* out);
+/* pt_render_device with the cascade resolve in place of the ordinary one, then the re-weighting pass: d_linear_rgb (width*height*3
+ * floats) the cascade film, d_rgba8 (width*height*4 bytes, may be NULL) its display plane, d_plain_linear (width*height*3 floats,
+ * may be NULL) the plain film.  Asynchronous on the context's stream.  The context owns the cascade state -- 3 (K + 1) doubles
+ * per pixel for the sums and K doubles per pixel for the counts --, which grows at first use and is freed with the context; once
+ * it is there the call allocates nothing beyond what pt_render_device does.  max_paths_in_flight cuts the job into sample batches
+ * and the film does not depend on them.                                                                                      */
+int pt_render_cascade_device(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, const PtCascade* cs,
+                             float* d_linear_rgb, uint8_t* d_rgba8, float* d_plain_linear);
+/* The same into host buffers (blocking).  Optional outputs (NULL: not wanted): out_plain_linear; out_layers, the layer sums
+ * S_j, K*width*height*3 doubles, layer-major; out_weights, w_j(p) rounded to f32, K*width*height floats, layer-major.         */
+int pt_render_cascade_host(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, const PtCascade* cs,
+                           float* out_linear_rgb, uint8_t* out_rgba8, float* out_plain_linear, double* out_layers,
+                           float* out_weights);
+/* The two kernels on GIVEN samples: d_samples = n * width*height RGB records of 12 bytes on the device in the renders' own
+ * sample-buffer layout, sample-major ([s * width*height + p]).  Needs no scene.  batch: the samples a launch of the resolve
+ * kernel takes, so that n is cut into ceil(n / batch) launches that hand the sums on (0: all n in one); the film does not
+ * depend on it.  Outputs as pt_render_cascade_device's.  Asynchronous on the context's stream.                               */
+int pt_cascade_samples_device(PtContext* ctx, const PtCascade* cs, uint32_t width, uint32_t height, uint32_t n, uint32_t batch,
+                              const float* d_samples, float* d_linear_rgb, uint8_t* d_rgba8, float* d_plain_linear);
+/* The same samples in HOST memory through the rule header on the CPU, with the optional outputs of pt_render_cascade_host.
+ * Needs no device and no context.                                                                                             */
+int pt_cascade_host(const PtCascade* cs, uint32_t width, uint32_t height, uint32_t n, const float* samples, float* out_linear,
+                    uint8_t* out_rgba8, float* out_plain, double* out_layers, float* out_weights);
+/* Debug, host only: the split of one luminance -> the lower layer j and the two weights.                                      */
+int pt_debug_cascade_split(const PtCascade* cs, double L, uint32_t* j, double* w_lo, double* w_hi);
+
 /* RenderingStrategy::ray_color(world, ray, depth = 0, rng, throughput = 1) (src/rendering.rs:34-142,
  * 214-265) for n arbitrary rays: rays = n * (origin3, direction3), the direction is normalised on
  * entry like Ray::new (camera.rs:10-16); xy = n * (x, y) = the RNG key of each ray's stream, and the

@@ -146,6 +146,15 @@ class PtLens(C.Structure):
     ]
 
 
+class PtCascade(C.Structure):
+    _fields_ = [
+        ("layers", C.c_uint32),
+        ("start", C.c_float),
+        ("base", C.c_float),
+        ("kappa", C.c_float),
+    ]
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -316,6 +325,15 @@ SYMBOLS = {
                                    C.c_void_p, C.c_void_p]),
     "pt_render_denoised_upsampled": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, C.c_uint32, C.c_uint32, _P(PtDenoise),
                                                _P(PtUpsample), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_default_cascade": (None, [_P(PtCascade)]),
+    "pt_render_cascade_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtCascade), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_render_cascade_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtCascade), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "pt_cascade_samples_device": (C.c_int, [C.c_void_p, _P(PtCascade), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "pt_cascade_host": (C.c_int, [_P(PtCascade), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "pt_debug_cascade_split": (C.c_int, [_P(PtCascade), C.c_double, _P(C.c_uint32), _P(C.c_double), _P(C.c_double)]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

@@ -81,6 +81,37 @@ def default_upsample(**over):
     return u
 
 
+def default_cascade(**over):
+    """pt_default_cascade (6 layers, start 1, base 8, the measured kappa) with keyword overrides (None keeps the default)."""
+    cs = _lib.PtCascade()
+    lib().pt_default_cascade(C.byref(cs))
+    for k, v in over.items():
+        if v is not None:
+            setattr(cs, k, v)
+    return cs
+
+
+def cascade_split(cs, L):
+    """pt_debug_cascade_split (host only): the split of one luminance -> (j, w_lo, w_hi)"""
+    j, lo, hi = C.c_uint32(0), C.c_double(0.0), C.c_double(0.0)
+    check(lib().pt_debug_cascade_split(C.byref(cs), C.c_double(L), C.byref(j), C.byref(lo), C.byref(hi)))
+    return j.value, lo.value, hi.value
+
+
+def cascade_host(samples, cs=None):
+    """pt_cascade_host: the cascade rule on the CPU (no device, no context) on samples f32[n,H,W,3] in sample order; cs:
+    default_cascade().  -> (linear f32[H,W,3], rgba u8[H,W,4], plain linear f32[H,W,3], layers f64[K,H,W,3], weights f32[K,H,W])"""
+    cs = default_cascade() if cs is None else cs
+    smp = np.ascontiguousarray(samples, dtype=np.float32)
+    n, H, W = smp.shape[:3]
+    assert smp.shape == (n, H, W, 3), smp.shape
+    K = max(int(cs.layers), 1)
+    out, rgba, plain = np.empty((H, W, 3), np.float32), np.empty((H, W, 4), np.uint8), np.empty((H, W, 3), np.float32)
+    layers, weights = np.empty((K, H, W, 3), np.float64), np.empty((K, H, W), np.float32)
+    check(lib().pt_cascade_host(C.byref(cs), W, H, n, *[a.ctypes.data_as(C.c_void_p) for a in (smp, out, rgba, plain, layers, weights)]))
+    return out, rgba, plain, layers, weights
+
+
 def default_lens(**over):
     """pt_default_lens (aperture 0 = pinhole, focus_distance 1) with keyword overrides (None keeps the default)."""
     l = _lib.PtLens()
@@ -542,6 +573,37 @@ class _ContextFunctions:
         out, rgba = self._film_pair(H, W)
         self._on_stream(lib().pt_upsample_device, w, h, d_lo, d_lo_feat, W, H, d_feat, C.byref(up), out, rgba)
         return out.cpu().numpy(), rgba.cpu().numpy()
+
+    def render_cascade(self, cam, params, cs=None):
+        """pt_render_cascade_host (host buffers, blocking): render() whose film is formed by the brightness cascade; cs:
+        default_cascade().  -> (linear f32[H,W,3], rgba u8[H,W,4], plain linear f32[H,W,3], layers f64[K,H,W,3], weights f32[K,H,W])"""
+        cs = default_cascade() if cs is None else cs
+        H, W, K = cam.height, cam.width, max(int(cs.layers), 1)
+        planes, ptrs = self._host_planes(H, W, (3, np.float32), (4, np.uint8), (3, np.float32))
+        layers, weights = np.empty((K, H, W, 3), np.float64), np.empty((K, H, W), np.float32)
+        check(lib().pt_render_cascade_host(self._h, C.byref(cam), C.byref(params), C.byref(cs), *ptrs, layers.ctypes.data_as(C.c_void_p),
+                                           weights.ctypes.data_as(C.c_void_p)))
+        return planes + (layers, weights)
+
+    def render_cascade_device(self, cam, params, cs=None, want_plain=True):
+        """pt_render_cascade_device into torch tensors.  -> (linear f32[H,W,3], rgba u8[H,W,4], plain linear f32[H,W,3] or None)"""
+        cs = default_cascade() if cs is None else cs
+        H, W = cam.height, cam.width
+        lin, rgba = self._film_pair(H, W)
+        plain = self._empty((H, W, 3)) if want_plain else None
+        self._on_stream(lib().pt_render_cascade_device, C.byref(cam), C.byref(params), C.byref(cs), lin, rgba, plain)
+        return lin, rgba, plain
+
+    def cascade_samples(self, samples, cs=None, batch=0):
+        """pt_cascade_samples_device: the two cascade kernels on given samples f32[n,H,W,3]; batch: samples per resolve launch
+        (0: all in one).  -> (linear f32[H,W,3], rgba u8[H,W,4], plain linear f32[H,W,3])"""
+        cs = default_cascade() if cs is None else cs
+        n, H, W = np.shape(samples)[:3]
+        d_smp = self._upload(samples, np.float32, (n, H, W, 3))
+        lin, rgba = self._film_pair(H, W)
+        plain = self._empty((H, W, 3))
+        self._on_stream(lib().pt_cascade_samples_device, C.byref(cs), W, H, n, batch, d_smp, lin, rgba, plain)
+        return lin.cpu().numpy(), rgba.cpu().numpy(), plain.cpu().numpy()
 
     def render_denoised_upsampled(self, cam, params, lo_size, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
                                   up_sigma_n=None, up_sigma_d=None):

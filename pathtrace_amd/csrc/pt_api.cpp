@@ -257,6 +257,7 @@ struct Exec {
     const FilmState& fs;
     const ListRender* list;
     const AdaptivePass* ad;
+    const CascadePass* cas;
     float* d_linear;
     uint8_t* d_rgba;
     void* d_packed;
@@ -322,6 +323,17 @@ int exec_resolve(Exec& x, const ptsched::Op& o, hipStream_t s) {
         r.finalize = o.batch + 1 == n_batches;
         if (o.zero_words) { r.zero_words = set_counters(c, o.set); r.n_zero = o.zero_words; }
         ptk::launch_resolve_adaptive(r, s);
+        HIP_TRY(hipGetLastError());
+        return PT_OK;
+    }
+    if (x.cas) {
+        ptk::CascadeResolveArgs r = x.cas->r;
+        r.lsamp = c->lsamp[o.set].p;
+        r.np = x.sh.np; r.nb = nb;
+        r.load = o.batch > 0;
+        r.finalize = o.batch + 1 == n_batches;
+        if (o.zero_words) { r.zero_words = set_counters(c, o.set); r.n_zero = o.zero_words; }
+        ptk::launch_resolve_cascade(r, s);
         HIP_TRY(hipGetLastError());
         return PT_OK;
     }
@@ -407,7 +419,7 @@ void commit(PtContext* c, const Exec& x, const ptsched::Job& job) {
 // was --, PLAN (ptsched::plan on a copy of the scheduling state: pure), fill the ARGS, EXECUTE the plan's stream operations in
 // order and COMMIT the copy.  A failure during EXECUTE: sched_recover.
 int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
-                float* d_linear, uint8_t* d_rgba, void* d_packed, const AdaptivePass* ad) {
+                float* d_linear, uint8_t* d_rgba, void* d_packed, const AdaptivePass* ad, const CascadePass* cas) {
     int rc;
     if ((rc = check_render(c, cam, prm, list, d_linear, d_rgba))) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -442,7 +454,7 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
         if ((rc = ensure_events(c, top))) return rc;
     }
 
-    Exec x{c, cam, prm, fs, list, ad, d_linear, d_rgba, d_packed, sh, plan, next, bounce_args(c, cam, prm, list, sh.np), {}, 0};
+    Exec x{c, cam, prm, fs, list, ad, cas, d_linear, d_rgba, d_packed, sh, plan, next, bounce_args(c, cam, prm, list, sh.np), {}, 0};
     for (size_t i = 0; i < plan.ops.size(); ++i)
         if ((rc = exec_op(x, plan.ops[i], i))) {
             const std::string keep = g_err;

@@ -244,6 +244,11 @@ struct PtContext {
     uint32_t gr_frame = 0;
     // pt_tonemap_device: the exposure lives on the device; no scene entry touches it
     TonemapState tone;
+    // pt_render_cascade_device / pt_cascade_samples_device: the layer sums and plain sums of every pixel ((3 K + 3)
+    // planes of doubles) and the K count planes; they grow at first use.  pt_render_cascade_host: device staging of the plain film
+    // and of the weight planes
+    DevBuf<double> cas_state, cas_cnt;
+    DevBuf<float> cas_plain, cas_weights;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).
@@ -272,9 +277,16 @@ struct AdaptivePass {
     uint32_t n_total = 0;     // samples per pixel of the pass's pixels once it is done
 };
 
+// A cascade render (pt_render_cascade_device): the film resolve is k_resolve_cascade into the context's cascade state instead of
+// k_resolve; the caller launches k_cascade_reweight behind the render.
+struct CascadePass {
+    ptk::CascadeResolveArgs r{};   // the levels and the state planes; the launch fills in its batch
+};
+
 // ---- functions that cross files
 int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
-                float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr);   // pt_api.cpp
+                float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr,
+                const CascadePass* cas = nullptr);   // pt_api.cpp
 int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad);   // pt_api.cpp
 // pt_render_lens_device in the name `who` (pt_api.cpp); pt_lens.cpp: the lens and the camera checked, the device's words
 int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,

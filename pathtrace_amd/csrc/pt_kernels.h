@@ -237,6 +237,39 @@ void launch_adaptive_select(const uint2* pixels, uint32_t n, uint32_t width, con
 // sums 5 doubles and count one word per image pixel, feat the 2 float4 feature records; var one float per pixel.
 void launch_adaptive_variance(const double* sums, const uint32_t* count, const float4* feat, uint32_t np, float* var, hipStream_t st);
 
+// Brightness cascade (pt_render_cascade_device, the rule in pt_cascade.h).  The levels as the host formed them (ptcas::levels), K
+// layers.  State of an image of np pixels: (3 K + 3) planes of np doubles -- plane 3 k + c = S_k.c, planes 3 K + c the plain sums
+// P.c -- and K planes of np doubles for the counts cnt_k.
+struct CascadeResolveArgs {
+    double B[8];
+    double kappa;
+    uint32_t K;
+    const Rgb* lsamp;         // nb * np samples, [s * np + p]
+    double* state;
+    double* cnt;              // written by the finalising launch
+    uint32_t np, nb;
+    uint32_t load;            // start from the stored sums (else from zero: the pixels' first samples)
+    uint32_t finalize;        // the last samples of the pixels: leave the counts for k_cascade_reweight
+    uint32_t* zero_words;     // as ResolveArgs
+    uint32_t n_zero;
+};
+void launch_resolve_cascade(const CascadeResolveArgs& a, hipStream_t st);
+// The film of a finalised state: out_linear np * 3 floats, out_rgba np * 4 bytes or null, out_plain (P / n_total) np * 3 floats or
+// null, out_weights K planes of np floats or null.
+struct CascadeReweightArgs {
+    double B[8];
+    double kappa;
+    uint32_t K;
+    const double* state;
+    const double* cnt;
+    uint32_t width, height, n_total;
+    float* out_linear;
+    uint8_t* out_rgba;
+    float* out_plain;
+    float* out_weights;
+};
+void launch_cascade_reweight(const CascadeReweightArgs& a, hipStream_t st);
+
 // Multi-GPU film exchange (pt_multi.cpp): tile -> 16 B per pixel (linear RGB + RGBA8) before the gather, gathered
 // padded tiles -> frame in image order after it.
 void launch_film_pack(const float* lin, const uint8_t* rgba, uint32_t np, void* packed, hipStream_t st);

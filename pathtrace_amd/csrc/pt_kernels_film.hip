@@ -7,6 +7,7 @@
 //   pt_film_bvh.h        device-side BVH refit and builds (Morton order, median order)
 //   pt_film_tonemap.h    auto-exposure and tone mapping
 //   pt_film_upsample.h   feature-guided upsampling of a low-resolution film
+//   pt_film_cascade.h    the brightness cascade: a firefly-robust resolve and its re-weighting pass
 // None of them has a division or square root whose result depends on the arithmetic mode, so the unit is compiled once, in
 // fast mode (its kernels live in ptk_fast_impl), and serves both modes.
 #include "pt_kernels_scan.h"
@@ -20,3 +21,4 @@
 #include "pt_film_bvh.h"
 #include "pt_film_tonemap.h"
 #include "pt_film_upsample.h"
+#include "pt_film_cascade.h"

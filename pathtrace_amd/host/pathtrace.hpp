@@ -19,6 +19,7 @@
 //   World::tonemap()                   auto-exposure, curve and transfer on the film the World holds
 //   World::render_denoised_upsampled() paths traced at a lower resolution, the film reconstructed under full-size features
 //   World::upsample()                  that reconstruction alone, on host planes (the rule on the CPU)
+//   World::render_cascade()            render() with a firefly-robust film: samples re-weighted through a brightness cascade
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -517,6 +518,26 @@ public:
         if (lo) {
             lo->resize(n_lo);
             for (size_t i = 0; i < n_lo; ++i) (*lo)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+        }
+    }
+    // render() whose film is formed by the brightness cascade (pt_render_cascade_host; cs: pt_default_cascade
+    // when null): fireflies are re-weighted where the samples are averaged.  data / luminance_data hold the cascade film;
+    // plain (optional, y*width+x) receives the plain film of the same samples.
+    void render_cascade(const PtCascade* cs = nullptr, std::vector<Vector3>* plain = nullptr, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtCascade c{};
+        if (cs) c = *cs; else pt_default_cascade(&c);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3), raw(plain ? n * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_cascade_host(ctx_, &camera_.pod(), &p, &c, lin.data(), rgba.data(), plain ? raw.data() : nullptr, nullptr, nullptr));
+        unpack(lin, rgba);
+        if (plain) {
+            plain->resize(n);
+            for (size_t i = 0; i < n; ++i) (*plain)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
         }
     }
     // The upsampling rule alone, on host planes and on the CPU (pt_upsample_host; needs no device): a low film (3 floats per

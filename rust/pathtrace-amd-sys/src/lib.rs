@@ -155,6 +155,16 @@ pub struct PtUpsample {
     pub sigma_d: f32,
 }
 
+/// pt_render_cascade_device: the brightness cascade of the firefly-robust film (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtCascade {
+    pub layers: u32,
+    pub start: f32,
+    pub base: f32,
+    pub kappa: f32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct PtStats {
@@ -422,6 +432,12 @@ extern "C" {
     pub fn pt_render_lens_denoised(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
     pub fn pt_debug_lens_rays(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, xys: *const u32, n: u32, exact_math: u32, out8: *mut f32) -> c_int;
     pub fn pt_debug_lens_setup(cam: *const PtCamera, lens: *const PtLens, out7: *mut f32) -> c_int;
+    pub fn pt_default_cascade(out: *mut PtCascade);
+    pub fn pt_render_cascade_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
+    pub fn pt_render_cascade_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_plain_linear: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;
+    pub fn pt_cascade_samples_device(ctx: *mut PtContext, cs: *const PtCascade, width: u32, height: u32, n: u32, batch: u32, d_samples: *const f32, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
+    pub fn pt_cascade_host(cs: *const PtCascade, width: u32, height: u32, n: u32, samples: *const f32, out_linear: *mut f32, out_rgba8: *mut u8, out_plain: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;
+    pub fn pt_debug_cascade_split(cs: *const PtCascade, l: f64, j: *mut u32, w_lo: *mut f64, w_hi: *mut f64) -> c_int;
     pub fn pt_default_gradient(out: *mut PtGradient);
     pub fn pt_temporal_gradient_device(ctx: *mut PtContext, cam: *const PtCamera, prev_params: *const PtRenderParams, seed: u32, d_prev_linear: *const f32, g: *const PtGradient, alpha_min: f32, d_alpha: *mut f32) -> c_int;
     pub fn pt_debug_gradient_strata(ctx: *mut PtContext, width: u32, height: u32, out_xy: *mut u32, out_film: *mut f32, out_rec: *mut f64) -> c_int;
