@@ -2,8 +2,10 @@
 // build World::new(), render every pixel, export luminance.csv, and write a PPM of
 // World.data instead of blitting it to a winit/pixels surface (out of scope).
 //
-//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F] [--cascade]       defaults: 400 400 64 cornell 0, no lens
+//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F] [--cascade] [--filter KIND --radius R]       defaults: 400 400 64 cornell 0, no lens
 //   --cascade: the film is formed by the brightness cascade (World::render_cascade, pt_default_cascade): fireflies are re-weighted
+//   --filter box|tent|gaussian|mitchell [--radius R]: the film is reconstructed with that filter (World::render_filtered; gaussian:
+//                       alpha 2, mitchell: B = C = 1/3; R defaults to 0.5 / 1 / 1.5 / 2)
 //   CORNELL_DENOISE=n: render_denoised with n feature samples (pt_render_denoised) instead of render()
 //   CORNELL_ADAPTIVE_DENOISE=n: render_adaptive_denoised with n feature samples (pt_render_adaptive_denoised): spp is spp_max,
 //                       spp_min 4, spp_step 4, rel_tol 0.1
@@ -22,7 +24,10 @@ int main(int argc, char** argv) {
     // optional, anywhere on the line: --aperture A --focus F (a thin lens, World::render_lens; with CORNELL_DENOISE its denoised form)
     PtLens lens;
     pt_default_lens(&lens);
-    bool use_lens = false, use_cascade = false;
+    bool use_lens = false, use_cascade = false, use_filter = false;
+    PtFilter flt;
+    pt_default_filter(&flt);
+    float flt_radius = 0.0f;
     {
         int keep = 1;
         for (int i = 1; i < argc; ++i) {
@@ -32,6 +37,15 @@ int main(int argc, char** argv) {
                 use_lens = true;
             } else if (arg == "--cascade") {
                 use_cascade = true;
+            } else if (arg == "--filter" && i + 1 < argc) {
+                const std::string kind = argv[++i];
+                use_filter = true;
+                if (kind == "box") { flt.kind = PT_FILTER_BOX; flt.radius = 0.5f; }
+                else if (kind == "tent") { flt.kind = PT_FILTER_TENT; flt.radius = 1.0f; }
+                else if (kind == "mitchell") { flt.kind = PT_FILTER_MITCHELL; flt.radius = 2.0f; flt.a = flt.b = 1.0f / 3.0f; }
+                else if (kind != "gaussian") { std::fprintf(stderr, "--filter: box, tent, gaussian or mitchell\n"); return 2; }
+            } else if (arg == "--radius" && i + 1 < argc) {
+                flt_radius = (float)std::atof(argv[++i]);
             } else {
                 argv[keep++] = argv[i];
             }
@@ -85,6 +99,10 @@ int main(int argc, char** argv) {
             world.render_lens(lens);
         else if (use_cascade)
             world.render_cascade();
+        else if (use_filter) {
+            if (flt_radius != 0.0f) flt.radius = flt_radius;
+            world.render_filtered(&flt);
+        }
         else if (std::getenv("CORNELL_DENOISE"))   // denoised form: CORNELL_DENOISE = feature samples
             world.render_denoised((uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
         else if (std::getenv("CORNELL_PROGRESSIVE"))      // live-preview form: one line per increment

@@ -155,6 +155,18 @@ class PtCascade(C.Structure):
     ]
 
 
+class PtFilter(C.Structure):
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("radius", C.c_float),
+        ("a", C.c_float),
+        ("b", C.c_float),
+    ]
+
+
+FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN, FILTER_MITCHELL = 0, 1, 2, 3
+
+
 class PtSchedJob(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_batches", "regen", "split", "hand_off", "regen_export", "profile", "in_order", "capturing",
                                           "grid", "regen_grid", "cont_grid", "regen_capacity", "fixed_grid", "counter_words")] + [("xchg_need", C.c_uint64)]
@@ -334,6 +346,17 @@ SYMBOLS = {
     "pt_cascade_host": (C.c_int, [_P(PtCascade), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "pt_debug_cascade_split": (C.c_int, [_P(PtCascade), C.c_double, _P(C.c_uint32), _P(C.c_double), _P(C.c_double)]),
+    "pt_default_filter": (None, [_P(PtFilter)]),
+    "pt_render_filtered_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtFilter), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_render_filtered_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtFilter), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "pt_filter_samples_device": (C.c_int, [C.c_void_p, _P(PtFilter), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_filter_host": (C.c_int, [_P(PtFilter), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    "pt_debug_filter_weight": (C.c_int, [_P(PtFilter), C.c_double, _P(C.c_double)]),
+    "pt_debug_filter_offsets": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_double), _P(C.c_double)]),
+    "pt_debug_filter_exp_neg": (C.c_int, [C.c_double, _P(C.c_double)]),
     "pt_ray_color": (C.c_int, [C.c_void_p, _P(PtRenderParams), _P(C.c_double), _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_shutdown": (None, []),
     "pt_multi_create": (C.c_int, [_P(C.c_int), C.c_uint32, _P(C.c_void_p)]),

@@ -112,6 +112,55 @@ def cascade_host(samples, cs=None):
     return out, rgba, plain, layers, weights
 
 
+FILTER_KINDS = {"box": _lib.FILTER_BOX, "tent": _lib.FILTER_TENT, "gaussian": _lib.FILTER_GAUSSIAN, "mitchell": _lib.FILTER_MITCHELL}
+
+
+def default_filter(**over):
+    """pt_default_filter (Gaussian, radius 1.5, alpha 2) with keyword overrides (None keeps the default); kind may be a name
+    of FILTER_KINDS."""
+    f = _lib.PtFilter()
+    lib().pt_default_filter(C.byref(f))
+    for k, v in over.items():
+        if v is not None:
+            setattr(f, k, FILTER_KINDS[v] if k == "kind" and isinstance(v, str) else v)
+    return f
+
+
+def filter_weight(flt, t):
+    """pt_debug_filter_weight (host only): f(|t|)"""
+    f = C.c_double(0.0)
+    check(lib().pt_debug_filter_weight(C.byref(flt), C.c_double(t), C.byref(f)))
+    return f.value
+
+
+def filter_offsets(x, y, sample):
+    """pt_debug_filter_offsets (host only): the jitter (ox, oy) of sample `sample` of pixel (x, y)"""
+    ox, oy = C.c_double(0.0), C.c_double(0.0)
+    check(lib().pt_debug_filter_offsets(x, y, sample, C.byref(ox), C.byref(oy)))
+    return ox.value, oy.value
+
+
+def filter_exp_neg(e):
+    """pt_debug_filter_exp_neg (host only): the rule's exp(-e), e in [0, 100]"""
+    out = C.c_double(0.0)
+    check(lib().pt_debug_filter_exp_neg(C.c_double(e), C.byref(out)))
+    return out.value
+
+
+def filter_host(samples, flt=None, first_sample=0):
+    """pt_filter_host: the filter rule on the CPU (no device, no context) on samples f32[n,H,W,3] in sample order, sample s
+    having the index first_sample + s; flt: default_filter().
+    -> (linear f32[H,W,3], rgba u8[H,W,4], plain linear f32[H,W,3], weight sums f64[H,W])"""
+    flt = default_filter() if flt is None else flt
+    smp = np.ascontiguousarray(samples, dtype=np.float32)
+    n, H, W = smp.shape[:3]
+    assert smp.shape == (n, H, W, 3), smp.shape
+    out, rgba, plain = np.empty((H, W, 3), np.float32), np.empty((H, W, 4), np.uint8), np.empty((H, W, 3), np.float32)
+    wsum = np.empty((H, W), np.float64)
+    check(lib().pt_filter_host(C.byref(flt), W, H, n, first_sample, *[a.ctypes.data_as(C.c_void_p) for a in (smp, out, rgba, plain, wsum)]))
+    return out, rgba, plain, wsum
+
+
 def default_lens(**over):
     """pt_default_lens (aperture 0 = pinhole, focus_distance 1) with keyword overrides (None keeps the default)."""
     l = _lib.PtLens()
@@ -604,6 +653,36 @@ class _ContextFunctions:
         plain = self._empty((H, W, 3))
         self._on_stream(lib().pt_cascade_samples_device, C.byref(cs), W, H, n, batch, d_smp, lin, rgba, plain)
         return lin.cpu().numpy(), rgba.cpu().numpy(), plain.cpu().numpy()
+
+    def render_filtered(self, cam, params, flt=None):
+        """pt_render_filtered_host (host buffers, blocking): render() whose film is reconstructed with a filter; flt:
+        default_filter().  -> (linear f32[H,W,3], rgba u8[H,W,4], plain linear f32[H,W,3], weight sums f64[H,W])"""
+        flt = default_filter() if flt is None else flt
+        H, W = cam.height, cam.width
+        planes, ptrs = self._host_planes(H, W, (3, np.float32), (4, np.uint8), (3, np.float32))
+        wsum = np.empty((H, W), np.float64)
+        check(lib().pt_render_filtered_host(self._h, C.byref(cam), C.byref(params), C.byref(flt), *ptrs, wsum.ctypes.data_as(C.c_void_p)))
+        return planes + (wsum,)
+
+    def render_filtered_device(self, cam, params, flt=None, want_plain=True):
+        """pt_render_filtered_device into torch tensors.  -> (linear f32[H,W,3], rgba u8[H,W,4], plain linear f32[H,W,3] or None)"""
+        flt = default_filter() if flt is None else flt
+        H, W = cam.height, cam.width
+        lin, rgba = self._film_pair(H, W)
+        plain = self._empty((H, W, 3)) if want_plain else None
+        self._on_stream(lib().pt_render_filtered_device, C.byref(cam), C.byref(params), C.byref(flt), lin, rgba, plain)
+        return lin, rgba, plain
+
+    def filter_samples(self, samples, flt=None, first_sample=0, batch=0):
+        """pt_filter_samples_device: k_resolve_filter on given samples f32[n,H,W,3]; batch: samples per launch (0: all in one).
+        -> (linear f32[H,W,3], rgba u8[H,W,4], plain linear f32[H,W,3], weight sums f64[H,W])"""
+        flt = default_filter() if flt is None else flt
+        n, H, W = np.shape(samples)[:3]
+        d_smp = self._upload(samples, np.float32, (n, H, W, 3))
+        lin, rgba = self._film_pair(H, W)
+        plain, wsum = self._empty((H, W, 3)), self._empty((H, W), "float64")
+        self._on_stream(lib().pt_filter_samples_device, C.byref(flt), W, H, n, first_sample, batch, d_smp, lin, rgba, plain, wsum)
+        return lin.cpu().numpy(), rgba.cpu().numpy(), plain.cpu().numpy(), wsum.cpu().numpy()
 
     def render_denoised_upsampled(self, cam, params, lo_size, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None,
                                   up_sigma_n=None, up_sigma_d=None):

@@ -258,6 +258,7 @@ struct Exec {
     const ListRender* list;
     const AdaptivePass* ad;
     const CascadePass* cas;
+    const FilterPass* flt;
     float* d_linear;
     uint8_t* d_rgba;
     void* d_packed;
@@ -334,6 +335,18 @@ int exec_resolve(Exec& x, const ptsched::Op& o, hipStream_t s) {
         r.finalize = o.batch + 1 == n_batches;
         if (o.zero_words) { r.zero_words = set_counters(c, o.set); r.n_zero = o.zero_words; }
         ptk::launch_resolve_cascade(r, s);
+        HIP_TRY(hipGetLastError());
+        return PT_OK;
+    }
+    if (x.flt) {
+        ptk::FilterResolveArgs r = x.flt->r;
+        r.lsamp = c->lsamp[o.set].p;
+        r.nb = nb;
+        r.first_sample = x.prm->spp_offset + o.batch * x.sh.nb_max;
+        r.load = o.batch > 0;
+        r.finalize = o.batch + 1 == n_batches;
+        if (o.zero_words) { r.zero_words = set_counters(c, o.set); r.n_zero = o.zero_words; }
+        ptk::launch_resolve_filter(r, s);
         HIP_TRY(hipGetLastError());
         return PT_OK;
     }
@@ -419,7 +432,7 @@ void commit(PtContext* c, const Exec& x, const ptsched::Job& job) {
 // was --, PLAN (ptsched::plan on a copy of the scheduling state: pure), fill the ARGS, EXECUTE the plan's stream operations in
 // order and COMMIT the copy.  A failure during EXECUTE: sched_recover.
 int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
-                float* d_linear, uint8_t* d_rgba, void* d_packed, const AdaptivePass* ad, const CascadePass* cas) {
+                float* d_linear, uint8_t* d_rgba, void* d_packed, const AdaptivePass* ad, const CascadePass* cas, const FilterPass* flt) {
     int rc;
     if ((rc = check_render(c, cam, prm, list, d_linear, d_rgba))) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -454,7 +467,7 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
         if ((rc = ensure_events(c, top))) return rc;
     }
 
-    Exec x{c, cam, prm, fs, list, ad, cas, d_linear, d_rgba, d_packed, sh, plan, next, bounce_args(c, cam, prm, list, sh.np), {}, 0};
+    Exec x{c, cam, prm, fs, list, ad, cas, flt, d_linear, d_rgba, d_packed, sh, plan, next, bounce_args(c, cam, prm, list, sh.np), {}, 0};
     for (size_t i = 0; i < plan.ops.size(); ++i)
         if ((rc = exec_op(x, plan.ops[i], i))) {
             const std::string keep = g_err;

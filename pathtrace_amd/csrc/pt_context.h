@@ -249,6 +249,10 @@ struct PtContext {
     // and of the weight planes
     DevBuf<double> cas_state, cas_cnt;
     DevBuf<float> cas_plain, cas_weights;
+    // pt_render_filtered_device / pt_filter_samples_device: the weighted sums, the weight sum and the plain sums of
+    // every pixel (7 planes of doubles); grows at first use.  pt_render_filtered_host: device staging of the plain film
+    DevBuf<double> flt_state;
+    DevBuf<float> flt_plain;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).
@@ -283,10 +287,16 @@ struct CascadePass {
     ptk::CascadeResolveArgs r{};   // the levels and the state planes; the launch fills in its batch
 };
 
+// A filtered render (pt_render_filtered_device): the film resolve is k_resolve_filter into the context's filter state instead of
+// k_resolve; its finalising launch writes the planes.
+struct FilterPass {
+    ptk::FilterResolveArgs r{};    // the rule, the state and the output planes; the launch fills in its batch
+};
+
 // ---- functions that cross files
 int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
                 float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr,
-                const CascadePass* cas = nullptr);   // pt_api.cpp
+                const CascadePass* cas = nullptr, const FilterPass* flt = nullptr);   // pt_api.cpp
 int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad);   // pt_api.cpp
 // pt_render_lens_device in the name `who` (pt_api.cpp); pt_lens.cpp: the lens and the camera checked, the device's words
 int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,

@@ -270,6 +270,28 @@ struct CascadeReweightArgs {
 };
 void launch_cascade_reweight(const CascadeReweightArgs& a, hipStream_t st);
 
+// Reconstruction filter (pt_render_filtered_device, the rule in pt_filter.h).  State of an image of np pixels: 7 planes of np
+// doubles -- planes 0..2 the weighted sums A.c, plane 3 the weight sum Wt, planes 4..6 the plain sums P.c.
+struct FilterResolveArgs {
+    uint32_t kind, m;         // ptflt::Rule, as the host formed it (ptflt::rule)
+    double R, alpha, gR;
+    double a3, a2, a0, b3, b2, b1, b0;
+    const Rgb* lsamp;         // nb * np samples, [s * np + y * width + x]
+    double* state;
+    uint32_t width, height, nb;
+    uint32_t first_sample;    // the sample index of the batch's first sample (spp_offset + the samples of the batches before it)
+    uint32_t n_total;         // samples per pixel once the last batch is in
+    uint32_t load;            // start from the stored sums (else from zero: the pixels' first samples)
+    uint32_t finalize;        // the last samples of the pixels: write the planes
+    float* out_linear;        // np * 3
+    uint8_t* out_rgba;        // np * 4 or null
+    float* out_plain;         // np * 3 or null
+    double* out_wsum;         // np or null
+    uint32_t* zero_words;     // as ResolveArgs
+    uint32_t n_zero;
+};
+void launch_resolve_filter(const FilterResolveArgs& a, hipStream_t st);
+
 // Multi-GPU film exchange (pt_multi.cpp): tile -> 16 B per pixel (linear RGB + RGBA8) before the gather, gathered
 // padded tiles -> frame in image order after it.
 void launch_film_pack(const float* lin, const uint8_t* rgba, uint32_t np, void* packed, hipStream_t st);

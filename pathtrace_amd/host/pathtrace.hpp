@@ -20,6 +20,7 @@
 //   World::render_denoised_upsampled() paths traced at a lower resolution, the film reconstructed under full-size features
 //   World::upsample()                  that reconstruction alone, on host planes (the rule on the CPU)
 //   World::render_cascade()            render() with a firefly-robust film: samples re-weighted through a brightness cascade
+//   World::render_filtered()           render() with a reconstruction filter (tent, Gaussian, Mitchell) in place of the box resolve
 //   World::draw(frame)                        src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
@@ -534,6 +535,27 @@ public:
         std::vector<float> lin(n * 3), raw(plain ? n * 3 : 0);
         std::vector<uint8_t> rgba(n * 4);
         check(pt_render_cascade_host(ctx_, &camera_.pod(), &p, &c, lin.data(), rgba.data(), plain ? raw.data() : nullptr, nullptr, nullptr));
+        unpack(lin, rgba);
+        if (plain) {
+            plain->resize(n);
+            for (size_t i = 0; i < n; ++i) (*plain)[i] = Vector3(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+        }
+    }
+    // render() whose film is reconstructed with a filter (pt_render_filtered_host; flt: pt_default_filter when
+    // null): a pixel also takes its neighbours' samples, weighted by the filter at each sample's own position.  data /
+    // luminance_data hold the filtered film (under Mitchell a value may be negative); plain (optional, y*width+x) receives the
+    // plain film of the same samples.
+    void render_filtered(const PtFilter* flt = nullptr, std::vector<Vector3>* plain = nullptr, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtFilter f{};
+        if (flt) f = *flt; else pt_default_filter(&f);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3), raw(plain ? n * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_filtered_host(ctx_, &camera_.pod(), &p, &f, lin.data(), rgba.data(), plain ? raw.data() : nullptr, nullptr));
         unpack(lin, rgba);
         if (plain) {
             plain->resize(n);

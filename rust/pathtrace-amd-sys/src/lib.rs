@@ -165,6 +165,20 @@ pub struct PtCascade {
     pub kappa: f32,
 }
 
+/// pt_render_filtered_device: the reconstruction filter of the film (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtFilter {
+    pub kind: u32,
+    pub radius: f32,
+    pub a: f32,
+    pub b: f32,
+}
+pub const PT_FILTER_BOX: u32 = 0;
+pub const PT_FILTER_TENT: u32 = 1;
+pub const PT_FILTER_GAUSSIAN: u32 = 2;
+pub const PT_FILTER_MITCHELL: u32 = 3;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct PtStats {
@@ -438,6 +452,14 @@ extern "C" {
     pub fn pt_cascade_samples_device(ctx: *mut PtContext, cs: *const PtCascade, width: u32, height: u32, n: u32, batch: u32, d_samples: *const f32, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
     pub fn pt_cascade_host(cs: *const PtCascade, width: u32, height: u32, n: u32, samples: *const f32, out_linear: *mut f32, out_rgba8: *mut u8, out_plain: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;
     pub fn pt_debug_cascade_split(cs: *const PtCascade, l: f64, j: *mut u32, w_lo: *mut f64, w_hi: *mut f64) -> c_int;
+    pub fn pt_default_filter(out: *mut PtFilter);
+    pub fn pt_render_filtered_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, flt: *const PtFilter, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
+    pub fn pt_render_filtered_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, flt: *const PtFilter, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_plain_linear: *mut f32, out_weight_sum: *mut f64) -> c_int;
+    pub fn pt_filter_samples_device(ctx: *mut PtContext, flt: *const PtFilter, width: u32, height: u32, n: u32, first_sample: u32, batch: u32, d_samples: *const f32, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32, d_weight_sum: *mut f64) -> c_int;
+    pub fn pt_filter_host(flt: *const PtFilter, width: u32, height: u32, n: u32, first_sample: u32, samples: *const f32, out_linear: *mut f32, out_rgba8: *mut u8, out_plain: *mut f32, out_weight_sum: *mut f64) -> c_int;
+    pub fn pt_debug_filter_weight(flt: *const PtFilter, t: f64, f: *mut f64) -> c_int;
+    pub fn pt_debug_filter_offsets(x: u32, y: u32, sample: u32, ox: *mut f64, oy: *mut f64) -> c_int;
+    pub fn pt_debug_filter_exp_neg(e: f64, out: *mut f64) -> c_int;
     pub fn pt_default_gradient(out: *mut PtGradient);
     pub fn pt_temporal_gradient_device(ctx: *mut PtContext, cam: *const PtCamera, prev_params: *const PtRenderParams, seed: u32, d_prev_linear: *const f32, g: *const PtGradient, alpha_min: f32, d_alpha: *mut f32) -> c_int;
     pub fn pt_debug_gradient_strata(ctx: *mut PtContext, width: u32, height: u32, out_xy: *mut u32, out_film: *mut f32, out_rec: *mut f64) -> c_int;
