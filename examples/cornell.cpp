@@ -2,16 +2,19 @@
 // build World::new(), render every pixel, export luminance.csv, and write a PPM of
 // World.data instead of blitting it to a winit/pixels surface (out of scope).
 //
-//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F] [--cascade] [--filter KIND --radius R]       defaults: 400 400 64 cornell 0, no lens
+//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F] [--cascade] [--filter KIND --radius R] [--bloom [INTENSITY]]       defaults: 400 400 64 cornell 0, no lens
 //   --cascade: the film is formed by the brightness cascade (World::render_cascade, pt_default_cascade): fireflies are re-weighted
 //   --filter box|tent|gaussian|mitchell [--radius R]: the film is reconstructed with that filter (World::render_filtered; gaussian:
 //                       alpha 2, mitchell: B = C = 1/3; R defaults to 0.5 / 1 / 1.5 / 2)
+//   --bloom [INTENSITY]: behind the render the film goes through World::display (pt_display_device: bloom with pt_default_bloom and
+//                       that intensity, default 0.05, then auto-exposure and ACES); the PPM is the displayed frame, the CSV the linear film
 //   CORNELL_DENOISE=n: render_denoised with n feature samples (pt_render_denoised) instead of render()
 //   CORNELL_ADAPTIVE_DENOISE=n: render_adaptive_denoised with n feature samples (pt_render_adaptive_denoised): spp is spp_max,
 //                       spp_min 4, spp_step 4, rel_tol 0.1
 //   CORNELL_TEMPORAL=k: k frames of render_denoised_temporal (4 feature samples), frame i at spp_offset i*spp with the camera
 //                       origin moved by (0.01 i, 0.005 i, 0); the files hold the last frame
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +31,9 @@ int main(int argc, char** argv) {
     PtFilter flt;
     pt_default_filter(&flt);
     float flt_radius = 0.0f;
+    bool use_bloom = false;
+    PtBloom bloom;
+    pt_default_bloom(&bloom);
     {
         int keep = 1;
         for (int i = 1; i < argc; ++i) {
@@ -44,6 +50,10 @@ int main(int argc, char** argv) {
                 else if (kind == "tent") { flt.kind = PT_FILTER_TENT; flt.radius = 1.0f; }
                 else if (kind == "mitchell") { flt.kind = PT_FILTER_MITCHELL; flt.radius = 2.0f; flt.a = flt.b = 1.0f / 3.0f; }
                 else if (kind != "gaussian") { std::fprintf(stderr, "--filter: box, tent, gaussian or mitchell\n"); return 2; }
+            } else if (arg == "--bloom") {
+                use_bloom = true;
+                if (i + 1 < argc && (std::isdigit((unsigned char)argv[i + 1][0]) || argv[i + 1][0] == '.') && std::strchr(argv[i + 1], '.'))
+                    bloom.intensity = (float)std::atof(argv[++i]);    // an intensity is written with a point: 0.1 (a bare integer is the width)
             } else if (arg == "--radius" && i + 1 < argc) {
                 flt_radius = (float)std::atof(argv[++i]);
             } else {
@@ -112,6 +122,7 @@ int main(int argc, char** argv) {
                 return false; });
         else
             world.render();
+        if (use_bloom) std::printf("display: bloom intensity %g, log2 exposure %.3f\n", bloom.intensity, world.display(&bloom));
         const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const PtStats st = world.stats();
         std::printf("Rendering complete: %ux%u, %u spp, %zu objects, %.3f s (%.1f Msamples/s), %llu vertices\n", w, h, spp,

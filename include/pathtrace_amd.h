@@ -830,6 +830,59 @@ uint32_t pt_debug_tonemap_bin(float L);
 double pt_debug_tonemap_meter(const uint32_t* hist258, const PtTonemap* tm, int fresh, double log2E_prev);
 int pt_debug_tonemap_pixel(const PtTonemap* tm, float E, const float* rgb, float* out_y, uint8_t* out_rgba8);
 
+/* Bloom (additive to ABI 6): the stage in front of pt_tonemap_device.  The display transform works pixel by pixel, so an
+ * emitter 20 times over white ends as the same 255 as one 1.1 times over; bloom spreads the part of the linear film above a threshold
+ * over its neighbourhood before the curve, and the meter then sees the bloomed film, as a camera's would.  The rule
+ * (pathtrace_amd/csrc/pt_bloom.h), all of it f32 with + - * /, comparisons and selects, so that host and device agree bit for bit;
+ * film c of W x H pixels:
+ *   plan        level 0 is ceil(W/2) x ceil(H/2), level i is ceil(w/2) x ceil(h/2) of level i - 1 and exists while i < levels and
+ *               level i - 1 is larger than 1 x 1; n levels
+ *   bright      L = L(c), the tone mapper's luminance.  L or a channel NaN or +-inf, or L <= 0: b = 0.  Else d = L - T,
+ *               q = min(max(d + k, 0), 2 k), soft = k > 0 ? q q / (4 k) : 0, g = min(max(max(soft, d), 0), clamp), b = max(c, 0) (g / L)
+ *   reduce      film under the bright pass -> level 0, level i -> level i + 1: separable, horizontal first, weights 1/8, 3/8, 3/8, 1/8
+ *               on the source indices 2 x - 1 .. 2 x + 2 clamped to the plane, summed left to right
+ *   expand      up(P): separable, horizontal first; destination j takes 3/4 P[j >> 1] + 1/4 of its neighbour on the side j lies
+ *               (j even: the one before, j odd: the one after), indices clamped
+ *   collect     U_(n-1) = D_(n-1);  U_i = (1 - s) D_i + s up(U_(i+1))
+ *   combine     a = intensity up(U_0);  out = a == 0 ? c : c + a per channel: a pixel without a bloom term is copied bit for bit,
+ *               and a non-finite pixel stays what it was without touching its neighbours
+ * Only pt_display_device applies bloom to an RGBA8 plane; the RGBA8 planes of the render entries carry none, and a multi-GPU render
+ * has no bloom form (the caller can run these entries on the gathered film, on device 0).
+ * PT_ERR_INVALID_ARG, before the context is looked at: a null argument, a plane that is not 4-byte aligned, an image smaller than
+ * 2 x 2 or of more than 2^30 pixels, levels outside 1 .. 8, a field outside the range its comment gives (NaN included).
+ * pt_default_bloom: 6 levels, threshold 1, knee 0.5, clamp +inf, scatter 0.7, intensity 0.05.                                    */
+typedef struct {
+    uint32_t levels;         /* pyramid levels asked for, 1 .. 8                                   */
+    float threshold;         /* T: luminance where bloom starts; finite, >= 0                      */
+    float knee;              /* k: half-width of the soft transition around T; finite, >= 0        */
+    float clamp;             /* cap on a pixel's bright-pass luminance; > 0, +inf allowed          */
+    float scatter;           /* s in [0, 1]: share each level takes from the coarser one           */
+    float intensity;         /* finite, >= 0: weight of the bloom term added to the film           */
+} PtBloom;
+void pt_default_bloom(PtBloom* out);
+/* d_linear_rgb (width*height*3 floats on the device) -> d_out_linear (the same size; may be d_linear_rgb: in place).  Asynchronous
+ * on the context's stream (the caller's after pt_context_set_stream); needs no scene.  The context owns the pyramid buffer, which
+ * grows at the first call of an image size and never afterwards.  PT_ERR_UNSUPPORTED for an image that needs 2^24 tiles or more
+ * (two or three pixels wide or high and of some 2^29 pixels).                                                                       */
+int pt_bloom_device(PtContext* ctx, uint32_t width, uint32_t height, const float* d_linear_rgb, const PtBloom* bloom, float* d_out_linear);
+/* The rule header on the CPU, on host planes.  Needs no GPU and no context; out_linear may be linear_rgb.                          */
+int pt_bloom_host(uint32_t width, uint32_t height, const float* linear_rgb, const PtBloom* bloom, float* out_linear);
+/* pt_bloom_device into a context-owned full-size plane, then pt_tonemap_device from that plane, bit for bit -- the metering and the
+ * exposure state included.  bloom NULL: pt_tonemap_device.  Refuses what either stage refuses, before anything is enqueued.         */
+int pt_display_device(PtContext* ctx, uint32_t width, uint32_t height, const float* d_linear_rgb, const PtBloom* bloom,
+                      const PtTonemap* tm, float* d_out_linear, uint8_t* d_out_rgba8);
+/* pt_display_device with HOST planes (blocking), staged like pt_tonemap_host; out_linear may be NULL.                              */
+int pt_display_host(PtContext* ctx, uint32_t width, uint32_t height, const float* linear_rgb, const PtBloom* bloom, const PtTonemap* tm,
+                    float* out_linear, uint8_t* out_rgba8);
+/* Debug entries, host only.  The plan of (width, height, levels): out_wh receives (w, h) of every level (room for 16 words), n_levels
+ * their number, first_tail_level the first level of at most 32 x 32 texels (w <= 32 and h <= 32; n_levels when there is none), from
+ * which on one workgroup runs the rest of the pyramid in LDS.  One pixel through the bright pass: rgb (3 floats) -> out_b (3).       */
+int pt_debug_bloom_plan(uint32_t width, uint32_t height, uint32_t levels, uint32_t* out_wh, uint32_t* n_levels, uint32_t* first_tail_level);
+int pt_debug_bloom_bright(const PtBloom* bloom, const float* rgb, float* out_b);
+/* Debug: enable = 0 makes the context run every level with the per-level kernels instead of the one-workgroup tail kernel (same
+ * bits, more launches); anything else restores the default.                                                                        */
+int pt_debug_bloom_tail(PtContext* ctx, int enable);
+
 /* Feature-guided upsampling (additive to ABI 6): paths traced on a w x h grid and first-hit features at the full
  * W x H reconstruct a full-size film -- joint bilateral upsampling in the denoiser's demodulated space.  The low camera is
  * the full camera with width / height replaced (the cached frustum fields of PtCamera do not depend on the pixel count).

@@ -132,6 +132,17 @@ class PtTonemap(C.Structure):
     ]
 
 
+class PtBloom(C.Structure):
+    _fields_ = [
+        ("levels", C.c_uint32),
+        ("threshold", C.c_float),
+        ("knee", C.c_float),
+        ("clamp", C.c_float),
+        ("scatter", C.c_float),
+        ("intensity", C.c_float),
+    ]
+
+
 class PtUpsample(C.Structure):
     _fields_ = [
         ("sigma_n", C.c_float),
@@ -346,6 +357,14 @@ SYMBOLS = {
     "pt_cascade_host": (C.c_int, [_P(PtCascade), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "pt_debug_cascade_split": (C.c_int, [_P(PtCascade), C.c_double, _P(C.c_uint32), _P(C.c_double), _P(C.c_double)]),
+    "pt_default_bloom": (None, [_P(PtBloom)]),
+    "pt_bloom_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _P(PtBloom), C.c_void_p]),
+    "pt_bloom_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, _P(PtBloom), C.c_void_p]),
+    "pt_display_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _P(PtBloom), _P(PtTonemap), C.c_void_p, C.c_void_p]),
+    "pt_display_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _P(PtBloom), _P(PtTonemap), C.c_void_p, C.c_void_p]),
+    "pt_debug_bloom_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
+    "pt_debug_bloom_bright": (C.c_int, [_P(PtBloom), C.c_void_p, C.c_void_p]),
+    "pt_debug_bloom_tail": (C.c_int, [C.c_void_p, C.c_int]),
     "pt_default_filter": (None, [_P(PtFilter)]),
     "pt_render_filtered_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtFilter), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_render_filtered_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), _P(PtFilter), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -221,6 +221,46 @@ def default_tonemap(**over):
     return t
 
 
+def default_bloom(**over):
+    """pt_default_bloom (6 levels, threshold 1, knee 0.5, clamp +inf, scatter 0.7, intensity 0.05) with keyword overrides (None
+    keeps the default)."""
+    b = _lib.PtBloom()
+    lib().pt_default_bloom(C.byref(b))
+    for k, v in over.items():
+        if v is not None:
+            if not hasattr(b, k):
+                raise AttributeError(f"PtBloom has no field {k}")
+            setattr(b, k, v)
+    return b
+
+
+def bloom_host(linear, bloom=None):
+    """pt_bloom_host: the bloom rule on the CPU (no device, no context) on a film f32[H,W,3] -> f32[H,W,3]"""
+    bloom = default_bloom() if bloom is None else bloom
+    lin = np.ascontiguousarray(linear, dtype=np.float32)
+    H, W = lin.shape[:2]
+    assert lin.shape == (H, W, 3), lin.shape
+    out = np.empty((H, W, 3), np.float32)
+    check(lib().pt_bloom_host(W, H, lin.ctypes.data_as(C.c_void_p), C.byref(bloom), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def bloom_plan(width, height, levels):
+    """pt_debug_bloom_plan (host only) -> ([(w, h) of every level], first_tail_level)"""
+    wh = np.zeros(16, dtype=np.uint32)
+    n, ft = C.c_uint32(0), C.c_uint32(0)
+    check(lib().pt_debug_bloom_plan(width, height, levels, _pu(wh), C.byref(n), C.byref(ft)))
+    return [(int(wh[2 * i]), int(wh[2 * i + 1])) for i in range(n.value)], ft.value
+
+
+def bloom_bright(bloom, rgb):
+    """pt_debug_bloom_bright (host only): one pixel through the bright pass -> f32[3]"""
+    c = np.ascontiguousarray(rgb, dtype=np.float32).reshape(3)
+    out = np.empty(3, np.float32)
+    check(lib().pt_debug_bloom_bright(C.byref(bloom), c.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def builtin_scene(scene_id, arg=0):
     """Scenes of SURVEY 8(d): 1 reference Cornell box, 2 ten-sphere Cornell, 4 random spheres (arg = n)."""
     n = C.c_uint32(0)
@@ -846,6 +886,30 @@ class _ContextFunctions:
             out = d_lin
         self._on_stream(lib().pt_tonemap_device, W, H, d_lin, C.byref(tm), out, rgba)
         return rgba.cpu().numpy(), out.cpu().numpy()
+
+    def bloom(self, linear, bloom=None, in_place=False):
+        """pt_bloom_device on a film (f32[H,W,3]); bloom: default_bloom().  in_place: the output is the uploaded film.
+        -> the bloomed linear film f32[H,W,3]"""
+        bloom = default_bloom() if bloom is None else bloom
+        H, W = np.shape(linear)[:2]
+        d_lin = self._upload(linear, np.float32, (H, W, 3))
+        out = d_lin if in_place else self._empty((H, W, 3))
+        self._on_stream(lib().pt_bloom_device, W, H, d_lin, C.byref(bloom), out)
+        return out.cpu().numpy()
+
+    def display(self, linear, bloom=None, **over):
+        """pt_display_device on a film (f32[H,W,3]): bloom (a PtBloom; None: no bloom stage, pt_tonemap_device alone), then the
+        tone mapper; the keywords are default_tonemap's.  -> (rgba u8[H,W,4], linear f32[H,W,3] in front of the transfer)"""
+        tm = default_tonemap(**over)
+        H, W = np.shape(linear)[:2]
+        d_lin = self._upload(linear, np.float32, (H, W, 3))
+        out, rgba = self._film_pair(H, W)
+        self._on_stream(lib().pt_display_device, W, H, d_lin, C.byref(bloom) if bloom is not None else None, C.byref(tm), out, rgba)
+        return rgba.cpu().numpy(), out.cpu().numpy()
+
+    def bloom_tail(self, enable=True):
+        """pt_debug_bloom_tail: False runs every pyramid level with the per-level kernels (same bits); True is the default."""
+        check(lib().pt_debug_bloom_tail(self._h, int(bool(enable))))
 
     def exposure_reset(self):
         """pt_exposure_reset: the next auto-exposure frame jumps to its target."""

@@ -253,6 +253,11 @@ struct PtContext {
     // every pixel (7 planes of doubles); grows at first use.  pt_render_filtered_host: device staging of the plain film
     DevBuf<double> flt_state;
     DevBuf<float> flt_plain;
+    // pt_bloom_device: the pyramid, every level three planes of floats; pt_display_device: the bloomed film between
+    // the two stages.  Both grow at the first call of a size and never afterwards.  bloom_no_tail: pt_debug_bloom_tail switched
+    // k_bloom_tail off (the per-level kernels run every level; same bits)
+    DevBuf<float> bloom_pyr, bloom_lin;
+    bool bloom_no_tail = false;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).
@@ -310,6 +315,8 @@ int render_lens_denoised_host(const char* who, PtContext* c, const PtCamera* cam
                               float* out_features);                   // pt_denoise.cpp
 int denoised_frame_device(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                           const PtDenoise* dn, PtRenderParams* p);   // pt_denoise.cpp
+int tonemap_check_args(const char* who, uint32_t width, uint32_t height, const float* d_linear, const PtTonemap* tm, const float* d_out_linear,
+                       const uint8_t* d_out_rgba);                  // pt_tonemap.cpp
 ptk::SceneView view_for(const PtContext* c, uint32_t exact_math);   // pt_scene.cpp
 int ensure_bvh(PtContext* c);                                       // pt_scene.cpp
 hipStream_t pt_internal_stream(PtContext* c);                       // pt_context.cpp

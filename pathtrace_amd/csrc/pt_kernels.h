@@ -512,6 +512,46 @@ void launch_film_histogram(const float* linear, uint32_t np, uint32_t* hist, uin
 void launch_exposure_meter(const ExposureArgs& a, hipStream_t st);
 void launch_tonemap(const TonemapArgs& a, hipStream_t st);
 
+// Bloom (pt_bloom_device; rule: pt_bloom.h).  A pyramid level is three planes (R, G, B) of `stride` floats.
+//   launch_bloom_reduce   one workgroup per 16 x 16 destination tile; first: the source is the film (interleaved RGB) under the bright pass
+//   launch_bloom_expand   one workgroup per 32 x 8 destination tile; last = 0: fine holds D_i and receives U_i = (1 - s) D_i + s up(coarse);
+//                         last = 1: out = film + intensity up(coarse), the combine (out may be film)
+//   launch_bloom_tail     one workgroup: the levels w[0 .. n) x h[0 .. n) in LDS, down and up again; dst receives U of the first of them.
+//                         src: the level above it, which the first is reduced from; null: dst already holds D of the first
+struct BloomRule {             // pbloom::Rule
+    float T, k, clamp, s, oms, intensity;
+};
+struct BloomReduceArgs {
+    const float* src;
+    float* dst;
+    size_t src_stride, dst_stride;
+    uint32_t sw, sh, dw, dh, tiles_x, first;
+    BloomRule r;
+};
+struct BloomExpandArgs {
+    const float* coarse;
+    size_t coarse_stride;
+    uint32_t cw, ch;
+    float* fine;               // last = 0
+    size_t fine_stride;
+    const float* film;         // last = 1
+    float* out;
+    uint32_t w, h, tiles_x, last;
+    BloomRule r;
+};
+struct BloomTailArgs {
+    const float* src;
+    size_t src_stride;
+    uint32_t sw, sh;
+    float* dst;
+    size_t dst_stride;
+    uint32_t n, w[8], h[8];
+    BloomRule r;
+};
+void launch_bloom_reduce(const BloomReduceArgs& a, uint32_t tiles, hipStream_t st);
+void launch_bloom_expand(const BloomExpandArgs& a, uint32_t tiles, hipStream_t st);
+void launch_bloom_tail(const BloomTailArgs& a, hipStream_t st);
+
 // Feature-guided upsampling (pt_upsample_device; rule: pt_upsample.h).  One launch: the low film and its feature
 // records, the full-size records -> the full-size film planes (out_rgba may be null).
 struct UpsampleArgs {

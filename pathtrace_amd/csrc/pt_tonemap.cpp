@@ -45,6 +45,16 @@ int check_tonemap(const char* who, const PtTonemap* tm) {
 
 }  // namespace
 
+// what pt_tonemap_device refuses before it looks at the context (pt_display_device asks the same in front of its bloom stage)
+int tonemap_check_args(const char* who, uint32_t width, uint32_t height, const float* d_linear, const PtTonemap* tm, const float* d_out_linear,
+                       const uint8_t* d_out_rgba) {
+    if (!tm || !d_out_rgba) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc;
+    if ((rc = check_film(who, width, height, d_linear))) return rc;
+    if ((uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u) return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
+    return check_tonemap(who, tm);
+}
+
 extern "C" {
 
 void pt_default_tonemap(PtTonemap* out) {
@@ -73,11 +83,8 @@ int pt_film_histogram_device(PtContext* c, uint32_t width, uint32_t height, cons
 int pt_tonemap_device(PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const PtTonemap* tm, float* d_out_linear,
                       uint8_t* d_out_rgba) {
     const char* who = "pt_tonemap_device";
-    if (!tm || !d_out_rgba) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = check_film(who, width, height, d_linear))) return rc;
-    if ((uintptr_t)d_out_linear % 4u || (uintptr_t)d_out_rgba % 4u) return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
-    if ((rc = check_tonemap(who, tm))) return rc;
+    if ((rc = tonemap_check_args(who, width, height, d_linear, tm, d_out_linear, d_out_rgba))) return rc;
     if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
     HIP_TRY(hipSetDevice(c->device));
     ptk::TonemapArgs t{};

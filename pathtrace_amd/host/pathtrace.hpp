@@ -21,7 +21,8 @@
 //   World::upsample()                  that reconstruction alone, on host planes (the rule on the CPU)
 //   World::render_cascade()            render() with a firefly-robust film: samples re-weighted through a brightness cascade
 //   World::render_filtered()           render() with a reconstruction filter (tent, Gaussian, Mitchell) in place of the box resolve
-//   World::draw(frame)                        src/world.rs:335-341
+//   World::bloom() / World::display()  bloom on the film held; bloom, auto-exposure and tone mapping in one device call
+//   World::draw(frame)                      src/world.rs:335-341
 //   World::export_luminance(path)             src/world.rs:344-369
 //   WIDTH, HEIGHT, SAMPLE_NUM                 src/world.rs:16-18
 //   Ray::new / at / set_eta_ratio             src/camera.rs:9-25
@@ -725,6 +726,42 @@ public:
         std::vector<uint8_t> rgba(n * 4);
         for (size_t i = 0; i < n; ++i) { lin[3 * i] = (float)luminance_data[i].x; lin[3 * i + 1] = (float)luminance_data[i].y; lin[3 * i + 2] = (float)luminance_data[i].z; }
         check(pt_tonemap_host(ctx_, camera_.width(), camera_.height(), lin.data(), &t, mapped ? out.data() : nullptr, rgba.data()));
+        for (size_t i = 0; i < n; ++i) data[i] = Color{rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]};
+        if (mapped) {
+            mapped->resize(n);
+            for (size_t i = 0; i < n; ++i) (*mapped)[i] = Vector3(out[3 * i], out[3 * i + 1], out[3 * i + 2]);
+        }
+        double log2E = 0.0;
+        check(pt_exposure_get(ctx_, &log2E, nullptr));
+        return log2E;
+    }
+    // Bloom on the film this World holds (pt_bloom_host, the rule on the CPU; bl: pt_default_bloom when null): luminance_data
+    // receives the bloomed linear film; data is left as it is (display() maps it).
+    void bloom(const PtBloom* bl = nullptr) {
+        check_abi();
+        PtBloom b{};
+        if (bl) b = *bl; else pt_default_bloom(&b);
+        const size_t n = luminance_data.size();
+        std::vector<float> lin(n * 3);
+        for (size_t i = 0; i < n; ++i) { lin[3 * i] = (float)luminance_data[i].x; lin[3 * i + 1] = (float)luminance_data[i].y; lin[3 * i + 2] = (float)luminance_data[i].z; }
+        check(pt_bloom_host(camera_.width(), camera_.height(), lin.data(), &b, lin.data()));
+        for (size_t i = 0; i < n; ++i) luminance_data[i] = Vector3(lin[3 * i], lin[3 * i + 1], lin[3 * i + 2]);
+    }
+    // tonemap() with the bloom stage in front of it, on the device in one call (pt_display_host = pt_display_device on staged planes;
+    // bl: pt_default_bloom when null): luminance_data -> data.  luminance_data stays the un-bloomed linear film.  Returns log2 of the
+    // exposure the context holds after the frame, metered on the bloomed film.
+    double display(const PtBloom* bl = nullptr, const PtTonemap* tm = nullptr, std::vector<Vector3>* mapped = nullptr, int device = 0) {
+        check_abi();
+        if (!ctx_) check(pt_context_create(device, &ctx_));
+        PtBloom b{};
+        if (bl) b = *bl; else pt_default_bloom(&b);
+        PtTonemap t{};
+        if (tm) t = *tm; else pt_default_tonemap(&t);
+        const size_t n = luminance_data.size();
+        std::vector<float> lin(n * 3), out(mapped ? n * 3 : 0);
+        std::vector<uint8_t> rgba(n * 4);
+        for (size_t i = 0; i < n; ++i) { lin[3 * i] = (float)luminance_data[i].x; lin[3 * i + 1] = (float)luminance_data[i].y; lin[3 * i + 2] = (float)luminance_data[i].z; }
+        check(pt_display_host(ctx_, camera_.width(), camera_.height(), lin.data(), &b, &t, mapped ? out.data() : nullptr, rgba.data()));
         for (size_t i = 0; i < n; ++i) data[i] = Color{rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]};
         if (mapped) {
             mapped->resize(n);

@@ -165,6 +165,18 @@ pub struct PtCascade {
     pub kappa: f32,
 }
 
+/// pt_bloom_device / pt_display_device: the bloom stage in front of the tone mapper (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtBloom {
+    pub levels: u32,
+    pub threshold: f32,
+    pub knee: f32,
+    pub clamp: f32,
+    pub scatter: f32,
+    pub intensity: f32,
+}
+
 /// pt_render_filtered_device: the reconstruction filter of the film (include/pathtrace_amd.h).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -452,6 +464,14 @@ extern "C" {
     pub fn pt_cascade_samples_device(ctx: *mut PtContext, cs: *const PtCascade, width: u32, height: u32, n: u32, batch: u32, d_samples: *const f32, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
     pub fn pt_cascade_host(cs: *const PtCascade, width: u32, height: u32, n: u32, samples: *const f32, out_linear: *mut f32, out_rgba8: *mut u8, out_plain: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;
     pub fn pt_debug_cascade_split(cs: *const PtCascade, l: f64, j: *mut u32, w_lo: *mut f64, w_hi: *mut f64) -> c_int;
+    pub fn pt_default_bloom(out: *mut PtBloom);
+    pub fn pt_bloom_device(ctx: *mut PtContext, width: u32, height: u32, d_linear_rgb: *const f32, bloom: *const PtBloom, d_out_linear: *mut f32) -> c_int;
+    pub fn pt_bloom_host(width: u32, height: u32, linear_rgb: *const f32, bloom: *const PtBloom, out_linear: *mut f32) -> c_int;
+    pub fn pt_display_device(ctx: *mut PtContext, width: u32, height: u32, d_linear_rgb: *const f32, bloom: *const PtBloom, tm: *const PtTonemap, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_display_host(ctx: *mut PtContext, width: u32, height: u32, linear_rgb: *const f32, bloom: *const PtBloom, tm: *const PtTonemap, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_debug_bloom_plan(width: u32, height: u32, levels: u32, out_wh: *mut u32, n_levels: *mut u32, first_tail_level: *mut u32) -> c_int;
+    pub fn pt_debug_bloom_bright(bloom: *const PtBloom, rgb: *const f32, out_b: *mut f32) -> c_int;
+    pub fn pt_debug_bloom_tail(ctx: *mut PtContext, enable: c_int) -> c_int;
     pub fn pt_default_filter(out: *mut PtFilter);
     pub fn pt_render_filtered_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, flt: *const PtFilter, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
     pub fn pt_render_filtered_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, flt: *const PtFilter, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_plain_linear: *mut f32, out_weight_sum: *mut f64) -> c_int;
