@@ -317,6 +317,23 @@ constexpr uint32_t kRegenBlock = PT_REGEN_BLOCK;
 // DENSE0 (the body's own parameter; the kernel below chooses it): a path's first vertex runs where its chunk is taken from the
 // batch, all 64 lanes on camera paths with a ONE-ray scan, instead of in the main loop, where a lane fresh from the ring occupies
 // a slot of the joint scan with an empty ray A.  The ring then holds paths at their second vertex (DenseWave, pt_kernels_vertex.h).
+// ONE_LIGHT (the body's own parameter too, chosen per launch by a wave-uniform branch on the scene's light count; DENSE0 instances
+// only): the scene's one light is read once, here, into scalar registers (OneLight, pt_kernels_vertex.h) and every vertex takes it
+// from there -- no lights[] read, no material and shape record of the light through per-lane addresses, no second emission read, the
+// sphere-or-triangle choice a scalar branch.  Scenes with no light or several take the per-lane code.  The two forms are two
+// copies of the loop in one kernel (a launch runs one of them); they share the workgroup's LDS, which is why it is declared in
+// paths_regen_body and handed down (RegenLds).
+struct RegenLds {            // one wave's parts of the workgroup's LDS
+    float4* pool_d;          // !DENSE0: the ring of camera rays
+    uint32_t* pool_s;
+    float4 *park0, *park1;   // the lane's parked NEE term (DENSE0: park0 and park1d)
+    float2* park1d;
+    DenseWave* dw;           // DENSE0: ring entries and parked terms
+    WgTotals* totals;
+};
+template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT>
+PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc, const RegenLds& w);
+
 template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0>
 PT_DEV void paths_regen_body(const BounceArgs& a) {
     // DENSE0 rebuilds a popped path's incoming eta (1) and its pending throughput (1, 1, 1) instead of storing them: true of a
@@ -345,12 +362,34 @@ PT_DEV void paths_regen_body(const BounceArgs& a) {
     const SceneRef sc = stage_scene<kModeLds>(a.sc, lds);          // (its barrier also publishes the words above)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wib = threadIdx.x >> 6;
-    float4* const pool_d = s_pool_d[wib];
-    uint32_t* const pool_s = s_pool_s[wib];
-    float4* const park0 = DENSE0 ? &s_dense[DENSE0 ? wib : 0u].park0[lane] : &s_park[MIS && !DENSE0 ? wib : 0u][0][DENSE0 ? 0u : lane];
-    float4* const park1 = &s_park[MIS && !DENSE0 ? wib : 0u][1][DENSE0 ? 0u : lane];
-    float2* const park1d = &s_dense[DENSE0 ? wib : 0u].park1[lane];
-    DenseWave& dw = s_dense[DENSE0 ? wib : 0u];
+    RegenLds w;
+    w.pool_d = s_pool_d[DENSE0 ? 0u : wib];
+    w.pool_s = s_pool_s[DENSE0 ? 0u : wib];
+    w.park0 = DENSE0 ? &s_dense[DENSE0 ? wib : 0u].park0[lane] : &s_park[MIS && !DENSE0 ? wib : 0u][0][DENSE0 ? 0u : lane];
+    w.park1 = &s_park[MIS && !DENSE0 ? wib : 0u][1][DENSE0 ? 0u : lane];
+    w.park1d = &s_dense[DENSE0 ? wib : 0u].park1[lane];
+    w.dw = &s_dense[DENSE0 ? wib : 0u];
+    w.totals = &s_totals;
+    if constexpr (DENSE0) {
+        if (sc.n_lights == 1u) { paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, true>(a, sc, w); return; }
+    }
+    paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, false>(a, sc, w);
+}
+
+template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT>
+PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, const RegenLds& w) {
+    SceneRef sc = sc_staged;
+    OneLight ol = OneLight{};
+    if constexpr (ONE_LIGHT) { sc.n_lights = 1u; ol = load_one_light(sc); }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wib = threadIdx.x >> 6;
+    float4* const pool_d = w.pool_d;
+    uint32_t* const pool_s = w.pool_s;
+    float4* const park0 = w.park0;
+    float4* const park1 = w.park1;
+    float2* const park1d = w.park1d;
+    DenseWave& dw = *w.dw;
+    WgTotals& s_totals = *w.totals;
     const uint32_t n_first = a.n_first;
     const uint32_t n_chunks = (n_first + 63u) >> 6;
     const uint32_t W = a.film_w;
@@ -474,12 +513,12 @@ PT_DEV void paths_regen_body(const BounceArgs& a) {
             int qid; float qt;
             scan_closest<kModeLds, false>(sc, q.o, q.d, a.t_min, kInf, qid, qt);
             Vertex qv;
-            vertex_begin<MIS, DIFFUSE>(sc, q, qa, qid, qt, qsample, qkx, qpy, qv);
+            vertex_begin<MIS, DIFFUSE, ONE_LIGHT>(sc, q, qa, qid, qt, qsample, qkx, qpy, qv, &ol);
             wave_vertices += valid;
             wave_shadow += (uint32_t)__popcll(__ballot(qv.need_shadow));
             Pending qpd;
             qpd.on = false; qpd.beta = mk(0.f, 0.f, 0.f); qpd.direct = mk(0.f, 0.f, 0.f);
-            const bool qalive = vertex_end<MIS, DIFFUSE, true, true>(sc, q, qv, false, qsample, qkx, qpy, a.min_depth, a.max_depth, &qpd);
+            const bool qalive = vertex_end<MIS, DIFFUSE, true, true, ONE_LIGHT>(sc, q, qv, false, qsample, qkx, qpy, a.min_depth, a.max_depth, &qpd, &ol);
             // miss, emitter, roulette: the sample is finished (depth 0: dmax stays); it never was in the ring, so it counts here
             const bool qdone = qa && !qalive && !qpd.on;
             if (qdone) a.lsamp[q.s_local * a.np + q.yl * W + q.px] = Rgb{q.L.x, q.L.y, q.L.z};
@@ -582,9 +621,9 @@ PT_DEV void paths_regen_body(const BounceArgs& a) {
             if (ended) retire();
             // ---- the new vertex up to the point where its own visibility is needed
             Vertex v;
-            vertex_begin<MIS, DIFFUSE>(sc, p, active, id, t, sample, kx, py, v);
+            vertex_begin<MIS, DIFFUSE, ONE_LIGHT>(sc, p, active, id, t, sample, kx, py, v, &ol);
             wave_shadow += (uint32_t)__popcll(__ballot(v.need_shadow));
-            alive = vertex_end<MIS, DIFFUSE, true, true>(sc, p, v, false, sample, kx, py, a.min_depth, a.max_depth, &pd);
+            alive = vertex_end<MIS, DIFFUSE, true, true, ONE_LIGHT>(sc, p, v, false, sample, kx, py, a.min_depth, a.max_depth, &pd, &ol);
             sdir = v.light_dir; smax = v.distance - a.t_min;
             park();
             if (active && !alive && !pd.on) retire();

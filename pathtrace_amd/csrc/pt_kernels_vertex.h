@@ -129,9 +129,50 @@ PT_DEV void assume_mats(uint32_t tag) {
     if (MATS == kMatsNoMirror) __builtin_assume(tag != MAT_MIRROR);
     if (MATS == kMatsMirror) __builtin_assume(tag == MAT_MIRROR);
 }
-template <int DIFFUSE>
+// A scene's ONLY light (sc.n_lights == 1; ONE below).  Which object it is, its shape tag, its first shape record and its emission
+// are the same in every lane at every vertex of a launch: a kernel reads them once (load_one_light, after stage_scene) into scalar
+// registers, and sample_light_point / vertex_begin / vertex_end take them from here where they otherwise read lights[], the light's
+// material (twice: REMAT) and its shape record through per-lane addresses and branch on the tag lane by lane.  The samplers get the
+// same numbers in the same order; only where an operand comes from differs.  An object that emits IS the light (the light list is the
+// objects whose material emits: pt_host.cpp), so the look-ahead pdf of an emitter hit takes the same record.
+struct OneLight {
+    int obj;
+    uint32_t shape_tag;
+    float4 r0;               // sphere: (centre, radius); triangle: (v0, normal.x) -- its other records are read where they are needed
+    f3 emission;
+};
+PT_DEV float wave_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+PT_DEV OneLight load_one_light(const SceneRef& sc) {
+    const int obj = (int)sc.lights[0];
+    const Mat lm = load_mat(sc.mat, obj);
+    const float4 r0 = sc.shape[3 * obj];
+    OneLight ol;
+    ol.obj = __builtin_amdgcn_readfirstlane(obj);
+    ol.shape_tag = (uint32_t)__builtin_amdgcn_readfirstlane((int)lm.shape_tag);
+    ol.r0 = make_float4(wave_uniform(r0.x), wave_uniform(r0.y), wave_uniform(r0.z), wave_uniform(r0.w));
+    ol.emission = mk(wave_uniform(lm.color.x), wave_uniform(lm.color.y), wave_uniform(lm.color.z));
+    return ol;
+}
+// shape_sample for that light: the tag is wave-uniform, so the sampler is chosen by a scalar branch
+PT_DEV void one_light_sample(const SceneRef& sc, const OneLight& ol, f3 from, bool with_target, f3 target, float r1, float r2, f3& point,
+                             float& pdf_omega, f3& dir, float& dist) {
+    if (ol.shape_tag == SHAPE_SPHERE) {
+        sphere_sample(ol.r0, from, with_target, target, r1, r2, point, pdf_omega, dir, dist);
+    } else {
+        const float4 q1 = sc.shape[3 * ol.obj + 1], q2 = sc.shape[3 * ol.obj + 2];      // (one address for all lanes: broadcast reads)
+        triangle_sample(mk(ol.r0.x, ol.r0.y, ol.r0.z), mk(q1.x, q1.y, q1.z), mk(q2.x, q2.y, q2.z), mk(ol.r0.w, q1.w, q2.w),
+                        sc.mat[2 * ol.obj + 1].w, from, with_target, target, r1, r2, point, pdf_omega, dir, dist);
+    }
+}
+template <int DIFFUSE, bool ONE = false>
 PT_DEV void sample_light_point(const SceneRef& sc, f3 from, uint32_t w_index, uint32_t w_r1, uint32_t w_r2, f3& point,
-                               int& lobj, f3& emission, float& pdf, f3& dir, float& dist) {
+                               int& lobj, f3& emission, float& pdf, f3& dir, float& dist, const OneLight* ol = nullptr) {
+    if constexpr (ONE) {
+        lobj = ol->obj;
+        one_light_sample(sc, *ol, from, false, from, u01(w_r1), u01(w_r2), point, pdf, dir, dist);
+        emission = ol->emission;                                                  // world.rs:259; pdf: world.rs:260 (x/1 == x)
+        return;
+    }
     const uint32_t li = __umulhi(w_index, sc.n_lights);                           // random_range(0..n), world.rs:255
     lobj = (int)sc.lights[li];
     const Mat lm = load_mat(sc.mat, lobj);
@@ -147,9 +188,10 @@ PT_DEV void sample_light_point(const SceneRef& sc, f3 from, uint32_t w_index, ui
 // DIFFUSE: the scene has Lambertian and emissive materials only (decided at pt_scene_upload); the GGX and
 // OrenNayar code is then compiled out of the kernel (same results; smaller code, no spills at 6 waves/SIMD: C2 +2 %).
 // (kx, py) = the pixel's RNG key (main.rs:51); it is the path's film position except in pixel-list renders.
-template <bool MIS, int DIFFUSE>
+// ONE: the scene has exactly one light and `ol` holds it (OneLight above).
+template <bool MIS, int DIFFUSE, bool ONE = false>
 PT_DEV void vertex_begin(const SceneRef& sc, PathState& p, bool active, int id, float t, uint32_t sample, uint32_t kx,
-                         uint32_t py, Vertex& v) {
+                         uint32_t py, Vertex& v, const OneLight* ol = nullptr) {
     v.alive = active && id >= 0;
     v.obj = id >= 0 ? id : 0; v.light_obj = 0;
     v.hit_emitter = false; v.emit_pdf_shape = 0.0f;
@@ -166,7 +208,8 @@ PT_DEV void vertex_begin(const SceneRef& sc, PathState& p, bool active, int id, 
                 // emitter reached by a BSDF-sampled ray: its MIS weight (vertex_end) is against the light pdf of
                 // this point seen from the previous vertex = this ray's origin (rendering.rs:107-116)
                 f3 sp, sd; float sl;
-                shape_sample(sc.shape, sc.mat, id, v.m.shape_tag, p.o, true, v.hit.point, 0.f, 0.f, sp, v.emit_pdf_shape, sd, sl);
+                if constexpr (ONE) one_light_sample(sc, *ol, p.o, true, v.hit.point, 0.f, 0.f, sp, v.emit_pdf_shape, sd, sl);
+                else shape_sample(sc.shape, sc.mat, id, v.m.shape_tag, p.o, true, v.hit.point, 0.f, 0.f, sp, v.emit_pdf_shape, sd, sl);
             }
             v.alive = false;
         }
@@ -182,16 +225,16 @@ PT_DEV void vertex_begin(const SceneRef& sc, PathState& p, bool active, int id, 
         philox4x32_draw(kx, py, sample, p.depth, BLK_SURFACE, 0u, ds);
         v.w_bsdf1 = ds[2]; v.w_bsdf2 = ds[3];
         v.w_rr = (ds[0] << 23) | ((ds[1] & 0x1FFu) << 14) | ((ds[2] & 0x1FFu) << 5);   // roulette word: the bits of the block u01() skips
-        if (MIS && sc.n_lights > 0u) {
+        if (MIS && (ONE || sc.n_lights > 0u)) {
             uint32_t w_index = 0u;                                                // umulhi(u, 1) = 0: one light needs no draw
-            if (sc.n_lights > 1u) {
+            if (!ONE && sc.n_lights > 1u) {
                 uint32_t dc[4];
                 philox4x32_draw(kx, py, sample, p.depth, BLK_CHOICE, 0u, dc);
                 w_index = dc[0]; v.w_lobe = dc[1];
             }
             f3 lp;                                                                // rendering.rs:58-60: direction and distance
-            sample_light_point<DIFFUSE>(sc, v.hit.point, w_index, ds[0], ds[1], lp, v.light_obj, v.ls_emission, v.ls_pdf,
-                                        v.light_dir, v.distance);                 // to the point, from the sampler itself
+            sample_light_point<DIFFUSE, ONE>(sc, v.hit.point, w_index, ds[0], ds[1], lp, v.light_obj, v.ls_emission, v.ls_pdf,
+                                             v.light_dir, v.distance, ol);        // to the point, from the sampler itself
             v.need_shadow = true;
         }
     }
@@ -218,16 +261,18 @@ PT_DEV void vertex_finish(PathState& p, Pending& pd, bool visible) {
         pd.on = false;
     }
 }
-template <bool MIS, int DIFFUSE, bool REMAT, bool DEFER = false>
+// ONE: the light's emission is ol.emission; nothing of the light is read again.
+template <bool MIS, int DIFFUSE, bool REMAT, bool DEFER = false, bool ONE = false>
 PT_DEV bool vertex_end(const SceneRef& sc, PathState& p, const Vertex& vin, bool visible, uint32_t sample, uint32_t kx,
-                       uint32_t py, uint32_t min_depth, uint32_t max_depth, Pending* pd = nullptr) {
-    const uint32_t n_lights = sc.n_lights;
+                       uint32_t py, uint32_t min_depth, uint32_t max_depth, Pending* pd = nullptr, const OneLight* ol = nullptr) {
+    const uint32_t n_lights = ONE ? 1u : sc.n_lights;
     Vertex v = vin;
     if (REMAT) {
         asm volatile("" ::: "memory");          // a real re-read, not the values of vertex_begin kept alive
         v.m = load_mat(sc.mat, vin.obj);
-        v.ls_emission = load_mat(sc.mat, vin.light_obj).color;
+        if constexpr (!ONE) v.ls_emission = load_mat(sc.mat, vin.light_obj).color;
     }
+    if constexpr (ONE) v.ls_emission = ol->emission;
     if (DIFFUSE != kMatsMirror) assume_mats<DIFFUSE>(v.m.tag);
     else if (vin.alive) assume_mats<DIFFUSE>(v.m.tag);         // (a lane without a path re-reads object 0's material)
     if (vin.hit_emitter) {
