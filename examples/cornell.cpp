@@ -2,7 +2,9 @@
 // build World::new(), render every pixel, export luminance.csv, and write a PPM of
 // World.data instead of blitting it to a winit/pixels surface (out of scope).
 //
-//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F] [--cascade] [--filter KIND --radius R] [--bloom [INTENSITY]]       defaults: 400 400 64 cornell 0, no lens
+//   ./cornell [width height spp [out_prefix [exact_math]]] [--aperture A --focus F] [--projection ortho|fisheye|equirect [--fov DEG]] [--cascade] [--filter KIND --radius R] [--bloom [INTENSITY]]       defaults: 400 400 64 cornell 0, no lens
+//   --projection ortho|fisheye|equirect [--fov DEG]: another projection of the same camera (World::render_projection; --fov: the
+//                       fisheye's field of view across the width, default 180)
 //   --cascade: the film is formed by the brightness cascade (World::render_cascade, pt_default_cascade): fireflies are re-weighted
 //   --filter box|tent|gaussian|mitchell [--radius R]: the film is reconstructed with that filter (World::render_filtered; gaussian:
 //                       alpha 2, mitchell: B = C = 1/3; R defaults to 0.5 / 1 / 1.5 / 2)
@@ -27,7 +29,9 @@ int main(int argc, char** argv) {
     // optional, anywhere on the line: --aperture A --focus F (a thin lens, World::render_lens; with CORNELL_DENOISE its denoised form)
     PtLens lens;
     pt_default_lens(&lens);
-    bool use_lens = false, use_cascade = false, use_filter = false;
+    bool use_lens = false, use_cascade = false, use_filter = false, use_projection = false;
+    Projection projection = Projection::Perspective;
+    double projection_fov = 180.0;
     PtFilter flt;
     pt_default_filter(&flt);
     float flt_radius = 0.0f;
@@ -41,6 +45,15 @@ int main(int argc, char** argv) {
             if ((arg == "--aperture" || arg == "--focus") && i + 1 < argc) {
                 (arg == "--aperture" ? lens.aperture : lens.focus_distance) = std::atof(argv[++i]);
                 use_lens = true;
+            } else if (arg == "--projection" && i + 1 < argc) {
+                const std::string kind = argv[++i];
+                use_projection = true;
+                if (kind == "ortho") projection = Projection::Orthographic;
+                else if (kind == "fisheye") projection = Projection::Fisheye;
+                else if (kind == "equirect") projection = Projection::Equirect;
+                else { std::fprintf(stderr, "--projection: ortho, fisheye or equirect\n"); return 2; }
+            } else if (arg == "--fov" && i + 1 < argc) {
+                projection_fov = std::atof(argv[++i]);
             } else if (arg == "--cascade") {
                 use_cascade = true;
             } else if (arg == "--filter" && i + 1 < argc) {
@@ -107,6 +120,8 @@ int main(int argc, char** argv) {
             world.render_lens_denoised(lens, (uint32_t)std::atoi(std::getenv("CORNELL_DENOISE")));
         else if (use_lens)
             world.render_lens(lens);
+        else if (use_projection)
+            world.render_projection(projection, projection_fov);
         else if (use_cascade)
             world.render_cascade();
         else if (use_filter) {

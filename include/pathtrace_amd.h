@@ -973,6 +973,69 @@ int pt_debug_lens_rays(PtContext* ctx, const PtCamera* cam, const PtLens* lens, 
 /* Debug, host only: out7 = Lu3, Lv3, inv_phi as the device receives them.  Needs no device. */
 int pt_debug_lens_setup(const PtCamera* cam, const PtLens* lens, float* out7);
 
+/* Projections and films from the caller's rays (additive to ABI 6).  The projection travels beside PtCamera; the
+ * rule (pathtrace_amd/csrc/pt_projection.h):
+ *   host, f64   C = lower_left + horizontal/2 + vertical/2 - origin, Wv = C/|C|, U = horizontal/|horizontal|,
+ *               V = vertical/|vertical|, aspect = |vertical|/|horizontal|; the device receives them rounded to f32
+ *   per sample  in the render's arithmetic, from the ONE Philox block the pinhole ray draws for (x, y, sample): words 0, 1 the
+ *               pixel jitter as ever; u, v and `dir` by the pinhole ray's own statements; a = 2u - 1, b = 2v - 1
+ *     PERSPECTIVE   o = origin, d = normalize(dir): the pinhole ray, and every entry below is its pinhole entry bit for bit
+ *     ORTHOGRAPHIC  o = origin + (dir - C), d = Wv: the view window is |horizontal| x |vertical| at the camera plane
+ *     FISHEYE       equidistant: bb = b aspect, rho = sqrt(a a + bb bb), theta = min(rho fov/720, 1/2) revolutions off the axis,
+ *                   d = normalize(cos Wv + sin (a/rho) U + sin (bb/rho) V), d = Wv at rho = 0, o = origin.  No masking: the
+ *                   corners see further, to at most 180 degrees off the axis
+ *     EQUIRECT      longitude a/2 revolutions, latitude b/4: d = normalize(cos(lat) (sin(lon) U + cos(lon) Wv) + sin(lat) V),
+ *                   o = origin.  Column 0 looks backwards on the left, the centre column along Wv, rows from +V (top) to -V
+ * The path kernels do not know the projection: the rays reach them as given paths, as the lens rays do, each traced with key
+ * (x, y) and its own sample index.
+ * PT_ERR_INVALID_ARG, and the context untouched, for: a null argument, an unknown kind, a reserved word that is not 0, a fisheye
+ * fov_degrees that is not finite or outside (0, 360], a degenerate camera (|C| or an axis of length 0 or not finite), and
+ * everything the pinhole entry refuses.
+ * Out of scope: the temporal, motion and gradient entries keep assuming a pinhole, and there is no lens, cascade, filtered,
+ * adaptive, progressive or multi-GPU form of the projection render.                                                          */
+enum { PT_PROJ_PERSPECTIVE = 0, PT_PROJ_ORTHOGRAPHIC = 1, PT_PROJ_FISHEYE = 2, PT_PROJ_EQUIRECT = 3 };
+typedef struct {
+    uint32_t kind;           /* PT_PROJ_*                                                                                     */
+    uint32_t reserved;       /* 0                                                                                             */
+    double fov_degrees;      /* FISHEYE only: the angle the image's width spans; finite, in (0, 360]                          */
+} PtProjection;
+void pt_default_projection(PtProjection* out);   /* perspective, fov 180 */
+/* pt_render_device under the projection (asynchronous on the context's stream), with the film, row bands, batching by
+ * max_paths_in_flight and plane ownership of pt_render_lens_device.                                                          */
+int pt_render_projection_device(PtContext* ctx, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* params,
+                                float* d_linear_rgb, uint8_t* d_rgba8);
+/* The same into host buffers (blocking), as pt_render_host. */
+int pt_render_projection_host(PtContext* ctx, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* params,
+                              float* out_linear_rgb, uint8_t* out_rgba8);
+/* pt_render_features_device with projection rays: the same records, sums and checks. */
+int pt_render_features_projection_device(PtContext* ctx, const PtCamera* cam, const PtProjection* proj,
+                                         const PtRenderParams* params, uint32_t n_samples, float* d_features);
+/* pt_render_denoised under the projection (host buffers, blocking): bit-identical to pt_render_projection_device ->
+ * pt_render_features_projection_device -> pt_denoise_device.                                                                 */
+int pt_render_projection_denoised(PtContext* ctx, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* params,
+                                  uint32_t feature_samples, const PtDenoise* dn, float* out_linear_rgb, uint8_t* out_rgba8,
+                                  float* out_noisy_linear, float* out_features);
+/* A film from the caller's own rays (asynchronous on the context's stream).  d_rays6: device float[spp][tile rows][width][6] =
+ * origin3, direction3, sample-major with the pixel fastest, 8-byte aligned; the planes hold the tile's rows only (row bands as
+ * in pt_render_device).  d_weights3: device float[spp][tile rows][width][3], the initial throughput of every ray, or NULL = 1.
+ * The ray of plane s at (row, x) is traced as sample spp_offset + s of that pixel, key (x, image row); the film is the mean
+ * through the ordinary resolve.  Directions are TAKEN AS GIVEN and not normalised, so rays this library produced come back bit
+ * for bit; a direction that is not a unit vector gives what the path kernels make of it.  max_paths_in_flight cuts the job
+ * into sample batches and the film does not depend on them.  The caller keeps the planes alive until the stream has passed
+ * the call.  width and tile rows < 65536.  PT_ERR_INVALID_ARG, and the context untouched, for a NULL d_rays6 or context, a
+ * misaligned buffer, spp = 0, and everything the pinhole entry refuses.                                                      */
+int pt_render_rays_device(PtContext* ctx, uint32_t width, uint32_t height, const PtRenderParams* params, const float* d_rays6,
+                          const float* d_weights3, float* d_linear_rgb, uint8_t* d_rgba8);
+/* Debug: the projection's rays of n (x, y, sample) triples (x, y the film position, top-down) on the device:
+ * out8 = n * (o3, d3, a, b).  Host arrays, blocking; needs no scene.                                                         */
+int pt_debug_projection_rays(PtContext* ctx, const PtCamera* cam, const PtProjection* proj, const uint32_t* xys, uint32_t n,
+                             uint32_t exact_math, float* out8);
+/* Host only: out11 = U3, V3, Wv3, aspect, fov_degrees/720 (0 unless FISHEYE) as the device receives them.  Needs no device. */
+int pt_projection_setup_host(const PtCamera* cam, const PtProjection* proj, float* out11);
+/* Host only: the rule on the CPU in the render's exact arithmetic, out8 as pt_debug_projection_rays with exact_math = 1, bit
+ * for bit.  Needs no device.                                                                                                 */
+int pt_projection_rays_host(const PtCamera* cam, const PtProjection* proj, const uint32_t* xys, uint32_t n, float* out8);
+
 /* Brightness cascade (additive to ABI 6): a firefly-robust film.  The samples of a render are averaged into the film
  * by an estimator that knows which of them are outliers -- the re-weighting of Zirr, Hanika and Dachsbacher (2018): every sample
  * is split between two layers of a per-pixel cascade by its luminance, and a layer keeps its energy in full only where enough

@@ -157,6 +157,17 @@ class PtLens(C.Structure):
     ]
 
 
+class PtProjection(C.Structure):
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("fov_degrees", C.c_double),
+    ]
+
+
+PT_PROJ_PERSPECTIVE, PT_PROJ_ORTHOGRAPHIC, PT_PROJ_FISHEYE, PT_PROJ_EQUIRECT = 0, 1, 2, 3
+
+
 class PtCascade(C.Structure):
     _fields_ = [
         ("layers", C.c_uint32),
@@ -341,6 +352,16 @@ SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_debug_lens_rays": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtLens), _P(C.c_uint32), C.c_uint32, C.c_uint32, _P(C.c_float)]),
     "pt_debug_lens_setup": (C.c_int, [_P(PtCamera), _P(PtLens), _P(C.c_float)]),
+    "pt_default_projection": (None, [_P(PtProjection)]),
+    "pt_render_projection_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtProjection), _P(PtRenderParams), C.c_void_p, C.c_void_p]),
+    "pt_render_projection_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtProjection), _P(PtRenderParams), C.c_void_p, C.c_void_p]),
+    "pt_render_features_projection_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtProjection), _P(PtRenderParams), C.c_uint32, C.c_void_p]),
+    "pt_render_projection_denoised": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtProjection), _P(PtRenderParams), C.c_uint32, _P(PtDenoise), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_render_rays_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(PtRenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_debug_projection_rays": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtProjection), _P(C.c_uint32), C.c_uint32, C.c_uint32, _P(C.c_float)]),
+    "pt_projection_setup_host": (C.c_int, [_P(PtCamera), _P(PtProjection), _P(C.c_float)]),
+    "pt_projection_rays_host": (C.c_int, [_P(PtCamera), _P(PtProjection), _P(C.c_uint32), C.c_uint32, _P(C.c_float)]),
     "pt_default_upsample": (None, [_P(PtUpsample)]),
     "pt_upsample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                      _P(PtUpsample), C.c_void_p, C.c_void_p]),

@@ -178,6 +178,36 @@ def lens_setup(cam, lens):
     return out
 
 
+PROJECTION_KINDS = {"perspective": 0, "orthographic": 1, "ortho": 1, "fisheye": 2, "equirect": 3}
+
+
+def default_projection(**over):
+    """pt_default_projection (perspective, fov 180) with keyword overrides (None keeps the default); kind may be a PT_PROJ_*
+    number or one of "perspective", "orthographic" ("ortho"), "fisheye", "equirect"."""
+    p = _lib.PtProjection()
+    lib().pt_default_projection(C.byref(p))
+    for k, v in over.items():
+        if v is not None:
+            setattr(p, k, PROJECTION_KINDS[v] if k == "kind" and isinstance(v, str) else v)
+    return p
+
+
+def projection_setup(cam, proj):
+    """pt_projection_setup_host (host only): -> float32[11] = U3, V3, Wv3, aspect, fov/720 as the device receives them."""
+    out = np.empty(11, dtype=np.float32)
+    check(lib().pt_projection_setup_host(C.byref(cam), C.byref(proj), _pf(out)))
+    return out
+
+
+def projection_rays_host(cam, proj, xys):
+    """pt_projection_rays_host (host only): the rule on the CPU in exact arithmetic.  xys n x (x, y film row, sample)
+    -> float32[n, 8] = origin3, direction3, a, b"""
+    xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+    out = np.empty((xys.shape[0], 8), dtype=np.float32)
+    check(lib().pt_projection_rays_host(C.byref(cam), C.byref(proj), _pu(xys), xys.shape[0], _pf(out)))
+    return out
+
+
 def upsample_host(lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
     """pt_upsample_host: the upsampling rule on the CPU (no device, no context), on a low film (f32[h,w,3]), its features
     (f32[h,w,8]) and the full-size features (f32[H,W,8]).  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
@@ -650,6 +680,62 @@ class _ContextFunctions:
         planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32))
         check(lib().pt_render_lens_denoised(self._h, C.byref(cam), C.byref(lens), C.byref(params), feature_samples, C.byref(dn), *ptrs))
         return planes
+
+    def render_projection(self, cam, proj, params, want_rgba=True):
+        """pt_render_projection_device: render() under a projection (default_projection).  -> (linear[rows,W,3] f32,
+        rgba[rows,W,4] u8 or None), torch device tensors"""
+        rows = tile_rows(cam.height, params.band_rows, params.band_index, params.band_count or 1)
+        lin = self._empty((rows, cam.width, 3))
+        rgba = self._empty((rows, cam.width, 4), "uint8") if want_rgba else None
+        self._on_stream(lib().pt_render_projection_device, C.byref(cam), C.byref(proj), C.byref(params), lin, rgba)
+        return lin, rgba
+
+    def render_features_projection(self, cam, proj, params, n_samples):
+        """pt_render_features_projection_device: render_features with projection rays.  -> f32[H,W,8]"""
+        feat = self._empty((cam.height, cam.width, 8))
+        self._on_stream(lib().pt_render_features_projection_device, C.byref(cam), C.byref(proj), C.byref(params), n_samples, feat)
+        return feat.cpu().numpy()
+
+    def render_projection_denoised(self, cam, proj, params, feature_samples=4, iterations=None, sigma_l=None, sigma_n=None, sigma_d=None):
+        """pt_render_projection_denoised (host buffers, blocking).  -> (linear f32[H,W,3], rgba u8[H,W,4], noisy linear
+        f32[H,W,3], features f32[H,W,8])"""
+        dn = default_denoise(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_d=sigma_d)
+        planes, ptrs = self._host_planes(cam.height, cam.width, (3, np.float32), (4, np.uint8), (3, np.float32), (8, np.float32))
+        check(lib().pt_render_projection_denoised(self._h, C.byref(cam), C.byref(proj), C.byref(params), feature_samples, C.byref(dn), *ptrs))
+        return planes
+
+    def projection_rays(self, cam, proj, xys, exact_math=0):
+        """pt_debug_projection_rays: xys n x (x, y film row, sample) -> float32[n, 8] = origin3, direction3, a, b"""
+        xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+        out = np.empty((xys.shape[0], 8), dtype=np.float32)
+        check(lib().pt_debug_projection_rays(self._h, C.byref(cam), C.byref(proj), _pu(xys), xys.shape[0], exact_math, _pf(out)))
+        return out
+
+    def render_rays(self, rays, weights=None, params=None, height=None, want_rgba=True):
+        """pt_render_rays_device: a film from the caller's own rays.  rays: a torch device tensor f32[spp, rows, W, 6] = origin3,
+        direction3 (directions are taken as given, not normalised); weights: f32[spp, rows, W, 3], every ray's initial
+        throughput, or None = 1; params: default_params() when None, its spp is taken from the tensor; height: the image's
+        height when the tensor holds one row band of it (params.band_*), default: its rows.  Runs on torch's current stream,
+        no host round trip.  -> (linear[rows,W,3] f32, rgba[rows,W,4] u8 or None), torch device tensors"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not (isinstance(rays, torch.Tensor) and rays.device == dev and rays.dtype == torch.float32 and rays.dim() == 4 and rays.shape[3] == 6):
+            raise ValueError("rays: a float32 tensor [spp, rows, W, 6] on this context's device")
+        rays = rays.contiguous()
+        spp, rows, W = (int(v) for v in rays.shape[:3])
+        if weights is not None:
+            if not (isinstance(weights, torch.Tensor) and weights.device == dev and weights.dtype == torch.float32 and tuple(weights.shape) == (spp, rows, W, 3)):
+                raise ValueError("weights: a float32 tensor [spp, rows, W, 3] on this context's device")
+            weights = weights.contiguous()
+        prm = _lib.PtRenderParams.from_buffer_copy(params) if params is not None else default_params()
+        prm.spp = spp
+        H = rows if height is None else height
+        if tile_rows(H, prm.band_rows, prm.band_index, prm.band_count or 1) != rows:
+            raise ValueError("rays: %d rows, but the tile of a %d-row image has %d" % (rows, H, tile_rows(H, prm.band_rows, prm.band_index, prm.band_count or 1)))
+        lin = self._empty((rows, W, 3))
+        rgba = self._empty((rows, W, 4), "uint8") if want_rgba else None
+        self._on_stream(lib().pt_render_rays_device, W, H, C.byref(prm), rays, weights, lin, rgba)
+        return lin, rgba
 
     def upsample(self, lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
         """pt_upsample_device on a low film (f32[h,w,3]), its features (f32[h,w,8]) and the full-size features (f32[H,W,8]);

@@ -480,22 +480,22 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
     return PT_OK;
 }
 
-// The thin-lens render.  The path kernels do not know the lens: per sample batch k_lens_paths writes the lens rays
-// of the tile as path states into the context's inject planes, and render_impl takes them up as given paths of the tile
+// The renders of injected camera paths: the thin lens, the projections and the caller's rays (5q).  The path kernels
+// know none of them: per sample batch `fill` enqueues the launch that writes the batch's rays as path states into the context's
+// inject planes (k_lens_paths, k_projection_paths, k_ray_paths), and render_impl takes them up as given paths of the tile
 // (ListRender::tile: the launches of pt_ray_color, the film slots, keys and bands of a plain render).  One render_impl per batch
 // of nb <= max_paths_in_flight / np samples; the f64 film sums travel between the batches as they do between the increments of
 // pt_render_progressive, so the film does not depend on the batching.  Everything is checked, and the planes are there, before
 // the first launch; all launches are on the caller's stream, which orders batch k's level-0 launch (the planes' only reader)
-// before batch k + 1's k_lens_paths.
-int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,
-                     uint8_t* d_rgba) {
-    if (!c || !cam || !lens || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+// before batch k + 1's fill.  The caller has checked what is its own (the lens, the projection, the ray planes) before.
+int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const InjectFill& fill, float* d_linear,
+                         uint8_t* d_rgba) {
+    if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
     ListRender lr;
     lr.tile = true;
     lr.inject[0] = reinterpret_cast<const float4*>(1);      // (check_render only asks whether the paths are given)
-    ptk::LensPathsArgs a{};
-    if ((rc = lens_setup(who, cam, lens, &a.lens)) || (rc = check_render(c, cam, prm, &lr, d_linear, d_rgba))) return rc;
+    if ((rc = check_render(c, cam, prm, &lr, d_linear, d_rgba))) return rc;
     const uint64_t np64 = tile_pixels(cam, prm);
     if (np64 == 0) return render_impl(c, cam, prm, FilmState{}, nullptr, d_linear, d_rgba);      // an empty tile, as ever
     if (!d_linear) return fail(PT_ERR_INVALID_ARG, "render: the linear output buffer is null");
@@ -510,18 +510,18 @@ int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const P
     HIP_TRY(hipSetDevice(c->device));
     for (int k = 0; k < 4; ++k)
         if ((rc = c->inject[k].ensure((size_t)np * nb_max))) return rc;
-    a.cam = camera_f32(cam);
-    a.tile = tile_map(cam, prm);
-    a.np = np; a.np_magic = magic_of(np); a.w_magic = magic_of(cam->width);
-    for (int k = 0; k < 4; ++k) { a.q[k] = c->inject[k].p; lr.inject[k] = c->inject[k].p; }
+    InjectBatch b{};
+    b.tile = tile_map(cam, prm);
+    b.np = np; b.np_magic = magic_of(np); b.w_magic = magic_of(cam->width);
+    for (int k = 0; k < 4; ++k) { b.q[k] = c->inject[k].p; lr.inject[k] = c->inject[k].p; }
     for (uint32_t done = 0; done < prm->spp;) {
         const uint32_t nb = std::min(nb_max, prm->spp - done);
         PtRenderParams p = *prm;
         p.spp = nb;
         p.spp_offset = prm->spp_offset + done;
         p.max_paths_in_flight = cap;      // (the cap the batches were cut for, whatever default the sizing would pick)
-        a.s_base = p.spp_offset; a.n = np * nb;
-        if (prm->exact_math) ptk::launch_lens_paths_exact(a, c->stream); else ptk::launch_lens_paths_fast(a, c->stream);
+        b.s_base = p.spp_offset; b.done = done; b.nb = nb; b.n = np * nb;
+        fill(b);
         HIP_TRY(hipGetLastError());
         lr.inject_spp = nb;
         FilmState fs;
@@ -532,6 +532,63 @@ int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const P
         done += nb;
     }
     return PT_OK;
+}
+
+// pt_render_lens_device in the name `who`: k_lens_paths fills the planes
+int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,
+                     uint8_t* d_rgba) {
+    if (!c || !cam || !lens || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    ptk::LensPathsArgs a{};
+    if (int rc = lens_setup(who, cam, lens, &a.lens)) return rc;
+    a.cam = camera_f32(cam);
+    const bool exact = prm->exact_math;
+    hipStream_t const st = c->stream;
+    return render_injected_impl(who, c, cam, prm, [&a, exact, st](const InjectBatch& b) {
+        a.tile = b.tile;
+        a.np = b.np; a.np_magic = b.np_magic; a.w_magic = b.w_magic;
+        for (int k = 0; k < 4; ++k) a.q[k] = b.q[k];
+        a.s_base = b.s_base; a.n = b.n;
+        if (exact) ptk::launch_lens_paths_exact(a, st); else ptk::launch_lens_paths_fast(a, st);
+    }, d_linear, d_rgba);
+}
+
+// pt_render_projection_device in the name `who`: k_projection_paths fills the planes
+int render_projection_impl(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
+                           float* d_linear, uint8_t* d_rgba) {
+    if (!c || !cam || !proj || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    ptk::ProjPathsArgs a{};
+    if (int rc = projection_setup(who, cam, proj, &a.proj)) return rc;
+    a.cam = camera_f32(cam);
+    const bool exact = prm->exact_math;
+    hipStream_t const st = c->stream;
+    return render_injected_impl(who, c, cam, prm, [&a, exact, st](const InjectBatch& b) {
+        a.tile = b.tile;
+        a.np = b.np; a.np_magic = b.np_magic; a.w_magic = b.w_magic;
+        for (int k = 0; k < 4; ++k) a.q[k] = b.q[k];
+        a.s_base = b.s_base; a.n = b.n;
+        if (exact) ptk::launch_projection_paths_exact(a, st); else ptk::launch_projection_paths_fast(a, st);
+    }, d_linear, d_rgba);
+}
+
+// pt_render_rays_device: k_ray_paths turns the batch's share of the caller's planes into path states
+int render_rays_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const float* d_rays6, const float* d_weights3,
+                     float* d_linear, uint8_t* d_rgba) {
+    if (!c || !cam || !prm || !d_rays6) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if ((uintptr_t)d_rays6 % 8u) return fail(PT_ERR_INVALID_ARG, "%s: d_rays6 must be 8-byte aligned", who);
+    if ((uintptr_t)d_weights3 % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_weights3 must be 4-byte aligned", who);
+    const bool exact = prm->exact_math;
+    hipStream_t const st = c->stream;
+    const uint32_t width = cam->width;
+    return render_injected_impl(who, c, cam, prm, [=](const InjectBatch& b) {
+        ptk::RayPathsArgs a{};
+        const size_t first = (size_t)b.done * b.np;       // the states before this batch's
+        a.rays6 = d_rays6 + 6 * first;
+        a.weights3 = d_weights3 ? d_weights3 + 3 * first : nullptr;
+        for (int k = 0; k < 4; ++k) a.q[k] = b.q[k];
+        a.width = width; a.np = b.np; a.np_magic = b.np_magic; a.w_magic = b.w_magic;
+        a.n = b.n;
+        if (exact) ptk::launch_ray_paths_exact(a, st); else ptk::launch_ray_paths_fast(a, st);
+    }, d_linear, d_rgba);
 }
 
 extern "C" {

@@ -2,6 +2,7 @@
 // resources, struct PtContext and the few functions that cross files.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -303,6 +304,29 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
                 float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr,
                 const CascadePass* cas = nullptr, const FilterPass* flt = nullptr);   // pt_api.cpp
 int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad);   // pt_api.cpp
+// The driver of every render of injected camera paths (pt_api.cpp): `fill` enqueues, per sample batch, the launch that writes the
+// batch's n = nb * np path states (samples s_base .. s_base + nb - 1 of the tile's np pixels, `done` samples before them) into q.
+struct InjectBatch {
+    float4* q[4];
+    ptk::TileMap tile;
+    uint32_t np, np_magic, w_magic;   // tile pixels; floor(2^32 / np) and floor(2^32 / width) for divmod_magic
+    uint32_t s_base, done, nb, n;
+};
+using InjectFill = std::function<void(const InjectBatch&)>;
+int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const InjectFill& fill, float* d_linear,
+                         uint8_t* d_rgba);
+// pt_render_projection_device and pt_render_rays_device in the name `who` (pt_api.cpp); pt_projection.cpp: the projection and the
+// camera checked, the device's words; pt_denoise.cpp: the projection forms of the feature pass and the one-call frame
+int render_projection_impl(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
+                           float* d_linear, uint8_t* d_rgba);
+int render_rays_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const float* d_rays6, const float* d_weights3,
+                     float* d_linear, uint8_t* d_rgba);
+int projection_setup(const char* who, const PtCamera* cam, const PtProjection* proj, ptk::ProjF* out);
+int features_projection_device(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
+                               uint32_t n_samples, float* d_features);
+int render_projection_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
+                                    uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                                    float* out_features);
 // pt_render_lens_device in the name `who` (pt_api.cpp); pt_lens.cpp: the lens and the camera checked, the device's words
 int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,
                      uint8_t* d_rgba);

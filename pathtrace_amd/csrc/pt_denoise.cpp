@@ -93,9 +93,9 @@ ptk::DenoiseArgs denoise_args(const PtContext* c, uint32_t width, uint32_t heigh
 // The front of a pt_render_denoised* frame: staging for np pixels, then the render into host_lin, the features into dn_feat and, from
 // History::motion on, the ids into dn_ids.  History::alpha (the gradient entries): gr_alpha too, and no previous frame from here on.
 int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
-                  float* d_features, int32_t* d_ids);
+                  float* d_features, int32_t* d_ids, const PtProjection* proj = nullptr);
 int frame_front(History form, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, size_t np, PtRenderParams* p,
-                const PtLens* lens = nullptr) {
+                const PtLens* lens = nullptr, const PtProjection* proj = nullptr) {
     int rc;
     if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) || (rc = c->dn_lin.ensure(3 * np)) ||
         (form >= History::motion && (rc = c->dn_ids.ensure(np))) || (form == History::alpha && (rc = c->gr_alpha.ensure(np))))
@@ -106,6 +106,13 @@ int frame_front(History form, PtContext* c, const PtCamera* cam, const PtRenderP
     if (lens) {                               // pt_render_lens_denoised: both passes through the lens (History::none only)
         if ((rc = render_lens_impl("pt_render_lens_denoised", c, cam, lens, p, c->host_lin.p, nullptr)) ||
             (rc = features_impl("pt_render_lens_denoised", c, cam, lens, p, std::min(feature_samples, p->spp), reinterpret_cast<float*>(c->dn_feat.p), nullptr)))
+            return rc;
+        return PT_OK;
+    }
+    if (proj) {                               // pt_render_projection_denoised: both passes through the projection (History::none only)
+        if ((rc = render_projection_impl("pt_render_projection_denoised", c, cam, proj, p, c->host_lin.p, nullptr)) ||
+            (rc = features_impl("pt_render_projection_denoised", c, cam, nullptr, p, std::min(feature_samples, p->spp),
+                                reinterpret_cast<float*>(c->dn_feat.p), nullptr, proj)))
             return rc;
         return PT_OK;
     }
@@ -125,14 +132,17 @@ int copy_back(std::initializer_list<CopyBack> copies) {
 // First-hit features: per batch of samples, k_feature_rays writes the camera rays, launch_debug_hit (the scan or BVH of the
 // parity entries) finds their hits, k_feature_resolve adds the records to the per-pixel sums in d_features.
 // pt_render_feature_ids_device is the same pass over the one sample spp_offset without the resolve: the hit ids of that batch,
-// copied out of the scratch (d_features null, d_ids set).  lens (pt_render_features_lens_device): k_lens_feature_rays writes the rays.
+// copied out of the scratch (d_features null, d_ids set).  lens (pt_render_features_lens_device): k_lens_feature_rays writes the rays;
+// proj (pt_render_features_projection_device): k_projection_feature_rays does.
 int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
-                  float* d_features, int32_t* d_ids) {
+                  float* d_features, int32_t* d_ids, const PtProjection* proj) {
     if (!c || !cam || !prm || (!d_features && !d_ids)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (n_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: n_samples must be > 0", who);
     int rc;
     ptk::LensF lf{};
     if (lens && (rc = lens_setup(who, cam, lens, &lf))) return rc;
+    ptk::ProjF pf{};
+    if (proj && (rc = projection_setup(who, cam, proj, &pf))) return rc;
     if ((rc = check_whole_image(who, "works on", prm))) return rc;
     if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
     if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
@@ -164,11 +174,13 @@ int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLe
         a.np = np; a.nb = nb; a.n_samples = n_samples; a.load = done > 0; a.finalize = done + nb == n_samples;
         if (prm->exact_math) {
             if (lens) ptk::launch_lens_feature_rays_exact(cf, lf, s_base, nb, c->ft_rays.p, st);
+            else if (proj) ptk::launch_projection_feature_rays_exact(cf, pf, s_base, nb, c->ft_rays.p, st);
             else ptk::launch_feature_rays_exact(cf, s_base, nb, c->ft_rays.p, st);
             ptk::launch_debug_hit_exact(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
             if (d_features) ptk::launch_feature_resolve_exact(a, st);
         } else {
             if (lens) ptk::launch_lens_feature_rays_fast(cf, lf, s_base, nb, c->ft_rays.p, st);
+            else if (proj) ptk::launch_projection_feature_rays_fast(cf, pf, s_base, nb, c->ft_rays.p, st);
             else ptk::launch_feature_rays_fast(cf, s_base, nb, c->ft_rays.p, st);
             ptk::launch_debug_hit_fast(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
             if (d_features) ptk::launch_feature_resolve_fast(a, st);
@@ -196,18 +208,21 @@ int denoise_steps(PtContext* c, ptk::DenoiseArgs a, uint32_t iterations) {
 // ids pass): render, features, filter; host buffers, blocking
 int render_denoised_impl(const char* who, History form, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                          const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                         float* out_features, int32_t* out_ids, const PtLens* lens = nullptr) {
+                         float* out_features, int32_t* out_ids, const PtLens* lens = nullptr,
+                         const PtProjection* proj = nullptr) {
     if (!c || !cam || !prm || !dn || (form != History::none && !tp) || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
     ptk::LensF checked;
     if (lens && (rc = lens_setup(who, cam, lens, &checked))) return rc;
+    ptk::ProjF proj_checked;
+    if (proj && (rc = projection_setup(who, cam, proj, &proj_checked))) return rc;
     if ((rc = check_whole_image(who, "renders", prm))) return rc;
     if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
     if ((rc = check_target(who, c, cam))) return rc;
     const size_t np = (size_t)cam->width * cam->height;
     HIP_TRY(hipSetDevice(c->device));
     PtRenderParams p;
-    if ((rc = frame_front(form, c, cam, prm, feature_samples, np, &p, lens))) return rc;
+    if ((rc = frame_front(form, c, cam, prm, feature_samples, np, &p, lens, proj))) return rc;
     float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
     uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
     if ((rc = form == History::motion  ? pt_denoise_temporal_motion_device(c, cam, c->host_lin.p, feat, c->dn_ids.p, dn, tp, c->dn_lin.p, rgba)
@@ -442,6 +457,18 @@ int render_lens_denoised_host(const char* who, PtContext* c, const PtCamera* cam
                               float* out_features) {
     return render_denoised_impl(who, History::none, c, cam, prm, feature_samples, dn, nullptr, out_linear, out_rgba, out_noisy, out_features,
                                 nullptr, lens);
+}
+
+// The projection forms of the same two (their entries: pt_projection.cpp), proj not null
+int features_projection_device(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
+                               uint32_t n_samples, float* d_features) {
+    return features_impl(who, c, cam, nullptr, prm, n_samples, d_features, nullptr, proj);
+}
+int render_projection_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
+                                    uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                                    float* out_features) {
+    return render_denoised_impl(who, History::none, c, cam, prm, feature_samples, dn, nullptr, out_linear, out_rgba, out_noisy, out_features,
+                                nullptr, nullptr, proj);
 }
 
 extern "C" {

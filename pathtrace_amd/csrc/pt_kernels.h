@@ -588,4 +588,37 @@ void launch_lens_feature_rays_fast(const CameraF& cam, const LensF& lens, uint32
 void launch_debug_lens_rays_exact(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
 void launch_debug_lens_rays_fast(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
 
+// Projections and caller rays (pt_render_projection_device, pt_render_rays_device; rule: pt_projection.h).  ProjF:
+// ptproj::Setup as the kernels take it, and the kind (PT_PROJ_*), which every kernel branches on once.
+// launch_projection_paths / _feature_rays / launch_debug_projection_rays: their lens namesakes with projection rays
+// (out8 = n * (o3, d3, a, b)).  launch_ray_paths: the caller's n = nb * np rays (rays6: float[n][6] in state order, 8-byte
+// aligned; weights3: float[n][3] or null = 1) as path states in the queue form; directions as given.
+struct ProjF {
+    float u[3], v[3], w[3], c[3], aspect, fov720;
+    uint32_t kind;
+};
+struct ProjPathsArgs {
+    CameraF cam;
+    ProjF proj;
+    TileMap tile;
+    float4* q[4];
+    uint32_t np, np_magic, w_magic;   // as LensPathsArgs
+    uint32_t s_base, n;
+};
+struct RayPathsArgs {
+    const float* rays6;
+    const float* weights3;
+    float4* q[4];
+    uint32_t width, np, np_magic, w_magic;
+    uint32_t n;
+};
+void launch_projection_paths_exact(const ProjPathsArgs& a, hipStream_t st);
+void launch_projection_paths_fast(const ProjPathsArgs& a, hipStream_t st);
+void launch_projection_feature_rays_exact(const CameraF& cam, const ProjF& pj, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
+void launch_projection_feature_rays_fast(const CameraF& cam, const ProjF& pj, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
+void launch_debug_projection_rays_exact(const CameraF& cam, const ProjF& pj, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
+void launch_debug_projection_rays_fast(const CameraF& cam, const ProjF& pj, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
+void launch_ray_paths_exact(const RayPathsArgs& a, hipStream_t st);
+void launch_ray_paths_fast(const RayPathsArgs& a, hipStream_t st);
+
 }  // namespace ptk

@@ -34,6 +34,7 @@
 #include "pt_kernels_scan.h"
 #include "pt_kernels_vertex.h"
 #include "pt_lens.h"
+#include "pt_projection.h"
 
 namespace PTK_IMPL {
 
@@ -1118,5 +1119,136 @@ void PT_LAUNCH(launch_lens_feature_rays)(const CameraF& cam, const LensF& lens, 
 }
 void PT_LAUNCH(launch_debug_lens_rays)(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st) {
     if (n) hipLaunchKernelGGL(PTK_IMPL::k_debug_lens_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, lens, words, n, out8);
+}
+}  // namespace ptk
+
+// ------------------------------------------------------------------ projections and caller rays (pt_render_projection_device,
+// pt_render_rays_device; rule: pt_projection.h)
+// projection_ray: camera_ray's block of draws and its statements up to `dir` (ptproj::screen), then the kind's rule.  The kind is
+// a kernel argument, the same for every lane: each kernel branches on it once, around the whole per-lane rule (KIND is a template
+// argument of everything below the branch).  As with the lens, the path kernels do not know the projection: the rays reach them
+// as path states in the queue form.
+//   k_projection_paths          k_lens_paths with projection rays: state i = s_local * np + tile pixel, one 16-byte store per
+//                               lane and plane
+//   k_projection_feature_rays   k_feature_rays with projection rays
+//   k_debug_projection_rays     words[4] = x, y, sample, - -> out[8] = o3, d3, a, b
+//   k_ray_paths                 the caller's rays, float[n][6] in state order (sample-major, the pixel fastest), as path states;
+//                               the directions are taken as given (not normalised); weights3 (float[n][3], or null = 1): the
+//                               initial throughput.  A lane reads its 24 bytes as three 8-byte words (rays6 is 8-byte aligned).
+namespace PTK_IMPL {
+struct ProjMath {
+    static PT_DEV float div(float a, float b) { return pt_div(a, b); }
+    static PT_DEV float sqrt(float x) { return pt_sqrt(x); }
+    static PT_DEV void sincos2pi(float u, float& s, float& c) { PTD_NS::sincos2pi(u, s, c); }
+};
+template <int KIND>
+PT_DEV void projection_ray(const CameraF& cam, const ProjF& pj, uint32_t sample, uint32_t px, uint32_t py, f3& o, f3& d, float& a, float& b) {
+    uint32_t dc[4];
+    philox4x32_draw(px, py, sample, kDepthCamera, BLK_SURFACE, 0u, dc);
+    float u, v, dir[3];
+    ptproj::screen<ProjMath>(cam.origin, cam.lower_left, cam.horizontal, cam.vertical, cam.width, cam.height, px, py, u01(dc[0]), u01(dc[1]),
+                             &u, &v, dir);
+    ptproj::Setup P;
+    for (int k = 0; k < 3; ++k) { P.u[k] = pj.u[k]; P.v[k] = pj.v[k]; P.w[k] = pj.w[k]; P.c[k] = pj.c[k]; }
+    P.aspect = pj.aspect; P.fov720 = pj.fov720;
+    float oo[3], dd[3];
+    const bool unnormalised = ptproj::ray<ProjMath, KIND>(P, cam.origin, u, v, dir, oo, dd, &a, &b);
+    o = mk(oo[0], oo[1], oo[2]);
+    d = mk(dd[0], dd[1], dd[2]);
+    if (unnormalised) d = normalize(d);
+}
+template <int KIND>
+PT_DEV void projection_path(const ProjPathsArgs& a, uint32_t i) {
+    uint32_t s_local, pix, yl, px;
+    divmod_magic(i, a.np, a.np_magic, s_local, pix);
+    divmod_magic(pix, a.cam.width, a.w_magic, yl, px);
+    f3 o, d; float sa, sb;
+    projection_ray<KIND>(a.cam, a.proj, a.s_base + s_local, px, image_row(a.tile, yl), o, d, sa, sb);
+    a.q[0][i] = make_float4(o.x, o.y, o.z, d.x);
+    a.q[1][i] = make_float4(d.y, d.z, __uint_as_float((yl << 16) | px), __uint_as_float(s_local << 16));
+    a.q[2][i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+    a.q[3][i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+}
+__global__ void __launch_bounds__(kBlock) k_projection_paths(ProjPathsArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    switch (a.proj.kind) {
+    case ptproj::kOrthographic: projection_path<ptproj::kOrthographic>(a, i); break;
+    case ptproj::kFisheye: projection_path<ptproj::kFisheye>(a, i); break;
+    case ptproj::kEquirect: projection_path<ptproj::kEquirect>(a, i); break;
+    default: projection_path<ptproj::kPerspective>(a, i); break;
+    }
+}
+template <int KIND>
+PT_DEV void projection_feature_ray(const CameraF& cam, const ProjF& pj, uint32_t s_base, uint32_t i, float* __restrict__ rays6) {
+    const uint32_t np = cam.width * cam.height;
+    const uint32_t s = i / np, p = i - s * np;
+    const uint32_t y = p / cam.width, x = p - y * cam.width;
+    f3 o, d; float sa, sb;
+    projection_ray<KIND>(cam, pj, s_base + s, x, y, o, d, sa, sb);
+    float* r = rays6 + 6 * (size_t)i;
+    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+}
+__global__ void __launch_bounds__(kBlock) k_projection_feature_rays(CameraF cam, ProjF pj, uint32_t s_base, uint32_t nb, float* __restrict__ rays6) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nb * cam.width * cam.height) return;
+    switch (pj.kind) {
+    case ptproj::kOrthographic: projection_feature_ray<ptproj::kOrthographic>(cam, pj, s_base, i, rays6); break;
+    case ptproj::kFisheye: projection_feature_ray<ptproj::kFisheye>(cam, pj, s_base, i, rays6); break;
+    case ptproj::kEquirect: projection_feature_ray<ptproj::kEquirect>(cam, pj, s_base, i, rays6); break;
+    default: projection_feature_ray<ptproj::kPerspective>(cam, pj, s_base, i, rays6); break;
+    }
+}
+template <int KIND>
+PT_DEV void debug_projection_ray(const CameraF& cam, const ProjF& pj, const uint32_t* __restrict__ w, float* __restrict__ out) {
+    f3 o, d; float sa, sb;
+    projection_ray<KIND>(cam, pj, w[2], w[0], w[1], o, d, sa, sb);
+    out[0] = o.x; out[1] = o.y; out[2] = o.z; out[3] = d.x; out[4] = d.y; out[5] = d.z; out[6] = sa; out[7] = sb;
+}
+__global__ void __launch_bounds__(kBlock) k_debug_projection_rays(CameraF cam, ProjF pj, const uint32_t* __restrict__ words, uint32_t n,
+                                                                  float* __restrict__ out8) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* w = words + 4 * (size_t)i;
+    float* out = out8 + 8 * (size_t)i;
+    switch (pj.kind) {
+    case ptproj::kOrthographic: debug_projection_ray<ptproj::kOrthographic>(cam, pj, w, out); break;
+    case ptproj::kFisheye: debug_projection_ray<ptproj::kFisheye>(cam, pj, w, out); break;
+    case ptproj::kEquirect: debug_projection_ray<ptproj::kEquirect>(cam, pj, w, out); break;
+    default: debug_projection_ray<ptproj::kPerspective>(cam, pj, w, out); break;
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_ray_paths(RayPathsArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    uint32_t s_local, pix, yl, px;
+    divmod_magic(i, a.np, a.np_magic, s_local, pix);
+    divmod_magic(pix, a.width, a.w_magic, yl, px);
+    const float2* __restrict__ r = reinterpret_cast<const float2*>(a.rays6) + 3 * (size_t)i;
+    const float2 r0 = r[0], r1 = r[1], r2 = r[2];
+    float wx = 1.0f, wy = 1.0f, wz = 1.0f;
+    if (a.weights3) {
+        const float* __restrict__ w = a.weights3 + 3 * (size_t)i;
+        wx = w[0]; wy = w[1]; wz = w[2];
+    }
+    a.q[0][i] = make_float4(r0.x, r0.y, r1.x, r1.y);
+    a.q[1][i] = make_float4(r2.x, r2.y, __uint_as_float((yl << 16) | px), __uint_as_float(s_local << 16));
+    a.q[2][i] = make_float4(wx, wy, wz, 0.0f);
+    a.q[3][i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void PT_LAUNCH(launch_projection_paths)(const ProjPathsArgs& a, hipStream_t st) {
+    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_projection_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+void PT_LAUNCH(launch_projection_feature_rays)(const CameraF& cam, const ProjF& pj, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st) {
+    const uint32_t n = nb * cam.width * cam.height;
+    if (n) hipLaunchKernelGGL(PTK_IMPL::k_projection_feature_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, pj, s_base, nb, rays6);
+}
+void PT_LAUNCH(launch_debug_projection_rays)(const CameraF& cam, const ProjF& pj, const uint32_t* words, uint32_t n, float* out8, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(PTK_IMPL::k_debug_projection_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, pj, words, n, out8);
+}
+void PT_LAUNCH(launch_ray_paths)(const RayPathsArgs& a, hipStream_t st) {
+    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_ray_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
 }
 }  // namespace ptk

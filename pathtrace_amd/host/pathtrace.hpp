@@ -86,6 +86,11 @@ private:
     int code_;
 };
 inline void check(int rc) { if (rc != PT_OK) throw PtError(rc, pt_last_error()); }
+
+// The projections of World::render_projection (PT_PROJ_*)
+enum class Projection : uint32_t {
+    Perspective = PT_PROJ_PERSPECTIVE, Orthographic = PT_PROJ_ORTHOGRAPHIC, Fisheye = PT_PROJ_FISHEYE, Equirect = PT_PROJ_EQUIRECT
+};
 // A binary built against another ABI version of the header must not call into the library (struct sizes differ: PtStats grew in
 // version 4): every context of this mirror is created through here.
 inline void check_abi() {
@@ -477,6 +482,33 @@ public:
         std::vector<uint8_t> rgba(n * 4);
         check(pt_render_lens_host(ctx_, &camera_.pod(), &lens, &p, lin.data(), rgba.data()));
         unpack(lin, rgba);
+    }
+    // render() under another projection (pt_render_projection_host).  fov_degrees: the fisheye's field of view
+    // across the image's width, (0, 360]; Projection::Perspective is render()'s film bit for bit.
+    void render_projection(Projection kind, double fov_degrees = 180.0, int device = 0) {
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtProjection proj;
+        pt_default_projection(&proj);
+        proj.kind = (uint32_t)kind;
+        proj.fov_degrees = fov_degrees;
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        std::vector<float> lin(n * 3);
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_projection_host(ctx_, &camera_.pod(), &proj, &p, lin.data(), rgba.data()));
+        unpack(lin, rgba);
+    }
+    // A film from the caller's own rays (pt_render_rays_device), everything in DEVICE memory: d_rays6 float[spp][height][width][6] =
+    // origin3, direction3 (taken as given, not normalised), 8-byte aligned; d_weights3 float[spp][height][width][3], the rays'
+    // initial throughput, or null = 1; the film goes to d_linear_rgb (float[height][width][3]) and d_rgba8 (may be null).
+    // Asynchronous on the context's stream: the caller keeps the planes alive until that stream has passed the call.
+    void render_rays(const float* d_rays6, const float* d_weights3, float* d_linear_rgb, uint8_t* d_rgba8, int device = 0) {
+        scene(device);
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        check(pt_render_rays_device(ctx_, camera_.width(), camera_.height(), &p, d_rays6, d_weights3, d_linear_rgb, d_rgba8));
     }
     // render_denoised() through the lens (pt_render_lens_denoised): the features are those of the lens rays.
     void render_lens_denoised(const PtLens& lens, uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, std::vector<Vector3>* noisy = nullptr,

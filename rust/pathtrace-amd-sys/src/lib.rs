@@ -139,6 +139,19 @@ pub const PT_CURVE_ACES: u32 = 2;
 pub const PT_TRANSFER_SQRT: u32 = 0;
 pub const PT_TRANSFER_SRGB: u32 = 1;
 
+/// pt_render_projection_device: the projection beside the camera (include/pathtrace_amd.h); kind = PT_PROJ_*.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtProjection {
+    pub kind: u32,
+    pub reserved: u32,
+    pub fov_degrees: f64,
+}
+pub const PT_PROJ_PERSPECTIVE: u32 = 0;
+pub const PT_PROJ_ORTHOGRAPHIC: u32 = 1;
+pub const PT_PROJ_FISHEYE: u32 = 2;
+pub const PT_PROJ_EQUIRECT: u32 = 3;
+
 /// pt_render_lens_device: the thin lens beside the camera (include/pathtrace_amd.h); aperture 0 = pinhole.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -458,6 +471,15 @@ extern "C" {
     pub fn pt_render_lens_denoised(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
     pub fn pt_debug_lens_rays(ctx: *mut PtContext, cam: *const PtCamera, lens: *const PtLens, xys: *const u32, n: u32, exact_math: u32, out8: *mut f32) -> c_int;
     pub fn pt_debug_lens_setup(cam: *const PtCamera, lens: *const PtLens, out7: *mut f32) -> c_int;
+    pub fn pt_default_projection(out: *mut PtProjection);
+    pub fn pt_render_projection_device(ctx: *mut PtContext, cam: *const PtCamera, proj: *const PtProjection, params: *const PtRenderParams, d_linear_rgb: *mut f32, d_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_projection_host(ctx: *mut PtContext, cam: *const PtCamera, proj: *const PtProjection, params: *const PtRenderParams, out_linear_rgb: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_features_projection_device(ctx: *mut PtContext, cam: *const PtCamera, proj: *const PtProjection, params: *const PtRenderParams, n_samples: u32, d_features: *mut f32) -> c_int;
+    pub fn pt_render_projection_denoised(ctx: *mut PtContext, cam: *const PtCamera, proj: *const PtProjection, params: *const PtRenderParams, feature_samples: u32, dn: *const PtDenoise, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_noisy_linear: *mut f32, out_features: *mut f32) -> c_int;
+    pub fn pt_render_rays_device(ctx: *mut PtContext, width: u32, height: u32, params: *const PtRenderParams, d_rays6: *const f32, d_weights3: *const f32, d_linear_rgb: *mut f32, d_rgba8: *mut u8) -> c_int;
+    pub fn pt_debug_projection_rays(ctx: *mut PtContext, cam: *const PtCamera, proj: *const PtProjection, xys: *const u32, n: u32, exact_math: u32, out8: *mut f32) -> c_int;
+    pub fn pt_projection_setup_host(cam: *const PtCamera, proj: *const PtProjection, out11: *mut f32) -> c_int;
+    pub fn pt_projection_rays_host(cam: *const PtCamera, proj: *const PtProjection, xys: *const u32, n: u32, out8: *mut f32) -> c_int;
     pub fn pt_default_cascade(out: *mut PtCascade);
     pub fn pt_render_cascade_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
     pub fn pt_render_cascade_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_plain_linear: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;
