@@ -1036,6 +1036,66 @@ int pt_projection_setup_host(const PtCamera* cam, const PtProjection* proj, floa
  * for bit.  Needs no device.                                                                                                 */
 int pt_projection_rays_host(const PtCamera* cam, const PtProjection* proj, const uint32_t* xys, uint32_t n, float* out8);
 
+/* Light baking (additive to ABI 6): the light that arrives at surface points (lightmaps) and at points in space
+ * (irradiance probes, as spherical harmonics).  The path kernels do not know: the rays reach them as given paths, as the lens
+ * and projection rays do, with the keys, film slots and resolve of a plain render.  The rule (pathtrace_amd/csrc/pt_bake.h):
+ *   texel ray   one record per texel, float[H][W][6] = point3, normal3.  Sample s of texel (x, y) takes words 0 and 1 of the ONE
+ *               Philox block the pinhole ray draws for the key (x, y, s): r1 = u01(w0), r2 = u01(w1); nn = normalize(normal) in
+ *               f32; d = the cosine-weighted direction about nn of the materials' own sampler; o = point as it is (t_min keeps
+ *               the ray off its surface, as for every continuation ray); throughput 1.  The film is the cosine-weighted mean
+ *               radiance E / pi: times a Lambert albedo it is the outgoing radiance.
+ *   empty texel one of its six numbers is not finite, or the f32 square of its normal's length is below 1e-36 or not finite.
+ *               Its outputs are +0.0 and the RGBA8 pixel of a black film pixel, whatever the scene; the render's sample count
+ *               stays W H spp.
+ *   probe ray   direction r of R, the same for every probe and sample: z = 1 - (2r + 1) / R; phase = the top 24 bits of
+ *               (r * 0x9E3779B9) mod 2^32, in revolutions; d = (sqrt(1 - z^2) cos, sqrt(1 - z^2) sin, z); o = the probe's
+ *               position; solid-angle weight 4 pi / R.  spp > 1 repeats the direction with independent continuations.
+ *   SH          real spherical harmonics through l = 2, coefficient k = l (l + 1) + m, constants 0.282095, 0.488603, 1.092548,
+ *               0.315392, 0.546274: sh[p][k][c] = (4 pi / R) sum_r radiance[p][r][c] Y_k(d_r), in f64 in a fixed order (lane j
+ *               of 64 sums r = j, j + 64, ..., then a pairwise tree), d_r the rule's direction in exact arithmetic.  Host and
+ *               device agree bit for bit.
+ *   irradiance  E(n) = sum A_l sh_lm Y_lm(n), A = (pi, 2 pi / 3, pi / 4).
+ * Under PT_INTEGRATOR_MIS the path kernels carry the reference's MIS weights, which do not sum to 1; a baked
+ * texel's first bounce is plain cosine sampling with emitters counted in full, so a bake differs from what a camera sees of the
+ * same Lambert point by that documented bias.  Under PT_INTEGRATOR_BRDF_ONLY the two agree in expectation.
+ * Every entry checks everything before its first launch.  PT_ERR_INVALID_ARG, with a message and the context untouched, for: a
+ * null or misaligned plane, a zero size, rays_per_probe = 0, a size of 65536 or more, band_count > 1, and everything the pinhole
+ * entry refuses.  Not there: a lens, filter, cascade, adaptive, progressive or multi-GPU form, and row bands.                 */
+enum { PT_BAKE_TEXELS = 0, PT_BAKE_PROBES = 1 };
+/* A lightmap (asynchronous on the context's stream).  d_texels6: device float[height][width][6], 8-byte aligned.
+ * d_linear_rgb: device float[height][width][3]; d_rgba8: device uint8[height][width][4], 4-byte aligned, or NULL.
+ * width, height in [1, 65535]; max_paths_in_flight cuts the job into sample batches and the film does not depend on them.     */
+int pt_bake_lightmap_device(PtContext* ctx, uint32_t width, uint32_t height, const float* d_texels6, const PtRenderParams* params,
+                            float* d_linear_rgb, uint8_t* d_rgba8);
+/* The same from and into host buffers (blocking). */
+int pt_bake_lightmap_host(PtContext* ctx, uint32_t width, uint32_t height, const float* texels6, const PtRenderParams* params,
+                          float* out_linear_rgb, uint8_t* out_rgba8);
+/* Probes (asynchronous on the context's stream).  d_positions3: device float[n_probes][3].  d_radiance: device
+ * float[n_probes][rays_per_probe][3], the film -- a probe per row, a direction per column --, the mean over spp.  d_sh27: device
+ * float[n_probes][9][3], or NULL.  n_probes, rays_per_probe in [1, 65535].                                                    */
+int pt_bake_probes_device(PtContext* ctx, const float* d_positions3, uint32_t n_probes, uint32_t rays_per_probe,
+                          const PtRenderParams* params, float* d_radiance, float* d_sh27);
+/* The same from and into host buffers (blocking); out_sh27 may be NULL. */
+int pt_bake_probes_host(PtContext* ctx, const float* positions3, uint32_t n_probes, uint32_t rays_per_probe,
+                        const PtRenderParams* params, float* out_radiance, float* out_sh27);
+/* The SH projection of radiance planes the caller holds on the device (asynchronous on the context's stream); needs no scene. */
+int pt_sh_project_device(PtContext* ctx, uint32_t n_probes, uint32_t rays_per_probe, const float* d_radiance, float* d_sh27);
+/* Host only: the same on the CPU, bit for bit.  Needs no device. */
+int pt_sh_project_host(uint32_t n_probes, uint32_t rays_per_probe, const float* radiance, float* sh27);
+/* Host only: the irradiance E(n) of ONE probe's coefficients sh27 = float[9][3] at n normals (normalised in f64 first; a normal
+ * of length 0 gives 0): out_rgb = float[n][3].  Needs no device.                                                              */
+int pt_sh_irradiance_host(const float* sh27, const float* normals3, uint32_t n, float* out_rgb);
+/* Debug: the bake's rays of n (x, y, sample) triples on the device: out6 = n * (o3, d3).  kind PT_BAKE_TEXELS: width x height
+ * texels, data = host float[height][width][6]; PT_BAKE_PROBES: width = rays_per_probe, height = n_probes, data = host
+ * float[n_probes][3], x the direction, y the probe.  Host arrays, blocking; needs no scene.  x >= width or y >= height is
+ * refused.                                                                                                                  */
+int pt_debug_bake_rays(PtContext* ctx, uint32_t kind, uint32_t width, uint32_t height, const float* data, const uint32_t* xys,
+                       uint32_t n, uint32_t exact_math, float* out6);
+/* Host only: the rule on the CPU in the render's exact arithmetic, out6 as pt_debug_bake_rays with exact_math = 1, bit for bit.
+ * Needs no device.                                                                                                           */
+int pt_bake_rays_host(uint32_t kind, uint32_t width, uint32_t height, const float* data, const uint32_t* xys, uint32_t n,
+                      float* out6);
+
 /* Brightness cascade (additive to ABI 6): a firefly-robust film.  The samples of a render are averaged into the film
  * by an estimator that knows which of them are outliers -- the re-weighting of Zirr, Hanika and Dachsbacher (2018): every sample
  * is split between two layers of a per-pixel cascade by its luminance, and a layer keeps its energy in full only where enough

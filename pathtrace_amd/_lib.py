@@ -166,6 +166,7 @@ class PtProjection(C.Structure):
 
 
 PT_PROJ_PERSPECTIVE, PT_PROJ_ORTHOGRAPHIC, PT_PROJ_FISHEYE, PT_PROJ_EQUIRECT = 0, 1, 2, 3
+PT_BAKE_TEXELS, PT_BAKE_PROBES = 0, 1
 
 
 class PtCascade(C.Structure):
@@ -362,6 +363,15 @@ SYMBOLS = {
     "pt_debug_projection_rays": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtProjection), _P(C.c_uint32), C.c_uint32, C.c_uint32, _P(C.c_float)]),
     "pt_projection_setup_host": (C.c_int, [_P(PtCamera), _P(PtProjection), _P(C.c_float)]),
     "pt_projection_rays_host": (C.c_int, [_P(PtCamera), _P(PtProjection), _P(C.c_uint32), C.c_uint32, _P(C.c_float)]),
+    "pt_bake_lightmap_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _P(PtRenderParams), C.c_void_p, C.c_void_p]),
+    "pt_bake_lightmap_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, _P(PtRenderParams), C.c_void_p, C.c_void_p]),
+    "pt_bake_probes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(PtRenderParams), C.c_void_p, C.c_void_p]),
+    "pt_bake_probes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(PtRenderParams), C.c_void_p, C.c_void_p]),
+    "pt_sh_project_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pt_sh_project_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pt_sh_irradiance_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "pt_debug_bake_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p]),
+    "pt_bake_rays_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _P(C.c_uint32), C.c_uint32, C.c_void_p]),
     "pt_default_upsample": (None, [_P(PtUpsample)]),
     "pt_upsample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                      _P(PtUpsample), C.c_void_p, C.c_void_p]),

@@ -208,6 +208,64 @@ def projection_rays_host(cam, proj, xys):
     return out
 
 
+BAKE_KINDS = {"texels": 0, "lightmap": 0, "probes": 1}
+
+
+def _pv(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _bake_film(kind, data):
+    """-> (kind number, the data as a contiguous float32 array, width, height) of a bake's film: texels f32[H, W, 6] = point3,
+    normal3, or (positions f32[P, 3], rays_per_probe)"""
+    kind = BAKE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    if kind == 0:
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        if data.ndim != 3 or data.shape[2] != 6:
+            raise ValueError("texels: float32[H, W, 6] = point3, normal3")
+        return kind, data, data.shape[1], data.shape[0]
+    pos, R = data
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+    return kind, pos, int(R), pos.shape[0]
+
+
+def bake_rays_host(kind, data, xys):
+    """pt_bake_rays_host (host only): the bake's rule on the CPU in exact arithmetic.  kind "texels": data f32[H, W, 6]; "probes":
+    data (positions f32[P, 3], rays_per_probe), x the direction and y the probe.  xys n x (x, y, sample) -> float32[n, 6] =
+    origin3, direction3"""
+    kind, data, W, H = _bake_film(kind, data)
+    xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+    out = np.empty((xys.shape[0], 6), dtype=np.float32)
+    check(lib().pt_bake_rays_host(kind, W, H, _pv(data), _pu(xys), xys.shape[0], _pv(out)))
+    return out
+
+
+def probe_directions(R):
+    """The R directions every probe of a bake looks along (pt_bake_rays_host, exact arithmetic) -> float32[R, 3]"""
+    xys = np.zeros((R, 3), dtype=np.uint32)
+    xys[:, 0] = np.arange(R)
+    return bake_rays_host("probes", (np.zeros((1, 3), dtype=np.float32), R), xys)[:, 3:6].copy()
+
+
+def sh_project_host(radiance):
+    """pt_sh_project_host (host only): radiance f32[P, R, 3] -> the SH coefficients f32[P, 9, 3]"""
+    rad = np.ascontiguousarray(radiance, dtype=np.float32)
+    if rad.ndim != 3 or rad.shape[2] != 3:
+        raise ValueError("radiance: float32[P, R, 3]")
+    out = np.empty((rad.shape[0], 9, 3), dtype=np.float32)
+    check(lib().pt_sh_project_host(rad.shape[0], rad.shape[1], _pv(rad), _pv(out)))
+    return out
+
+
+def sh_irradiance(sh27, normals):
+    """pt_sh_irradiance_host (host only): the irradiance of ONE probe's coefficients f32[9, 3] at normals f32[n, 3] -> f32[n, 3]"""
+    sh = np.ascontiguousarray(sh27, dtype=np.float32).reshape(9, 3)
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    out = np.empty((nrm.shape[0], 3), dtype=np.float32)
+    check(lib().pt_sh_irradiance_host(_pv(sh), _pv(nrm), nrm.shape[0], _pv(out)))
+    return out
+
+
 def upsample_host(lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
     """pt_upsample_host: the upsampling rule on the CPU (no device, no context), on a low film (f32[h,w,3]), its features
     (f32[h,w,8]) and the full-size features (f32[H,W,8]).  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
@@ -736,6 +794,57 @@ class _ContextFunctions:
         rgba = self._empty((rows, W, 4), "uint8") if want_rgba else None
         self._on_stream(lib().pt_render_rays_device, W, H, C.byref(prm), rays, weights, lin, rgba)
         return lin, rgba
+
+    def _device_f32(self, a, shape_tail, name):
+        """a numpy array or a torch tensor -> a contiguous float32 tensor [..., *shape_tail] on this context's device"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        t = t.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(t.shape[-len(shape_tail):]) != tuple(shape_tail):
+            raise ValueError("%s: float32[..., %s]" % (name, ", ".join(str(v) for v in shape_tail)))
+        return t
+
+    def bake_lightmap(self, texels, params, want_rgba=True):
+        """pt_bake_lightmap_device: texels f32[H, W, 6] = point3, normal3 (numpy, or a torch tensor on the device) -> (linear[H,W,3]
+        f32 = the cosine-weighted mean radiance E / pi, rgba[H,W,4] u8 or None), torch device tensors.  A texel with a zero normal
+        or a number that is not finite is empty: +0.0 and the black pixel."""
+        t = self._device_f32(texels, (6,), "texels")
+        if t.dim() != 3:
+            raise ValueError("texels: float32[H, W, 6]")
+        H, W = int(t.shape[0]), int(t.shape[1])
+        lin = self._empty((H, W, 3))
+        rgba = self._empty((H, W, 4), "uint8") if want_rgba else None
+        self._on_stream(lib().pt_bake_lightmap_device, W, H, t, C.byref(params), lin, rgba)
+        return lin, rgba
+
+    def bake_probes(self, positions, rays_per_probe, params, want_sh=True):
+        """pt_bake_probes_device: positions f32[P, 3] -> (radiance[P, R, 3] f32 along probe_directions(R), sh[P, 9, 3] f32 or None),
+        torch device tensors"""
+        t = self._device_f32(positions, (3,), "positions").reshape(-1, 3)
+        P, R = int(t.shape[0]), int(rays_per_probe)
+        rad = self._empty((P, R, 3))
+        sh = self._empty((P, 9, 3)) if want_sh else None
+        self._on_stream(lib().pt_bake_probes_device, t, P, R, C.byref(params), rad, sh)
+        return rad, sh
+
+    def sh_project(self, radiance):
+        """pt_sh_project_device: radiance f32[P, R, 3] (numpy or a device tensor) -> sh f32[P, 9, 3], a torch device tensor.
+        Needs no scene."""
+        t = self._device_f32(radiance, (3,), "radiance")
+        if t.dim() != 3:
+            raise ValueError("radiance: float32[P, R, 3]")
+        sh = self._empty((int(t.shape[0]), 9, 3))
+        self._on_stream(lib().pt_sh_project_device, int(t.shape[0]), int(t.shape[1]), t, sh)
+        return sh
+
+    def bake_rays(self, kind, data, xys, exact_math=0):
+        """pt_debug_bake_rays: the device's rays of a bake; arguments as bake_rays_host -> float32[n, 6] = origin3, direction3"""
+        kind, data, W, H = _bake_film(kind, data)
+        xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+        out = np.empty((xys.shape[0], 6), dtype=np.float32)
+        check(lib().pt_debug_bake_rays(self._h, kind, W, H, _pv(data), _pu(xys), xys.shape[0], exact_math, _pv(out)))
+        return out
 
     def upsample(self, lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
         """pt_upsample_device on a low film (f32[h,w,3]), its features (f32[h,w,8]) and the full-size features (f32[H,W,8]);

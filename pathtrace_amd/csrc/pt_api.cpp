@@ -102,7 +102,7 @@ int check_scene_and_camera(const PtContext* c, const PtCamera* cam) {
 int check_render(const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const ListRender* list, const float* d_linear,
                  const uint8_t* d_rgba) {
     if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "render: null argument");
-    if (int rc = check_scene_and_camera(c, list && list->inject[0] && !list->tile ? nullptr : cam)) return rc;
+    if (int rc = check_scene_and_camera(c, list && list->inject[0] && (!list->tile || list->no_camera) ? nullptr : cam)) return rc;
     if (prm->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
     if (prm->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "unknown integrator %u", prm->integrator);
     if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
@@ -482,18 +482,19 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
 
 // The renders of injected camera paths: the thin lens, the projections and the caller's rays (5q).  The path kernels
 // know none of them: per sample batch `fill` enqueues the launch that writes the batch's rays as path states into the context's
-// inject planes (k_lens_paths, k_projection_paths, k_ray_paths), and render_impl takes them up as given paths of the tile
+// inject planes (k_lens_paths, k_projection_paths, k_ray_paths, k_bake_paths: pt_bake.cpp), and render_impl takes them up as given paths of the tile
 // (ListRender::tile: the launches of pt_ray_color, the film slots, keys and bands of a plain render).  One render_impl per batch
 // of nb <= max_paths_in_flight / np samples; the f64 film sums travel between the batches as they do between the increments of
 // pt_render_progressive, so the film does not depend on the batching.  Everything is checked, and the planes are there, before
 // the first launch; all launches are on the caller's stream, which orders batch k's level-0 launch (the planes' only reader)
 // before batch k + 1's fill.  The caller has checked what is its own (the lens, the projection, the ray planes) before.
 int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const InjectFill& fill, float* d_linear,
-                         uint8_t* d_rgba) {
+                         uint8_t* d_rgba, bool no_camera) {
     if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
     ListRender lr;
     lr.tile = true;
+    lr.no_camera = no_camera;
     lr.inject[0] = reinterpret_cast<const float4*>(1);      // (check_render only asks whether the paths are given)
     if ((rc = check_render(c, cam, prm, &lr, d_linear, d_rgba))) return rc;
     const uint64_t np64 = tile_pixels(cam, prm);

@@ -259,6 +259,9 @@ struct PtContext {
     // k_bloom_tail off (the per-level kernels run every level; same bits)
     DevBuf<float> bloom_pyr, bloom_lin;
     bool bloom_no_tail = false;
+    // pt_bake_*_host: device staging of the texel records or probe positions and of the SH coefficients (the film
+    // goes through host_lin / host_rgba)
+    DevBuf<float> bake_in, bake_sh;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).
@@ -279,6 +282,9 @@ struct ListRender {
     // state s_local * np + tile pixel (0: one sample)
     bool tile = false;
     uint32_t inject_spp = 0;
+    // tile only (the bakes): the film is no camera's image -- no camera ray is ever generated for it, so a width or height of 1
+    // is as good as any
+    bool no_camera = false;
 };
 // A pass of pt_render_adaptive: the film resolve is k_resolve_adaptive into the image-indexed state instead of k_resolve.
 struct AdaptivePass {
@@ -314,7 +320,7 @@ struct InjectBatch {
 };
 using InjectFill = std::function<void(const InjectBatch&)>;
 int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const InjectFill& fill, float* d_linear,
-                         uint8_t* d_rgba);
+                         uint8_t* d_rgba, bool no_camera = false);   // no_camera: ListRender::no_camera (the bakes, pt_bake.cpp)
 // pt_render_projection_device and pt_render_rays_device in the name `who` (pt_api.cpp); pt_projection.cpp: the projection and the
 // camera checked, the device's words; pt_denoise.cpp: the projection forms of the feature pass and the one-call frame
 int render_projection_impl(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,

@@ -621,4 +621,23 @@ void launch_debug_projection_rays_fast(const CameraF& cam, const ProjF& pj, cons
 void launch_ray_paths_exact(const RayPathsArgs& a, hipStream_t st);
 void launch_ray_paths_fast(const RayPathsArgs& a, hipStream_t st);
 
+// Light baking (pt_bake_lightmap_device, pt_bake_probes_device, pt_sh_project_device; rule: pt_bake.h).
+// launch_bake_paths: the bake's rays of one sample batch as path states in the queue form, k_projection_paths's indexing with the
+// film's width x rows = texels (kind 0, data: float[H][W][6], 8-byte aligned) or directions x probes (kind 1, data: float[P][3]).
+// launch_debug_bake_rays: words[4] = x, y, sample, - -> out6 = o3, d3 (x < width and y < the rows: the caller has checked).
+// launch_bake_mask, launch_probe_sh (film unit, one form for both modes): what follows the render.
+struct BakePathsArgs {
+    const float* data;
+    float4* q[4];
+    uint32_t kind, width;
+    uint32_t np, np_magic, w_magic;   // as LensPathsArgs
+    uint32_t s_base, n;
+};
+void launch_bake_paths_exact(const BakePathsArgs& a, hipStream_t st);
+void launch_bake_paths_fast(const BakePathsArgs& a, hipStream_t st);
+void launch_debug_bake_rays_exact(const float* data, uint32_t kind, uint32_t width, const uint32_t* words, uint32_t n, float* out6, hipStream_t st);
+void launch_debug_bake_rays_fast(const float* data, uint32_t kind, uint32_t width, const uint32_t* words, uint32_t n, float* out6, hipStream_t st);
+void launch_bake_mask(const float* texels6, uint32_t n, float* out_linear, uint8_t* out_rgba, hipStream_t st);
+void launch_probe_sh(uint32_t n_probes, uint32_t rays_per_probe, const float* radiance, float* sh27, hipStream_t st);
+
 }  // namespace ptk

@@ -35,6 +35,7 @@
 #include "pt_kernels_vertex.h"
 #include "pt_lens.h"
 #include "pt_projection.h"
+#include "pt_bake.h"
 
 namespace PTK_IMPL {
 
@@ -1250,5 +1251,84 @@ void PT_LAUNCH(launch_debug_projection_rays)(const CameraF& cam, const ProjF& pj
 }
 void PT_LAUNCH(launch_ray_paths)(const RayPathsArgs& a, hipStream_t st) {
     if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_ray_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+}  // namespace ptk
+
+// ------------------------------------------------------------------ light baking (pt_bake_lightmap_device, pt_bake_probes_device;
+// rule: pt_bake.h)
+// bake_ray: the ray of film position (x, y) -- texel (x, y), or direction x of probe y -- and sample `sample` by the rule, in this
+// unit's arithmetic (BakeMath: pt_device.h's own u01, sincos2pi, normalize and cosine_sample).  The kind is a kernel argument, the
+// same for every lane: each kernel branches on it once, around the whole per-lane rule.  A texel lane reads its record's 24 bytes
+// as three 8-byte words (the plane is 8-byte aligned) and draws camera_ray's block for its key.
+//   k_bake_paths        k_projection_paths with the bake's rays: state i = s_local * np + film position, one 16-byte store per
+//                       lane and plane; the throughput of an empty texel's ray is 0
+//   k_debug_bake_rays   words[4] = x, y, sample, - -> out[6] = o3, d3
+namespace PTK_IMPL {
+struct BakeMath {
+    static PT_DEV float u01(uint32_t w) { return PTD_NS::u01(w); }
+    static PT_DEV float sqrt(float x) { return pt_sqrt(x); }
+    static PT_DEV void sincos2pi(float u, float& s, float& c) { PTD_NS::sincos2pi(u, s, c); }
+    static PT_DEV void normalize(float v[3]) {
+        const f3 r = PTD_NS::normalize(mk(v[0], v[1], v[2]));
+        v[0] = r.x; v[1] = r.y; v[2] = r.z;
+    }
+    static PT_DEV void cosine_sample(const float n[3], float r1, float r2, float d[3]) {
+        const f3 r = PTD_NS::cosine_sample(mk(n[0], n[1], n[2]), r1, r2);
+        d[0] = r.x; d[1] = r.y; d[2] = r.z;
+    }
+};
+template <int KIND>
+PT_DEV void bake_ray(const float* __restrict__ data, uint32_t width, uint32_t x, uint32_t y, uint32_t sample, float o[3], float d[3], float& tp) {
+    if (KIND == ptbake::kTexel) {
+        const float2* __restrict__ r = reinterpret_cast<const float2*>(data) + 3 * ((size_t)y * width + x);
+        const float2 r0 = r[0], r1 = r[1], r2 = r[2];
+        const float t[6] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y};
+        uint32_t dc[4];
+        philox4x32_draw(x, y, sample, kDepthCamera, BLK_SURFACE, 0u, dc);
+        ptbake::texel_ray<BakeMath>(t, dc[0], dc[1], o, d, &tp);
+    } else {
+        const float* __restrict__ p = data + 3 * (size_t)y;
+        o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+        ptbake::probe_dir<BakeMath>(x, width, d);
+        tp = 1.0f;
+    }
+}
+template <int KIND>
+PT_DEV void bake_path(const BakePathsArgs& a, uint32_t i) {
+    uint32_t s_local, pix, yl, px;
+    divmod_magic(i, a.np, a.np_magic, s_local, pix);
+    divmod_magic(pix, a.width, a.w_magic, yl, px);
+    float o[3], d[3], tp;
+    bake_ray<KIND>(a.data, a.width, px, yl, a.s_base + s_local, o, d, tp);      // the whole image: tile row = image row
+    a.q[0][i] = make_float4(o[0], o[1], o[2], d[0]);
+    a.q[1][i] = make_float4(d[1], d[2], __uint_as_float((yl << 16) | px), __uint_as_float(s_local << 16));
+    a.q[2][i] = make_float4(tp, tp, tp, 0.0f);
+    a.q[3][i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+}
+__global__ void __launch_bounds__(kBlock) k_bake_paths(BakePathsArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    if (a.kind == (uint32_t)ptbake::kTexel) bake_path<ptbake::kTexel>(a, i);
+    else bake_path<ptbake::kProbe>(a, i);
+}
+__global__ void __launch_bounds__(kBlock) k_debug_bake_rays(const float* __restrict__ data, uint32_t kind, uint32_t width,
+                                                            const uint32_t* __restrict__ words, uint32_t n, float* __restrict__ out6) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* w = words + 4 * (size_t)i;
+    float o[3], d[3], tp;
+    if (kind == (uint32_t)ptbake::kTexel) bake_ray<ptbake::kTexel>(data, width, w[0], w[1], w[2], o, d, tp);
+    else bake_ray<ptbake::kProbe>(data, width, w[0], w[1], w[2], o, d, tp);
+    float* out = out6 + 6 * (size_t)i;
+    out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = d[0]; out[4] = d[1]; out[5] = d[2];
+}
+}  // namespace PTK_IMPL
+namespace ptk {
+void PT_LAUNCH(launch_bake_paths)(const BakePathsArgs& a, hipStream_t st) {
+    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_bake_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+}
+void PT_LAUNCH(launch_debug_bake_rays)(const float* data, uint32_t kind, uint32_t width, const uint32_t* words, uint32_t n, float* out6,
+                                       hipStream_t st) {
+    if (n) hipLaunchKernelGGL(PTK_IMPL::k_debug_bake_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, data, kind, width, words, n, out6);
 }
 }  // namespace ptk

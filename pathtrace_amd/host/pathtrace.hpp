@@ -510,6 +510,45 @@ public:
         p.band_rows = 0; p.band_index = 0; p.band_count = 1;
         check(pt_render_rays_device(ctx_, camera_.width(), camera_.height(), &p, d_rays6, d_weights3, d_linear_rgb, d_rgba8));
     }
+    // Light baking.  bake_lightmap (pt_bake_lightmap_host): texels6 = width x height records of point3, normal3;
+    // -> width x height values of the cosine-weighted mean radiance E / pi at those points (times a Lambert albedo: the outgoing
+    // radiance).  A record with a zero normal or a number that is not finite is an empty texel: black.  rgba8 (may be null)
+    // receives the display bytes.  Uses params()'s spp, integrator and depths; luminance_data is not touched.
+    std::vector<Vector3> bake_lightmap(uint32_t width, uint32_t height, const std::vector<float>& texels6, std::vector<uint8_t>* rgba8 = nullptr,
+                                       int device = 0) {
+        if (texels6.size() != (size_t)width * height * 6) throw std::runtime_error("bake_lightmap: texels6 must hold width x height x 6 floats");
+        scene(device);
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        const size_t n = (size_t)width * height;
+        std::vector<float> lin(n * 3);
+        if (rgba8) rgba8->resize(n * 4);
+        check(pt_bake_lightmap_host(ctx_, width, height, texels6.data(), &p, lin.data(), rgba8 ? rgba8->data() : nullptr));
+        std::vector<Vector3> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = Vector3(lin[3 * i], lin[3 * i + 1], lin[3 * i + 2]);
+        return out;
+    }
+    // bake_probes (pt_bake_probes_host): positions3 = n x 3 floats -> sh27 = n x 9 x 3 coefficients of the radiance around every
+    // probe (real spherical harmonics through l = 2, coefficient l (l + 1) + m, RGB innermost); radiance (may be null) receives the
+    // n x rays_per_probe x 3 values the coefficients were projected from.  irradiance(): pt_sh_irradiance_host of one probe.
+    std::vector<float> bake_probes(const std::vector<float>& positions3, uint32_t rays_per_probe, std::vector<float>* radiance = nullptr,
+                                   int device = 0) {
+        if (positions3.empty() || positions3.size() % 3) throw std::runtime_error("bake_probes: positions3 must hold n x 3 floats, n > 0");
+        scene(device);
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        const uint32_t n = (uint32_t)(positions3.size() / 3);
+        std::vector<float> rad((size_t)n * rays_per_probe * 3), sh((size_t)n * 27);
+        check(pt_bake_probes_host(ctx_, positions3.data(), n, rays_per_probe, &p, rad.data(), sh.data()));
+        if (radiance) *radiance = std::move(rad);
+        return sh;
+    }
+    static Vector3 irradiance(const float* sh27, const Vector3& normal) {
+        const float n3[3] = {(float)normal.x, (float)normal.y, (float)normal.z};
+        float e[3];
+        check(pt_sh_irradiance_host(sh27, n3, 1, e));
+        return Vector3(e[0], e[1], e[2]);
+    }
     // render_denoised() through the lens (pt_render_lens_denoised): the features are those of the lens rays.
     void render_lens_denoised(const PtLens& lens, uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, std::vector<Vector3>* noisy = nullptr,
                               int device = 0) {

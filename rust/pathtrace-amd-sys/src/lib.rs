@@ -151,6 +151,9 @@ pub const PT_PROJ_PERSPECTIVE: u32 = 0;
 pub const PT_PROJ_ORTHOGRAPHIC: u32 = 1;
 pub const PT_PROJ_FISHEYE: u32 = 2;
 pub const PT_PROJ_EQUIRECT: u32 = 3;
+/// pt_debug_bake_rays / pt_bake_rays_host: what the film of a bake holds
+pub const PT_BAKE_TEXELS: u32 = 0;
+pub const PT_BAKE_PROBES: u32 = 1;
 
 /// pt_render_lens_device: the thin lens beside the camera (include/pathtrace_amd.h); aperture 0 = pinhole.
 #[repr(C)]
@@ -480,6 +483,15 @@ extern "C" {
     pub fn pt_debug_projection_rays(ctx: *mut PtContext, cam: *const PtCamera, proj: *const PtProjection, xys: *const u32, n: u32, exact_math: u32, out8: *mut f32) -> c_int;
     pub fn pt_projection_setup_host(cam: *const PtCamera, proj: *const PtProjection, out11: *mut f32) -> c_int;
     pub fn pt_projection_rays_host(cam: *const PtCamera, proj: *const PtProjection, xys: *const u32, n: u32, out8: *mut f32) -> c_int;
+    pub fn pt_bake_lightmap_device(ctx: *mut PtContext, width: u32, height: u32, d_texels6: *const f32, params: *const PtRenderParams, d_linear_rgb: *mut f32, d_rgba8: *mut u8) -> c_int;
+    pub fn pt_bake_lightmap_host(ctx: *mut PtContext, width: u32, height: u32, texels6: *const f32, params: *const PtRenderParams, out_linear_rgb: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_bake_probes_device(ctx: *mut PtContext, d_positions3: *const f32, n_probes: u32, rays_per_probe: u32, params: *const PtRenderParams, d_radiance: *mut f32, d_sh27: *mut f32) -> c_int;
+    pub fn pt_bake_probes_host(ctx: *mut PtContext, positions3: *const f32, n_probes: u32, rays_per_probe: u32, params: *const PtRenderParams, out_radiance: *mut f32, out_sh27: *mut f32) -> c_int;
+    pub fn pt_sh_project_device(ctx: *mut PtContext, n_probes: u32, rays_per_probe: u32, d_radiance: *const f32, d_sh27: *mut f32) -> c_int;
+    pub fn pt_sh_project_host(n_probes: u32, rays_per_probe: u32, radiance: *const f32, sh27: *mut f32) -> c_int;
+    pub fn pt_sh_irradiance_host(sh27: *const f32, normals3: *const f32, n: u32, out_rgb: *mut f32) -> c_int;
+    pub fn pt_debug_bake_rays(ctx: *mut PtContext, kind: u32, width: u32, height: u32, data: *const f32, xys: *const u32, n: u32, exact_math: u32, out6: *mut f32) -> c_int;
+    pub fn pt_bake_rays_host(kind: u32, width: u32, height: u32, data: *const f32, xys: *const u32, n: u32, out6: *mut f32) -> c_int;
     pub fn pt_default_cascade(out: *mut PtCascade);
     pub fn pt_render_cascade_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
     pub fn pt_render_cascade_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_plain_linear: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;
