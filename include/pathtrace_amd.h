@@ -1096,6 +1096,75 @@ int pt_debug_bake_rays(PtContext* ctx, uint32_t kind, uint32_t width, uint32_t h
 int pt_bake_rays_host(uint32_t kind, uint32_t width, uint32_t height, const float* data, const uint32_t* xys, uint32_t n,
                       float* out6);
 
+/* Irradiance volume (additive to ABI 6): a regular grid of baked SH probes, sampled at every visible point -- diffuse
+ * global illumination for the price of a first-hit pass.  pt_probe_grid_bake_device bakes the grid, pt_probe_shade_device turns
+ * first-hit features (pt_render_features_device) and the baked coefficients into a film, pt_render_probe_lit_device does the
+ * feature pass and the shading in one call.  No path kernel knows.  The rule (pathtrace_amd/csrc/pt_probe_grid.h), f64 with
+ * + - * /, square root, comparisons and selects in a fixed order, so that the host and the device agree bit for bit:
+ *   grid        probe (ix, iy, iz) has index (iz ny + iy) nx + ix and the position origin_a + i_a spacing_a, formed in f64 and
+ *               rounded to f32 once.  Valid: no count 0, origin and spacing finite, spacing > 0 on every axis with more than one
+ *               probe, at most 65535 probes.
+ *   unlit       a pixel whose depth is not > 0 (a miss, NaN), whose emitter flag is > 0, whose normal, depth or albedo is not
+ *               finite, whose normal has the f64 length 0, or whose point is not finite (every pixel when width or height is 1):
+ *               it takes the fallback pixel bit for bit, +0.0 without a fallback plane, and reads no probe.
+ *   point       s = (x + 0.5) / (W - 1), t = (H - 1 - y + 0.5) / (H - 1), D = lower_left + s horizontal + t vertical - origin,
+ *               P = origin + depth (D (1 / |D|)): the temporal denoiser's reconstruction.  nn = n / |n|; Q = P + normal_bias nn.
+ *   cell        per axis with more than one probe g = (Q_a - origin_a) / spacing_a, clamped to [0, count - 1] (NaN: unlit),
+ *               i = min(floor(g), count - 2), f = g - i; an axis with one probe has i = 0, f = 0 and one corner for both.
+ *   weights     corner j = 0..7 (bit 0 x, bit 1 y, bit 2 z): (wx wy) wz, each f or 1 - f.  PT_PROBE_WEIGHT_FACING multiplies by
+ *               ((c + 1) / 2)^2 + 0.2 with c = (v . nn) / |v|, v = the corner's f32 position - P, c = 1 when |v| = 0: the backface
+ *               weight of Majercik et al. 2019.  Its visibility term is not there: light leaks through thin walls.
+ *   blend       every coefficient C = C_0 + (sum_{j=1..7} w_j (C_j - C_0)) / (sum_j w_j), j ascending from 0.0: a constant field
+ *               comes out exactly
+ *   shade       E_c = sum_k A_l C[k][c] Y_k(nn) in pt_sh_irradiance_host's order; a negative E_c becomes 0, NaN stays;
+ *               out_c = (float)((max(albedo_c, 0) E_c) / pi); the RGBA8 word through the sqrt, clamp and `as u8` of every render.
+ * A Mirror surface is shaded as a diffuse one of its colour.  Every entry checks everything before its first launch.
+ * PT_ERR_INVALID_ARG, with a message and the context untouched, for: a null or misaligned plane (features 16 bytes, the others
+ * 4), an invalid grid, weight > 1, a normal_bias that is not finite, a zero size, band_count > 1, and everything the feature and
+ * probe-bake entries refuse.                                                                                                   */
+enum { PT_PROBE_WEIGHT_TRILINEAR = 0, PT_PROBE_WEIGHT_FACING = 1 };
+typedef struct {
+    double origin[3];        /* the position of probe (0, 0, 0); finite                         */
+    double spacing[3];       /* between neighbours; finite, > 0 on an axis with more than one probe */
+    uint32_t counts[3];      /* nx, ny, nz >= 1; nx ny nz <= 65535                              */
+    uint32_t reserved;
+} PtProbeGrid;
+typedef struct {
+    float normal_bias;       /* the lookup point is moved this far along the normal; finite    */
+    uint32_t weight;         /* PT_PROBE_WEIGHT_*                                              */
+} PtProbeShade;
+/* normal_bias 0, PT_PROBE_WEIGHT_TRILINEAR */
+void pt_default_probe_shade(PtProbeShade* out);
+/* Host only: nx ny nz, or 0 for an invalid (or null) grid. */
+uint32_t pt_probe_grid_count(const PtProbeGrid* grid);
+/* Host only: the positions, float[count][3], as pt_bake_probes_* takes them.  Needs no device. */
+int pt_probe_grid_positions_host(const PtProbeGrid* grid, float* out_positions3);
+/* Bakes the grid (asynchronous on the context's stream): the positions are written on the device into a context-owned plane, then
+ * pt_bake_probes_device runs with a context-owned radiance plane.  d_sh27: device float[count][9][3].  Bit-identical to
+ * pt_bake_probes_device on the positions of pt_probe_grid_positions_host.                                                    */
+int pt_probe_grid_bake_device(PtContext* ctx, const PtProbeGrid* grid, uint32_t rays_per_probe, const PtRenderParams* params,
+                              float* d_sh27);
+/* The shading pass (asynchronous on the context's stream; needs no scene).  cam: the camera the features were rendered with.
+ * d_features: device float[height][width][8], 16-byte aligned.  d_fallback_linear: device float[height][width][3] or NULL; it may be
+ * d_out_linear itself (in place).  d_out_rgba8: device uint8[height][width][4], 4-byte aligned, or NULL.                        */
+int pt_probe_shade_device(PtContext* ctx, const PtCamera* cam, const PtProbeGrid* grid, const float* d_sh27, const float* d_features,
+                          const float* d_fallback_linear, const PtProbeShade* shade, float* d_out_linear, uint8_t* d_out_rgba8);
+/* Host only: the same rule on the CPU, host buffers (features 4-byte aligned), bit for bit.  Needs no device. */
+int pt_probe_shade_host(const PtCamera* cam, const PtProbeGrid* grid, const float* sh27, const float* features,
+                        const float* fallback_linear, const PtProbeShade* shade, float* out_linear, uint8_t* out_rgba8);
+/* pt_render_features_device of feature_samples samples into a context-owned plane, then pt_probe_shade_device: bit-identical to
+ * the two calls.  Asynchronous on the context's stream.                                                                     */
+int pt_render_probe_lit_device(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
+                               const PtProbeGrid* grid, const float* d_sh27, const float* d_fallback_linear, const PtProbeShade* shade,
+                               float* d_out_linear, uint8_t* d_out_rgba8);
+/* The same from and into host buffers (blocking); fallback_linear and out_rgba8 may be NULL. */
+int pt_render_probe_lit_host(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
+                             const PtProbeGrid* grid, const float* sh27, const float* fallback_linear, const PtProbeShade* shade,
+                             float* out_linear, uint8_t* out_rgba8);
+/* Debug: the grid's positions as the device writes them for pt_probe_grid_bake_device, copied to out_positions3 = host
+ * float[count][3] (blocking; needs no scene).  The same bits as pt_probe_grid_positions_host.                               */
+int pt_debug_probe_positions(PtContext* ctx, const PtProbeGrid* grid, float* out_positions3);
+
 /* Brightness cascade (additive to ABI 6): a firefly-robust film.  The samples of a render are averaged into the film
  * by an estimator that knows which of them are outliers -- the re-weighting of Zirr, Hanika and Dachsbacher (2018): every sample
  * is split between two layers of a per-pixel cascade by its luminance, and a layer keeps its energy in full only where enough

@@ -169,6 +169,25 @@ PT_PROJ_PERSPECTIVE, PT_PROJ_ORTHOGRAPHIC, PT_PROJ_FISHEYE, PT_PROJ_EQUIRECT = 0
 PT_BAKE_TEXELS, PT_BAKE_PROBES = 0, 1
 
 
+class PtProbeGrid(C.Structure):
+    _fields_ = [
+        ("origin", C.c_double * 3),
+        ("spacing", C.c_double * 3),
+        ("counts", C.c_uint32 * 3),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class PtProbeShade(C.Structure):
+    _fields_ = [
+        ("normal_bias", C.c_float),
+        ("weight", C.c_uint32),
+    ]
+
+
+PT_PROBE_WEIGHT_TRILINEAR, PT_PROBE_WEIGHT_FACING = 0, 1
+
+
 class PtCascade(C.Structure):
     _fields_ = [
         ("layers", C.c_uint32),
@@ -372,6 +391,18 @@ SYMBOLS = {
     "pt_sh_irradiance_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "pt_debug_bake_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p]),
     "pt_bake_rays_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _P(C.c_uint32), C.c_uint32, C.c_void_p]),
+    "pt_default_probe_shade": (None, [_P(PtProbeShade)]),
+    "pt_probe_grid_count": (C.c_uint32, [_P(PtProbeGrid)]),
+    "pt_probe_grid_positions_host": (C.c_int, [_P(PtProbeGrid), C.c_void_p]),
+    "pt_probe_grid_bake_device": (C.c_int, [C.c_void_p, _P(PtProbeGrid), C.c_uint32, _P(PtRenderParams), C.c_void_p]),
+    "pt_probe_shade_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, _P(PtProbeShade), C.c_void_p,
+                                        C.c_void_p]),
+    "pt_probe_shade_host": (C.c_int, [_P(PtCamera), _P(PtProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, _P(PtProbeShade), C.c_void_p, C.c_void_p]),
+    "pt_render_probe_lit_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtProbeGrid), C.c_void_p, C.c_void_p,
+                                             _P(PtProbeShade), C.c_void_p, C.c_void_p]),
+    "pt_render_probe_lit_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtProbeGrid), C.c_void_p, C.c_void_p,
+                                           _P(PtProbeShade), C.c_void_p, C.c_void_p]),
+    "pt_debug_probe_positions": (C.c_int, [C.c_void_p, _P(PtProbeGrid), C.c_void_p]),
     "pt_default_upsample": (None, [_P(PtUpsample)]),
     "pt_upsample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                      _P(PtUpsample), C.c_void_p, C.c_void_p]),

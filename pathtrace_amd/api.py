@@ -266,6 +266,55 @@ def sh_irradiance(sh27, normals):
     return out
 
 
+PROBE_WEIGHTS = {"trilinear": _lib.PT_PROBE_WEIGHT_TRILINEAR, "facing": _lib.PT_PROBE_WEIGHT_FACING}
+
+
+def probe_grid(origin, spacing, counts):
+    """A PtProbeGrid: probe (ix, iy, iz) sits at origin + (ix, iy, iz) * spacing and has index (iz ny + iy) nx + ix"""
+    g = _lib.PtProbeGrid()
+    for k in range(3):
+        g.origin[k], g.spacing[k], g.counts[k] = float(origin[k]), float(spacing[k]), int(counts[k])
+    return g
+
+
+def probe_grid_count(grid):
+    """pt_probe_grid_count: the number of probes, 0 for an invalid grid"""
+    return int(lib().pt_probe_grid_count(C.byref(grid)))
+
+
+def default_probe_shade(**over):
+    """pt_default_probe_shade with keyword overrides (None keeps the default); weight may be "trilinear" or "facing\""""
+    s = _lib.PtProbeShade()
+    lib().pt_default_probe_shade(C.byref(s))
+    for k, v in over.items():
+        if v is not None:
+            setattr(s, k, PROBE_WEIGHTS[v] if k == "weight" and isinstance(v, str) else v)
+    return s
+
+
+def probe_grid_positions(grid):
+    """pt_probe_grid_positions_host (host only): the positions of the grid's probes -> float32[P, 3], as bake_probes takes them"""
+    out = np.empty((probe_grid_count(grid), 3), dtype=np.float32)
+    check(lib().pt_probe_grid_positions_host(C.byref(grid), _pv(out)))
+    return out
+
+
+def probe_shade_host(cam, grid, sh27, features, fallback=None, shade=None):
+    """pt_probe_shade_host (host only): first-hit features f32[H, W, 8] shaded from the grid's coefficients sh27 f32[P, 9, 3]; an
+    unlit pixel takes fallback f32[H, W, 3] (None: +0.0).  -> (linear f32[H, W, 3], rgba u8[H, W, 4])"""
+    shade = shade if shade is not None else default_probe_shade()
+    H, W = cam.height, cam.width
+    sh = np.ascontiguousarray(sh27, dtype=np.float32)
+    feat = np.ascontiguousarray(features, dtype=np.float32)
+    fb = None if fallback is None else np.ascontiguousarray(fallback, dtype=np.float32)
+    if sh.size != 27 * probe_grid_count(grid) or feat.shape != (H, W, 8) or (fb is not None and fb.shape != (H, W, 3)):
+        raise ValueError("probe_shade_host: sh27 f32[P, 9, 3], features f32[H, W, 8], fallback f32[H, W, 3]")
+    out, rgba = np.empty((H, W, 3), dtype=np.float32), np.empty((H, W, 4), dtype=np.uint8)
+    check(lib().pt_probe_shade_host(C.byref(cam), C.byref(grid), _pv(sh), _pv(feat), None if fb is None else _pv(fb), C.byref(shade), _pv(out),
+                                    _pv(rgba)))
+    return out, rgba
+
+
 def upsample_host(lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
     """pt_upsample_host: the upsampling rule on the CPU (no device, no context), on a low film (f32[h,w,3]), its features
     (f32[h,w,8]) and the full-size features (f32[H,W,8]).  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
@@ -844,6 +893,51 @@ class _ContextFunctions:
         xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
         out = np.empty((xys.shape[0], 6), dtype=np.float32)
         check(lib().pt_debug_bake_rays(self._h, kind, W, H, _pv(data), _pu(xys), xys.shape[0], exact_math, _pv(out)))
+        return out
+
+    def probe_grid_bake(self, grid, rays_per_probe, params):
+        """pt_probe_grid_bake_device: the grid's probes baked in one call -> sh[P, 9, 3] f32, a torch device tensor"""
+        sh = self._empty((probe_grid_count(grid), 9, 3))
+        self._on_stream(lib().pt_probe_grid_bake_device, C.byref(grid), int(rays_per_probe), C.byref(params), sh)
+        return sh
+
+    def probe_shade(self, cam, grid, sh27, features, fallback=None, shade=None, in_place=False, want_rgba=True):
+        """pt_probe_shade_device: features f32[H, W, 8] (numpy or device tensor) shaded from sh27 f32[P, 9, 3]; an unlit pixel takes
+        fallback f32[H, W, 3] (None: +0.0); in_place: the fallback tensor is the output.  Needs no scene.  -> (linear[H,W,3] f32,
+        rgba[H,W,4] u8 or None), torch device tensors"""
+        shade = shade if shade is not None else default_probe_shade()
+        H, W = cam.height, cam.width
+        sh = self._device_f32(sh27, (9, 3), "sh27")
+        feat = self._device_f32(features, (8,), "features")
+        fb = None if fallback is None else self._device_f32(fallback, (3,), "fallback")
+        if sh.numel() != 27 * probe_grid_count(grid) or tuple(feat.shape) != (H, W, 8) or (fb is not None and tuple(fb.shape) != (H, W, 3)):
+            raise ValueError("probe_shade: sh27 f32[P, 9, 3], features f32[H, W, 8], fallback f32[H, W, 3]")
+        if in_place and fb is None:
+            raise ValueError("probe_shade: in_place needs a fallback plane")
+        out = fb if in_place else self._empty((H, W, 3))
+        rgba = self._empty((H, W, 4), "uint8") if want_rgba else None
+        self._on_stream(lib().pt_probe_shade_device, C.byref(cam), C.byref(grid), sh, feat, fb, C.byref(shade), out, rgba)
+        return out, rgba
+
+    def render_probe_lit(self, cam, params, grid, sh27, feature_samples=1, fallback=None, shade=None, want_rgba=True):
+        """pt_render_probe_lit_device: the first-hit pass and the shading in one call -> (linear[H,W,3] f32, rgba[H,W,4] u8 or None),
+        torch device tensors"""
+        shade = shade if shade is not None else default_probe_shade()
+        H, W = cam.height, cam.width
+        sh = self._device_f32(sh27, (9, 3), "sh27")
+        fb = None if fallback is None else self._device_f32(fallback, (3,), "fallback")
+        if sh.numel() != 27 * probe_grid_count(grid) or (fb is not None and tuple(fb.shape) != (H, W, 3)):
+            raise ValueError("render_probe_lit: sh27 f32[P, 9, 3], fallback f32[H, W, 3]")
+        out = self._empty((H, W, 3))
+        rgba = self._empty((H, W, 4), "uint8") if want_rgba else None
+        self._on_stream(lib().pt_render_probe_lit_device, C.byref(cam), C.byref(params), int(feature_samples), C.byref(grid), sh, fb, C.byref(shade),
+                        out, rgba)
+        return out, rgba
+
+    def probe_positions(self, grid):
+        """pt_debug_probe_positions: the grid's positions as the device writes them -> float32[P, 3]"""
+        out = np.empty((probe_grid_count(grid), 3), dtype=np.float32)
+        check(lib().pt_debug_probe_positions(self._h, C.byref(grid), _pv(out)))
         return out
 
     def upsample(self, lo_linear, lo_features, features, sigma_n=None, sigma_d=None):

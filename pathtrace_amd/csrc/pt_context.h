@@ -262,6 +262,10 @@ struct PtContext {
     // pt_bake_*_host: device staging of the texel records or probe positions and of the SH coefficients (the film
     // goes through host_lin / host_rgba)
     DevBuf<float> bake_in, bake_sh;
+    // pt_probe_grid_bake_device: the grid's positions and the radiance plane of its bake; pt_render_probe_lit_device:
+    // the feature plane (pt_render_probe_lit_host stages the coefficients in bake_sh and the film in host_lin / host_rgba)
+    DevBuf<float> pg_pos, pg_rad;
+    DevBuf<float4> pg_feat;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).

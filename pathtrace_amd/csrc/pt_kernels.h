@@ -640,4 +640,25 @@ void launch_debug_bake_rays_fast(const float* data, uint32_t kind, uint32_t widt
 void launch_bake_mask(const float* texels6, uint32_t n, float* out_linear, uint8_t* out_rgba, hipStream_t st);
 void launch_probe_sh(uint32_t n_probes, uint32_t rays_per_probe, const float* radiance, float* sh27, hipStream_t st);
 
+// Irradiance volume (pt_probe_grid_bake_device, pt_probe_shade_device; rule: pt_probe_grid.h; film unit, one form
+// for both modes).  launch_probe_positions: the n = nx ny nz positions of a valid grid, 3 floats each.  launch_probe_shade: one
+// thread per pixel of the width x height image; fallback may be null, or out_linear itself; out_rgba may be null.
+struct ProbeGridArgs {
+    double origin[3], spacing[3];
+    uint32_t counts[3];
+};
+struct ProbeShadeArgs {
+    const float4* feat;
+    const float* sh27;
+    const float* fallback;
+    float* out_linear;
+    uint8_t* out_rgba;
+    double cam[12];               // origin, lower_left, horizontal, vertical
+    ProbeGridArgs grid;
+    uint32_t width, height, weight;
+    float normal_bias;
+};
+void launch_probe_positions(const ProbeGridArgs& g, uint32_t n, float* out, hipStream_t st);
+void launch_probe_shade(const ProbeShadeArgs& a, hipStream_t st);
+
 }  // namespace ptk

@@ -8,7 +8,8 @@
 //   pt_kernels_bvh.hip    the BVH form (k_paths_bvh, k_debug_hit_bvh)                     with the SLP vectoriser (its 4-wide box tests pack well: +2 % without)
 //   pt_kernels_film.hip   the kernels on the film and the device-side BVH refit / builds  the main unit's options
 //                         (fast mode only), one header per concern: pt_film_exchange.h, _adaptive.h, _denoise.h, _temporal.h
-//                         (accumulation and gradients), _bvh.h, _tonemap.h
+//                         (accumulation and gradients), _bvh.h, _tonemap.h, _upsample.h, _cascade.h, _filter.h, _bloom.h,
+//                         _bake.h, _probe.h (k_probe_positions, k_probe_shade)
 // Shared device code: pt_kernels_scan.h (primitive tests, scene staging, scans), pt_kernels_vertex.h (one path vertex).
 // Kernel templates are instantiated where their launcher is; the launchers that cross units are declared in pt_kernels.h.
 #pragma once

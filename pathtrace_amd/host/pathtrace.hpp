@@ -549,6 +549,37 @@ public:
         check(pt_sh_irradiance_host(sh27, n3, 1, e));
         return Vector3(e[0], e[1], e[2]);
     }
+    // Irradiance volume.  bake_probe_grid: the probes of a regular grid (pt_probe_grid_positions_host) through
+    // bake_probes -> sh27 = count x 9 x 3 coefficients, probe (ix, iy, iz) at index (iz ny + iy) nx + ix; the same bits as
+    // pt_probe_grid_bake_device.
+    std::vector<float> bake_probe_grid(const PtProbeGrid& grid, uint32_t rays_per_probe, int device = 0) {
+        const uint32_t n = pt_probe_grid_count(&grid);
+        if (n == 0) throw std::runtime_error("bake_probe_grid: invalid probe grid");
+        std::vector<float> pos((size_t)n * 3);
+        check(pt_probe_grid_positions_host(&grid, pos.data()));
+        return bake_probes(pos, rays_per_probe, nullptr, device);
+    }
+    // render_probe_lit (pt_render_probe_lit_host): every first-hit pixel shaded from the baked grid -- diffuse global illumination
+    // for the price of a first-hit pass, biased (light leaks through thin walls, mirrors are shaded as diffuse).  Emitter and miss
+    // pixels take `fallback` (y*width+x; empty: black).  data / luminance_data hold the frame.
+    void render_probe_lit(const PtProbeGrid& grid, const std::vector<float>& sh27, const PtProbeShade* shade = nullptr, uint32_t feature_samples = 1,
+                          const std::vector<Vector3>* fallback = nullptr, int device = 0) {
+        if (sh27.size() != (size_t)pt_probe_grid_count(&grid) * 27 || sh27.empty()) throw std::runtime_error("render_probe_lit: sh27 must hold count x 27 floats");
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtProbeShade s{};
+        if (shade) s = *shade; else pt_default_probe_shade(&s);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        if (fallback && fallback->size() != n) throw std::runtime_error("render_probe_lit: fallback must hold width x height values");
+        std::vector<float> lin(n * 3), fb(fallback ? n * 3 : 0);
+        for (size_t i = 0; i < fb.size() / 3; ++i) { fb[3 * i] = (float)(*fallback)[i].x; fb[3 * i + 1] = (float)(*fallback)[i].y; fb[3 * i + 2] = (float)(*fallback)[i].z; }
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_probe_lit_host(ctx_, &camera_.pod(), &p, feature_samples, &grid, sh27.data(), fallback ? fb.data() : nullptr, &s, lin.data(),
+                                       rgba.data()));
+        unpack(lin, rgba);
+    }
     // render_denoised() through the lens (pt_render_lens_denoised): the features are those of the lens rays.
     void render_lens_denoised(const PtLens& lens, uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, std::vector<Vector3>* noisy = nullptr,
                               int device = 0) {

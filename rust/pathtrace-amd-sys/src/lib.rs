@@ -155,6 +155,24 @@ pub const PT_PROJ_EQUIRECT: u32 = 3;
 pub const PT_BAKE_TEXELS: u32 = 0;
 pub const PT_BAKE_PROBES: u32 = 1;
 
+/// A regular grid of SH probes (the irradiance volume): probe (ix, iy, iz) has index (iz ny + iy) nx + ix
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtProbeGrid {
+    pub origin: [f64; 3],
+    pub spacing: [f64; 3],
+    pub counts: [u32; 3],
+    pub reserved: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtProbeShade {
+    pub normal_bias: f32,
+    pub weight: u32,
+}
+pub const PT_PROBE_WEIGHT_TRILINEAR: u32 = 0;
+pub const PT_PROBE_WEIGHT_FACING: u32 = 1;
+
 /// pt_render_lens_device: the thin lens beside the camera (include/pathtrace_amd.h); aperture 0 = pinhole.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -492,6 +510,15 @@ extern "C" {
     pub fn pt_sh_irradiance_host(sh27: *const f32, normals3: *const f32, n: u32, out_rgb: *mut f32) -> c_int;
     pub fn pt_debug_bake_rays(ctx: *mut PtContext, kind: u32, width: u32, height: u32, data: *const f32, xys: *const u32, n: u32, exact_math: u32, out6: *mut f32) -> c_int;
     pub fn pt_bake_rays_host(kind: u32, width: u32, height: u32, data: *const f32, xys: *const u32, n: u32, out6: *mut f32) -> c_int;
+    pub fn pt_default_probe_shade(out: *mut PtProbeShade);
+    pub fn pt_probe_grid_count(grid: *const PtProbeGrid) -> u32;
+    pub fn pt_probe_grid_positions_host(grid: *const PtProbeGrid, out_positions3: *mut f32) -> c_int;
+    pub fn pt_probe_grid_bake_device(ctx: *mut PtContext, grid: *const PtProbeGrid, rays_per_probe: u32, params: *const PtRenderParams, d_sh27: *mut f32) -> c_int;
+    pub fn pt_probe_shade_device(ctx: *mut PtContext, cam: *const PtCamera, grid: *const PtProbeGrid, d_sh27: *const f32, d_features: *const f32, d_fallback_linear: *const f32, shade: *const PtProbeShade, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_probe_shade_host(cam: *const PtCamera, grid: *const PtProbeGrid, sh27: *const f32, features: *const f32, fallback_linear: *const f32, shade: *const PtProbeShade, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_probe_lit_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, grid: *const PtProbeGrid, d_sh27: *const f32, d_fallback_linear: *const f32, shade: *const PtProbeShade, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_probe_lit_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, grid: *const PtProbeGrid, sh27: *const f32, fallback_linear: *const f32, shade: *const PtProbeShade, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_debug_probe_positions(ctx: *mut PtContext, grid: *const PtProbeGrid, out_positions3: *mut f32) -> c_int;
     pub fn pt_default_cascade(out: *mut PtCascade);
     pub fn pt_render_cascade_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
     pub fn pt_render_cascade_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_plain_linear: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;
