@@ -11,8 +11,37 @@
 #include <algorithm>
 #include <cstring>
 
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_shape.h"
+
+// ---- the render's preconditions (pt_entry.h): each message stands here and nowhere else.  who: "<who>: " in front, null: nothing
+#define PT_WHO(who) (who) ? (who) : "", (who) ? ": " : ""
+int check_scene(const PtContext* c, const char* who) {
+    if (!c || !c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s%sno scene uploaded", PT_WHO(who));
+    return PT_OK;
+}
+int check_camera_size(const PtCamera* cam, const char* who) {   // get_ray_with_offset divides by width-1 / height-1 (camera.rs:140-141)
+    if (cam->width < 2 || cam->height < 2)
+        return fail(PT_ERR_INVALID_ARG, "%s%scamera %ux%u: width and height must be >= 2", PT_WHO(who), cam->width, cam->height);
+    return PT_OK;
+}
+int check_spp(uint32_t spp, const char* who) {
+    if (spp == 0) return fail(PT_ERR_INVALID_ARG, "%s%sspp must be > 0", PT_WHO(who));
+    return PT_OK;
+}
+int check_integrator(uint32_t integrator, const char* who) {
+    if (integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "%s%sunknown integrator %u", PT_WHO(who), integrator);
+    return PT_OK;
+}
+int check_accel(uint32_t accel, const char* who) {
+    if (accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "%s%sunknown accel %u", PT_WHO(who), accel);
+    return PT_OK;
+}
+int check_band_index(uint32_t band_index, uint32_t band_count) {
+    if (band_index >= band_count) return fail(PT_ERR_INVALID_ARG, "band_index %u >= band_count %u", band_index, band_count);
+    return PT_OK;
+}
+#undef PT_WHO
 
 namespace {
 
@@ -63,19 +92,15 @@ void sched_recover(PtContext* c, hipStream_t st, const ptsched::State& planned) 
 }
 
 // render_impl into the context's device staging, then over PCIe into the caller's host buffers (blocking)
+int film_back(const PtContext* c, size_t np, float* out_linear, uint8_t* out_rgba) {
+    return copy_back({{out_linear, c->host_lin.p, np * 3 * sizeof(float)}, {out_rgba, c->host_rgba.p, np * 4}});
+}
 int render_to_host(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const FilmState& fs, const ListRender* list,
                    size_t np, float* out_linear, uint8_t* out_rgba) {
     if (np == 0) return render_impl(c, cam, prm, fs, list, nullptr, nullptr);   // validates, renders nothing
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->host_lin.ensure(np * 3))) return rc;
-    if (out_rgba && (rc = c->host_rgba.ensure(np * 4))) return rc;
-    rc = render_impl(c, cam, prm, fs, list, c->host_lin.p, out_rgba ? c->host_rgba.p : nullptr);
-    if (!rc) rc = pt_sync(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, np * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, np * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return render_staged(c, np * 3, out_rgba ? np * 4 : 0, [&](float* d_linear, uint8_t* d_rgba) { return render_impl(c, cam, prm, fs, list, d_linear, d_rgba); },
+                         [&] { return film_back(c, np, out_linear, out_rgba); });
 }
 size_t tile_pixels(const PtCamera* cam, const PtRenderParams* prm) {
     return (size_t)pt_tile_rows(cam->height, prm->band_rows, prm->band_index, prm->band_count ? prm->band_count : 1) * cam->width;
@@ -92,22 +117,17 @@ void begin_period(PtContext* c) {        // the first render since the last coll
     c->expected_samples = 0;
 }
 
-// CHECK, the part render_adaptive_impl makes too.  cam = null: the paths are given, no camera ray is generated.
-int check_scene_and_camera(const PtContext* c, const PtCamera* cam) {
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    if (cam && (cam->width < 2 || cam->height < 2))   // get_ray_with_offset divides by width-1 / height-1 (camera.rs:140-141)
-        return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
-    return PT_OK;
-}
+// CHECK: the pieces (pt_entry.h; above the namespace) in render_impl's order.  No camera is checked where the paths are given and
+// no camera ray is generated.
 int check_render(const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const ListRender* list, const float* d_linear,
                  const uint8_t* d_rgba) {
     if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "render: null argument");
-    if (int rc = check_scene_and_camera(c, list && list->inject[0] && (!list->tile || list->no_camera) ? nullptr : cam)) return rc;
-    if (prm->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
-    if (prm->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "unknown integrator %u", prm->integrator);
-    if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
+    const bool given = list && list->inject[0] && (!list->tile || list->no_camera);
     const uint32_t band_count = prm->band_count ? prm->band_count : 1;
-    if (prm->band_index >= band_count) return fail(PT_ERR_INVALID_ARG, "band_index %u >= band_count %u", prm->band_index, band_count);
+    int rc;
+    if ((rc = check_scene(c)) || (!given && (rc = check_camera_size(cam))) || (rc = check_spp(prm->spp)) || (rc = check_integrator(prm->integrator)) ||
+        (rc = check_accel(prm->accel)) || (rc = check_band_index(prm->band_index, band_count)))
+        return rc;
     if (list && !list->tile && band_count != 1) return fail(PT_ERR_INVALID_ARG, "pixel-list renders take the whole image (band_count = 1)");
     // the resolve stores a pixel's RGBA8 as one 32-bit word (a byte-offset pointer would fault on the device)
     if (d_rgba && (uintptr_t)d_rgba % 4u) return fail(PT_ERR_INVALID_ARG, "render: the RGBA8 output buffer must be 4-byte aligned");
@@ -605,15 +625,9 @@ int pt_render_lens_host(PtContext* c, const PtCamera* cam, const PtLens* lens, c
     const size_t np = tile_pixels(cam, prm);
     if (np == 0) return render_lens_impl("pt_render_lens_host", c, cam, lens, prm, nullptr, nullptr);   // validates, renders nothing
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->host_lin.ensure(np * 3))) return rc;
-    if (out_rgba && (rc = c->host_rgba.ensure(np * 4))) return rc;
-    rc = render_lens_impl("pt_render_lens_host", c, cam, lens, prm, c->host_lin.p, out_rgba ? c->host_rgba.p : nullptr);
-    if (!rc) rc = pt_sync(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, np * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, np * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return render_staged(c, np * 3, out_rgba ? np * 4 : 0,
+                         [&](float* d_linear, uint8_t* d_rgba) { return render_lens_impl("pt_render_lens_host", c, cam, lens, prm, d_linear, d_rgba); },
+                         [&] { return film_back(c, np, out_linear, out_rgba); });
 }
 
 int pt_render_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, float* d_linear, uint8_t* d_rgba) {
@@ -639,7 +653,7 @@ int pt_render_progressive(PtContext* c, const PtCamera* cam, const PtRenderParam
                           PtProgressFn fn, void* user, float* out_linear, uint8_t* out_rgba) {
     if (!c || !cam || !prm || !out_linear || !out_rgba)
         return fail(PT_ERR_INVALID_ARG, "pt_render_progressive: null argument");
-    if (prm->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
+    if (int rc = check_spp(prm->spp)) return rc;
     if (spp_step == 0) spp_step = prm->spp;
     const size_t np = tile_pixels(cam, prm);
     int rc = PT_OK;
@@ -712,15 +726,13 @@ int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams
     if (prm->spp < ad->spp_min) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: spp (= spp_max) %u < spp_min %u", prm->spp, ad->spp_min);
     if (!(ad->rel_tol >= 0.0) || !std::isfinite(ad->rel_tol)) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: rel_tol must be finite and >= 0");
     if (!(ad->abs_floor > 0.0)) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: abs_floor must be > 0");
-    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: renders the whole image (band_count = 1)");
-    if (int rc = check_scene_and_camera(c, cam)) return rc;
-    const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "pt_render_adaptive: %llu pixels", (unsigned long long)np64);
-    const uint32_t np = (uint32_t)np64, spp_max = prm->spp, W = cam->width;
+    int rc;
+    if ((rc = check_whole_image("pt_render_adaptive", ": renders", "", prm)) || (rc = check_scene(c)) || (rc = check_camera_size(cam)) ||
+        (rc = check_pixel_count("pt_render_adaptive", cam->width, cam->height)))
+        return rc;
+    const uint32_t np = cam->width * cam->height, spp_max = prm->spp, W = cam->width;
     HIP_TRY(hipSetDevice(c->device));
     const hipStream_t st = c->stream;
-    int rc;
     if ((rc = c->ad_sums.ensure(5 * (size_t)np)) || (rc = c->ad_count.ensure(np)) || (rc = c->ad_conv.ensure(np)) ||
         (rc = c->ad_err.ensure(np)) || (rc = c->ad_list[0].ensure(np)) || (rc = c->ad_list[1].ensure(np)) ||
         (rc = c->ad_words.ensure(1 + (np + ptk::kSelectTile - 1) / ptk::kSelectTile)) || (rc = c->host_lin.ensure(3 * (size_t)np)) ||
@@ -768,11 +780,8 @@ int pt_render_adaptive(PtContext* c, const PtCamera* cam, const PtRenderParams* 
     int rc;
     if ((rc = render_adaptive_impl(c, cam, prm, ad))) return rc;
     const size_t np = (size_t)cam->width * cam->height;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    if (out_spp) HIP_TRY(hipMemcpy(out_spp, c->ad_count.p, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_rel_err) HIP_TRY(hipMemcpy(out_rel_err, c->ad_err.p, np * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return copy_back({{out_linear, c->host_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np},
+                      {out_spp, c->ad_count.p, np * sizeof(uint32_t)}, {out_rel_err, c->ad_err.p, np * sizeof(float)}});
 }
 
 int pt_ray_color(PtContext* c, const PtRenderParams* prm, const double* rays, const uint32_t* xy, uint32_t n, float* out_rgb) {

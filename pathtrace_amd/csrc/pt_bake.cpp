@@ -1,7 +1,8 @@
 // pt_bake.cpp -- the host side of light baking: lightmaps and probe bakes as users of the injected-path driver
 // (render_injected_impl, pt_api.cpp) with k_bake_paths as their fill, the launches that follow the render (k_bake_mask, k_probe_sh),
-// the rule on the CPU (pt_bake.h in exact arithmetic), the SH entries that need no device, and the debug entry.
-#include "pt_context.h"
+// the rule on the CPU (pt_bake.h in exact arithmetic), the SH entries that need no device, and the debug entry.  The entries' rule,
+// check_plane and the host entries' staging: pt_entry.h.
+#include "pt_entry.h"
 #include "pt_bake.h"
 #include "pt_filter.h"        // ptflt::camera_words: words 0 and 1 of the camera block, on the host
 
@@ -21,15 +22,7 @@ int check_film(const char* who, uint32_t kind, uint32_t width, uint32_t height) 
     }
     return PT_OK;
 }
-int check_whole(const char* who, const PtRenderParams* prm) {
-    if (prm->band_count > 1) return fail(PT_ERR_INVALID_ARG, "%s bakes the whole image (band_count = 1)", who);
-    return PT_OK;
-}
-int check_plane(const char* who, const char* name, const void* p, uint32_t align, bool may_be_null = false) {
-    if (!p && !may_be_null) return fail(PT_ERR_INVALID_ARG, "%s: %s is null", who, name);
-    if ((uintptr_t)p % align) return fail(PT_ERR_INVALID_ARG, "%s: %s must be %u-byte aligned", who, name, align);
-    return PT_OK;
-}
+int check_whole(const char* who, const PtRenderParams* prm) { return check_whole_image(who, " bakes", "", prm, /*band_index_too=*/false); }
 
 // a camera for the film's geometry only (no camera ray is generated): the size, and a frame nothing reads
 PtCamera film_camera(uint32_t width, uint32_t height) {
@@ -124,16 +117,12 @@ int pt_bake_lightmap_host(PtContext* c, uint32_t width, uint32_t height, const f
     if (int rc = check_lightmap(who, c, width, height, texels6, prm, out_linear, out_rgba, 4)) return rc;
     const size_t np = (size_t)width * height;
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->bake_in.ensure(6 * np)) || (rc = c->host_lin.ensure(3 * np)) || (out_rgba && (rc = c->host_rgba.ensure(4 * np)))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));      // (an earlier call may still read the staging)
-    HIP_TRY(hipMemcpy(c->bake_in.p, texels6, 6 * np * sizeof(float), hipMemcpyHostToDevice));
-    rc = lightmap_impl(who, c, width, height, c->bake_in.p, prm, c->host_lin.p, out_rgba ? c->host_rgba.p : nullptr);
-    if (!rc) rc = pt_sync(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    return PT_OK;
+    if (int rc = c->bake_in.ensure(6 * np)) return rc;
+    return render_staged(c, 3 * np, out_rgba ? 4 * np : 0, [&](float* d_linear, uint8_t* d_rgba) {
+        HIP_TRY(hipStreamSynchronize(c->stream));      // (an earlier call may still read the staging)
+        HIP_TRY(hipMemcpy(c->bake_in.p, texels6, 6 * np * sizeof(float), hipMemcpyHostToDevice));
+        return lightmap_impl(who, c, width, height, c->bake_in.p, prm, d_linear, d_rgba);
+    }, [&] { return copy_back({{out_linear, c->host_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np}}); });
 }
 
 int pt_bake_probes_device(PtContext* c, const float* d_positions3, uint32_t n_probes, uint32_t rays_per_probe, const PtRenderParams* prm,
@@ -148,17 +137,15 @@ int pt_bake_probes_host(PtContext* c, const float* positions3, uint32_t n_probes
     if (int rc = check_probes(who, c, positions3, n_probes, rays_per_probe, prm, out_radiance, out_sh27)) return rc;
     const size_t np = (size_t)n_probes * rays_per_probe;
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->bake_in.ensure(3 * (size_t)n_probes)) || (rc = c->host_lin.ensure(3 * np)) || (out_sh27 && (rc = c->bake_sh.ensure(27 * (size_t)n_probes))))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->bake_in.p, positions3, 3 * (size_t)n_probes * sizeof(float), hipMemcpyHostToDevice));
-    rc = probes_impl(who, c, c->bake_in.p, n_probes, rays_per_probe, prm, c->host_lin.p, out_sh27 ? c->bake_sh.p : nullptr);
-    if (!rc) rc = pt_sync(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_radiance, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_sh27) HIP_TRY(hipMemcpy(out_sh27, c->bake_sh.p, 27 * (size_t)n_probes * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    if (int rc = c->bake_in.ensure(3 * (size_t)n_probes)) return rc;
+    return render_staged(c, 3 * np, 0, [&](float* d_radiance, uint8_t*) {
+        if (int rc = c->bake_sh.ensure(out_sh27 ? 27 * (size_t)n_probes : 0)) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));      // (an earlier call may still read the staging)
+        HIP_TRY(hipMemcpy(c->bake_in.p, positions3, 3 * (size_t)n_probes * sizeof(float), hipMemcpyHostToDevice));
+        return probes_impl(who, c, c->bake_in.p, n_probes, rays_per_probe, prm, d_radiance, out_sh27 ? c->bake_sh.p : nullptr);
+    }, [&] {
+        return copy_back({{out_radiance, c->host_lin.p, 3 * np * sizeof(float)}, {out_sh27, c->bake_sh.p, 27 * (size_t)n_probes * sizeof(float)}});
+    });
 }
 
 int pt_sh_project_device(PtContext* c, uint32_t n_probes, uint32_t rays_per_probe, const float* d_radiance, float* d_sh27) {

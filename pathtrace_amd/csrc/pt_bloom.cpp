@@ -1,12 +1,12 @@
 // pt_bloom.cpp -- the host side of the bloom stage (rule: pt_bloom.h): the entries, their one argument check, the
-// launches of a frame's pyramid, the rule on the CPU (pt_bloom_host), and pt_display_device = bloom, then pt_tonemap_device.  As in
-// pt_tonemap.cpp the arguments are checked before the context is looked at and before any HIP call.
+// launches of a frame's pyramid, the rule on the CPU (pt_bloom_host), and pt_display_device = bloom, then pt_tonemap_device.  The
+// entries' rule and the checks they share with the other film entries: pt_entry.h.
 #include <cassert>
 #include <cmath>
 #include <vector>
 
 #include "pt_bloom.h"
-#include "pt_context.h"
+#include "pt_entry.h"
 
 namespace {
 
@@ -14,7 +14,8 @@ namespace {
 int check_bloom(const char* who, uint32_t width, uint32_t height, const PtBloom* bl, const float* in, const float* out) {
     if (!bl || !in || !out) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if ((uintptr_t)in % 4u || (uintptr_t)out % 4u) return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
-    if (width < 2 || height < 2) return fail(PT_ERR_INVALID_ARG, "%s: image %ux%u: width and height must be >= 2", who, width, height);
+    if (int rc = check_image_min(who, width, height)) return rc;
+    // (not check_pixel_count: this entry's code and words for the same limit differ from the other film entries', and are its ABI)
     if ((uint64_t)width * height > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "%s: %llu pixels: at most 2^30", who, (unsigned long long)width * height);
     if (bl->levels < 1u || bl->levels > pbloom::kMaxLevels) return fail(PT_ERR_INVALID_ARG, "%s: levels %u not in 1 .. 8", who, bl->levels);
     if (!std::isfinite(bl->threshold) || !(bl->threshold >= 0.0f)) return fail(PT_ERR_INVALID_ARG, "%s: threshold must be finite and >= 0", who);
@@ -153,10 +154,8 @@ int pt_display_host(PtContext* c, uint32_t width, uint32_t height, const float* 
     if ((rc = c->tone.lin.ensure(3 * np)) || (rc = c->tone.rgba.ensure(4 * np))) return rc;
     HIP_TRY(hipMemcpyAsync(c->tone.lin.p, linear, 3 * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if ((rc = pt_display_device(c, width, height, c->tone.lin.p, bl, tm, c->tone.lin.p, c->tone.rgba.p))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (out_linear) HIP_TRY(hipMemcpy(out_linear, c->tone.lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_rgba, c->tone.rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    return PT_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (as pt_tonemap_host: not pt_sync)
+    return copy_back({{out_linear, c->tone.lin.p, 3 * np * sizeof(float)}, {out_rgba, c->tone.rgba.p, 4 * np}});
 }
 
 int pt_bloom_host(uint32_t width, uint32_t height, const float* linear, const PtBloom* bl, float* out) {

@@ -1,13 +1,12 @@
 // pt_cascade.cpp -- the host side of the brightness cascade (rule: pt_cascade.h): the render whose resolve is
 // k_resolve_cascade followed by k_cascade_reweight, the two kernels on given samples, and the same rule on host planes on the
-// CPU.  The arguments are checked before the context is looked at and before any HIP call, as the other film entries do: a
-// refused call leaves the context as it was.
+// CPU.  The entries' rule and the checks they share with the other film entries: pt_entry.h; here, the cascade's own.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_cascade.h"
 
 namespace {
@@ -23,31 +22,12 @@ int check_cascade(const char* who, const PtCascade* cs, ptcas::Levels* lv) {
     return PT_OK;
 }
 
-int check_size(const char* who, uint32_t width, uint32_t height) {
-    if (width < 2 || height < 2) return fail(PT_ERR_INVALID_ARG, "%s: image %ux%u: width and height must be >= 2", who, width, height);
-    if ((uint64_t)width * height > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)width * height);
-    return PT_OK;
-}
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 // the planes an entry writes: aligned, and no two of them (nor any of them and the samples read) share a byte
 int check_planes(const char* who, size_t np, const void* samples, size_t samples_bytes, const float* linear, const uint8_t* rgba,
                  const float* plain) {
     if ((uintptr_t)samples % 4u || (uintptr_t)linear % 4u || (uintptr_t)rgba % 4u || (uintptr_t)plain % 4u)
         return fail(PT_ERR_INVALID_ARG, "%s: the sample and film buffers must be 4-byte aligned", who);
-    const void* const out[3] = {linear, rgba, plain};
-    const size_t bytes[3] = {12 * np, 4 * np, 12 * np};
-    for (int i = 0; i < 3; ++i) {
-        if (overlap(out[i], bytes[i], samples, samples_bytes)) return fail(PT_ERR_INVALID_ARG, "%s: an output must not alias the samples", who);
-        for (int k = i + 1; k < 3; ++k)
-            if (overlap(out[i], bytes[i], out[k], bytes[k])) return fail(PT_ERR_INVALID_ARG, "%s: the outputs must not alias one another", who);
-    }
-    return PT_OK;
+    return check_no_alias(who, {{linear, 12 * np}, {rgba, 4 * np}, {plain, 12 * np}}, {samples, samples_bytes});
 }
 
 int ensure_state(PtContext* c, uint32_t K, size_t np) {
@@ -81,12 +61,10 @@ int reweight(PtContext* c, const ptcas::Levels& lv, uint32_t width, uint32_t hei
 int check_render_cascade(const char* who, const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtCascade* cs,
                          ptcas::Levels* lv) {
     int rc;
-    if ((rc = check_cascade(who, cs, lv)) || (rc = check_size(who, cam->width, cam->height))) return rc;
-    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "%s: renders the whole image (band_count = 1): the re-weighting reads a pixel's neighbours", who);
-    if (prm->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    return PT_OK;
+    if ((rc = check_cascade(who, cs, lv)) || (rc = check_image_size(who, cam->width, cam->height)) ||
+        (rc = check_whole_image(who, ": renders", ": the re-weighting reads a pixel's neighbours", prm)) || (rc = check_spp(prm->spp)))
+        return rc;
+    return check_scene(c);
 }
 
 int render_cascade_device(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtCascade* cs, float* d_linear,
@@ -142,7 +120,7 @@ int pt_cascade_host(const PtCascade* cs, uint32_t width, uint32_t height, uint32
     if (!cs || !samples || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     ptcas::Levels lv;
     int rc;
-    if ((rc = check_cascade(who, cs, &lv)) || (rc = check_size(who, width, height))) return rc;
+    if ((rc = check_cascade(who, cs, &lv)) || (rc = check_image_size(who, width, height))) return rc;
     if (n == 0) return fail(PT_ERR_INVALID_ARG, "%s: n must be > 0", who);
     const size_t np = (size_t)width * height;
     if ((rc = check_planes(who, np, samples, 12 * np * n, out_linear, out_rgba, out_plain))) return rc;
@@ -158,7 +136,7 @@ int pt_cascade_samples_device(PtContext* c, const PtCascade* cs, uint32_t width,
     if (!cs || !d_samples || !d_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     ptcas::Levels lv;
     int rc;
-    if ((rc = check_cascade(who, cs, &lv)) || (rc = check_size(who, width, height))) return rc;
+    if ((rc = check_cascade(who, cs, &lv)) || (rc = check_image_size(who, width, height))) return rc;
     if (n == 0) return fail(PT_ERR_INVALID_ARG, "%s: n must be > 0", who);
     const size_t np = (size_t)width * height;
     if ((rc = check_planes(who, np, d_samples, 12 * np * n, d_linear, d_rgba, d_plain))) return rc;
@@ -194,23 +172,19 @@ int pt_render_cascade_host(PtContext* c, const PtCamera* cam, const PtRenderPara
     const size_t np = (size_t)cam->width * cam->height;
     const uint32_t K = lv.K;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->host_lin.ensure(3 * np)) || (out_rgba && (rc = c->host_rgba.ensure(4 * np))) || (out_plain && (rc = c->cas_plain.ensure(3 * np))) ||
-        (out_weights && (rc = c->cas_weights.ensure((size_t)K * np))))
-        return rc;
-    rc = render_cascade_device(who, c, cam, prm, cs, c->host_lin.p, out_rgba ? c->host_rgba.p : nullptr, out_plain ? c->cas_plain.p : nullptr,
-                               out_weights ? c->cas_weights.p : nullptr);
-    if (!rc) rc = pt_sync(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    if (out_plain) HIP_TRY(hipMemcpy(out_plain, c->cas_plain.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_weights) HIP_TRY(hipMemcpy(out_weights, c->cas_weights.p, (size_t)K * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_layers) {
-        std::vector<double> planes(3 * (size_t)K * np);
-        HIP_TRY(hipMemcpy(planes.data(), c->cas_state.p, planes.size() * sizeof(double), hipMemcpyDeviceToHost));
-        layers_from_planes(planes, K, np, out_layers);
-    }
-    return PT_OK;
+    std::vector<double> planes;
+    rc = render_staged(c, 3 * np, out_rgba ? 4 * np : 0, [&](float* d_linear, uint8_t* d_rgba) {
+        int bad;
+        if ((bad = c->cas_plain.ensure(out_plain ? 3 * np : 0)) || (bad = c->cas_weights.ensure(out_weights ? (size_t)K * np : 0))) return bad;
+        return render_cascade_device(who, c, cam, prm, cs, d_linear, d_rgba, out_plain ? c->cas_plain.p : nullptr, out_weights ? c->cas_weights.p : nullptr);
+    }, [&] {
+        if (out_layers) planes.resize(3 * (size_t)K * np);
+        return copy_back({{out_linear, c->host_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np},
+                          {out_plain, c->cas_plain.p, 3 * np * sizeof(float)}, {out_weights, c->cas_weights.p, (size_t)K * np * sizeof(float)},
+                          {out_layers ? planes.data() : nullptr, c->cas_state.p, planes.size() * sizeof(double)}});
+    });
+    if (!rc && out_layers) layers_from_planes(planes, K, np, out_layers);
+    return rc;
 }
 
 }  // extern "C"

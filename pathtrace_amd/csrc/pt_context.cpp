@@ -6,7 +6,7 @@
 #include <memory>
 #include <mutex>
 
-#include "pt_context.h"
+#include "pt_entry.h"
 
 namespace {
 
@@ -177,7 +177,7 @@ int pt_debug_launch_log(PtContext* c, uint32_t* out, uint32_t cap, uint32_t* n) 
 // Debug: what one linear scan of the uploaded scene tests -- spheres, single triangles, triangle PAIRS (two consecutive
 // triangles with the same v0 and plane normal share determinant, t and hit point: tripair_test).
 int pt_debug_scan_layout(PtContext* c, uint32_t* n_spheres, uint32_t* n_triangles, uint32_t* n_pairs) {
-    if (!c || !c->has_scene) return fail(PT_ERR_INVALID_ARG, "no scene uploaded");
+    if (int rc = check_scene(c, nullptr)) return rc;
     if (n_spheres) *n_spheres = c->scan_counts[0];
     if (n_triangles) *n_triangles = c->scan_counts[1];
     if (n_pairs) *n_pairs = c->scan_counts[2];

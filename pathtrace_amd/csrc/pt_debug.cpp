@@ -1,14 +1,14 @@
 // pt_debug.cpp -- the pt_debug_* entries that launch a kernel over the uploaded scene: closest hits, and one function of the
 // device code per launch of k_debug_fn (BSDF, shape and light sampling, camera rays, the joint scan).
-#include "pt_context.h"
+#include "pt_entry.h"
 
 namespace {
 
 int debug_hit_impl(PtContext* c, const double* rays, uint32_t n, double t_min, double t_max, uint32_t exact_math,
                    uint32_t accel, int32_t* out_id, float* out_t, float* out_rec) {
     if (!c || !rays || !out_id) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "no scene uploaded");
-    if (accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", accel);
+    if (int rc = check_scene(c, nullptr)) return rc;
+    if (int rc = check_accel(accel)) return rc;
     if (n == 0) return PT_OK;
     HIP_TRY(hipSetDevice(c->device));
     if (accel == PT_ACCEL_AUTO) {
@@ -41,7 +41,7 @@ int debug_hit_impl(PtContext* c, const double* rays, uint32_t n, double t_min, d
 int debug_fn(PtContext* c, uint32_t op, uint32_t obj, const std::vector<float>& in, uint32_t in_stride, const uint32_t* words,
              uint32_t n, uint32_t out_stride, uint32_t exact_math, const PtCamera* cam, float* out) {
     if (!c || !out) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "no scene uploaded");
+    if (int rc = check_scene(c, nullptr)) return rc;
     if (op != ptk::kFnLightPoint && op != ptk::kFnCameraRay && obj >= c->view.n_objs)
         return fail(PT_ERR_INVALID_ARG, "object %u out of range (%u objects)", obj, c->view.n_objs);
     if (n == 0) return PT_OK;
@@ -118,7 +118,7 @@ int pt_debug_light_point(PtContext* c, const double* from3, const uint32_t* word
 }
 int pt_debug_camera_rays(PtContext* c, const PtCamera* cam, const uint32_t* xys, uint32_t n, uint32_t exact_math, float* out8) {
     if ((!cam || !xys) && n) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (cam && (cam->width < 2 || cam->height < 2)) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    if (int rc = cam ? check_camera_size(cam) : PT_OK) return rc;
     std::vector<uint32_t> w(4 * (size_t)n, 0u);
     for (size_t i = 0; i < n; ++i) { w[4 * i] = xys[3 * i]; w[4 * i + 1] = xys[3 * i + 1]; w[4 * i + 2] = xys[3 * i + 2]; }
     return debug_fn(c, ptk::kFnCameraRay, 0, std::vector<float>(), 1, w.data(), n, 8, exact_math, cam, out8);

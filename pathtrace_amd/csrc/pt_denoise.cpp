@@ -1,11 +1,12 @@
 // pt_denoise.cpp -- the host side of the denoisers.  Device entries: the first-hit feature and id passes, the a-trous filter (its
 // own or a given variance plane), the adaptive pass's variance plane, temporal accumulation (plain, following moving objects through
 // pt_motion.h, with a per-pixel weight) and the gradients (pt_gradient.h) that make that weight.  Host entries: pt_render_*denoised*.
+// The entries' rule, the checks shared with the other entries, the render's preconditions and copy_back: pt_entry.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_gradient.h"
 #include "pt_motion.h"
 
@@ -46,22 +47,13 @@ int check_film_aligned(const char* who, const Film& f) {
 
 int check_film_size(const char* who, uint32_t width, uint32_t height, const Film& f) {
     if (f.out_linear == f.linear) return fail(PT_ERR_INVALID_ARG, "%s: the output must not be the input", who);
-    if ((uint64_t)width * height > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)width * height);
-    return PT_OK;
+    return check_pixel_count(who, width, height);
 }
 
-int check_whole_image(const char* who, const char* verb, const PtRenderParams* prm) {   // verb: "works on" or "renders"
-    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "%s: %s the whole image (band_count = 1)", who, verb);
-    return PT_OK;
-}
-
-int check_target(const char* who, const PtContext* c, const PtCamera* cam) {   // what render_impl would refuse, in its words
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    if (cam->width < 2 || cam->height < 2) return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
-    const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
-    return PT_OK;
+int check_target(const char* who, const PtContext* c, const PtCamera* cam) {   // what render_impl would refuse, by its own checks
+    int rc;
+    if ((rc = check_scene(c)) || (rc = check_camera_size(cam))) return rc;
+    return check_pixel_count(who, cam->width, cam->height);
 }
 
 bool same_camera(const PtCamera& a, const PtCamera& b) {   // the four vectors, field by field (the sizes are the caller's to compare)
@@ -122,13 +114,6 @@ int frame_front(History form, PtContext* c, const PtCamera* cam, const PtRenderP
     return form >= History::motion ? pt_render_feature_ids_device(c, cam, p, c->dn_ids.p) : PT_OK;
 }
 
-struct CopyBack { void* host; const void* dev; size_t bytes; };   // blocking, the stream is through; a null host pointer: not asked for
-int copy_back(std::initializer_list<CopyBack> copies) {
-    for (const CopyBack& k : copies)
-        if (k.host) HIP_TRY(hipMemcpy(k.host, k.dev, k.bytes, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
 // First-hit features: per batch of samples, k_feature_rays writes the camera rays, launch_debug_hit (the scan or BVH of the
 // parity entries) finds their hits, k_feature_resolve adds the records to the per-pixel sums in d_features.
 // pt_render_feature_ids_device is the same pass over the one sample spp_offset without the resolve: the hit ids of that batch,
@@ -143,11 +128,10 @@ int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLe
     if (lens && (rc = lens_setup(who, cam, lens, &lf))) return rc;
     ptk::ProjF pf{};
     if (proj && (rc = projection_setup(who, cam, proj, &pf))) return rc;
-    if ((rc = check_whole_image(who, "works on", prm))) return rc;
+    if ((rc = check_whole_image(who, ": works on", "", prm))) return rc;
     if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
     if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
-    if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
-    if ((rc = check_target(who, c, cam))) return rc;
+    if ((rc = check_accel(prm->accel)) || (rc = check_target(who, c, cam))) return rc;
     const size_t np = (size_t)cam->width * cam->height;
     HIP_TRY(hipSetDevice(c->device));
     uint32_t accel = prm->accel;
@@ -216,7 +200,7 @@ int render_denoised_impl(const char* who, History form, PtContext* c, const PtCa
     if (lens && (rc = lens_setup(who, cam, lens, &checked))) return rc;
     ptk::ProjF proj_checked;
     if (proj && (rc = projection_setup(who, cam, proj, &proj_checked))) return rc;
-    if ((rc = check_whole_image(who, "renders", prm))) return rc;
+    if ((rc = check_whole_image(who, ": renders", "", prm))) return rc;
     if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
     if ((rc = check_target(who, c, cam))) return rc;
     const size_t np = (size_t)cam->width * cam->height;
@@ -274,10 +258,8 @@ int temporal_impl(const char* who, History form, PtContext* c, const PtCamera* c
     const bool motion = form != History::plain;
     if (!cam || !dn || !tp || !f.linear || !f.features || !f.out_linear || (motion && !d_ids) || (form == History::alpha && !d_alpha))
         return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
-    if (cam->width < 2 || cam->height < 2)
-        return fail(PT_ERR_INVALID_ARG, "%s: camera %ux%u: width and height must be >= 2", who, cam->width, cam->height);
     int rc;
-    if ((rc = check_denoise(who, dn)) || (rc = check_weight(who, "alpha", tp->alpha))) return rc;
+    if ((rc = check_camera_size(cam, who)) || (rc = check_denoise(who, dn)) || (rc = check_weight(who, "alpha", tp->alpha))) return rc;
     if (!(tp->depth_tol >= 0.0f) || !(tp->normal_tol >= 0.0f) || !std::isfinite(tp->depth_tol) || !std::isfinite(tp->normal_tol))
         return fail(PT_ERR_INVALID_ARG, "%s: depth_tol and normal_tol must be finite and >= 0", who);
     if ((rc = check_film_aligned(who, f)) || (rc = check_film_size(who, cam->width, cam->height, f))) return rc;
@@ -285,7 +267,7 @@ int temporal_impl(const char* who, History form, PtContext* c, const PtCamera* c
     if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
     if ((uintptr_t)d_alpha % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_alpha must be 4-byte aligned", who);
     if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
-    if (motion && !c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
+    if (motion && (rc = check_scene(c, who))) return rc;
     if (motion && c->view.n_objs > (1u << 24) - 2u)
         return fail(PT_ERR_UNSUPPORTED, "%s: %u objects (an id + 1 must be exact in the history's f32 lane: at most 2^24 - 2)", who, c->view.n_objs);
     HIP_TRY(hipSetDevice(c->device));
@@ -354,16 +336,12 @@ int gradient_impl(const char* who, Strata form, PtContext* c, const PtCamera* ca
         return fail(PT_ERR_INVALID_ARG, "%s: the previous camera is %ux%u, the camera %ux%u", who, prev_cam->width, prev_cam->height,
                     cam->width, cam->height);
     int rc;
-    if ((rc = check_whole_image(who, "works on", prev)) || (rc = check_gradient(who, g)) || (rc = check_weight(who, "alpha_min", alpha_min))) return rc;
-    if (cam->width < 2 || cam->height < 2)
-        return fail(PT_ERR_INVALID_ARG, "%s: camera %ux%u: width and height must be >= 2", who, cam->width, cam->height);
-    if (prev->spp == 0) return fail(PT_ERR_INVALID_ARG, "%s: spp must be > 0", who);
-    if (prev->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "%s: unknown integrator %u", who, prev->integrator);
-    if (prev->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "%s: unknown accel %u", who, prev->accel);
-    const uint64_t np64 = (uint64_t)cam->width * cam->height;
-    if (np64 > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)np64);
+    if ((rc = check_whole_image(who, ": works on", "", prev)) || (rc = check_gradient(who, g)) || (rc = check_weight(who, "alpha_min", alpha_min)) ||
+        (rc = check_camera_size(cam, who)) || (rc = check_spp(prev->spp, who)) || (rc = check_integrator(prev->integrator, who)) ||
+        (rc = check_accel(prev->accel, who)) || (rc = check_pixel_count(who, cam->width, cam->height)))
+        return rc;
     if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
+    if ((rc = check_scene(c, who))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t ns = (size_t)ptgr::strata(cam->width) * ptgr::strata(cam->height);
     if ((rc = c->gr_list.ensure(ns)) || (rc = c->gr_film.ensure(3 * ns)) || (rc = c->gr_rec.ensure(2 * ns))) return rc;
@@ -400,7 +378,7 @@ int render_gradient_impl(const char* who, Strata form, PtContext* c, const PtCam
                          float* out_noisy, float* out_features, int32_t* out_ids, float* out_alpha) {
     if (!c || !cam || !prm || !dn || !tp || !g || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = check_whole_image(who, "renders", prm))) return rc;
+    if ((rc = check_whole_image(who, ": renders", "", prm))) return rc;
     if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
     if ((rc = check_gradient(who, g)) || (rc = check_weight(who, "alpha", tp->alpha)) || (rc = check_target(who, c, cam))) return rc;
     const size_t np = (size_t)cam->width * cam->height;
@@ -439,7 +417,7 @@ int denoised_frame_device(const char* who, PtContext* c, const PtCamera* cam, co
                           const PtDenoise* dn, PtRenderParams* p) {
     if (!c || !cam || !prm || !dn) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = check_whole_image(who, "renders", prm))) return rc;
+    if ((rc = check_whole_image(who, ": renders", "", prm))) return rc;
     if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
     if ((rc = check_denoise(who, dn)) || (rc = check_target(who, c, cam))) return rc;
     HIP_TRY(hipSetDevice(c->device));

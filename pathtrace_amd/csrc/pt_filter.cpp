@@ -1,13 +1,12 @@
 // pt_filter.cpp -- the host side of the film's reconstruction filters (rule: pt_filter.h): the render whose resolve
-// is k_resolve_filter, that kernel on given samples, and the same rule on host planes on the CPU.  The arguments are checked
-// before the context is looked at and before any HIP call, as the other film entries do: a refused call leaves the context as
-// it was.
+// is k_resolve_filter, that kernel on given samples, and the same rule on host planes on the CPU.  The entries' rule and the
+// checks they share with the other film entries: pt_entry.h; here, the filter's own.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_filter.h"
 
 namespace {
@@ -25,31 +24,12 @@ int check_filter(const char* who, const PtFilter* f, ptflt::Rule* r) {
     return PT_OK;
 }
 
-int check_size(const char* who, uint32_t width, uint32_t height) {
-    if (width < 2 || height < 2) return fail(PT_ERR_INVALID_ARG, "%s: image %ux%u: width and height must be >= 2", who, width, height);
-    if ((uint64_t)width * height > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)width * height);
-    return PT_OK;
-}
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 // the planes an entry writes: aligned, and no two of them (nor any of them and the samples read) share a byte
 int check_planes(const char* who, size_t np, const void* samples, size_t samples_bytes, const float* linear, const uint8_t* rgba,
                  const float* plain, const double* wsum) {
     if ((uintptr_t)samples % 4u || (uintptr_t)linear % 4u || (uintptr_t)rgba % 4u || (uintptr_t)plain % 4u || (uintptr_t)wsum % 8u)
         return fail(PT_ERR_INVALID_ARG, "%s: the sample and film buffers must be 4-byte aligned, the weight sums 8-byte", who);
-    const void* const out[4] = {linear, rgba, plain, wsum};
-    const size_t bytes[4] = {12 * np, 4 * np, 12 * np, 8 * np};
-    for (int i = 0; i < 4; ++i) {
-        if (overlap(out[i], bytes[i], samples, samples_bytes)) return fail(PT_ERR_INVALID_ARG, "%s: an output must not alias the samples", who);
-        for (int k = i + 1; k < 4; ++k)
-            if (overlap(out[i], bytes[i], out[k], bytes[k])) return fail(PT_ERR_INVALID_ARG, "%s: the outputs must not alias one another", who);
-    }
-    return PT_OK;
+    return check_no_alias(who, {{linear, 12 * np}, {rgba, 4 * np}, {plain, 12 * np}, {wsum, 8 * np}}, {samples, samples_bytes});
 }
 
 ptk::FilterResolveArgs resolve_args(const PtContext* c, const ptflt::Rule& r, uint32_t width, uint32_t height, uint32_t n, float* d_linear,
@@ -67,12 +47,10 @@ ptk::FilterResolveArgs resolve_args(const PtContext* c, const ptflt::Rule& r, ui
 int check_render_filtered(const char* who, const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtFilter* f,
                           ptflt::Rule* r) {
     int rc;
-    if ((rc = check_filter(who, f, r)) || (rc = check_size(who, cam->width, cam->height))) return rc;
-    if ((prm->band_count ? prm->band_count : 1) != 1 || prm->band_index != 0)
-        return fail(PT_ERR_INVALID_ARG, "%s: renders the whole image (band_count = 1): the filter reads a pixel's neighbours", who);
-    if (prm->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    return PT_OK;
+    if ((rc = check_filter(who, f, r)) || (rc = check_image_size(who, cam->width, cam->height)) ||
+        (rc = check_whole_image(who, ": renders", ": the filter reads a pixel's neighbours", prm)) || (rc = check_spp(prm->spp)))
+        return rc;
+    return check_scene(c);
 }
 
 int render_filtered_device(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtFilter* f, float* d_linear,
@@ -132,7 +110,7 @@ int pt_filter_host(const PtFilter* flt, uint32_t width, uint32_t height, uint32_
     if (!flt || !samples || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     ptflt::Rule r;
     int rc;
-    if ((rc = check_filter(who, flt, &r)) || (rc = check_size(who, width, height))) return rc;
+    if ((rc = check_filter(who, flt, &r)) || (rc = check_image_size(who, width, height))) return rc;
     if (n == 0) return fail(PT_ERR_INVALID_ARG, "%s: n must be > 0", who);
     const size_t np = (size_t)width * height;
     if ((rc = check_planes(who, np, samples, 12 * np * n, out_linear, out_rgba, out_plain, out_wsum))) return rc;
@@ -148,7 +126,7 @@ int pt_filter_samples_device(PtContext* c, const PtFilter* flt, uint32_t width, 
     if (!flt || !d_samples || !d_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     ptflt::Rule r;
     int rc;
-    if ((rc = check_filter(who, flt, &r)) || (rc = check_size(who, width, height))) return rc;
+    if ((rc = check_filter(who, flt, &r)) || (rc = check_image_size(who, width, height))) return rc;
     if (n == 0) return fail(PT_ERR_INVALID_ARG, "%s: n must be > 0", who);
     const size_t np = (size_t)width * height;
     if ((rc = check_planes(who, np, d_samples, 12 * np * n, d_linear, d_rgba, d_plain, d_wsum))) return rc;
@@ -183,16 +161,14 @@ int pt_render_filtered_host(PtContext* c, const PtCamera* cam, const PtRenderPar
     if ((rc = check_render_filtered(who, c, cam, prm, flt, &r))) return rc;
     const size_t np = (size_t)cam->width * cam->height;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->host_lin.ensure(3 * np)) || (out_rgba && (rc = c->host_rgba.ensure(4 * np))) || (out_plain && (rc = c->flt_plain.ensure(3 * np))))
-        return rc;
-    rc = render_filtered_device(who, c, cam, prm, flt, c->host_lin.p, out_rgba ? c->host_rgba.p : nullptr, out_plain ? c->flt_plain.p : nullptr);
-    if (!rc) rc = pt_sync(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    if (out_plain) HIP_TRY(hipMemcpy(out_plain, c->flt_plain.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_wsum) HIP_TRY(hipMemcpy(out_wsum, c->flt_state.p + 3 * np, np * sizeof(double), hipMemcpyDeviceToHost));   // plane 3 of the state: Wt
-    return PT_OK;
+    return render_staged(c, 3 * np, out_rgba ? 4 * np : 0, [&](float* d_linear, uint8_t* d_rgba) {
+        if (int bad = c->flt_plain.ensure(out_plain ? 3 * np : 0)) return bad;
+        return render_filtered_device(who, c, cam, prm, flt, d_linear, d_rgba, out_plain ? c->flt_plain.p : nullptr);
+    }, [&] {
+        return copy_back({{out_linear, c->host_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np},
+                          {out_plain, c->flt_plain.p, 3 * np * sizeof(float)},
+                          {out_wsum, c->flt_state.p + 3 * np, np * sizeof(double)}});   // plane 3 of the state: Wt
+    });
 }
 
 }  // extern "C"

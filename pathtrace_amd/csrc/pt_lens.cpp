@@ -1,6 +1,6 @@
 // pt_lens.cpp -- the host side of the thin-lens camera that is not the render driver's (pt_api.cpp: render_lens_impl): the checks
 // and the device's words (pt_lens.h), the defaults, the debug entries, and the entries of the lens forms pt_denoise.cpp holds.
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_lens.h"
 
 ptk::CameraF camera_f32(const PtCamera* cam) {
@@ -62,12 +62,10 @@ int pt_debug_lens_rays(PtContext* c, const PtCamera* cam, const PtLens* lens, co
                        float* out8) {
     if (!c || !cam || !lens || (n && (!xys || !out8))) return fail(PT_ERR_INVALID_ARG, "pt_debug_lens_rays: null argument");
     ptk::LensF l;
-    if (int rc = lens_setup("pt_debug_lens_rays", cam, lens, &l)) return rc;
-    if (cam->width < 2 || cam->height < 2)
-        return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
+    int rc;
+    if ((rc = lens_setup("pt_debug_lens_rays", cam, lens, &l)) || (rc = check_camera_size(cam))) return rc;
     if (n == 0) return PT_OK;
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
     if ((rc = c->fn_out.ensure(8 * (size_t)n)) || (rc = c->fn_words.ensure(4 * (size_t)n))) return rc;
     std::vector<uint32_t> w(4 * (size_t)n, 0u);
     for (size_t i = 0; i < n; ++i) { w[4 * i] = xys[3 * i]; w[4 * i + 1] = xys[3 * i + 1]; w[4 * i + 2] = xys[3 * i + 2]; }

@@ -1,11 +1,11 @@
 // pt_probe_grid.cpp -- the host side of the irradiance volume: the grid helpers, the bake of a grid (k_probe_positions in
 // front of pt_bake_probes_device), the shading pass (k_probe_shade) alone and behind the feature pass, and the rule on the CPU
-// (pt_probe_grid.h).
+// (pt_probe_grid.h).  The entries' rule, check_plane, the render's preconditions and the host entry's staging: pt_entry.h.
 #include <cmath>
 #include <cstddef>
 #include <cstring>
 
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_probe_grid.h"
 
 namespace {
@@ -26,11 +26,6 @@ ptk::ProbeGridArgs kernel_grid(const PtProbeGrid* g) {
     return a;
 }
 
-int check_plane(const char* who, const char* name, const void* p, uint32_t align, bool may_be_null = false) {
-    if (!p && !may_be_null) return fail(PT_ERR_INVALID_ARG, "%s: %s is null", who, name);
-    if ((uintptr_t)p % align) return fail(PT_ERR_INVALID_ARG, "%s: %s must be %u-byte aligned", who, name, align);
-    return PT_OK;
-}
 int check_grid(const char* who, const PtProbeGrid* g) {
     if (!g) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (pt_probe_grid_count(g) == 0u)
@@ -49,9 +44,7 @@ int check_shade(const char* who, const PtCamera* cam, const PtProbeGrid* g, cons
     if (sp->weight >= (uint32_t)ptgrid::kWeights) return fail(PT_ERR_INVALID_ARG, "%s: unknown weight %u", who, sp->weight);
     if (!std::isfinite(sp->normal_bias)) return fail(PT_ERR_INVALID_ARG, "%s: normal_bias must be finite", who);
     if (cam->width == 0 || cam->height == 0) return fail(PT_ERR_INVALID_ARG, "%s: image %ux%u: a zero size", who, cam->width, cam->height);
-    if ((uint64_t)cam->width * cam->height > (1ull << 30))
-        return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)cam->width * cam->height);
-    if ((rc = check_plane(who, "sh27", sh27, 4)) || (!own_features && (rc = check_plane(who, "the feature plane", features, feat_align))) ||
+    if ((rc = check_pixel_count(who, cam->width, cam->height)) || (rc = check_plane(who, "sh27", sh27, 4)) || (!own_features && (rc = check_plane(who, "the feature plane", features, feat_align))) ||
         (rc = check_plane(who, "the fallback plane", fallback, 4, true)) || (rc = check_plane(who, "the linear output", out_linear, 4)) ||
         (rc = check_plane(who, "the RGBA8 output", out_rgba, 4, true)))
         return rc;
@@ -119,13 +112,10 @@ int pt_probe_grid_bake_device(PtContext* c, const PtProbeGrid* g, uint32_t rays_
     if ((rc = check_grid(who, g))) return rc;
     if (rays_per_probe == 0 || rays_per_probe > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: rays_per_probe must be in [1, 65535]", who);
     if ((rc = check_plane(who, "sh27", d_sh27, 4))) return rc;
-    // what the probe bake would refuse behind the positions launch, in its words
-    if (prm->band_count > 1) return fail(PT_ERR_INVALID_ARG, "%s bakes the whole image (band_count = 1)", who);
-    if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "render: no scene uploaded");
-    if (prm->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
-    if (prm->integrator > PT_INTEGRATOR_BRDF_ONLY) return fail(PT_ERR_INVALID_ARG, "unknown integrator %u", prm->integrator);
-    if (prm->accel > PT_ACCEL_AUTO) return fail(PT_ERR_INVALID_ARG, "unknown accel %u", prm->accel);
-    if (prm->band_index != 0) return fail(PT_ERR_INVALID_ARG, "band_index %u >= band_count %u", prm->band_index, 1u);
+    // what the probe bake would refuse behind the positions launch, by its own checks (band_count <= 1 from here on)
+    if ((rc = check_whole_image(who, " bakes", "", prm, /*band_index_too=*/false)) || (rc = check_scene(c)) || (rc = check_spp(prm->spp)) ||
+        (rc = check_integrator(prm->integrator)) || (rc = check_accel(prm->accel)) || (rc = check_band_index(prm->band_index, 1u)))
+        return rc;
     const uint32_t n = pt_probe_grid_count(g);
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = c->pg_pos.ensure(3 * (size_t)n)) || (rc = c->pg_rad.ensure(3 * (size_t)n * rays_per_probe))) return rc;
@@ -177,18 +167,13 @@ int pt_render_probe_lit_host(PtContext* c, const PtCamera* cam, const PtRenderPa
     if (int rc = check_probe_lit("pt_render_probe_lit_host", c, cam, prm, g, sh27, fallback, sp, out_linear, out_rgba)) return rc;
     const size_t np = (size_t)cam->width * cam->height, nsh = 27 * (size_t)pt_probe_grid_count(g);
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->bake_sh.ensure(nsh)) || (rc = c->host_lin.ensure(3 * np)) || (out_rgba && (rc = c->host_rgba.ensure(4 * np)))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));      // (an earlier call may still read the staging)
-    HIP_TRY(hipMemcpy(c->bake_sh.p, sh27, nsh * sizeof(float), hipMemcpyHostToDevice));
-    if (fallback) HIP_TRY(hipMemcpy(c->host_lin.p, fallback, 3 * np * sizeof(float), hipMemcpyHostToDevice));
-    rc = probe_lit_impl(c, cam, prm, feature_samples, g, c->bake_sh.p, fallback ? c->host_lin.p : nullptr, sp, c->host_lin.p,
-                        out_rgba ? c->host_rgba.p : nullptr);
-    if (!rc) rc = pt_sync(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    return PT_OK;
+    if (int rc = c->bake_sh.ensure(nsh)) return rc;
+    return render_staged(c, 3 * np, out_rgba ? 4 * np : 0, [&](float* d_linear, uint8_t* d_rgba) {
+        HIP_TRY(hipStreamSynchronize(c->stream));      // (an earlier call may still read the staging)
+        HIP_TRY(hipMemcpy(c->bake_sh.p, sh27, nsh * sizeof(float), hipMemcpyHostToDevice));
+        if (fallback) HIP_TRY(hipMemcpy(d_linear, fallback, 3 * np * sizeof(float), hipMemcpyHostToDevice));
+        return probe_lit_impl(c, cam, prm, feature_samples, g, c->bake_sh.p, fallback ? d_linear : nullptr, sp, d_linear, d_rgba);
+    }, [&] { return copy_back({{out_linear, c->host_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np}}); });
 }
 
 int pt_debug_probe_positions(PtContext* c, const PtProbeGrid* g, float* out_positions3) {

@@ -1,7 +1,8 @@
 // pt_projection.cpp -- the host side of the projections and the caller's rays that is not the render driver's
 // (pt_api.cpp: render_injected_impl and its users): the checks and the device's words (pt_projection.h), the defaults, the rule
-// on the CPU, the debug entry, and the entries of the projection forms pt_denoise.cpp holds.
-#include "pt_context.h"
+// on the CPU, the debug entry, and the entries of the projection forms pt_denoise.cpp holds.  The entries' rule and the host
+// render's staging: pt_entry.h.
+#include "pt_entry.h"
 #include "pt_filter.h"        // ptflt::camera_words: words 0 and 1 of the camera block, on the host
 #include "pt_projection.h"
 
@@ -66,12 +67,6 @@ void host_ray(const ptproj::Setup& P, const ptk::CameraF& cf, uint32_t x, uint32
     out8[6] = a; out8[7] = b;
 }
 
-int check_camera_size(const PtCamera* cam) {
-    if (cam->width < 2 || cam->height < 2)
-        return fail(PT_ERR_INVALID_ARG, "camera %ux%u: width and height must be >= 2", cam->width, cam->height);
-    return PT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -96,15 +91,9 @@ int pt_render_projection_host(PtContext* c, const PtCamera* cam, const PtProject
     const size_t np = (size_t)pt_tile_rows(cam->height, prm->band_rows, prm->band_index, prm->band_count ? prm->band_count : 1) * cam->width;
     if (np == 0) return render_projection_impl("pt_render_projection_host", c, cam, proj, prm, nullptr, nullptr);   // validates, renders nothing
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->host_lin.ensure(np * 3))) return rc;
-    if (out_rgba && (rc = c->host_rgba.ensure(np * 4))) return rc;
-    rc = render_projection_impl("pt_render_projection_host", c, cam, proj, prm, c->host_lin.p, out_rgba ? c->host_rgba.p : nullptr);
-    if (!rc) rc = pt_sync(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->host_lin.p, np * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, np * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return render_staged(c, np * 3, out_rgba ? np * 4 : 0, [&](float* d_linear, uint8_t* d_rgba) {
+        return render_projection_impl("pt_render_projection_host", c, cam, proj, prm, d_linear, d_rgba);
+    }, [&] { return copy_back({{out_linear, c->host_lin.p, np * 3 * sizeof(float)}, {out_rgba, c->host_rgba.p, np * 4}}); });
 }
 
 int pt_render_features_projection_device(PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,

@@ -5,7 +5,7 @@
 #include <utility>
 
 #include "pt_bvh.h"
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_scene_records.h"
 
 // The scene as a launch in the given arithmetic mode sees it (the records carry constants evaluated in that mode)
@@ -80,7 +80,7 @@ int scene_set(const char* who, PtContext* c, const PtObject* objs, uint32_t n, b
     if (!c || (!objs && n)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (order != PT_BVH_ORDER_MORTON && order != PT_BVH_ORDER_MEDIAN) return fail(PT_ERR_INVALID_ARG, "%s: order %u (PT_BVH_ORDER_MORTON or PT_BVH_ORDER_MEDIAN)", who, order);
     if (keep_history) {
-        if (!c->has_scene) return fail(PT_ERR_INVALID_ARG, "%s: no scene uploaded", who);
+        if (int rc = check_scene(c, who)) return rc;
         if (n != c->view.n_objs) return fail(PT_ERR_INVALID_ARG, "%s: %u objects, the uploaded scene has %u", who, n, c->view.n_objs);
         for (uint32_t i = 0; i < n; ++i)
             if (objs[i].shape_tag != c->h_shape_tag[i])

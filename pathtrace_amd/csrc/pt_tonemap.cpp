@@ -1,10 +1,10 @@
 // pt_tonemap.cpp -- the host side of the display transform (rule: pt_tonemap.h): the film's luminance histogram,
-// the exposure the context adapts over frames, the curve and the transfer.  The arguments are checked before the context is
-// looked at and before any HIP call, as the denoiser entries do: a refused call leaves the context as it was.
+// the exposure the context adapts over frames, the curve and the transfer.  The entries' rule and the checks they share with the
+// other film entries: pt_entry.h.
 #include <cmath>
 #include <cstring>
 
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_tonemap.h"
 
 int TonemapState::ensure(hipStream_t st) {
@@ -22,9 +22,7 @@ namespace {
 int check_film(const char* who, uint32_t width, uint32_t height, const float* d_linear) {
     if (!d_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if ((uintptr_t)d_linear % 4u) return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
-    if (width < 2 || height < 2) return fail(PT_ERR_INVALID_ARG, "%s: image %ux%u: width and height must be >= 2", who, width, height);
-    if ((uint64_t)width * height > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)width * height);
-    return PT_OK;
+    return check_image_size(who, width, height);
 }
 
 bool in_unit(float v) { return v >= 0.0f && v <= 1.0f; }      // false for NaN
@@ -119,10 +117,8 @@ int pt_tonemap_host(PtContext* c, uint32_t width, uint32_t height, const float* 
     if ((rc = c->tone.lin.ensure(3 * np)) || (rc = c->tone.rgba.ensure(4 * np))) return rc;
     HIP_TRY(hipMemcpyAsync(c->tone.lin.p, linear, 3 * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if ((rc = pt_tonemap_device(c, width, height, c->tone.lin.p, tm, c->tone.lin.p, c->tone.rgba.p))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (out_linear) HIP_TRY(hipMemcpy(out_linear, c->tone.lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_rgba, c->tone.rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    return PT_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (not pt_sync: no render ran, there are no statistics to collect)
+    return copy_back({{out_linear, c->tone.lin.p, 3 * np * sizeof(float)}, {out_rgba, c->tone.rgba.p, 4 * np}});
 }
 
 // On the stream, like the frames around it: a context that has not metered yet has nothing to forget.

@@ -1,12 +1,11 @@
 // pt_upsample.cpp -- the host side of feature-guided upsampling (rule: pt_upsample.h): the device entry (one launch
 // of k_upsample), the same rule on host planes on the CPU, and the one-call frame that renders low and reconstructs at full size.
-// The arguments are checked before the context is looked at and before any HIP call, as the denoiser entries do: a refused call
-// leaves the context as it was.
+// The entries' rule, the pixel limit and the one-call frame's staging: pt_entry.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
-#include "pt_context.h"
+#include "pt_entry.h"
 #include "pt_upsample.h"
 
 namespace {
@@ -22,8 +21,7 @@ int check_size(const char* who, uint32_t lo_width, uint32_t lo_height, uint32_t 
         return fail(PT_ERR_INVALID_ARG, "%s: image %ux%u from %ux%u: every dimension must be >= 2", who, width, height, lo_width, lo_height);
     if (lo_width > width || lo_height > height)
         return fail(PT_ERR_INVALID_ARG, "%s: the low size %ux%u is above the full size %ux%u", who, lo_width, lo_height, width, height);
-    if ((uint64_t)width * height > (1ull << 30)) return fail(PT_ERR_UNSUPPORTED, "%s: %llu pixels", who, (unsigned long long)width * height);
-    return PT_OK;
+    return check_pixel_count(who, width, height);      // (the two lines above: this entry's own four-dimension form)
 }
 
 // What pt_upsample_device and pt_upsample_host read and write, and what both check before anything is looked at
@@ -106,20 +104,19 @@ int pt_render_denoised_upsampled(PtContext* c, const PtCamera* cam, const PtRend
     lo_cam.width = lo_width; lo_cam.height = lo_height;
     const size_t np = (size_t)cam->width * cam->height, np_lo = (size_t)lo_width * lo_height;
     PtRenderParams p;
-    if ((rc = denoised_frame_device(who, c, &lo_cam, prm, feature_samples, dn, &p)) ||      // (the remaining checks are its own)
-        (rc = c->host_rgba.ensure(4 * np)) || (rc = c->up_feat.ensure(2 * np)) || (rc = c->up_lin.ensure(3 * np)))
-        return rc;
-    float* const feat = reinterpret_cast<float*>(c->up_feat.p);
-    if ((rc = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat)) ||
-        (rc = pt_upsample_device(c, lo_width, lo_height, c->dn_lin.p, reinterpret_cast<float*>(c->dn_feat.p), cam->width, cam->height, feat, up,
-                                 c->up_lin.p, out_rgba ? c->host_rgba.p : nullptr)) ||
-        (rc = pt_sync(c)))
-        return rc;
-    HIP_TRY(hipMemcpy(out_linear, c->up_lin.p, 3 * np * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, c->host_rgba.p, 4 * np, hipMemcpyDeviceToHost));
-    if (out_lo_linear) HIP_TRY(hipMemcpy(out_lo_linear, c->dn_lin.p, 3 * np_lo * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_features) HIP_TRY(hipMemcpy(out_features, feat, 8 * np * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    if ((rc = denoised_frame_device(who, c, &lo_cam, prm, feature_samples, dn, &p))) return rc;      // (the remaining checks are its own)
+    // (the RGBA8 staging whether asked for or not, and none of host_lin: it holds the low film's noisy input)
+    return render_staged(c, 0, 4 * np, [&](float*, uint8_t* d_rgba) {
+        int bad;
+        if ((bad = c->up_feat.ensure(2 * np)) || (bad = c->up_lin.ensure(3 * np))) return bad;
+        float* const feat = reinterpret_cast<float*>(c->up_feat.p);
+        if ((bad = pt_render_features_device(c, cam, &p, std::min(feature_samples, p.spp), feat))) return bad;
+        return pt_upsample_device(c, lo_width, lo_height, c->dn_lin.p, reinterpret_cast<float*>(c->dn_feat.p), cam->width, cam->height, feat, up,
+                                  c->up_lin.p, out_rgba ? d_rgba : nullptr);
+    }, [&] {
+        return copy_back({{out_linear, c->up_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np},
+                          {out_lo_linear, c->dn_lin.p, 3 * np_lo * sizeof(float)}, {out_features, c->up_feat.p, 8 * np * sizeof(float)}});
+    });
 }
 
 }  // extern "C"

@@ -12,23 +12,19 @@ with this file copied into that checkout, and is only ever recorded again from a
 new truth.  ENTRIES below restates that commit's order of checks, entry by entry; the context is a pointer that is never
 followed (a case that reached the context would read the zeroed scratch behind it, not a PtContext).
 """
-import ctypes as C
-import json
 import math
 import os
 import sys
 
 import pytest
 
+from refusal_cases import BAD_F, HUGE, at, merge, call as _call, cases as _cases, floats as _floats, nulls as _nulls, record, table_of
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = os.path.join(ROOT, "tests", "golden", "denoise_refusals.json")
-HUGE = {"width": 1 << 16, "height": 1 << 15}                   # 2^31 pixels
-BAD_F = (("-1", -1.0), ("nan", math.nan), ("inf", math.inf))
 STRUCTS = ("cam", "prev_cam", "prm", "dn", "tp", "g", "ad")
 
-_scratch = (C.c_char * (1 << 16))()
-_base = C.addressof(_scratch) + (-C.addressof(_scratch)) % 16
-OK, ODD4, ODD16, OUT, FAKE = (C.c_void_p(_base + k) for k in (0, 2, 4, 2048, 4096))
+OK, ODD4, ODD16, OUT, FAKE = (at(k) for k in (0, 2, 4, 2048, 4096))
 
 # ---------------------------------------------------------------- the arguments of a call that passes every check
 _frame = dict(c=FAKE, cam={}, prm={}, fs=2, dn={})
@@ -59,15 +55,7 @@ GOOD = {
 # ---------------------------------------------------------------- the checks, in the order 6aa9e05 makes them
 # A step is one check: a list of (label, the arguments that trip it).  Every entry of the list is a case of its own; the
 # first stands for the step in the pair with the step after it.  A dict as the value of a struct argument names the fields
-# that differ from the defaults.
-def _nulls(*names):
-    return [(f"null {n}", {n: None}) for n in names]
-
-
-def _floats(arg, field, bad=BAD_F):
-    return [(f"{field}={t}", {arg: {field: v}}) for t, v in bad]
-
-
+# that differ from the defaults.  (The machinery: refusal_cases.py.)
 BAND = [("band_count=2", {"prm": {"band_rows": 2, "band_count": 2}}), ("band_index=1", {"prm": {"band_index": 1}})]
 SMALL = [(f"camera {w}x{h}", {"cam": {"width": w, "height": h}}) for w, h in ((1, 8), (8, 1), (0, 0))]
 DENOISE = [[("iterations=17", {"dn": {"iterations": 17}})],
@@ -128,20 +116,9 @@ ENTRIES = {
 }
 
 
-def _merge(a, b):
-    out = dict(a)
-    for k, v in b.items():
-        assert not (isinstance(v, dict) and k in out and out[k] is None), "a field of a null struct"
-        out[k] = {**out[k], **v} if isinstance(v, dict) and isinstance(out.get(k), dict) else v
-    return out
-
-
 def cases(entry):
     """-> [(label, overrides)]: every case of every step, then the pair of each step with the next"""
-    steps = ENTRIES[entry]
-    out = [case for step in steps for case in step]
-    out += [(f"{a[0][0]} + {b[0][0]}", _merge(a[0][1], b[0][1])) for a, b in zip(steps, steps[1:])]
-    return out
+    return _cases(ENTRIES[entry])
 
 
 def _struct(pt, name, fields):
@@ -158,11 +135,7 @@ def _struct(pt, name, fields):
 
 def call(pt, entry, overrides):
     """-> [return code, message]"""
-    lib = pt._lib.lib()
-    args = _merge(GOOD[entry], overrides)
-    held = [_struct(pt, n, v) if n in STRUCTS and v is not None else v for n, v in args.items()]
-    rc = getattr(lib, entry)(*[C.byref(v) if isinstance(v, C.Structure) else v for v in held])
-    return [rc, lib.pt_last_error().decode()]
+    return _call(pt, entry, merge(GOOD[entry], overrides), STRUCTS, _struct)
 
 
 def test_every_entry_of_the_file_is_covered():
@@ -175,7 +148,7 @@ def test_every_entry_of_the_file_is_covered():
 
 @pytest.mark.parametrize("entry", sorted(ENTRIES))
 def test_refusals_are_those_of_the_recorded_commit(pt, entry):
-    table = {t: [rc, msg.replace("{who}", entry)] for rc, msg, labels in json.load(open(TABLE))[entry] for t in labels}
+    table = table_of(TABLE, entry)
     mine = cases(entry)
     assert sorted(t for t, _ in mine) == sorted(table) and len(mine) == len(table), "the cases are not the recorded ones"
     for label, overrides in mine:
@@ -187,15 +160,4 @@ if __name__ == "__main__":
         sys.exit(__doc__)
     sys.path.insert(0, ROOT)
     import pathtrace_amd
-    n, lines = 0, []
-    for e in sorted(ENTRIES):
-        answers = {}                                            # (code, message) -> labels, in the order of first appearance
-        for t, o in cases(e):
-            rc, msg = call(pathtrace_amd, e, o)
-            assert rc != 0, f"{e}: {t} was not refused"
-            answers.setdefault((rc, msg.replace(e, "{who}")), []).append(t)
-            n += 1
-        lines.append(json.dumps(e) + ": [\n" + ",\n".join("  " + json.dumps([rc, msg, ts]) for (rc, msg), ts in answers.items()) + "\n ]")
-    with open(TABLE, "w") as f:
-        f.write("{\n " + ",\n ".join(lines) + "\n}\n")
-    print(n, "cases ->", TABLE)
+    record(TABLE, ENTRIES, cases, lambda e, o: call(pathtrace_amd, e, o))
