@@ -211,8 +211,13 @@ def projection_rays_host(cam, proj, xys):
 BAKE_KINDS = {"texels": 0, "lightmap": 0, "probes": 1}
 
 
-def _pv(a):
-    return a.ctypes.data_as(C.c_void_p)
+def _ptr(ctype):
+    """-> the function array -> pointer to its data as ctype* (void* without a type); None stays a null pointer"""
+    t = C.POINTER(ctype) if ctype else C.c_void_p
+    return lambda a: a.ctypes.data_as(t) if a is not None else None
+
+
+_pv, _pd, _pu, _pf, _pu64 = (_ptr(t) for t in (None, C.c_double, C.c_uint32, C.c_float, C.c_uint64))
 
 
 def _bake_film(kind, data):
@@ -482,12 +487,7 @@ class Context:
 
     def debug_bvh_read(self):
         """pt_debug_bvh_read: the context's device tree -> dict as bvh_refit_check's (without cost_at_build)."""
-        nn, ns = C.c_uint32(0), C.c_uint32(0)
-        check(lib().pt_debug_bvh_read(self._h, None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None))
-        t = _BvhArrays(nn.value, ns.value)
-        check(lib().pt_debug_bvh_read(self._h, _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids), ns.value,
-                                      C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now)))
-        return t.as_dict()
+        return _bvh_export(lib().pt_debug_bvh_read, (self._h,))
 
     def set_stream(self, hip_stream_ptr):
         """Render on a caller-owned stream.  0 is the handle of HIP's legacy default stream (torch's default stream):
@@ -581,22 +581,6 @@ def _f64(a, cols):
     return np.ascontiguousarray(a, dtype=np.float64).reshape(-1, cols)
 
 
-def _pd(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
-
-
-def _pu(a):
-    return a.ctypes.data_as(C.POINTER(C.c_uint32)) if a is not None else None
-
-
-def _pf(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _pu64(a):
-    return a.ctypes.data_as(C.POINTER(C.c_uint64))
-
-
 class _BvhArrays:
     """Output arrays of pt_debug_bvh_refit_check / pt_debug_bvh_read for a tree of the given size."""
 
@@ -614,6 +598,23 @@ class _BvhArrays:
         return dict(qnodes=self.qnodes, leaf_rec=self.leaf_rec, leaf_lead=self.leaf_lead, leaf_ids=self.leaf_ids, grid_min=self.grid[:3].copy(),
                     grid_cell=self.grid[3:6].copy(), scene_abs=self.grid[6:7].copy(), root=self.root.value, cost_now=self.cost_now,
                     cost_at_build=self.cost_at_build)
+
+
+def _bvh_export(fn, lead, keys=None, order=None, cost_at_build=False):
+    """The two-call exchange of a tree export: fn(*lead, <arrays, capacities, sizes, grid, root, cost_now>, <extras>) once for the
+    sizes, then with a _BvhArrays of that size.  The extras: cost_at_build (pt_debug_bvh_refit_check), or keys, order and their
+    capacity (the checks of an order: the dict then carries no cost_at_build).  -> the dict of _BvhArrays"""
+    nn, ns = C.c_uint32(0), C.c_uint32(0)
+    no_extras = (None,) if cost_at_build else (None, None, 0) if keys is not None else ()
+    check(fn(*lead, None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None, *no_extras))
+    t = _BvhArrays(nn.value, ns.value)
+    extras = (_pu64(t.cost_at_build),) if cost_at_build else (_pu(keys), _pu(order), len(order)) if keys is not None else ()
+    check(fn(*lead, _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids), ns.value, C.byref(nn), C.byref(ns), _pf(t.grid),
+             C.byref(t.root), _pu64(t.cost_now), *extras))
+    d = t.as_dict()
+    if keys is not None:
+        del d["cost_at_build"]
+    return d
 
 
 class _ContextFunctions:
@@ -1386,13 +1387,7 @@ def bvh_refit_check(prev_objs, cur_objs, refit=True):
     u32[slots], grid_min f32[3], grid_cell f32[3], scene_abs f32[1], root, cost_now u64[3], cost_at_build u64[3]"""
     n = len(cur_objs)
     assert len(prev_objs) == n
-    nn, ns = C.c_uint32(0), C.c_uint32(0)
-    check(lib().pt_debug_bvh_refit_check(prev_objs, cur_objs, n, int(refit), None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None, None))
-    t = _BvhArrays(nn.value, ns.value)
-    check(lib().pt_debug_bvh_refit_check(prev_objs, cur_objs, n, int(refit), _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids),
-                                         ns.value, C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now),
-                                         _pu64(t.cost_at_build)))
-    return t.as_dict()
+    return _bvh_export(lib().pt_debug_bvh_refit_check, (prev_objs, cur_objs, n, int(refit)), cost_at_build=True)
 
 
 def bvh_morton_check(objs, refit_to=None):
@@ -1400,15 +1395,9 @@ def bvh_morton_check(objs, refit_to=None):
     (pt_scene_rebuild), verified; refit_to: then refitted to that pose of the same objects by the host refit.  -> dict as bvh_refit_check's (without cost_at_build) plus keys u32[n] (the 30-bit Morton key
     of every object) and order u32[n] (the object at every sorted position)."""
     n = len(objs)
-    nn, ns = C.c_uint32(0), C.c_uint32(0)
     assert refit_to is None or len(refit_to) == n
-    check(lib().pt_debug_bvh_morton_check(objs, refit_to, n, None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None, None, None, 0))
-    t = _BvhArrays(nn.value, ns.value)
     keys, order = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
-    check(lib().pt_debug_bvh_morton_check(objs, refit_to, n, _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids), ns.value,
-                                          C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now), _pu(keys), _pu(order), n))
-    d = t.as_dict()
-    del d["cost_at_build"]
+    d = _bvh_export(lib().pt_debug_bvh_morton_check, (objs, refit_to, n), keys, order)
     d.update(keys=keys, order=order)
     return d
 
@@ -1417,15 +1406,9 @@ def bvh_median_check(objs, refit_to=None):
     """pt_debug_bvh_median_check (host only): bvh_morton_check for the median order (pt_scene_rebuild_ordered).  -> the same
     dict with g u32[n,3] (the grid cells of every object) in place of keys."""
     n = len(objs)
-    nn, ns = C.c_uint32(0), C.c_uint32(0)
     assert refit_to is None or len(refit_to) == n
-    check(lib().pt_debug_bvh_median_check(objs, refit_to, n, None, 0, None, None, None, 0, C.byref(nn), C.byref(ns), None, None, None, None, None, 0))
-    t = _BvhArrays(nn.value, ns.value)
     g, order = np.zeros((n, 3), dtype=np.uint32), np.zeros(n, dtype=np.uint32)
-    check(lib().pt_debug_bvh_median_check(objs, refit_to, n, _pu(t.qnodes), nn.value, _pf(t.leaf_rec), _pf(t.leaf_lead), _pu(t.leaf_ids), ns.value,
-                                          C.byref(nn), C.byref(ns), _pf(t.grid), C.byref(t.root), _pu64(t.cost_now), _pu(g), _pu(order), n))
-    d = t.as_dict()
-    del d["cost_at_build"]
+    d = _bvh_export(lib().pt_debug_bvh_median_check, (objs, refit_to, n), g, order)
     d.update(g=g, order=order)
     return d
 

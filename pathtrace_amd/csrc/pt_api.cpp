@@ -138,7 +138,7 @@ int check_render(const PtContext* c, const PtCamera* cam, const PtRenderParams* 
 // ACCEL: PT_ACCEL_AUTO -> what actually runs
 uint32_t resolve_accel(PtContext* c, uint32_t accel) {
     if (accel != PT_ACCEL_AUTO) return accel;
-    if (c->auto_bvh && !c->bvh_refused && !c->bvh_failed) {
+    if (c->auto_bvh && c->tree.may_build()) {
         const std::string keep = g_err;              // a refused BVH is not an error of this call
         if (ensure_bvh(c) == PT_OK) return PT_ACCEL_BVH;
         g_err = keep;

@@ -1,5 +1,5 @@
 // pt_context.h -- what the host files of the library share (internal to csrc/): the error channel, the owners of GPU
-// resources, struct PtContext and the few functions that cross files.
+// resources, struct PtContext (its device BVH: struct DeviceBvh, pt_scene_bvh.h) and the few functions that cross files.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -78,6 +78,8 @@ struct TonemapState {   // pt_tonemap_device: the last histogram (258 words) and
     int ensure(hipStream_t st);   // pt_tonemap.cpp
 };
 
+#include "pt_scene_bvh.h"   // struct DeviceBvh, made of the owners above
+
 // lanes, buffer sets and the core size of overlapping launches: pt_sched.h (the scheduler's constants)
 using ptsched::kLanes;
 using ptsched::kSets;
@@ -99,54 +101,14 @@ struct PtContext {
     bool split_ok = false;            // a minority of the objects is Mirror: the regenerating form that batches their vertices pays
     uint32_t scan_counts[3] = {0, 0, 0};   // entries of the scan array by kind: spheres, single triangles, triangle pairs (pt_debug_scan_layout)
     uint32_t regen_occ[2][2][2] = {};  // cached occupancy query [exact_math][integrator][split] of this scene (0: not asked yet)
-    // BVH (PtRenderParams.accel): built from the host copy of the shape records at first use
+    // BVH (PtRenderParams.accel): the host copy of the shape records the first build reads, the shape tags on the device (uploaded
+    // with the scene; no later call can change them) for the device builds, and the device tree itself -- one object with its
+    // invariants and operations (pt_scene_bvh.h); no other file reads or writes its state
     std::vector<float4> h_shape;
     std::vector<uint32_t> h_shape_tag;
-    DevBuf<uint4> bvh_nodes;
-    DevBuf<float4> bvh_rec, bvh_lead;
-    DevBuf<uint32_t> bvh_ids;
-    bool has_bvh = false;
-    bool bvh_refused = false;         // the scene has a non-finite object: PT_ACCEL_AUTO stays with the linear scan
-    bool bvh_failed = false;          // the BVH builder refused this scene (depth): PT_ACCEL_AUTO stays with the scan
-    bool auto_bvh = false;            // PT_ACCEL_AUTO would take the BVH for this scene (ptscene::kAutoBvhWeight)
-    uint32_t bvh_depth = 0;
-    // pt_scene_refit: what the device-side refit needs beyond the tree -- the node indices by height (uploaded with the tree)
-    // and the first position of every height in that order (one launch per height), scratch for the f32 boxes (2 float4 per
-    // leaf slot, 2 per node), the three cost sums (pt_scene_bvh_cost) on the device and as the builder computed them
-    DevBuf<uint32_t> bvh_order;
-    std::vector<uint32_t> bvh_height_first;
-    DevBuf<float4> bvh_slot_box, bvh_node_box;
-    DevBuf<unsigned long long> bvh_cost;
-    uint32_t bvh_n_nodes = 0, bvh_n_slots = 0;
-    double bvh_cost_build = 0.0;      // cost of the tree as built, in the grid it was built with
-    uint32_t bvh_refits = 0;          // refits since the build
-    // pt_scene_rebuild (the Morton build on the device): the shape tags on the device (uploaded with the scene; no
-    // later call can change them), the (key, index) pairs and digit histograms of the sort, and the topology of
-    // ptbvh::morton_topology(bvh_topo_n) -- child codes and the order by height on the device, the rest here --, kept until
-    // the object count changes.  bvh_is_morton: the code words of bvh_nodes and bvh_order hold that topology (the host builder
-    // writes another).  A device build leaves the cost sums of the tree as built on the device (bvh_cost_built, copied on the
-    // stream behind the last level launch) and the grid cell they were counted in here; bvh_cost_on_device says which holds.
     DevBuf<uint32_t> shape_tag;
-    DevBuf<uint2> bvh_pairs[2];
-    DevBuf<uint32_t> bvh_hist;
-    DevBuf<uint4> bvh_topo_codes;
-    DevBuf<uint32_t> bvh_topo_order;
-    std::vector<uint32_t> bvh_topo_height_first;
-    int64_t bvh_topo_n = -1;
-    uint32_t bvh_topo_nodes = 0, bvh_topo_slots = 0, bvh_topo_root = 0, bvh_topo_depth = 0;
-    bool bvh_is_morton = false;
-    DevBuf<unsigned long long> bvh_cost_built;
-    float bvh_cost_cell[3] = {0.f, 0.f, 0.f};
-    bool bvh_cost_on_device = false;
-    // pt_scene_rebuild_ordered, the median order: the objects' grid cells, the bound words of a level's steps,
-    // and the split plan of ptbvh::median_plan(bvh_med_n) on the device (its levels here), kept until the object count changes
-    DevBuf<uint2> bvh_cells;
-    DevBuf<uint32_t> bvh_med_bounds, bvh_med_groups;
-    DevBuf<uint4> bvh_med_tiles;
-    DevBuf<uint2> bvh_med_tsteps;
-    std::vector<ptk::BvhMedianLevel> bvh_med_levels;
-    int64_t bvh_med_n = -1;
-    uint32_t bvh_med_n_tiles = 0, bvh_med_index_bits = 0;
+    bool auto_bvh = false;            // PT_ACCEL_AUTO would take the BVH for this scene (ptscene::kAutoBvhWeight)
+    DeviceBvh tree;
     // wavefront state
     DevBuf<float4> xchg;              // k_paths_regen_split: exchange stacks of every wave, one region per lane (stride: sched.xchg_stride)
     DevBuf<float4> queue[4];

@@ -13,7 +13,7 @@ int debug_hit_impl(PtContext* c, const double* rays, uint32_t n, double t_min, d
     HIP_TRY(hipSetDevice(c->device));
     if (accel == PT_ACCEL_AUTO) {
         const std::string keep = g_err;
-        accel = (c->auto_bvh && !c->bvh_refused && !c->bvh_failed && ensure_bvh(c) == PT_OK) ? PT_ACCEL_BVH : PT_ACCEL_LINEAR;
+        accel = (c->auto_bvh && c->tree.may_build() && ensure_bvh(c) == PT_OK) ? PT_ACCEL_BVH : PT_ACCEL_LINEAR;
         if (!accel) g_err = keep;
     }
     if (accel) { int rb = ensure_bvh(c); if (rb) return rb; }
@@ -136,31 +136,16 @@ int pt_debug_joint_scan(PtContext* c, const double* rays10, uint32_t n, double t
     return debug_fn(c, ptk::kFnJointScan, 0, in, 12, nullptr, n, 6, exact_math, nullptr, out6);
 }
 
-// The context's device tree, copied back (pt_debug_bvh_refit_check's outputs; blocking)
+// The context's device tree, copied back (the outputs of pt_debug_bvh_refit_check: struct BvhExport; blocking)
 int pt_debug_bvh_read(PtContext* c, uint32_t* out_qnodes, uint32_t cap_nodes, float* out_leaf_rec, float* out_leaf_lead, uint32_t* out_leaf_ids,
                       uint32_t cap_slots, uint32_t* n_nodes, uint32_t* n_slots, float* out_grid, uint32_t* root, uint64_t* cost_now) {
+    const BvhExport out{out_qnodes, cap_nodes, out_leaf_rec, out_leaf_lead, out_leaf_ids, cap_slots, out_grid, root, cost_now};
     if (!c) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_read: null context");
-    if ((cap_nodes && !out_qnodes) || (cap_slots && (!out_leaf_rec || !out_leaf_lead || !out_leaf_ids)))
-        return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_read: null output array with a non-zero capacity");
-    if (!c->has_bvh) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_read: the context holds no BVH");
+    if (out.null_array()) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_read: null output array with a non-zero capacity");
+    if (!c->tree.held()) return fail(PT_ERR_INVALID_ARG, "pt_debug_bvh_read: the context holds no BVH");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const size_t nn = cap_nodes < c->bvh_n_nodes ? cap_nodes : c->bvh_n_nodes, ns = cap_slots < c->bvh_n_slots ? cap_slots : c->bvh_n_slots;
-    if (nn) HIP_TRY(hipMemcpy(out_qnodes, c->bvh_nodes.p, nn * 4 * sizeof(uint4), hipMemcpyDeviceToHost));
-    if (ns) {
-        HIP_TRY(hipMemcpy(out_leaf_rec, c->bvh_rec.p, ns * 3 * sizeof(float4), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_leaf_lead, c->bvh_lead.p, ns * sizeof(float4), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_leaf_ids, c->bvh_ids.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    if (cost_now) HIP_TRY(hipMemcpy(cost_now, c->bvh_cost.p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (n_nodes) *n_nodes = c->bvh_n_nodes;
-    if (n_slots) *n_slots = c->bvh_n_slots;
-    if (out_grid) {
-        for (int k = 0; k < 3; ++k) { out_grid[k] = c->view.bvh.grid_min[k]; out_grid[3 + k] = c->view.bvh.grid_cell[k]; }
-        out_grid[6] = c->view.bvh.scene_abs;
-    }
-    if (root) *root = c->view.bvh.root;
-    return PT_OK;
+    return c->tree.read(c->view, out, n_nodes, n_slots);
 }
 
 }  // extern "C"

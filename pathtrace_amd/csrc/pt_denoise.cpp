@@ -137,7 +137,7 @@ int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLe
     uint32_t accel = prm->accel;
     if (accel == PT_ACCEL_AUTO) {
         const std::string keep = g_err;
-        accel = (c->auto_bvh && !c->bvh_refused && !c->bvh_failed && ensure_bvh(c) == PT_OK) ? PT_ACCEL_BVH : PT_ACCEL_LINEAR;
+        accel = (c->auto_bvh && c->tree.may_build() && ensure_bvh(c) == PT_OK) ? PT_ACCEL_BVH : PT_ACCEL_LINEAR;
         if (!accel) g_err = keep;
     }
     if (accel && (rc = ensure_bvh(c))) return rc;

@@ -259,3 +259,38 @@ def test_every_scene_call_mixes_on_one_context(pt, ctx2, scenes):
         f.close()
     ctx2.upload(poses[3])
     assert _same_film(got, _film(ctx2, cam, pt.default_params(spp=2, accel=PT_ACCEL_LINEAR)))
+
+
+# ------------------------------------------------------------------------------- the object count changes between builds
+# 5: the smallest count with a node; 4: one leaf, no node; 0: the empty tree; 1000: the arrays grow past 300's; the returns to
+# 65, 5 and 300 build in arrays that are larger than needed and hold another count's topology
+COUNTS = (300, 5, 4, 0, 65, 1000, 65, 5, 300)
+
+
+@pytest.mark.parametrize("schedule", ["morton", "median", "alternating"])
+def test_rebuilds_across_object_counts(pt, ctx2, schedule):
+    check = {"morton": pt.bvh_morton_check, "median": pt.bvh_median_check}
+    c = pt.Context(0)
+    try:
+        for step, n in enumerate(COUNTS):
+            order = ("morton", "median")[step % 2] if schedule == "alternating" else schedule
+            objs = rc.hand_made(pt, n) if n <= 4 else pt.builtin_scene(4, n)
+            c.upload(objs)
+            c.scene_rebuild(objs, order)
+            _is_the_host_build(pt, c, check[order](objs))
+            if n == 0:
+                continue
+            at_build = c.bvh_cost()[1]
+            pose = rc.moved(pt, np.random.default_rng(100 * step + n), objs)
+            c.scene_refit(pose)
+            want = check[order](objs, refit_to=pose)
+            got = c.debug_bvh_read()
+            assert rc.same_tree(got, want) is None, (step, n, order, rc.same_tree(got, want))
+            now, at_build2, refits = c.bvh_cost()
+            assert refits == 1 and at_build2 == at_build
+            assert now == pt.bvh_cost_value(want["cost_now"], want["grid_cell"])
+        cam = pt.camera_new(width=16, height=16)
+        ctx2.upload(pose)
+        assert _same_film(_film(c, cam, pt.default_params(spp=1, accel=PT_ACCEL_BVH)), _film(ctx2, cam, pt.default_params(spp=1, accel=PT_ACCEL_LINEAR)))
+    finally:
+        c.close()
