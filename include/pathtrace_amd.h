@@ -242,6 +242,10 @@ int pt_debug_raw_stats(PtContext* ctx, uint64_t* out16);
 /* Debug: the entries one linear scan of the uploaded scene tests: spheres, single triangles, and triangle PAIRS (two consecutive
  * triangles with the same first vertex and plane normal, e.g. the halves of a wall of World::new(), are tested together).     */
 int pt_debug_scan_layout(PtContext* ctx, uint32_t* n_spheres, uint32_t* n_triangles, uint32_t* n_pairs);
+/* Debug: *out = 1 when the scan consists of one run of at most 16 spheres and nothing else (k_paths_regen<MIS, diffuse> then walks
+ * it without the run records), else 0.  ctx != NULL: the flag the uploaded scene carries (objs, n unused).  ctx == NULL: what an
+ * upload of objs[0 .. n) would record; host only, no device.                                                                    */
+int pt_debug_spheres_only(PtContext* ctx, const PtObject* objs, uint32_t n, uint32_t* out);
 
 /* Same render with HOST output buffers (blocking): device staging is owned by the
  * context, results are copied back over PCIe.  out_rgba8 may be NULL.          */

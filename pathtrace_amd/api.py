@@ -528,6 +528,12 @@ class Context:
         check(lib().pt_debug_scan_layout(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def spheres_only(self):
+        """-> whether the uploaded scene's scan is one run of at most 16 spheres and nothing else (pt_debug_spheres_only)"""
+        v = C.c_uint32(0)
+        check(lib().pt_debug_spheres_only(self._h, None, 0, C.byref(v)))
+        return bool(v.value)
+
     def render_packed_into(self, cam, params, packed_ptr):
         """pt_render_device_packed: the tile as 16 B per pixel (linear RGB + RGBA8), the send-buffer form of the film gather."""
         check(lib().pt_render_device_packed(self._h, C.byref(cam), C.byref(params), C.c_void_p(packed_ptr)))
@@ -1331,6 +1337,14 @@ def render_multi(devices, cam, objs, params):
     check(lib().pt_render_multi(arr, len(devices), C.byref(cam), objs, len(objs), C.byref(params),
                                 lin.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p)))
     return lin, rgba
+
+
+def scene_spheres_only(objs):
+    """-> whether an upload of objs would record a scan of one run of at most 16 spheres and nothing else (pt_debug_spheres_only
+    without a context: host only)."""
+    v = C.c_uint32(0)
+    check(lib().pt_debug_spheres_only(None, objs, len(objs), C.byref(v)))
+    return bool(v.value)
 
 
 def path_instances():

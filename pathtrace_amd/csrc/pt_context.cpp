@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "pt_entry.h"
+#include "pt_scene_records.h"
 
 namespace {
 
@@ -181,6 +182,23 @@ int pt_debug_scan_layout(PtContext* c, uint32_t* n_spheres, uint32_t* n_triangle
     if (n_spheres) *n_spheres = c->scan_counts[0];
     if (n_triangles) *n_triangles = c->scan_counts[1];
     if (n_pairs) *n_pairs = c->scan_counts[2];
+    return PT_OK;
+}
+
+// Debug: is the scan array nothing but one run of at most kSpheresOnlyMax spheres (SceneView::spheres_only)?  With a context: the
+// flag the uploaded scene carries to the kernels (objs, n unused).  Without one: what an upload of objs[0 .. n) would record, on the
+// host alone (ptscene::build).
+int pt_debug_spheres_only(PtContext* c, const PtObject* objs, uint32_t n, uint32_t* out) {
+    if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_spheres_only: null argument");
+    if (c) {
+        if (int rc = check_scene(c, nullptr)) return rc;
+        *out = c->view.spheres_only;
+        return PT_OK;
+    }
+    if (!objs && n) return fail(PT_ERR_INVALID_ARG, "pt_debug_spheres_only: null argument");
+    ptscene::Records rec;
+    if (int rc = ptscene::build(objs, n, &rec)) return rc;
+    *out = rec.spheres_only ? 1u : 0u;
     return PT_OK;
 }
 

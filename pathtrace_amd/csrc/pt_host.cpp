@@ -116,6 +116,9 @@ int build(const PtObject* objs, uint32_t n, Records* out) {
         i += pair ? 2u : 1u;
     }
     for (const ptk::Run& run : runs) r.scan_counts[run.tag == ptk::kRunSphere ? 0 : run.tag == ptk::kRunTriangle ? 1 : 2] += run.count;
+    // the shape of the scan array a kernel may be compiled for: nothing but a few spheres (a fact of the object list, like the light count)
+    r.spheres_only = runs.size() == 1 && runs[0].tag == ptk::kRunSphere && runs[0].off4 == 0 && runs[0].first_obj == 0 &&
+                     runs[0].count == n && n <= ptk::kSpheresOnlyMax;
     r.has_blob = n <= ptk::kSmallObjs;
     if (r.has_blob) {
         // LDS image of a small scene: [scan | shape 3n | mat 2n | runs | lights (padded to 16 B)]

@@ -10,6 +10,9 @@ constexpr uint32_t kBlock = 256;
 // records: at most 9 float4 per object = 18 KiB); larger scenes stream their scan array
 // through one LDS tile and gather shape/material records from global memory.
 constexpr uint32_t kSmallObjs = 128;
+// SceneView::spheres_only holds for scenes of at most this many spheres (and nothing else): k_paths_regen<MIS, diffuse> then walks
+// the scan array as spheres 0 .. n - 1 without the run records (pt_kernels_scan.h)
+constexpr uint32_t kSpheresOnlyMax = 16;
 // occupancy k_paths_regen is compiled for (waves per SIMD = workgroups per CU): the host launches exactly that many
 #ifndef PT_REGEN_WAVES_DIFFUSE
 #define PT_REGEN_WAVES_DIFFUSE 6

@@ -19,7 +19,8 @@
 //                             world.rs:299) or, in a continuation launch (OVF), takes over the overflow queue.
 //   k_paths_regen<MIS, MATS>  level-0 launch of a batch of > 2^17 paths over a scene in LDS: a path stays in its lane's registers,
 //                             a lane whose path ends takes the batch's next one (chunk counters); compiled per material set.
-//                             A vertex's visibility ray and the next path ray go through the scene in one pass (scan_closest2).
+//                             A vertex's visibility ray and the next path ray go through the scene in one pass (scan_closest2);
+//                             a one-light scene of at most 16 spheres is scanned without the run records (SPHERES).
 //   k_paths_regen_split<..>   (pt_kernels_split.hip) the same for scenes with a few Mirror objects (the reference's own): a wave's Mirror vertices are
 //                             set aside on a per-wave stack and shaded 64 at a time.
 //   k_paths_bvh<MIS, OVF>     (pt_kernels_bvh.hip) the queue form for PtRenderParams.accel = 1: hit_scene by traversal of a 4-wide BVH, each pass cut
@@ -325,6 +326,13 @@ constexpr uint32_t kRegenBlock = PT_REGEN_BLOCK;
 // sphere-or-triangle choice a scalar branch.  Scenes with no light or several take the per-lane code.  The two forms are two
 // copies of the loop in one kernel (a launch runs one of them); they share the workgroup's LDS, which is why it is declared in
 // paths_regen_body and handed down (RegenLds).
+// SPHERES (chosen with ONE_LIGHT, by the same wave-uniform branch): the scan array is one run of at most kSpheresOnlyMax spheres at
+// offset 0, first object 0 (SceneView::spheres_only, decided at upload).  The scans enter the run's sphere code with those constants
+// and the count (scan_closest / scan_closest2 <.., SPHERES>, pt_kernels_scan.h): no loop over runs, no run record out of LDS and its
+// four readfirstlane, no dispatch on the tag, no triangle code in the loop; same tests, same order, same bits.  The kernel holds TWO
+// loops: <ONE_LIGHT, SPHERES> for one-light scenes of spheres only (C2, C3, C5) and the generic per-lane one for every other scene
+// -- a third copy (one light with triangles, as before this form existed) spills two to five VGPRs at 80, so such scenes take the
+// generic loop again (docs/EXPERIMENTS.md, "A spheres-only scene ...").
 struct RegenLds {            // one wave's parts of the workgroup's LDS
     float4* pool_d;          // !DENSE0: the ring of camera rays
     uint32_t* pool_s;
@@ -333,7 +341,7 @@ struct RegenLds {            // one wave's parts of the workgroup's LDS
     DenseWave* dw;           // DENSE0: ring entries and parked terms
     WgTotals* totals;
 };
-template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT>
+template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT, bool SPHERES>
 PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc, const RegenLds& w);
 
 template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0>
@@ -373,12 +381,12 @@ PT_DEV void paths_regen_body(const BounceArgs& a) {
     w.dw = &s_dense[DENSE0 ? wib : 0u];
     w.totals = &s_totals;
     if constexpr (DENSE0) {
-        if (sc.n_lights == 1u) { paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, true>(a, sc, w); return; }
+        if (sc.n_lights == 1u && sc.n_spheres != 0u) { paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, true, true>(a, sc, w); return; }
     }
-    paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, false>(a, sc, w);
+    paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, false, false>(a, sc, w);
 }
 
-template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT>
+template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT, bool SPHERES>
 PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, const RegenLds& w) {
     SceneRef sc = sc_staged;
     OneLight ol = OneLight{};
@@ -513,7 +521,7 @@ PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, cons
             dw.e4[2][lane] = make_float4(sdir.x, sdir.y, sdir.z, 0.0f);
             const uint32_t qsample = a.s_base + q.s_local;
             int qid; float qt;
-            scan_closest<kModeLds, false>(sc, q.o, q.d, a.t_min, kInf, qid, qt);
+            scan_closest<kModeLds, false, false, SPHERES>(sc, q.o, q.d, a.t_min, kInf, qid, qt);
             Vertex qv;
             vertex_begin<MIS, DIFFUSE, ONE_LIGHT>(sc, q, qa, qid, qt, qsample, qkx, qpy, qv, &ol);
             wave_vertices += valid;
@@ -613,9 +621,9 @@ PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, cons
             const bool shadow = pd.on && sc.n_lights > 0u;
             int id, sid = -1; float t;
             if (__ballot(shadow) != 0ull)
-                scan_closest2<kModeLds>(sc, p.o, shadow ? sdir : p.d, shadow ? smax : -1.0f, p.d, a.t_min, kInf, sid, id, t);
+                scan_closest2<kModeLds, SPHERES>(sc, p.o, shadow ? sdir : p.d, shadow ? smax : -1.0f, p.d, a.t_min, kInf, sid, id, t);
             else
-                scan_closest<kModeLds, false>(sc, p.o, p.d, a.t_min, kInf, id, t);
+                scan_closest<kModeLds, false, false, SPHERES>(sc, p.o, p.d, a.t_min, kInf, id, t);
             // ---- the previous vertex's NEE term, now that its visibility is known; a path that ended there retires
             const bool ended = pd.on && !alive;
             unpark();
@@ -631,7 +639,7 @@ PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, cons
             if (active && !alive && !pd.on) retire();
         } else {
             int id; float t;
-            scan_closest<kModeLds, false>(sc, p.o, p.d, a.t_min, kInf, id, t);
+            scan_closest<kModeLds, false, false, SPHERES>(sc, p.o, p.d, a.t_min, kInf, id, t);
             Vertex v;
             vertex_begin<MIS, DIFFUSE>(sc, p, active, id, t, sample, kx, py, v);
             alive = vertex_end<MIS, DIFFUSE, true>(sc, p, v, false, sample, kx, py, a.min_depth, a.max_depth);
@@ -646,7 +654,7 @@ PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, cons
             const bool shadow = pd.on && sc.n_lights > 0u;
             int sid = -1; float st;
             if (__ballot(shadow) != 0ull)
-                scan_closest<kModeLds, true>(sc, shadow ? p.o : parked_origin(), shadow ? sdir : parked_dir(), a.t_min, smax, sid, st);
+                scan_closest<kModeLds, true, false, SPHERES>(sc, shadow ? p.o : parked_origin(), shadow ? sdir : parked_dir(), a.t_min, smax, sid, st);
             const bool ended = pd.on && !alive;
             unpark();
             vertex_finish(p, pd, shadow && sid < 0);

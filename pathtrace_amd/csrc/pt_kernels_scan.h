@@ -218,6 +218,7 @@ struct SceneRef {
     const float4* scan_global;
     const Run* runs_global;
     uint32_t n_runs, n_lights;
+    uint32_t n_spheres;     // SceneView::spheres_only: the scan array is spheres 0 .. n_spheres - 1 and nothing else; 0: walk the runs
     BvhView bvh;
     uint32_t* stack;        // kModeBvh: LDS traversal stack, entry e of thread t at stack[e * kBlock + t]
 };
@@ -225,6 +226,7 @@ template <int MODE>
 PT_DEV SceneRef stage_scene(const SceneView& sc, float4* lds) {
     SceneRef r;
     r.n_runs = sc.n_runs; r.n_lights = sc.n_lights;
+    r.n_spheres = sc.spheres_only ? sc.n_objs : 0u;
     r.scan_global = sc.scan;
     r.runs_global = sc.runs;
     r.bvh = sc.bvh;
@@ -248,11 +250,18 @@ PT_DEV SceneRef stage_scene(const SceneView& sc, float4* lds) {
 // shrinking t_max.  kModeLds: the whole scan array already sits in LDS.  kModeTiled:
 // every run is streamed through one LDS tile; the loop is block-uniform (all
 // threads of the workgroup call this together, active or not).
-template <int MODE, bool ANY = false, bool PF = false>
+// SPHERES (kModeLds; the caller has seen sc.n_spheres != 0): the scan array is ONE run of spheres at offset 0, objects 0 .. n - 1
+// (SceneView::spheres_only, decided at upload).  The run's sphere code is entered directly with those constants: no loop over runs,
+// no run record out of LDS, no dispatch on its tag -- the same tests on the same records in the same order, so the same bits.
+template <int MODE, bool ANY = false, bool PF = false, bool SPHERES = false>
 PT_DEV void scan_closest(const SceneRef& sc, f3 o, f3 d, float t_min, float t_max, int& id_out, float& t_out) {
     constexpr bool SMALL = MODE == kModeLds;
     float closest = t_max;
     int id = -1;
+    if constexpr (SPHERES) {
+        static_assert(SMALL, "the whole scan array in LDS");
+        scan_run<false, ANY, PF>(sc.scan, SHAPE_SPHERE, sc.n_spheres, 0, o, d, t_min, closest, id);
+    } else
     for (uint32_t r = 0; r < sc.n_runs; ++r) {
         Run run = sc.runs[r];
         // the run record is the same in every lane: keep it (and the loop counters and object indices derived
@@ -285,6 +294,9 @@ PT_DEV void scan_closest(const SceneRef& sc, f3 o, f3 d, float t_min, float t_ma
 // scan_run<false, true> / scan_run<false, false>, in the same order, with the same NaN and tie rules; shared are the record read
 // and oc = o - centre (s = o - v0 for triangles): the same subtraction of the same operands, so identical bits.  The scheduler gets
 // two independent dependency chains per record.
+// SPHERES: as scan_closest's -- scan_run2's sphere code on sc.scan[0 .. n_spheres), objects numbered from 0, groups of four, then a
+// pair, then singles, each group behind a scalar branch on the count.  (Not a switch on the count into unrolled bodies: sixteen of
+// them are 136 joint tests of code for the sake of immediate offsets, and the count's branches are scalar and few.)
 PT_DEV void sphere_pre2(float4 s, f3 o, f3 da, f3 db, float& half_a, float& disc_a, float& half_b, float& disc_b) {
     const f3 oc = o - mk(s.x, s.y, s.z);
     half_a = dot(oc, da);
@@ -345,12 +357,14 @@ PT_DEV void scan_run2(const float4* __restrict__ p, uint32_t tag, uint32_t n, in
     }
 }
 // id_a >= 0: something lies on ray A inside [t_min, t_max_a]; (id_b, t_b): World::hit_scene of ray B, as scan_closest gives it
-template <int MODE>
+template <int MODE, bool SPHERES = false>
 PT_DEV void scan_closest2(const SceneRef& sc, f3 o, f3 da, float t_max_a, f3 db, float t_min, float t_max_b, int& id_a, int& id_b,
                           float& t_b) {
     static_assert(MODE == kModeLds, "the whole scan array in LDS");
     float closest = t_max_b;
     int ia = -1, ib = -1;
+    if constexpr (SPHERES) scan_run2(sc.scan, SHAPE_SPHERE, sc.n_spheres, 0, o, da, db, t_min, t_max_a, ia, closest, ib);
+    else
     for (uint32_t r = 0; r < sc.n_runs; ++r) {
         Run run = sc.runs[r];
         run.tag = __builtin_amdgcn_readfirstlane(run.tag); run.first_obj = __builtin_amdgcn_readfirstlane(run.first_obj);

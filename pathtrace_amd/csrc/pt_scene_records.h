@@ -24,6 +24,7 @@ struct Records {
     std::vector<double> pose;         // the f64 shape fields, 9 per object
     uint32_t scan_counts[3] = {0, 0, 0};   // spheres, single triangles, triangle pairs
     bool has_blob = false;            // n <= ptk::kSmallObjs
+    bool spheres_only = false;        // runs is one run of at most ptk::kSpheresOnlyMax spheres at offset 0, first object 0
     bool diffuse_only = true, no_mirror = true, no_oren_nayar = true;
     bool split_ok = false;            // a minority of the objects is Mirror
     bool auto_bvh = false;
