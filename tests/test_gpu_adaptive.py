@@ -8,8 +8,11 @@ take, and restate the stopping rule in numpy on the per-sample radiance pt_rende
 import numpy as np
 import pytest
 
+import launch_cover as lc
+
 pytestmark = pytest.mark.gpu
 LUM = (0.2126, 0.7152, 0.0722)
+BIG_RULE = (4, 4, 32, 0.08, 1e-3)     # spp_min, spp_step, spp_max, rel_tol, abs_floor of the 520 x 520 job: about half stops early
 
 
 def _with(prm, **kw):
@@ -95,18 +98,11 @@ def test_each_pixel_equals_pt_render_pixels_at_its_spp(pt, gpu_ctx):
     _pixel_parity(gpu_ctx, cam, prm, lin, rgba, spp)
 
 
-def test_the_rule_restated_in_numpy(pt, gpu_ctx):
-    """Replay S1 / S2 from the per-sample radiance at every check point in f64: the first check that passes is out_spp
-    and out_rel_err is se / max(mean, abs_floor) there."""
-    spp_min, step, spp_max, tol, floor = 16, 16, 200, 0.05, 1e-3
-    gpu_ctx.upload(pt.builtin_scene(1))
-    cam = pt.camera_new(width=200, height=200)
-    prm = pt.default_params(spp=spp_max)
-    _, _, spp, err = gpu_ctx.render_adaptive(cam, prm, spp_min=spp_min, spp_step=step, rel_tol=tol, abs_floor=floor)
-    rng = np.random.default_rng(1)
-    flat = rng.choice(cam.width * cam.height, size=64, replace=False)
-    xy = np.stack([flat % cam.width, flat // cam.width], axis=1)
-    _, _, smp = gpu_ctx.render_pixels(cam, prm, xy, want_samples=True)
+def _rule_restated(ctx, cam, prm, xy, spp, err, spp_min, step, spp_max, tol, floor):
+    """Replay S1 / S2 of the pixels xy from the per-sample radiance at every check point in f64: the first check that passes is
+    out_spp and out_rel_err is se / max(mean, abs_floor) there.  -> the pixels tested (a check within 1e-9 of its threshold
+    decides nothing)"""
+    _, _, smp = ctx.render_pixels(cam, prm, xy, want_samples=True)
     checks = list(range(spp_min, spp_max, step)) + [spp_max]
     tested = 0
     for i, (x, y) in enumerate(xy):
@@ -129,7 +125,20 @@ def test_the_rule_restated_in_numpy(pt, gpu_ctx):
         tested += 1
         assert spp[y, x] == stop, (x, y, spp[y, x], stop)
         assert err[y, x] == pytest.approx(rel, rel=1e-6, abs=0)
-    assert tested >= 48
+    return tested
+
+
+def test_the_rule_restated_in_numpy(pt, gpu_ctx):
+    """The stopping rule on 64 pixels of the 200 x 200 reference scene"""
+    spp_min, step, spp_max, tol, floor = 16, 16, 200, 0.05, 1e-3
+    gpu_ctx.upload(pt.builtin_scene(1))
+    cam = pt.camera_new(width=200, height=200)
+    prm = pt.default_params(spp=spp_max)
+    _, _, spp, err = gpu_ctx.render_adaptive(cam, prm, spp_min=spp_min, spp_step=step, rel_tol=tol, abs_floor=floor)
+    rng = np.random.default_rng(1)
+    flat = rng.choice(cam.width * cam.height, size=64, replace=False)
+    xy = np.stack([flat % cam.width, flat // cam.width], axis=1)
+    assert _rule_restated(gpu_ctx, cam, prm, xy, spp, err, spp_min, step, spp_max, tol, floor) >= 48
 
 
 @pytest.mark.parametrize("form", ["tiled", "bvh", "batches", "brdf", "brdf_tiled", "brdf_bvh", "oren_nayar", "oren_nayar_brdf"])
@@ -180,3 +189,50 @@ def test_counts_determinism_and_arguments(pt, gpu_ctx):
     with pytest.raises(pt._lib.PtError) as e:
         gpu_ctx.render_adaptive(cam, _with(prm, band_count=2), spp_min=4, spp_step=4, rel_tol=0.1)
     assert e.value.code == 1
+
+
+# ---- 520 x 520: 270 400 list slots, 265 workgroups of k_adaptive_select, of which 257 .. 264 add up more than 256 counts (a
+# second trip of the offset loop; tests/launch_cover.py)
+@pytest.mark.parametrize("exact", [0, 1])
+def test_select_past_256_workgroups_keeps_every_pixel(pt, gpu_ctx, exact):
+    """rel_tol = 0: the image-form select of pass 1 and the list-form select of pass 2 keep all 270 400 pixels, and the film
+    is the uniform 6-spp one bit for bit"""
+    W, H = lc.ADAPTIVE_SIZE
+    assert lc.select_trips(W * H).max() == 2
+    gpu_ctx.upload(pt.builtin_scene(2))
+    cam = pt.camera_new(width=W, height=H)
+    prm = pt.default_params(spp=6, exact_math=exact)
+    lin, rgba, spp, err = gpu_ctx.render_adaptive(cam, prm, spp_min=2, spp_step=2, rel_tol=0.0)
+    assert (spp == 6).all(), np.argwhere(spp != 6)[:8]
+    ulin, urgba = _uniform(gpu_ctx, cam, prm)
+    assert np.array_equal(lin, ulin), np.argwhere((lin != ulin).any(-1))[:8]
+    assert np.array_equal(rgba, urgba)
+    assert np.isfinite(err).all() and (err >= 0).all()
+
+
+def test_select_past_256_workgroups_with_a_real_tolerance(pt, gpu_ctx):
+    """A tolerance at which part of the image stops at every check: the survivors of the workgroups before the 257th are counted
+    by two trips.  The rule restated on 96 pixels, half of them in the rows whose slots lie in those workgroups; 4096 random
+    pixels and every pixel of the rows y >= 505 against pt_render_pixels at their own spp."""
+    W, H = lc.ADAPTIVE_SIZE
+    spp_min, step, spp_max, tol, floor = BIG_RULE
+    gpu_ctx.upload(pt.builtin_scene(1))
+    cam = pt.camera_new(width=W, height=H)
+    prm = pt.default_params(spp=spp_max)
+    lin, rgba, spp, err = gpu_ctx.render_adaptive(cam, prm, spp_min=spp_min, spp_step=step, rel_tol=tol, abs_floor=floor)
+    early = float((spp < spp_max).mean())
+    print(f"{W}x{H}: {early:.3f} of the pixels stop before {spp_max} spp; spp values {np.unique(spp)}")
+    assert 0.25 <= early <= 0.75                                  # a condition on the input, not on the kernel
+    assert int((spp[505:] < spp_max).sum()) > 0 and int((spp[505:] == spp_max).sum()) > 0
+    rng = np.random.default_rng(3)
+    first = lc.select_first_row_of_workgroup(257, W)
+    flat = np.concatenate([rng.choice(first * W, size=48, replace=False), first * W + rng.choice((H - first) * W, size=48, replace=False)])
+    xy = np.stack([flat % W, flat // W], axis=1)
+    assert _rule_restated(gpu_ctx, cam, prm, xy, spp, err, spp_min, step, spp_max, tol, floor) >= 72
+    flat = np.concatenate([rng.choice(505 * W, size=4096, replace=False), np.arange(505 * W, H * W)])
+    ys, xs = flat // W, flat % W
+    for n in np.unique(spp[ys, xs]):
+        sel = spp[ys, xs] == n
+        plin, prgba, _ = gpu_ctx.render_pixels(cam, _with(prm, spp=int(n)), np.stack([xs[sel], ys[sel]], axis=1))
+        assert np.array_equal(plin, lin[ys[sel], xs[sel]]), f"spp {n}: linear film differs from pt_render_pixels"
+        assert np.array_equal(prgba, rgba[ys[sel], xs[sel]]), f"spp {n}: RGBA8 differs from pt_render_pixels"

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import launch_cover as lc
 import tonemap_ref as tr
 
 pytestmark = pytest.mark.gpu
@@ -43,6 +44,67 @@ def test_histogram_is_exact_and_cleared(pt, gpu_ctx, W, H):
     assert np.array_equal(got, ref), np.argwhere(got != ref)[:8]
     assert int(got.sum()) == W * H
     assert np.array_equal(gpu_ctx.film_histogram(film), ref)          # the words were zeroed in front of the second pass
+
+
+def _large_shapes():
+    """the two film sizes past the launch boundaries of k_film_histogram on this device (tests/launch_cover.py)"""
+    import torch
+    return lc.hist_sizes(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_histogram_past_the_grid_cap(pt, gpu_ctx, which):
+    """More pixels than the capped grid holds in one slot (which = 0: batch slots 1 .. 3 in use) and than it holds in one trip
+    (which = 1: a second grid-stride trip, a few workgroups long, the last of them partly filled)"""
+    import torch
+    n_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    W, H = _large_shapes()[which]
+    reach = lc.hist_reach(W * H, n_cus)
+    assert reach["grid"] == n_cus and (reach["max_slot"] >= 1 and reach["trips"] == 1 if which == 0 else
+                                       reach["max_slot"] == 3 and reach["trips"] == 2 and reach["last_trip_fill"] < 1.0)
+    film = tr.crafted_film(W, H, 11 + which)
+    ref = tr.histogram(film)
+    assert ref.sum() == W * H
+    for _ in range(2):
+        got = gpu_ctx.film_histogram(film)
+        assert np.array_equal(got, ref), np.argwhere(got != ref)[:8]
+
+
+def test_auto_exposure_past_the_grid_cap(pt, ctx):
+    """One auto-mode frame of the larger film: the stored histogram and the metered exposure, then the two planes on the curve
+    film of that size at the bars of test_curves_and_transfers"""
+    W, H = _large_shapes()[1]
+    film = tr.crafted_film(W, H, 12)
+    over = dict(log2_min=-40.0, log2_max=40.0)                 # (the crafted film's median lies far outside the default range)
+    ctx.exposure_reset()
+    ctx.tonemap(film, **over)
+    log2E, hist = ctx.exposure()
+    ref = tr.histogram(film)
+    assert np.array_equal(hist, ref), np.argwhere(hist != ref)[:8]
+    want = tr.target(ref, tr.params(**over))
+    print(f"{W}x{H} crafted: log2E {log2E:.15f} restatement {want:.15f} diff {abs(log2E - want):.2e}")
+    assert abs(log2E - want) <= 1e-12
+    for seed, curve, transfer in ((0, tr.ACES, tr.SQRT), (1, tr.REINHARD, tr.SRGB)):
+        film = tr.curve_film(W, H, seed)
+        over = tr.random_params(seed) if seed else {}
+        p = tr.params(curve=curve, transfer=transfer, **over)
+        ctx.exposure_reset()
+        got8, gotf = ctx.tonemap(film, curve=curve, transfer=transfer, **over)
+        log2E, hist = ctx.exposure()
+        ref = tr.histogram(film)
+        assert np.array_equal(hist, ref) and abs(log2E - tr.target(ref, p)) <= 1e-12
+        _, E, valid = ctx.debug_exposure_state()
+        assert valid == 1
+        y = tr.curve(film, E, p)
+        ref8, safe = tr.rgba8(y, p)
+        assert (~safe).mean() <= 0.02
+        err = _max_rel(gotf.astype(np.float64), y)
+        print(f"{W}x{H} seed {seed}: max rel err of the float plane {err:.2e}")
+        assert err <= 1e-4, (curve, transfer, err)
+        d = np.abs(got8.astype(int) - ref8.astype(int)).max(-1)
+        assert (d[safe] == 0).all() and (d <= 1).all(), (curve, transfer, int(d.max()), int((d[safe] != 0).sum()))
+        assert (got8[..., 3] == 255).all()
+        assert gotf.reshape(-1, 3)[5, 1] == 0.0 and got8.reshape(-1, 4)[5, 1] == 0
 
 
 def test_histogram_of_the_real_films(pt, gpu_ctx):
