@@ -472,6 +472,10 @@ int pt_render_features_device(PtContext* ctx, const PtCamera* cam, const PtRende
  *                q != p:  w = k max(0, n_p.n_q)^sigma_n exp(-|L_p - L_q| / (sigma_l g_p + 1e-10)
  *                                                    -|d_p - d_q| / (sigma_d h max(d_p, 1e-3) + 1e-10)),
  *                         w = 0 when emitter_p > 0 or emitter_q > 0;  the centre tap: w = k;
+ *                         w = 0 when n_p.n_q <= 0, for every sigma_n, 0 included (0^0 is not consulted: orthogonal
+ *                         and opposite normals, and every miss pixel, whose normal is 0, never mix);
+ *                         a tap with w = 0 by one of these cases (outside the image, an emitter, n_p.n_q <= 0) is not
+ *                         read: nothing of pixel q, a NaN or an infinity included, reaches pixel p through it;
  *                u' = sum w u_q / sum w,  var' = sum w^2 var_q / (sum w)^2
  *   remodulate   c' = u a; the RGBA8 plane is c' through the sqrt-gamma / clamp / `as u8` steps of every render.
  * iterations = 0 gives u a of the input.  The device computes in f32 (the sums as u_p + sum w (u_q - u_p) / sum w).

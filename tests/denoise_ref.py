@@ -4,7 +4,8 @@
 features_f32 rebuilds pt_render_features_device's records from the f32 oracle (orc.philox, orc.u01, orc.camera_rays,
 orc.hit_scene) with the device's exact-mode arithmetic: every record in f32, summed in sample order, divided by n.
 sample_records gives the records of ONE sample in any oracle precision (the fast-mode bars are per sample).
-denoise is the filter in f64, stated as the header states it."""
+denoise is the filter in f64, stated as the header states it: a tap the rule gives weight 0 by a case (outside the image, an
+emitter at either end, n_p.n_q <= 0) is a selection, not a product, so nothing of that tap reaches the sum."""
 import numpy as np
 
 LW = np.array([0.2126, 0.7152, 0.0722])
@@ -64,73 +65,109 @@ def _shift(img, dy, dx):
     return out, m
 
 
-def demodulate(c, feat):
-    a = np.maximum(np.asarray(feat, np.float64)[..., 0:3], 1e-3)
-    return np.asarray(c, np.float64) / a, a
+def demodulate(c, feat, dtype=np.float64):
+    a = np.maximum(np.asarray(feat, dtype)[..., 0:3], dtype(1e-3))
+    with np.errstate(all="ignore"):
+        return np.asarray(c, dtype) / a, a
+
+
+def luminance(u):
+    """L(u), the three products added left to right, in u's type."""
+    t = u.dtype.type
+    return t(LW[0]) * u[..., 0] + t(LW[1]) * u[..., 1] + t(LW[2]) * u[..., 2]
 
 
 def initial_variance(u):
-    """3x3 population variance of L(u), taps outside the image skipped."""
-    L = u @ LW
-    s1 = np.zeros(L.shape)
-    cnt = np.zeros(L.shape)
-    taps = [_shift(L, dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
-    for v, m in taps:
-        s1 += v * m
-        cnt += m
-    mu = s1 / cnt
-    s2 = np.zeros(L.shape)
-    for v, m in taps:
-        s2 += (v - mu) ** 2 * m
-    return s2 / cnt
+    """3x3 population variance of L(u), taps outside the image skipped; in u's type."""
+    t = u.dtype.type
+    with np.errstate(all="ignore"):
+        L = luminance(u)
+        s1 = np.zeros(L.shape, t)
+        cnt = np.zeros(L.shape, t)
+        taps = [_shift(L, dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
+        for v, m in taps:
+            s1 += np.where(m, v, t(0))
+            cnt += m
+        mu = s1 / cnt
+        s2 = np.zeros(L.shape, t)
+        for v, m in taps:
+            s2 += np.where(m, (v - mu) ** 2, t(0))
+        return s2 / cnt
 
 
-def atrous_step(u, var, feat, h, sigma_l, sigma_n, sigma_d):
-    """One iteration with step h -> (u', var')."""
-    feat = np.asarray(feat, np.float64)
-    em, nrm, dep = feat[..., 3], feat[..., 4:7], feat[..., 7]
-    g = np.zeros(var.shape)
-    gs = np.zeros(var.shape)
-    for dy in (-1, 0, 1):
-        for dx in (-1, 0, 1):
-            k = (0.5 if dy == 0 else 0.25) * (0.5 if dx == 0 else 0.25)
-            v, m = _shift(var, dy, dx)
-            g += k * v * m
-            gs += k * m
-    sig = np.sqrt(g / gs)
-    L = u @ LW
-    num = np.zeros_like(u)
-    den = np.zeros(var.shape)
-    vnum = np.zeros(var.shape)
-    for j in range(5):
-        for i in range(5):
-            dy, dx = (j - 2) * h, (i - 2) * h
-            k = B3[j] * B3[i]
-            uq, m = _shift(u, dy, dx)
-            vq, _ = _shift(var, dy, dx)
-            if dy == 0 and dx == 0:
-                w = np.full(var.shape, k)
-            else:
-                eq, _ = _shift(em, dy, dx)
-                nq, _ = _shift(nrm, dy, dx)
+def excluded(feat, dy, dx):
+    """The taps q = p + (dy, dx) != p of weight 0 by one of the rule's cases: q outside the image, emitter_p > 0 or
+    emitter_q > 0, or not n_p.n_q > 0 (orthogonal or opposite normals, every miss pixel: whatever sigma_n is).  Such a
+    tap is not read: nothing of pixel q, a NaN or an infinity included, reaches pixel p through it."""
+    em, nrm = feat[..., 3], feat[..., 4:7]
+    eq, m = _shift(em, dy, dx)
+    nq, _ = _shift(nrm, dy, dx)
+    with np.errstate(all="ignore"):
+        nd = nrm[..., 0] * nq[..., 0] + nrm[..., 1] * nq[..., 1] + nrm[..., 2] * nq[..., 2]
+        return ~m | (em > 0) | (eq > 0) | ~(nd > 0), nd
+
+
+def atrous_step(u, var, feat, h, sigma_l, sigma_n, sigma_d, dtype=np.float64):
+    """One iteration with step h -> (u', var'), every array and constant in dtype, the taps added in row order."""
+    t = dtype
+    u, var, feat = np.asarray(u, t), np.asarray(var, t), np.asarray(feat, t)
+    dep = feat[..., 7]
+    b3 = B3.astype(t)
+    with np.errstate(all="ignore"):
+        g = np.zeros(var.shape, t)
+        gs = np.zeros(var.shape, t)
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                k = t(0.5 if dy == 0 else 0.25) * t(0.5 if dx == 0 else 0.25)
+                v, m = _shift(var, dy, dx)
+                g += np.where(m, k * v, t(0))
+                gs += np.where(m, k, t(0))
+        sig = np.sqrt(g / gs)
+        L = luminance(u)
+        stop_l = t(sigma_l) * sig + t(1e-10)
+        stop_d = t(sigma_d) * t(h) * np.maximum(dep, t(1e-3)) + t(1e-10)
+        num = np.zeros_like(u)
+        den = np.zeros(var.shape, t)
+        vnum = np.zeros(var.shape, t)
+        for j in range(5):
+            for i in range(5):
+                dy, dx = (j - 2) * h, (i - 2) * h
+                k = b3[j] * b3[i]
+                uq, _ = _shift(u, dy, dx)
+                vq, _ = _shift(var, dy, dx)
+                if dy == 0 and dx == 0:
+                    num += k * uq
+                    den += k
+                    vnum += k * k * vq
+                    continue
+                out, nd = excluded(feat, dy, dx)
                 dq, _ = _shift(dep, dy, dx)
-                wn = np.maximum(0.0, (nrm * nq).sum(-1)) ** sigma_n
-                el = np.abs(L - uq @ LW) / (sigma_l * sig + 1e-10)
-                ed = np.abs(dep - dq) / (sigma_d * h * np.maximum(dep, 1e-3) + 1e-10)
-                w = k * wn * np.exp(-el - ed) * m * ((em <= 0) & (eq <= 0))
-            num += w[..., None] * uq
-            den += w
-            vnum += w * w * vq
-    return num / den[..., None], vnum / (den * den)
+                wn = np.maximum(t(0), nd) ** t(sigma_n)
+                el = np.abs(L - luminance(uq)) / stop_l
+                ed = np.abs(dep - dq) / stop_d
+                w = k * wn * np.exp(-el - ed)
+                num += np.where(out[..., None], t(0), w[..., None] * uq)
+                den += np.where(out, t(0), w)
+                vnum += np.where(out, t(0), w * w * vq)
+        res = num / den[..., None], vnum / (den * den)
+    assert res[0].dtype == t and res[1].dtype == t
+    return res
 
 
-def denoise(c, feat, iterations=5, sigma_l=4.0, sigma_n=128.0, sigma_d=0.025):
-    """The filter of pt_denoise_device in f64 -> linear f64[H,W,3]."""
-    u, a = demodulate(c, feat)
-    var = initial_variance(u)
+def denoise(c, feat, iterations=5, sigma_l=4.0, sigma_n=128.0, sigma_d=0.025, dtype=np.float64, var=None):
+    """The filter of pt_denoise_device -> linear dtype[H,W,3]: in f64 the rule as the header states it; dtype=np.float32 runs
+    the same text with every array and constant in f32 (no model of the device's instructions: a measure of what f32 costs
+    this rule on a given input).  var: pt_denoise_var_device's plane, an entry that is finite and >= 0 replaces the 3x3 variance."""
+    u, a = demodulate(c, feat, dtype)
+    v = initial_variance(u)
+    if var is not None:
+        with np.errstate(invalid="ignore"):
+            given = np.isfinite(var) & (np.asarray(var) >= 0)
+        v = np.where(given, np.asarray(var, dtype), v)
     for i in range(iterations):
-        u, var = atrous_step(u, var, feat, 1 << i, sigma_l, sigma_n, sigma_d)
-    return u * a
+        u, v = atrous_step(u, v, feat, 1 << i, sigma_l, sigma_n, sigma_d, dtype)
+    with np.errstate(all="ignore"):
+        return u * a
 
 
 def rgba8(lin):
