@@ -246,6 +246,10 @@ int pt_debug_scan_layout(PtContext* ctx, uint32_t* n_spheres, uint32_t* n_triang
  * it without the run records), else 0.  ctx != NULL: the flag the uploaded scene carries (objs, n unused).  ctx == NULL: what an
  * upload of objs[0 .. n) would record; host only, no device.                                                                    */
 int pt_debug_spheres_only(PtContext* ctx, const PtObject* objs, uint32_t n, uint32_t* out);
+/* Debug, same two forms: *out = 1 when every object is Lambertian or Emissive with a non-zero emission (a path then goes on from
+ * Lambertian surfaces only: k_paths_regen<MIS, diffuse> shades a one-light scene of such spheres without the other materials'
+ * arms), else 0 -- a black Emissive, an OrenNayar or a Mirror object clears it.  No object: 1.                                   */
+int pt_debug_lambert_surfaces(PtContext* ctx, const PtObject* objs, uint32_t n, uint32_t* out);
 
 /* Same render with HOST output buffers (blocking): device staging is owned by the
  * context, results are copied back over PCIe.  out_rgba8 may be NULL.          */

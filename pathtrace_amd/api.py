@@ -534,6 +534,12 @@ class Context:
         check(lib().pt_debug_spheres_only(self._h, None, 0, C.byref(v)))
         return bool(v.value)
 
+    def lambert_surfaces(self):
+        """-> whether every object of the uploaded scene is Lambertian or Emissive with a non-zero emission (pt_debug_lambert_surfaces)"""
+        v = C.c_uint32(0)
+        check(lib().pt_debug_lambert_surfaces(self._h, None, 0, C.byref(v)))
+        return bool(v.value)
+
     def render_packed_into(self, cam, params, packed_ptr):
         """pt_render_device_packed: the tile as 16 B per pixel (linear RGB + RGBA8), the send-buffer form of the film gather."""
         check(lib().pt_render_device_packed(self._h, C.byref(cam), C.byref(params), C.c_void_p(packed_ptr)))
@@ -1344,6 +1350,14 @@ def scene_spheres_only(objs):
     without a context: host only)."""
     v = C.c_uint32(0)
     check(lib().pt_debug_spheres_only(None, objs, len(objs), C.byref(v)))
+    return bool(v.value)
+
+
+def scene_lambert_surfaces(objs):
+    """-> whether an upload of objs would record that every object is Lambertian or Emissive with a non-zero emission
+    (pt_debug_lambert_surfaces without a context: host only)."""
+    v = C.c_uint32(0)
+    check(lib().pt_debug_lambert_surfaces(None, objs, len(objs), C.byref(v)))
     return bool(v.value)
 
 

@@ -188,18 +188,27 @@ int pt_debug_scan_layout(PtContext* c, uint32_t* n_spheres, uint32_t* n_triangle
 // Debug: is the scan array nothing but one run of at most kSpheresOnlyMax spheres (SceneView::spheres_only)?  With a context: the
 // flag the uploaded scene carries to the kernels (objs, n unused).  Without one: what an upload of objs[0 .. n) would record, on the
 // host alone (ptscene::build).
-int pt_debug_spheres_only(PtContext* c, const PtObject* objs, uint32_t n, uint32_t* out) {
-    if (!out) return fail(PT_ERR_INVALID_ARG, "pt_debug_spheres_only: null argument");
+static int debug_scene_flag(const char* who, PtContext* c, const PtObject* objs, uint32_t n, uint32_t* out,
+                            uint32_t ptk::SceneView::*of_view, bool ptscene::Records::*of_records) {
+    if (!out) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (c) {
         if (int rc = check_scene(c, nullptr)) return rc;
-        *out = c->view.spheres_only;
+        *out = c->view.*of_view;
         return PT_OK;
     }
-    if (!objs && n) return fail(PT_ERR_INVALID_ARG, "pt_debug_spheres_only: null argument");
+    if (!objs && n) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     ptscene::Records rec;
     if (int rc = ptscene::build(objs, n, &rec)) return rc;
-    *out = rec.spheres_only ? 1u : 0u;
+    *out = rec.*of_records ? 1u : 0u;
     return PT_OK;
+}
+int pt_debug_spheres_only(PtContext* c, const PtObject* objs, uint32_t n, uint32_t* out) {
+    return debug_scene_flag("pt_debug_spheres_only", c, objs, n, out, &ptk::SceneView::spheres_only, &ptscene::Records::spheres_only);
+}
+// Debug, in the same two forms: can a path go on from Lambertian surfaces only -- every object Lambertian, or Emissive with a
+// non-zero emission (SceneView::lambert_surfaces)?  No object: yes.
+int pt_debug_lambert_surfaces(PtContext* c, const PtObject* objs, uint32_t n, uint32_t* out) {
+    return debug_scene_flag("pt_debug_lambert_surfaces", c, objs, n, out, &ptk::SceneView::lambert_surfaces, &ptscene::Records::lambert_surfaces);
 }
 
 // Debug: the 16 raw device-side statistics words as last collected (pt_sync / pt_get_stats).  [0] shadow rays [1] vertices

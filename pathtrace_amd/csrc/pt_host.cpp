@@ -81,6 +81,9 @@ int build(const PtObject* objs, uint32_t n, Records* out) {
         mat[2 * (size_t)i] = make_float4(fb, p[0], p[1], p[2]);
         mat[2 * (size_t)i + 1] = make_float4(p[3], p[4], p[5], 0.f);
         if (emits) lights.push_back(i);
+        // the surfaces a path can go on from: a hit on an Emissive that emits ends the path, so only a black one (the path goes on with
+        // f = 0, pdf = 1, wo = n), OrenNayar or Mirror is a surface other than Lambertian
+        if (o.mat_tag != PT_MAT_LAMBERT && !emits) r.lambert_surfaces = false;
     }
     // Scan array: runs of same-kind primitives in object order (the order decides closest-hit ties, world.rs:281-287).
     // Two consecutive triangles whose records carry the SAME vertex v0 and the SAME plane normal bit for bit -- the two

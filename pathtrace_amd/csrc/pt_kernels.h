@@ -47,6 +47,7 @@ struct SceneView {
     uint32_t scan_f4;        // float4 count of `scan`
     uint32_t n_runs, n_objs, n_lights;
     uint32_t spheres_only;   // the scan array is ONE run of n_objs <= kSpheresOnlyMax spheres at offset 0, first object 0 (decided at upload: ptscene::build)
+    uint32_t lambert_surfaces;   // every material is Lambertian, or Emissive with a non-zero emission (a hit there ends the path): decided at upload too
     uint32_t diffuse_only;   // every material is Lambertian or emissive: kernels without the GGX / OrenNayar code
     uint32_t no_mirror;      // no Mirror surface (k_paths_regen without the GGX code also for scenes with OrenNayar surfaces)
     uint32_t no_oren_nayar;  // no OrenNayar surface (k_paths_regen_split: its plain iterations are then the diffuse-only code)

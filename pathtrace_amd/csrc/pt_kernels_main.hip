@@ -20,7 +20,8 @@
 //   k_paths_regen<MIS, MATS>  level-0 launch of a batch of > 2^17 paths over a scene in LDS: a path stays in its lane's registers,
 //                             a lane whose path ends takes the batch's next one (chunk counters); compiled per material set.
 //                             A vertex's visibility ray and the next path ray go through the scene in one pass (scan_closest2);
-//                             a one-light scene of at most 16 spheres is scanned without the run records (SPHERES).
+//                             a one-light scene of at most 16 Lambertian spheres is scanned without the run records (SPHERES) and
+//                             shaded by a vertex stage compiled for sphere hits and Lambertian surfaces (LAMBERT).
 //   k_paths_regen_split<..>   (pt_kernels_split.hip) the same for scenes with a few Mirror objects (the reference's own): a wave's Mirror vertices are
 //                             set aside on a per-wave stack and shaded 64 at a time.
 //   k_paths_bvh<MIS, OVF>     (pt_kernels_bvh.hip) the queue form for PtRenderParams.accel = 1: hit_scene by traversal of a 4-wide BVH, each pass cut
@@ -329,10 +330,16 @@ constexpr uint32_t kRegenBlock = PT_REGEN_BLOCK;
 // SPHERES (chosen with ONE_LIGHT, by the same wave-uniform branch): the scan array is one run of at most kSpheresOnlyMax spheres at
 // offset 0, first object 0 (SceneView::spheres_only, decided at upload).  The scans enter the run's sphere code with those constants
 // and the count (scan_closest / scan_closest2 <.., SPHERES>, pt_kernels_scan.h): no loop over runs, no run record out of LDS and its
-// four readfirstlane, no dispatch on the tag, no triangle code in the loop; same tests, same order, same bits.  The kernel holds TWO
-// loops: <ONE_LIGHT, SPHERES> for one-light scenes of spheres only (C2, C3, C5) and the generic per-lane one for every other scene
-// -- a third copy (one light with triangles, as before this form existed) spills two to five VGPRs at 80, so such scenes take the
-// generic loop again (docs/EXPERIMENTS.md, "A spheres-only scene ...").
+// four readfirstlane, no dispatch on the tag, no triangle code in the loop; same tests, same order, same bits.  vertex_begin finishes
+// every hit as a sphere's, without the shape tag of the material word.
+// LAMBERT (chosen with the two above, by the same branch): every object is Lambertian or an Emissive that emits
+// (SceneView::lambert_surfaces, decided at upload), so a path that goes on past a vertex stands on a Lambertian surface there.
+// vertex_end re-reads the colour alone and enters the BSDF code with the tag a constant: no Emissive arms, no select of the sampled
+// direction, no second normalisation, no eta (pt_kernels_vertex.h).  The kernel holds TWO loops: <ONE_LIGHT, SPHERES, LAMBERT> for
+// one-light scenes of Lambertian spheres only (C2, C3, C5) and the generic per-lane one for every other scene -- a third copy (one
+// light with triangles, as before the spheres form existed) spills two to five VGPRs at 80, so such scenes take the generic loop
+// again, and so does a spheres-only one-light scene with a black Emissive object (docs/EXPERIMENTS.md, "A spheres-only scene ...",
+// "Sphere hits and Lambertian surfaces ...").
 struct RegenLds {            // one wave's parts of the workgroup's LDS
     float4* pool_d;          // !DENSE0: the ring of camera rays
     uint32_t* pool_s;
@@ -341,7 +348,7 @@ struct RegenLds {            // one wave's parts of the workgroup's LDS
     DenseWave* dw;           // DENSE0: ring entries and parked terms
     WgTotals* totals;
 };
-template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT, bool SPHERES>
+template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT, bool SPHERES, bool LAMBERT>
 PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc, const RegenLds& w);
 
 template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0>
@@ -381,12 +388,12 @@ PT_DEV void paths_regen_body(const BounceArgs& a) {
     w.dw = &s_dense[DENSE0 ? wib : 0u];
     w.totals = &s_totals;
     if constexpr (DENSE0) {
-        if (sc.n_lights == 1u && sc.n_spheres != 0u) { paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, true, true>(a, sc, w); return; }
+        if (sc.n_lights == 1u && sc.n_spheres != 0u && sc.lambert_surfaces != 0u) { paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, true, true, true>(a, sc, w); return; }
     }
-    paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, false, false>(a, sc, w);
+    paths_regen_run<MIS, DIFFUSE, LIST, DENSE0, false, false, false>(a, sc, w);
 }
 
-template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT, bool SPHERES>
+template <bool MIS, int DIFFUSE, bool LIST, bool DENSE0, bool ONE_LIGHT, bool SPHERES, bool LAMBERT>
 PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, const RegenLds& w) {
     SceneRef sc = sc_staged;
     OneLight ol = OneLight{};
@@ -523,12 +530,12 @@ PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, cons
             int qid; float qt;
             scan_closest<kModeLds, false, false, SPHERES>(sc, q.o, q.d, a.t_min, kInf, qid, qt);
             Vertex qv;
-            vertex_begin<MIS, DIFFUSE, ONE_LIGHT>(sc, q, qa, qid, qt, qsample, qkx, qpy, qv, &ol);
+            vertex_begin<MIS, DIFFUSE, ONE_LIGHT, SPHERES>(sc, q, qa, qid, qt, qsample, qkx, qpy, qv, &ol);
             wave_vertices += valid;
             wave_shadow += (uint32_t)__popcll(__ballot(qv.need_shadow));
             Pending qpd;
             qpd.on = false; qpd.beta = mk(0.f, 0.f, 0.f); qpd.direct = mk(0.f, 0.f, 0.f);
-            const bool qalive = vertex_end<MIS, DIFFUSE, true, true, ONE_LIGHT>(sc, q, qv, false, qsample, qkx, qpy, a.min_depth, a.max_depth, &qpd, &ol);
+            const bool qalive = vertex_end<MIS, DIFFUSE, true, true, ONE_LIGHT, LAMBERT>(sc, q, qv, false, qsample, qkx, qpy, a.min_depth, a.max_depth, &qpd, &ol);
             // miss, emitter, roulette: the sample is finished (depth 0: dmax stays); it never was in the ring, so it counts here
             const bool qdone = qa && !qalive && !qpd.on;
             if (qdone) a.lsamp[q.s_local * a.np + q.yl * W + q.px] = Rgb{q.L.x, q.L.y, q.L.z};
@@ -631,9 +638,9 @@ PT_DEV void paths_regen_run(const BounceArgs& a, const SceneRef& sc_staged, cons
             if (ended) retire();
             // ---- the new vertex up to the point where its own visibility is needed
             Vertex v;
-            vertex_begin<MIS, DIFFUSE, ONE_LIGHT>(sc, p, active, id, t, sample, kx, py, v, &ol);
+            vertex_begin<MIS, DIFFUSE, ONE_LIGHT, SPHERES>(sc, p, active, id, t, sample, kx, py, v, &ol);
             wave_shadow += (uint32_t)__popcll(__ballot(v.need_shadow));
-            alive = vertex_end<MIS, DIFFUSE, true, true, ONE_LIGHT>(sc, p, v, false, sample, kx, py, a.min_depth, a.max_depth, &pd, &ol);
+            alive = vertex_end<MIS, DIFFUSE, true, true, ONE_LIGHT, LAMBERT>(sc, p, v, false, sample, kx, py, a.min_depth, a.max_depth, &pd, &ol);
             sdir = v.light_dir; smax = v.distance - a.t_min;
             park();
             if (active && !alive && !pd.on) retire();

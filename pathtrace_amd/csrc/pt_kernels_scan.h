@@ -219,6 +219,7 @@ struct SceneRef {
     const Run* runs_global;
     uint32_t n_runs, n_lights;
     uint32_t n_spheres;     // SceneView::spheres_only: the scan array is spheres 0 .. n_spheres - 1 and nothing else; 0: walk the runs
+    uint32_t lambert_surfaces;   // SceneView::lambert_surfaces: a path that goes on past a vertex stands on a Lambertian surface there
     BvhView bvh;
     uint32_t* stack;        // kModeBvh: LDS traversal stack, entry e of thread t at stack[e * kBlock + t]
 };
@@ -227,6 +228,7 @@ PT_DEV SceneRef stage_scene(const SceneView& sc, float4* lds) {
     SceneRef r;
     r.n_runs = sc.n_runs; r.n_lights = sc.n_lights;
     r.n_spheres = sc.spheres_only ? sc.n_objs : 0u;
+    r.lambert_surfaces = sc.lambert_surfaces;
     r.scan_global = sc.scan;
     r.runs_global = sc.runs;
     r.bvh = sc.bvh;

@@ -189,7 +189,8 @@ PT_DEV void sample_light_point(const SceneRef& sc, f3 from, uint32_t w_index, ui
 // OrenNayar code is then compiled out of the kernel (same results; smaller code, no spills at 6 waves/SIMD: C2 +2 %).
 // (kx, py) = the pixel's RNG key (main.rs:51); it is the path's film position except in pixel-list renders.
 // ONE: the scene has exactly one light and `ol` holds it (OneLight above).
-template <bool MIS, int DIFFUSE, bool ONE = false>
+// SPHERES: every object is a sphere (SceneView::spheres_only): the hit record is finished by the sphere code, no shape tag is looked at.
+template <bool MIS, int DIFFUSE, bool ONE = false, bool SPHERES = false>
 PT_DEV void vertex_begin(const SceneRef& sc, PathState& p, bool active, int id, float t, uint32_t sample, uint32_t kx,
                          uint32_t py, Vertex& v, const OneLight* ol = nullptr) {
     v.alive = active && id >= 0;
@@ -201,7 +202,8 @@ PT_DEV void vertex_begin(const SceneRef& sc, PathState& p, bool active, int id, 
     if (v.alive) {
         v.m = load_mat(sc.mat, id);
         assume_mats<DIFFUSE>(v.m.tag);
-        v.hit = finish_hit(sc.shape, id, v.m.shape_tag, p.o, p.d, t);
+        if constexpr (SPHERES) v.hit = finish_hit(sc.shape, id, SHAPE_SPHERE, p.o, p.d, t);
+        else v.hit = finish_hit(sc.shape, id, v.m.shape_tag, p.o, p.d, t);
         if (v.m.emits) {
             v.hit_emitter = true;
             if (MIS && p.depth != 0u) {
@@ -262,17 +264,29 @@ PT_DEV void vertex_finish(PathState& p, Pending& pd, bool visible) {
     }
 }
 // ONE: the light's emission is ol.emission; nothing of the light is read again.
-template <bool MIS, int DIFFUSE, bool REMAT, bool DEFER = false, bool ONE = false>
+// LAMBERT (SceneView::lambert_surfaces, decided at upload; REMAT only): every object is Lambertian or an Emissive that emits.  A hit
+// on one that emits ends the path in vertex_begin, so a lane with need_shadow or alive set stands on a Lambertian surface: the re-read
+// fetches the object's colour and nothing else (an emitter's colour for its credit: the same three words), bsdf_pdf and
+// bsdf_pdf_sample are entered with the tag a constant, the sampled direction is the cosine sampler's as it is (normalised there), and
+// eta_here is 1: pt_rcp(1) is exactly 1 in both arithmetic modes, Lambert's bsdf_pdf reads no eta, and p.eta_in, 1 when the path
+// started, is never written.  What remains has the operands and the order it had.
+template <bool MIS, int DIFFUSE, bool REMAT, bool DEFER = false, bool ONE = false, bool LAMBERT = false>
 PT_DEV bool vertex_end(const SceneRef& sc, PathState& p, const Vertex& vin, bool visible, uint32_t sample, uint32_t kx,
                        uint32_t py, uint32_t min_depth, uint32_t max_depth, Pending* pd = nullptr, const OneLight* ol = nullptr) {
     const uint32_t n_lights = ONE ? 1u : sc.n_lights;
     Vertex v = vin;
     if (REMAT) {
         asm volatile("" ::: "memory");          // a real re-read, not the values of vertex_begin kept alive
-        v.m = load_mat(sc.mat, vin.obj);
+        if constexpr (LAMBERT) {
+            const float4 m0 = sc.mat[2 * vin.obj];
+            v.m.tag = MAT_LAMBERT; v.m.color = mk(m0.y, m0.z, m0.w);
+        } else {
+            v.m = load_mat(sc.mat, vin.obj);
+        }
         if constexpr (!ONE) v.ls_emission = load_mat(sc.mat, vin.light_obj).color;
     }
     if constexpr (ONE) v.ls_emission = ol->emission;
+    static_assert(!LAMBERT || (REMAT && DIFFUSE == kMatsDiffuse), "a Lambert-surfaced scene is a diffuse one, its material re-read here");
     if (DIFFUSE != kMatsMirror) assume_mats<DIFFUSE>(v.m.tag);
     else if (vin.alive) assume_mats<DIFFUSE>(v.m.tag);         // (a lane without a path re-reads object 0's material)
     if (vin.hit_emitter) {
@@ -305,6 +319,7 @@ PT_DEV bool vertex_end(const SceneRef& sc, PathState& p, const Vertex& vin, bool
         }
         float eta_mat = v.m.tag == MAT_MIRROR ? v.m.ior : 1.0f;               // get_eta, material.rs:50 / mirror.rs:317
         float eta_here = v.hit.front_face ? pt_rcp(eta_mat) : eta_mat;         // rendering.rs:20-25
+        if constexpr (LAMBERT) eta_here = 1.0f;                                // pt_rcp(1) == 1 exactly, fast and exact arithmetic
         f3 wo, bsdf; float pdf, cos_theta;
         bsdf_pdf_sample(v.m, p.d, eta_here, v.hit.normal, v.w_bsdf1, v.w_bsdf2, w_lobe, wo, bsdf, pdf, cos_theta);   // :84-85
         f3 next_tp = p.beta * bsdf * cos_theta / pdf;                         // :89
@@ -323,7 +338,7 @@ PT_DEV bool vertex_end(const SceneRef& sc, PathState& p, const Vertex& vin, bool
                 p.o = v.hit.point;
                 p.d = v.m.tag == MAT_EMISSIVE ? normalize(wo) : wo;           // Ray::new, :86; every sampler but
                                                                               // Emissive's returns a normalised wo
-                p.eta_in = eta_here;                                          // :87
+                if constexpr (!LAMBERT) p.eta_in = eta_here;                  // :87 (LAMBERT: it is 1 and stays 1)
                 p.depth += 1u;
             }
         }

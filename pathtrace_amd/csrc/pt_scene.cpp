@@ -156,6 +156,7 @@ int upload(PtContext* c, const SceneJob& j) {
     c->view.scan_f4 = (uint32_t)scan.size();
     c->view.n_runs = (uint32_t)runs.size(); c->view.n_objs = n; c->view.n_lights = (uint32_t)lights.size();
     c->view.spheres_only = rec.spheres_only;
+    c->view.lambert_surfaces = rec.lambert_surfaces;
     c->view.diffuse_only = rec.diffuse_only; c->view.no_mirror = rec.no_mirror; c->view.no_oren_nayar = rec.no_oren_nayar;
     c->split_ok = rec.split_ok;
     std::memcpy(c->scan_counts, rec.scan_counts, sizeof c->scan_counts);

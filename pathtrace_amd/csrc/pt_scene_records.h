@@ -25,6 +25,7 @@ struct Records {
     uint32_t scan_counts[3] = {0, 0, 0};   // spheres, single triangles, triangle pairs
     bool has_blob = false;            // n <= ptk::kSmallObjs
     bool spheres_only = false;        // runs is one run of at most ptk::kSpheresOnlyMax spheres at offset 0, first object 0
+    bool lambert_surfaces = true;     // every material is Lambertian, or Emissive with a non-zero emission
     bool diffuse_only = true, no_mirror = true, no_oren_nayar = true;
     bool split_ok = false;            // a minority of the objects is Mirror
     bool auto_bvh = false;
