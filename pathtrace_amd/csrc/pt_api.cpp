@@ -500,15 +500,15 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
     return PT_OK;
 }
 
-// The renders of injected camera paths: the thin lens, the projections and the caller's rays (5q).  The path kernels
-// know none of them: per sample batch `fill` enqueues the launch that writes the batch's rays as path states into the context's
-// inject planes (k_lens_paths, k_projection_paths, k_ray_paths, k_bake_paths: pt_bake.cpp), and render_impl takes them up as given paths of the tile
+// The renders of injected camera paths: the thin lens, the projections and the caller's rays (5q), the bakes (5r).
+// The path kernels know none of them: per sample batch the source's paths form (k_source_paths, pt_kernels_rays.hip) writes the
+// batch's rays as path states into the context's inject planes, and render_impl takes them up as given paths of the tile
 // (ListRender::tile: the launches of pt_ray_color, the film slots, keys and bands of a plain render).  One render_impl per batch
 // of nb <= max_paths_in_flight / np samples; the f64 film sums travel between the batches as they do between the increments of
 // pt_render_progressive, so the film does not depend on the batching.  Everything is checked, and the planes are there, before
 // the first launch; all launches are on the caller's stream, which orders batch k's level-0 launch (the planes' only reader)
 // before batch k + 1's fill.  The caller has checked what is its own (the lens, the projection, the ray planes) before.
-int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const InjectFill& fill, float* d_linear,
+int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const ptk::RaySourceF& src, float* d_linear,
                          uint8_t* d_rgba, bool no_camera) {
     if (!c || !cam || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
@@ -531,18 +531,19 @@ int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, con
     HIP_TRY(hipSetDevice(c->device));
     for (int k = 0; k < 4; ++k)
         if ((rc = c->inject[k].ensure((size_t)np * nb_max))) return rc;
-    InjectBatch b{};
-    b.tile = tile_map(cam, prm);
-    b.np = np; b.np_magic = magic_of(np); b.w_magic = magic_of(cam->width);
-    for (int k = 0; k < 4; ++k) { b.q[k] = c->inject[k].p; lr.inject[k] = c->inject[k].p; }
+    ptk::SourcePathsArgs a{};
+    a.src = src;
+    a.tile = tile_map(cam, prm);
+    a.np = np; a.np_magic = magic_of(np); a.w_magic = magic_of(cam->width);
+    for (int k = 0; k < 4; ++k) { a.q[k] = c->inject[k].p; lr.inject[k] = c->inject[k].p; }
     for (uint32_t done = 0; done < prm->spp;) {
         const uint32_t nb = std::min(nb_max, prm->spp - done);
         PtRenderParams p = *prm;
         p.spp = nb;
         p.spp_offset = prm->spp_offset + done;
         p.max_paths_in_flight = cap;      // (the cap the batches were cut for, whatever default the sizing would pick)
-        b.s_base = p.spp_offset; b.done = done; b.nb = nb; b.n = np * nb;
-        fill(b);
+        a.s_base = p.spp_offset; a.done = done; a.n = np * nb;
+        if (!ptk::launch_source_paths(prm->exact_math, a, c->stream)) return fail(PT_ERR_INVALID_ARG, "%s: ray source %u has no paths kernel", who, src.tag);
         HIP_TRY(hipGetLastError());
         lr.inject_spp = nb;
         FilmState fs;
@@ -555,67 +556,26 @@ int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, con
     return PT_OK;
 }
 
-// pt_render_lens_device in the name `who`: k_lens_paths fills the planes
-int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,
-                     uint8_t* d_rgba) {
-    if (!c || !cam || !lens || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
-    ptk::LensPathsArgs a{};
-    if (int rc = lens_setup(who, cam, lens, &a.lens)) return rc;
-    a.cam = camera_f32(cam);
-    const bool exact = prm->exact_math;
-    hipStream_t const st = c->stream;
-    return render_injected_impl(who, c, cam, prm, [&a, exact, st](const InjectBatch& b) {
-        a.tile = b.tile;
-        a.np = b.np; a.np_magic = b.np_magic; a.w_magic = b.w_magic;
-        for (int k = 0; k < 4; ++k) a.q[k] = b.q[k];
-        a.s_base = b.s_base; a.n = b.n;
-        if (exact) ptk::launch_lens_paths_exact(a, st); else ptk::launch_lens_paths_fast(a, st);
-    }, d_linear, d_rgba);
+int source_setup(const char* who, const PtCamera* cam, const FrameSource& src, ptk::RaySourceF* out) {
+    *out = ptk::RaySourceF{};
+    out->tag = src.lens ? ptk::kSrcLens : src.proj ? ptk::kSrcProjection : ptk::kSrcCamera;
+    out->cam = camera_f32(cam);
+    if (src.lens) return lens_setup(who, cam, src.lens, &out->lens);
+    return src.proj ? projection_setup(who, cam, src.proj, &out->proj) : PT_OK;
 }
 
-// pt_render_projection_device in the name `who`: k_projection_paths fills the planes
-int render_projection_impl(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
-                           float* d_linear, uint8_t* d_rgba) {
-    if (!c || !cam || !proj || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
-    ptk::ProjPathsArgs a{};
-    if (int rc = projection_setup(who, cam, proj, &a.proj)) return rc;
-    a.cam = camera_f32(cam);
-    const bool exact = prm->exact_math;
-    hipStream_t const st = c->stream;
-    return render_injected_impl(who, c, cam, prm, [&a, exact, st](const InjectBatch& b) {
-        a.tile = b.tile;
-        a.np = b.np; a.np_magic = b.np_magic; a.w_magic = b.w_magic;
-        for (int k = 0; k < 4; ++k) a.q[k] = b.q[k];
-        a.s_base = b.s_base; a.n = b.n;
-        if (exact) ptk::launch_projection_paths_exact(a, st); else ptk::launch_projection_paths_fast(a, st);
-    }, d_linear, d_rgba);
-}
-
-// pt_render_rays_device: k_ray_paths turns the batch's share of the caller's planes into path states
-int render_rays_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const float* d_rays6, const float* d_weights3,
-                     float* d_linear, uint8_t* d_rgba) {
-    if (!c || !cam || !prm || !d_rays6) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
-    if ((uintptr_t)d_rays6 % 8u) return fail(PT_ERR_INVALID_ARG, "%s: d_rays6 must be 8-byte aligned", who);
-    if ((uintptr_t)d_weights3 % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_weights3 must be 4-byte aligned", who);
-    const bool exact = prm->exact_math;
-    hipStream_t const st = c->stream;
-    const uint32_t width = cam->width;
-    return render_injected_impl(who, c, cam, prm, [=](const InjectBatch& b) {
-        ptk::RayPathsArgs a{};
-        const size_t first = (size_t)b.done * b.np;       // the states before this batch's
-        a.rays6 = d_rays6 + 6 * first;
-        a.weights3 = d_weights3 ? d_weights3 + 3 * first : nullptr;
-        for (int k = 0; k < 4; ++k) a.q[k] = b.q[k];
-        a.width = width; a.np = b.np; a.np_magic = b.np_magic; a.w_magic = b.w_magic;
-        a.n = b.n;
-        if (exact) ptk::launch_ray_paths_exact(a, st); else ptk::launch_ray_paths_fast(a, st);
-    }, d_linear, d_rgba);
+int render_source_impl(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm, float* d_linear,
+                       uint8_t* d_rgba) {
+    if (!c || !cam || !prm || (!src.lens && !src.proj)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    ptk::RaySourceF s;
+    if (int rc = source_setup(who, cam, src, &s)) return rc;
+    return render_injected_impl(who, c, cam, prm, s, d_linear, d_rgba);
 }
 
 extern "C" {
 
 int pt_render_lens_device(PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear, uint8_t* d_rgba) {
-    return render_lens_impl("pt_render_lens_device", c, cam, lens, prm, d_linear, d_rgba);
+    return render_source_impl("pt_render_lens_device", c, cam, {lens, nullptr}, prm, d_linear, d_rgba);
 }
 
 int pt_render_lens_host(PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* out_linear, uint8_t* out_rgba) {
@@ -623,10 +583,10 @@ int pt_render_lens_host(PtContext* c, const PtCamera* cam, const PtLens* lens, c
     ptk::LensF checked;
     if (int bad = lens_setup("pt_render_lens_host", cam, lens, &checked)) return bad;      // before the staging is touched
     const size_t np = tile_pixels(cam, prm);
-    if (np == 0) return render_lens_impl("pt_render_lens_host", c, cam, lens, prm, nullptr, nullptr);   // validates, renders nothing
+    if (np == 0) return render_source_impl("pt_render_lens_host", c, cam, {lens, nullptr}, prm, nullptr, nullptr);   // validates, renders nothing
     HIP_TRY(hipSetDevice(c->device));
     return render_staged(c, np * 3, out_rgba ? np * 4 : 0,
-                         [&](float* d_linear, uint8_t* d_rgba) { return render_lens_impl("pt_render_lens_host", c, cam, lens, prm, d_linear, d_rgba); },
+                         [&](float* d_linear, uint8_t* d_rgba) { return render_source_impl("pt_render_lens_host", c, cam, {lens, nullptr}, prm, d_linear, d_rgba); },
                          [&] { return film_back(c, np, out_linear, out_rgba); });
 }
 

@@ -1,5 +1,5 @@
 // pt_bake.cpp -- the host side of light baking: lightmaps and probe bakes as users of the injected-path driver
-// (render_injected_impl, pt_api.cpp) with k_bake_paths as their fill, the launches that follow the render (k_bake_mask, k_probe_sh),
+// (render_injected_impl, pt_api.cpp) with the bake as their ray source, the launches that follow the render (k_bake_mask, k_probe_sh),
 // the rule on the CPU (pt_bake.h in exact arithmetic), the SH entries that need no device, and the debug entry.  The entries' rule,
 // check_plane and the host entries' staging: pt_entry.h.
 #include "pt_entry.h"
@@ -33,21 +33,20 @@ PtCamera film_camera(uint32_t width, uint32_t height) {
     return cam;
 }
 
-// The render of a bake: the planes checked by the caller; k_bake_paths fills the inject planes of every sample batch
+ptk::RaySourceF bake_source(uint32_t kind, uint32_t width, uint32_t height, const float* d_data) {
+    const PtCamera cam = film_camera(width, height);
+    ptk::RaySourceF s{};
+    s.tag = ptk::kSrcBake;
+    s.cam = camera_f32(&cam);
+    s.bake.data = d_data; s.bake.kind = kind; s.bake.width = width;
+    return s;
+}
+
+// The render of a bake: the planes checked by the caller; the bake's paths form fills the inject planes of every sample batch
 int bake_render(const char* who, PtContext* c, uint32_t kind, uint32_t width, uint32_t height, const float* d_data, const PtRenderParams* prm,
                 float* d_linear, uint8_t* d_rgba) {
     const PtCamera cam = film_camera(width, height);
-    const bool exact = prm->exact_math;
-    hipStream_t const st = c->stream;
-    return render_injected_impl(who, c, &cam, prm, [=](const InjectBatch& b) {
-        ptk::BakePathsArgs a{};
-        a.data = d_data;
-        for (int k = 0; k < 4; ++k) a.q[k] = b.q[k];
-        a.kind = kind; a.width = width;
-        a.np = b.np; a.np_magic = b.np_magic; a.w_magic = b.w_magic;
-        a.s_base = b.s_base; a.n = b.n;
-        if (exact) ptk::launch_bake_paths_exact(a, st); else ptk::launch_bake_paths_fast(a, st);
-    }, d_linear, d_rgba, /*no_camera=*/true);
+    return render_injected_impl(who, c, &cam, prm, bake_source(kind, width, height, d_data), d_linear, d_rgba, /*no_camera=*/true);
 }
 
 int lightmap_impl(const char* who, PtContext* c, uint32_t width, uint32_t height, const float* d_texels6, const PtRenderParams* prm,
@@ -209,18 +208,10 @@ int pt_debug_bake_rays(PtContext* c, uint32_t kind, uint32_t width, uint32_t hei
     if (n == 0) return PT_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t nd = data_floats(kind, width, height);
-    if ((rc = c->fn_in.ensure(nd + 2)) || (rc = c->fn_out.ensure(6 * (size_t)n)) || (rc = c->fn_words.ensure(4 * (size_t)n))) return rc;
-    std::vector<uint32_t> w(4 * (size_t)n, 0u);
-    for (size_t i = 0; i < n; ++i) { w[4 * i] = xys[3 * i]; w[4 * i + 1] = xys[3 * i + 1]; w[4 * i + 2] = xys[3 * i + 2]; }
+    if ((rc = c->fn_in.ensure(nd + 2))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->fn_in.p, data, nd * sizeof(float), hipMemcpyHostToDevice));      // (hipMalloc's alignment: fine for 8-byte words)
-    HIP_TRY(hipMemcpy(c->fn_words.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (exact_math) ptk::launch_debug_bake_rays_exact(c->fn_in.p, kind, width, c->fn_words.p, n, c->fn_out.p, c->stream);
-    else ptk::launch_debug_bake_rays_fast(c->fn_in.p, kind, width, c->fn_words.p, n, c->fn_out.p, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out6, c->fn_out.p, 6 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_source_rays(c, bake_source(kind, width, height, c->fn_in.p), xys, n, exact_math, 6, out6);
 }
 
 }  // extern "C"

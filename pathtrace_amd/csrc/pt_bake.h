@@ -1,5 +1,5 @@
 // pt_bake.h -- the rule of light baking (pt_bake_lightmap_device, pt_bake_probes_device, pt_sh_project_device), written
-// once for the kernels (k_bake_paths and k_debug_bake_rays in pt_kernels_main.hip, k_bake_mask and k_probe_sh in pt_film_bake.h),
+// once for the kernels (BakeSource under the paths and debug-ray forms of pt_kernels_rays.hip, k_bake_mask and k_probe_sh in pt_film_bake.h),
 // the host entries (pt_bake.cpp) and the host compilers of the tests.  Build with -ffp-contract=off: no compiler fuses what the
 // rule writes apart.
 //

@@ -2,7 +2,6 @@
 // resources, struct PtContext (its device BVH: struct DeviceBvh, pt_scene_bvh.h) and the few functions that cross files.
 #pragma once
 #include <cstdint>
-#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -276,39 +275,32 @@ int render_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, co
                 float* d_linear, uint8_t* d_rgba, void* d_packed = nullptr, const AdaptivePass* ad = nullptr,
                 const CascadePass* cas = nullptr, const FilterPass* flt = nullptr);   // pt_api.cpp
 int render_adaptive_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtAdaptive* ad);   // pt_api.cpp
-// The driver of every render of injected camera paths (pt_api.cpp): `fill` enqueues, per sample batch, the launch that writes the
-// batch's n = nb * np path states (samples s_base .. s_base + nb - 1 of the tile's np pixels, `done` samples before them) into q.
-struct InjectBatch {
-    float4* q[4];
-    ptk::TileMap tile;
-    uint32_t np, np_magic, w_magic;   // tile pixels; floor(2^32 / np) and floor(2^32 / width) for divmod_magic
-    uint32_t s_base, done, nb, n;
+// The source of a frame's first rays as an entry receives it: a lens, a projection, or neither (the pinhole camera).
+struct FrameSource {
+    const PtLens* lens = nullptr;
+    const PtProjection* proj = nullptr;
 };
-using InjectFill = std::function<void(const InjectBatch&)>;
-int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const InjectFill& fill, float* d_linear,
-                         uint8_t* d_rgba, bool no_camera = false);   // no_camera: ListRender::no_camera (the bakes, pt_bake.cpp)
-// pt_render_projection_device and pt_render_rays_device in the name `who` (pt_api.cpp); pt_projection.cpp: the projection and the
-// camera checked, the device's words; pt_denoise.cpp: the projection forms of the feature pass and the one-call frame
-int render_projection_impl(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
-                           float* d_linear, uint8_t* d_rgba);
-int render_rays_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const float* d_rays6, const float* d_weights3,
-                     float* d_linear, uint8_t* d_rgba);
-int projection_setup(const char* who, const PtCamera* cam, const PtProjection* proj, ptk::ProjF* out);
-int features_projection_device(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
-                               uint32_t n_samples, float* d_features);
-int render_projection_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
-                                    uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                                    float* out_features);
-// pt_render_lens_device in the name `who` (pt_api.cpp); pt_lens.cpp: the lens and the camera checked, the device's words
-int render_lens_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, float* d_linear,
-                     uint8_t* d_rgba);
-int lens_setup(const char* who, const PtCamera* cam, const PtLens* lens, ptk::LensF* out);
-ptk::CameraF camera_f32(const PtCamera* cam);                        // pt_lens.cpp
-int features_lens_device(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
-                         float* d_features);                          // pt_denoise.cpp
-int render_lens_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm,
-                              uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                              float* out_features);                   // pt_denoise.cpp
+// The source and the camera's frame checked (a check answers in the entry's name, who), the kernels' words.  No context.  (pt_api.cpp)
+int source_setup(const char* who, const PtCamera* cam, const FrameSource& src, ptk::RaySourceF* out);
+// The driver of every render of injected camera paths (pt_api.cpp): per sample batch it launches the source's paths form into the
+// context's inject planes and renders them.  The caller has checked what is its own.  no_camera: ListRender::no_camera (the bakes)
+int render_injected_impl(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const ptk::RaySourceF& src, float* d_linear,
+                         uint8_t* d_rgba, bool no_camera = false);
+// pt_render_lens_device and pt_render_projection_device in the name `who` (pt_api.cpp): src holds the lens or the projection
+int render_source_impl(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm, float* d_linear,
+                       uint8_t* d_rgba);
+// the words of xys = n * (x, y, sample) through the source's debug form into out = n * stride floats; blocking (pt_debug.cpp)
+int debug_source_rays(PtContext* c, const ptk::RaySourceF& src, const uint32_t* xys, uint32_t n, uint32_t exact_math, uint32_t stride, float* out);
+int lens_setup(const char* who, const PtCamera* cam, const PtLens* lens, ptk::LensF* out);                  // pt_lens.cpp
+int projection_setup(const char* who, const PtCamera* cam, const PtProjection* proj, ptk::ProjF* out);      // pt_projection.cpp
+ptk::CameraF camera_f32(const PtCamera* cam);                                                               // pt_lens.cpp
+// The lens and projection forms of pt_render_features_device and pt_render_denoised (pt_denoise.cpp; their entries: pt_lens.cpp,
+// pt_projection.cpp), src not empty
+int features_source_device(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm,
+                           uint32_t n_samples, float* d_features);
+int render_source_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm,
+                                uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                                float* out_features);
 int denoised_frame_device(const char* who, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                           const PtDenoise* dn, PtRenderParams* p);   // pt_denoise.cpp
 int tonemap_check_args(const char* who, uint32_t width, uint32_t height, const float* d_linear, const PtTonemap* tm, const float* d_out_linear,

@@ -78,6 +78,25 @@ std::vector<float> to_f32(const double* p, size_t n) {
 
 }  // namespace
 
+// pt_debug_lens_rays, pt_debug_projection_rays and pt_debug_bake_rays behind their checks: the words, the source's debug form, the
+// floats back
+int debug_source_rays(PtContext* c, const ptk::RaySourceF& src, const uint32_t* xys, uint32_t n, uint32_t exact_math, uint32_t stride, float* out) {
+    if (n == 0) return PT_OK;
+    int rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->fn_out.ensure(stride * (size_t)n)) || (rc = c->fn_words.ensure(4 * (size_t)n))) return rc;
+    std::vector<uint32_t> w(4 * (size_t)n, 0u);
+    for (size_t i = 0; i < n; ++i) { w[4 * i] = xys[3 * i]; w[4 * i + 1] = xys[3 * i + 1]; w[4 * i + 2] = xys[3 * i + 2]; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->fn_words.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!ptk::launch_debug_source_rays(exact_math, src, c->fn_words.p, n, c->fn_out.p, c->stream))
+        return fail(PT_ERR_INVALID_ARG, "ray source %u has no debug-ray kernel", src.tag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, c->fn_out.p, stride * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 extern "C" {
 
 int pt_debug_hit_scene(PtContext* c, const double* rays, uint32_t n, double t_min, double t_max, uint32_t exact_math,

@@ -84,10 +84,10 @@ ptk::DenoiseArgs denoise_args(const PtContext* c, uint32_t width, uint32_t heigh
 
 // The front of a pt_render_denoised* frame: staging for np pixels, then the render into host_lin, the features into dn_feat and, from
 // History::motion on, the ids into dn_ids.  History::alpha (the gradient entries): gr_alpha too, and no previous frame from here on.
-int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
-                  float* d_features, int32_t* d_ids, const PtProjection* proj = nullptr);
+int features_impl(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm, uint32_t n_samples,
+                  float* d_features, int32_t* d_ids);
 int frame_front(History form, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, size_t np, PtRenderParams* p,
-                const PtLens* lens = nullptr, const PtProjection* proj = nullptr) {
+                const FrameSource& src = {}) {
     int rc;
     if ((rc = c->host_lin.ensure(3 * np)) || (rc = c->host_rgba.ensure(4 * np)) || (rc = c->dn_feat.ensure(2 * np)) || (rc = c->dn_lin.ensure(3 * np)) ||
         (form >= History::motion && (rc = c->dn_ids.ensure(np))) || (form == History::alpha && (rc = c->gr_alpha.ensure(np))))
@@ -95,39 +95,27 @@ int frame_front(History form, PtContext* c, const PtCamera* cam, const PtRenderP
     if (form == History::alpha) c->gr_valid = false;
     *p = *prm;                                // for the whole image
     p->band_count = 1; p->band_index = 0; p->band_rows = 0;
-    if (lens) {                               // pt_render_lens_denoised: both passes through the lens (History::none only)
-        if ((rc = render_lens_impl("pt_render_lens_denoised", c, cam, lens, p, c->host_lin.p, nullptr)) ||
-            (rc = features_impl("pt_render_lens_denoised", c, cam, lens, p, std::min(feature_samples, p->spp), reinterpret_cast<float*>(c->dn_feat.p), nullptr)))
-            return rc;
-        return PT_OK;
-    }
-    if (proj) {                               // pt_render_projection_denoised: both passes through the projection (History::none only)
-        if ((rc = render_projection_impl("pt_render_projection_denoised", c, cam, proj, p, c->host_lin.p, nullptr)) ||
-            (rc = features_impl("pt_render_projection_denoised", c, cam, nullptr, p, std::min(feature_samples, p->spp),
-                                reinterpret_cast<float*>(c->dn_feat.p), nullptr, proj)))
-            return rc;
-        return PT_OK;
-    }
-    if ((rc = render_impl(c, cam, p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
-        (rc = pt_render_features_device(c, cam, p, std::min(feature_samples, p->spp), reinterpret_cast<float*>(c->dn_feat.p))))
+    // pt_render_lens_denoised, pt_render_projection_denoised: both passes through the source (History::none only)
+    const char* const who = src.lens ? "pt_render_lens_denoised" : src.proj ? "pt_render_projection_denoised" : nullptr;
+    if ((rc = who ? render_source_impl(who, c, cam, src, p, c->host_lin.p, nullptr) : render_impl(c, cam, p, FilmState{}, nullptr, c->host_lin.p, nullptr)) ||
+        (rc = features_impl(who ? who : "pt_render_features_device", c, cam, src, p, std::min(feature_samples, p->spp),
+                            reinterpret_cast<float*>(c->dn_feat.p), nullptr)))
         return rc;
     return form >= History::motion ? pt_render_feature_ids_device(c, cam, p, c->dn_ids.p) : PT_OK;
 }
 
-// First-hit features: per batch of samples, k_feature_rays writes the camera rays, launch_debug_hit (the scan or BVH of the
+// First-hit features: per batch of samples, k_source_feature_rays writes the rays, launch_debug_hit (the scan or BVH of the
 // parity entries) finds their hits, k_feature_resolve adds the records to the per-pixel sums in d_features.
 // pt_render_feature_ids_device is the same pass over the one sample spp_offset without the resolve: the hit ids of that batch,
-// copied out of the scratch (d_features null, d_ids set).  lens (pt_render_features_lens_device): k_lens_feature_rays writes the rays;
-// proj (pt_render_features_projection_device): k_projection_feature_rays does.
-int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
-                  float* d_features, int32_t* d_ids, const PtProjection* proj) {
+// copied out of the scratch (d_features null, d_ids set).  src (pt_render_features_lens_device, pt_render_features_projection_device):
+// the source whose feature-ray form writes the rays; empty: the pinhole camera's.
+int features_impl(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm, uint32_t n_samples,
+                  float* d_features, int32_t* d_ids) {
     if (!c || !cam || !prm || (!d_features && !d_ids)) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (n_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: n_samples must be > 0", who);
     int rc;
-    ptk::LensF lf{};
-    if (lens && (rc = lens_setup(who, cam, lens, &lf))) return rc;
-    ptk::ProjF pf{};
-    if (proj && (rc = projection_setup(who, cam, proj, &pf))) return rc;
+    ptk::RaySourceF sf;
+    if ((rc = source_setup(who, cam, src, &sf))) return rc;
     if ((rc = check_whole_image(who, ": works on", "", prm))) return rc;
     if ((uintptr_t)d_features % 16u) return fail(PT_ERR_INVALID_ARG, "%s: d_features must be 16-byte aligned", who);
     if ((uintptr_t)d_ids % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_ids must be 4-byte aligned", who);
@@ -147,7 +135,6 @@ int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLe
         (accel && (rc = c->ft_scratch.ensure(3 * n_rays))))
         return rc;
     const ptk::SceneView sv = view_for(c, prm->exact_math);
-    const ptk::CameraF cf = camera_f32(cam);
     const hipStream_t st = c->stream;
     const float t_min = (float)prm->t_min, t_max = INFINITY;
     for (uint32_t done = 0; done < n_samples;) {
@@ -156,19 +143,11 @@ int features_impl(const char* who, PtContext* c, const PtCamera* cam, const PtLe
         ptk::FeatureResolveArgs a{};
         a.mat = sv.mat; a.ids = c->ft_ids.p; a.rec = c->ft_rec.p; a.out = reinterpret_cast<float4*>(d_features);
         a.np = np; a.nb = nb; a.n_samples = n_samples; a.load = done > 0; a.finalize = done + nb == n_samples;
-        if (prm->exact_math) {
-            if (lens) ptk::launch_lens_feature_rays_exact(cf, lf, s_base, nb, c->ft_rays.p, st);
-            else if (proj) ptk::launch_projection_feature_rays_exact(cf, pf, s_base, nb, c->ft_rays.p, st);
-            else ptk::launch_feature_rays_exact(cf, s_base, nb, c->ft_rays.p, st);
-            ptk::launch_debug_hit_exact(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
-            if (d_features) ptk::launch_feature_resolve_exact(a, st);
-        } else {
-            if (lens) ptk::launch_lens_feature_rays_fast(cf, lf, s_base, nb, c->ft_rays.p, st);
-            else if (proj) ptk::launch_projection_feature_rays_fast(cf, pf, s_base, nb, c->ft_rays.p, st);
-            else ptk::launch_feature_rays_fast(cf, s_base, nb, c->ft_rays.p, st);
-            ptk::launch_debug_hit_fast(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
-            if (d_features) ptk::launch_feature_resolve_fast(a, st);
-        }
+        if (!ptk::launch_source_feature_rays(prm->exact_math, sf, s_base, nb, c->ft_rays.p, st))
+            return fail(PT_ERR_INVALID_ARG, "%s: ray source %u has no feature-ray kernel", who, sf.tag);
+        if (prm->exact_math) ptk::launch_debug_hit_exact(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
+        else ptk::launch_debug_hit_fast(sv, accel, c->ft_rays.p, nb * np, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, c->ft_rec.p, st);
+        if (d_features) ptk::launch_feature_resolve(prm->exact_math, a, st);
         HIP_TRY(hipGetLastError());
         if (d_ids && done == 0) HIP_TRY(hipMemcpyAsync(d_ids, c->ft_ids.p, (size_t)np * sizeof(int32_t), hipMemcpyDeviceToDevice, st));   // sample spp_offset
         done += nb;
@@ -192,21 +171,18 @@ int denoise_steps(PtContext* c, ptk::DenoiseArgs a, uint32_t iterations) {
 // ids pass): render, features, filter; host buffers, blocking
 int render_denoised_impl(const char* who, History form, PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples,
                          const PtDenoise* dn, const PtTemporal* tp, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                         float* out_features, int32_t* out_ids, const PtLens* lens = nullptr,
-                         const PtProjection* proj = nullptr) {
+                         float* out_features, int32_t* out_ids, const FrameSource& src = {}) {
     if (!c || !cam || !prm || !dn || (form != History::none && !tp) || !out_linear) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    ptk::LensF checked;
-    if (lens && (rc = lens_setup(who, cam, lens, &checked))) return rc;
-    ptk::ProjF proj_checked;
-    if (proj && (rc = projection_setup(who, cam, proj, &proj_checked))) return rc;
+    ptk::RaySourceF checked;
+    if ((rc = source_setup(who, cam, src, &checked))) return rc;
     if ((rc = check_whole_image(who, ": renders", "", prm))) return rc;
     if (feature_samples == 0) return fail(PT_ERR_INVALID_ARG, "%s: feature_samples must be > 0", who);
     if ((rc = check_target(who, c, cam))) return rc;
     const size_t np = (size_t)cam->width * cam->height;
     HIP_TRY(hipSetDevice(c->device));
     PtRenderParams p;
-    if ((rc = frame_front(form, c, cam, prm, feature_samples, np, &p, lens, proj))) return rc;
+    if ((rc = frame_front(form, c, cam, prm, feature_samples, np, &p, src))) return rc;
     float* const feat = reinterpret_cast<float*>(c->dn_feat.p);
     uint8_t* const rgba = out_rgba ? c->host_rgba.p : nullptr;
     if ((rc = form == History::motion  ? pt_denoise_temporal_motion_device(c, cam, c->host_lin.p, feat, c->dn_ids.p, dn, tp, c->dn_lin.p, rgba)
@@ -425,38 +401,26 @@ int denoised_frame_device(const char* who, PtContext* c, const PtCamera* cam, co
     return pt_denoise_device(c, cam->width, cam->height, c->host_lin.p, reinterpret_cast<float*>(c->dn_feat.p), dn, c->dn_lin.p, nullptr);
 }
 
-// The lens forms of pt_render_features_device and pt_render_denoised (their entries: pt_lens.cpp), lens not null
-int features_lens_device(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
-                         float* d_features) {
-    return features_impl(who, c, cam, lens, prm, n_samples, d_features, nullptr);
+// The lens and projection forms of pt_render_features_device and pt_render_denoised (their entries: pt_lens.cpp, pt_projection.cpp)
+int features_source_device(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm,
+                           uint32_t n_samples, float* d_features) {
+    return features_impl(who, c, cam, src, prm, n_samples, d_features, nullptr);
 }
-int render_lens_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm,
-                              uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                              float* out_features) {
+int render_source_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm,
+                                uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
+                                float* out_features) {
     return render_denoised_impl(who, History::none, c, cam, prm, feature_samples, dn, nullptr, out_linear, out_rgba, out_noisy, out_features,
-                                nullptr, lens);
-}
-
-// The projection forms of the same two (their entries: pt_projection.cpp), proj not null
-int features_projection_device(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
-                               uint32_t n_samples, float* d_features) {
-    return features_impl(who, c, cam, nullptr, prm, n_samples, d_features, nullptr, proj);
-}
-int render_projection_denoised_host(const char* who, PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
-                                    uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
-                                    float* out_features) {
-    return render_denoised_impl(who, History::none, c, cam, prm, feature_samples, dn, nullptr, out_linear, out_rgba, out_noisy, out_features,
-                                nullptr, nullptr, proj);
+                                nullptr, src);
 }
 
 extern "C" {
 
 int pt_render_features_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t n_samples, float* d_features) {
-    return features_impl("pt_render_features_device", c, cam, nullptr, prm, n_samples, d_features, nullptr);
+    return features_impl("pt_render_features_device", c, cam, {}, prm, n_samples, d_features, nullptr);
 }
 
 int pt_render_feature_ids_device(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, int32_t* d_ids) {
-    return features_impl("pt_render_feature_ids_device", c, cam, nullptr, prm, 1, nullptr, d_ids);
+    return features_impl("pt_render_feature_ids_device", c, cam, {}, prm, 1, nullptr, d_ids);
 }
 
 int pt_denoise_device(PtContext* c, uint32_t width, uint32_t height, const float* d_linear, const float* d_features,

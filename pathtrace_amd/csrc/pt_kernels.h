@@ -323,10 +323,9 @@ void launch_debug_fn_exact(const DebugFnArgs& a, hipStream_t st);
 void launch_debug_fn_fast(const DebugFnArgs& a, hipStream_t st);
 
 
-// First-hit feature buffers (pt_render_features_device).  launch_feature_rays: the camera rays of samples s_base .. s_base + nb - 1
-// of every image pixel, ray s_local * np + p, as the rays6 launch_debug_hit reads.  launch_feature_resolve: the hits of that batch
-// (launch_debug_hit's ids and records) -> 32-byte records (albedo rgb, emitter | normal xyz, depth), summed per pixel in sample
-// order into out (2 float4 per pixel; load: add to the sums there); finalize divides by n_samples.
+// First-hit feature buffers (pt_render_features_device).  launch_feature_resolve: the hits of one batch of feature rays
+// (launch_source_feature_rays below; launch_debug_hit's ids and records) -> 32-byte records (albedo rgb, emitter | normal xyz, depth),
+// summed per pixel in sample order into out (2 float4 per pixel; load: add to the sums there); finalize divides by n_samples.
 struct FeatureResolveArgs {
     const float4* mat;        // material records of the arithmetic mode's scene view
     const int32_t* ids;       // nb * np
@@ -334,10 +333,11 @@ struct FeatureResolveArgs {
     float4* out;
     uint32_t np, nb, n_samples, load, finalize;
 };
-void launch_feature_rays_exact(const CameraF& cam, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
-void launch_feature_rays_fast(const CameraF& cam, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
 void launch_feature_resolve_exact(const FeatureResolveArgs& a, hipStream_t st);
 void launch_feature_resolve_fast(const FeatureResolveArgs& a, hipStream_t st);
+inline void launch_feature_resolve(bool exact, const FeatureResolveArgs& a, hipStream_t st) {
+    exact ? launch_feature_resolve_exact(a, st) : launch_feature_resolve_fast(a, st);
+}
 
 // Edge-avoiding a-trous denoiser (pt_denoise_device; rule: include/pathtrace_amd.h PtDenoise).  init: the film -> the state
 // plane dst (u.rgb, var); a step (init = false): src -> dst with the taps at distance `step`.  finalize: the launch writes
@@ -567,78 +567,63 @@ struct UpsampleArgs {
 };
 void launch_upsample(const UpsampleArgs& a, hipStream_t st);
 
-// Thin-lens camera (pt_render_lens_device; rule: pt_lens.h).  LensF: ptlens::Setup as the kernels take it.
-// launch_lens_paths: the lens rays of samples s_base .. s_base + nb - 1 of every tile pixel as n = nb * np path states in the
-// queue form (state s_local * np + tile pixel), for a path-kernel launch with src_mode = 1 to take up from ovf_in.
-// launch_lens_feature_rays: launch_feature_rays with lens rays.  launch_debug_lens_rays: words = n * (x, y, sample, -) ->
-// out8 = n * (o'3, d'3, dx, dy).
+// Sources of first rays (pt_kernels_rays.hip): the pinhole camera (feature rays only), the thin lens (pt_render_lens_device; rule:
+// pt_lens.h), the projections and the caller's rays (pt_render_projection_device, pt_render_rays_device; rule:
+// pt_projection.h) and the bakes (pt_bake_lightmap_device, pt_bake_probes_device; rule: pt_bake.h).
+// LensF, ProjF: ptlens::Setup and ptproj::Setup as the kernels take them; ProjF::kind: PT_PROJ_*.
 struct LensF {
     float lu[3], lv[3], inv_phi;
 };
-struct LensPathsArgs {
-    CameraF cam;
-    LensF lens;
-    TileMap tile;
-    float4* q[4];
-    uint32_t np, np_magic, w_magic;   // tile pixels; floor(2^32 / np) and floor(2^32 / cam.width), 0xFFFFFFFF for 1
-    uint32_t s_base, n;
-};
-void launch_lens_paths_exact(const LensPathsArgs& a, hipStream_t st);
-void launch_lens_paths_fast(const LensPathsArgs& a, hipStream_t st);
-void launch_lens_feature_rays_exact(const CameraF& cam, const LensF& lens, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
-void launch_lens_feature_rays_fast(const CameraF& cam, const LensF& lens, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
-void launch_debug_lens_rays_exact(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
-void launch_debug_lens_rays_fast(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
-
-// Projections and caller rays (pt_render_projection_device, pt_render_rays_device; rule: pt_projection.h).  ProjF:
-// ptproj::Setup as the kernels take it, and the kind (PT_PROJ_*), which every kernel branches on once.
-// launch_projection_paths / _feature_rays / launch_debug_projection_rays: their lens namesakes with projection rays
-// (out8 = n * (o3, d3, a, b)).  launch_ray_paths: the caller's n = nb * np rays (rays6: float[n][6] in state order, 8-byte
-// aligned; weights3: float[n][3] or null = 1) as path states in the queue form; directions as given.
 struct ProjF {
     float u[3], v[3], w[3], c[3], aspect, fov720;
     uint32_t kind;
 };
-struct ProjPathsArgs {
-    CameraF cam;
+enum { kSrcCamera = 0, kSrcLens = 1, kSrcProjection = 2, kSrcBake = 3, kSrcRays = 4 };
+struct RaySourceF {
+    uint32_t tag;             // kSrc*: which of the words below are read
+    CameraF cam;              // every source: the film's width and height; camera, lens, projection: the frame
+    LensF lens;
     ProjF proj;
+    struct {                  // the film is width x rows = texels (kind 0, data: float[H][W][6], 8-byte aligned) or directions x
+        const float* data;    // probes (kind 1, data: float[P][3])
+        uint32_t kind, width;
+    } bake;
+    struct {                  // the render's rays in state order, float[n][6], 8-byte aligned, directions as given; weights3:
+        const float* rays6;   // float[n][3], or null = 1
+        const float* weights3;
+    } rays;
+};
+// launch_source_paths: the source's rays of samples s_base .. s_base + nb - 1 of every tile pixel as n = nb * np path states in the
+// queue form (state s_local * np + tile pixel), for a path-kernel launch with src_mode = 1 to take up from ovf_in.
+struct SourcePathsArgs {
+    RaySourceF src;
     TileMap tile;
     float4* q[4];
-    uint32_t np, np_magic, w_magic;   // as LensPathsArgs
-    uint32_t s_base, n;
+    uint32_t np, np_magic, w_magic;   // tile pixels; floor(2^32 / np) and floor(2^32 / cam.width), 0xFFFFFFFF for 1
+    uint32_t s_base, done, n;         // done: samples of the render before this batch (the caller's rays start at state done * np)
 };
-struct RayPathsArgs {
-    const float* rays6;
-    const float* weights3;
-    float4* q[4];
-    uint32_t width, np, np_magic, w_magic;
-    uint32_t n;
-};
-void launch_projection_paths_exact(const ProjPathsArgs& a, hipStream_t st);
-void launch_projection_paths_fast(const ProjPathsArgs& a, hipStream_t st);
-void launch_projection_feature_rays_exact(const CameraF& cam, const ProjF& pj, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
-void launch_projection_feature_rays_fast(const CameraF& cam, const ProjF& pj, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
-void launch_debug_projection_rays_exact(const CameraF& cam, const ProjF& pj, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
-void launch_debug_projection_rays_fast(const CameraF& cam, const ProjF& pj, const uint32_t* words, uint32_t n, float* out8, hipStream_t st);
-void launch_ray_paths_exact(const RayPathsArgs& a, hipStream_t st);
-void launch_ray_paths_fast(const RayPathsArgs& a, hipStream_t st);
+// launch_source_feature_rays: the source's rays of samples s_base .. s_base + nb - 1 of every image pixel, ray s_local * np + p, as
+// the rays6 launch_debug_hit reads.  launch_debug_source_rays: words = n * (x, y, sample, -) -> out = n * (o3, d3, dx, dy) for the
+// lens, n * (o3, d3, a, b) for a projection, n * (o3, d3) for a bake (x < width and y < the rows: the caller has checked).
+// false: the source has no kernel of that form (paths: all but the camera; feature rays: camera, lens, projection; debug rays:
+// lens, projection, bake), nothing was launched.
+bool launch_source_paths_exact(const SourcePathsArgs& a, hipStream_t st);
+bool launch_source_paths_fast(const SourcePathsArgs& a, hipStream_t st);
+bool launch_source_feature_rays_exact(const RaySourceF& src, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
+bool launch_source_feature_rays_fast(const RaySourceF& src, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
+bool launch_debug_source_rays_exact(const RaySourceF& src, const uint32_t* words, uint32_t n, float* out, hipStream_t st);
+bool launch_debug_source_rays_fast(const RaySourceF& src, const uint32_t* words, uint32_t n, float* out, hipStream_t st);
+inline bool launch_source_paths(bool exact, const SourcePathsArgs& a, hipStream_t st) {
+    return exact ? launch_source_paths_exact(a, st) : launch_source_paths_fast(a, st);
+}
+inline bool launch_source_feature_rays(bool exact, const RaySourceF& src, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st) {
+    return exact ? launch_source_feature_rays_exact(src, s_base, nb, rays6, st) : launch_source_feature_rays_fast(src, s_base, nb, rays6, st);
+}
+inline bool launch_debug_source_rays(bool exact, const RaySourceF& src, const uint32_t* words, uint32_t n, float* out, hipStream_t st) {
+    return exact ? launch_debug_source_rays_exact(src, words, n, out, st) : launch_debug_source_rays_fast(src, words, n, out, st);
+}
 
-// Light baking (pt_bake_lightmap_device, pt_bake_probes_device, pt_sh_project_device; rule: pt_bake.h).
-// launch_bake_paths: the bake's rays of one sample batch as path states in the queue form, k_projection_paths's indexing with the
-// film's width x rows = texels (kind 0, data: float[H][W][6], 8-byte aligned) or directions x probes (kind 1, data: float[P][3]).
-// launch_debug_bake_rays: words[4] = x, y, sample, - -> out6 = o3, d3 (x < width and y < the rows: the caller has checked).
-// launch_bake_mask, launch_probe_sh (film unit, one form for both modes): what follows the render.
-struct BakePathsArgs {
-    const float* data;
-    float4* q[4];
-    uint32_t kind, width;
-    uint32_t np, np_magic, w_magic;   // as LensPathsArgs
-    uint32_t s_base, n;
-};
-void launch_bake_paths_exact(const BakePathsArgs& a, hipStream_t st);
-void launch_bake_paths_fast(const BakePathsArgs& a, hipStream_t st);
-void launch_debug_bake_rays_exact(const float* data, uint32_t kind, uint32_t width, const uint32_t* words, uint32_t n, float* out6, hipStream_t st);
-void launch_debug_bake_rays_fast(const float* data, uint32_t kind, uint32_t width, const uint32_t* words, uint32_t n, float* out6, hipStream_t st);
+// What follows a bake's render (pt_sh_project_device too; film unit, one form for both modes).
 void launch_bake_mask(const float* texels6, uint32_t n, float* out_linear, uint8_t* out_rgba, hipStream_t st);
 void launch_probe_sh(uint32_t n_probes, uint32_t rays_per_probe, const float* radiance, float* sh27, hipStream_t st);
 

@@ -35,9 +35,6 @@
 // conflict-free).  Grids are persistent (one queue segment per wave), so no host round trip sits between bounces.
 #include "pt_kernels_scan.h"
 #include "pt_kernels_vertex.h"
-#include "pt_lens.h"
-#include "pt_projection.h"
-#include "pt_bake.h"
 
 namespace PTK_IMPL {
 
@@ -998,352 +995,5 @@ void PT_LAUNCH(launch_debug_hit)(const SceneView& sc, uint32_t accel, const floa
         hipLaunchKernelGGL(k_debug_hit<kModeTiled>, dim3(grid), dim3(kBlock), lds, st, sc, rays6, n, t_min, t_max, out_id, out_t, out_rec);
     else
         PT_LAUNCH(launch_debug_hit_bvh)(sc, grid, lds, rays6, n, t_min, t_max, scratch, out_id, out_t, out_rec, st);
-}
-}  // namespace ptk
-
-// ------------------------------------------------------------------ first-hit feature buffers (pt_render_features_device)
-// k_feature_rays: the camera rays of samples s_base .. s_base + nb - 1 of every image pixel (camera_ray: the key, jitter draws
-// and arithmetic of the path kernels), ray i = s_local * np + p in the rays6 form k_debug_hit reads.  k_feature_resolve maps
-// the hits of one batch to records (albedo rgb, emitter | normal xyz, depth) and adds them to the pixel's f32 sums in sample
-// order; the sums of earlier batches wait in `out` (load), and the last batch divides by n_samples.
-namespace PTK_IMPL {
-__global__ void __launch_bounds__(kBlock) k_feature_rays(CameraF cam, uint32_t s_base, uint32_t nb, float* __restrict__ rays6) {
-    const uint32_t np = cam.width * cam.height;
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= nb * np) return;
-    const uint32_t s = i / np, p = i - s * np;
-    const uint32_t y = p / cam.width, x = p - y * cam.width;
-    f3 o, d;
-    camera_ray(cam, s_base + s, x, y, o, d);
-    float* r = rays6 + 6 * (size_t)i;
-    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
-}
-__global__ void __launch_bounds__(kBlock) k_feature_resolve(FeatureResolveArgs a) {
-    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= a.np) return;
-    float4 f0 = make_float4(0.f, 0.f, 0.f, 0.f), f1 = f0;
-    if (a.load) { f0 = a.out[2 * (size_t)p]; f1 = a.out[2 * (size_t)p + 1]; }
-    for (uint32_t s = 0; s < a.nb; ++s) {
-        const size_t i = (size_t)s * a.np + p;
-        const int id = a.ids[i];
-        float4 g0 = make_float4(1.f, 1.f, 1.f, 0.f), g1 = make_float4(0.f, 0.f, 0.f, 0.f);   // a miss
-        if (id >= 0) {
-            const Mat m = load_mat(a.mat, id);
-            const float* rec = a.rec + 8 * i;
-            if (m.tag == MAT_EMISSIVE) g0.w = 1.0f;
-            else g0 = make_float4(fminf(fmaxf(m.color.x, 0.f), 1.f), fminf(fmaxf(m.color.y, 0.f), 1.f), fminf(fmaxf(m.color.z, 0.f), 1.f), 0.f);
-            g1 = make_float4(rec[4], rec[5], rec[6], rec[0]);                         // face-forwarded normal, t
-        }
-        f0.x += g0.x; f0.y += g0.y; f0.z += g0.z; f0.w += g0.w;
-        f1.x += g1.x; f1.y += g1.y; f1.z += g1.z; f1.w += g1.w;
-    }
-    if (a.finalize) {
-        const float n = (float)a.n_samples;
-        f0 = make_float4(pt_div(f0.x, n), pt_div(f0.y, n), pt_div(f0.z, n), pt_div(f0.w, n));
-        f1 = make_float4(pt_div(f1.x, n), pt_div(f1.y, n), pt_div(f1.z, n), pt_div(f1.w, n));
-    }
-    a.out[2 * (size_t)p] = f0; a.out[2 * (size_t)p + 1] = f1;
-}
-}  // namespace PTK_IMPL
-namespace ptk {
-void PT_LAUNCH(launch_feature_rays)(const CameraF& cam, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st) {
-    const uint32_t n = nb * cam.width * cam.height;
-    if (n) hipLaunchKernelGGL(PTK_IMPL::k_feature_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, s_base, nb, rays6);
-}
-void PT_LAUNCH(launch_feature_resolve)(const FeatureResolveArgs& a, hipStream_t st) {
-    if (a.np) hipLaunchKernelGGL(PTK_IMPL::k_feature_resolve, dim3((a.np + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
-}
-}  // namespace ptk
-
-// ------------------------------------------------------------------ thin-lens camera (pt_render_lens_device; rule: pt_lens.h)
-// lens_ray: camera_ray with the lens point -- the same block of draws, the same statements up to `dir`, then pt_lens.h.  The
-// path kernels do not know the lens: k_lens_paths writes the rays as path states in the queue form, and a launch with
-// src_mode = 1 takes them up as it takes up handed-over paths (what pt_ray_color does with rays of the caller's).
-//   k_lens_paths          state i = s_local * np + tile pixel (the pixel fastest): the four planes store_state writes, depth 0,
-//                         throughput 1, pdf_prev 0, no radiance, eta 1; one 16-byte store per lane and plane
-//   k_lens_feature_rays   k_feature_rays with lens rays
-//   k_debug_lens_rays     words[4] = x, y, sample, - -> out[8] = o'3, d'3, dx, dy
-namespace PTK_IMPL {
-struct LensMath {
-    static PT_DEV float div(float a, float b) { return pt_div(a, b); }
-    static PT_DEV void sincos2pi(float u, float& s, float& c) { PTD_NS::sincos2pi(u, s, c); }
-};
-PT_DEV void lens_ray(const CameraF& cam, const LensF& lens, uint32_t sample, uint32_t px, uint32_t py, f3& o, f3& d, float& dx, float& dy) {
-    uint32_t dc[4];
-    philox4x32_draw(px, py, sample, kDepthCamera, BLK_SURFACE, 0u, dc);
-    float ox = u01(dc[0]), oy = u01(dc[1]);
-    float wm1 = (float)(cam.width - 1u), hm1 = (float)(cam.height - 1u);
-    asm volatile("" : "+v"(wm1), "+v"(hm1));
-    float u = pt_div((float)px + ox, wm1);
-    float v = pt_div((float)(cam.height - 1u - py) + oy, hm1);
-    const f3 cam_o = mk(cam.origin[0], cam.origin[1], cam.origin[2]);
-    f3 dir = mk(cam.lower_left[0], cam.lower_left[1], cam.lower_left[2]) +
-             mk(cam.horizontal[0], cam.horizontal[1], cam.horizontal[2]) * u +
-             mk(cam.vertical[0], cam.vertical[1], cam.vertical[2]) * v - cam_o;
-    ptlens::disc<LensMath>(u01(dc[2]), u01(dc[3]), &dx, &dy);
-    ptlens::Setup L;
-    for (int k = 0; k < 3; ++k) { L.lu[k] = lens.lu[k]; L.lv[k] = lens.lv[k]; }
-    L.inv_phi = lens.inv_phi;
-    const float o3[3] = {cam_o.x, cam_o.y, cam_o.z}, d3[3] = {dir.x, dir.y, dir.z};
-    float oo[3], dd[3];
-    ptlens::ray(L, o3, d3, dx, dy, oo, dd);
-    o = mk(oo[0], oo[1], oo[2]);
-    d = normalize(mk(dd[0], dd[1], dd[2]));
-}
-__global__ void __launch_bounds__(kBlock) k_lens_paths(LensPathsArgs a) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    uint32_t s_local, pix, yl, px;
-    divmod_magic(i, a.np, a.np_magic, s_local, pix);
-    divmod_magic(pix, a.cam.width, a.w_magic, yl, px);
-    f3 o, d; float dx, dy;
-    lens_ray(a.cam, a.lens, a.s_base + s_local, px, image_row(a.tile, yl), o, d, dx, dy);
-    a.q[0][i] = make_float4(o.x, o.y, o.z, d.x);
-    a.q[1][i] = make_float4(d.y, d.z, __uint_as_float((yl << 16) | px), __uint_as_float(s_local << 16));
-    a.q[2][i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-    a.q[3][i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-}
-__global__ void __launch_bounds__(kBlock) k_lens_feature_rays(CameraF cam, LensF lens, uint32_t s_base, uint32_t nb, float* __restrict__ rays6) {
-    const uint32_t np = cam.width * cam.height;
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= nb * np) return;
-    const uint32_t s = i / np, p = i - s * np;
-    const uint32_t y = p / cam.width, x = p - y * cam.width;
-    f3 o, d; float dx, dy;
-    lens_ray(cam, lens, s_base + s, x, y, o, d, dx, dy);
-    float* r = rays6 + 6 * (size_t)i;
-    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
-}
-__global__ void __launch_bounds__(kBlock) k_debug_lens_rays(CameraF cam, LensF lens, const uint32_t* __restrict__ words, uint32_t n,
-                                                            float* __restrict__ out8) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t* w = words + 4 * (size_t)i;
-    f3 o, d; float dx, dy;
-    lens_ray(cam, lens, w[2], w[0], w[1], o, d, dx, dy);
-    float* out = out8 + 8 * (size_t)i;
-    out[0] = o.x; out[1] = o.y; out[2] = o.z; out[3] = d.x; out[4] = d.y; out[5] = d.z; out[6] = dx; out[7] = dy;
-}
-}  // namespace PTK_IMPL
-namespace ptk {
-void PT_LAUNCH(launch_lens_paths)(const LensPathsArgs& a, hipStream_t st) {
-    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_lens_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
-}
-void PT_LAUNCH(launch_lens_feature_rays)(const CameraF& cam, const LensF& lens, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st) {
-    const uint32_t n = nb * cam.width * cam.height;
-    if (n) hipLaunchKernelGGL(PTK_IMPL::k_lens_feature_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, lens, s_base, nb, rays6);
-}
-void PT_LAUNCH(launch_debug_lens_rays)(const CameraF& cam, const LensF& lens, const uint32_t* words, uint32_t n, float* out8, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(PTK_IMPL::k_debug_lens_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, lens, words, n, out8);
-}
-}  // namespace ptk
-
-// ------------------------------------------------------------------ projections and caller rays (pt_render_projection_device,
-// pt_render_rays_device; rule: pt_projection.h)
-// projection_ray: camera_ray's block of draws and its statements up to `dir` (ptproj::screen), then the kind's rule.  The kind is
-// a kernel argument, the same for every lane: each kernel branches on it once, around the whole per-lane rule (KIND is a template
-// argument of everything below the branch).  As with the lens, the path kernels do not know the projection: the rays reach them
-// as path states in the queue form.
-//   k_projection_paths          k_lens_paths with projection rays: state i = s_local * np + tile pixel, one 16-byte store per
-//                               lane and plane
-//   k_projection_feature_rays   k_feature_rays with projection rays
-//   k_debug_projection_rays     words[4] = x, y, sample, - -> out[8] = o3, d3, a, b
-//   k_ray_paths                 the caller's rays, float[n][6] in state order (sample-major, the pixel fastest), as path states;
-//                               the directions are taken as given (not normalised); weights3 (float[n][3], or null = 1): the
-//                               initial throughput.  A lane reads its 24 bytes as three 8-byte words (rays6 is 8-byte aligned).
-namespace PTK_IMPL {
-struct ProjMath {
-    static PT_DEV float div(float a, float b) { return pt_div(a, b); }
-    static PT_DEV float sqrt(float x) { return pt_sqrt(x); }
-    static PT_DEV void sincos2pi(float u, float& s, float& c) { PTD_NS::sincos2pi(u, s, c); }
-};
-template <int KIND>
-PT_DEV void projection_ray(const CameraF& cam, const ProjF& pj, uint32_t sample, uint32_t px, uint32_t py, f3& o, f3& d, float& a, float& b) {
-    uint32_t dc[4];
-    philox4x32_draw(px, py, sample, kDepthCamera, BLK_SURFACE, 0u, dc);
-    float u, v, dir[3];
-    ptproj::screen<ProjMath>(cam.origin, cam.lower_left, cam.horizontal, cam.vertical, cam.width, cam.height, px, py, u01(dc[0]), u01(dc[1]),
-                             &u, &v, dir);
-    ptproj::Setup P;
-    for (int k = 0; k < 3; ++k) { P.u[k] = pj.u[k]; P.v[k] = pj.v[k]; P.w[k] = pj.w[k]; P.c[k] = pj.c[k]; }
-    P.aspect = pj.aspect; P.fov720 = pj.fov720;
-    float oo[3], dd[3];
-    const bool unnormalised = ptproj::ray<ProjMath, KIND>(P, cam.origin, u, v, dir, oo, dd, &a, &b);
-    o = mk(oo[0], oo[1], oo[2]);
-    d = mk(dd[0], dd[1], dd[2]);
-    if (unnormalised) d = normalize(d);
-}
-template <int KIND>
-PT_DEV void projection_path(const ProjPathsArgs& a, uint32_t i) {
-    uint32_t s_local, pix, yl, px;
-    divmod_magic(i, a.np, a.np_magic, s_local, pix);
-    divmod_magic(pix, a.cam.width, a.w_magic, yl, px);
-    f3 o, d; float sa, sb;
-    projection_ray<KIND>(a.cam, a.proj, a.s_base + s_local, px, image_row(a.tile, yl), o, d, sa, sb);
-    a.q[0][i] = make_float4(o.x, o.y, o.z, d.x);
-    a.q[1][i] = make_float4(d.y, d.z, __uint_as_float((yl << 16) | px), __uint_as_float(s_local << 16));
-    a.q[2][i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-    a.q[3][i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-}
-__global__ void __launch_bounds__(kBlock) k_projection_paths(ProjPathsArgs a) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    switch (a.proj.kind) {
-    case ptproj::kOrthographic: projection_path<ptproj::kOrthographic>(a, i); break;
-    case ptproj::kFisheye: projection_path<ptproj::kFisheye>(a, i); break;
-    case ptproj::kEquirect: projection_path<ptproj::kEquirect>(a, i); break;
-    default: projection_path<ptproj::kPerspective>(a, i); break;
-    }
-}
-template <int KIND>
-PT_DEV void projection_feature_ray(const CameraF& cam, const ProjF& pj, uint32_t s_base, uint32_t i, float* __restrict__ rays6) {
-    const uint32_t np = cam.width * cam.height;
-    const uint32_t s = i / np, p = i - s * np;
-    const uint32_t y = p / cam.width, x = p - y * cam.width;
-    f3 o, d; float sa, sb;
-    projection_ray<KIND>(cam, pj, s_base + s, x, y, o, d, sa, sb);
-    float* r = rays6 + 6 * (size_t)i;
-    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
-}
-__global__ void __launch_bounds__(kBlock) k_projection_feature_rays(CameraF cam, ProjF pj, uint32_t s_base, uint32_t nb, float* __restrict__ rays6) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= nb * cam.width * cam.height) return;
-    switch (pj.kind) {
-    case ptproj::kOrthographic: projection_feature_ray<ptproj::kOrthographic>(cam, pj, s_base, i, rays6); break;
-    case ptproj::kFisheye: projection_feature_ray<ptproj::kFisheye>(cam, pj, s_base, i, rays6); break;
-    case ptproj::kEquirect: projection_feature_ray<ptproj::kEquirect>(cam, pj, s_base, i, rays6); break;
-    default: projection_feature_ray<ptproj::kPerspective>(cam, pj, s_base, i, rays6); break;
-    }
-}
-template <int KIND>
-PT_DEV void debug_projection_ray(const CameraF& cam, const ProjF& pj, const uint32_t* __restrict__ w, float* __restrict__ out) {
-    f3 o, d; float sa, sb;
-    projection_ray<KIND>(cam, pj, w[2], w[0], w[1], o, d, sa, sb);
-    out[0] = o.x; out[1] = o.y; out[2] = o.z; out[3] = d.x; out[4] = d.y; out[5] = d.z; out[6] = sa; out[7] = sb;
-}
-__global__ void __launch_bounds__(kBlock) k_debug_projection_rays(CameraF cam, ProjF pj, const uint32_t* __restrict__ words, uint32_t n,
-                                                                  float* __restrict__ out8) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t* w = words + 4 * (size_t)i;
-    float* out = out8 + 8 * (size_t)i;
-    switch (pj.kind) {
-    case ptproj::kOrthographic: debug_projection_ray<ptproj::kOrthographic>(cam, pj, w, out); break;
-    case ptproj::kFisheye: debug_projection_ray<ptproj::kFisheye>(cam, pj, w, out); break;
-    case ptproj::kEquirect: debug_projection_ray<ptproj::kEquirect>(cam, pj, w, out); break;
-    default: debug_projection_ray<ptproj::kPerspective>(cam, pj, w, out); break;
-    }
-}
-__global__ void __launch_bounds__(kBlock) k_ray_paths(RayPathsArgs a) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    uint32_t s_local, pix, yl, px;
-    divmod_magic(i, a.np, a.np_magic, s_local, pix);
-    divmod_magic(pix, a.width, a.w_magic, yl, px);
-    const float2* __restrict__ r = reinterpret_cast<const float2*>(a.rays6) + 3 * (size_t)i;
-    const float2 r0 = r[0], r1 = r[1], r2 = r[2];
-    float wx = 1.0f, wy = 1.0f, wz = 1.0f;
-    if (a.weights3) {
-        const float* __restrict__ w = a.weights3 + 3 * (size_t)i;
-        wx = w[0]; wy = w[1]; wz = w[2];
-    }
-    a.q[0][i] = make_float4(r0.x, r0.y, r1.x, r1.y);
-    a.q[1][i] = make_float4(r2.x, r2.y, __uint_as_float((yl << 16) | px), __uint_as_float(s_local << 16));
-    a.q[2][i] = make_float4(wx, wy, wz, 0.0f);
-    a.q[3][i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-}
-}  // namespace PTK_IMPL
-namespace ptk {
-void PT_LAUNCH(launch_projection_paths)(const ProjPathsArgs& a, hipStream_t st) {
-    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_projection_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
-}
-void PT_LAUNCH(launch_projection_feature_rays)(const CameraF& cam, const ProjF& pj, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st) {
-    const uint32_t n = nb * cam.width * cam.height;
-    if (n) hipLaunchKernelGGL(PTK_IMPL::k_projection_feature_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, pj, s_base, nb, rays6);
-}
-void PT_LAUNCH(launch_debug_projection_rays)(const CameraF& cam, const ProjF& pj, const uint32_t* words, uint32_t n, float* out8, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(PTK_IMPL::k_debug_projection_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cam, pj, words, n, out8);
-}
-void PT_LAUNCH(launch_ray_paths)(const RayPathsArgs& a, hipStream_t st) {
-    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_ray_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
-}
-}  // namespace ptk
-
-// ------------------------------------------------------------------ light baking (pt_bake_lightmap_device, pt_bake_probes_device;
-// rule: pt_bake.h)
-// bake_ray: the ray of film position (x, y) -- texel (x, y), or direction x of probe y -- and sample `sample` by the rule, in this
-// unit's arithmetic (BakeMath: pt_device.h's own u01, sincos2pi, normalize and cosine_sample).  The kind is a kernel argument, the
-// same for every lane: each kernel branches on it once, around the whole per-lane rule.  A texel lane reads its record's 24 bytes
-// as three 8-byte words (the plane is 8-byte aligned) and draws camera_ray's block for its key.
-//   k_bake_paths        k_projection_paths with the bake's rays: state i = s_local * np + film position, one 16-byte store per
-//                       lane and plane; the throughput of an empty texel's ray is 0
-//   k_debug_bake_rays   words[4] = x, y, sample, - -> out[6] = o3, d3
-namespace PTK_IMPL {
-struct BakeMath {
-    static PT_DEV float u01(uint32_t w) { return PTD_NS::u01(w); }
-    static PT_DEV float sqrt(float x) { return pt_sqrt(x); }
-    static PT_DEV void sincos2pi(float u, float& s, float& c) { PTD_NS::sincos2pi(u, s, c); }
-    static PT_DEV void normalize(float v[3]) {
-        const f3 r = PTD_NS::normalize(mk(v[0], v[1], v[2]));
-        v[0] = r.x; v[1] = r.y; v[2] = r.z;
-    }
-    static PT_DEV void cosine_sample(const float n[3], float r1, float r2, float d[3]) {
-        const f3 r = PTD_NS::cosine_sample(mk(n[0], n[1], n[2]), r1, r2);
-        d[0] = r.x; d[1] = r.y; d[2] = r.z;
-    }
-};
-template <int KIND>
-PT_DEV void bake_ray(const float* __restrict__ data, uint32_t width, uint32_t x, uint32_t y, uint32_t sample, float o[3], float d[3], float& tp) {
-    if (KIND == ptbake::kTexel) {
-        const float2* __restrict__ r = reinterpret_cast<const float2*>(data) + 3 * ((size_t)y * width + x);
-        const float2 r0 = r[0], r1 = r[1], r2 = r[2];
-        const float t[6] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y};
-        uint32_t dc[4];
-        philox4x32_draw(x, y, sample, kDepthCamera, BLK_SURFACE, 0u, dc);
-        ptbake::texel_ray<BakeMath>(t, dc[0], dc[1], o, d, &tp);
-    } else {
-        const float* __restrict__ p = data + 3 * (size_t)y;
-        o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
-        ptbake::probe_dir<BakeMath>(x, width, d);
-        tp = 1.0f;
-    }
-}
-template <int KIND>
-PT_DEV void bake_path(const BakePathsArgs& a, uint32_t i) {
-    uint32_t s_local, pix, yl, px;
-    divmod_magic(i, a.np, a.np_magic, s_local, pix);
-    divmod_magic(pix, a.width, a.w_magic, yl, px);
-    float o[3], d[3], tp;
-    bake_ray<KIND>(a.data, a.width, px, yl, a.s_base + s_local, o, d, tp);      // the whole image: tile row = image row
-    a.q[0][i] = make_float4(o[0], o[1], o[2], d[0]);
-    a.q[1][i] = make_float4(d[1], d[2], __uint_as_float((yl << 16) | px), __uint_as_float(s_local << 16));
-    a.q[2][i] = make_float4(tp, tp, tp, 0.0f);
-    a.q[3][i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-}
-__global__ void __launch_bounds__(kBlock) k_bake_paths(BakePathsArgs a) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    if (a.kind == (uint32_t)ptbake::kTexel) bake_path<ptbake::kTexel>(a, i);
-    else bake_path<ptbake::kProbe>(a, i);
-}
-__global__ void __launch_bounds__(kBlock) k_debug_bake_rays(const float* __restrict__ data, uint32_t kind, uint32_t width,
-                                                            const uint32_t* __restrict__ words, uint32_t n, float* __restrict__ out6) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t* w = words + 4 * (size_t)i;
-    float o[3], d[3], tp;
-    if (kind == (uint32_t)ptbake::kTexel) bake_ray<ptbake::kTexel>(data, width, w[0], w[1], w[2], o, d, tp);
-    else bake_ray<ptbake::kProbe>(data, width, w[0], w[1], w[2], o, d, tp);
-    float* out = out6 + 6 * (size_t)i;
-    out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = d[0]; out[4] = d[1]; out[5] = d[2];
-}
-}  // namespace PTK_IMPL
-namespace ptk {
-void PT_LAUNCH(launch_bake_paths)(const BakePathsArgs& a, hipStream_t st) {
-    if (a.n) hipLaunchKernelGGL(PTK_IMPL::k_bake_paths, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
-}
-void PT_LAUNCH(launch_debug_bake_rays)(const float* data, uint32_t kind, uint32_t width, const uint32_t* words, uint32_t n, float* out6,
-                                       hipStream_t st) {
-    if (n) hipLaunchKernelGGL(PTK_IMPL::k_debug_bake_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, data, kind, width, words, n, out6);
 }
 }  // namespace ptk

@@ -3,7 +3,9 @@
 // The kernels are built as one translation unit per group, each with the compiler options its kernels measured best with
 // (Makefile: KFLAGS_*; profiles/r05/ab_noslp.txt, ab_bvh_slp.txt, ab_compiler_flags2.txt), and each but the last once per
 // arithmetic mode (PT_MATH_EXACT, pt_device.h):
-//   pt_kernels_main.hip   k_paths, k_paths_regen, the debug / setup / feature kernels     -fno-slp-vectorize (C2 launch -2.6 %)
+//   pt_kernels_main.hip   k_paths, k_paths_regen, the debug / setup kernels               -fno-slp-vectorize (C2 launch -2.6 %)
+//   pt_kernels_rays.hip   the ray sources beside the pinhole camera (k_source_paths,      the main unit's options
+//                         k_source_feature_rays, k_debug_source_rays), k_feature_resolve
 //   pt_kernels_split.hip  k_paths_regen_split                                             -fno-slp-vectorize, scheduling strategy max-ilp (C1 -1.2 %; C2 would pay 1.6 %)
 //   pt_kernels_bvh.hip    the BVH form (k_paths_bvh, k_debug_hit_bvh)                     with the SLP vectoriser (its 4-wide box tests pack well: +2 % without)
 //   pt_kernels_film.hip   the kernels on the film and the device-side BVH refit / builds  the main unit's options

@@ -1,4 +1,4 @@
-// pt_lens.cpp -- the host side of the thin-lens camera that is not the render driver's (pt_api.cpp: render_lens_impl): the checks
+// pt_lens.cpp -- the host side of the thin-lens camera that is not the render driver's (pt_api.cpp: render_source_impl): the checks
 // and the device's words (pt_lens.h), the defaults, the debug entries, and the entries of the lens forms pt_denoise.cpp holds.
 #include "pt_entry.h"
 #include "pt_lens.h"
@@ -39,14 +39,14 @@ void pt_default_lens(PtLens* out) {
 int pt_render_features_lens_device(PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t n_samples,
                                    float* d_features) {
     if (!lens) return fail(PT_ERR_INVALID_ARG, "pt_render_features_lens_device: null argument");
-    return features_lens_device("pt_render_features_lens_device", c, cam, lens, prm, n_samples, d_features);
+    return features_source_device("pt_render_features_lens_device", c, cam, {lens, nullptr}, prm, n_samples, d_features);
 }
 
 int pt_render_lens_denoised(PtContext* c, const PtCamera* cam, const PtLens* lens, const PtRenderParams* prm, uint32_t feature_samples,
                             const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy, float* out_features) {
     if (!lens) return fail(PT_ERR_INVALID_ARG, "pt_render_lens_denoised: null argument");
-    return render_lens_denoised_host("pt_render_lens_denoised", c, cam, lens, prm, feature_samples, dn, out_linear, out_rgba, out_noisy,
-                                     out_features);
+    return render_source_denoised_host("pt_render_lens_denoised", c, cam, {lens, nullptr}, prm, feature_samples, dn, out_linear, out_rgba,
+                                       out_noisy, out_features);
 }
 
 int pt_debug_lens_setup(const PtCamera* cam, const PtLens* lens, float* out7) {
@@ -64,19 +64,11 @@ int pt_debug_lens_rays(PtContext* c, const PtCamera* cam, const PtLens* lens, co
     ptk::LensF l;
     int rc;
     if ((rc = lens_setup("pt_debug_lens_rays", cam, lens, &l)) || (rc = check_camera_size(cam))) return rc;
-    if (n == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->fn_out.ensure(8 * (size_t)n)) || (rc = c->fn_words.ensure(4 * (size_t)n))) return rc;
-    std::vector<uint32_t> w(4 * (size_t)n, 0u);
-    for (size_t i = 0; i < n; ++i) { w[4 * i] = xys[3 * i]; w[4 * i + 1] = xys[3 * i + 1]; w[4 * i + 2] = xys[3 * i + 2]; }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->fn_words.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (exact_math) ptk::launch_debug_lens_rays_exact(camera_f32(cam), l, c->fn_words.p, n, c->fn_out.p, c->stream);
-    else ptk::launch_debug_lens_rays_fast(camera_f32(cam), l, c->fn_words.p, n, c->fn_out.p, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out8, c->fn_out.p, 8 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    ptk::RaySourceF s{};
+    s.tag = ptk::kSrcLens;
+    s.cam = camera_f32(cam);
+    s.lens = l;
+    return debug_source_rays(c, s, xys, n, exact_math, 8, out8);
 }
 
 }  // extern "C"

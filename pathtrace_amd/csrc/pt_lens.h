@@ -1,5 +1,5 @@
-// pt_lens.h -- the thin-lens camera (pt_render_lens_device), written once for the kernels (k_lens_paths,
-// k_lens_feature_rays, k_debug_lens_rays in pt_kernels_main.hip), the host entries (pt_lens.cpp) and the host compilers of the
+// pt_lens.h -- the thin-lens camera (pt_render_lens_device), written once for the kernels (LensSource
+// under the three forms of pt_kernels_rays.hip), the host entries (pt_lens.cpp) and the host compilers of the
 // tests (tests/tools/lens_san.cpp).  Build with -ffp-contract=off: no compiler fuses what the rule writes apart.
 //
 // Host side, f64 (setup): from the PtCamera's cached fields

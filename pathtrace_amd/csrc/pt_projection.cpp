@@ -1,5 +1,5 @@
 // pt_projection.cpp -- the host side of the projections and the caller's rays that is not the render driver's
-// (pt_api.cpp: render_injected_impl and its users): the checks and the device's words (pt_projection.h), the defaults, the rule
+// (pt_api.cpp: render_injected_impl and render_source_impl): the checks and the device's words (pt_projection.h), the defaults, the rule
 // on the CPU, the debug entry, and the entries of the projection forms pt_denoise.cpp holds.  The entries' rule and the host
 // render's staging: pt_entry.h.
 #include "pt_entry.h"
@@ -80,7 +80,7 @@ void pt_default_projection(PtProjection* out) {
 
 int pt_render_projection_device(PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm, float* d_linear,
                                 uint8_t* d_rgba) {
-    return render_projection_impl("pt_render_projection_device", c, cam, proj, prm, d_linear, d_rgba);
+    return render_source_impl("pt_render_projection_device", c, cam, {nullptr, proj}, prm, d_linear, d_rgba);
 }
 
 int pt_render_projection_host(PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm, float* out_linear,
@@ -89,35 +89,43 @@ int pt_render_projection_host(PtContext* c, const PtCamera* cam, const PtProject
     ptk::ProjF checked;
     if (int bad = projection_setup("pt_render_projection_host", cam, proj, &checked)) return bad;      // before the staging is touched
     const size_t np = (size_t)pt_tile_rows(cam->height, prm->band_rows, prm->band_index, prm->band_count ? prm->band_count : 1) * cam->width;
-    if (np == 0) return render_projection_impl("pt_render_projection_host", c, cam, proj, prm, nullptr, nullptr);   // validates, renders nothing
+    if (np == 0) return render_source_impl("pt_render_projection_host", c, cam, {nullptr, proj}, prm, nullptr, nullptr);   // validates, renders nothing
     HIP_TRY(hipSetDevice(c->device));
     return render_staged(c, np * 3, out_rgba ? np * 4 : 0, [&](float* d_linear, uint8_t* d_rgba) {
-        return render_projection_impl("pt_render_projection_host", c, cam, proj, prm, d_linear, d_rgba);
+        return render_source_impl("pt_render_projection_host", c, cam, {nullptr, proj}, prm, d_linear, d_rgba);
     }, [&] { return copy_back({{out_linear, c->host_lin.p, np * 3 * sizeof(float)}, {out_rgba, c->host_rgba.p, np * 4}}); });
 }
 
 int pt_render_features_projection_device(PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
                                          uint32_t n_samples, float* d_features) {
     if (!proj) return fail(PT_ERR_INVALID_ARG, "pt_render_features_projection_device: null argument");
-    return features_projection_device("pt_render_features_projection_device", c, cam, proj, prm, n_samples, d_features);
+    return features_source_device("pt_render_features_projection_device", c, cam, {nullptr, proj}, prm, n_samples, d_features);
 }
 
 int pt_render_projection_denoised(PtContext* c, const PtCamera* cam, const PtProjection* proj, const PtRenderParams* prm,
                                   uint32_t feature_samples, const PtDenoise* dn, float* out_linear, uint8_t* out_rgba, float* out_noisy,
                                   float* out_features) {
     if (!proj) return fail(PT_ERR_INVALID_ARG, "pt_render_projection_denoised: null argument");
-    return render_projection_denoised_host("pt_render_projection_denoised", c, cam, proj, prm, feature_samples, dn, out_linear, out_rgba,
-                                           out_noisy, out_features);
+    return render_source_denoised_host("pt_render_projection_denoised", c, cam, {nullptr, proj}, prm, feature_samples, dn, out_linear, out_rgba,
+                                       out_noisy, out_features);
 }
 
 int pt_render_rays_device(PtContext* c, uint32_t width, uint32_t height, const PtRenderParams* prm, const float* d_rays6, const float* d_weights3,
                           float* d_linear, uint8_t* d_rgba) {
+    const char* const who = "pt_render_rays_device";
+    if (!c || !prm || !d_rays6) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
+    if ((uintptr_t)d_rays6 % 8u) return fail(PT_ERR_INVALID_ARG, "%s: d_rays6 must be 8-byte aligned", who);
+    if ((uintptr_t)d_weights3 % 4u) return fail(PT_ERR_INVALID_ARG, "%s: d_weights3 must be 4-byte aligned", who);
     // a camera for the tile's geometry only (no camera ray is generated): the image size, and a frame nothing reads
     PtCamera cam{};
     cam.lower_left[0] = cam.lower_left[1] = cam.lower_left[2] = -1.0;
     cam.horizontal[0] = 2.0; cam.vertical[1] = 2.0;
     cam.width = width; cam.height = height;
-    return render_rays_impl("pt_render_rays_device", c, &cam, prm, d_rays6, d_weights3, d_linear, d_rgba);
+    ptk::RaySourceF s{};
+    s.tag = ptk::kSrcRays;
+    s.cam = camera_f32(&cam);
+    s.rays.rays6 = d_rays6; s.rays.weights3 = d_weights3;
+    return render_injected_impl(who, c, &cam, prm, s, d_linear, d_rgba);
 }
 
 int pt_projection_setup_host(const PtCamera* cam, const PtProjection* proj, float* out11) {
@@ -157,19 +165,11 @@ int pt_debug_projection_rays(PtContext* c, const PtCamera* cam, const PtProjecti
     ptk::ProjF p;
     int rc;
     if ((rc = projection_setup("pt_debug_projection_rays", cam, proj, &p)) || (rc = check_camera_size(cam))) return rc;
-    if (n == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->fn_out.ensure(8 * (size_t)n)) || (rc = c->fn_words.ensure(4 * (size_t)n))) return rc;
-    std::vector<uint32_t> w(4 * (size_t)n, 0u);
-    for (size_t i = 0; i < n; ++i) { w[4 * i] = xys[3 * i]; w[4 * i + 1] = xys[3 * i + 1]; w[4 * i + 2] = xys[3 * i + 2]; }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->fn_words.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (exact_math) ptk::launch_debug_projection_rays_exact(camera_f32(cam), p, c->fn_words.p, n, c->fn_out.p, c->stream);
-    else ptk::launch_debug_projection_rays_fast(camera_f32(cam), p, c->fn_words.p, n, c->fn_out.p, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out8, c->fn_out.p, 8 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    ptk::RaySourceF s{};
+    s.tag = ptk::kSrcProjection;
+    s.cam = camera_f32(cam);
+    s.proj = p;
+    return debug_source_rays(c, s, xys, n, exact_math, 8, out8);
 }
 
 }  // extern "C"

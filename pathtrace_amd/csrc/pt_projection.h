@@ -1,5 +1,5 @@
 // pt_projection.h -- the camera projections beyond the pinhole (pt_render_projection_device), written once for the
-// kernels (k_projection_paths, k_projection_feature_rays, k_debug_projection_rays in pt_kernels_main.hip), the host entries
+// kernels (ProjectionSource under the three forms of pt_kernels_rays.hip), the host entries
 // (pt_projection.cpp) and the host compilers of the tests (tests/tools/projection_san.cpp).  Build with -ffp-contract=off: no
 // compiler fuses what the rule writes apart.
 //

@@ -30,7 +30,7 @@ def _shipped_path_kernels(pt, tmp_path):
     # --offloading writes one file per bundle entry next to its (relative) input: run it in tmp_path
     subprocess.run([objdump, "--offloading", so.name], cwd=tmp_path, check=True, capture_output=True)
     objs = sorted(p for p in os.listdir(tmp_path) if p.endswith("gfx950"))
-    assert len(objs) == 7, objs             # the kernel units: main, split, BVH, each exact and fast, and film (fast only)
+    assert len(objs) == 9, objs             # the kernel units: main, rays, split, BVH, each exact and fast, and film (fast only)
     found = []
     for o in objs:
         out = subprocess.run([readelf, "--syms", "--demangle", "-W", o], cwd=tmp_path, check=True, capture_output=True,

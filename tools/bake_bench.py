@@ -2,7 +2,7 @@
 fed the bake's own rays, alternating in one process: a 256^2 x 64 spp lightmap of the floor of World::new() (builtin scene 1) and
 4096 probes x 256 rays in its box by default.  Per form the wall time of `--runs` calls between device events (ms, all of them,
 the median and the spread max - min).  A bake enqueues the path launches of the render of its rays; what differs is the fill
-(k_bake_paths computes the rays, k_ray_paths reads them) and what follows the resolve (k_bake_mask; k_probe_sh, which is also
+(k_source_paths<BakeSource> computes the rays, k_source_paths<CallerSource> reads them) and what follows the resolve (k_bake_mask; k_probe_sh, which is also
 timed alone through pt_sh_project_device).  The kernels' own durations: run this tool under a kernel trace.  One JSON line."""
 import argparse
 import ctypes as C

@@ -1,7 +1,7 @@
 """Thin-lens render (pt_render_lens_device) beside the pinhole render of the same job, alternating in one process:
 C2 at 1024^2 x 16 spp by default, aperture 0.2.  Per form the wall time of `--runs` renders between device events (ms, all of
 them and the median): the pinhole render in the default (regenerating) form, the pinhole render in the queue form
-(level0_form = 1) and the lens render, which takes the queue form's kernels.  k_lens_paths' own time: run this tool under a
+(level0_form = 1) and the lens render, which takes the queue form's kernels.  k_source_paths<LensSource>'s own time: run this tool under a
 kernel trace.  One JSON line."""
 import argparse
 import json

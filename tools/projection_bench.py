@@ -3,8 +3,8 @@ lens render at aperture 0, alternating in one process: C2 at 1024^2 x 16 spp by 
 renders between device events (ms, all of them, the median and the spread max - min): the lens render, the projection render
 of every kind, and the render of caller rays (the pinhole's own, written once by the debug entry in chunks).  All of them
 enqueue the same path launches; what differs is the launch that writes the path states.  The fill kernels' own times
-(k_lens_paths, k_projection_paths, k_ray_paths): run this tool under a kernel trace; `bytes` below is what each of them moves
-per render (four 16-byte state planes written per path; k_ray_paths also reads 24 bytes per path), for bytes / s against the
+(k_source_paths<LensSource>, <ProjectionSource>, <CallerSource>): run this tool under a kernel trace; `bytes` below is what each of them moves
+per render (four 16-byte state planes written per path; the caller-ray instance also reads 24 bytes per path), for bytes / s against the
 HBM peak.  One JSON line."""
 import argparse
 import ctypes as C
@@ -77,7 +77,7 @@ def main():
                 times[name].append(round(t, 4))
     paths = a.size * a.size * a.spp
     out = {"scene": a.scene, "size": a.size, "spp": a.spp, "fov": a.fov, "runs": a.runs,
-           "fill_bytes": {"k_lens_paths": 64 * paths, "k_projection_paths": 64 * paths, "k_ray_paths": 88 * paths}}
+           "fill_bytes": {"k_source_paths<LensSource>": 64 * paths, "k_source_paths<ProjectionSource>": 64 * paths, "k_source_paths<CallerSource>": 88 * paths}}
     for k, v in times.items():
         out[k] = v
         out[k.replace("_ms", "_median_ms")] = round(statistics.median(v), 4)

@@ -8,7 +8,7 @@ exact = "--exact" in sys.argv
 extra = [a for a in sys.argv[1:] if a != "--exact"]
 # the kernel units of the library's build, compiled by the commands of the Makefile's own rules (make -n prints them): "... -c <unit> -o <object>"
 mode = "exact" if exact else "fast"
-objs = [f"pt_kernels_{u}_{mode}.o" for u in ("main", "split", "bvh")] + ([] if exact else ["pt_kernels_film.o"])
+objs = [f"pt_kernels_{u}_{mode}.o" for u in ("main", "rays", "split", "bvh")] + ([] if exact else ["pt_kernels_film.o"])
 cmds = subprocess.run(["make", "-n", "-B", "KDEFS=" + " ".join(extra)] + objs, cwd=CSRC, stdout=subprocess.PIPE, text=True, check=True).stdout
 out = ""
 for c in cmds.splitlines():
