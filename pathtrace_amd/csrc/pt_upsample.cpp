@@ -34,9 +34,13 @@ int check_planes(const char* who, uint32_t lo_width, uint32_t lo_height, uint32_
         return fail(PT_ERR_INVALID_ARG, "%s: the film buffers must be 4-byte aligned", who);
     int rc;
     if ((rc = check_size(who, lo_width, lo_height, width, height))) return rc;
-    const void* const in[3] = {f.lo_linear, f.lo_features, f.features};
-    for (const void* q : in)
-        if (f.out_linear == q || (f.out_rgba && f.out_rgba == q)) return fail(PT_ERR_INVALID_ARG, "%s: the output must not be an input", who);
+    // (byte ranges, not addresses: an output that starts inside an input is overwritten under the taps other threads still read)
+    const size_t np = (size_t)width * height, np_lo = (size_t)lo_width * lo_height;
+    const Range in[3] = {{f.lo_linear, 12 * np_lo}, {f.lo_features, 32 * np_lo}, {f.features, 32 * np}};
+    const Range out_lin{f.out_linear, 12 * np}, out_rgba{f.out_rgba, 4 * np};        // (a null out_rgba: no range)
+    for (const Range& q : in)
+        if (ranges_overlap(out_lin, q) || ranges_overlap(out_rgba, q)) return fail(PT_ERR_INVALID_ARG, "%s: the output must not be an input", who);
+    if (ranges_overlap(out_lin, out_rgba)) return fail(PT_ERR_INVALID_ARG, "%s: the two outputs must not share a byte", who);
     return check_upsample(who, up);
 }
 

@@ -21,16 +21,20 @@
 //    skipped.  Ties go to the first tap in the order of 2.
 // 5. Interpolation: u_q = c_q / max(albedo_q, 1e-3) per channel in f32 (the a-trous kernels' demodulation), then
 //      u = u_a + sum_q w_q (u_q - u_a) / (sum_q w_q + 1e-6),
-//    both sums over the taps in the order of 2, the quotient as a product with the reciprocal of (sum + 1e-6); these few
-//    operations in f64 from the f32 values, u rounded to f32.  No threshold and no branch on the sum: the value is continuous
-//    in the weights and falls back to the anchor when nothing agrees with p.  (Why f64: the anchor is the NEAREST tap of p's
+//    both sums over the taps with w_q > 0, in the order of 2, the quotient as a product with the reciprocal of (sum + 1e-6);
+//    these few operations in f64 from the f32 values, u rounded to f32.  A tap with w_q = 0 or w_q NaN (a NaN in its record or
+//    in p's) contributes nothing: its film value is not read, a NaN or an infinity included (0 x NaN would be NaN), as a tap
+//    with w = 0 of the a-trous filter is not read.  A non-finite anchor still makes its pixel non-finite.  No threshold and no
+//    branch on the sum: the value is continuous in the weights (a skipped term is +-0 on finite inputs: the same bits) and
+//    falls back to the anchor when nothing agrees with p.  (Why f64: the anchor is the NEAREST tap of p's
 //    class, not the heaviest.  Where its weight is small against the others' and its u_a large against the result -- a tap of
 //    albedo 0 behind a normal edge -- the f32 sum cancels u_a against -u_a and keeps only ulp(u_a) of the result: 4e-4
 //    relative on the crafted inputs of tests/upsample_ref.py.  A dozen f64 operations per pixel cost a streaming kernel nothing.)
 // 6. c' = u max(A, 1e-3); the RGBA8 word is c' through sqrt / clamp / `as u8` (ptone::transfer_sqrt: the steps of every render).
 //
-// Consequences (tests/test_upsample_cpu.py, tests/test_gpu_upsample.py): with w = W, h = H and F = f the output is
-// pt_denoise_device's with iterations = 0, bit for bit; a tap of another class never influences a pixel that has a tap of its own.
+// Consequences (tests/test_upsample_cpu.py, tests/test_gpu_upsample.py, tests/test_upsample_cases_cpu.py,
+// tests/test_gpu_upsample_cases.py): with w = W, h = H and F = f the output is pt_denoise_device's with iterations = 0, bit for
+// bit; a tap of another class never influences a pixel that has a tap of its own, whatever its film value holds.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -101,7 +105,7 @@ PT_AD_HD void pixel(const Shape& s, const float* lo_linear, const Rec* lo_feat, 
         }
     double wsum = 0.0, num[3] = {0.0, 0.0, 0.0};
     for (int k = 0; k < 4; ++k) {
-        if (!live[k]) continue;
+        if (!live[k] || !(wq[k] > 0.0f)) continue;          // w_q = 0 or NaN: the tap is not read, whatever its film value holds
         wsum += (double)wq[k];
         for (int ch = 0; ch < 3; ++ch) num[ch] += (double)wq[k] * ((double)u[k][ch] - (double)ua[ch]);
     }

@@ -54,9 +54,26 @@ def test_upsample_refuses_bad_arguments_without_a_device(pt, entry):
     for src in (0, 1, 2):
         _refused(pt, call(out=FAKE[src]), "must not be an input")
         _refused(pt, call(rgba=FAKE[src]), "must not be an input")
+    # byte ranges, not addresses: 4 x 4 low (film 192 B, records 512 B), 8 x 8 full (records 2048 B, film 768 B, RGBA8 256 B)
+    at = lambda p, off: C.c_void_p(p.value + off)
+    for src, size in ((0, 192), (1, 512), (2, 2048)):
+        _refused(pt, call(out=at(FAKE[src], 4)), "must not be an input")                  # starts 4 bytes into the input
+        _refused(pt, call(rgba=at(FAKE[src], 4)), "must not be an input")
+        _refused(pt, call(out=at(FAKE[src], 4 - 768)), "must not be an input")            # ends 4 bytes into it
+        _refused(pt, call(rgba=at(FAKE[src], 4 - 256)), "must not be an input")
+        _refused(pt, call(out=at(FAKE[src], size - 4)), "must not be an input")           # starts in its last word
+    for off in (0, 4, 768 - 256, 768 - 4, 4 - 256):
+        _refused(pt, call(rgba=at(FAKE[3], off)), "the two outputs must not share a byte")
+    _refused(pt, call(out=FAKE[0], rgba=FAKE[3]), "must not be an input")                 # (an input comes before the other output)
     for field in ("sigma_n", "sigma_d"):
         for bad in (-1.0, float("nan"), float("inf")):
             _refused(pt, call(up=pt.default_upsample(**{field: bad})), "finite and >= 0")
+    # ranges that only touch share no byte: accepted up to the null context (the host entry would go on to read them: device only)
+    touching = [dict(out=at(FAKE[0], 192)), dict(out=at(FAKE[1], 512)), dict(out=at(FAKE[2], 2048)), dict(out=at(FAKE[2], -768)),
+                dict(rgba=at(FAKE[0], -256)), dict(rgba=at(FAKE[3], 768)), dict(rgba=at(FAKE[3], -256)), dict(out=at(FAKE[4], 256))]
+    if entry == "pt_upsample_device":
+        for kw in touching:
+            _refused(pt, call(**kw), entry + ": null context")
     if entry == "pt_upsample_device":      # zero sigmas, equal sizes, the least image and no RGBA8 plane are arguments like any other
         for kw in (dict(up=pt.default_upsample(sigma_n=0.0, sigma_d=0.0)), dict(lo=(8, 8)), dict(lo=(2, 2), full=(2, 2)), dict(rgba=None)):
             _refused(pt, call(**kw), entry + ": null context")
