@@ -2,18 +2,26 @@
 // (World::bake_probe_grid), then a frame is shaded from it for the price of a first-hit pass (World::render_probe_lit,
 // pt_render_probe_lit_host), beside a path-traced frame of the same camera.
 //
-//   ./probe_preview [nx [ny [nz [spp [out_prefix]]]]]        defaults: 6 6 6 16 probe_preview
-// writes <prefix>_probe_lit.ppm and <prefix>_path_traced.ppm.  The probe-lit frame is biased by construction: light leaks through
-// thin walls (the probes carry no visibility) and mirrors are shaded as diffuse surfaces of their colour.
+//   ./probe_preview [--visibility[=T]] [nx [ny [nz [spp [out_prefix]]]]]        defaults: 6 6 6 16 probe_preview
+// writes <prefix>_probe_lit.ppm and <prefix>_path_traced.ppm.  The probe-lit frame is biased by construction: mirrors are shaded as
+// diffuse surfaces of their colour, and without --visibility light leaks through thin walls.  --visibility[=T] (T in 2 .. 16, default
+// 8) bakes the probes' distance-moment maps too (World::bake_probe_visibility) and shades with the visibility term
+// (World::render_probe_lit_visibility).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "../pathtrace_amd/host/pathtrace.hpp"
 
 using namespace pathtrace;
 
 int main(int argc, char** argv) {
+    uint32_t resolution = 0;                      // 0: no visibility term
+    if (argc > 1 && std::strncmp(argv[1], "--visibility", 12) == 0) {
+        resolution = argv[1][12] == '=' ? (uint32_t)std::atoi(argv[1] + 13) : 8u;
+        --argc; ++argv;
+    }
     uint32_t counts[3] = {6, 6, 6};
     for (int a = 0; a < 3; ++a)
         if (argc > 1 + a) counts[a] = (uint32_t)std::atoi(argv[1 + a]);
@@ -47,7 +55,15 @@ int main(int argc, char** argv) {
         pt_default_probe_shade(&shade);
         shade.normal_bias = 0.02f;
         shade.weight = PT_PROBE_WEIGHT_FACING;
-        world.render_probe_lit(grid, sh, &shade, 1, &traced);
+        if (resolution) {
+            PtProbeVisibility vis{};
+            pt_default_probe_visibility(&grid, &vis);
+            vis.resolution = resolution;
+            const std::vector<float> maps = world.bake_probe_visibility(grid, 256, vis);
+            world.render_probe_lit_visibility(grid, sh, maps, vis, &shade, 1, &traced);
+        } else {
+            world.render_probe_lit(grid, sh, &shade, 1, &traced);
+        }
         world.write_ppm(prefix + "_probe_lit.ppm");
         std::printf("baked %u x %u x %u probes (256 rays x %u spp each); wrote %s_probe_lit.ppm and %s_path_traced.ppm (%u x %u)\n", counts[0], counts[1],
                     counts[2], spp, prefix.c_str(), prefix.c_str(), W, H);

@@ -188,6 +188,15 @@ class PtProbeShade(C.Structure):
 PT_PROBE_WEIGHT_TRILINEAR, PT_PROBE_WEIGHT_FACING = 0, 1
 
 
+class PtProbeVisibility(C.Structure):
+    _fields_ = [
+        ("resolution", C.c_uint32),
+        ("sharpness_log2", C.c_uint32),
+        ("max_distance", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class PtCascade(C.Structure):
     _fields_ = [
         ("layers", C.c_uint32),
@@ -405,6 +414,20 @@ SYMBOLS = {
     "pt_render_probe_lit_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtProbeGrid), C.c_void_p, C.c_void_p,
                                            _P(PtProbeShade), C.c_void_p, C.c_void_p]),
     "pt_debug_probe_positions": (C.c_int, [C.c_void_p, _P(PtProbeGrid), C.c_void_p]),
+    "pt_default_probe_visibility": (None, [_P(PtProbeGrid), _P(PtProbeVisibility)]),
+    "pt_probe_distances_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(PtRenderParams), C.c_void_p]),
+    "pt_probe_distances_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(PtRenderParams), C.c_void_p]),
+    "pt_probe_moments_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(PtProbeVisibility), C.c_void_p]),
+    "pt_probe_moments_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(PtProbeVisibility), C.c_void_p]),
+    "pt_probe_grid_visibility_device": (C.c_int, [C.c_void_p, _P(PtProbeGrid), C.c_uint32, _P(PtRenderParams), _P(PtProbeVisibility), C.c_void_p]),
+    "pt_probe_shade_visibility_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtProbeGrid), C.c_void_p, C.c_void_p, _P(PtProbeVisibility),
+                                                   C.c_void_p, C.c_void_p, _P(PtProbeShade), C.c_void_p, C.c_void_p]),
+    "pt_probe_shade_visibility_host": (C.c_int, [_P(PtCamera), _P(PtProbeGrid), C.c_void_p, C.c_void_p, _P(PtProbeVisibility), C.c_void_p,
+                                                 C.c_void_p, _P(PtProbeShade), C.c_void_p, C.c_void_p]),
+    "pt_render_probe_lit_visibility_device": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtProbeGrid), C.c_void_p,
+                                                        C.c_void_p, _P(PtProbeVisibility), C.c_void_p, _P(PtProbeShade), C.c_void_p, C.c_void_p]),
+    "pt_render_probe_lit_visibility_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtProbeGrid), C.c_void_p,
+                                                      C.c_void_p, _P(PtProbeVisibility), C.c_void_p, _P(PtProbeShade), C.c_void_p, C.c_void_p]),
     "pt_default_upsample": (None, [_P(PtUpsample)]),
     "pt_upsample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                      _P(PtUpsample), C.c_void_p, C.c_void_p]),

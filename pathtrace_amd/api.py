@@ -320,6 +320,45 @@ def probe_shade_host(cam, grid, sh27, features, fallback=None, shade=None):
     return out, rgba
 
 
+def default_probe_visibility(grid=None, **over):
+    """pt_default_probe_visibility for the grid (None: max_distance 1) with keyword overrides (None keeps the default)"""
+    v = _lib.PtProbeVisibility()
+    lib().pt_default_probe_visibility(None if grid is None else C.byref(grid), C.byref(v))
+    for k, val in over.items():
+        if val is not None:
+            setattr(v, k, val)
+    return v
+
+
+def probe_moments_host(distances, vis):
+    """pt_probe_moments_host (host only): distances f32[P, R] -> the moment maps f32[P, T, T, 2], [p, j, i] = texel (i, j)"""
+    d = np.ascontiguousarray(distances, dtype=np.float32)
+    if d.ndim != 2:
+        raise ValueError("distances: float32[P, R]")
+    T = int(vis.resolution)
+    out = np.empty((d.shape[0], T, T, 2), dtype=np.float32)
+    check(lib().pt_probe_moments_host(_pv(d), d.shape[0], d.shape[1], C.byref(vis), _pv(out)))
+    return out
+
+
+def probe_shade_visibility_host(cam, grid, sh27, moments, vis, features, fallback=None, shade=None):
+    """pt_probe_shade_visibility_host (host only): probe_shade_host with the moment maps f32[P, T, T, 2] of the grid's probes;
+    shade.weight is not read.  -> (linear f32[H, W, 3], rgba u8[H, W, 4])"""
+    shade = shade if shade is not None else default_probe_shade()
+    H, W = cam.height, cam.width
+    sh = np.ascontiguousarray(sh27, dtype=np.float32)
+    mom = np.ascontiguousarray(moments, dtype=np.float32)
+    feat = np.ascontiguousarray(features, dtype=np.float32)
+    fb = None if fallback is None else np.ascontiguousarray(fallback, dtype=np.float32)
+    P, T = probe_grid_count(grid), int(vis.resolution)
+    if sh.size != 27 * P or mom.size != 2 * T * T * P or feat.shape != (H, W, 8) or (fb is not None and fb.shape != (H, W, 3)):
+        raise ValueError("probe_shade_visibility_host: sh27 f32[P, 9, 3], moments f32[P, T, T, 2], features f32[H, W, 8], fallback f32[H, W, 3]")
+    out, rgba = np.empty((H, W, 3), dtype=np.float32), np.empty((H, W, 4), dtype=np.uint8)
+    check(lib().pt_probe_shade_visibility_host(C.byref(cam), C.byref(grid), _pv(sh), _pv(mom), C.byref(vis), _pv(feat),
+                                               None if fb is None else _pv(fb), C.byref(shade), _pv(out), _pv(rgba)))
+    return out, rgba
+
+
 def upsample_host(lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
     """pt_upsample_host: the upsampling rule on the CPU (no device, no context), on a low film (f32[h,w,3]), its features
     (f32[h,w,8]) and the full-size features (f32[H,W,8]).  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
@@ -945,6 +984,72 @@ class _ContextFunctions:
         rgba = self._empty((H, W, 4), "uint8") if want_rgba else None
         self._on_stream(lib().pt_render_probe_lit_device, C.byref(cam), C.byref(params), int(feature_samples), C.byref(grid), sh, fb, C.byref(shade),
                         out, rgba)
+        return out, rgba
+
+    def probe_distances(self, positions, rays_per_probe, params):
+        """pt_probe_distances_device: positions f32[P, 3] -> the first-hit distances f32[P, R] along probe_directions(R), +inf for a
+        miss; a torch device tensor.  Of params only t_min, accel and exact_math are read."""
+        t = self._device_f32(positions, (3,), "positions").reshape(-1, 3)
+        P, R = int(t.shape[0]), int(rays_per_probe)
+        out = self._empty((P, R))
+        self._on_stream(lib().pt_probe_distances_device, t, P, R, C.byref(params), out)
+        return out
+
+    def probe_moments(self, distances, vis):
+        """pt_probe_moments_device: distances f32[P, R] (numpy or a device tensor) -> the moment maps f32[P, T, T, 2], a torch device
+        tensor.  Needs no scene."""
+        d = distances if hasattr(distances, "shape") else np.asarray(distances, dtype=np.float32)
+        t = self._device_f32(d, tuple(d.shape[-1:]), "distances")
+        if t.dim() != 2:
+            raise ValueError("distances: float32[P, R]")
+        T = int(vis.resolution)
+        out = self._empty((int(t.shape[0]), T, T, 2))
+        self._on_stream(lib().pt_probe_moments_device, t, int(t.shape[0]), int(t.shape[1]), C.byref(vis), out)
+        return out
+
+    def probe_grid_visibility(self, grid, rays_per_probe, params, vis):
+        """pt_probe_grid_visibility_device: the moment maps of the grid's probes in one call -> f32[P, T, T, 2], a torch device tensor"""
+        T = int(vis.resolution)
+        out = self._empty((probe_grid_count(grid), T, T, 2))
+        self._on_stream(lib().pt_probe_grid_visibility_device, C.byref(grid), int(rays_per_probe), C.byref(params), C.byref(vis), out)
+        return out
+
+    def _visibility_args(self, who, grid, sh27, moments, vis, fallback, H, W):
+        sh = self._device_f32(sh27, (9, 3), "sh27")
+        mom = self._device_f32(moments, (2,), "moments")
+        fb = None if fallback is None else self._device_f32(fallback, (3,), "fallback")
+        P, T = probe_grid_count(grid), int(vis.resolution)
+        if sh.numel() != 27 * P or mom.numel() != 2 * T * T * P or (fb is not None and tuple(fb.shape) != (H, W, 3)):
+            raise ValueError(who + ": sh27 f32[P, 9, 3], moments f32[P, T, T, 2], fallback f32[H, W, 3]")
+        return sh, mom, fb
+
+    def probe_shade_visibility(self, cam, grid, sh27, moments, vis, features, fallback=None, shade=None, in_place=False, want_rgba=True):
+        """pt_probe_shade_visibility_device: probe_shade with the moment maps f32[P, T, T, 2] of the grid's probes (shade.weight is not
+        read).  -> (linear[H,W,3] f32, rgba[H,W,4] u8 or None), torch device tensors"""
+        shade = shade if shade is not None else default_probe_shade()
+        H, W = cam.height, cam.width
+        sh, mom, fb = self._visibility_args("probe_shade_visibility", grid, sh27, moments, vis, fallback, H, W)
+        feat = self._device_f32(features, (8,), "features")
+        if tuple(feat.shape) != (H, W, 8):
+            raise ValueError("probe_shade_visibility: features f32[H, W, 8]")
+        if in_place and fb is None:
+            raise ValueError("probe_shade_visibility: in_place needs a fallback plane")
+        out = fb if in_place else self._empty((H, W, 3))
+        rgba = self._empty((H, W, 4), "uint8") if want_rgba else None
+        self._on_stream(lib().pt_probe_shade_visibility_device, C.byref(cam), C.byref(grid), sh, mom, C.byref(vis), feat, fb, C.byref(shade), out,
+                        rgba)
+        return out, rgba
+
+    def render_probe_lit_visibility(self, cam, params, grid, sh27, moments, vis, feature_samples=1, fallback=None, shade=None, want_rgba=True):
+        """pt_render_probe_lit_visibility_device: the first-hit pass and the shading with the visibility term in one call ->
+        (linear[H,W,3] f32, rgba[H,W,4] u8 or None), torch device tensors"""
+        shade = shade if shade is not None else default_probe_shade()
+        H, W = cam.height, cam.width
+        sh, mom, fb = self._visibility_args("render_probe_lit_visibility", grid, sh27, moments, vis, fallback, H, W)
+        out = self._empty((H, W, 3))
+        rgba = self._empty((H, W, 4), "uint8") if want_rgba else None
+        self._on_stream(lib().pt_render_probe_lit_visibility_device, C.byref(cam), C.byref(params), int(feature_samples), C.byref(grid), sh, mom,
+                        C.byref(vis), fb, C.byref(shade), out, rgba)
         return out, rgba
 
     def probe_positions(self, grid):

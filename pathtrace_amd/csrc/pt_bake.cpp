@@ -33,6 +33,8 @@ PtCamera film_camera(uint32_t width, uint32_t height) {
     return cam;
 }
 
+}  // namespace
+
 ptk::RaySourceF bake_source(uint32_t kind, uint32_t width, uint32_t height, const float* d_data) {
     const PtCamera cam = film_camera(width, height);
     ptk::RaySourceF s{};
@@ -41,6 +43,8 @@ ptk::RaySourceF bake_source(uint32_t kind, uint32_t width, uint32_t height, cons
     s.bake.data = d_data; s.bake.kind = kind; s.bake.width = width;
     return s;
 }
+
+namespace {
 
 // The render of a bake: the planes checked by the caller; the bake's paths form fills the inject planes of every sample batch
 int bake_render(const char* who, PtContext* c, uint32_t kind, uint32_t width, uint32_t height, const float* d_data, const PtRenderParams* prm,

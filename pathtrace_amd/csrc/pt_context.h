@@ -227,6 +227,10 @@ struct PtContext {
     // the feature plane (pt_render_probe_lit_host stages the coefficients in bake_sh and the film in host_lin / host_rgba)
     DevBuf<float> pg_pos, pg_rad;
     DevBuf<float4> pg_feat;
+    // pt_probe_grid_visibility_device: the distance plane of the grid's probe rays; pt_probe_distances_host: device
+    // staging of its output (the positions go through bake_in); pt_render_probe_lit_visibility_host: device staging of the moment maps
+    DevBuf<float> pv_dist, pv_out;
+    DevBuf<float2> pv_mom;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).
@@ -294,6 +298,8 @@ int debug_source_rays(PtContext* c, const ptk::RaySourceF& src, const uint32_t* 
 int lens_setup(const char* who, const PtCamera* cam, const PtLens* lens, ptk::LensF* out);                  // pt_lens.cpp
 int projection_setup(const char* who, const PtCamera* cam, const PtProjection* proj, ptk::ProjF* out);      // pt_projection.cpp
 ptk::CameraF camera_f32(const PtCamera* cam);                                                               // pt_lens.cpp
+// the bake as a ray source: a film of width x height texels, or directions x probes, over the device records d_data (pt_bake.cpp)
+ptk::RaySourceF bake_source(uint32_t kind, uint32_t width, uint32_t height, const float* d_data);
 // The lens and projection forms of pt_render_features_device and pt_render_denoised (pt_denoise.cpp; their entries: pt_lens.cpp,
 // pt_projection.cpp), src not empty
 int features_source_device(const char* who, PtContext* c, const PtCamera* cam, const FrameSource& src, const PtRenderParams* prm,

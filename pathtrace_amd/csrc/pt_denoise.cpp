@@ -12,8 +12,6 @@
 
 namespace {
 
-constexpr uint64_t kFeatureRays = 1ull << 21;    // pt_render_features_device: rays per batch (108 B of scratch each with the BVH)
-
 enum class History { none, plain, motion, alpha };   // the accumulation before the a-trous steps; motion reads d_ids, alpha d_alpha too
 enum class Variance { spatial, given };              // the filter's initial variance: its own 3 x 3 estimate, or the plane d_var
 enum class Strata { same_camera, prev_camera };      // the camera whose frame the gradient strata re-trace

@@ -39,6 +39,10 @@ int check_integrator(uint32_t integrator, const char* who = nullptr);
 int check_accel(uint32_t accel, const char* who = nullptr);
 int check_band_index(uint32_t band_index, uint32_t band_count);
 
+// ---- the first-hit passes over the context's ft_* scratch (pt_render_features_device, pt_probe_distances_device): rays per batch
+// (108 B of scratch each with the BVH)
+constexpr uint64_t kFeatureRays = 1ull << 21;
+
 // ---- from the device to the caller's host planes
 struct CopyBack { void* host; const void* dev; size_t bytes; };   // blocking, the stream is through; a null host pointer: not asked for
 int copy_back(std::initializer_list<CopyBack> copies);

@@ -605,8 +605,8 @@ struct SourcePathsArgs {
 // launch_source_feature_rays: the source's rays of samples s_base .. s_base + nb - 1 of every image pixel, ray s_local * np + p, as
 // the rays6 launch_debug_hit reads.  launch_debug_source_rays: words = n * (x, y, sample, -) -> out = n * (o3, d3, dx, dy) for the
 // lens, n * (o3, d3, a, b) for a projection, n * (o3, d3) for a bake (x < width and y < the rows: the caller has checked).
-// false: the source has no kernel of that form (paths: all but the camera; feature rays: camera, lens, projection; debug rays:
-// lens, projection, bake), nothing was launched.
+// false: the source has no kernel of that form (paths: all but the camera; feature rays: camera, lens, projection, bake -- there
+// the "image" is directions x probes --; debug rays: lens, projection, bake), nothing was launched.
 bool launch_source_paths_exact(const SourcePathsArgs& a, hipStream_t st);
 bool launch_source_paths_fast(const SourcePathsArgs& a, hipStream_t st);
 bool launch_source_feature_rays_exact(const RaySourceF& src, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
@@ -647,5 +647,19 @@ struct ProbeShadeArgs {
 };
 void launch_probe_positions(const ProbeGridArgs& g, uint32_t n, float* out, hipStream_t st);
 void launch_probe_shade(const ProbeShadeArgs& a, hipStream_t st);
+
+// Probe visibility (pt_probe_distances_device, pt_probe_moments_device, pt_probe_shade_visibility_device; rule: pt_probe_vis.h,
+// DESIGN.md 5t; film unit).  launch_probe_distances: the ids and t of launch_debug_hit for n rays -> out[n], t or +inf.
+// launch_probe_moments: distances float[n_probes][rays_per_probe] -> moments float[n_probes][T][T][2], checked parameters.
+// launch_probe_shade_vis: launch_probe_shade with the maps (a.weight is not read).
+struct ProbeMomentsArgs {
+    const float* distances;
+    float* moments;
+    uint32_t n_probes, rays_per_probe, resolution, sharpness_log2;
+    float max_distance;
+};
+void launch_probe_distances(const int32_t* ids, const float* t, uint32_t n, float* out, hipStream_t st);
+void launch_probe_moments(const ProbeMomentsArgs& a, hipStream_t st);
+void launch_probe_shade_vis(const ProbeShadeArgs& a, const float* moments, uint32_t resolution, hipStream_t st);
 
 }  // namespace ptk

@@ -282,6 +282,7 @@ bool PT_LAUNCH(launch_source_feature_rays)(const RaySourceF& src, uint32_t s_bas
     case kSrcCamera: return launch_per_item(k_source_feature_rays<CameraSource>, n, st, src, s_base, nb, rays6);
     case kSrcLens: return launch_per_item(k_source_feature_rays<LensSource>, n, st, src, s_base, nb, rays6);
     case kSrcProjection: return launch_per_item(k_source_feature_rays<ProjectionSource>, n, st, src, s_base, nb, rays6);
+    case kSrcBake: return launch_per_item(k_source_feature_rays<BakeSource>, n, st, src, s_base, nb, rays6);
     default: return false;
     }
 }

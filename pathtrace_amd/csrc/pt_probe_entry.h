@@ -1,0 +1,33 @@
+// pt_probe_entry.h -- what the two host files of the irradiance volume share (internal to csrc/): the checks and passes of
+// pt_probe_grid.cpp that the probe-visibility entries of pt_probe_vis.cpp run with their moment maps.
+#pragma once
+#include "pt_entry.h"
+#include "pt_probe_grid.h"
+
+namespace ptprobe {
+
+// The moment maps of a shading pass with the visibility term; none: the pass without it
+struct Maps { const float* moments = nullptr; const PtProbeVisibility* vis = nullptr; };
+
+ptk::ProbeGridArgs kernel_grid(const PtProbeGrid* g);
+int check_grid(const char* who, const PtProbeGrid* g);
+// what a shading pass reads and writes, checked before anything looks at a context; feat_align: 16 on the device, 4 on the host
+int check_shade(const char* who, const PtCamera* cam, const PtProbeGrid* g, const void* sh27, const void* features, const void* fallback,
+                const PtProbeShade* sp, const void* out_linear, const void* out_rgba, uint32_t feat_align, bool own_features = false);
+// what pt_render_probe_lit_* checks of its own before the feature pass checks the rest
+int check_probe_lit(const char* who, const PtContext* c, const PtCamera* cam, const PtRenderParams* prm, const PtProbeGrid* g, const void* sh27,
+                    const void* fallback, const PtProbeShade* sp, const void* out_linear, const void* out_rgba);
+// the launch of a checked shading pass
+int shade_launch(PtContext* c, const PtCamera* cam, const PtProbeGrid* g, const float* d_sh27, const float* d_features, const float* d_fallback,
+                 const PtProbeShade* sp, float* d_out_linear, uint8_t* d_out_rgba, const Maps& maps = {});
+// the feature pass into the context's plane, then the shading
+int probe_lit_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtProbeGrid* g, const float* d_sh27,
+                   const float* d_fallback, const PtProbeShade* sp, float* d_out_linear, uint8_t* d_out_rgba, const Maps& maps = {});
+// the rule on the CPU
+void shade_host(const PtCamera* cam, const PtProbeGrid* g, const float* sh27, const float* features, const float* fallback, const PtProbeShade* sp,
+                float* out_linear, uint8_t* out_rgba, const Maps& maps = {});
+// probe_lit_impl from and into host buffers through the context's staging
+int probe_lit_host(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtProbeGrid* g, const float* sh27,
+                   const float* fallback, const PtProbeShade* sp, float* out_linear, uint8_t* out_rgba, const Maps& maps = {});
+
+}  // namespace ptprobe

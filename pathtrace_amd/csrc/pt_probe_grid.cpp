@@ -1,14 +1,18 @@
 // pt_probe_grid.cpp -- the host side of the irradiance volume: the grid helpers, the bake of a grid (k_probe_positions in
 // front of pt_bake_probes_device), the shading pass (k_probe_shade) alone and behind the feature pass, and the rule on the CPU
-// (pt_probe_grid.h).  The entries' rule, check_plane, the render's preconditions and the host entry's staging: pt_entry.h.
+// (pt_probe_grid.h).  The shading passes take the moment maps of the probe visibility where they are given; the entries
+// that give them stand in pt_probe_vis.cpp and share this file's checks and passes through pt_probe_entry.h.  The entries' rule,
+// check_plane, the render's preconditions and the host entry's staging: pt_entry.h.
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <vector>
 
-#include "pt_entry.h"
-#include "pt_probe_grid.h"
+#include "pt_probe_entry.h"
+#include "pt_probe_vis.h"
 
-namespace {
+namespace ptprobe {
 
 static_assert(sizeof(PtProbeGrid) == sizeof(ptgrid::Grid) && offsetof(PtProbeGrid, spacing) == offsetof(ptgrid::Grid, spacing) &&
                   offsetof(PtProbeGrid, counts) == offsetof(ptgrid::Grid, counts),
@@ -37,7 +41,7 @@ int check_grid(const char* who, const PtProbeGrid* g) {
 }
 // what a shading pass reads and writes, checked before anything looks at a context; feat_align: 16 on the device, 4 on the host
 int check_shade(const char* who, const PtCamera* cam, const PtProbeGrid* g, const void* sh27, const void* features, const void* fallback,
-                const PtProbeShade* sp, const void* out_linear, const void* out_rgba, uint32_t feat_align, bool own_features = false) {
+                const PtProbeShade* sp, const void* out_linear, const void* out_rgba, uint32_t feat_align, bool own_features) {
     if (!cam || !sp) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
     if ((rc = check_grid(who, g))) return rc;
@@ -53,7 +57,7 @@ int check_shade(const char* who, const PtCamera* cam, const PtProbeGrid* g, cons
 
 // the launch of a checked shading pass
 int shade_launch(PtContext* c, const PtCamera* cam, const PtProbeGrid* g, const float* d_sh27, const float* d_features, const float* d_fallback,
-                 const PtProbeShade* sp, float* d_out_linear, uint8_t* d_out_rgba) {
+                 const PtProbeShade* sp, float* d_out_linear, uint8_t* d_out_rgba, const Maps& maps) {
     ptk::ProbeShadeArgs a{};
     a.feat = reinterpret_cast<const float4*>(d_features);
     a.sh27 = d_sh27; a.fallback = d_fallback; a.out_linear = d_out_linear; a.out_rgba = d_out_rgba;
@@ -62,7 +66,8 @@ int shade_launch(PtContext* c, const PtCamera* cam, const PtProbeGrid* g, const 
     }
     a.grid = kernel_grid(g);
     a.width = cam->width; a.height = cam->height; a.weight = sp->weight; a.normal_bias = sp->normal_bias;
-    ptk::launch_probe_shade(a, c->stream);
+    if (maps.vis) ptk::launch_probe_shade_vis(a, maps.moments, maps.vis->resolution, c->stream);
+    else ptk::launch_probe_shade(a, c->stream);
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
@@ -74,16 +79,60 @@ int check_probe_lit(const char* who, const PtContext* c, const PtCamera* cam, co
     return check_shade(who, cam, g, sh27, nullptr, fallback, sp, out_linear, out_rgba, 16, /*own_features=*/true);
 }
 int probe_lit_impl(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtProbeGrid* g, const float* d_sh27,
-                   const float* d_fallback, const PtProbeShade* sp, float* d_out_linear, uint8_t* d_out_rgba) {
+                   const float* d_fallback, const PtProbeShade* sp, float* d_out_linear, uint8_t* d_out_rgba, const Maps& maps) {
     int rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = c->pg_feat.ensure(2 * (size_t)cam->width * cam->height))) return rc;
     float* const feat = reinterpret_cast<float*>(c->pg_feat.p);
     if ((rc = pt_render_features_device(c, cam, prm, feature_samples, feat))) return rc;      // (refuses before its first launch)
-    return shade_launch(c, cam, g, d_sh27, feat, d_fallback, sp, d_out_linear, d_out_rgba);
+    return shade_launch(c, cam, g, d_sh27, feat, d_fallback, sp, d_out_linear, d_out_rgba, maps);
 }
 
-}  // namespace
+// the rule on the CPU, with the maps or without
+void shade_host(const PtCamera* cam, const PtProbeGrid* g, const float* sh27, const float* features, const float* fallback, const PtProbeShade* sp,
+                float* out_linear, uint8_t* out_rgba, const Maps& maps) {
+    const ptgrid::Grid r = rule_grid(g);
+    const double camv[12] = {cam->origin[0],     cam->origin[1],     cam->origin[2],     cam->lower_left[0], cam->lower_left[1], cam->lower_left[2],
+                             cam->horizontal[0], cam->horizontal[1], cam->horizontal[2], cam->vertical[0],   cam->vertical[1],   cam->vertical[2]};
+    for (uint32_t y = 0; y < cam->height; ++y)
+        for (uint32_t x = 0; x < cam->width; ++x) {
+            const size_t p = (size_t)y * cam->width + x;
+            float v[3];
+            const bool lit = maps.vis ? ptvis::shade(r, sp->normal_bias, cam->width, cam->height, x, y, features + 8 * p, camv, sh27, maps.moments,
+                                                     maps.vis->resolution, v)
+                                      : ptgrid::shade(r, sp->normal_bias, sp->weight, cam->width, cam->height, x, y, features + 8 * p, camv, sh27, v);
+            if (!lit)
+                for (int k = 0; k < 3; ++k) v[k] = fallback ? fallback[3 * p + k] : 0.0f;
+            for (int k = 0; k < 3; ++k) out_linear[3 * p + k] = v[k];
+            if (out_rgba) {
+                const uint32_t q8 = ptgrid::rgba8(v);
+                std::memcpy(out_rgba + 4 * p, &q8, 4);
+            }
+        }
+}
+
+// pt_render_probe_lit_host, and with maps pt_render_probe_lit_visibility_host: the coefficients through bake_sh, the maps through
+// pv_mom, the film through host_lin / host_rgba
+int probe_lit_host(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtProbeGrid* g, const float* sh27,
+                   const float* fallback, const PtProbeShade* sp, float* out_linear, uint8_t* out_rgba, const Maps& maps) {
+    const size_t np = (size_t)cam->width * cam->height, n = pt_probe_grid_count(g), nsh = 27 * n;
+    const size_t nm = maps.vis ? n * maps.vis->resolution * maps.vis->resolution : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->bake_sh.ensure(nsh)) || (rc = c->pv_mom.ensure(nm))) return rc;
+    return render_staged(c, 3 * np, out_rgba ? 4 * np : 0, [&](float* d_linear, uint8_t* d_rgba) {
+        HIP_TRY(hipStreamSynchronize(c->stream));      // (an earlier call may still read the staging)
+        HIP_TRY(hipMemcpy(c->bake_sh.p, sh27, nsh * sizeof(float), hipMemcpyHostToDevice));
+        if (nm) HIP_TRY(hipMemcpy(c->pv_mom.p, maps.moments, nm * sizeof(float2), hipMemcpyHostToDevice));
+        if (fallback) HIP_TRY(hipMemcpy(d_linear, fallback, 3 * np * sizeof(float), hipMemcpyHostToDevice));
+        Maps dm = maps;
+        if (nm) dm.moments = reinterpret_cast<const float*>(c->pv_mom.p);
+        return probe_lit_impl(c, cam, prm, feature_samples, g, c->bake_sh.p, fallback ? d_linear : nullptr, sp, d_linear, d_rgba, dm);
+    }, [&] { return copy_back({{out_linear, c->host_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np}}); });
+}
+
+}  // namespace ptprobe
+using namespace ptprobe;
 
 extern "C" {
 
@@ -138,21 +187,7 @@ int pt_probe_shade_device(PtContext* c, const PtCamera* cam, const PtProbeGrid* 
 int pt_probe_shade_host(const PtCamera* cam, const PtProbeGrid* g, const float* sh27, const float* features, const float* fallback,
                         const PtProbeShade* sp, float* out_linear, uint8_t* out_rgba) {
     if (int rc = check_shade("pt_probe_shade_host", cam, g, sh27, features, fallback, sp, out_linear, out_rgba, 4)) return rc;
-    const ptgrid::Grid r = rule_grid(g);
-    const double camv[12] = {cam->origin[0],     cam->origin[1],     cam->origin[2],     cam->lower_left[0], cam->lower_left[1], cam->lower_left[2],
-                             cam->horizontal[0], cam->horizontal[1], cam->horizontal[2], cam->vertical[0],   cam->vertical[1],   cam->vertical[2]};
-    for (uint32_t y = 0; y < cam->height; ++y)
-        for (uint32_t x = 0; x < cam->width; ++x) {
-            const size_t p = (size_t)y * cam->width + x;
-            float v[3];
-            if (!ptgrid::shade(r, sp->normal_bias, sp->weight, cam->width, cam->height, x, y, features + 8 * p, camv, sh27, v))
-                for (int k = 0; k < 3; ++k) v[k] = fallback ? fallback[3 * p + k] : 0.0f;
-            for (int k = 0; k < 3; ++k) out_linear[3 * p + k] = v[k];
-            if (out_rgba) {
-                const uint32_t q8 = ptgrid::rgba8(v);
-                std::memcpy(out_rgba + 4 * p, &q8, 4);
-            }
-        }
+    shade_host(cam, g, sh27, features, fallback, sp, out_linear, out_rgba);
     return PT_OK;
 }
 
@@ -165,15 +200,7 @@ int pt_render_probe_lit_device(PtContext* c, const PtCamera* cam, const PtRender
 int pt_render_probe_lit_host(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtProbeGrid* g,
                              const float* sh27, const float* fallback, const PtProbeShade* sp, float* out_linear, uint8_t* out_rgba) {
     if (int rc = check_probe_lit("pt_render_probe_lit_host", c, cam, prm, g, sh27, fallback, sp, out_linear, out_rgba)) return rc;
-    const size_t np = (size_t)cam->width * cam->height, nsh = 27 * (size_t)pt_probe_grid_count(g);
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = c->bake_sh.ensure(nsh)) return rc;
-    return render_staged(c, 3 * np, out_rgba ? 4 * np : 0, [&](float* d_linear, uint8_t* d_rgba) {
-        HIP_TRY(hipStreamSynchronize(c->stream));      // (an earlier call may still read the staging)
-        HIP_TRY(hipMemcpy(c->bake_sh.p, sh27, nsh * sizeof(float), hipMemcpyHostToDevice));
-        if (fallback) HIP_TRY(hipMemcpy(d_linear, fallback, 3 * np * sizeof(float), hipMemcpyHostToDevice));
-        return probe_lit_impl(c, cam, prm, feature_samples, g, c->bake_sh.p, fallback ? d_linear : nullptr, sp, d_linear, d_rgba);
-    }, [&] { return copy_back({{out_linear, c->host_lin.p, 3 * np * sizeof(float)}, {out_rgba, c->host_rgba.p, 4 * np}}); });
+    return probe_lit_host(c, cam, prm, feature_samples, g, sh27, fallback, sp, out_linear, out_rgba);
 }
 
 int pt_debug_probe_positions(PtContext* c, const PtProbeGrid* g, float* out_positions3) {

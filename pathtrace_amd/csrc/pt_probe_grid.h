@@ -19,7 +19,8 @@
 //      never formed (its spacing may be 0).
 //   4. corner j = 0..7 (bit 0 = x, bit 1 = y, bit 2 = z): w_j = (wx wy) wz, each f or 1 - f.  kFacing: v = pos_j - P from the f32
 //      position, c = (v . nn) / |v| (1 when |v| = 0), w_j = w_j (((c + 1) / 2)^2 + 0.2) -- the backface weight of Majercik et al.
-//      2019 without its visibility term.
+//      2019 without its visibility term.  (With it: pt_probe_vis.h, whose MomentMaps replaces the last statement through the
+//      Visibility argument of shade_rule below; the two weights here go through NoVisibility and keep their arithmetic.)
 //   5. every coefficient: C = C_0 + (sum_{j=1..7} w_j (C_j - C_0)) / (sum_{j=0..7} w_j), both sums from 0.0 with j ascending:
 //      a constant field comes out exactly.
 //   6. E_c = sum_k (A_l C[k][c]) Y_k(nn) from 0.0 with k ascending (sh_basis and A of pt_bake.h, the order of ptbake::sh_irradiance);
@@ -70,10 +71,19 @@ PT_AD_HD void position(const Grid& g, uint32_t p, float out[3]) {
     out[0] = coordinate(g, 0, ix); out[1] = coordinate(g, 1, r % ny); out[2] = coordinate(g, 2, r / ny);
 }
 
+// The visibility term of step 4 is a type: NoVisibility here (the two weights above, nothing added to their arithmetic), and
+// ptvis::MomentMaps of pt_probe_vis.h, whose factor(probe, Q, pos) is the Chebyshev weight of the probe's moment map
+// towards the biased point Q and which replaces the last statement of kFacing by its own.
+struct NoVisibility {
+    static constexpr bool kOn = false;
+    PT_AD_HD double weight(uint32_t, const double*, const double*, double tri, double) const { return tri; }
+};
+
 // One pixel: rec = the 8 floats of its feature record, cam = o3, l3, hz3, vt3, sh27 = float[count][9][3].  false: unlit (nothing
 // read from sh27, out untouched).  Every loop unrolls: on the device the arrays live in registers.
-PT_AD_HD bool shade(const Grid& g, float normal_bias, uint32_t weight, uint32_t W, uint32_t H, uint32_t x, uint32_t y, const float rec[8],
-                    const double cam[12], const float* sh27, float out[3]) {
+template <class Visibility>
+PT_AD_HD bool shade_rule(const Grid& g, float normal_bias, uint32_t weight, uint32_t W, uint32_t H, uint32_t x, uint32_t y, const float rec[8],
+                         const double cam[12], const float* sh27, const Visibility& vis, float out[3]) {
     // 1
     const float d = rec[7];
     bool ok = d > 0.0f && finitef(d) && !(rec[3] > 0.0f);
@@ -131,7 +141,7 @@ PT_AD_HD bool shade(const Grid& g, float normal_bias, uint32_t weight, uint32_t 
         }
         double wj = wa[0] * wa[1];
         wj = wj * wa[2];
-        if (weight == (uint32_t)kFacing) {
+        if (Visibility::kOn || weight == (uint32_t)kFacing) {
             double v[3];
             PT_BAKE_UNROLL
             for (int a = 0; a < 3; ++a) v[a] = (double)coordinate(g, a, c[a]) - P[a];
@@ -139,7 +149,14 @@ PT_AD_HD bool shade(const Grid& g, float normal_bias, uint32_t weight, uint32_t 
             const double vn = dot3(v, nn);
             const double cs = vlen == 0.0 ? 1.0 : vn / vlen;
             const double h = (cs + 1.0) / 2.0;
-            wj = wj * (h * h + 0.2);
+            if (Visibility::kOn) {
+                double Q[3], pos[3];
+                PT_BAKE_UNROLL
+                for (int a = 0; a < 3; ++a) { Q[a] = P[a] + (double)normal_bias * nn[a]; pos[a] = (double)coordinate(g, a, c[a]); }
+                wj = vis.weight((c[2] * g.counts[1] + c[1]) * g.counts[0] + c[0], Q, pos, wj, h * h + 0.2);
+            } else {
+                wj = wj * (h * h + 0.2);
+            }
         }
         idx[j] = (c[2] * g.counts[1] + c[1]) * g.counts[0] + c[0];
         w[j] = wj;
@@ -175,6 +192,10 @@ PT_AD_HD bool shade(const Grid& g, float normal_bias, uint32_t weight, uint32_t 
         out[ch] = (float)((a * E) / ptbake::kPi);
     }
     return true;
+}
+PT_AD_HD bool shade(const Grid& g, float normal_bias, uint32_t weight, uint32_t W, uint32_t H, uint32_t x, uint32_t y, const float rec[8],
+                    const double cam[12], const float* sh27, float out[3]) {
+    return shade_rule(g, normal_bias, weight, W, H, x, y, rec, cam, sh27, NoVisibility(), out);
 }
 
 // the RGBA8 word of a linear pixel

@@ -580,6 +580,43 @@ public:
                                        rgba.data()));
         unpack(lin, rgba);
     }
+    // Probe visibility.  bake_probe_visibility: the octahedral distance-moment maps of the grid's probes
+    // (pt_probe_distances_host on pt_probe_grid_positions_host, then pt_probe_moments_host) -> count x T x T x 2 floats; the same
+    // bits as pt_probe_grid_visibility_device in the same arithmetic mode.
+    std::vector<float> bake_probe_visibility(const PtProbeGrid& grid, uint32_t rays_per_probe, const PtProbeVisibility& vis, int device = 0) {
+        const uint32_t n = pt_probe_grid_count(&grid);
+        if (n == 0) throw std::runtime_error("bake_probe_visibility: invalid probe grid");
+        scene(device);
+        std::vector<float> pos((size_t)n * 3), dist((size_t)n * rays_per_probe), maps((size_t)n * vis.resolution * vis.resolution * 2);
+        check(pt_probe_grid_positions_host(&grid, pos.data()));
+        check(pt_probe_distances_host(ctx_, pos.data(), n, rays_per_probe, &params_, dist.data()));
+        check(pt_probe_moments_host(dist.data(), n, rays_per_probe, &vis, maps.data()));
+        return maps;
+    }
+    // render_probe_lit with the visibility term (pt_render_probe_lit_visibility_host): a probe the point cannot see drops out of
+    // the blend, so light does not leak through walls between probes.  shade->weight is not read.
+    void render_probe_lit_visibility(const PtProbeGrid& grid, const std::vector<float>& sh27, const std::vector<float>& moments,
+                                     const PtProbeVisibility& vis, const PtProbeShade* shade = nullptr, uint32_t feature_samples = 1,
+                                     const std::vector<Vector3>* fallback = nullptr, int device = 0) {
+        const size_t count = pt_probe_grid_count(&grid);
+        if (sh27.size() != count * 27 || sh27.empty()) throw std::runtime_error("render_probe_lit_visibility: sh27 must hold count x 27 floats");
+        if (moments.size() != count * vis.resolution * vis.resolution * 2)
+            throw std::runtime_error("render_probe_lit_visibility: moments must hold count x T x T x 2 floats");
+        scene(device);
+        resize_film();
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        PtProbeShade s{};
+        if (shade) s = *shade; else pt_default_probe_shade(&s);
+        const size_t n = (size_t)camera_.width() * camera_.height();
+        if (fallback && fallback->size() != n) throw std::runtime_error("render_probe_lit_visibility: fallback must hold width x height values");
+        std::vector<float> lin(n * 3), fb(fallback ? n * 3 : 0);
+        for (size_t i = 0; i < fb.size() / 3; ++i) { fb[3 * i] = (float)(*fallback)[i].x; fb[3 * i + 1] = (float)(*fallback)[i].y; fb[3 * i + 2] = (float)(*fallback)[i].z; }
+        std::vector<uint8_t> rgba(n * 4);
+        check(pt_render_probe_lit_visibility_host(ctx_, &camera_.pod(), &p, feature_samples, &grid, sh27.data(), moments.data(), &vis,
+                                                  fallback ? fb.data() : nullptr, &s, lin.data(), rgba.data()));
+        unpack(lin, rgba);
+    }
     // render_denoised() through the lens (pt_render_lens_denoised): the features are those of the lens rays.
     void render_lens_denoised(const PtLens& lens, uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, std::vector<Vector3>* noisy = nullptr,
                               int device = 0) {

@@ -172,6 +172,15 @@ pub struct PtProbeShade {
 }
 pub const PT_PROBE_WEIGHT_TRILINEAR: u32 = 0;
 pub const PT_PROBE_WEIGHT_FACING: u32 = 1;
+/// pt_probe_moments_*, pt_probe_shade_visibility_*: the probes' octahedral distance-moment maps (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtProbeVisibility {
+    pub resolution: u32,
+    pub sharpness_log2: u32,
+    pub max_distance: f32,
+    pub reserved: u32,
+}
 
 /// pt_render_lens_device: the thin lens beside the camera (include/pathtrace_amd.h); aperture 0 = pinhole.
 #[repr(C)]
@@ -521,6 +530,16 @@ extern "C" {
     pub fn pt_render_probe_lit_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, grid: *const PtProbeGrid, d_sh27: *const f32, d_fallback_linear: *const f32, shade: *const PtProbeShade, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_probe_lit_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, grid: *const PtProbeGrid, sh27: *const f32, fallback_linear: *const f32, shade: *const PtProbeShade, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
     pub fn pt_debug_probe_positions(ctx: *mut PtContext, grid: *const PtProbeGrid, out_positions3: *mut f32) -> c_int;
+    pub fn pt_default_probe_visibility(grid: *const PtProbeGrid, out: *mut PtProbeVisibility);
+    pub fn pt_probe_distances_device(ctx: *mut PtContext, d_positions3: *const f32, n_probes: u32, rays_per_probe: u32, params: *const PtRenderParams, d_distances: *mut f32) -> c_int;
+    pub fn pt_probe_distances_host(ctx: *mut PtContext, positions3: *const f32, n_probes: u32, rays_per_probe: u32, params: *const PtRenderParams, out_distances: *mut f32) -> c_int;
+    pub fn pt_probe_moments_device(ctx: *mut PtContext, d_distances: *const f32, n_probes: u32, rays_per_probe: u32, vis: *const PtProbeVisibility, d_moments: *mut f32) -> c_int;
+    pub fn pt_probe_moments_host(distances: *const f32, n_probes: u32, rays_per_probe: u32, vis: *const PtProbeVisibility, out_moments: *mut f32) -> c_int;
+    pub fn pt_probe_grid_visibility_device(ctx: *mut PtContext, grid: *const PtProbeGrid, rays_per_probe: u32, params: *const PtRenderParams, vis: *const PtProbeVisibility, d_moments: *mut f32) -> c_int;
+    pub fn pt_probe_shade_visibility_device(ctx: *mut PtContext, cam: *const PtCamera, grid: *const PtProbeGrid, d_sh27: *const f32, d_moments: *const f32, vis: *const PtProbeVisibility, d_features: *const f32, d_fallback_linear: *const f32, shade: *const PtProbeShade, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_probe_shade_visibility_host(cam: *const PtCamera, grid: *const PtProbeGrid, sh27: *const f32, moments: *const f32, vis: *const PtProbeVisibility, features: *const f32, fallback_linear: *const f32, shade: *const PtProbeShade, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_probe_lit_visibility_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, grid: *const PtProbeGrid, d_sh27: *const f32, d_moments: *const f32, vis: *const PtProbeVisibility, d_fallback_linear: *const f32, shade: *const PtProbeShade, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
+    pub fn pt_render_probe_lit_visibility_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, grid: *const PtProbeGrid, sh27: *const f32, moments: *const f32, vis: *const PtProbeVisibility, fallback_linear: *const f32, shade: *const PtProbeShade, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
     pub fn pt_default_cascade(out: *mut PtCascade);
     pub fn pt_render_cascade_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
     pub fn pt_render_cascade_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_plain_linear: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;

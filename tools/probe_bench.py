@@ -55,13 +55,55 @@ def rel_mse(a, ref):
     return float(np.mean((a - ref) ** 2 / (ref ** 2 + 1e-2)))
 
 
+def visibility(a):
+    """--visibility, one JSON line: k_probe_moments for 16^3 probes x 256 rays at T = 8 and 16 (us); k_probe_shade_vis
+    at --size^2 beside k_probe_shade FACING on the same 16^3 grid, the forms alternating (us); the probe-lit frame with and without
+    the term (ms).  The leak numbers are those tests/test_gpu_probe_vis.py prints (pytest -s)."""
+    ctx = pt.Context(0)
+    ctx.upload(pt.builtin_scene(2))
+    dev = torch.device("cuda", 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    L = pt._lib.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    S = a.size
+    cam = pt.camera_new(width=S, height=S)
+    prm1 = pt.default_params(spp=1)
+    feat = torch.from_numpy(ctx.render_features(cam, prm1, 1)).to(dev)
+    lin = torch.empty((S, S, 3), dtype=torch.float32, device=dev)
+    rgba = torch.empty((S, S, 4), dtype=torch.uint8, device=dev)
+    g = box_grid(16)
+    sh = ctx.probe_grid_bake(g, 64, prm1)
+    dist = ctx.probe_distances(pt.probe_grid_positions(g), 256, prm1)
+    sp = pt.default_probe_shade(normal_bias=0.02, weight=1)
+    vis = {T: pt.default_probe_visibility(g, resolution=T) for T in (8, 16)}
+    maps = {T: ctx.probe_moments(dist, vis[T]) for T in (8, 16)}
+    out = {"size": S, "runs": a.runs, "reps": a.reps}
+    moments = {f"T={T}": lambda T=T: pt._lib.check(L.pt_probe_moments_device(ctx._h, p(dist), 4096, 256, C.byref(vis[T]), p(maps[T]))) for T in (8, 16)}
+    out["moments_us"] = {k: summary(t, 1e3, 2) for k, t in timed(ctx, moments, a.runs, a.reps).items()}
+    shade = {"facing": lambda: pt._lib.check(L.pt_probe_shade_device(ctx._h, C.byref(cam), C.byref(g), p(sh), p(feat), None, C.byref(sp), p(lin), p(rgba)))}
+    frame = {"probe_lit": lambda: pt._lib.check(L.pt_render_probe_lit_device(ctx._h, C.byref(cam), C.byref(prm1), 1, C.byref(g), p(sh), None, C.byref(sp),
+                                                                             p(lin), p(rgba)))}
+    for T in (8, 16):
+        shade[f"visibility T={T}"] = lambda T=T: pt._lib.check(L.pt_probe_shade_visibility_device(
+            ctx._h, C.byref(cam), C.byref(g), p(sh), p(maps[T]), C.byref(vis[T]), p(feat), None, C.byref(sp), p(lin), p(rgba)))
+        frame[f"probe_lit_visibility T={T}"] = lambda T=T: pt._lib.check(L.pt_render_probe_lit_visibility_device(
+            ctx._h, C.byref(cam), C.byref(prm1), 1, C.byref(g), p(sh), p(maps[T]), C.byref(vis[T]), None, C.byref(sp), p(lin), p(rgba)))
+    out["shade_us"] = {k: summary(t, 1e3, 2) for k, t in timed(ctx, shade, a.runs, a.reps).items()}
+    out["frame_ms"] = {k: summary(t, 1.0, 4) for k, t in timed(ctx, frame, a.runs, 4).items()}
+    print(json.dumps(out))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--ref-spp", type=int, default=4096)
+    ap.add_argument("--visibility", action="store_true", help="the probe-visibility kernels and frame instead (DESIGN.md 5t)")
     a = ap.parse_args()
+    if a.visibility:
+        return visibility(a)
     ctx = pt.Context(0)
     ctx.upload(pt.builtin_scene(2))
     dev = torch.device("cuda", 0)
