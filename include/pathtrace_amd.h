@@ -1200,7 +1200,7 @@ int pt_debug_probe_positions(PtContext* ctx, const PtProbeGrid* grid, float* out
  *               PT_PROBE_WEIGHT_FACING's film bit for bit.
  * Everything else is pt_probe_shade_*'s.  Refused as there, and: resolution outside [2, 16], sharpness_log2 > 8, a max_distance
  * that is not finite or not > 0, a moments plane that is null or not 8-byte aligned, n_probes or rays_per_probe outside
- * [1, 65535].  Not there: temporal hysteresis, probe relocation, a multi-GPU form.                                              */
+ * [1, 65535].  Not there: probe relocation, a multi-GPU form (temporal hysteresis: the update entries below).                 */
 typedef struct {
     uint32_t resolution;     /* T: texels per side of a probe's map, 2 .. 16                    */
     uint32_t sharpness_log2; /* k: the cosine lobe's exponent is 2^k, k <= 8                    */
@@ -1244,6 +1244,76 @@ int pt_render_probe_lit_visibility_device(PtContext* ctx, const PtCamera* cam, c
 int pt_render_probe_lit_visibility_host(PtContext* ctx, const PtCamera* cam, const PtRenderParams* params, uint32_t feature_samples,
                                         const PtProbeGrid* grid, const float* sh27, const float* moments, const PtProbeVisibility* vis,
                                         const float* fallback_linear, const PtProbeShade* shade, float* out_linear, uint8_t* out_rgba8);
+
+/* Irradiance volume, updates over frames (additive to ABI 6): the temporal half of Majercik et al. 2019.  After a
+ * scene change the volume need not be baked again: each call re-traces a SUBSET of the probes with FEW rays along a freshly rotated
+ * direction set and blends the result into the stored coefficients and moment maps with a per-probe hysteresis, so the quadrature
+ * error of a small direction set averages away over frames.  The rule (pathtrace_amd/csrc/pt_probe_update.h), host and device bit
+ * for bit:
+ *   slots       a call updates the probes p = first + k stride < count, k = 0, 1, ...; slot k is probe first + k stride, n_upd =
+ *               ceil((count - first) / stride).  The planes of a call's new data are slot-indexed: radiance float[n_upd][R][3],
+ *               distances float[n_upd][R].
+ *   ray         of slot k, direction r of R: the probe's position by the grid rule; d = the bake's direction r of R in the render's
+ *               arithmetic; d'_a = fma(M[a][2], d_2, fma(M[a][1], d_1, M[a][0] d_0)) in f32, not normalised again; a rotation that is
+ *               bit for bit the identity leaves d as it is (a select).  spp > 1 repeats a direction with independent continuations.
+ *   new values  the SH projection of pt_sh_project_* and the moments of pt_probe_moments_* with the rotated direction in exact
+ *               arithmetic in the place of the bake's.
+ *   blend       per probe with age = d_age[p] (uint32): alpha = 1 when age = 0, else max(1 - hysteresis, 1 / (age + 1)) in f64 -- a
+ *               plain running mean until the floor is reached.  Per SH coefficient and moment component: out = (float)(old + alpha
+ *               (new - old)) in f64; out = new when age = 0 or old is not finite (old is never multiplied: a NaN of a plane that was
+ *               never written does not survive); when new is not finite, out = old (age > 0) or +0.0 (age = 0).  age' = min(age + 1,
+ *               65535).
+ *   change gate change_threshold > 0 and age > 0: L0 = 0.2126 C[0][0] + 0.7152 C[0][1] + 0.0722 C[0][2] of the old and the new
+ *               coefficients; both finite and |L0_new - L0_old| > change_threshold max(L0_old, L0_new, 0): alpha = max(alpha,
+ *               change_alpha) for every coefficient and moment of that probe.
+ *   untouched   probes that are not a slot of the call keep sh27, moments and age bit for bit.
+ * Refused (PT_ERR_INVALID_ARG, before the first launch, the context untouched): what the probe-grid and visibility entries refuse of
+ * the grid, the visibility struct and the planes; rays_per_probe outside [1, 65535]; stride = 0 or first >= count; a hysteresis
+ * outside [0, 1) or not finite; a change_threshold that is negative or not finite; a change_alpha outside [0, 1] or not finite; a
+ * rotation that is not finite, with max |M M^T - I| > 1e-5 or with a determinant <= 0; a NULL or misaligned d_age (4 bytes);
+ * band_count > 1.  stride may be anything from 1 to 2^32 - 1 (a stride past the grid leaves the one slot `first`).  Not there:
+ * probe relocation and classification, a multi-GPU form, lens, filter or cascade forms.                                          */
+typedef struct {
+    uint32_t rays_per_probe;   /* R, 1 .. 65535                                                                              */
+    uint32_t first, stride;    /* this call updates probes p = first + k stride < P, k = 0, 1, ...; stride >= 1, first < P    */
+    float    hysteresis;       /* h in [0, 1): the floor of the blend weight is 1 - h                                         */
+    float    change_threshold; /* 0: off; else see "change gate"; finite, >= 0                                                */
+    float    change_alpha;     /* in [0, 1]                                                                                   */
+    float    rotation[9];      /* row-major M; finite, max |M M^T - I| <= 1e-5, det > 0                                       */
+    uint32_t reserved;
+} PtProbeUpdate;
+/* Host only: the rotation of a frame, row-major.  Frame 0 is the identity exactly; otherwise u_i = (((frame c_i) mod 2^32) >> 8)
+ * 2^-24 with c = 0x9E3779B9, 0x85EBCA6B, 0xC2B2AE35, Shoemake's uniform quaternion (sqrt(1 - u0) sin 2 pi u1, sqrt(1 - u0) cos 2 pi
+ * u1, sqrt(u0) sin 2 pi u2, sqrt(u0) cos 2 pi u2) = (x, y, z, w) in f64, the matrix in f64, rounded to f32 once.                  */
+void pt_probe_rotation(uint32_t frame, float* out9);
+/* Host only: rays_per_probe 64, first = frame % stride (stride 0 counts as 1), hysteresis 0.9375, the change gate off
+ * (change_threshold 0, change_alpha 1), pt_probe_rotation(frame).                                                                */
+void pt_default_probe_update(uint32_t frame, uint32_t stride, PtProbeUpdate* out);
+/* Host only: the ray rule on the CPU in exact arithmetic.  xys = n x (direction r, slot, sample) inside the update's film of
+ * rays_per_probe x n_upd; out6 = n x (o3, d3).                                                                                   */
+int pt_probe_update_rays_host(const PtProbeGrid* grid, const PtProbeUpdate* upd, const uint32_t* xys, uint32_t n, float* out6);
+/* The same rays from the device's debug-ray form (blocking; needs no scene).  In exact arithmetic the same bits. */
+int pt_debug_probe_update_rays(PtContext* ctx, const PtProbeGrid* grid, const PtProbeUpdate* upd, const uint32_t* xys, uint32_t n,
+                               uint32_t exact_math, float* out6);
+/* The blend on planes the caller holds (k_probe_update; asynchronous on the context's stream; needs no scene).  d_radiance: device
+ * float[n_upd][R][3]; vis may be NULL: no moments, and d_distances and d_moments are not read; else d_distances: device
+ * float[n_upd][R], d_moments: device float[n_probes][T][T][2], 8-byte aligned.  d_sh27: device float[n_probes][9][3]; d_age: device
+ * uint32[n_probes].  sh27, moments and age are updated in place.                                                                 */
+int pt_probe_blend_device(PtContext* ctx, uint32_t n_probes, const PtProbeUpdate* upd, const PtProbeVisibility* vis,
+                          const float* d_radiance, const float* d_distances, float* d_sh27, float* d_moments, uint32_t* d_age);
+/* Host only: the same rule on the CPU, bit for bit, in place on host planes.  Needs no device. */
+int pt_probe_blend_host(uint32_t n_probes, const PtProbeUpdate* upd, const PtProbeVisibility* vis, const float* radiance,
+                        const float* distances, float* sh27, float* moments, uint32_t* age);
+/* The whole update of a grid (asynchronous on the context's stream): the slots' rays through the path kernels into a context-owned
+ * radiance plane (the fifth user of the injected-path driver), with vis their first-hit distances into a context-owned plane, then
+ * pt_probe_blend_device.  Bit-identical to tracing and then blending.  params->spp_offset is the caller's means to draw fresh
+ * continuations per frame.  vis may be NULL (d_moments is then not read).                                                         */
+int pt_probe_grid_update_device(PtContext* ctx, const PtProbeGrid* grid, const PtRenderParams* params, const PtProbeVisibility* vis,
+                                const PtProbeUpdate* upd, float* d_sh27, float* d_moments, uint32_t* d_age);
+/* The same from and into host planes (blocking): sh27 float[count][9][3], moments float[count][T][T][2] (not read when vis is NULL)
+ * and age uint32[count] go through the context's staging and come back updated; the same bits as the device entry.            */
+int pt_probe_grid_update_host(PtContext* ctx, const PtProbeGrid* grid, const PtRenderParams* params, const PtProbeVisibility* vis,
+                              const PtProbeUpdate* upd, float* sh27, float* moments, uint32_t* age);
 
 /* Brightness cascade (additive to ABI 6): a firefly-robust film.  The samples of a render are averaged into the film
  * by an estimator that knows which of them are outliers -- the re-weighting of Zirr, Hanika and Dachsbacher (2018): every sample

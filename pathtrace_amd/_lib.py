@@ -197,6 +197,19 @@ class PtProbeVisibility(C.Structure):
     ]
 
 
+class PtProbeUpdate(C.Structure):
+    _fields_ = [
+        ("rays_per_probe", C.c_uint32),
+        ("first", C.c_uint32),
+        ("stride", C.c_uint32),
+        ("hysteresis", C.c_float),
+        ("change_threshold", C.c_float),
+        ("change_alpha", C.c_float),
+        ("rotation", C.c_float * 9),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class PtCascade(C.Structure):
     _fields_ = [
         ("layers", C.c_uint32),
@@ -428,6 +441,18 @@ SYMBOLS = {
                                                         C.c_void_p, _P(PtProbeVisibility), C.c_void_p, _P(PtProbeShade), C.c_void_p, C.c_void_p]),
     "pt_render_probe_lit_visibility_host": (C.c_int, [C.c_void_p, _P(PtCamera), _P(PtRenderParams), C.c_uint32, _P(PtProbeGrid), C.c_void_p,
                                                       C.c_void_p, _P(PtProbeVisibility), C.c_void_p, _P(PtProbeShade), C.c_void_p, C.c_void_p]),
+    "pt_probe_rotation": (None, [C.c_uint32, C.c_void_p]),
+    "pt_default_probe_update": (None, [C.c_uint32, C.c_uint32, _P(PtProbeUpdate)]),
+    "pt_probe_update_rays_host": (C.c_int, [_P(PtProbeGrid), _P(PtProbeUpdate), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "pt_debug_probe_update_rays": (C.c_int, [C.c_void_p, _P(PtProbeGrid), _P(PtProbeUpdate), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "pt_probe_blend_device": (C.c_int, [C.c_void_p, C.c_uint32, _P(PtProbeUpdate), _P(PtProbeVisibility), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "pt_probe_blend_host": (C.c_int, [C.c_uint32, _P(PtProbeUpdate), _P(PtProbeVisibility), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "pt_probe_grid_update_device": (C.c_int, [C.c_void_p, _P(PtProbeGrid), _P(PtRenderParams), _P(PtProbeVisibility), _P(PtProbeUpdate),
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_probe_grid_update_host": (C.c_int, [C.c_void_p, _P(PtProbeGrid), _P(PtRenderParams), _P(PtProbeVisibility), _P(PtProbeUpdate),
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_default_upsample": (None, [_P(PtUpsample)]),
     "pt_upsample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                      _P(PtUpsample), C.c_void_p, C.c_void_p]),

@@ -359,6 +359,64 @@ def probe_shade_visibility_host(cam, grid, sh27, moments, vis, features, fallbac
     return out, rgba
 
 
+def probe_rotation(frame):
+    """pt_probe_rotation (host only): the rotation of a frame's direction set -> float32[3, 3], row-major; frame 0 is the identity"""
+    out = np.empty((3, 3), dtype=np.float32)
+    lib().pt_probe_rotation(int(frame), _pv(out))
+    return out
+
+
+def default_probe_update(frame=0, stride=1, **over):
+    """pt_default_probe_update for the frame and stride (64 rays, first = frame % stride, hysteresis 0.9375, the change gate off, the
+    frame's rotation) with keyword overrides (None keeps the default); rotation: nine numbers, row-major"""
+    u = _lib.PtProbeUpdate()
+    lib().pt_default_probe_update(int(frame), int(stride), C.byref(u))
+    for k, val in over.items():
+        if val is None:
+            continue
+        if k == "rotation":
+            for i, m in enumerate(np.asarray(val, dtype=np.float32).reshape(9)):
+                u.rotation[i] = float(m)
+        else:
+            setattr(u, k, val)
+    return u
+
+
+def probe_update_slots(n_probes, upd):
+    """the number of probes a call with upd re-traces: ceil((n_probes - first) / stride), first < n_probes"""
+    return 1 + (int(n_probes) - int(upd.first) - 1) // int(upd.stride)
+
+
+def probe_update_rays_host(grid, upd, xys):
+    """pt_probe_update_rays_host (host only): the rays of an update on the CPU in exact arithmetic.  xys n x (direction, slot, sample)
+    -> float32[n, 6] = origin3, direction3"""
+    xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+    out = np.empty((xys.shape[0], 6), dtype=np.float32)
+    check(lib().pt_probe_update_rays_host(C.byref(grid), C.byref(upd), _pu(xys), xys.shape[0], _pv(out)))
+    return out
+
+
+def probe_blend_host(upd, vis, radiance, distances, sh27, moments, age):
+    """pt_probe_blend_host (host only): the update's projection and blend on the CPU.  radiance f32[n_upd, R, 3] and distances
+    f32[n_upd, R] of the call's slots (vis None: no distances, no moments), sh27 f32[P, 9, 3], moments f32[P, T, T, 2], age u32[P] ->
+    the new (sh27, moments or None, age); the inputs are not written"""
+    sh = np.array(sh27, dtype=np.float32, order="C")
+    ag = np.array(age, dtype=np.uint32, order="C")
+    rad = np.ascontiguousarray(radiance, dtype=np.float32)
+    P = ag.size
+    if sh.size != 27 * P or rad.ndim != 3 or rad.shape[2] != 3:
+        raise ValueError("probe_blend_host: radiance f32[n_upd, R, 3], sh27 f32[P, 9, 3], age u32[P]")
+    dist = mom = None
+    if vis is not None:
+        dist = np.ascontiguousarray(distances, dtype=np.float32)
+        mom = np.array(moments, dtype=np.float32, order="C")
+        if dist.shape != rad.shape[:2] or mom.size != 2 * P * int(vis.resolution) ** 2:
+            raise ValueError("probe_blend_host: distances f32[n_upd, R], moments f32[P, T, T, 2]")
+    check(lib().pt_probe_blend_host(P, C.byref(upd), None if vis is None else C.byref(vis), _pv(rad), None if dist is None else _pv(dist),
+                                    _pv(sh), None if mom is None else _pv(mom), ag.ctypes.data_as(C.c_void_p)))
+    return sh, mom, ag
+
+
 def upsample_host(lo_linear, lo_features, features, sigma_n=None, sigma_d=None):
     """pt_upsample_host: the upsampling rule on the CPU (no device, no context), on a low film (f32[h,w,3]), its features
     (f32[h,w,8]) and the full-size features (f32[H,W,8]).  -> (linear f32[H,W,3], rgba u8[H,W,4])"""
@@ -1051,6 +1109,61 @@ class _ContextFunctions:
         self._on_stream(lib().pt_render_probe_lit_visibility_device, C.byref(cam), C.byref(params), int(feature_samples), C.byref(grid), sh, mom,
                         C.byref(vis), fb, C.byref(shade), out, rgba)
         return out, rgba
+
+    def probe_update_rays(self, grid, upd, xys, exact_math=0):
+        """pt_debug_probe_update_rays: the device's rays of an update; arguments as probe_update_rays_host -> float32[n, 6]"""
+        xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+        out = np.empty((xys.shape[0], 6), dtype=np.float32)
+        check(lib().pt_debug_probe_update_rays(self._h, C.byref(grid), C.byref(upd), _pu(xys), xys.shape[0], exact_math, _pv(out)))
+        return out
+
+    def _probe_state(self, who, P, vis, sh27, moments, age):
+        """the planes an update writes in place: contiguous torch tensors on this context's device"""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def plane(t, dtypes, numel, name):
+            if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype in dtypes and t.is_contiguous() and (numel is None or t.numel() == numel)):
+                raise ValueError("%s: %s must be a contiguous tensor on this context's device (it is updated in place)" % (who, name))
+
+        plane(sh27, (torch.float32,), 27 * P, "sh27 f32[P, 9, 3]")
+        plane(age, (torch.int32, torch.uint32), P, "age i32[P]")
+        if vis is not None:                                  # (without a visibility struct the maps are not read)
+            T = int(vis.resolution)
+            plane(moments, (torch.float32,), 2 * T * T * P if 2 <= T <= 16 else None, "moments f32[P, T, T, 2]")      # (another T: the library refuses)
+
+    def probe_blend(self, upd, vis, radiance, distances, sh27, moments, age):
+        """pt_probe_blend_device: k_probe_update on planes the caller holds.  radiance f32[n_upd, R, 3] and distances f32[n_upd, R] of
+        the call's slots (numpy or device tensors; vis None: no distances, no moments); sh27 f32[P, 9, 3], moments f32[P, T, T, 2]
+        and age i32[P] are torch device tensors, updated in place.  Needs no scene."""
+        P = int(age.numel())
+        self._probe_state("probe_blend", P, vis, sh27, moments, age)
+        rad = self._device_f32(radiance, (3,), "radiance")
+        dist = None if vis is None else self._device_f32(distances, tuple(rad.shape[1:2]), "distances")
+        if rad.dim() != 3 or (dist is not None and tuple(dist.shape) != tuple(rad.shape[:2])):
+            raise ValueError("probe_blend: radiance f32[n_upd, R, 3], distances f32[n_upd, R]")
+        self._on_stream(lib().pt_probe_blend_device, P, C.byref(upd), None if vis is None else C.byref(vis), rad, dist, sh27,
+                        None if vis is None else moments, age)
+
+    def probe_grid_update(self, grid, params, vis, upd, sh27, moments, age):
+        """pt_probe_grid_update_device: one update of the grid's stored state -- the call's slots re-traced with upd.rays_per_probe rays
+        under upd.rotation and blended into sh27 f32[P, 9, 3], moments f32[P, T, T, 2] (vis None: not read) and age i32[P], torch
+        device tensors, in place.  params.spp_offset draws fresh continuations."""
+        self._probe_state("probe_grid_update", probe_grid_count(grid), vis, sh27, moments, age)
+        self._on_stream(lib().pt_probe_grid_update_device, C.byref(grid), C.byref(params), None if vis is None else C.byref(vis), C.byref(upd), sh27,
+                        None if vis is None else moments, age)
+
+    def probe_grid_update_host(self, grid, params, vis, upd, sh27, moments, age):
+        """pt_probe_grid_update_host: probe_grid_update from and into host planes -> the new (sh27 f32[P, 9, 3], moments f32[P, T, T, 2]
+        or None, age u32[P]); the inputs are not written"""
+        P = probe_grid_count(grid)
+        sh, ag = np.array(sh27, dtype=np.float32, order="C"), np.array(age, dtype=np.uint32, order="C")
+        mom = None if vis is None else np.array(moments, dtype=np.float32, order="C")
+        if sh.size != 27 * P or ag.size != P or (mom is not None and mom.size != 2 * P * int(vis.resolution) ** 2):
+            raise ValueError("probe_grid_update_host: sh27 f32[P, 9, 3], moments f32[P, T, T, 2], age u32[P]")
+        check(lib().pt_probe_grid_update_host(self._h, C.byref(grid), C.byref(params), None if vis is None else C.byref(vis), C.byref(upd), _pv(sh),
+                                              None if mom is None else _pv(mom), ag.ctypes.data_as(C.c_void_p)))
+        return sh, mom, ag
 
     def probe_positions(self, grid):
         """pt_debug_probe_positions: the grid's positions as the device writes them -> float32[P, 3]"""

@@ -231,6 +231,10 @@ struct PtContext {
     // staging of its output (the positions go through bake_in); pt_render_probe_lit_visibility_host: device staging of the moment maps
     DevBuf<float> pv_dist, pv_out;
     DevBuf<float2> pv_mom;
+    // pt_probe_grid_update_device: the radiance and the distance plane of the call's slots; pt_probe_grid_update_host:
+    // device staging of the ages (the coefficients go through bake_sh, the maps through pv_mom)
+    DevBuf<float> pu_rad, pu_dist;
+    DevBuf<uint32_t> pu_age;
 };
 
 // What a render does with the f64 film sums (pt_render_progressive carries them across calls).

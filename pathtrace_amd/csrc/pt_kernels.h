@@ -578,7 +578,12 @@ struct ProjF {
     float u[3], v[3], w[3], c[3], aspect, fov720;
     uint32_t kind;
 };
-enum { kSrcCamera = 0, kSrcLens = 1, kSrcProjection = 2, kSrcBake = 3, kSrcRays = 4 };
+enum { kSrcCamera = 0, kSrcLens = 1, kSrcProjection = 2, kSrcBake = 3, kSrcRays = 4, kSrcProbeUpdate = 5 };
+struct ProbeUpdateRule {       // ptupd::Params (pt_probe_update.h)
+    uint32_t rays_per_probe, first, stride;
+    float hysteresis, change_threshold, change_alpha, rotation[9];
+    uint32_t reserved;
+};
 struct RaySourceF {
     uint32_t tag;             // kSrc*: which of the words below are read
     CameraF cam;              // every source: the film's width and height; camera, lens, projection: the frame
@@ -592,6 +597,11 @@ struct RaySourceF {
         const float* rays6;   // float[n][3], or null = 1
         const float* weights3;
     } rays;
+    struct {                  // an update of a probe grid: the film is directions x slots, slot y = probe
+        double origin[3], spacing[3];      // first + y stride of the grid; rule.rays_per_probe = the film's width
+        uint32_t counts[3];
+        ProbeUpdateRule rule;
+    } upd;
 };
 // launch_source_paths: the source's rays of samples s_base .. s_base + nb - 1 of every tile pixel as n = nb * np path states in the
 // queue form (state s_local * np + tile pixel), for a path-kernel launch with src_mode = 1 to take up from ovf_in.
@@ -605,8 +615,8 @@ struct SourcePathsArgs {
 // launch_source_feature_rays: the source's rays of samples s_base .. s_base + nb - 1 of every image pixel, ray s_local * np + p, as
 // the rays6 launch_debug_hit reads.  launch_debug_source_rays: words = n * (x, y, sample, -) -> out = n * (o3, d3, dx, dy) for the
 // lens, n * (o3, d3, a, b) for a projection, n * (o3, d3) for a bake (x < width and y < the rows: the caller has checked).
-// false: the source has no kernel of that form (paths: all but the camera; feature rays: camera, lens, projection, bake -- there
-// the "image" is directions x probes --; debug rays: lens, projection, bake), nothing was launched.
+// false: the source has no kernel of that form (paths: all but the camera; feature rays: camera, lens, projection, bake, probe
+// update -- there the "image" is directions x probes --; debug rays: lens, projection, bake, probe update), nothing was launched.
 bool launch_source_paths_exact(const SourcePathsArgs& a, hipStream_t st);
 bool launch_source_paths_fast(const SourcePathsArgs& a, hipStream_t st);
 bool launch_source_feature_rays_exact(const RaySourceF& src, uint32_t s_base, uint32_t nb, float* rays6, hipStream_t st);
@@ -661,5 +671,20 @@ struct ProbeMomentsArgs {
 void launch_probe_distances(const int32_t* ids, const float* t, uint32_t n, float* out, hipStream_t st);
 void launch_probe_moments(const ProbeMomentsArgs& a, hipStream_t st);
 void launch_probe_shade_vis(const ProbeShadeArgs& a, const float* moments, uint32_t resolution, hipStream_t st);
+
+// Updates of the irradiance volume over frames (pt_probe_blend_device, pt_probe_grid_update_device; rule: pt_probe_update.h, DESIGN.md
+// 5u; film unit).  launch_probe_update: one workgroup per slot; radiance float[n_upd][R][3] and distances float[n_upd][R] (null: no
+// moments; then moments is not read) of the slots -> the slots' probes of sh27, moments and age, in place.  Checked parameters.
+struct ProbeUpdateArgs {
+    const float* radiance;
+    const float* distances;
+    float* sh27;
+    float* moments;
+    uint32_t* age;
+    uint32_t n_probes, resolution, sharpness_log2;
+    float max_distance;
+    ProbeUpdateRule u;
+};
+void launch_probe_update(const ProbeUpdateArgs& a, uint32_t n_upd, hipStream_t st);
 
 }  // namespace ptk

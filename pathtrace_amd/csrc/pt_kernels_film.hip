@@ -13,6 +13,7 @@
 //   pt_film_bake.h       light baking: the mask of a lightmap's empty texels, the per-probe spherical-harmonics reduction
 //   pt_film_probe.h      irradiance volume: the positions of a probe grid, first-hit pixels shaded from its SH coefficients
 //   pt_film_probe_vis.h  its probe visibility: ray distances, per-probe octahedral moment maps, the shading pass that reads them
+//   pt_film_probe_update.h  its updates over frames: the fused projection, moments and hysteresis blend of the re-traced probes
 // None of them has a division or square root whose result depends on the arithmetic mode, so the unit is compiled once, in
 // fast mode (its kernels live in ptk_fast_impl), and serves both modes.
 #include "pt_kernels_scan.h"
@@ -32,3 +33,4 @@
 #include "pt_film_bake.h"
 #include "pt_film_probe.h"
 #include "pt_film_probe_vis.h"
+#include "pt_film_probe_update.h"

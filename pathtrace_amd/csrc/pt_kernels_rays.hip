@@ -18,6 +18,7 @@
 #include "pt_lens.h"
 #include "pt_projection.h"
 #include "pt_bake.h"
+#include "pt_probe_update.h"
 
 namespace PTK_IMPL {
 struct SourceRay {
@@ -165,6 +166,30 @@ struct BakeSource {
     }
 };
 
+// ------------------------------------------------------------------ updates of a probe grid (pt_probe_grid_update_device; rule:
+// pt_probe_update.h).  Film position (x, y) is direction x of slot y: the origin is the position of probe first + y stride
+// by the grid's rule (f64, rounded once), the direction the bake's in this unit's arithmetic under the call's rotation (three
+// fmas; the identity by a select).  Throughput 1; a sample index only chooses the path's continuation.
+struct ProbeUpdateSource {
+    static constexpr bool kTiled = false;           // the whole film: tile row = film row
+    static constexpr uint32_t kDebugFloats = 6;
+    static PT_DEV SourceRay ray(const RaySourceF& s, uint32_t x, uint32_t y, uint32_t, size_t) {
+        static_assert(sizeof(ProbeUpdateRule) == sizeof(ptupd::Params), "ProbeUpdateRule is ptupd::Params");
+        const ptupd::Params& u = reinterpret_cast<const ptupd::Params&>(s.upd.rule);
+        ptgrid::Grid g;
+        for (int k = 0; k < 3; ++k) { g.origin[k] = s.upd.origin[k]; g.spacing[k] = s.upd.spacing[k]; g.counts[k] = s.upd.counts[k]; }
+        g.reserved = 0u;
+        float o[3], d[3];
+        ptgrid::position(g, u.first + y * u.stride, o);
+        ptupd::dir<BakeMath>(x, u.rays_per_probe, u.rotation, ptupd::is_identity(u.rotation), d);
+        SourceRay r;
+        r.o = mk(o[0], o[1], o[2]); r.d = mk(d[0], d[1], d[2]);
+        r.e0 = r.e1 = 0.0f;
+        r.tp = mk(1.0f, 1.0f, 1.0f);
+        return r;
+    }
+};
+
 // ------------------------------------------------------------------ caller rays (pt_render_rays_device): float[n][6] in
 // state order (sample-major, the pixel fastest), the directions taken as given (not normalised); weights3 (float[n][3], or null =
 // 1): the initial throughput.  A lane reads its 24 bytes as three 8-byte words (rays6 is 8-byte aligned).
@@ -272,6 +297,7 @@ bool PT_LAUNCH(launch_source_paths)(const SourcePathsArgs& a, hipStream_t st) {
     case kSrcProjection: return launch_per_item(k_source_paths<ProjectionSource>, a.n, st, a);
     case kSrcBake: return launch_per_item(k_source_paths<BakeSource>, a.n, st, a);
     case kSrcRays: return launch_per_item(k_source_paths<CallerSource>, a.n, st, a);
+    case kSrcProbeUpdate: return launch_per_item(k_source_paths<ProbeUpdateSource>, a.n, st, a);
     default: return false;
     }
 }
@@ -283,6 +309,7 @@ bool PT_LAUNCH(launch_source_feature_rays)(const RaySourceF& src, uint32_t s_bas
     case kSrcLens: return launch_per_item(k_source_feature_rays<LensSource>, n, st, src, s_base, nb, rays6);
     case kSrcProjection: return launch_per_item(k_source_feature_rays<ProjectionSource>, n, st, src, s_base, nb, rays6);
     case kSrcBake: return launch_per_item(k_source_feature_rays<BakeSource>, n, st, src, s_base, nb, rays6);
+    case kSrcProbeUpdate: return launch_per_item(k_source_feature_rays<ProbeUpdateSource>, n, st, src, s_base, nb, rays6);
     default: return false;
     }
 }
@@ -292,6 +319,7 @@ bool PT_LAUNCH(launch_debug_source_rays)(const RaySourceF& src, const uint32_t* 
     case kSrcLens: return launch_per_item(k_debug_source_rays<LensSource>, n, st, src, words, n, out);
     case kSrcProjection: return launch_per_item(k_debug_source_rays<ProjectionSource>, n, st, src, words, n, out);
     case kSrcBake: return launch_per_item(k_debug_source_rays<BakeSource>, n, st, src, words, n, out);
+    case kSrcProbeUpdate: return launch_per_item(k_debug_source_rays<ProbeUpdateSource>, n, st, src, words, n, out);
     default: return false;
     }
 }

@@ -11,7 +11,8 @@
 //   pt_kernels_film.hip   the kernels on the film and the device-side BVH refit / builds  the main unit's options
 //                         (fast mode only), one header per concern: pt_film_exchange.h, _adaptive.h, _denoise.h, _temporal.h
 //                         (accumulation and gradients), _bvh.h, _tonemap.h, _upsample.h, _cascade.h, _filter.h, _bloom.h,
-//                         _bake.h, _probe.h (k_probe_positions, k_probe_shade), _probe_vis.h (k_probe_distances, k_probe_moments, k_probe_shade_vis)
+//                         _bake.h, _probe.h (k_probe_positions, k_probe_shade), _probe_vis.h (k_probe_distances, k_probe_moments, k_probe_shade_vis),
+//                         _probe_update.h (k_probe_update)
 // Shared device code: pt_kernels_scan.h (primitive tests, scene staging, scans), pt_kernels_vertex.h (one path vertex).
 // Kernel templates are instantiated where their launcher is; the launchers that cross units are declared in pt_kernels.h.
 #pragma once

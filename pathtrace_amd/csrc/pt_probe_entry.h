@@ -1,5 +1,6 @@
 // pt_probe_entry.h -- what the two host files of the irradiance volume share (internal to csrc/): the checks and passes of
-// pt_probe_grid.cpp that the probe-visibility entries of pt_probe_vis.cpp run with their moment maps.
+// pt_probe_grid.cpp that the probe-visibility entries of pt_probe_vis.cpp run with their moment maps, and the checks and the
+// distance pass of pt_probe_vis.cpp that the update entries of pt_probe_update.cpp run with their own ray source.
 #pragma once
 #include "pt_entry.h"
 #include "pt_probe_grid.h"
@@ -29,5 +30,13 @@ void shade_host(const PtCamera* cam, const PtProbeGrid* g, const float* sh27, co
 // probe_lit_impl from and into host buffers through the context's staging
 int probe_lit_host(PtContext* c, const PtCamera* cam, const PtRenderParams* prm, uint32_t feature_samples, const PtProbeGrid* g, const float* sh27,
                    const float* fallback, const PtProbeShade* sp, float* out_linear, uint8_t* out_rgba, const Maps& maps = {});
+
+// ---- pt_probe_vis.cpp
+// the parameters of the maps, and the plane where there is one (moments_too: 8-byte aligned)
+int check_visibility(const char* who, const PtProbeVisibility* vis, const void* moments, bool moments_too = true);
+// the first-hit distances of n_rows x R rays of a source whose film has one row per probe, in chunks of whole rows through the
+// feature pass's scratch: source(ctx, base, nb) is the source of the rows base .. base + nb - 1.  Everything checked by the caller.
+using RowSource = ptk::RaySourceF (*)(const void* ctx, uint32_t base, uint32_t nb);
+int distances_of(PtContext* c, uint32_t n_rows, uint32_t R, const PtRenderParams* prm, float* d_out, RowSource source, const void* ctx);
 
 }  // namespace ptprobe

@@ -12,14 +12,14 @@
 
 using namespace ptprobe;
 
-namespace {
-
 static_assert(sizeof(PtProbeVisibility) == sizeof(ptvis::Params) && offsetof(PtProbeVisibility, max_distance) == offsetof(ptvis::Params, max_distance) &&
                   offsetof(PtProbeVisibility, sharpness_log2) == offsetof(ptvis::Params, sharpness_log2),
               "ptvis::Params is PtProbeVisibility");
 
+namespace ptprobe {
+
 // the parameters of the maps, and the plane where there is one (moments_too)
-int check_visibility(const char* who, const PtProbeVisibility* vis, const void* moments, bool moments_too = true) {
+int check_visibility(const char* who, const PtProbeVisibility* vis, const void* moments, bool moments_too) {
     if (!vis) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (vis->resolution < ptvis::kMinResolution || vis->resolution > ptvis::kMaxResolution)
         return fail(PT_ERR_INVALID_ARG, "%s: resolution %u not in [%u, %u]", who, vis->resolution, ptvis::kMinResolution, ptvis::kMaxResolution);
@@ -28,15 +28,11 @@ int check_visibility(const char* who, const PtProbeVisibility* vis, const void* 
     if (!(vis->max_distance > 0.0f) || !std::isfinite(vis->max_distance)) return fail(PT_ERR_INVALID_ARG, "%s: max_distance must be finite and > 0", who);
     return moments_too ? check_plane(who, "the moments plane", moments, 8) : PT_OK;
 }
-int check_probe_rays(const char* who, uint32_t n_probes, uint32_t rays_per_probe) {
-    if (n_probes == 0 || n_probes > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: n_probes must be in [1, 65535]", who);
-    if (rays_per_probe == 0 || rays_per_probe > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: rays_per_probe must be in [1, 65535]", who);
-    return PT_OK;
-}
 
-// The distances of n_probes x R probe rays into d_out, everything checked: per chunk of whole probes the bake's feature-ray form,
-// the first-hit pass of the feature entries, k_probe_distances.  No path kernel.
-int distances_impl(PtContext* c, const float* d_positions3, uint32_t n_probes, uint32_t R, const PtRenderParams* prm, float* d_out) {
+// The distances of n_rows x R probe rays into d_out, everything checked: per chunk of whole rows the source's feature-ray form
+// (source(ctx, base, nb): the film of the rows base .. base + nb - 1), the first-hit pass of the feature entries, k_probe_distances.
+// No path kernel.
+int distances_of(PtContext* c, uint32_t n_rows, uint32_t R, const PtRenderParams* prm, float* d_out, RowSource source, const void* ctx) {
     int rc;
     uint32_t accel = prm->accel;
     if (accel == PT_ACCEL_AUTO) {
@@ -45,7 +41,7 @@ int distances_impl(PtContext* c, const float* d_positions3, uint32_t n_probes, u
         if (!accel) g_err = keep;
     }
     if (accel && (rc = ensure_bvh(c))) return rc;
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_probes, kFeatureRays / R));
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(n_rows, kFeatureRays / R));
     const size_t n_rays = (size_t)chunk * R;
     if ((rc = c->ft_rays.ensure(6 * n_rays)) || (rc = c->ft_ids.ensure(n_rays)) || (rc = c->ft_t.ensure(n_rays)) ||
         (accel && (rc = c->ft_scratch.ensure(3 * n_rays))))
@@ -53,16 +49,37 @@ int distances_impl(PtContext* c, const float* d_positions3, uint32_t n_probes, u
     const ptk::SceneView sv = view_for(c, prm->exact_math);
     const hipStream_t st = c->stream;
     const float t_min = (float)prm->t_min, t_max = INFINITY;
-    for (uint32_t base = 0; base < n_probes; base += chunk) {
-        const uint32_t nb = std::min(chunk, n_probes - base), n = nb * R;
-        if (!ptk::launch_source_feature_rays(prm->exact_math, bake_source(ptbake::kProbe, R, nb, d_positions3 + 3 * (size_t)base), 0u, 1u, c->ft_rays.p, st))
-            return fail(PT_ERR_INVALID_ARG, "the bake has no feature-ray kernel");
+    for (uint32_t base = 0; base < n_rows; base += chunk) {
+        const uint32_t nb = std::min(chunk, n_rows - base), n = nb * R;
+        if (!ptk::launch_source_feature_rays(prm->exact_math, source(ctx, base, nb), 0u, 1u, c->ft_rays.p, st))
+            return fail(PT_ERR_INVALID_ARG, "the ray source has no feature-ray kernel");
         if (prm->exact_math) ptk::launch_debug_hit_exact(sv, accel, c->ft_rays.p, n, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, nullptr, st);
         else ptk::launch_debug_hit_fast(sv, accel, c->ft_rays.p, n, t_min, t_max, c->ft_scratch.p, c->ft_ids.p, c->ft_t.p, nullptr, st);
         ptk::launch_probe_distances(c->ft_ids.p, c->ft_t.p, n, d_out + (size_t)base * R, st);
         HIP_TRY(hipGetLastError());
     }
     return PT_OK;
+}
+
+}  // namespace ptprobe
+
+namespace {
+
+int check_probe_rays(const char* who, uint32_t n_probes, uint32_t rays_per_probe) {
+    if (n_probes == 0 || n_probes > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: n_probes must be in [1, 65535]", who);
+    if (rays_per_probe == 0 || rays_per_probe > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: rays_per_probe must be in [1, 65535]", who);
+    return PT_OK;
+}
+
+// the distances of the bake's rays from given positions
+struct BakeRows { const float* d_positions3; uint32_t R; };
+ptk::RaySourceF bake_rows(const void* ctx, uint32_t base, uint32_t nb) {
+    const BakeRows* b = static_cast<const BakeRows*>(ctx);
+    return bake_source(ptbake::kProbe, b->R, nb, b->d_positions3 + 3 * (size_t)base);
+}
+int distances_impl(PtContext* c, const float* d_positions3, uint32_t n_probes, uint32_t R, const PtRenderParams* prm, float* d_out) {
+    const BakeRows rows{d_positions3, R};
+    return distances_of(c, n_probes, R, prm, d_out, bake_rows, &rows);
 }
 int check_distances(const char* who, const PtContext* c, const void* positions3, uint32_t n_probes, uint32_t R, const PtRenderParams* prm, const void* out) {
     if (!c || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);

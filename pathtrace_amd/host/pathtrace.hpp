@@ -617,6 +617,31 @@ public:
                                                   fallback ? fb.data() : nullptr, &s, lin.data(), rgba.data()));
         unpack(lin, rgba);
     }
+    // Updates of the volume over frames.  update_probe_grid (pt_probe_grid_update_host): the probes first, first +
+    // stride, ... are re-traced with upd.rays_per_probe rays under upd.rotation and blended into sh27 (count x 27), moments (count x T
+    // x T x 2; vis null: not read) and age (count) in place, with params()'s spp, spp_offset (fresh continuations per frame),
+    // integrator and depths.  After set_object() the scene is updated first, as in every render.
+    void update_probe_grid(const PtProbeGrid& grid, const PtProbeVisibility* vis, const PtProbeUpdate& upd, std::vector<float>& sh27,
+                           std::vector<float>& moments, std::vector<uint32_t>& age, int device = 0) {
+        const size_t count = pt_probe_grid_count(&grid);
+        if (count == 0 || sh27.size() != count * 27 || age.size() != count)
+            throw std::runtime_error("update_probe_grid: sh27 must hold count x 27 floats and age count words");
+        if (vis && moments.size() != count * vis->resolution * vis->resolution * 2)
+            throw std::runtime_error("update_probe_grid: moments must hold count x T x T x 2 floats");
+        scene(device);
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        check(pt_probe_grid_update_host(ctx_, &grid, &p, vis, &upd, sh27.data(), vis ? moments.data() : nullptr, age.data()));
+    }
+    // The same on DEVICE planes the caller holds (pt_probe_grid_update_device): asynchronous on the context's stream, the caller keeps
+    // the planes alive until that stream has passed the call.
+    void update_probe_grid_device(const PtProbeGrid& grid, const PtProbeVisibility* vis, const PtProbeUpdate& upd, float* d_sh27, float* d_moments,
+                                  uint32_t* d_age, int device = 0) {
+        scene(device);
+        PtRenderParams p = params_;
+        p.band_rows = 0; p.band_index = 0; p.band_count = 1;
+        check(pt_probe_grid_update_device(ctx_, &grid, &p, vis, &upd, d_sh27, d_moments, d_age));
+    }
     // render_denoised() through the lens (pt_render_lens_denoised): the features are those of the lens rays.
     void render_lens_denoised(const PtLens& lens, uint32_t feature_samples = 4, const PtDenoise* dn = nullptr, std::vector<Vector3>* noisy = nullptr,
                               int device = 0) {

@@ -181,6 +181,19 @@ pub struct PtProbeVisibility {
     pub max_distance: f32,
     pub reserved: u32,
 }
+/// pt_probe_grid_update_device, pt_probe_blend_*: one update of the irradiance volume over frames (include/pathtrace_amd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PtProbeUpdate {
+    pub rays_per_probe: u32,
+    pub first: u32,
+    pub stride: u32,
+    pub hysteresis: f32,
+    pub change_threshold: f32,
+    pub change_alpha: f32,
+    pub rotation: [f32; 9],
+    pub reserved: u32,
+}
 
 /// pt_render_lens_device: the thin lens beside the camera (include/pathtrace_amd.h); aperture 0 = pinhole.
 #[repr(C)]
@@ -540,6 +553,14 @@ extern "C" {
     pub fn pt_probe_shade_visibility_host(cam: *const PtCamera, grid: *const PtProbeGrid, sh27: *const f32, moments: *const f32, vis: *const PtProbeVisibility, features: *const f32, fallback_linear: *const f32, shade: *const PtProbeShade, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_probe_lit_visibility_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, grid: *const PtProbeGrid, d_sh27: *const f32, d_moments: *const f32, vis: *const PtProbeVisibility, d_fallback_linear: *const f32, shade: *const PtProbeShade, d_out_linear: *mut f32, d_out_rgba8: *mut u8) -> c_int;
     pub fn pt_render_probe_lit_visibility_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, feature_samples: u32, grid: *const PtProbeGrid, sh27: *const f32, moments: *const f32, vis: *const PtProbeVisibility, fallback_linear: *const f32, shade: *const PtProbeShade, out_linear: *mut f32, out_rgba8: *mut u8) -> c_int;
+    pub fn pt_probe_rotation(frame: u32, out9: *mut f32);
+    pub fn pt_default_probe_update(frame: u32, stride: u32, out: *mut PtProbeUpdate);
+    pub fn pt_probe_update_rays_host(grid: *const PtProbeGrid, upd: *const PtProbeUpdate, xys: *const u32, n: u32, out6: *mut f32) -> c_int;
+    pub fn pt_debug_probe_update_rays(ctx: *mut PtContext, grid: *const PtProbeGrid, upd: *const PtProbeUpdate, xys: *const u32, n: u32, exact_math: u32, out6: *mut f32) -> c_int;
+    pub fn pt_probe_blend_device(ctx: *mut PtContext, n_probes: u32, upd: *const PtProbeUpdate, vis: *const PtProbeVisibility, d_radiance: *const f32, d_distances: *const f32, d_sh27: *mut f32, d_moments: *mut f32, d_age: *mut u32) -> c_int;
+    pub fn pt_probe_blend_host(n_probes: u32, upd: *const PtProbeUpdate, vis: *const PtProbeVisibility, radiance: *const f32, distances: *const f32, sh27: *mut f32, moments: *mut f32, age: *mut u32) -> c_int;
+    pub fn pt_probe_grid_update_device(ctx: *mut PtContext, grid: *const PtProbeGrid, params: *const PtRenderParams, vis: *const PtProbeVisibility, upd: *const PtProbeUpdate, d_sh27: *mut f32, d_moments: *mut f32, d_age: *mut u32) -> c_int;
+    pub fn pt_probe_grid_update_host(ctx: *mut PtContext, grid: *const PtProbeGrid, params: *const PtRenderParams, vis: *const PtProbeVisibility, upd: *const PtProbeUpdate, sh27: *mut f32, moments: *mut f32, age: *mut u32) -> c_int;
     pub fn pt_default_cascade(out: *mut PtCascade);
     pub fn pt_render_cascade_device(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, d_linear_rgb: *mut f32, d_rgba8: *mut u8, d_plain_linear: *mut f32) -> c_int;
     pub fn pt_render_cascade_host(ctx: *mut PtContext, cam: *const PtCamera, params: *const PtRenderParams, cs: *const PtCascade, out_linear_rgb: *mut f32, out_rgba8: *mut u8, out_plain_linear: *mut f32, out_layers: *mut f64, out_weights: *mut f32) -> c_int;

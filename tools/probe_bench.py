@@ -94,6 +94,59 @@ def visibility(a):
     ctx.close()
 
 
+def update(a):
+    """--update, one JSON line, builtin scene 2, 16^3 probes, T = 8: k_probe_update on 4096 slots x 64 rays beside
+    k_probe_sh + k_probe_moments on the same planes (us); one stride-8 update of 64 rays end to end beside the full bake and
+    visibility pass at 256 rays (ms); the probe-lit frame with the visibility term alone and behind a stride-8 update (ms)."""
+    ctx = pt.Context(0)
+    ctx.upload(pt.builtin_scene(2))
+    dev = torch.device("cuda", 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    L = pt._lib.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    S = a.size
+    cam = pt.camera_new(width=S, height=S)
+    prm1 = pt.default_params(spp=1)
+    g = box_grid(16)
+    P, T = 4096, 8
+    vis = pt.default_probe_visibility(g, resolution=T)
+    sp = pt.default_probe_shade(normal_bias=0.02, weight=1)
+    rad, sh = ctx.bake_probes(pt.probe_grid_positions(g), 64, prm1)
+    dist = ctx.probe_distances(pt.probe_grid_positions(g), 64, prm1)
+    maps = ctx.probe_moments(dist, vis)
+    age = torch.full((P,), 16, dtype=torch.int32, device=dev)
+    lin = torch.empty((S, S, 3), dtype=torch.float32, device=dev)
+    rgba = torch.empty((S, S, 4), dtype=torch.uint8, device=dev)
+    sh2, maps2 = sh.clone(), maps.clone()
+    all_slots = pt.default_probe_update(1, 1)
+    stride8 = pt.default_probe_update(1, 8)
+    out = {"size": S, "runs": a.runs, "reps": a.reps}
+
+    def separate():
+        pt._lib.check(L.pt_sh_project_device(ctx._h, P, 64, p(rad), p(sh2)))
+        pt._lib.check(L.pt_probe_moments_device(ctx._h, p(dist), P, 64, C.byref(vis), p(maps2)))
+
+    kernels = {"k_probe_update": lambda: pt._lib.check(L.pt_probe_blend_device(ctx._h, P, C.byref(all_slots), C.byref(vis), p(rad), p(dist), p(sh), p(maps),
+                                                                               p(age))),
+               "k_probe_update, no maps": lambda: pt._lib.check(L.pt_probe_blend_device(ctx._h, P, C.byref(all_slots), None, p(rad), None, p(sh), None, p(age))),
+               "k_probe_sh + k_probe_moments": separate,
+               "k_probe_sh": lambda: pt._lib.check(L.pt_sh_project_device(ctx._h, P, 64, p(rad), p(sh2)))}
+    out["kernels_us"] = {k: summary(t, 1e3, 2) for k, t in timed(ctx, kernels, a.runs, a.reps).items()}
+
+    def full():
+        pt._lib.check(L.pt_probe_grid_bake_device(ctx._h, C.byref(g), 256, C.byref(prm1), p(sh2)))
+        pt._lib.check(L.pt_probe_grid_visibility_device(ctx._h, C.byref(g), 256, C.byref(prm1), C.byref(vis), p(maps2)))
+
+    upd_call = lambda: pt._lib.check(L.pt_probe_grid_update_device(ctx._h, C.byref(g), C.byref(prm1), C.byref(vis), C.byref(stride8), p(sh), p(maps), p(age)))
+    frame_call = lambda: pt._lib.check(L.pt_render_probe_lit_visibility_device(ctx._h, C.byref(cam), C.byref(prm1), 1, C.byref(g), p(sh), p(maps),
+                                                                               C.byref(vis), None, C.byref(sp), p(lin), p(rgba)))
+    whole = {"update stride 8, 64 rays": upd_call, "bake + visibility, 256 rays": full, "probe_lit_visibility": frame_call,
+             "update stride 8 + probe_lit_visibility": lambda: (upd_call(), frame_call())}
+    out["calls_ms"] = {k: summary(t, 1.0, 4) for k, t in timed(ctx, whole, a.runs, 4).items()}
+    print(json.dumps(out))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=1024)
@@ -101,9 +154,12 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--ref-spp", type=int, default=4096)
     ap.add_argument("--visibility", action="store_true", help="the probe-visibility kernels and frame instead (DESIGN.md 5t)")
+    ap.add_argument("--update", action="store_true", help="the update kernel and calls instead (DESIGN.md 5u)")
     a = ap.parse_args()
     if a.visibility:
         return visibility(a)
+    if a.update:
+        return update(a)
     ctx = pt.Context(0)
     ctx.upload(pt.builtin_scene(2))
     dev = torch.device("cuda", 0)
