@@ -32,6 +32,9 @@
 //      sh[p][k][c] = (float)(((4 pi) / R) * S),      S = sum over r of (double)radiance[p][r][c] * Y_k(d_r)
 //    S in a fixed order: lane j of 64 sums r = j, j + 64, ... ascending (acc = acc + product, the product rounded first); then the
 //    tree  v[j] = v[j] + v[j + h] for j < h,  h = 32, 16, 8, 4, 2, 1;  S = v[0].  Host and device agree bit for bit.
+//    One text per piece, for the bake and for the updates over frames (pt_probe_update.h), whose directions are rotated: one ray's
+//    nine-by-three terms are sh_add, a lane's share of a bake sh_lane, the tree sh_tree on the host and sh_wave_tree (pt_film_bake.h)
+//    on the device, the output word sh_finish.
 //
 // Irradiance from SH (host): E_c(n) = sum_k A_l sh[k][c] Y_k(n), A = (pi, 2 pi / 3, pi / 4), f64, n normalised in f64 first.
 #pragma once
@@ -159,6 +162,20 @@ PT_AD_HD void sh_basis(double x, double y, double z, double Y[9]) {
     Y[8] = 0.546274 * (xx - yy);
 }
 
+// one ray's terms into a lane's 27 sums: d = the ray's f32 direction widened, rad = its radiance
+PT_AD_HD void sh_add(const double d[3], const float rad[3], double acc[27]) {
+    double Y[9];
+    sh_basis(d[0], d[1], d[2], Y);
+    const double v[3] = {(double)rad[0], (double)rad[1], (double)rad[2]};
+    PT_BAKE_UNROLL
+    for (int k = 0; k < 9; ++k)
+        PT_BAKE_UNROLL
+        for (int c = 0; c < 3; ++c) {
+            const double p = v[c] * Y[k];
+            acc[3 * k + c] = acc[3 * k + c] + p;
+        }
+}
+
 // lane `lane`'s share of one probe's 27 sums; rad = the probe's float[R][3]
 PT_AD_HD void sh_lane(uint32_t lane, uint32_t R, const float* rad, double acc[27]) {
     PT_BAKE_UNROLL
@@ -166,16 +183,8 @@ PT_AD_HD void sh_lane(uint32_t lane, uint32_t R, const float* rad, double acc[27
     for (uint32_t r = lane; r < R; r += kLanes) {
         float d[3];
         probe_dir<Exact>(r, R, d);
-        double Y[9];
-        sh_basis((double)d[0], (double)d[1], (double)d[2], Y);
-        const double v[3] = {(double)rad[3 * (size_t)r], (double)rad[3 * (size_t)r + 1], (double)rad[3 * (size_t)r + 2]};
-        PT_BAKE_UNROLL
-        for (int k = 0; k < 9; ++k)
-            PT_BAKE_UNROLL
-            for (int c = 0; c < 3; ++c) {
-                const double p = v[c] * Y[k];
-                acc[3 * k + c] = acc[3 * k + c] + p;
-            }
+        const double dd[3] = {(double)d[0], (double)d[1], (double)d[2]};
+        sh_add(dd, rad + 3 * (size_t)r, acc);
     }
 }
 
@@ -185,13 +194,18 @@ PT_AD_HD float sh_finish(double sum, uint32_t R) {
     return (float)(scale * sum);
 }
 
+// The rule's tree over the lanes' sums on the CPU: S = v[0] afterwards
+inline void sh_tree(double v[kLanes][27]) {
+    for (uint32_t h = kLanes / 2; h >= 1; h /= 2)
+        for (uint32_t j = 0; j < h; ++j)
+            for (int k = 0; k < 27; ++k) v[j][k] = v[j][k] + v[j + h][k];
+}
+
 // The whole projection of one probe on the CPU, in the kernel's order: out27 = [k][c]
 inline void sh_project_probe(uint32_t R, const float* rad, float out27[27]) {
     double v[kLanes][27];
     for (uint32_t j = 0; j < kLanes; ++j) sh_lane(j, R, rad, v[j]);
-    for (uint32_t h = kLanes / 2; h >= 1; h /= 2)
-        for (uint32_t j = 0; j < h; ++j)
-            for (int k = 0; k < 27; ++k) v[j][k] = v[j][k] + v[j + h][k];
+    sh_tree(v);
     for (int k = 0; k < 27; ++k) out27[k] = sh_finish(v[0][k], R);
 }
 

@@ -8,9 +8,18 @@
 //                 pixel of every resolve (alpha 255); the other texels are not touched.  The texel is read as three 8-byte words.
 //   k_probe_sh    one wave per probe.  Lane j adds the terms of directions j, j + 64, ... to its 27 f64 sums (9 coefficients x
 //                 RGB), the direction recomputed from the rule in exact arithmetic (ptbake::Exact: nothing in it depends on this
-//                 unit's arithmetic mode), then the rule's tree over the 64 lanes goes through cross-lane moves: after the step of
-//                 width h lane j < h holds v[j] + v[j + h], which is all the next step reads.  No LDS.
+//                 unit's arithmetic mode), then sh_wave_tree.  No LDS.
+//   sh_wave_tree  the rule's tree over the 64 lanes' sums through cross-lane moves, for k_probe_sh and k_probe_update
+//                 (pt_film_probe_update.h): after the step of width h lane j < h holds v[j] + v[j + h], which is all the next step
+//                 reads; lane 0 ends with S.  The whole wave calls it.
 namespace PTK_IMPL {
+PT_DEV void sh_wave_tree(double acc[27]) {
+#pragma unroll
+    for (uint32_t h = ptbake::kLanes / 2; h >= 1u; h /= 2u) {
+#pragma unroll
+        for (int k = 0; k < 27; ++k) acc[k] = acc[k] + __shfl_down(acc[k], h, (int)ptbake::kLanes);
+    }
+}
 __global__ void __launch_bounds__(kBlock) k_bake_mask(const float* __restrict__ texels6, uint32_t n, float* __restrict__ out_linear,
                                                       uint8_t* __restrict__ out_rgba) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -27,11 +36,7 @@ __global__ void __launch_bounds__(ptbake::kLanes) k_probe_sh(uint32_t rays_per_p
     const uint32_t p = blockIdx.x, lane = threadIdx.x;
     double acc[27];
     ptbake::sh_lane(lane, rays_per_probe, radiance + 3 * (size_t)p * rays_per_probe, acc);
-#pragma unroll
-    for (uint32_t h = ptbake::kLanes / 2; h >= 1u; h /= 2u) {
-#pragma unroll
-        for (int k = 0; k < 27; ++k) acc[k] = acc[k] + __shfl_down(acc[k], h, (int)ptbake::kLanes);
-    }
+    sh_wave_tree(acc);
     if (lane != 0u) return;
 #pragma unroll
     for (int k = 0; k < 27; ++k) sh27[27 * (size_t)p + k] = ptbake::sh_finish(acc[k], rays_per_probe);

@@ -11,18 +11,11 @@
 //                       probe.  The fallback may be the output plane: a thread reads its own 12 bytes before it writes them.
 //                       (A form that staged the table in LDS first was no faster: docs/EXPERIMENTS.md "Irradiance volume".)
 namespace PTK_IMPL {
-PT_DEV ptgrid::Grid pg_grid(const double* origin, const double* spacing, const uint32_t* counts) {
-    ptgrid::Grid g;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { g.origin[k] = origin[k]; g.spacing[k] = spacing[k]; g.counts[k] = counts[k]; }
-    g.reserved = 0u;
-    return g;
-}
-__global__ void __launch_bounds__(kBlock) k_probe_positions(ProbeGridArgs a, uint32_t n, float* __restrict__ out) {
+__global__ void __launch_bounds__(kBlock) k_probe_positions(ptgrid::Grid g, uint32_t n, float* __restrict__ out) {
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
     float v[3];
-    ptgrid::position(pg_grid(a.origin, a.spacing, a.counts), p, v);
+    ptgrid::position(g, p, v);
     out[3 * (size_t)p] = v[0]; out[3 * (size_t)p + 1] = v[1]; out[3 * (size_t)p + 2] = v[2];
 }
 __global__ void __launch_bounds__(kDnBx * kDnBy) k_probe_shade(ProbeShadeArgs a) {
@@ -32,7 +25,7 @@ __global__ void __launch_bounds__(kDnBx * kDnBy) k_probe_shade(ProbeShadeArgs a)
     const float4 f0 = a.feat[2 * p], f1 = a.feat[2 * p + 1];
     const float rec[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
     float v[3];
-    if (!ptgrid::shade(pg_grid(a.grid.origin, a.grid.spacing, a.grid.counts), a.normal_bias, a.weight, a.width, a.height, x, y, rec, a.cam, a.sh27, v)) {
+    if (!ptgrid::shade(a.grid, a.normal_bias, a.weight, a.width, a.height, x, y, rec, a.cam, a.sh27, v)) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) v[k] = a.fallback ? a.fallback[3 * p + k] : 0.0f;
     }
@@ -41,7 +34,7 @@ __global__ void __launch_bounds__(kDnBx * kDnBy) k_probe_shade(ProbeShadeArgs a)
 }
 }  // namespace PTK_IMPL
 namespace ptk {
-void launch_probe_positions(const ProbeGridArgs& g, uint32_t n, float* out, hipStream_t st) {
+void launch_probe_positions(const ptgrid::Grid& g, uint32_t n, float* out, hipStream_t st) {
     if (n) hipLaunchKernelGGL(PTK_IMPL::k_probe_positions, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, g, n, out);
 }
 void launch_probe_shade(const ProbeShadeArgs& a, hipStream_t st) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pt_probe_params.h"    // ptgrid::Grid, ptvis::Params, ptupd::Params
 #include "pt_kernel_consts.h"   // kBlock, kSmallObjs, kRegenWaves*, kRegenSplitF4PerWave, kRegenCounters, kRegenCounterStride
 
 namespace ptk {
@@ -579,11 +580,6 @@ struct ProjF {
     uint32_t kind;
 };
 enum { kSrcCamera = 0, kSrcLens = 1, kSrcProjection = 2, kSrcBake = 3, kSrcRays = 4, kSrcProbeUpdate = 5 };
-struct ProbeUpdateRule {       // ptupd::Params (pt_probe_update.h)
-    uint32_t rays_per_probe, first, stride;
-    float hysteresis, change_threshold, change_alpha, rotation[9];
-    uint32_t reserved;
-};
 struct RaySourceF {
     uint32_t tag;             // kSrc*: which of the words below are read
     CameraF cam;              // every source: the film's width and height; camera, lens, projection: the frame
@@ -598,9 +594,8 @@ struct RaySourceF {
         const float* weights3;
     } rays;
     struct {                  // an update of a probe grid: the film is directions x slots, slot y = probe
-        double origin[3], spacing[3];      // first + y stride of the grid; rule.rays_per_probe = the film's width
-        uint32_t counts[3];
-        ProbeUpdateRule rule;
+        ptgrid::Grid grid;    // first + y stride of the grid; rule.rays_per_probe = the film's width
+        ptupd::Params rule;
     } upd;
 };
 // launch_source_paths: the source's rays of samples s_base .. s_base + nb - 1 of every tile pixel as n = nb * np path states in the
@@ -640,10 +635,6 @@ void launch_probe_sh(uint32_t n_probes, uint32_t rays_per_probe, const float* ra
 // Irradiance volume (pt_probe_grid_bake_device, pt_probe_shade_device; rule: pt_probe_grid.h; film unit, one form
 // for both modes).  launch_probe_positions: the n = nx ny nz positions of a valid grid, 3 floats each.  launch_probe_shade: one
 // thread per pixel of the width x height image; fallback may be null, or out_linear itself; out_rgba may be null.
-struct ProbeGridArgs {
-    double origin[3], spacing[3];
-    uint32_t counts[3];
-};
 struct ProbeShadeArgs {
     const float4* feat;
     const float* sh27;
@@ -651,11 +642,11 @@ struct ProbeShadeArgs {
     float* out_linear;
     uint8_t* out_rgba;
     double cam[12];               // origin, lower_left, horizontal, vertical
-    ProbeGridArgs grid;
+    ptgrid::Grid grid;
     uint32_t width, height, weight;
     float normal_bias;
 };
-void launch_probe_positions(const ProbeGridArgs& g, uint32_t n, float* out, hipStream_t st);
+void launch_probe_positions(const ptgrid::Grid& g, uint32_t n, float* out, hipStream_t st);
 void launch_probe_shade(const ProbeShadeArgs& a, hipStream_t st);
 
 // Probe visibility (pt_probe_distances_device, pt_probe_moments_device, pt_probe_shade_visibility_device; rule: pt_probe_vis.h,
@@ -665,8 +656,8 @@ void launch_probe_shade(const ProbeShadeArgs& a, hipStream_t st);
 struct ProbeMomentsArgs {
     const float* distances;
     float* moments;
-    uint32_t n_probes, rays_per_probe, resolution, sharpness_log2;
-    float max_distance;
+    uint32_t n_probes, rays_per_probe;
+    ptvis::Params vis;
 };
 void launch_probe_distances(const int32_t* ids, const float* t, uint32_t n, float* out, hipStream_t st);
 void launch_probe_moments(const ProbeMomentsArgs& a, hipStream_t st);
@@ -681,9 +672,9 @@ struct ProbeUpdateArgs {
     float* sh27;
     float* moments;
     uint32_t* age;
-    uint32_t n_probes, resolution, sharpness_log2;
-    float max_distance;
-    ProbeUpdateRule u;
+    uint32_t n_probes;
+    ptvis::Params vis;            // all zero without maps
+    ptupd::Params u;
 };
 void launch_probe_update(const ProbeUpdateArgs& a, uint32_t n_upd, hipStream_t st);
 

@@ -174,13 +174,9 @@ struct ProbeUpdateSource {
     static constexpr bool kTiled = false;           // the whole film: tile row = film row
     static constexpr uint32_t kDebugFloats = 6;
     static PT_DEV SourceRay ray(const RaySourceF& s, uint32_t x, uint32_t y, uint32_t, size_t) {
-        static_assert(sizeof(ProbeUpdateRule) == sizeof(ptupd::Params), "ProbeUpdateRule is ptupd::Params");
-        const ptupd::Params& u = reinterpret_cast<const ptupd::Params&>(s.upd.rule);
-        ptgrid::Grid g;
-        for (int k = 0; k < 3; ++k) { g.origin[k] = s.upd.origin[k]; g.spacing[k] = s.upd.spacing[k]; g.counts[k] = s.upd.counts[k]; }
-        g.reserved = 0u;
+        const ptupd::Params& u = s.upd.rule;
         float o[3], d[3];
-        ptgrid::position(g, u.first + y * u.stride, o);
+        ptgrid::position(s.upd.grid, u.first + y * u.stride, o);
         ptupd::dir<BakeMath>(x, u.rays_per_probe, u.rotation, ptupd::is_identity(u.rotation), d);
         SourceRay r;
         r.o = mk(o[0], o[1], o[2]); r.d = mk(d[0], d[1], d[2]);

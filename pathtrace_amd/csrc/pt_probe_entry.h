@@ -10,8 +10,12 @@ namespace ptprobe {
 // The moment maps of a shading pass with the visibility term; none: the pass without it
 struct Maps { const float* moments = nullptr; const PtProbeVisibility* vis = nullptr; };
 
-ptk::ProbeGridArgs kernel_grid(const PtProbeGrid* g);
+// the public grid as the rule and the kernels take it: the one conversion
+ptgrid::Grid rule_grid(const PtProbeGrid* g);
 int check_grid(const char* who, const PtProbeGrid* g);
+// the 1..65535 rows and columns of a probe film
+int check_probe_count(const char* who, uint32_t n_probes);
+int check_rays_per_probe(const char* who, uint32_t rays_per_probe);
 // what a shading pass reads and writes, checked before anything looks at a context; feat_align: 16 on the device, 4 on the host
 int check_shade(const char* who, const PtCamera* cam, const PtProbeGrid* g, const void* sh27, const void* features, const void* fallback,
                 const PtProbeShade* sp, const void* out_linear, const void* out_rgba, uint32_t feat_align, bool own_features = false);
@@ -32,8 +36,10 @@ int probe_lit_host(PtContext* c, const PtCamera* cam, const PtRenderParams* prm,
                    const float* fallback, const PtProbeShade* sp, float* out_linear, uint8_t* out_rgba, const Maps& maps = {});
 
 // ---- pt_probe_vis.cpp
-// the parameters of the maps, and the plane where there is one (moments_too: 8-byte aligned)
-int check_visibility(const char* who, const PtProbeVisibility* vis, const void* moments, bool moments_too = true);
+// the public visibility struct as the rule and the kernels take it: the one conversion; null: all zero, no maps
+ptvis::Params rule_visibility(const PtProbeVisibility* vis);
+// the parameters of the maps, then their plane: 8-byte aligned for a device entry, 4-byte for a host entry
+int check_moments_plane(const char* who, const PtProbeVisibility* vis, const void* moments, bool device);
 // the first-hit distances of n_rows x R rays of a source whose film has one row per probe, in chunks of whole rows through the
 // feature pass's scratch: source(ctx, base, nb) is the source of the rows base .. base + nb - 1.  Everything checked by the caller.
 using RowSource = ptk::RaySourceF (*)(const void* ctx, uint32_t base, uint32_t nb);

@@ -24,11 +24,6 @@ ptgrid::Grid rule_grid(const PtProbeGrid* g) {
     std::memcpy(&r, g, sizeof r);
     return r;
 }
-ptk::ProbeGridArgs kernel_grid(const PtProbeGrid* g) {
-    ptk::ProbeGridArgs a{};
-    for (int k = 0; k < 3; ++k) { a.origin[k] = g->origin[k]; a.spacing[k] = g->spacing[k]; a.counts[k] = g->counts[k]; }
-    return a;
-}
 
 int check_grid(const char* who, const PtProbeGrid* g) {
     if (!g) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
@@ -37,6 +32,14 @@ int check_grid(const char* who, const PtProbeGrid* g) {
                     "%s: invalid probe grid %ux%ux%u: counts >= 1, at most 65535 probes, origin and spacing finite, spacing > 0 on an axis with "
                     "more than one probe",
                     who, g->counts[0], g->counts[1], g->counts[2]);
+    return PT_OK;
+}
+int check_probe_count(const char* who, uint32_t n_probes) {
+    if (n_probes == 0 || n_probes > ptgrid::kMaxProbes) return fail(PT_ERR_INVALID_ARG, "%s: n_probes must be in [1, 65535]", who);
+    return PT_OK;
+}
+int check_rays_per_probe(const char* who, uint32_t rays_per_probe) {
+    if (rays_per_probe == 0 || rays_per_probe > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: rays_per_probe must be in [1, 65535]", who);
     return PT_OK;
 }
 // what a shading pass reads and writes, checked before anything looks at a context; feat_align: 16 on the device, 4 on the host
@@ -64,7 +67,7 @@ int shade_launch(PtContext* c, const PtCamera* cam, const PtProbeGrid* g, const 
     for (int k = 0; k < 3; ++k) {
         a.cam[k] = cam->origin[k]; a.cam[3 + k] = cam->lower_left[k]; a.cam[6 + k] = cam->horizontal[k]; a.cam[9 + k] = cam->vertical[k];
     }
-    a.grid = kernel_grid(g);
+    a.grid = rule_grid(g);
     a.width = cam->width; a.height = cam->height; a.weight = sp->weight; a.normal_bias = sp->normal_bias;
     if (maps.vis) ptk::launch_probe_shade_vis(a, maps.moments, maps.vis->resolution, c->stream);
     else ptk::launch_probe_shade(a, c->stream);
@@ -158,9 +161,7 @@ int pt_probe_grid_bake_device(PtContext* c, const PtProbeGrid* g, uint32_t rays_
     const char* const who = "pt_probe_grid_bake_device";
     if (!c || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = check_grid(who, g))) return rc;
-    if (rays_per_probe == 0 || rays_per_probe > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: rays_per_probe must be in [1, 65535]", who);
-    if ((rc = check_plane(who, "sh27", d_sh27, 4))) return rc;
+    if ((rc = check_grid(who, g)) || (rc = check_rays_per_probe(who, rays_per_probe)) || (rc = check_plane(who, "sh27", d_sh27, 4))) return rc;
     // what the probe bake would refuse behind the positions launch, by its own checks (band_count <= 1 from here on)
     if ((rc = check_whole_image(who, " bakes", "", prm, /*band_index_too=*/false)) || (rc = check_scene(c)) || (rc = check_spp(prm->spp)) ||
         (rc = check_integrator(prm->integrator)) || (rc = check_accel(prm->accel)) || (rc = check_band_index(prm->band_index, 1u)))
@@ -170,7 +171,7 @@ int pt_probe_grid_bake_device(PtContext* c, const PtProbeGrid* g, uint32_t rays_
     if ((rc = c->pg_pos.ensure(3 * (size_t)n)) || (rc = c->pg_rad.ensure(3 * (size_t)n * rays_per_probe))) return rc;
     // (a bake larger than max_paths_in_flight is refused by the bake itself, PT_ERR_UNSUPPORTED, behind this launch, which writes
     // the context's own plane and nothing else)
-    ptk::launch_probe_positions(kernel_grid(g), n, c->pg_pos.p, c->stream);
+    ptk::launch_probe_positions(rule_grid(g), n, c->pg_pos.p, c->stream);
     HIP_TRY(hipGetLastError());
     return pt_bake_probes_device(c, c->pg_pos.p, n, rays_per_probe, prm, c->pg_rad.p, d_sh27);
 }
@@ -211,7 +212,7 @@ int pt_debug_probe_positions(PtContext* c, const PtProbeGrid* g, float* out_posi
     const uint32_t n = pt_probe_grid_count(g);
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = c->pg_pos.ensure(3 * (size_t)n))) return rc;
-    ptk::launch_probe_positions(kernel_grid(g), n, c->pg_pos.p, c->stream);
+    ptk::launch_probe_positions(rule_grid(g), n, c->pg_pos.p, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out_positions3, c->pg_pos.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));

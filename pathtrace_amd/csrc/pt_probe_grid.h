@@ -31,19 +31,13 @@
 #include <stdint.h>
 
 #include "pt_bake.h"          // ptbake::sh_basis, kPi; PT_AD_HD
+#include "pt_probe_params.h"  // ptgrid::Grid
 #include "pt_tonemap.h"       // ptone::transfer_sqrt
 
 namespace ptgrid {
 
 enum { kTrilinear = 0, kFacing = 1, kWeights = 2 };
 constexpr uint32_t kMaxProbes = 65535u;
-
-struct Grid {                 // PtProbeGrid's layout (pt_probe_grid.cpp asserts it)
-    double origin[3];
-    double spacing[3];
-    uint32_t counts[3];
-    uint32_t reserved;
-};
 
 PT_AD_HD bool finite(double v) { return v - v == 0.0; }
 PT_AD_HD bool finitef(float v) { return v - v == 0.0f; }

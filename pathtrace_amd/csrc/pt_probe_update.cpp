@@ -18,15 +18,7 @@ static_assert(sizeof(PtProbeUpdate) == sizeof(ptupd::Params) && offsetof(PtProbe
                   offsetof(PtProbeUpdate, hysteresis) == offsetof(ptupd::Params, hysteresis) &&
                   offsetof(PtProbeUpdate, change_alpha) == offsetof(ptupd::Params, change_alpha),
               "ptupd::Params is PtProbeUpdate");
-static_assert(sizeof(ptk::ProbeUpdateRule) == sizeof(ptupd::Params) && offsetof(ptk::ProbeUpdateRule, first) == offsetof(ptupd::Params, first) &&
-                  offsetof(ptk::ProbeUpdateRule, stride) == offsetof(ptupd::Params, stride) &&
-                  offsetof(ptk::ProbeUpdateRule, hysteresis) == offsetof(ptupd::Params, hysteresis) &&
-                  offsetof(ptk::ProbeUpdateRule, change_threshold) == offsetof(ptupd::Params, change_threshold) &&
-                  offsetof(ptk::ProbeUpdateRule, change_alpha) == offsetof(ptupd::Params, change_alpha) &&
-                  offsetof(ptk::ProbeUpdateRule, rotation) == offsetof(ptupd::Params, rotation) &&
-                  offsetof(ptk::ProbeUpdateRule, reserved) == offsetof(ptupd::Params, reserved),
-              "ptk::ProbeUpdateRule is ptupd::Params, field for field (the kernels read it as one)");
-
+// the public update struct as the rule and the kernels take it: the one conversion
 ptupd::Params rule_update(const PtProbeUpdate* u) {
     ptupd::Params r;
     std::memcpy(&r, u, sizeof r);
@@ -36,7 +28,7 @@ ptupd::Params rule_update(const PtProbeUpdate* u) {
 // the parameters of an update of n_probes probes; the first rule broken answers
 int check_update(const char* who, const PtProbeUpdate* u, uint32_t n_probes) {
     if (!u) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
-    if (u->rays_per_probe == 0 || u->rays_per_probe > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: rays_per_probe must be in [1, 65535]", who);
+    if (int rc = check_rays_per_probe(who, u->rays_per_probe)) return rc;
     if (u->stride == 0) return fail(PT_ERR_INVALID_ARG, "%s: stride must be >= 1", who);
     if (u->first >= n_probes) return fail(PT_ERR_INVALID_ARG, "%s: first %u is not below the %u probes", who, u->first, n_probes);
     if (!std::isfinite(u->hysteresis) || u->hysteresis < 0.0f || !(u->hysteresis < 1.0f))
@@ -54,19 +46,13 @@ int check_update(const char* who, const PtProbeUpdate* u, uint32_t n_probes) {
                     det);
     return PT_OK;
 }
-int check_n_probes(const char* who, uint32_t n_probes) {
-    if (n_probes == 0 || n_probes > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: n_probes must be in [1, 65535]", who);
-    return PT_OK;
-}
-// what a blend reads and writes; align8: the moments plane of the device entries
+// what a blend reads and writes
 int check_blend(const char* who, uint32_t n_probes, const PtProbeUpdate* u, const PtProbeVisibility* vis, const void* radiance, const void* distances,
-                const void* sh27, const void* moments, const void* age, bool align8) {
+                const void* sh27, const void* moments, const void* age, bool device) {
     int rc;
-    if ((rc = check_n_probes(who, n_probes)) || (rc = check_update(who, u, n_probes))) return rc;
+    if ((rc = check_probe_count(who, n_probes)) || (rc = check_update(who, u, n_probes))) return rc;
     if (vis) {
-        if ((rc = check_visibility(who, vis, moments, align8)) || (!align8 && (rc = check_plane(who, "the moments plane", moments, 4))) ||
-            (rc = check_plane(who, "the distances plane", distances, 4)))
-            return rc;
+        if ((rc = check_moments_plane(who, vis, moments, device)) || (rc = check_plane(who, "the distances plane", distances, 4))) return rc;
     } else if (distances) {
         return fail(PT_ERR_INVALID_ARG, "%s: a distances plane without a visibility struct", who);
     }
@@ -90,8 +76,8 @@ ptk::RaySourceF update_source(const PtProbeGrid* g, const PtProbeUpdate* u, uint
     ptk::RaySourceF s{};
     s.tag = ptk::kSrcProbeUpdate;
     s.cam = camera_f32(&cam);
-    for (int k = 0; k < 3; ++k) { s.upd.origin[k] = g->origin[k]; s.upd.spacing[k] = g->spacing[k]; s.upd.counts[k] = g->counts[k]; }
-    std::memcpy(&s.upd.rule, u, sizeof s.upd.rule);
+    s.upd.grid = rule_grid(g);
+    s.upd.rule = rule_update(u);
     s.upd.rule.first = u->first + base * u->stride;
     return s;
 }
@@ -121,8 +107,8 @@ void blend_launch(PtContext* c, uint32_t n_probes, const PtProbeUpdate* u, const
     ptk::ProbeUpdateArgs a{};
     a.radiance = d_radiance; a.distances = vis ? d_distances : nullptr; a.sh27 = d_sh27; a.moments = vis ? d_moments : nullptr; a.age = d_age;
     a.n_probes = n_probes;
-    if (vis) { a.resolution = vis->resolution; a.sharpness_log2 = vis->sharpness_log2; a.max_distance = vis->max_distance; }
-    std::memcpy(&a.u, u, sizeof a.u);
+    a.vis = rule_visibility(vis);
+    a.u = rule_update(u);
     ptk::launch_probe_update(a, ptupd::slots(n_probes, u->first, u->stride), c->stream);
 }
 
@@ -131,30 +117,15 @@ void blend_launch(PtContext* c, uint32_t n_probes, const PtProbeUpdate* u, const
 void update_probe(const ptupd::Params& u, const ptvis::Params* vis, const float* rad, const float* dist, float* sh27, float* moments, uint32_t* age) {
     const uint32_t R = u.rays_per_probe, old_age = *age;
     const bool id = ptupd::is_identity(u.rotation);
-    std::vector<double> rays(4 * (size_t)R), v((size_t)ptbake::kLanes * 27, 0.0);
+    std::vector<double> rays(4 * (size_t)R);
     for (uint32_t r = 0; r < R; ++r) ptupd::stage_ray(r, R, u.rotation, id, vis != nullptr, vis ? dist[r] : 0.0f, vis ? vis->max_distance : 0.0f, &rays[4 * (size_t)r]);
-    for (uint32_t j = 0; j < ptbake::kLanes; ++j)
-        for (uint32_t r = j; r < R; r += ptbake::kLanes) ptupd::sh_add(&rays[4 * (size_t)r], rad + 3 * (size_t)r, &v[27 * (size_t)j]);
-    for (uint32_t h = ptbake::kLanes / 2; h >= 1; h /= 2)
-        for (uint32_t j = 0; j < h; ++j)
-            for (int k = 0; k < 27; ++k) v[27 * (size_t)j + k] = v[27 * (size_t)j + k] + v[27 * (size_t)(j + h) + k];
-    float nw[27];
-    for (int k = 0; k < 27; ++k) nw[k] = ptbake::sh_finish(v[k], R);
-    const float old0[3] = {sh27[0], sh27[1], sh27[2]};
-    const double a = ptupd::alpha(u, old_age, old0, nw);
-    for (int k = 0; k < 27; ++k) sh27[k] = ptupd::blend(sh27[k], nw[k], a, old_age);
-    if (vis) {
-        const uint32_t T = vis->resolution;
-        for (uint32_t t = 0; t < T * T; ++t) {
-            double n[3], S[3] = {0.0, 0.0, 0.0};
-            ptvis::oct_decode(ptvis::centre(T, t % T), ptvis::centre(T, t / T), n);
-            for (uint32_t r = 0; r < R; ++r) ptvis::add_ray(n, &rays[4 * (size_t)r], vis->sharpness_log2, S);
-            float m[2];
-            ptvis::finish(S, vis->max_distance, m);
-            moments[2 * t] = ptupd::blend(moments[2 * t], m[0], a, old_age);
-            moments[2 * t + 1] = ptupd::blend(moments[2 * t + 1], m[1], a, old_age);
-        }
-    }
+    float new_sh[27], new_moments[2 * ptvis::kMaxResolution * ptvis::kMaxResolution];
+    ptupd::sh_project_staged(R, rays.data(), rad, new_sh);
+    const uint32_t n_moments = vis ? 2u * vis->resolution * vis->resolution : 0u;
+    if (vis) ptvis::probe_moments(*vis, R, rays.data(), new_moments);
+    const double a = ptupd::alpha(u, old_age, sh27, new_sh);
+    for (int k = 0; k < 27; ++k) sh27[k] = ptupd::blend(sh27[k], new_sh[k], a, old_age);
+    for (uint32_t k = 0; k < n_moments; ++k) moments[k] = ptupd::blend(moments[k], new_moments[k], a, old_age);
     *age = ptupd::next_age(old_age);
 }
 
@@ -164,9 +135,8 @@ int check_grid_update(const char* who, const PtContext* c, const PtProbeGrid* g,
     if (!c || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
     if ((rc = check_grid(who, g))) return rc;
-    if ((rc = check_update(who, u, pt_probe_grid_count(g))) || (vis && (rc = check_visibility(who, vis, moments, device))) ||
-        (vis && !device && (rc = check_plane(who, "the moments plane", moments, 4))) || (rc = check_plane(who, "sh27", sh27, 4)) ||
-        (rc = check_plane(who, "the age plane", age, 4)))
+    if ((rc = check_update(who, u, pt_probe_grid_count(g))) || (vis && (rc = check_moments_plane(who, vis, moments, device))) ||
+        (rc = check_plane(who, "sh27", sh27, 4)) || (rc = check_plane(who, "the age plane", age, 4)))
         return rc;
     // what the render of the slots would refuse, by its own checks
     if ((rc = check_whole_image(who, " updates", "", prm, /*band_index_too=*/false)) || (rc = check_scene(c)) || (rc = check_spp(prm->spp)) ||
@@ -224,8 +194,7 @@ void pt_default_probe_update(uint32_t frame, uint32_t stride, PtProbeUpdate* out
 int pt_probe_update_rays_host(const PtProbeGrid* g, const PtProbeUpdate* u, const uint32_t* xys, uint32_t n, float* out6) {
     const char* const who = "pt_probe_update_rays_host";
     if (int rc = check_rays(who, g, u, xys, n, out6)) return rc;
-    ptgrid::Grid r;
-    std::memcpy(&r, g, sizeof r);
+    const ptgrid::Grid r = rule_grid(g);
     const bool id = ptupd::is_identity(u->rotation);
     for (size_t i = 0; i < n; ++i) {
         float* o = out6 + 6 * i;
@@ -259,8 +228,7 @@ int pt_probe_blend_host(uint32_t n_probes, const PtProbeUpdate* u, const PtProbe
     const char* const who = "pt_probe_blend_host";
     if (int rc = check_blend(who, n_probes, u, vis, radiance, distances, sh27, moments, age, false)) return rc;
     const ptupd::Params r = rule_update(u);
-    ptvis::Params vp{};
-    if (vis) std::memcpy(&vp, vis, sizeof vp);
+    const ptvis::Params vp = rule_visibility(vis);
     const uint32_t R = r.rays_per_probe, n_upd = ptupd::slots(n_probes, r.first, r.stride);
     const size_t tt = vis ? (size_t)vis->resolution * vis->resolution : 0;
     for (uint32_t k = 0; k < n_upd; ++k) {

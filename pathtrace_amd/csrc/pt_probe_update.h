@@ -32,21 +32,11 @@
 // c = 0x9E3779B9, 0x85EBCA6B, 0xC2B2AE35; Shoemake's uniform quaternion q = (sqrt(1 - u0) sin 2 pi u1, sqrt(1 - u0) cos 2 pi u1,
 // sqrt(u0) sin 2 pi u2, sqrt(u0) cos 2 pi u2) = (x, y, z, w) in f64; the matrix in f64, rounded to f32 once.
 #pragma once
-#include "pt_probe_vis.h"     // ptvis::add_ray, finish, clamp_distance; ptgrid; ptbake
+#include "pt_probe_vis.h"     // ptvis::clamp_distance, probe_moments; ptgrid; ptbake; pt_probe_params.h: ptupd::Params
 
 namespace ptupd {
 
 constexpr uint32_t kMaxAge = 65535u;
-
-struct Params {               // PtProbeUpdate's layout (pt_probe_update.cpp asserts it)
-    uint32_t rays_per_probe;
-    uint32_t first, stride;
-    float hysteresis;
-    float change_threshold;
-    float change_alpha;
-    float rotation[9];
-    uint32_t reserved;
-};
 
 PT_AD_HD uint32_t bits(float v) {
     uint32_t u;
@@ -90,26 +80,22 @@ PT_AD_HD void dir(uint32_t r, uint32_t R, const float M[9], bool identity, float
     ptbake::probe_dir<Mth>(r, R, d);
     rotate(M, identity, d, out);
 }
-// ray r of R as ptvis::add_ray takes it and as the SH sums read it: the rotated exact direction widened, the clamped distance
-// (0 where there is no visibility struct)
+// ray r of R as ptvis::add_ray takes it and as ptbake::sh_add reads it: the rotated exact direction widened, the clamped distance
+// (0 where there is no visibility struct).  The one staging of a probe ray: the visibility pass (pt_probe_vis.h) calls it with the
+// identity and a distance
 PT_AD_HD void stage_ray(uint32_t r, uint32_t R, const float M[9], bool identity, bool with_distance, float t, float max_distance, double ray[4]) {
     float d[3];
     dir<ptbake::Exact>(r, R, M, identity, d);
     ray[0] = (double)d[0]; ray[1] = (double)d[1]; ray[2] = (double)d[2];
     ray[3] = with_distance ? ptvis::clamp_distance(t, max_distance) : 0.0;
 }
-// one staged ray's terms into a lane's 27 sums (ptbake::sh_lane's statements)
-PT_AD_HD void sh_add(const double ray[4], const float rad[3], double acc[27]) {
-    double Y[9];
-    ptbake::sh_basis(ray[0], ray[1], ray[2], Y);
-    const double v[3] = {(double)rad[0], (double)rad[1], (double)rad[2]};
-    PT_BAKE_UNROLL
-    for (int k = 0; k < 9; ++k)
-        PT_BAKE_UNROLL
-        for (int c = 0; c < 3; ++c) {
-            const double p = v[c] * Y[k];
-            acc[3 * k + c] = acc[3 * k + c] + p;
-        }
+// New SH of one slot on the CPU from its R staged rays and rad = its float[R][3], in the kernel's order: out27 = [k][c]
+inline void sh_project_staged(uint32_t R, const double* rays4, const float* rad, float out27[27]) {
+    double v[ptbake::kLanes][27] = {};
+    for (uint32_t j = 0; j < ptbake::kLanes; ++j)
+        for (uint32_t r = j; r < R; r += ptbake::kLanes) ptbake::sh_add(rays4 + 4 * (size_t)r, rad + 3 * (size_t)r, v[j]);
+    ptbake::sh_tree(v);
+    for (int k = 0; k < 27; ++k) out27[k] = ptbake::sh_finish(v[0][k], R);
 }
 
 // ---- blend

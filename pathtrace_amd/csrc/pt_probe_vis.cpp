@@ -5,10 +5,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstring>
 #include <vector>
 
 #include "pt_probe_entry.h"
-#include "pt_probe_vis.h"
+#include "pt_probe_update.h"      // ptupd::stage_ray; pt_probe_vis.h
 
 using namespace ptprobe;
 
@@ -18,15 +19,20 @@ static_assert(sizeof(PtProbeVisibility) == sizeof(ptvis::Params) && offsetof(PtP
 
 namespace ptprobe {
 
-// the parameters of the maps, and the plane where there is one (moments_too)
-int check_visibility(const char* who, const PtProbeVisibility* vis, const void* moments, bool moments_too) {
+ptvis::Params rule_visibility(const PtProbeVisibility* vis) {
+    ptvis::Params r{};
+    if (vis) std::memcpy(&r, vis, sizeof r);
+    return r;
+}
+
+int check_moments_plane(const char* who, const PtProbeVisibility* vis, const void* moments, bool device) {
     if (!vis) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     if (vis->resolution < ptvis::kMinResolution || vis->resolution > ptvis::kMaxResolution)
         return fail(PT_ERR_INVALID_ARG, "%s: resolution %u not in [%u, %u]", who, vis->resolution, ptvis::kMinResolution, ptvis::kMaxResolution);
     if (vis->sharpness_log2 > ptvis::kMaxSharpness)
         return fail(PT_ERR_INVALID_ARG, "%s: sharpness_log2 %u (at most %u)", who, vis->sharpness_log2, ptvis::kMaxSharpness);
     if (!(vis->max_distance > 0.0f) || !std::isfinite(vis->max_distance)) return fail(PT_ERR_INVALID_ARG, "%s: max_distance must be finite and > 0", who);
-    return moments_too ? check_plane(who, "the moments plane", moments, 8) : PT_OK;
+    return check_plane(who, "the moments plane", moments, device ? 8 : 4);
 }
 
 // The distances of n_rows x R probe rays into d_out, everything checked: per chunk of whole rows the source's feature-ray form
@@ -65,12 +71,6 @@ int distances_of(PtContext* c, uint32_t n_rows, uint32_t R, const PtRenderParams
 
 namespace {
 
-int check_probe_rays(const char* who, uint32_t n_probes, uint32_t rays_per_probe) {
-    if (n_probes == 0 || n_probes > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: n_probes must be in [1, 65535]", who);
-    if (rays_per_probe == 0 || rays_per_probe > 65535u) return fail(PT_ERR_INVALID_ARG, "%s: rays_per_probe must be in [1, 65535]", who);
-    return PT_OK;
-}
-
 // the distances of the bake's rays from given positions
 struct BakeRows { const float* d_positions3; uint32_t R; };
 ptk::RaySourceF bake_rows(const void* ctx, uint32_t base, uint32_t nb) {
@@ -84,7 +84,7 @@ int distances_impl(PtContext* c, const float* d_positions3, uint32_t n_probes, u
 int check_distances(const char* who, const PtContext* c, const void* positions3, uint32_t n_probes, uint32_t R, const PtRenderParams* prm, const void* out) {
     if (!c || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = check_probe_rays(who, n_probes, R)) || (rc = check_plane(who, "positions3", positions3, 4)) ||
+    if ((rc = check_probe_count(who, n_probes)) || (rc = check_rays_per_probe(who, R)) || (rc = check_plane(who, "positions3", positions3, 4)) ||
         (rc = check_plane(who, "the distances output", out, 4)) || (rc = check_accel(prm->accel)) || (rc = check_scene(c)))
         return rc;
     return PT_OK;
@@ -92,7 +92,7 @@ int check_distances(const char* who, const PtContext* c, const void* positions3,
 void moments_launch(PtContext* c, const float* d_distances, uint32_t n_probes, uint32_t R, const PtProbeVisibility* vis, float* d_moments) {
     ptk::ProbeMomentsArgs a{};
     a.distances = d_distances; a.moments = d_moments; a.n_probes = n_probes; a.rays_per_probe = R;
-    a.resolution = vis->resolution; a.sharpness_log2 = vis->sharpness_log2; a.max_distance = vis->max_distance;
+    a.vis = rule_visibility(vis);
     ptk::launch_probe_moments(a, c->stream);
 }
 
@@ -135,8 +135,8 @@ int pt_probe_moments_device(PtContext* c, const float* d_distances, uint32_t n_p
                             float* d_moments) {
     const char* const who = "pt_probe_moments_device";
     int rc;
-    if ((rc = check_visibility(who, vis, d_moments)) || (rc = check_probe_rays(who, n_probes, rays_per_probe)) ||
-        (rc = check_plane(who, "the distances plane", d_distances, 4)))
+    if ((rc = check_moments_plane(who, vis, d_moments, true)) || (rc = check_probe_count(who, n_probes)) ||
+        (rc = check_rays_per_probe(who, rays_per_probe)) || (rc = check_plane(who, "the distances plane", d_distances, 4)))
         return rc;
     if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
     HIP_TRY(hipSetDevice(c->device));
@@ -148,20 +148,17 @@ int pt_probe_moments_device(PtContext* c, const float* d_distances, uint32_t n_p
 int pt_probe_moments_host(const float* distances, uint32_t n_probes, uint32_t rays_per_probe, const PtProbeVisibility* vis, float* out_moments) {
     const char* const who = "pt_probe_moments_host";
     int rc;
-    if ((rc = check_visibility(who, vis, out_moments, false)) || (rc = check_plane(who, "the moments plane", out_moments, 4)) ||
-        (rc = check_probe_rays(who, n_probes, rays_per_probe)) || (rc = check_plane(who, "the distances plane", distances, 4)))
+    if ((rc = check_moments_plane(who, vis, out_moments, false)) || (rc = check_probe_count(who, n_probes)) ||
+        (rc = check_rays_per_probe(who, rays_per_probe)) || (rc = check_plane(who, "the distances plane", distances, 4)))
         return rc;
-    const uint32_t T = vis->resolution, R = rays_per_probe;
-    std::vector<double> rays(4 * (size_t)R), dirs(3 * (size_t)T * T);
-    for (uint32_t j = 0; j < T; ++j)
-        for (uint32_t i = 0; i < T; ++i) ptvis::oct_decode(ptvis::centre(T, i), ptvis::centre(T, j), &dirs[3 * (size_t)(j * T + i)]);
+    const ptvis::Params v = rule_visibility(vis);
+    const uint32_t R = rays_per_probe;
+    const size_t tt = (size_t)v.resolution * v.resolution;
+    const float identity[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    std::vector<double> rays(4 * (size_t)R);
     for (size_t p = 0; p < n_probes; ++p) {
-        for (uint32_t r = 0; r < R; ++r) ptvis::stage_ray(r, R, distances[p * R + r], vis->max_distance, &rays[4 * (size_t)r]);
-        for (uint32_t t = 0; t < T * T; ++t) {
-            double S[3] = {0.0, 0.0, 0.0};
-            for (uint32_t r = 0; r < R; ++r) ptvis::add_ray(&dirs[3 * (size_t)t], &rays[4 * (size_t)r], vis->sharpness_log2, S);
-            ptvis::finish(S, vis->max_distance, out_moments + 2 * (p * T * T + t));
-        }
+        for (uint32_t r = 0; r < R; ++r) ptupd::stage_ray(r, R, identity, true, true, distances[p * R + r], v.max_distance, &rays[4 * (size_t)r]);
+        ptvis::probe_moments(v, R, rays.data(), out_moments + 2 * tt * p);
     }
     return PT_OK;
 }
@@ -171,13 +168,13 @@ int pt_probe_grid_visibility_device(PtContext* c, const PtProbeGrid* g, uint32_t
     const char* const who = "pt_probe_grid_visibility_device";
     if (!c || !prm) return fail(PT_ERR_INVALID_ARG, "%s: null argument", who);
     int rc;
-    if ((rc = check_grid(who, g)) || (rc = check_visibility(who, vis, d_moments)) || (rc = check_probe_rays(who, 1u, rays_per_probe)) ||
+    if ((rc = check_grid(who, g)) || (rc = check_moments_plane(who, vis, d_moments, true)) || (rc = check_rays_per_probe(who, rays_per_probe)) ||
         (rc = check_accel(prm->accel)) || (rc = check_scene(c)))
         return rc;
     const uint32_t n = pt_probe_grid_count(g);
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = c->pg_pos.ensure(3 * (size_t)n)) || (rc = c->pv_dist.ensure((size_t)n * rays_per_probe))) return rc;
-    ptk::launch_probe_positions(kernel_grid(g), n, c->pg_pos.p, c->stream);
+    ptk::launch_probe_positions(rule_grid(g), n, c->pg_pos.p, c->stream);
     HIP_TRY(hipGetLastError());
     if ((rc = distances_impl(c, c->pg_pos.p, n, rays_per_probe, prm, c->pv_dist.p))) return rc;
     moments_launch(c, c->pv_dist.p, n, rays_per_probe, vis, d_moments);
@@ -190,7 +187,7 @@ int pt_probe_shade_visibility_device(PtContext* c, const PtCamera* cam, const Pt
                                      float* d_out_linear, uint8_t* d_out_rgba) {
     const char* const who = "pt_probe_shade_visibility_device";
     int rc;
-    if ((rc = check_shade(who, cam, g, d_sh27, d_features, d_fallback, sp, d_out_linear, d_out_rgba, 16)) || (rc = check_visibility(who, vis, d_moments)))
+    if ((rc = check_shade(who, cam, g, d_sh27, d_features, d_fallback, sp, d_out_linear, d_out_rgba, 16)) || (rc = check_moments_plane(who, vis, d_moments, true)))
         return rc;
     if (!c) return fail(PT_ERR_INVALID_ARG, "%s: null context", who);
     HIP_TRY(hipSetDevice(c->device));
@@ -201,9 +198,7 @@ int pt_probe_shade_visibility_host(const PtCamera* cam, const PtProbeGrid* g, co
                                    const float* features, const float* fallback, const PtProbeShade* sp, float* out_linear, uint8_t* out_rgba) {
     const char* const who = "pt_probe_shade_visibility_host";
     int rc;
-    if ((rc = check_shade(who, cam, g, sh27, features, fallback, sp, out_linear, out_rgba, 4)) || (rc = check_visibility(who, vis, moments, false)) ||
-        (rc = check_plane(who, "the moments plane", moments, 4)))
-        return rc;
+    if ((rc = check_shade(who, cam, g, sh27, features, fallback, sp, out_linear, out_rgba, 4)) || (rc = check_moments_plane(who, vis, moments, false))) return rc;
     shade_host(cam, g, sh27, features, fallback, sp, out_linear, out_rgba, Maps{moments, vis});
     return PT_OK;
 }
@@ -213,7 +208,7 @@ int pt_render_probe_lit_visibility_device(PtContext* c, const PtCamera* cam, con
                                           const PtProbeShade* sp, float* d_out_linear, uint8_t* d_out_rgba) {
     const char* const who = "pt_render_probe_lit_visibility_device";
     int rc;
-    if ((rc = check_probe_lit(who, c, cam, prm, g, d_sh27, d_fallback, sp, d_out_linear, d_out_rgba)) || (rc = check_visibility(who, vis, d_moments))) return rc;
+    if ((rc = check_probe_lit(who, c, cam, prm, g, d_sh27, d_fallback, sp, d_out_linear, d_out_rgba)) || (rc = check_moments_plane(who, vis, d_moments, true))) return rc;
     return probe_lit_impl(c, cam, prm, feature_samples, g, d_sh27, d_fallback, sp, d_out_linear, d_out_rgba, Maps{d_moments, vis});
 }
 
@@ -222,9 +217,7 @@ int pt_render_probe_lit_visibility_host(PtContext* c, const PtCamera* cam, const
                                         const PtProbeShade* sp, float* out_linear, uint8_t* out_rgba) {
     const char* const who = "pt_render_probe_lit_visibility_host";
     int rc;
-    if ((rc = check_probe_lit(who, c, cam, prm, g, sh27, fallback, sp, out_linear, out_rgba)) || (rc = check_visibility(who, vis, moments, false)) ||
-        (rc = check_plane(who, "the moments plane", moments, 4)))
-        return rc;
+    if ((rc = check_probe_lit(who, c, cam, prm, g, sh27, fallback, sp, out_linear, out_rgba)) || (rc = check_moments_plane(who, vis, moments, false))) return rc;
     return probe_lit_host(c, cam, prm, feature_samples, g, sh27, fallback, sp, out_linear, out_rgba, Maps{moments, vis});
 }
 

@@ -20,12 +20,15 @@
 //
 // Moments of one probe from its R distances t[r] (float; pt_probe_distances_*: the first hit's t, +inf for a miss) with the
 // parameters (T, k = sharpness_log2 in [0, 8], max_distance finite and > 0):
-//   d_r = ptbake::probe_dir<Exact>(r, R), widened: the directions k_probe_sh uses, whatever arithmetic traced the rays
+//   d_r = ptbake::probe_dir<Exact>(r, R), widened: the directions k_probe_sh uses, whatever arithmetic traced the rays.  (d_r, dist_r)
+//   is staged as four doubles by ptupd::stage_ray (pt_probe_update.h) under the identity: the updates stage their rotated rays with it
 //   dist_r = t[r] when 0 < t[r] <= max_distance, else max_distance (a miss, +inf, NaN, 0 and negative values)
 //   per texel with n = oct_decode(centre):  c = dot(n, d_r);  w = max(c, 0) = c > 0 ? c : 0, then w = w w, k times
 //   S0 = S0 + w,  S1 = S1 + w dist_r,  S2 = S2 + w (dist_r dist_r),  from 0.0 with r ASCENDING (no split order: the kernel's time is
 //   not in the sums, docs/EXPERIMENTS.md "Irradiance volume: visibility")
 //   texel = ((float)(S1 / S0), (float)(S2 / S0)), or (max_distance, (float)(max_distance max_distance) in f64) when S0 == 0.
+//   On the CPU a probe's map from its staged rays is probe_moments below, for pt_probe_moments_host and the host update; on the device
+//   the pass over the staged rays is probe_staged_rays (pt_film_probe_vis.h), for k_probe_moments and k_probe_update.
 //
 // Shading: steps 1-3, 5 and 6 of pt_probe_grid.h as they are.  Step 4 of corner j, whatever PtProbeShade.weight says:
 //   tri = (wx wy) wz and F = h h + 0.2 as kFacing forms them (its v = pos_j - P from the UNBIASED point).  Then with Q = P +
@@ -36,18 +39,11 @@
 //   So den > 0 always (tri sums to 1, g > 0), and when every corner has m1 >= r the pixel is PT_PROBE_WEIGHT_FACING's bit for
 //   bit: vis = 1, g = F >= 0.2, w_j = tri F.
 #pragma once
-#include "pt_probe_grid.h"
+#include "pt_probe_grid.h"        // (pt_probe_params.h: ptvis::Params)
 
 namespace ptvis {
 
 constexpr uint32_t kMinResolution = 2u, kMaxResolution = 16u, kMaxSharpness = 8u;
-
-struct Params {               // PtProbeVisibility's layout (pt_probe_grid.cpp asserts it)
-    uint32_t resolution;
-    uint32_t sharpness_log2;
-    float max_distance;
-    uint32_t reserved;
-};
 
 PT_AD_HD bool valid(const Params& p) {
     return p.resolution >= kMinResolution && p.resolution <= kMaxResolution && p.sharpness_log2 <= kMaxSharpness && p.max_distance > 0.0f &&
@@ -136,12 +132,16 @@ PT_AD_HD void finish(const double S[3], float max_distance, float out[2]) {
     out[0] = none ? max_distance : (float)(S[1] / S[0]);
     out[1] = none ? (float)(m * m) : (float)(S[2] / S[0]);
 }
-// ray r of R as add_ray takes it
-PT_AD_HD void stage_ray(uint32_t r, uint32_t R, float t, float max_distance, double ray[4]) {
-    float d[3];
-    ptbake::probe_dir<ptbake::Exact>(r, R, d);
-    ray[0] = (double)d[0]; ray[1] = (double)d[1]; ray[2] = (double)d[2];
-    ray[3] = clamp_distance(t, max_distance);
+// The moments of one probe on the CPU from its R staged rays (rays4 = R x (d3, dist): ptupd::stage_ray of pt_probe_update.h), in the
+// kernels' order: out = the probe's float[T][T][2]
+inline void probe_moments(const Params& p, uint32_t R, const double* rays4, float* out) {
+    const uint32_t T = p.resolution;
+    for (uint32_t t = 0; t < T * T; ++t) {
+        double n[3], S[3] = {0.0, 0.0, 0.0};
+        oct_decode(centre(T, t % T), centre(T, t / T), n);
+        for (uint32_t r = 0; r < R; ++r) add_ray(n, rays4 + 4 * (size_t)r, p.sharpness_log2, S);
+        finish(S, p.max_distance, out + 2 * (size_t)t);
+    }
 }
 
 // ---- the visibility type of ptgrid::shade_rule
